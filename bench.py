@@ -10,7 +10,7 @@ Workload (config.workload): the 1024 x 1024 DMDA node grid of BASELINE.json's
 configs (2 097 152 rows, 37 699 600 stored non-zeros in A, 4 constraint rows),
 K = [A B^T; B 0], FGMRES(30) with classical Gram-Schmidt and the full Schur
 fieldsplit preconditioner S^ = diag(B diag(A)^-1 B^T): the call the reference
-makes at /root/reference/src/SaddlePointProblem.c:70 with the finished nest.
+makes at src/SaddlePointProblem.c:70 with the finished nest.
 The whole system fits one MI355X; N > 1 row-partitions the SAME system (strong
 scaling) with RCCL all-reduces and halo send/recv on the solver's stream.
 
@@ -22,6 +22,11 @@ solution update).
 
 Only the cpu_baseline leg touches oracle/ (the CPU restatement), as a reported
 baseline on a bounded sample of the same workload.
+
+--dump-outputs DIR writes what the timed solve returned -- the iterate x (float64, the
+whole saddle vector, multipliers last) and its residual history -- as DIR/<name>.npy.
+The inputs depend on the arguments alone, so two builds can be compared output for
+output.  Beyond DUMP_MAX_BYTES, x is a fixed seeded sample of its entries.
 """
 import argparse
 import json
@@ -36,6 +41,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0          # measured float4 copy ceiling, same guide
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SEED = 20240607          # the sample of x kept when the whole vector exceeds the bound
 METRIC = "FGMRES iterations/sec + achieved HBM GB/s on A-block SpMV, 1/2/4/8 MI355X"
 
 
@@ -113,6 +120,25 @@ def solve_bytes(n, nnz, nnzB, restart, steps, planes, m, spmv_matrix_bytes=None,
     return total
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy (float64), all of them within DUMP_MAX_BYTES.  An array that does
+    not fit keeps a sample of its entries: the same indices, in ascending order, for the same length."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES - sum(a.nbytes for k, a in arrays.items() if k != "x") - 4096 * len(arrays)   # (.npy headers)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64)
+        note = "whole"
+        if name == "x" and a.nbytes > budget:
+            keep = budget // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+            note = f"{keep} of {arrays[name].size} entries, sampled with seed {DUMP_SEED}"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "content": note}
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,6 +168,8 @@ def main():
                     help="opts.iteration_form: 0 auto, 1 four launches per iteration, 2 two launches, 3 three launches, 4 BA, "
                          "5 un-normalised three-launch, 6 resident restart-cycle kernel")
     ap.add_argument("--single-reduce", type=int, default=0, help="1: single-reduction Gram-Schmidt (one all-reduce per iteration; see include/spk.h)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed solve's outputs (x, residual history) as DIR/<name>.npy")
     ap.add_argument("--watchdog", type=float, default=900.0, help="seconds after which a run that is still going says WHERE it "
                                                                   "is stuck (rank, phase) on stderr and exits 4; 0: off")
     args = ap.parse_args()
@@ -320,6 +348,12 @@ def main():
     xh = ctx.vec_get(x_dev, len(rhs))
     yh = ctx.mult(xh)
     nl_ = len(f)
+    x_out = xh
+    if args.dump_outputs and dist is not None and world > 1:
+        # the whole iterate on rank 0: every rank's own rows in rank order, then the (replicated) multipliers
+        parts = [None] * world
+        dist.all_gather_object(parts, xh[:nl_])
+        x_out = np.concatenate(parts + [xh[nl_:]])
     r2 = float(np.sum((rhs[:nl_] - yh[:nl_]) ** 2)) + (float(np.sum((rhs[nl_:] - yh[nl_:]) ** 2)) if rank == 0 else 0.0)
     if dist is not None:
         import torch
@@ -572,6 +606,8 @@ def main():
                                "label": "PETSc-equivalent CPU restatement (PETSc not installable offline)"}
         out["speedup_vs_cpu"] = (io["its"] / el_same) / out["cpu_baseline"]["value"]
         out["speedup_vs_cpu_note"] = f"GPU and CPU both over iterations 0..{io['its'] - 1} of a restart cycle"
+    if args.dump_outputs:
+        out["outputs_dumped"] = dump_outputs(args.dump_outputs, {"x": x_out, "residual_history": info["history"]})
     print(json.dumps(out))
     ctx.vec_destroy(b_dev); ctx.vec_destroy(x_dev); ctx.close()
     if dist is not None:

@@ -1,5 +1,5 @@
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import saddle_point_petsc_amd as S
 import oracle as O
 M=int(sys.argv[1]) if len(sys.argv)>1 else 1024
