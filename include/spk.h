@@ -111,7 +111,7 @@ typedef struct spk_opts {
                                reductions otherwise). */
     int32_t iteration_form; /* how the head-kernel paths launch one classical Gram-Schmidt iteration (same
                                algorithm, two reductions, norms taken from w' itself):
-                               SPK_ITER_AUTO (0): SPK_ITER_UNNORM wherever it applies (classical Gram-Schmidt
+                               SPK_ITER_AUTO (0): 6, 7 or SPK_ITER_UNNORM wherever it applies (classical Gram-Schmidt
                                without refinement, two reductions), else four launches;
                                SPK_ITER_UNNORM (5): three launches on an UN-NORMALISED basis -- VecMDot (raw inner
                                products and B D w~), VecMAXPY + norm + the next PCApply (+ B^T part), plain MatMult
@@ -134,12 +134,18 @@ typedef struct spk_opts {
                                all of them in one order and runs the Hessenberg / Givens / convergence scalars itself),
                                VecMAXPY touches no memory, the product gathers z~ from the neighbours' write-through
                                stores.  Same algorithm and basis as 5.  SPK_RESIDENT=0 keeps AUTO on 5;
+                               SPK_ITER_GS_FUSED (7; what AUTO takes on one rank with >= 1 M local rows where form 6
+                               does not fit): form 5 with VecMDot and the VecMAXPY + PCApply pass in ONE launch (every
+                               iteration of a cycle but its last), the MDot totals handed over inside the launch: the
+                               first MAXPY loads are in flight while they are summed.  Same tiles and summation orders
+                               as 5: the same bits.  Needs restart + m <= 41 and every workgroup resident at once;
                                Measured us per iteration, forms 1 / 3 / 5: 1/8 slab of 1024^2 47.9 / 44.7 / 43.3,
                                512^2 71.8 / 67.6 / 66.0, 1024^2 219.7 / 218 / 209.2 (profiles/r02*). */
     int32_t reserved;
 } spk_opts;
 enum { SPK_ITER_AUTO = 0, SPK_ITER_FOUR_LAUNCH = 1, SPK_ITER_TWO_LAUNCH = 2, SPK_ITER_THREE_LAUNCH = 3, SPK_ITER_BA = 4,
-       SPK_ITER_UNNORM = 5, SPK_ITER_RESIDENT = 6, SPK_ITER_LAST = 6 };
+       SPK_ITER_UNNORM = 5, SPK_ITER_RESIDENT = 6, SPK_ITER_GS_FUSED = 7,
+       SPK_ITER_LAST = 7 };
 
 typedef struct spk_result {
     int32_t its;            /* KSPGetIterationNumber   */

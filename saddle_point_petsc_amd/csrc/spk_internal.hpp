@@ -661,6 +661,20 @@ struct IterB {
     int loc;
     int defer_fin;       // publish the partials of ||w'||^2 and leave: the rider of the next product launch reduces them
 };
+// Form 7: VecMDot and kernel B in one launch (gs_fused_kernel).  b as for iter_maxpy_uhead (dots unused, defer_fin set,
+// one rank); MDot's operands below.  Returns the number of partial rows of ||w'||^2 (GivensRider::fin_n).
+struct GsArgs {
+    const double *V2;    // planes of B D (parity-interleaved when split)
+    int cnt, split;      // cnt = nv + m values (<= 40), w.w after them
+    int64_t n2, n_dot;   // MDot's length in double2 (the multiplier entries included), entries that count
+    double *partials;    // MDot's partial rows (column offset 1 of the context's partials)
+    double *out;         // the reduced [h, q, w.w] (as mdot's Finish::out)
+    double *tot, *tot_next;   // the armed totals line of this launch, the line it arms for the next one
+    FinErr fe;
+};
+int gs_fused(IterB b, GsArgs g, hipStream_t s);
+int gs_fused_occupancy(int ng, int m);   // workgroups of the fused kernel that fit one CU
+int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
 // dots = false: the SpMV / normalisation part alone (three-launch form; one tile per workgroup: slots = tiles_per_xcd)
 void iter_spmv_mdot(const IterA &a, hipStream_t s, bool dots = true);
 // BA: w' = s_w w~ - V~ (h .* sc) with ||w'||^2, z~ = M^-1 w', then -- behind neighbour flags instead of a kernel
@@ -856,6 +870,10 @@ struct spk_ctx {
     spk::DevBuf<double> res_P;       // resident cycle kernel: all-to-all buffer of the inner products
     int num_cus = 0;                 // compute units of the device (grid of the resident cycle kernel)
     uint32_t ba_seq = 0;
+    spk::DevBuf<double> gs_tot;      // form 7: two armed lines of MDot totals (the launch reads one, arms the other)
+    uint32_t gs_seq = 0;
+    int gs_occ[3] = {-1, -1, -1};    // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes), -1 unknown
+    bool gs_fused_fits(int64_t nl, int m);   // fat vectors and every workgroup of the fused launch resident at once
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist
     spk::DevBuf<spk::KrylovState> kst;
     spk::k::KrylovArrays ka{};

@@ -284,8 +284,11 @@ void iter_spmv_mdot(const IterA &a0, hipStream_t s, bool dots)
     else hipLaunchKernelGGL((iter_spmv_mdot_kernel<16, 2>), grid, block, 0, s, a);
 }
 
-template <int T, int G, int U, int MP>
-__global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
+// The body of kernel B (iter_maxpy_uhead_kernel, gs_fused_kernel).  scalar_wg: the workgroup that also writes the
+// multiplier entries of w', z~, c~, tb, the Hessenberg column and the multiplier entries' share of ||w'||^2 (a workgroup
+// of its own in kernel B, one of the streaming ones in the fused launch); dots(i): the reduced [h, q] value i.
+template <int T, int G, int U, int MP, class Dots>
+__device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg, Dots dots)
 {
     const int32_t dn = __builtin_nontemporal_load(b.done);  // looked at behind the first loads (see mdot_ws16_kernel)
     __shared__ double hs[kMaxNv], lam[kMaxNv * 8], ys[8], wraws[8], tus[8];
@@ -293,7 +296,6 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
     const int nv = b.nv, m = b.m;
     constexpr int NP = MP > 0 ? MP : 1;
     const int gmain = b.gmain;
-    const int nhalo = b.sr.peer ? (2 * b.sr.nrecv + T - 1) / T : 0;
     const bool is_main = (int)blockIdx.x < gmain;
     const int64_t n2 = b.nl / 2;
     const int bid = blockIdx.x;
@@ -353,11 +355,11 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
     const double s_w = b.sc ? b.sc[nv - 1] : 1.0;   // w = s_w w~ (un-normalised basis); 1 otherwise
     if (threadIdx.x < kWave) {
         const int i = threadIdx.x;
-        hi_pre = i < nv ? b.dots[i] : 0.0;
+        hi_pre = i < nv ? dots(i) : 0.0;
         if (b.sc) sci = i < nv ? b.sc[i] : 0.0;
 #pragma unroll
         for (int r = 0; r < 8; ++r) tbv_pre[r] = (r < m && i < nv) ? b.tb[i * 8 + r] : 0.0;
-        qv_pre = (i < m) ? b.dots[nv + i] : 0.0;
+        qv_pre = (i < m) ? dots(nv + i) : 0.0;
     }
     if (dn) return;
     if (threadIdx.x < kWave) {  // lane i owns basis vector i (nv <= 63)
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
         for (int r = 0; r < 8; ++r) tbv[r] = tbv_pre[r] * (b.sc ? sci : 1.0);
         const double qv = qv_pre * s_w;
         if (i < nv) hs[i] = ci;
-        if (b.sc && (int)blockIdx.x == gmain + nhalo && i < nv) b.hbuf[i] = hi;  // the Hessenberg column (reducer only)
+        if (b.sc && (int)blockIdx.x == scalar_wg && i < nv) b.hbuf[i] = hi;  // the Hessenberg column (reducer only)
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             if (r < m) {  // uniform
@@ -406,7 +408,7 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
         }
     }
 
-    if ((int)blockIdx.x == gmain + nhalo) {
+    if ((int)blockIdx.x == scalar_wg) {
         // ---- the scalar / reducing workgroup: multiplier entries of w', z~, c~; B D w' for the recurrence
         if ((int)threadIdx.x < m) {
             const int r = threadIdx.x;
@@ -428,14 +430,15 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
             // (scale factor, Givens step), so the rider also REDUCES the partials (and all-reduces the sum) beside the
             // row tiles: this launch ends with its last streaming workgroup -- no publish -> re-read tail
             if (threadIdx.x == 0) publish(b.partials + (size_t)gmain * kPartialLd, lam2);
+            if (!is_main) return;   // (the fused launch: this workgroup streams its tiles too)
+        } else {
+            final_reduce(b.partials, gmain, kPartialLd, 1, red, FinErr{b.err, b.fin_ticks});
+            if (threadIdx.x == 0) red[0] = red[0] + lam2;
+            __syncthreads();
+            if (b.ar.P) peer_allreduce_block(b.ar, red, 1, b.out);
+            else if (threadIdx.x == 0) b.out[0] = red[0];
             return;
         }
-        final_reduce(b.partials, gmain, kPartialLd, 1, red, FinErr{b.err, b.fin_ticks});
-        if (threadIdx.x == 0) red[0] = red[0] + lam2;
-        __syncthreads();
-        if (b.ar.P) peer_allreduce_block(b.ar, red, 1, b.out);
-        else if (threadIdx.x == 0) b.out[0] = red[0];
-        return;
     }
     if (!is_main) {  // peer-store halo: unpack this rank's ghost rows (see fused_head_kernel)
         const int64_t g = (int64_t)((int)blockIdx.x - gmain) * T + threadIdx.x;
@@ -598,6 +601,12 @@ __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
         publish(b.partials + (size_t)bx * kPartialLd, tsum);
     }
 }
+template <int T, int G, int U, int MP>
+__global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
+{
+    const int nhalo = b.sr.peer ? (2 * b.sr.nrecv + T - 1) / T : 0;
+    maxpy_uhead_tiles<T, G, U, MP>(b, b.gmain + nhalo, [&](int i) { return b.dots[i]; });
+}
 
 int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial rows its norm is spread over (defer_fin)
 {
@@ -636,6 +645,101 @@ int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial 
 #undef SPK_IB
     return b.gmain;
 }
+
+// ---------------------------------------------------------------------------
+// Form 7 (opts.iteration_form = 7; what AUTO takes on one rank with fat vectors): VecMDot and kernel B in ONE launch.
+// Kernel B needs ~40 reduced scalars from MDot; everything else it reads (basis rows, w~, D^-1, the planes of B D) is known
+// when MDot starts.  On the 256 x 512-thread grid of the fat vector shape every workgroup
+//   1. runs exactly mdot_kernel's tiles and publishes its partials (columns 1.. of the partial rows: column 0 carries the
+//      ||w'||^2 partials of step 3, which the rider of the next product launch reduces);
+//   2. the last workgroup reduces them as mdot_kernel does and publishes the totals, write-through, into a line armed
+//      with the sentinel (a value is its own flag; the launch arms the OTHER of two lines for the next launch);
+//   3. every workgroup requests its first tile of kernel B, then waits for the totals it needs, and runs kernel B's body;
+//      kernel B's scalar workgroup duties go to workgroup grid - 2 (one that streams the fewest MDot tiles).
+// The tile mapping and every summation order are those of the two launches: the results are the same bits.  The waits
+// need every workgroup resident at once (gs_fused_occupancy) and are bounded: a wait that gives up raises the context's
+// execution-error word.
+// ---------------------------------------------------------------------------
+struct TotalsWait {   // kernel B's dots(i): spins (bounded) while the totals line still holds the sentinel
+    const double *tot;
+    FinErr fe;
+    __device__ double operator()(int i) const
+    {
+        double v = peek(tot + i);
+        if (is_sentinel(v)) {
+            const unsigned long long t0 = wall_clock64();
+            do {
+                __builtin_amdgcn_s_sleep(1);
+                v = peek(tot + i);
+            } while (is_sentinel(v) && wall_clock64() - t0 < (unsigned long long)fe.ticks &&
+                     !(fe.err && __hip_atomic_load(fe.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+            if (is_sentinel(v) && fe.err) __hip_atomic_store(fe.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return v;
+    }
+};
+
+constexpr int kGsT = 512, kGsU = 4, kGsG = 4;   // vec_shape's fat shape (mdot_kernel<NG, 512, 4, true, 4>, kernel B <512, 4, 4, MP>)
+
+template <int NG, int MP>
+__global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
+{
+    constexpr int NA = NG * 8 + 1, W = kGsT / kWave;
+    __shared__ double lds[(W * NA > kGsT) ? W * NA : kGsT];
+    if (blockIdx.x == 0 && threadIdx.x < kWave) publish(g.tot_next + threadIdx.x, __longlong_as_double((long long)kSentinelBits));
+    if (*b.done) return;
+    mdot_tiles<NG, kGsT, kGsG, true, kGsU>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1, g.split, lds);
+    if (arrive_last(gridDim.x)) {
+        const int k = g.cnt + 1;
+        final_reduce(g.partials, gridDim.x, kPartialLd, k, lds, g.fe);
+        if ((int)threadIdx.x < k) {
+            g.out[threadIdx.x] = lds[threadIdx.x];
+            publish(g.tot + threadIdx.x, lds[threadIdx.x]);
+        }
+    }
+    maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe});
+}
+
+#define SPK_GS_SWITCH(NGV, MPV, CASE)                                                        \
+    switch ((NGV) * 10 + (MPV)) {                                                           \
+    case 10: CASE(1, 0); case 20: CASE(2, 0); case 30: CASE(3, 0); case 40: CASE(4, 0); case 50: CASE(5, 0); \
+    case 14: CASE(1, 4); case 24: CASE(2, 4); case 34: CASE(3, 4); case 44: CASE(4, 4); case 54: CASE(5, 4); \
+    case 18: CASE(1, 8); case 28: CASE(2, 8); case 38: CASE(3, 8); case 48: CASE(4, 8); default: CASE(5, 8); \
+    }
+
+int gs_fused_occupancy(int ng, int m)
+{
+    const int mp = m == 0 ? 0 : (m <= 4 ? 4 : 8);
+    int nb = 0;
+#define SPK_GS_OCC(NG, MP) SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP>, kGsT, 0)); break
+    SPK_GS_SWITCH(ng, mp, SPK_GS_OCC)
+#undef SPK_GS_OCC
+    return nb;
+}
+
+int64_t gs_fused_grid(int64_t nl)
+{
+    const int64_t n2 = nl / 2;
+    if (n2 < (int64_t)kVecMaxBlocks * 2048) return 0;   // not the fat vector shape
+    return kVecMaxBlocks;                               // >= 256 tiles of 2048 double2: both kernels' grids
+}
+
+int gs_fused(IterB b, GsArgs g, hipStream_t s)
+{
+    const int64_t grid = gs_fused_grid(b.nl);
+    const VecShape vs = vec_shape(g.n2);
+    if (!grid || vs.T != kGsT || vs.U != kGsU || vs.grid != grid) fail(SPK_ERR_STATE, "gs_fused: not the fat vector shape");
+    if (!b.defer_fin || b.ar.P || b.sr.n || b.sr.peer) fail(SPK_ERR_STATE, "gs_fused: one rank, norm reduced by the rider only");
+    if (g.cnt > 40 || b.nv + b.m > kMaxNv - 1) fail(SPK_ERR_ARG, "gs_fused: %d values exceed one reduction", g.cnt);
+    b.gmain = (int)grid;
+    const int ng = (g.cnt + 7) / 8 > 0 ? (g.cnt + 7) / 8 : 1;
+    const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+#define SPK_GS_LAUNCH(NG, MP) hipLaunchKernelGGL((gs_fused_kernel<NG, MP>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); break
+    SPK_GS_SWITCH(ng, mp, SPK_GS_LAUNCH)
+#undef SPK_GS_LAUNCH
+    return b.gmain;
+}
+#undef SPK_GS_SWITCH
 
 // ---------------------------------------------------------------------------
 // "BA": VecMAXPY (+ VecNorm, + the next PCApply) and the NEXT MatMult in ONE launch (opts.iteration_form = 4; single

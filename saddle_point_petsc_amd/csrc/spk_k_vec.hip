@@ -145,84 +145,9 @@ __global__ __launch_bounds__(T) void mdot_kernel(const double *__restrict__ V, i
                                                  const int32_t *__restrict__ done)
 {
     if (done && *done) return;
-    constexpr int NA = NG * 8 + 1, W = T / kWave, TILE2 = T * U;
+    constexpr int NA = NG * 8 + 1, W = T / kWave;
     __shared__ double lds[(W * NA > T) ? W * NA : T];
-    double acc[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) acc[i] = 0.0;
-
-    for (int64_t tile = blockIdx.x; tile * TILE2 < n2; tile += gridDim.x) {
-        double2 wv[U];
-        int64_t idx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            idx[u] = tile * TILE2 + u * T + threadIdx.x;
-            if (idx[u] < n2) {
-                wv[u] = ld2(w, idx[u]);
-                if (2 * idx[u] >= n_dot) wv[u].x = 0.0;
-                if (2 * idx[u] + 1 >= n_dot) wv[u].y = 0.0;
-            } else {
-                wv[u].x = wv[u].y = 0.0;
-                idx[u] = 0;  // safe address, zero weight
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[NA - 1] += wv[u].x * wv[u].x + wv[u].y * wv[u].y;
-#pragma unroll
-        for (int g0 = 0; g0 < NG * 8; g0 += G) {
-            if (g0 < nv) {  // wave-uniform
-                double2 a[G][U];
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    // a slot past nv loads ONE broadcast address (w[0..1], weight 0) instead of a
-                    // vector tile: the group stays branch-free and costs no bandwidth
-                    const bool live = g0 + v < nv;
-                    const int ic = live ? g0 + v : 0;
-                    // vectors nv1.. come from a second slab (the rows of B D in the single-reduction mode);
-                    // split: that slab holds parity-interleaved planes, "vector" j is half j & 1 of plane j / 2
-                    const int j2 = ic - nv1;
-                    const double *Vi = !live ? w : (ic < nv1 ? V + (size_t)ic * ldv : V2 + (size_t)(split ? j2 >> 1 : j2) * ldv);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) a[v][u] = ld2s<NT>(Vi, live ? idx[u] : 0);
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    const double mk = (g0 + v < nv) ? 1.0 : 0.0;
-                    double d = 0.0;
-                    if (split && g0 + v >= nv1 && g0 + v < nv) {  // wave-uniform
-                        if ((g0 + v - nv1) & 1) {
-#pragma unroll
-                            for (int u = 0; u < U; ++u) d += a[v][u].y * wv[u].y;
-                        } else {
-#pragma unroll
-                            for (int u = 0; u < U; ++u) d += a[v][u].x * wv[u].x;
-                        }
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < U; ++u) d += a[v][u].x * wv[u].x + a[v][u].y * wv[u].y;
-                    }
-                    acc[g0 + v] += mk * d;
-                }
-            }
-        }
-    }
-    // workgroup sums -> partials[block][i]; w.w goes to slot nv
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const double s = wave_sum(acc[i]);
-        if (lane == 0) lds[wave * NA + i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NA) {
-        const int i = threadIdx.x;
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < W; ++j) s += lds[j * NA + i];
-        double *row = partials + (size_t)blockIdx.x * kPartialLd;
-        if (i < nv) publish(row + i, s);
-        else if (i == NA - 1 && with_ww) publish(row + nv, s);
-    }
+    mdot_tiles<NG, T, G, NT, U>(V, ldv, nv, V2, nv1, w, n2, n_dot, partials, with_ww, split, lds);
     if (!arrive_last(gridDim.x)) return;
     const int k = nv + (with_ww ? 1 : 0);
     final_reduce(partials, gridDim.x, kPartialLd, k, lds, fe);

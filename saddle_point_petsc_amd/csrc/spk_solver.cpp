@@ -47,9 +47,23 @@ void spk_ctx::check_device_error()
     SPK_HIP(hipStreamSynchronize(stream));
     SPK_HIP(hipMemset(errw.p, 0, sizeof(int32_t)));
     k::arm_partials(partials.p, partials.n, stream);
+    if (gs_tot.p) k::arm_partials(gs_tot.p, gs_tot.n, stream);
     SPK_HIP(hipStreamSynchronize(stream));
     fail(SPK_ERR_HIP, "a cross-workgroup reduction timed out on the device (a workgroup never published its partial "
                       "sums within %.1f s): execution failure, the result of this call is not valid", fin_ticks / 1e8);
+}
+
+bool spk_ctx::gs_fused_fits(int64_t nl, int m)
+{
+    const int64_t grid = k::gs_fused_grid(nl);
+    if (!grid) return false;
+    const int mi = m == 0 ? 0 : (m <= 4 ? 1 : 2);
+    if (gs_occ[mi] < 0) {   // blocks per CU of the fused kernel at its real block size and LDS: the fewest over its instantiations
+        int occ = 1 << 30;
+        for (int ng = 1; ng <= 5; ++ng) occ = std::min(occ, k::gs_fused_occupancy(ng, m));
+        gs_occ[mi] = occ;
+    }
+    return (int64_t)gs_occ[mi] * num_cus >= grid;
 }
 
 void spk_ctx::ensure_vectors()
@@ -1389,7 +1403,8 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     // with the Givens step and the new scale factor in one extra workgroup (GivensRider).  V~_j = h_{j,j-1} v_j: nothing
     // compounds, no vector is ever scaled in memory.  Either matrix format, any number of ranks, any transport.
     const bool un3 = head && !single && o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER &&
-                     mk + c->m <= k::kMaxNv - 2 && (form == SPK_ITER_UNNORM || form == SPK_ITER_AUTO || form == SPK_ITER_RESIDENT);
+                     mk + c->m <= k::kMaxNv - 2 &&
+                     (form == SPK_ITER_UNNORM || form == SPK_ITER_AUTO || form == SPK_ITER_RESIDENT || form == SPK_ITER_GS_FUSED);
     // RESIDENT: one launch per restart cycle, the basis in registers (spk_k_resident.hip): what AUTO takes where it fits
     static const bool res_env_off = [] { const char *e = getenv("SPK_RESIDENT"); return e && !strcmp(e, "0"); }();
     const int res_planes = !fused ? 0 : (bpk ? m / 2 : m);
@@ -1404,6 +1419,14 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     if (resident) {
         const size_t need = (size_t)k::resident_scratch_doubles(c->num_cus, mk);
         if (c->res_P.n < need) c->res_P.alloc(need);
+    }
+    // GS_FUSED (form 7): MDot and kernel B in one launch (every iteration of a cycle but its last) -- one rank, fat vectors,
+    // every workgroup of the launch resident at once; what AUTO takes there
+    const bool gsf = un3 && !resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
+                     c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m);
+    if (gsf && !c->gs_tot.p) {
+        c->gs_tot.alloc(2 * k::kPartialLd);
+        k::arm_partials(c->gs_tot.p, c->gs_tot.n, s);
     }
     const bool two_ok = head && !single && o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER &&
                         c->spmv_format == 1 && c->Ab.ok && !c->Ab.long_rows && mk + c->m <= k::kMaxNv - 2;
@@ -1426,7 +1449,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     }
     if (two && c->zun.n < (size_t)ld) c->zun.alloc((size_t)ld);
     const int lam_in_dot = c->comm->rank() == 0 ? 1 : 0;
-    c->last_form = resident ? SPK_ITER_RESIDENT : ba ? SPK_ITER_BA : un3 ? SPK_ITER_UNNORM : two ? (three ? SPK_ITER_THREE_LAUNCH : SPK_ITER_TWO_LAUNCH)
+    c->last_form = resident ? SPK_ITER_RESIDENT : gsf ? SPK_ITER_GS_FUSED : ba ? SPK_ITER_BA : un3 ? SPK_ITER_UNNORM : two ? (three ? SPK_ITER_THREE_LAUNCH : SPK_ITER_TWO_LAUNCH)
                    : head ? SPK_ITER_FOUR_LAUNCH : -1;
     c->last_single = single ? 1 : 0;
 
@@ -1544,7 +1567,9 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
                     break;
                 }
                 // raw inner products of the un-normalised basis with w~ (and B D w~); scaled where they are consumed
-                {
+                // (form 7: inside the launch of kernel B, below -- except behind the last iteration of a cycle)
+                const bool gs = gsf && loc + 1 < mk;
+                if (!gs) {
                     const bool one = loc + 1 + m <= 40;
                     const bool spl = bpk && one;
                     const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + (fused ? m : 0), k::kStatArDots) : k::PeerAR{};
@@ -1572,7 +1597,23 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
                     const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
                     if (sr.n > 0) b.sr = sr;
                     b.done = done;
-                    const int fin_n = k::iter_maxpy_uhead(b, s);
+                    int fin_n;
+                    if (gs) {
+                        k::GsArgs g{};
+                        g.V2 = fused ? (bpk ? c->bdpk.p : c->bd.p) : nullptr;
+                        g.cnt = loc + 1 + (fused ? m : 0);
+                        g.split = bpk;
+                        g.n2 = (N + 1) / 2; g.n_dot = n_dot;
+                        g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
+                        g.out = db;
+                        g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
+                        g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
+                        g.fe = k::FinErr{c->errw.p, c->fin_ticks};
+                        fin_n = k::gs_fused(b, g, s);
+                        ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
+                    } else {
+                        fin_n = k::iter_maxpy_uhead(b, s);
+                    }
                     if (!ar2.P && !defer) c->comm->allreduce_sum(nb, 1, s);
                     // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
                     k::GivensRider gr{c->ka, loc, sm2, nb, c->ba_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
