@@ -118,15 +118,9 @@ typedef struct spk_opts {
                                carrying the Givens step in one extra workgroup.  V~_j = h_{j,j-1} v_j is stored with
                                a scale factor beside it and every consumer scales the scalars, never the vectors:
                                no VecScale traffic, either matrix format, any number of ranks;
-                               SPK_ITER_FOUR_LAUNCH (1): head (VecScale + PCApply), SpMV, MDot, MAXPY;
-                               SPK_ITER_TWO_LAUNCH (2): SpMV with MDot in its tile epilogues (VecScale of v and z
-                               folded in), MAXPY with the norm and the next iteration's preconditioner + B^T
-                               product on the un-normalised vector (B D w' by linearity from B D w).  Needs
-                               the 2x2-blocked matrix layout and restart + m <= 62; otherwise four launches;
-                               SPK_ITER_THREE_LAUNCH (3): as 2 with VecMDot (h and B D w) as a launch of its own;
-                               SPK_ITER_BA (4, single rank, small systems): VecMAXPY + norm + next PCApply AND the next
-                               MatMult in one launch behind neighbour flags, un-normalised basis (two launches per
-                               iteration; measured no faster than 5: bandwidth-bound).
+                               SPK_ITER_FOUR_LAUNCH (1): head (VecScale + PCApply), SpMV, MDot, MAXPY; what every
+                               form falls back to where it does not apply (MGS, CGS refinement, single reduction,
+                               restart + m beyond 62);
                                SPK_ITER_RESIDENT (6; what AUTO takes on small single-rank systems: <= 512 block rows per
                                compute unit, restart <= 30, the row-type matrix layout): ONE launch per restart cycle, one
                                workgroup per CU, every thread keeps its entries of the un-normalised basis in registers --
@@ -138,12 +132,15 @@ typedef struct spk_opts {
                                does not fit): form 5 with VecMDot and the VecMAXPY + PCApply pass in ONE launch (every
                                iteration of a cycle but its last), the MDot totals handed over inside the launch: the
                                first MAXPY loads are in flight while they are summed.  Same tiles and summation orders
-                               as 5: the same bits.  Needs restart + m <= 41 and every workgroup resident at once;
-                               Measured us per iteration, forms 1 / 3 / 5: 1/8 slab of 1024^2 47.9 / 44.7 / 43.3,
-                               512^2 71.8 / 67.6 / 66.0, 1024^2 219.7 / 218 / 209.2 (profiles/r02*). */
+                               as 5: the same bits.  Needs restart + m <= 41 and every workgroup resident at once.
+                               SPK_ITER_TWO_LAUNCH, SPK_ITER_THREE_LAUNCH, SPK_ITER_BA (2, 3, 4): retired aliases of
+                               5 (same algorithm; spk_get_iteration_form reports what ran).
+                               Measured us per iteration, forms 1 / 5: 1/8 slab of 1024^2 47.9 / 43.3,
+                               512^2 71.8 / 66.0, 1024^2 219.7 / 209.2. */
     int32_t reserved;
 } spk_opts;
-enum { SPK_ITER_AUTO = 0, SPK_ITER_FOUR_LAUNCH = 1, SPK_ITER_TWO_LAUNCH = 2, SPK_ITER_THREE_LAUNCH = 3, SPK_ITER_BA = 4,
+enum { SPK_ITER_AUTO = 0, SPK_ITER_FOUR_LAUNCH = 1,
+       SPK_ITER_TWO_LAUNCH = 2, SPK_ITER_THREE_LAUNCH = 3, SPK_ITER_BA = 4,   /* retired: run as SPK_ITER_UNNORM */
        SPK_ITER_UNNORM = 5, SPK_ITER_RESIDENT = 6, SPK_ITER_GS_FUSED = 7,
        SPK_ITER_LAST = 7 };
 

@@ -693,8 +693,9 @@ public:
             if (hipMemcpy(w, err_.p, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
             const char *where = w[1] == 1 ? "all-reduce after MDot" : w[1] == 2 ? "all-reduce after MAXPY" : w[1] == 3 ? "stand-alone all-reduce"
                               : w[1] == 16 ? "halo rows (head kernel)" : w[1] == 17 ? "halo rows (MAXPY-head kernel)"
-                              : w[1] == 18 ? "halo rows (two-launch kernel B)" : w[1] == 19 ? "halo exchange kernel"
-                              : w[1] == 20 ? "bulk halo exchange kernel" : "unknown wait";
+                              : w[1] == 18 ? "halo rows (kernel B: MAXPY + PCApply)" : w[1] == 19 ? "halo exchange kernel"
+                              : w[1] == 20 ? "bulk halo exchange kernel" : w[1] == 21 ? "halo rows (resident cycle kernel)"
+                              : "unknown wait";
             fail(SPK_ERR_COMM, "peer-store collective timed out after %u ms waiting for another rank (rank %d, first in: %s, sequence %d; "
                                "all-reduces issued %u, halo exchanges issued %u)", timeout_ms_, me_, where, w[2], ar_seq_, halo_seq_);
         }

@@ -210,8 +210,8 @@ __device__ __forceinline__ bool granule_wait(const unsigned long long *p, uint32
 }
 // Raises the sticky error word of the peer-store backend and notes WHICH wait gave up (first one wins):
 // err[1] = where (1..3: all-reduce after MDot / after MAXPY / stand-alone; 16: halo rows in a head kernel,
-// 17: in the MAXPY-head kernel, 18: in kernel B of the two-launch iteration, 19: granule exchange kernel,
-// 20: bulk exchange kernel), err[2] = sequence number waited for.
+// 17: in the MAXPY-head kernel, 18: in kernel B (MAXPY + PCApply, forms 5 and 7), 19: granule exchange kernel,
+// 20: bulk exchange kernel, 21: in the resident cycle kernel), err[2] = sequence number waited for.
 __device__ __forceinline__ void raise_comm_error(int32_t *err, int where, uint32_t seq)
 {
     if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
@@ -277,10 +277,6 @@ __device__ __forceinline__ int converged_default(double rnorm, const KrylovState
 // loads), lane 0 runs the dependent chain out of LDS and writes the column back once.
 // Called from the stand-alone kernel (generic path) and from workgroup 0 of the fused
 // iteration-head kernel, where it overlaps with that kernel's streaming.
-// gate != nullptr (two words in LDS, zeroed by the caller): the words that GATE the kernels of an
-// iteration (done, skip_iter) are not stored here but handed back as gate[0], gate[1]; the caller
-// stores them once no workgroup of ITS launch can still be about to read them (kernel A of the
-// two-launch iteration: its workgroups must all take the same branch, they feed one reduction).
 // CAP: capacity of the LDS staging (restart + 2); the fused kernels carry the small instance, restart lengths beyond
 // kMaxNv - 2 take the stand-alone kernel with the large one (krylov_givens)
 // lds: 4 * cap + 4 doubles of LDS scratch (the caller's own staging where it has any: a rider workgroup of a product
@@ -309,8 +305,7 @@ __device__ __forceinline__ GivensPre givens_prefetch(const KrylovArrays &ka, int
     return p;
 }
 template <bool LEAN = false>
-__device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2, int *gate,
-                                        double *lds, int cap, const GivensPre *pre = nullptr)
+__device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2, double *lds, int cap, const GivensPre *pre = nullptr)
 {
     double *Hc = lds, *Hr = lds + cap, *ccs = lds + 2 * cap, *sss = lds + 3 * cap, *sc = lds + 4 * cap;
     KrylovState *st = ka.st;
@@ -341,8 +336,7 @@ __device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const d
     if (isnan(tt) || isinf(tt)) {  // KSPCheckNorm: KSP_DIVERGED_NANORINF
         st->rnorm = tt;
         st->reason = SPK_DIVERGED_NANORINF;
-        if (gate) gate[0] = gate[1] = 1;
-        else st->done = 1, st->skip_iter = 1;
+        st->done = 1, st->skip_iter = 1;
         return;
     }
     // happy breakdown test
@@ -379,8 +373,7 @@ __device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const d
         const double d = sqrt(h0 * h0 + h1 * h1);
         if (d == 0.0) {
             st->reason = SPK_DIVERGED_NULL;
-            if (gate) gate[0] = gate[1] = 1;
-            else st->done = 1, st->skip_iter = 1;
+            st->done = 1, st->skip_iter = 1;
             return;
         }
         const double c = h0 / d, sn = h1 / d;
@@ -410,26 +403,24 @@ __device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const d
     if (reason > 0 && ka.tentative) {
         // single-reduction mode: ||w'|| came out of a difference that can sit in rounding noise, so the
         // recurrence is trusted to END THE CYCLE only; the restart's true residual decides (krylov_cycle_begin)
-        if (gate) gate[1] = 1;
-        else st->skip_iter = 1;
+        st->skip_iter = 1;
         return;
     }
     st->reason = reason;
     if (reason) {
-        if (gate) gate[0] = gate[1] = 1;
-        else st->done = 1, st->skip_iter = 1;
+        st->done = 1, st->skip_iter = 1;
     }
 }
 
 template <int CAP>
-__device__ void givens_block_t(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2, int *gate)
+__device__ void givens_block_t(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2)
 {
     __shared__ double lds[4 * CAP + 4];
-    givens_block_lds<false>(ka, loc, dots, nrm2, gate, lds, CAP);
+    givens_block_lds<false>(ka, loc, dots, nrm2, lds, CAP);
 }
-__device__ inline void givens_block(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2, int *gate = nullptr)
+__device__ inline void givens_block(const KrylovArrays &ka, int loc, const double *dots, const double *nrm2)
 {
-    givens_block_t<kMaxNv + 2>(ka, loc, dots, nrm2, gate);
+    givens_block_t<kMaxNv + 2>(ka, loc, dots, nrm2);
 }
 
 __device__ __forceinline__ double inv_norm(double nrm2)  // the VecScale guard of the head kernels
@@ -463,7 +454,7 @@ __device__ __forceinline__ void givens_rider(const GivensRider &gr, double *lds)
     // un-normalised basis: the scale factor of the vector the MAXPY launch just wrote (its norm is all-reduced by now)
     // (nothing compounds: V~_j = w' of the product of the NORMALISED v_{j-1}, so ||V~_j|| = h_{j,j-1} <= ||K M^-1||)
     if (gr.sc && threadIdx.x == 0) gr.sc[gr.loc + 1] = inv_norm(*gr.nrm2);
-    givens_block_lds<true>(gr.ka, gr.loc, gr.h, gr.nrm2, nullptr, lds + kThreads, kMaxNv + 2, &pre);
+    givens_block_lds<true>(gr.ka, gr.loc, gr.h, gr.nrm2, lds + kThreads, kMaxNv + 2, &pre);
 }
 
 void givens_rider_alone(const GivensRider &gr, const int32_t *done, hipStream_t s);  // spk_k_krylov.hip

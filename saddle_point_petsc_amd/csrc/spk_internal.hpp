@@ -109,15 +109,8 @@ struct BcsrDev {
     DevBuf<double> vtop, vbot;  // (a00,a01) and (a10,a11) per block
     DevBuf<float> vtop32, vbot32;  // the same in single precision, for the FP32 inner sweeps (spk_pc_setup with sweeps)
     DevBuf<int32_t> tile_brow;
-    DevBuf<int32_t> tile_desc;  // per tile {first block row, end block row, first block, end block} (one load instead of a chain)
     int32_t ntiles = 0;
     bool ok = false;
-    bool long_rows = false;  // a block row longer than one tile exists (the two-launch iteration does not take those)
-    // "BA" iteration kernel (MAXPY + next SpMV in one launch, neighbour flags): workgroup rho (row order) owns
-    // ba_tb consecutive tiles; ba_nbr[2 rho], [2 rho + 1] = first / last workgroup whose rows its columns touch
-    bool ba_ok = false;
-    int32_t ba_slots = 0, ba_tb = 0, ba_chunk = 0;
-    DevBuf<int32_t> ba_nbr, ba_wt;   // ba_wt[2 rho], [2 rho + 1] = its tiles [t0, t1)
 };
 
 // 3x3-blocked copy (dof-3 grids): one block column index per nine values; plane k (stride ldp) = entry (k / 3, k % 3) of
@@ -588,45 +581,7 @@ struct GivensRider {
     FinErr fe;
     PeerAR ar;
 };
-// ---- two-launch iteration (spk_k_iter.hip, "Two-launch iteration") ----
-// kernel A: w = s (A z~ + c~), v and z normalised on the way, h = V^T w and q = B D w from the tile epilogues
-struct IterA {
-    // 2x2-blocked matrix and its tiling
-    const int32_t *browptr, *bcol;
-    const double *vtop, *vbot;
-    const int32_t *tile_brow;
-    const int4 *tdesc;
-    int ntiles, tiles_per_xcd, slots;  // slots: workgroups per XCD (iter_slots)
-    OffDiag od;
-    // vectors
-    const double *zsrc;  // gathered: z~ (un-normalised, from kernel B) or Z_0 (first iteration of a cycle)
-    double *zdst;        // Z_loc = s z~ (nrm2 != nullptr)
-    double *vcur;        // V_loc: normalised in place (nrm2 != nullptr)
-    double *w;           // V_{loc+1}: in c~ when acc, out w
-    int acc;
-    const double *nrm2;  // ||w'||^2 of the previous iteration: s = 1/sqrt(nrm2[0]); nullptr: s = 1, operands normalised
-    const double *V;     // basis V_0 .. V_{nv-1} (V_{nv-1} = vcur)
-    int64_t ldv;
-    int nv;
-    const double *bd;    // B D: m dense rows or m/2 parity-interleaved planes (nullptr with m = 0)
-    int64_t ldb;
-    int m, packed;
-    int64_t nl;
-    int lam_in_dot;      // this rank counts the m multiplier entries in inner products (rank 0)
-    double *tb;          // B D v_i per basis vector, (restart+2) x 8
-    double *wl_out;      // side copy of the multiplier entries of w for kernel B
-    // finish: [h_0..h_{nv-1}, q_0..q_{m-1}]
-    double *partials, *out;
-    PeerAR ar;
-    int32_t *err;
-    uint32_t fin_ticks;
-    // Givens step of the previous iteration (loc_prev < 0: none)
-    KrylovArrays ka;
-    int loc_prev;
-    const double *dots_prev, *nrm_prev;
-    const int32_t *done;
-};
-// kernel B: w' = w - V h, ||w'||^2, and the next iteration's PC / B^T product on the un-normalised w'
+// kernel B (forms 5 and 7, spk_k_iter.hip): w' = s_w w~ - V~ (h .* sc), ||w'||^2, and the next iteration's PC / B^T product
 struct IterB {
     const double *V;
     int64_t ldv;
@@ -651,10 +606,10 @@ struct IterB {
     SendRanges sr;
     int gmain;           // set by the launcher
     const int32_t *done;
-    // un-normalised basis (opts.iteration_form = 5): sc != nullptr -- dots are RAW inner products of V~_i with w~, the
-    // scale factors sc[i] = 1 / ||w'_i|| are applied to the scalars here (h_i = sc_i s_w dots_i, MAXPY coefficient
-    // h_i sc_i, w = s_w w~); zun is Z_{loc+1} itself; the reducer stores the scaled Hessenberg column (hbuf).  sc[nv] and
-    // the Givens step of THIS iteration follow in the rider of the next product launch (GivensRider).  No vector is ever
+    // un-normalised basis, sc required: dots are RAW inner products of V~_i with w~, the scale factors
+    // sc[i] = 1 / ||w'_i|| are applied to the scalars here (h_i = sc_i s_w dots_i, MAXPY coefficient h_i sc_i,
+    // w = s_w w~); zun is Z_{loc+1} itself; the reducer stores the scaled Hessenberg column (hbuf).  sc[nv] and the
+    // Givens step of THIS iteration follow in the rider of the next product launch (GivensRider).  No vector is ever
     // normalised, no pass exists for it.
     double *sc, *hbuf, *wl_out;
     KrylovArrays ka;
@@ -675,49 +630,6 @@ struct GsArgs {
 int gs_fused(IterB b, GsArgs g, hipStream_t s);
 int gs_fused_occupancy(int ng, int m);   // workgroups of the fused kernel that fit one CU
 int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
-// dots = false: the SpMV / normalisation part alone (three-launch form; one tile per workgroup: slots = tiles_per_xcd)
-void iter_spmv_mdot(const IterA &a, hipStream_t s, bool dots = true);
-// BA: w' = s_w w~ - V~ (h .* sc) with ||w'||^2, z~ = M^-1 w', then -- behind neighbour flags instead of a kernel
-// boundary -- the NEXT product w~ = A z~ + B^T y~ of the same row tiles; Givens of this iteration in the reducer.
-// The basis stays UN-normalised (V~_i, Z~_i) with one scale factor per vector (sc[i] = 1 / ||w'_i||).
-struct IterBA {
-    const int32_t *browptr, *bcol;
-    const double *vtop, *vbot;
-    const int32_t *tile_brow;
-    const int32_t *tdesc;  // per tile {first block row, end block row, first block, end block}
-    int ntiles, tiles_per_xcd, slots, tb;
-    int chunk;             // double2 entries per workgroup in phase B (<= 256)
-    const int32_t *nbr, *wt;   // wt: per workgroup {t0, t1, first owner, last owner to wait for}
-    uint32_t *flags;
-    uint32_t seq;
-    const double *V;       // basis, un-normalised from vector 1 on
-    int64_t ldv;
-    int nv;                // loc + 1
-    const double *dots;    // reduced RAW [V~_i . w~ (nv), B D w~ (m)]
-    double *sc;            // scale factors, (restart + 2)
-    double *tb_;           // B D V~_i per basis vector, (restart + 2) x 8
-    double *w;             // V_{loc+1}: in w~, out w'
-    const double *dinv, *bd;
-    int64_t ldb;
-    const double *shat, *gram;
-    int fact;
-    int64_t nl;
-    int m, packed;
-    double *zout;          // Z_{loc+1} = z~ (gathered by the SpMV phase of this launch)
-    double *wnext;         // V_{loc+2} = w~ of the next iteration
-    const double *wl_in;
-    double *wl_out;
-    double *hbuf;          // scaled Hessenberg column of this iteration (nv values)
-    int lam_in_dot, last;  // last: no SpMV phase (last iteration of a restart cycle)
-    double *partials, *nrm_out;
-    PeerAR ar;
-    int32_t *err;
-    uint32_t fin_ticks;
-    KrylovArrays ka;
-    int loc;
-    const int32_t *done;
-};
-void iter_ba(const IterBA &p, hipStream_t s);
 // Resident restart cycle (spk_k_resident.hip): ONE launch runs iterations 0 .. mk-1 of a cycle with the basis in registers
 // (single rank, row-type layout with 2x2 blocks, <= 512 block rows per CU, restart <= 30, <= 4 planes of B D).  On entry
 // V0 = v_0 (normalised), V1 = K z_0; Z_1.. are written; the Krylov scalars end up where krylov_cycle_end expects them.
@@ -741,10 +653,7 @@ struct ResidentArgs {
 bool cycle_resident(const DictDev &A, int num_cus, ResidentArgs r, const int32_t *done, hipStream_t s);   // false: shape does not fit
 int64_t resident_scratch_doubles(int num_cus, int mk);
 bool resident_fits(const DictDev &A, int num_cus, int mk, int planes);   // planes: dense planes of B D the iteration streams
-// block-column range of every tile of the blocked matrix (set-up of the BA kernel's neighbour lists)
-void tile_col_range(const int32_t *browptr, const int32_t *bcol, const int32_t *tile_brow, int ntiles, int32_t *out, hipStream_t s);
 int iter_maxpy_uhead(IterB b, hipStream_t s);   // returns the number of partial rows (GivensRider::fin_n)
-int iter_slots(int tiles_per_xcd, int wg_per_cu);
 void krylov_init(const KrylovArrays &ka, const spk_opts &o, const double *bnorm2, hipStream_t s);
 void krylov_cycle_begin(const KrylovArrays &ka, const double *nrm2, hipStream_t s, double *tb = nullptr, int m = 0,
                         double *sc = nullptr, const StateReport *report = nullptr);
@@ -864,12 +773,9 @@ struct spk_ctx {
     // Krylov workspace (sized by restart)
     int ws_restart = -1;
     spk::DevBuf<double> V, Z, xsol, rhs, tmp;
-    spk::DevBuf<double> zun;    // z~ of the two-launch iteration (un-normalised M^-1 w')
-    spk::DevBuf<uint32_t> ba_flags;  // BA kernel: one 128-byte line per workgroup
-    spk::DevBuf<double> ba_sc;       // scale factors of the un-normalised basis
+    spk::DevBuf<double> basis_sc;    // scale factors of the un-normalised basis (forms 5, 6, 7)
     spk::DevBuf<double> res_P;       // resident cycle kernel: all-to-all buffer of the inner products
     int num_cus = 0;                 // compute units of the device (grid of the resident cycle kernel)
-    uint32_t ba_seq = 0;
     spk::DevBuf<double> gs_tot;      // form 7: two armed lines of MDot totals (the launch reads one, arms the other)
     uint32_t gs_seq = 0;
     int gs_occ[3] = {-1, -1, -1};    // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes), -1 unknown

@@ -102,7 +102,7 @@ __global__ void krylov_givens_kernel(KrylovArrays ka, int loc, const double *dot
 }
 __global__ __launch_bounds__(256) void krylov_givens_big_kernel(KrylovArrays ka, int loc, const double *dots, const double *nrm2)
 {
-    givens_block_t<kBigNv + 2>(ka, loc, dots, nrm2, nullptr);
+    givens_block_t<kBigNv + 2>(ka, loc, dots, nrm2);
 }
 __global__ __launch_bounds__(kThreads) void givens_rider_kernel(GivensRider gr, const int32_t *done)
 {

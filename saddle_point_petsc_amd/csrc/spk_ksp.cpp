@@ -237,8 +237,8 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (!val || !parse_int(val, &k->opts.single_reduce)) return need("an integer (0 off, 1 on)");
         } else if (key == "-spk_iteration_form") {
             if (!val || !parse_int(val, &k->opts.iteration_form) || k->opts.iteration_form < 0 || k->opts.iteration_form > SPK_ITER_LAST)
-                return need("an integer 0..7 (0 automatic, 1 four / 2 two / 3 three launches per iteration, 4 BA, 5 three launches on an "
-                            "un-normalised basis, 6 one launch per restart cycle, 7 as 5 with MDot and MAXPY in one launch)");
+                return need("an integer 0..7 (0 automatic, 1 four launches per iteration, 5 three launches on an un-normalised basis, "
+                            "6 one launch per restart cycle, 7 as 5 with MDot and MAXPY in one launch; 2..4 are accepted and run as 5)");
         } else if (key == "-spk_check_every") {
             if (!val || !parse_int(val, &k->opts.check_every)) return need("an integer");
         } else if (key.rfind("-ksp_", 0) == 0 || key.rfind("-pc_", 0) == 0 || key.rfind("-fieldsplit_", 0) == 0) {

@@ -72,8 +72,7 @@ void spk_ctx::ensure_vectors()
     if (want != ld) {
         ld = want;
         ws_restart = -1;
-        tmp.release();
-        zun.release();   // every vector sized by ld goes with it (a second KSPSetOperators may bring a larger system)
+        tmp.release();   // every vector sized by ld goes with it (a second KSPSetOperators may bring a larger system)
         tmpb.release();
         bt_cached = nullptr;
         stage_x.release();
@@ -574,7 +573,6 @@ static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int6
         Ab.ok = false;
         Ab.nbrows = 0;
         Ab.ntiles = 0;
-        Ab.long_rows = false;
         if (n % 2 == 0 && n > 0 && nnzd % 4 == 0) {
             const int32_t nbr = n / 2;
             Ab.browptr.alloc_raw((size_t)nbr + 1, 8);
@@ -595,87 +593,10 @@ static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int6
                 Ab.nblocks = nnzd / 4;
                 std::vector<int32_t> tb;
                 k::build_btiles(brp.data(), Ab.nbrows, tb);
-                for (int32_t br = 0; br < Ab.nbrows && !Ab.long_rows; ++br) Ab.long_rows = brp[(size_t)br + 1] - brp[(size_t)br] > k::kBTile;
                 Ab.ntiles = (int32_t)tb.size() - 1;
                 Ab.tile_brow.upload(tb.data(), tb.size(), 8);
-                {
-                    std::vector<int32_t> td((size_t)4 * Ab.ntiles);
-                    for (int32_t t = 0; t < Ab.ntiles; ++t) {
-                        td[(size_t)4 * t] = tb[(size_t)t];
-                        td[(size_t)4 * t + 1] = tb[(size_t)t + 1];
-                        td[(size_t)4 * t + 2] = brp[(size_t)tb[(size_t)t]];
-                        td[(size_t)4 * t + 3] = brp[(size_t)tb[(size_t)t + 1]];
-                    }
-                    Ab.tile_desc.upload(td.data(), td.size(), 8);
-                }
                 Ab.ok = true;
                 build_dict(c, 2, brp.data());
-                // BA iteration kernel: workgroup rho (row order) owns ba_tb consecutive tiles of its XCD's range; it
-                // may start its SpMV phase once the owners of the rows its block columns touch have stored their z~
-                Ab.ba_ok = false;
-                if (!Ab.long_rows && Ab.ntiles > 0) {
-                    const int TB = 4, tpx = (Ab.ntiles + 7) / 8;
-                    DevBuf<int32_t> rng;
-                    rng.alloc_raw((size_t)2 * Ab.ntiles, 8);
-                    k::tile_col_range(Ab.browptr.p, Ab.bcol.p, Ab.tile_brow.p, Ab.ntiles, rng.p, s);
-                    std::vector<int32_t> rh((size_t)2 * Ab.ntiles);
-                    SPK_HIP(hipMemcpyAsync(rh.data(), rng.p, rh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                    SPK_HIP(hipStreamSynchronize(s));
-                    // groups of <= TB consecutive tiles with <= 256 block rows (one double2 per thread in phase B),
-                    // XCD by XCD (each XCD keeps its contiguous run of tiles, as in the SpMV kernels)
-                    std::vector<std::vector<std::pair<int32_t, int32_t>>> groups(8);
-                    bool fits = true;
-                    int S = 1;
-                    for (int x = 0; x < 8; ++x) {
-                        const int tbeg = std::min(x * tpx, (int)Ab.ntiles), tend = std::min((x + 1) * tpx, (int)Ab.ntiles);
-                        int t = tbeg;
-                        while (t < tend) {
-                            int t1 = t;
-                            while (t1 < tend && t1 - t < TB && tb[(size_t)t1 + 1] - tb[(size_t)t] <= 256) ++t1;
-                            if (t1 == t) { fits = false; break; }   // one tile beyond 256 block rows
-                            groups[(size_t)x].push_back({t, t1});
-                            t = t1;
-                        }
-                        S = std::max(S, (int)groups[(size_t)x].size());
-                    }
-                    const int nwg = 8 * S;
-                    if (nwg > 1024) fits = false;
-                    // phase B deals the double2 entries (= block rows) out evenly, in the same row order: workgroup rho owns
-                    // [rho chunk, (rho + 1) chunk) -- no table in front of its loads; one entry per thread
-                    const int chunk = (Ab.nbrows + nwg - 1) / nwg;
-                    if (chunk > 256 || chunk < 1) fits = false;
-                    // per workgroup rho = x S + k: {t0, t1, first owner, last owner it waits for}: the owners (phase B) of the
-                    // block rows its columns touch and of its own rows (their c~)
-                    std::vector<int32_t> wt((size_t)4 * nwg, 0);
-                    for (int rho = 0; rho < nwg && fits; ++rho) {
-                        const int x = rho / S, kk = rho % S;
-                        const auto &gx = groups[(size_t)x];
-                        int32_t *w4 = wt.data() + (size_t)4 * rho;
-                        if (kk < (int)gx.size()) {
-                            const int t0 = gx[(size_t)kk].first, t1 = gx[(size_t)kk].second;
-                            int32_t lo = tb[(size_t)t0], hi = tb[(size_t)t1] - 1;
-                            for (int t = t0; t < t1; ++t) {
-                                lo = std::min(lo, rh[(size_t)2 * t]);
-                                hi = std::max(hi, rh[(size_t)2 * t + 1]);
-                            }
-                            w4[0] = t0;
-                            w4[1] = t1;
-                            w4[2] = std::max(0, lo / chunk);
-                            w4[3] = std::min(nwg - 1, hi / chunk);
-                        } else {  // no tiles: waits for nobody
-                            w4[0] = w4[1] = 0;
-                            w4[2] = 0;
-                            w4[3] = -1;
-                        }
-                    }
-                    if (fits) {
-                        Ab.ba_slots = S;
-                        Ab.ba_tb = TB;
-                        Ab.ba_chunk = chunk;
-                        Ab.ba_wt.upload(wt.data(), wt.size(), 8);
-                        Ab.ba_ok = true;
-                    }
-                }
             } else {
                 Ab.browptr.release(); Ab.bcol.release(); Ab.vtop.release(); Ab.vbot.release();
             }
@@ -1399,6 +1320,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         form = (int)f;
     }
     if (form < SPK_ITER_AUTO || form > SPK_ITER_LAST) fail(SPK_ERR_ARG, "fgmres: unknown iteration_form %d", form);
+    if (form == SPK_ITER_TWO_LAUNCH || form == SPK_ITER_THREE_LAUNCH || form == SPK_ITER_BA) form = SPK_ITER_UNNORM;   // retired: aliases of 5
     // AUTO: three launches on an UN-normalised basis -- MDot (raw inner products), MAXPY + norm + next PCApply, plain SpMV
     // with the Givens step and the new scale factor in one extra workgroup (GivensRider).  V~_j = h_{j,j-1} v_j: nothing
     // compounds, no vector is ever scaled in memory.  Either matrix format, any number of ranks, any transport.
@@ -1428,29 +1350,9 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         c->gs_tot.alloc(2 * k::kPartialLd);
         k::arm_partials(c->gs_tot.p, c->gs_tot.n, s);
     }
-    const bool two_ok = head && !single && o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER &&
-                        c->spmv_format == 1 && c->Ab.ok && !c->Ab.long_rows && mk + c->m <= k::kMaxNv - 2;
-    const bool two = two_ok && !un3 && (form == SPK_ITER_TWO_LAUNCH || form == SPK_ITER_THREE_LAUNCH);
-    // forms 2 / 3 (normalised basis, MDot inside / behind the SpMV launch): opt-in, kept for comparison
-    const bool three = two && form != SPK_ITER_TWO_LAUNCH;
-    // BA: MAXPY + the next SpMV in one launch behind neighbour flags, un-normalised basis (two launches per
-    // iteration: MDot, BA).  Single rank; opt-in (opts.iteration_form = 4 / SPK_ITER_FORM=4)
-    const bool ba = two_ok && form == SPK_ITER_BA && c->Ab.ba_ok && c->peers.empty() && c->comm->size() == 1 &&
-                    (c->m <= 4 || 8 * c->Ab.ba_slots + 1 <= 512);   // every workgroup resident at once (registers: 3 / 2 per CU)
-    if (ba) {
-        const size_t nfl = (size_t)(8 * c->Ab.ba_slots + 1) * 32;
-        if (c->ba_flags.n < nfl) {
-            c->ba_flags.alloc(nfl);
-            c->ba_seq = 0;
-        }
-    }
-    if (ba || un3) {
-        if (c->ba_sc.n < (size_t)mk + 2) c->ba_sc.alloc((size_t)mk + 2);
-    }
-    if (two && c->zun.n < (size_t)ld) c->zun.alloc((size_t)ld);
+    if (un3 && c->basis_sc.n < (size_t)mk + 2) c->basis_sc.alloc((size_t)mk + 2);
     const int lam_in_dot = c->comm->rank() == 0 ? 1 : 0;
-    c->last_form = resident ? SPK_ITER_RESIDENT : gsf ? SPK_ITER_GS_FUSED : ba ? SPK_ITER_BA : un3 ? SPK_ITER_UNNORM : two ? (three ? SPK_ITER_THREE_LAUNCH : SPK_ITER_TWO_LAUNCH)
-                   : head ? SPK_ITER_FOUR_LAUNCH : -1;
+    c->last_form = resident ? SPK_ITER_RESIDENT : gsf ? SPK_ITER_GS_FUSED : un3 ? SPK_ITER_UNNORM : head ? SPK_ITER_FOUR_LAUNCH : -1;
     c->last_single = single ? 1 : 0;
 
     c->ka.tentative = single ? 1 : 0;
@@ -1489,8 +1391,8 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         // (the kernel also reports the state it finds / leaves into pinned memory: the verdict on the PREVIOUS cycle and,
         // through its own convergence test on the true residual, on the solve -- read by the host at loc == kAhead)
         const k::StateReport report{ps, pe, c->errw.p, c->comm->error_dev()};
-        k::krylov_cycle_begin(c->ka, nrmbuf(1), s, (single || two || ba || un3) ? c->ka.tb : nullptr, m,
-                              (ba || un3) ? c->ba_sc.p : nullptr, &report);
+        k::krylov_cycle_begin(c->ka, nrmbuf(1), s, (single || un3) ? c->ka.tb : nullptr, m,
+                              un3 ? c->basis_sc.p : nullptr, &report);
         SPK_HIP(hipEventRecord(c->state_ev, s));
         pend_check = true;
         if (!head) k::scale_dev(Vj(0), N, inv_tt, done, s);
@@ -1519,7 +1421,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
             const int32_t *done = &c->kst.p->skip_iter;  // the gate of everything inside an iteration
             double *w = Vj(loc + 1);
             double *db = big ? c->bigdots.p : dotsbuf(loc), *nb = nrmbuf(loc);
-            if (ba || un3) {
+            if (un3) {
                 // the product K z~ of a vector (halo, then diagonal and off-rank columns in one kernel), either format
                 auto product = [&](const double *zvec, double *wvec, bool halo_done, const k::GivensRider *rider = nullptr) {
                     k::SendRanges srp = c->send_ranges;
@@ -1550,7 +1452,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
                     r.mk = mk; r.m = fused ? m : 0; r.packed = bpk; r.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
                     r.lam_in_dot = lam_in_dot; r.nl = nl; r.ld = ld;
                     r.V0 = Vj(0); r.V1 = Vj(1); r.Z = Z; r.dinv = c->dinv.p; r.bd = bdp; r.ldb = ld;
-                    r.shat = c->shat.p; r.gram = c->gram.p; r.P = c->res_P.p; r.ka = c->ka; r.sc_out = c->ba_sc.p;
+                    r.shat = c->shat.p; r.gram = c->gram.p; r.P = c->res_P.p; r.ka = c->ka; r.sc_out = c->basis_sc.p;
                     r.err = c->errw.p; r.ticks = c->fin_ticks;
                     r.sr0 = k::SendRanges{};
                     r.sr1 = k::SendRanges{};
@@ -1577,146 +1479,49 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
                             fused ? m : 0, spl ? 1 : 0);
                     if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + (fused ? m : 0), s);
                 }
-                if (un3) {
-                    const k::PeerAR ar2 = c->comm->fused_allreduce(1, k::kStatArNorm);
-                    k::IterB b{};
-                    b.V = V; b.ldv = ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
-                    b.w = w; b.dinv = c->dinv.p; b.bd = bdp; b.ldb = ld; b.shat = c->shat.p; b.gram = c->gram.p;
-                    b.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
-                    b.nl = nl; b.m = m; b.packed = bpk;
-                    b.zun = Zj(loc + 1); b.c = fused ? Vj(loc + 2) : nullptr; b.wl_in = wl(loc); b.wl_out = wl(loc + 1);
-                    b.lam_in_dot = lam_in_dot;
-                    b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
-                    b.sc = c->ba_sc.p; b.hbuf = sm2; b.ka = c->ka; b.loc = loc;
-                    // ||w'||^2 is left as one partial per workgroup: the rider of the product launch reduces it (and all-reduces
-                    // it, peer-store) beside the row tiles -- the product of an un-normalised vector does not need the norm.
-                    // (Not with an all-reduce that is a launch of its own, nor behind the last iteration of a cycle.)
-                    const bool defer = loc + 1 < mk && (c->comm->size() == 1 || ar2.P);
-                    b.defer_fin = defer ? 1 : 0;
-                    k::SendRanges sr = c->send_ranges;
-                    const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
-                    if (sr.n > 0) b.sr = sr;
-                    b.done = done;
-                    int fin_n;
-                    if (gs) {
-                        k::GsArgs g{};
-                        g.V2 = fused ? (bpk ? c->bdpk.p : c->bd.p) : nullptr;
-                        g.cnt = loc + 1 + (fused ? m : 0);
-                        g.split = bpk;
-                        g.n2 = (N + 1) / 2; g.n_dot = n_dot;
-                        g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
-                        g.out = db;
-                        g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
-                        g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
-                        g.fe = k::FinErr{c->errw.p, c->fin_ticks};
-                        fin_n = k::gs_fused(b, g, s);
-                        ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
-                    } else {
-                        fin_n = k::iter_maxpy_uhead(b, s);
-                    }
-                    if (!ar2.P && !defer) c->comm->allreduce_sum(nb, 1, s);
-                    // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
-                    k::GivensRider gr{c->ka, loc, sm2, nb, c->ba_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
-                                      k::FinErr{c->errw.p, c->fin_ticks}, defer ? ar2 : k::PeerAR{}};
-                    if (loc + 1 < mk) product(Zj(loc + 1), Vj(loc + 2), inb, &gr);
-                    else pend_h = sm2, pend_n = nb, pend_loc = loc;   // no product behind it: the step runs in the cycle-end launch
-                    last = -1;
-                }
-                if (ba) {
-                k::IterBA p{};
-                p.browptr = c->Ab.browptr.p; p.bcol = c->Ab.bcol.p; p.vtop = c->Ab.vtop.p; p.vbot = c->Ab.vbot.p;
-                p.tile_brow = c->Ab.tile_brow.p; p.ntiles = c->Ab.ntiles; p.tiles_per_xcd = (c->Ab.ntiles + 7) / 8;
-                p.slots = c->Ab.ba_slots; p.tb = c->Ab.ba_tb; p.chunk = c->Ab.ba_chunk; p.nbr = nullptr; p.wt = c->Ab.ba_wt.p;
-                p.tdesc = c->Ab.tile_desc.p;
-                p.flags = c->ba_flags.p; p.seq = ++c->ba_seq;
-                p.V = V; p.ldv = ld; p.nv = loc + 1; p.dots = db; p.sc = c->ba_sc.p; p.tb_ = c->ka.tb;
-                p.w = w; p.dinv = c->dinv.p; p.bd = bdp; p.ldb = ld; p.shat = c->shat.p; p.gram = c->gram.p;
-                p.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
-                p.nl = nl; p.m = m; p.packed = bpk;
-                p.last = loc + 1 >= mk ? 1 : 0;
-                p.zout = p.last ? nullptr : Zj(loc + 1);
-                p.wnext = p.last ? nullptr : Vj(loc + 2);
-                p.wl_in = wl(loc); p.wl_out = wl(loc + 1);
-                p.hbuf = sm2;
-                p.lam_in_dot = lam_in_dot;
-                p.partials = c->partials.p; p.nrm_out = nb;
-                p.err = c->errw.p; p.fin_ticks = c->fin_ticks;
-                p.ka = c->ka; p.loc = loc; p.done = done;
-                k::iter_ba(p, s);
-                last = -1;  // the Givens step of this iteration ran inside the launch
-                }
-            } else if (two) {
-                k::SendRanges sr0 = c->send_ranges;
-                const bool packed = sr0.n > 0;
-                if (loc == 0) {
-                    // first iteration of a cycle: the classic head on the normalised r (no kernel B behind it)
-                    bool inhead = packed && c->comm->fused_halo(sr0, c->xghost.p);
-                    if (fused)
-                        k::fused_head(Vj(0), nrmbuf(1), w1side, c->dinv.p, bdp, ld, c->shat.p, c->gram.p, c->schur_fact, nl, m,
-                                      Zj(0), w, c->ka, -1, dotsbuf(1), done, s, packed ? &sr0 : nullptr, bpk);
-                    else
-                        k::fused_head(Vj(0), nrmbuf(1), nullptr, c->dinv.p, nullptr, ld, nullptr, nullptr, SPK_SCHUR_LOWER, nl, 0,
-                                      Zj(0), nullptr, c->ka, -1, dotsbuf(1), done, s, packed ? &sr0 : nullptr);
-                    prev_inhead = inhead;
-                }
-                // halo of the vector kernel A gathers (z~ of kernel B, or Z_0): the producer sent it (peer-store),
-                // or packed it (exchange here), or it is gathered first
-                const double *zsrc = loc == 0 ? Zj(0) : c->zun.p;
-                if (!c->peers.empty() && !prev_inhead) {
-                    if (!packed) k::gather(zsrc, c->send_idx.p, c->send_off.back(), c->send_buf.p, done, s);
-                    c->comm->exchange(c->send_buf.p, c->peers, c->send_off, c->xghost.p, c->recv_off, s);
-                }
-                k::IterA a{};
-                a.browptr = c->Ab.browptr.p; a.bcol = c->Ab.bcol.p; a.vtop = c->Ab.vtop.p; a.vbot = c->Ab.vbot.p;
-                a.tile_brow = c->Ab.tile_brow.p; a.ntiles = c->Ab.ntiles; a.tiles_per_xcd = (c->Ab.ntiles + 7) / 8;
-                a.tdesc = reinterpret_cast<const int4 *>(c->Ab.tile_desc.p);
-                a.slots = 0;  // set by the launcher
-                a.od = c->n_ghost > 0 ? c->offdiag() : k::OffDiag{nullptr, nullptr, nullptr, nullptr};
-                a.zsrc = zsrc;
-                a.zdst = loc == 0 ? nullptr : Zj(loc);
-                a.vcur = Vj(loc);
-                a.w = w;
-                a.acc = fused ? 1 : 0;
-                a.nrm2 = loc == 0 ? nullptr : nrmbuf(loc - 1);
-                a.V = V; a.ldv = ld; a.nv = loc + 1;
-                a.bd = bdp; a.ldb = ld; a.m = m; a.packed = bpk;
-                a.nl = nl; a.lam_in_dot = lam_in_dot;
-                a.tb = c->ka.tb; a.wl_out = wl(0);
-                a.partials = c->partials.p; a.out = db;
-                if (!three) a.ar = c->comm->fused_allreduce(loc + 1 + m, k::kStatArDots);
-                a.err = c->errw.p; a.fin_ticks = c->fin_ticks;
-                a.ka = c->ka; a.loc_prev = loc - 1; a.dots_prev = dotsbuf(loc - 1); a.nrm_prev = nrmbuf(loc - 1);
-                a.done = done;
-                k::iter_spmv_mdot(a, s, !three);
-                if (three) {
-                    // h = V^T w and q = B D w (dense rows, or two halves per parity-interleaved plane) in one pass
-                    const bool one = loc + 1 + m <= 40;  // beyond 40 vectors MDot is two launches: dense rows, no ride-along
-                    const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + m, k::kStatArDots) : k::PeerAR{};
-                    const bool spl = bpk && one;
-                    k::mdot(V, ld, loc + 1, w, N, n_dot, c->fin(db, ar), done, s, spl ? c->bdpk.p : c->bd.p, m, spl ? 1 : 0);
-                    if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + m, s);
-                } else if (!a.ar.P) c->comm->allreduce_sum(db, loc + 1 + m, s);
                 const k::PeerAR ar2 = c->comm->fused_allreduce(1, k::kStatArNorm);
-                if (loc + 1 < mk) {
-                    k::IterB b{};
-                    b.V = V; b.ldv = ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
-                    b.w = w; b.dinv = c->dinv.p; b.bd = bdp; b.ldb = ld; b.shat = c->shat.p; b.gram = c->gram.p;
-                    b.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
-                    b.nl = nl; b.m = m; b.packed = bpk;
-                    b.zun = c->zun.p; b.c = fused ? Vj(loc + 2) : nullptr; b.wl_in = wl(0);
-                    b.lam_in_dot = lam_in_dot;
-                    b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
-                    k::SendRanges sr = c->send_ranges;
-                    prev_inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
-                    if (sr.n > 0) b.sr = sr;
-                    b.done = done;
-                    k::iter_maxpy_uhead(b, s);
+                k::IterB b{};
+                b.V = V; b.ldv = ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
+                b.w = w; b.dinv = c->dinv.p; b.bd = bdp; b.ldb = ld; b.shat = c->shat.p; b.gram = c->gram.p;
+                b.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
+                b.nl = nl; b.m = m; b.packed = bpk;
+                b.zun = Zj(loc + 1); b.c = fused ? Vj(loc + 2) : nullptr; b.wl_in = wl(loc); b.wl_out = wl(loc + 1);
+                b.lam_in_dot = lam_in_dot;
+                b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
+                b.sc = c->basis_sc.p; b.hbuf = sm2; b.ka = c->ka; b.loc = loc;
+                // ||w'||^2 is left as one partial per workgroup: the rider of the product launch reduces it (and all-reduces
+                // it, peer-store) beside the row tiles -- the product of an un-normalised vector does not need the norm.
+                // (Not with an all-reduce that is a launch of its own, nor behind the last iteration of a cycle.)
+                const bool defer = loc + 1 < mk && (c->comm->size() == 1 || ar2.P);
+                b.defer_fin = defer ? 1 : 0;
+                k::SendRanges sr = c->send_ranges;
+                const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
+                if (sr.n > 0) b.sr = sr;
+                b.done = done;
+                int fin_n;
+                if (gs) {
+                    k::GsArgs g{};
+                    g.V2 = fused ? (bpk ? c->bdpk.p : c->bd.p) : nullptr;
+                    g.cnt = loc + 1 + (fused ? m : 0);
+                    g.split = bpk;
+                    g.n2 = (N + 1) / 2; g.n_dot = n_dot;
+                    g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
+                    g.out = db;
+                    g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
+                    g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
+                    g.fe = k::FinErr{c->errw.p, c->fin_ticks};
+                    fin_n = k::gs_fused(b, g, s);
+                    ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
                 } else {
-                    // last iteration of the cycle: nothing follows the update but its norm
-                    k::maxpy(V, ld, loc + 1, nullptr, db, -1.0, w, N, n_dot, c->fin(nb, ar2), done, s);
+                    fin_n = k::iter_maxpy_uhead(b, s);
                 }
-                if (!ar2.P) c->comm->allreduce_sum(nb, 1, s);
-                last = loc;  // its Givens step rides in kernel A of the next iteration (or runs alone below)
+                if (!ar2.P && !defer) c->comm->allreduce_sum(nb, 1, s);
+                // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
+                k::GivensRider gr{c->ka, loc, sm2, nb, c->basis_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
+                                  k::FinErr{c->errw.p, c->fin_ticks}, defer ? ar2 : k::PeerAR{}};
+                if (loc + 1 < mk) product(Zj(loc + 1), Vj(loc + 2), inb, &gr);
+                else pend_h = sm2, pend_n = nb, pend_loc = loc;   // no product behind it: the step runs in the cycle-end launch
+                last = -1;
             } else if (fused) {
                 // v_j = w'/||w'|| (in place), z_j = M^-1 v_j, w = B^T z1 (u part) | B z0 (lambda part);
                 // workgroup 0 also runs the Givens step of iteration loc-1
@@ -1752,7 +1557,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
                 op_pc_apply(c, Vj(loc), Zj(loc), done);  // z_j = M^-1 v_j
                 op_mult(c, Zj(loc), w, done, false, true);   // w = K z_j (B^T z_1 of a general block: as PCApply left it)
             }
-            if (two || ba || un3) {
+            if (un3) {
                 // (orthogonalisation done above, inside the launches)
             } else if (o.orthog == SPK_ORTHOG_MGS) {
                 // KSPGMRESModifiedGramSchmidtOrthogonalization: one dot + one axpy per basis vector
@@ -1861,7 +1666,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         // ---- x += Z y (KSPFGMRESBuildSoln); always runs, count comes from the device ----
         {
             k::GivensRider pend{c->ka, pend_loc, pend_h, pend_n, nullptr, nullptr, 0, k::FinErr{nullptr, 0}, k::PeerAR{}};
-            k::krylov_cycle_end(c->ka, s, (ba || un3) ? c->ba_sc.p : nullptr, mk, pend_loc >= 0 ? &pend : nullptr);
+            k::krylov_cycle_end(c->ka, s, un3 ? c->basis_sc.p : nullptr, mk, pend_loc >= 0 ? &pend : nullptr);
         }
         k::maxpy(Z, ld, mk, loc_done, c->ka.nrs, 1.0, x, N, 0, c->fin(nullptr), nullptr, s);
         // ---- true residual for the next cycle (KSPFGMRESResidual); skipped once done ----

@@ -375,7 +375,8 @@ def test_every_iteration_form_against_the_oracle(spk, oracle, form, pc):
     """opts.iteration_form 1..6 (include/spk.h) are re-schedulings of the same classical Gram-Schmidt FGMRES:
     every one of them must reproduce the oracle's residual history and solution (AUTO picks form 6 -- the resident
     restart-cycle kernel -- on small single-rank systems and form 5 elsewhere, so the rest of the suite covers those;
-    a form that does not apply to a set-up falls back)."""
+    a form that does not apply to a set-up falls back).  Forms 2..4 are retired aliases of form 5: they must run as 5
+    and give its bits."""
     M = 48
     A, f = spk.AssembleOperator_Laplace(M)
     if pc == "schur":
@@ -393,6 +394,10 @@ def test_every_iteration_form_against_the_oracle(spk, oracle, form, pc):
         x, info = c.fgmres(rhs, rtol=1e-9, iteration_form=form)
         if form >= 5:
             assert c.iteration_form()[0] == form    # (these two apply to this set-up: no silent fall-back)
+        if 2 <= form <= 4:
+            assert c.iteration_form()[0] == 5
+            x5, info5 = c.fgmres(rhs, rtol=1e-9, iteration_form=5)
+            assert np.array_equal(x, x5) and np.array_equal(info["history"], info5["history"])
         # -ksp_max_it ending the solve in the middle of a cycle (the host stops enqueuing there; the last Givens step
         # of the form -- a rider, the next head, the cycle end -- must still have run)
         _, tr = c.fgmres(rhs, rtol=1e-30, max_it=47, iteration_form=form)
