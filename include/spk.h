@@ -69,7 +69,7 @@ enum { SPK_SPMV_CSR = 0 };
 enum { SPK_CONVERGED_RTOL = 2, SPK_CONVERGED_ATOL = 3, SPK_CONVERGED_ITS = 4,
        SPK_CONVERGED_HAPPY_BREAKDOWN = 7, SPK_DIVERGED_NULL = -2,
        SPK_DIVERGED_ITS = -3, SPK_DIVERGED_DTOL = -4, SPK_DIVERGED_BREAKDOWN = -5,
-       SPK_DIVERGED_NANORINF = -9, SPK_ITERATING = 0 };
+       SPK_DIVERGED_INDEFINITE_PC = -8, SPK_DIVERGED_NANORINF = -9, SPK_ITERATING = 0 };
 
 /* Solver options = the slice of the PETSc options database the reference
  * exposes through KSPSetFromOptions (SaddlePointProblem.c:67).  Fill with
@@ -151,7 +151,7 @@ typedef struct spk_result {
     double rnorm0;          /* residual norm at iteration 0 */
     int32_t hist_len;       /* entries written to history[] */
     int32_t cycles;         /* restart cycles executed */
-    double solve_seconds;   /* wall time inside spk_fgmres, upload excluded */
+    double solve_seconds;   /* wall time inside spk_fgmres / spk_minres, upload excluded */
 } spk_result;
 
 /* ---- lifetime (KSPCreate / KSPDestroy, SaddlePointProblem.c:65,72) ------- */
@@ -271,6 +271,30 @@ int spk_pc_apply(spk_ctx *ctx, const double *x, double *y, int mem);
  * b, x: n_local + m values.  history (may be NULL) receives the residual norm
  * per iteration, starting with iteration 0. */
 int spk_fgmres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts,
+               spk_result *result, double *history, int32_t history_cap);
+
+/* KSP type minres: preconditioned MINRES (Paige-Saunders; Elman-Silvester-Wathen Alg. 4.1) on the device, for a
+ * symmetric K and a symmetric positive definite M^-1: PC none, Jacobi (with or without B) and Schur DIAG (any
+ * constraint block).  LOWER / UPPER / FULL (not symmetric) and FP32 inner sweeps (spk_pc_set_inner > 0) are refused
+ * with SPK_ERR_UNSUPPORTED.  A short recurrence: no restart, twelve work vectors of its own (allocated on first use;
+ * nothing of spk_fgmres's workspace or state is touched).  Per iteration: the product K z, one pass with the previous
+ * iteration's lagged w / x (/ Kw / r) update and <K z, z>, one pass forming v_{j+1} and z_{j+1} = M^-1 v_{j+1}
+ * (PC applied in the pass) with <z, v>; the scalar recurrence runs in the finishing workgroup of each pass (one rank)
+ * or as a one-thread launch after the all-reduce.
+ * norm_type: the norm of the convergence test (KSPConvergedDefault: ttol = max(rtol ||b||, abstol), divergence at
+ * dtol ||b||, both in that norm):
+ *   SPK_NORM_UNPRECONDITIONED: ||b - K x||, kept by recurrence (K w_j by recurrence too: no extra product);
+ *   SPK_NORM_NATURAL: ||b - K x||_{M^-1} = |eta| of the recurrence (no r / K w streams).
+ * A convergence (or -ksp_max_it) seen by the recurrence is confirmed on the true b - K x in the same norm; if that
+ * misses ttol the recurrence restarts from the current x.  <z, v> < 0 ends the solve with
+ * SPK_DIVERGED_INDEFINITE_PC (a reason, not an error); gamma_{j+1} = 0 with SPK_CONVERGED_HAPPY_BREAKDOWN.
+ * opts: max_it, rtol, abstol, dtol, guess_nonzero, check_every (0: the host looks at the state once per chunk of
+ * iterations while the next chunk is queued), fused (0: PCApply as a step of its own, same algorithm);
+ * restart, orthog, cgs_refine, single_reduce and iteration_form are ignored.
+ * history[0] = the initial residual norm, then one recurrence value per iteration; result.rnorm = the true norm
+ * confirmed at the end; result.cycles = recurrence (re)starts. */
+enum { SPK_NORM_UNPRECONDITIONED = 0, SPK_NORM_NATURAL = 1 };
+int spk_minres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts, int norm_type,
                spk_result *result, double *history, int32_t history_cap);
 
 /* How the LAST spk_fgmres on ctx launched its iterations: *form = the SPK_ITER_* actually run (AUTO resolved; options

@@ -44,7 +44,10 @@ int SpkKSPSetOperators(SpkKSP ksp, const SpkMatCSR *A, const SpkMatCSR *B); /* K
  * DEVIATION from PETSc, on purpose: -ksp_type and -pc_type have NO default here.  PETSc would fall
  * back to gmres (left preconditioning) and ilu (bjacobi+ilu in parallel), neither of which this
  * library implements; SpkKSPSetUp / SpkKSPSolve return SPK_ERR_UNSUPPORTED with a message unless
- * "-ksp_type fgmres" and "-pc_type jacobi|fieldsplit|none" were given. */
+ * "-ksp_type fgmres|minres" and "-pc_type jacobi|fieldsplit|none" were given.
+ * -ksp_type minres (spk_minres) takes -ksp_norm_type unpreconditioned (default) | natural and needs a symmetric
+ * positive definite preconditioner: none, jacobi, or fieldsplit with -pc_fieldsplit_schur_fact_type diag and no
+ * FP32 inner sweeps; SpkKSPSetUp refuses the others with SPK_ERR_UNSUPPORTED before it looks at the operators. */
 int SpkKSPSetFromOptions(SpkKSP ksp, int argc, const char *const *argv);    /* KSPSetFromOptions :67 */
 int SpkKSPSetUp(SpkKSP ksp);                                                /* KSPSetUp       :68 */
 /* b, x: host vectors of n_local + m values ([u ; lambda]) */
@@ -57,6 +60,8 @@ int SpkKSPGetResidualNorm(SpkKSP ksp, double *rnorm);
 int SpkKSPGetResidualHistory(SpkKSP ksp, const double **hist, int32_t *n);
 int SpkKSPGetSolveTime(SpkKSP ksp, double *seconds);
 int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schur_fact);
+/* -ksp_type as set ("fgmres", "minres", or "" before KSPSetFromOptions gave one) and -ksp_norm_type (SPK_NORM_*) */
+int SpkKSPGetType(SpkKSP ksp, const char **type, int32_t *norm_type);
 int SpkKSPGetContext(SpkKSP ksp, spk_ctx **ctx);
 const char *SpkKSPGetError(SpkKSP ksp);
 const char *SpkKSPConvergedReasonName(int32_t reason);

@@ -14,5 +14,5 @@ from .assembly import (  # noqa: F401
 from .solver import (  # noqa: F401
     Context, KSP, LocalGroup, default_opts, unique_id,
     PC_NONE, PC_JACOBI, PC_SCHUR, SCHUR_DIAG, SCHUR_LOWER, SCHUR_UPPER, SCHUR_FULL,
-    BLOCK_A00, BLOCK_A10,
+    BLOCK_A00, BLOCK_A10, MEM_HOST, MEM_DEVICE, NORM_UNPRECONDITIONED, NORM_NATURAL, DIVERGED_INDEFINITE_PC,
 )

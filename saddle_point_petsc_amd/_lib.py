@@ -148,6 +148,7 @@ def _load():
     L.spk_mult.argtypes = [vp, f64p, f64p, C.c_int]
     L.spk_pc_apply.argtypes = [vp, f64p, f64p, C.c_int]
     L.spk_fgmres.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(Opts), C.POINTER(Result), vp, i32]
+    L.spk_minres.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32]
     L.spk_vec_create.argtypes = [vp, i64, C.POINTER(vp)]
     L.spk_vec_destroy.argtypes = [vp, vp]
     L.spk_vec_set.argtypes = [vp, vp, f64p, i64]
@@ -200,6 +201,7 @@ def _load():
     L.SpkKSPGetSolveTime.argtypes = [vp, C.POINTER(dbl)]
     L.SpkKSPGetOptions.argtypes = [vp, C.POINTER(Opts), C.POINTER(i32), C.POINTER(i32)]
     L.SpkKSPGetContext.argtypes = [vp, C.POINTER(vp)]
+    L.SpkKSPGetType.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i32)]
     L.SpkKSPGetError.restype = C.c_char_p
     L.SpkKSPGetError.argtypes = [vp]
     L.SpkKSPConvergedReasonName.restype = C.c_char_p

@@ -343,6 +343,20 @@ struct KrylovState {
     double tt;
 };
 
+// MINRES state (spk_minres): the convergence words of KrylovState (converged_default) and the scalar recurrence
+struct MinresState {
+    KrylovState ks;
+    int32_t norm;     // SPK_NORM_*
+    int32_t first;    // first iteration of a recurrence (v_0 = 0)
+    int32_t tent;     // ks.reason was set by the recurrence alone: confirmed on b - K x
+    int32_t pend;     // reason to end with once the pending update is applied (happy breakdown)
+    int32_t starts;   // recurrence (re)starts
+    int32_t started;  // rnorm0 / ttol fixed
+    double gam, gam_prev, delta, eta, c0, c1, s0, s1;
+    double vz_ig, vz_dg, vz_gg;                 // v_{j+1} = ig p - dg v_j - gg v_{j-1}   (p = K z_j, z_j not scaled)
+    double wx_ig, wx_a2, wx_a3, wx_ia1, wx_cx;  // w_{j+1} = (ig z_j - a3 w_{j-1} - a2 w_j) ia1 ;  x += cx w_{j+1}
+};
+
 // kernel launch wrappers (spk_k_*.hip)
 namespace k {
 constexpr int kMaxNv = 64;       // max vectors in one mdot/maxpy launch; restart <= 62 takes the fused kernels
@@ -654,6 +668,27 @@ bool cycle_resident(const DictDev &A, int num_cus, ResidentArgs r, const int32_t
 int64_t resident_scratch_doubles(int num_cus, int mk);
 bool resident_fits(const DictDev &A, int num_cus, int mk, int planes);   // planes: dense planes of B D the iteration streams
 int iter_maxpy_uhead(IterB b, hipStream_t s);   // returns the number of partial rows (GivensRider::fin_n)
+// MINRES (spk_k_minres.hip).  Scalar steps, run by the finishing workgroup of the pass that reduces their sums (one rank) or
+// by minres_scalar after the all-reduce: sums = [<.,.>, ||.||^2]
+enum { kMrBnorm = 0, kMrBegin = 1, kMrDelta = 2, kMrTest = 3, kMrRecur = 4 };
+struct MrStep {
+    MinresState *ms;
+    int mode;            // kMr*, < 0: no step in the kernel (several ranks)
+    double *hist;
+    int32_t hist_cap;
+};
+// v pass: v_{j+1} = ig p - dg v_j - gg v_{j-1} into vm (resid != 0: vm = r = p - vj, vj == nullptr: vm = p, r2 a
+// second copy); z = M^-1 v (z == nullptr: no PC in the pass); sums = [<z, v>, v.v (sq)] over the first n_dot entries
+void minres_vz(const double *p, const double *vj, double *vm, double *r2, double *z, const double *dinv, const double *shat,
+               int64_t nl, int64_t n, int64_t n_dot, int resid, int sq, const MinresState *ms, MrStep step, const Finish &f,
+               const int32_t *done, hipStream_t s);
+// lagged pass: (wx) w_{j+1} = (ig z_j - a3 w_{j-1} - a2 w_j) ia1 into wm, x += cx w_{j+1}; (kwm) the same for K w with
+// p_j, r -= cx K w_{j+1}; sums = [<da, db>, r.r (kwm) | db.db (sq)]
+void minres_wd(int wx, const double *zp, const double *pp, double *wm, const double *w, double *x, double *kwm,
+               const double *kw, double *r, const double *da, const double *db, int sq, int64_t n, int64_t n_dot,
+               const MinresState *ms, MrStep step, const Finish &f, const int32_t *done, hipStream_t s);
+void minres_init(MinresState *ms, const spk_opts &o, int norm, hipStream_t s);
+void minres_scalar(MrStep step, const double *sums, const int32_t *done, hipStream_t s);
 void krylov_init(const KrylovArrays &ka, const spk_opts &o, const double *bnorm2, hipStream_t s);
 void krylov_cycle_begin(const KrylovArrays &ka, const double *nrm2, hipStream_t s, double *tb = nullptr, int m = 0,
                         double *sc = nullptr, const StateReport *report = nullptr);
@@ -780,6 +815,13 @@ struct spk_ctx {
     uint32_t gs_seq = 0;
     int gs_occ[3] = {-1, -1, -1};    // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes), -1 unknown
     bool gs_fused_fits(int64_t nl, int m);   // fat vectors and every workgroup of the fused launch resident at once
+    // MINRES workspace (spk_minres, allocated on first use; FGMRES's V / Z / small / kst are not touched)
+    int64_t mr_ld = 0;
+    spk::DevBuf<double> mr_vec;              // kMrVecs vectors of stride ld
+    spk::DevBuf<double> mr_out, mr_hist;     // reduced sums, residual history
+    spk::DevBuf<spk::MinresState> mr_st;
+    void *mr_pin = nullptr;                  // pinned landing place of the state read-back
+    hipEvent_t mr_ev[2] = {nullptr, nullptr};
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist
     spk::DevBuf<spk::KrylovState> kst;
     spk::k::KrylovArrays ka{};
@@ -806,6 +848,8 @@ void op_mult(spk_ctx *c, const double *x, double *y, const int32_t *done, bool h
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done);
 void pc_setup(spk_ctx *c, int pc_type, int schur_fact);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
+            double *history, int32_t history_cap);
+void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,
             double *history, int32_t history_cap);
 void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
                const int32_t *rowptr, const int32_t *colidx, const double *val);

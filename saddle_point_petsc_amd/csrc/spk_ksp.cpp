@@ -21,6 +21,8 @@ struct SpkKSP_s {
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
     bool ksp_type_given = false, pc_type_given = false;
+    bool minres = false;                          // -ksp_type minres (else fgmres)
+    int32_t norm_type = SPK_NORM_UNPRECONDITIONED;   // -ksp_norm_type
     bool monitor = false, print_reason = false, view = false;
     spk_result result;
     std::vector<double> history;
@@ -73,6 +75,7 @@ const char *SpkKSPConvergedReasonName(int32_t r)
     case SPK_DIVERGED_ITS: return "DIVERGED_ITS";
     case SPK_DIVERGED_DTOL: return "DIVERGED_DTOL";
     case SPK_DIVERGED_BREAKDOWN: return "DIVERGED_BREAKDOWN";
+    case SPK_DIVERGED_INDEFINITE_PC: return "DIVERGED_INDEFINITE_PC";
     case SPK_DIVERGED_NANORINF: return "DIVERGED_NANORINF";
     case SPK_ITERATING: return "CONVERGED_ITERATING";
     default: return "UNKNOWN";
@@ -154,7 +157,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         bool flag = true;
         if (key == "-ksp_type") {
             if (!val) return need("a type");
-            if (std::string(val) != "fgmres") return bad();
+            const std::string v(val);
+            if (v == "fgmres") k->minres = false;
+            else if (v == "minres") k->minres = true;
+            else return bad();
             k->ksp_type_given = true;
         } else if (key == "-ksp_rtol") {
             if (!val || !parse_double(val, &k->opts.rtol)) return need("a real");
@@ -185,7 +191,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (std::string(val) != "right") return bad();
         } else if (key == "-ksp_norm_type") {
             if (!val) return need("a type");
-            if (std::string(val) != "unpreconditioned") return bad();
+            const std::string v(val);
+            if (v == "unpreconditioned") k->norm_type = SPK_NORM_UNPRECONDITIONED;
+            else if (v == "natural") k->norm_type = SPK_NORM_NATURAL;   // minres only (checked at KSPSetUp)
+            else return bad();
         } else if (key == "-ksp_monitor" || key == "-ksp_monitor_true_residual") {
             k->monitor = true;
         } else if (key == "-ksp_converged_reason") {
@@ -254,10 +263,23 @@ int SpkKSPSetUp(SpkKSP k)
     if (!k) return SPK_ERR_ARG;
     if (!k->ksp_type_given)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -ksp_type given; PETSc's default (gmres, left preconditioning) is "
-                                               "not implemented -- pass -ksp_type fgmres");
+                                               "not implemented -- pass -ksp_type fgmres (or -ksp_type minres for a symmetric "
+                                               "preconditioner)");
     if (!k->pc_type_given)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -pc_type given; PETSc's default (ilu, bjacobi+ilu in parallel) is "
                                                "not implemented -- pass -pc_type jacobi | fieldsplit | none");
+    // KSP / PC compatibility: option checks only, no GPU needed
+    if (!k->minres && k->norm_type == SPK_NORM_NATURAL)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres; fgmres tests the "
+                                               "unpreconditioned norm -- drop -ksp_norm_type natural or pass -ksp_type minres");
+    if (k->minres && k->pc_type == SPK_PC_SCHUR && k->schur_fact != SPK_SCHUR_DIAG)
+        return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: -ksp_type minres needs a symmetric positive definite "
+                       "preconditioner and the Schur ") + (k->schur_fact == SPK_SCHUR_LOWER ? "lower" : k->schur_fact == SPK_SCHUR_UPPER ?
+                       "upper" : "full") + " factorisation is not symmetric -- pass -pc_fieldsplit_schur_fact_type diag, or -ksp_type fgmres");
+    if (k->minres && k->pc_type != SPK_PC_NONE && k->inner_richardson && k->inner_sweeps > 0)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres needs a symmetric preconditioner and the FP32 inner "
+                                               "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
+                                               "pass -ksp_type fgmres");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
         return set_err(k, SPK_ERR_STATE, "KSPSetUp: -pc_type fieldsplit (schur) needs the constraint block B");
@@ -280,7 +302,9 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     }
     const int64_t cap = (int64_t)k->opts.max_it + 2;
     k->history.assign((size_t)(cap > (1 << 22) ? (1 << 22) : cap), 0.0);
-    const int rc = spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
+    const int rc = k->minres ? spk_minres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
+                                          (int32_t)k->history.size())
+                             : spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
     if (rc != SPK_OK) return from_ctx(k, rc);
     k->history.resize((size_t)k->result.hist_len);
     if (k->monitor)
@@ -288,7 +312,11 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->print_reason)
         std::printf("Linear solve %s due to %s iterations %d\n", k->result.reason > 0 ? "converged" : "did not converge",
                     SpkKSPConvergedReasonName(k->result.reason), k->result.its);
-    if (k->view)
+    if (k->view && k->minres)
+        std::printf("KSP Object: type minres (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, pc=%d schur_fact=%d\n",
+                    k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol, k->opts.abstol, k->opts.dtol,
+                    k->opts.max_it, k->pc_type, k->schur_fact);
+    else if (k->view)
         std::printf("KSP Object: type fgmres (MI355X device-resident), restart=%d, classical Gram-Schmidt, rtol=%g atol=%g divtol=%g max_it=%d, right preconditioning, pc=%d schur_fact=%d\n",
                     k->opts.restart, k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_type, k->schur_fact);
     return SPK_OK;
@@ -311,6 +339,13 @@ int SpkKSPGetOptions(SpkKSP k, spk_opts *o, int32_t *pc, int32_t *sf)
     if (o) *o = k->opts;
     if (pc) *pc = k->pc_type;
     if (sf) *sf = k->schur_fact;
+    return SPK_OK;
+}
+int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)
+{
+    if (!k) return SPK_ERR_ARG;
+    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : "fgmres";
+    if (norm_type) *norm_type = k->norm_type;
     return SPK_OK;
 }
 int SpkKSPGetContext(SpkKSP k, spk_ctx **c) { if (!k || !c) return SPK_ERR_ARG; *c = k->ctx; return SPK_OK; }

@@ -11,6 +11,9 @@ PC_NONE, PC_JACOBI, PC_SCHUR = 0, 1, 2
 SCHUR_DIAG, SCHUR_LOWER, SCHUR_UPPER, SCHUR_FULL = 0, 1, 2, 3
 BLOCK_A00, BLOCK_A10 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
+NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1
+DIVERGED_INDEFINITE_PC = -8
+_NORMS = {"unpreconditioned": NORM_UNPRECONDITIONED, "natural": NORM_NATURAL}
 
 
 def default_opts(**kw):
@@ -257,6 +260,33 @@ class Context:
                        cycles=res.cycles, solve_seconds=res.solve_seconds,
                        history=hist[:res.hist_len].copy())
 
+    def minres(self, b, x0=None, norm="unpreconditioned", **kw):
+        """Preconditioned MINRES (spk_minres) with the context's PC (none, Jacobi or Schur DIAG); norm: the norm of the
+        convergence test, "unpreconditioned" (||b - K x||) or "natural" (||b - K x|| in M^-1).  Same return as fgmres."""
+        b = np.ascontiguousarray(b, np.float64)
+        assert b.shape == (self._n(),)
+        x = np.zeros_like(b)
+        if x0 is not None:
+            x[:] = x0
+            kw["guess_nonzero"] = 1
+        return x, self._minres(b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw)
+
+    def minres_device(self, b_dev, x_dev, norm="unpreconditioned", **kw):
+        """MINRES on vectors that already live in device memory (vec_create)."""
+        return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw)
+
+    def _minres(self, bp, xp, mem, norm, kw):
+        if norm not in _NORMS:
+            raise ValueError(f"norm must be one of {sorted(_NORMS)}")
+        o = default_opts(**kw)
+        res = Result()
+        cap = int(min(o.max_it + 2, 1 << 22))
+        hist = np.zeros(cap)
+        self._chk(lib.spk_minres(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap))
+        return dict(its=res.its, reason=res.reason, rnorm=res.rnorm, rnorm0=res.rnorm0,
+                    cycles=res.cycles, solve_seconds=res.solve_seconds,
+                    history=hist[:res.hist_len].copy())
+
     # ---- device-resident vectors (inputs already in HBM when a solve starts)
     def vec_create(self, host=None, n=None):
         n = len(host) if host is not None else n
@@ -402,6 +432,18 @@ class KSP:
         o, pc, sf = Opts(), C.c_int32(), C.c_int32()
         lib.SpkKSPGetOptions(self.h, C.byref(o), C.byref(pc), C.byref(sf))
         return o, pc.value, sf.value
+
+    def getType(self):
+        """-ksp_type as set: 'fgmres', 'minres', or '' before setFromOptions gave one."""
+        t, n = C.c_char_p(), C.c_int32()
+        self._chk(lib.SpkKSPGetType(self.h, C.byref(t), C.byref(n)))
+        return t.value.decode()
+
+    def getNormType(self):
+        """-ksp_norm_type as set: 'unpreconditioned' or 'natural'."""
+        t, n = C.c_char_p(), C.c_int32()
+        self._chk(lib.SpkKSPGetType(self.h, C.byref(t), C.byref(n)))
+        return {v: k for k, v in _NORMS.items()}[n.value]
 
     def destroy(self):
         if self.h:
