@@ -107,8 +107,8 @@ typedef struct spk_opts {
                                ||w'|| over-estimates the residual), and a convergence seen by the
                                recurrence only ENDS THE CYCLE -- the solve ends when the true
                                residual computed at the restart confirms it, never on the
-                               recurrence alone.  Needs restart + m <= 63 (falls back to two
-                               reductions otherwise). */
+                               recurrence alone.  Needs restart + m <= 63 and restart <= 62
+                               (falls back to two reductions otherwise). */
     int32_t iteration_form; /* how the head-kernel paths launch one classical Gram-Schmidt iteration (same
                                algorithm, two reductions, norms taken from w' itself):
                                SPK_ITER_AUTO (0): 6, 7 or SPK_ITER_UNNORM wherever it applies (classical Gram-Schmidt

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -851,6 +852,11 @@ void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, s
             double *history, int32_t history_cap);
 void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,
             double *history, int32_t history_cap);
+// what the two drivers share: the checks they start with (an operator, KSPSetUp done) ...
+void require_setup(spk_ctx *c, const char *who);
+// ... and their end: drain the stream, raise a communicator or device error, fill res, copy the history (hist: device)
+void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono::steady_clock::time_point t0,
+                  const double *hist, int32_t hist_cap, spk_result *res, double *history, int32_t history_cap);
 void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
                const int32_t *rowptr, const int32_t *colidx, const double *val);
 }  // namespace spk

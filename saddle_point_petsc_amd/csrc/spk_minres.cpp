@@ -20,8 +20,7 @@ constexpr int kMrChunk = 16;  // iterations per look at the state when opts.chec
 void minres(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, spk_result *res, double *history,
             int32_t history_cap)
 {
-    if (!c->have_A) fail(SPK_ERR_STATE, "minres: no operator");
-    if (!c->pc_ready) fail(SPK_ERR_STATE, "minres: call spk_pc_setup first (KSPSetUp)");
+    require_setup(c, "minres");
     if (norm != SPK_NORM_UNPRECONDITIONED && norm != SPK_NORM_NATURAL) fail(SPK_ERR_ARG, "minres: unknown norm type %d", norm);
     if (c->pc_type == SPK_PC_SCHUR && c->schur_fact != SPK_SCHUR_DIAG)
         fail(SPK_ERR_UNSUPPORTED, "minres needs a symmetric positive definite preconditioner: the Schur %s factorisation is not "
@@ -151,22 +150,7 @@ void minres(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
         kx = T;
         SPK_HIP(hipGetLastError());
     }
-    SPK_HIP(hipStreamSynchronize(s));
-    c->comm->check(s);
-    c->check_device_error();
-    const auto t1 = std::chrono::steady_clock::now();
-
-    res->its = st.ks.its;
-    res->reason = st.ks.reason;
-    res->rnorm = st.ks.rnorm;
-    res->rnorm0 = st.ks.rnorm0;
-    res->cycles = st.starts;
-    res->solve_seconds = std::chrono::duration<double>(t1 - t0).count();
-    int32_t nh = std::min<int32_t>(st.ks.its + 1, hist_cap);
-    if (!history) nh = 0;
-    nh = std::min(nh, history_cap);
-    if (nh > 0) SPK_HIP(hipMemcpy(history, hist, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost));
-    res->hist_len = nh;
+    finish_solve(c, st.ks, st.starts, t0, hist, hist_cap, res, history, history_cap);
 }
 
 }  // namespace spk

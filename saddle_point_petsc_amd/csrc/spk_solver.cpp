@@ -1202,6 +1202,34 @@ void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done)
 }
 
 // ---------------------------------------------------------------------------
+// What the two Krylov drivers (fgmres, minres) share
+// ---------------------------------------------------------------------------
+void require_setup(spk_ctx *c, const char *who)
+{
+    if (!c->have_A) fail(SPK_ERR_STATE, "%s: no operator", who);
+    if (!c->pc_ready) fail(SPK_ERR_STATE, "%s: call spk_pc_setup first (KSPSetUp)", who);
+}
+
+void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono::steady_clock::time_point t0,
+                  const double *hist, int32_t hist_cap, spk_result *res, double *history, int32_t history_cap)
+{
+    SPK_HIP(hipStreamSynchronize(c->stream));  // (a speculative start of a cycle that will not run drains as no-ops)
+    c->comm->check(c->stream);  // what was raised after the last report (once per solve: blocking reads)
+    c->check_device_error();
+    const auto t1 = std::chrono::steady_clock::now();
+    res->its = st.its;
+    res->reason = st.reason;
+    res->rnorm = st.rnorm;
+    res->rnorm0 = st.rnorm0;
+    res->cycles = cycles;
+    res->solve_seconds = std::chrono::duration<double>(t1 - t0).count();
+    int32_t nh = history ? std::min<int32_t>(st.its + 1, hist_cap) : 0;
+    nh = std::min(nh, history_cap);
+    if (nh > 0) SPK_HIP(hipMemcpy(history, hist, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost));
+    res->hist_len = nh;
+}
+
+// ---------------------------------------------------------------------------
 // KSPSolve_FGMRES, device resident
 // ---------------------------------------------------------------------------
 static void ensure_krylov(spk_ctx *c, const spk_opts &o)
@@ -1236,79 +1264,24 @@ static void ensure_krylov(spk_ctx *c, const spk_opts &o)
     c->ka.hist_cap = hist_cap;
 }
 
-void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_result *res, double *history,
-            int32_t history_cap)
+namespace {
+// How an FGMRES iteration is launched, resolved once per solve (plan_fgmres).  The product K z_j: forms 5-7 (the
+// orthogonalisation inside their launches), a head kernel (Schur or Jacobi), or PCApply + MatMult.
+struct FgmresPlan {
+    enum Product { kUn3, kSchurHead, kJacobiHead, kStep } product;
+    enum Orth { kOrthUn3, kOrthMgs, kOrthSingle, kOrthCgs } orth;
+    bool schur, head;     // a head kernel scales v_j, runs the Givens step of j-1; Schur: B D w' out of the last MAXPY
+    bool big;             // restart > kMaxNv - 2: the Givens step is a launch of its own
+    bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
+    int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
+    int nn, bpk, form;    // norm (+ B D w') out of the last MAXPY; B D as m/2 parity planes; what is reported
+    const double *bdp;    // the B D rows the kernels stream (Schur)
+};
+
+FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
 {
-    if (!c->have_A) fail(SPK_ERR_STATE, "fgmres: no operator");
-    if (!c->pc_ready) fail(SPK_ERR_STATE, "fgmres: call spk_pc_setup first (KSPSetUp)");
-    if (o.orthog != SPK_ORTHOG_CGS && o.orthog != SPK_ORTHOG_MGS) fail(SPK_ERR_ARG, "fgmres: unknown orthogonalisation %d", o.orthog);
-    if (o.cgs_refine < SPK_REFINE_NEVER || o.cgs_refine > SPK_REFINE_ALWAYS) fail(SPK_ERR_ARG, "fgmres: unknown cgs_refine %d", o.cgs_refine);
-    ensure_krylov(c, o);
-    hipStream_t s = c->stream;
-    const int mk = o.restart;
-    const int64_t N = (int64_t)c->n_local + c->m, ld = c->ld;
-    const int64_t n_dot = (int64_t)c->n_local + (c->comm->rank() == 0 ? c->m : 0);
-    const int32_t *done = &c->kst.p->done;
-    const int32_t *loc_done = &c->kst.p->loc_done;
-    const double *inv_tt = &c->kst.p->inv_tt;
-    double *sm = c->small.p;  // [0..63] dots (+w.w), [64] norm^2, [128] ||b||^2
-    double *V = c->V.p, *Z = c->Z.p;
-    auto Vj = [&](int j) { return V + (size_t)ld * j; };
-    auto Zj = [&](int j) { return Z + (size_t)ld * j; };
-
-    SPK_HIP(hipStreamSynchronize(s));
-    const auto t0 = std::chrono::steady_clock::now();
-
-    // small[]: two parity sets so that a deferred Givens step (fused path) can still read iteration
-    // j-1's scalars while iteration j produces its own: dots at p*128, norm (+ B D w') at p*128+64
-    auto dotsbuf = [&](int p) { return sm + (p & 1) * 128; };
-    auto nrmbuf = [&](int p) { return sm + (p & 1) * 128 + 64; };
-    double *sm2 = sm + 256, *nrm2b = sm + 320, *bn2 = sm + 384, *w1side = c->y1tmp.p + 48;
-
-    // ||b|| for KSPConvergedDefault
-    k::sqnorm(b, n_dot, c->fin(bn2), nullptr, s);
-    c->comm->allreduce_sum(bn2, 1, s);
-    k::krylov_init(c->ka, o, bn2, s);
-
-    // initial residual into V0
-    if (!o.guess_nonzero) {
-        SPK_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, s));
-        SPK_HIP(hipMemcpyAsync(Vj(0), b, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
-    } else {
-        op_mult(c, x, c->tmp.p, nullptr);
-        SPK_HIP(hipMemcpyAsync(Vj(0), b, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
-        k::axpby(-1.0, c->tmp.p, 1.0, Vj(0), N, nullptr, s);
-    }
-
-    // fused Schur path: VecScale + PC + B^T part of the operator in one pass ("head"), B D w' in the
-    // MAXPY pass, the Givens step of iteration j-1 inside the head kernel of iteration j
-    // -ksp_gmres_restart beyond 62: the step-by-step path, Gram-Schmidt in chunks of <= 40 vectors (the fused kernels
-    // keep one lane / one LDS slot per basis vector)
-    const bool big = mk > k::kMaxNv - 2;
-    if (big && c->bigdots.n < 2 * ((size_t)mk + 4)) c->bigdots.alloc(2 * ((size_t)mk + 4));   // first and refinement pass
-    // (a long restart keeps the head kernel -- VecScale + PCApply + the B^T part of the product in one pass, the product
-    // accumulating onto it, B D w' out of the last MAXPY chunk -- and only the Givens step is a launch of its own: its
-    // column no longer fits the head kernel's workgroup 0)
-    const bool fused = o.fused && c->bd.p && c->pc_type == SPK_PC_SCHUR;
-    const int m = c->m;
-    const int32_t nl = c->n_local;
-    // the same head kernel without a constraint block: Jacobi on K = A (the reference as written,
-    // SaddlePointProblem.c:66, and BASELINE config 2): VecScale + PCApply_Jacobi + deferred Givens
-    const bool fusedj = o.fused && !fused && c->pc_type == SPK_PC_JACOBI && m == 0 && c->even_all && c->nonempty_all &&
-                        c->inner_sweeps == 0;
-    const bool head = fused || fusedj;
-    const int nn = fused ? 1 + m : 1;  // norm (+ B D w') coming out of the last MAXPY of an iteration
-    const int bpk = fused && c->bd_packed ? 1 : 0;   // B D as m/2 parity-interleaved planes
-    const double *bdp = fused ? (bpk ? c->bdpk.p : c->bd.p) : nullptr;
-    // single-reduction Gram-Schmidt (fused CGS without refinement): h = V^T w, q = B D w and w.w
-    // come out of ONE pass and ONE all-reduce; ||w'||^2 = w.w - |h|^2 and B D w' = q - sum h_i B D v_i
-    // follow without touching w' -- one collective per iteration instead of two.
-    // Opt-in (opts.single_reduce = 1): the subtraction cancels, see include/spk.h.
-    // The Jacobi head path (K = A) takes the same route with m = 0: ||w'||^2 = w.w - |h|^2 only.
-    // (MDot then carries restart + m vectors: both must fit one reduction.)
-    const bool single = head && o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER &&
-                        o.single_reduce == 1 && mk + c->m <= k::kMaxNv - 1;
-
+    FgmresPlan p{};
+    const int mk = o.restart, m = c->m, nl = c->n_local;
     // How one classical Gram-Schmidt iteration (two reductions) is launched on the head-kernel paths
     // (opts.iteration_form / SPK_ITER_FORM; include/spk.h lists the forms and their measured times).
     int form = o.iteration_form;
@@ -1321,43 +1294,338 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     }
     if (form < SPK_ITER_AUTO || form > SPK_ITER_LAST) fail(SPK_ERR_ARG, "fgmres: unknown iteration_form %d", form);
     if (form == SPK_ITER_TWO_LAUNCH || form == SPK_ITER_THREE_LAUNCH || form == SPK_ITER_BA) form = SPK_ITER_UNNORM;   // retired: aliases of 5
+    // -ksp_gmres_restart beyond 62: Gram-Schmidt in chunks of <= 40 vectors (the fused kernels keep one lane / one LDS
+    // slot per basis vector).  A long restart keeps the head kernel -- VecScale + PCApply + the B^T part of the product in
+    // one pass, the product accumulating onto it, B D w' out of the last MAXPY chunk -- and only the Givens step is a
+    // launch of its own: its column no longer fits the head kernel's workgroup 0.
+    p.big = mk > k::kMaxNv - 2;
+    p.chunk = p.big ? 40 : k::kMaxNv;
+    p.refine = o.cgs_refine;
+    // fused Schur path: VecScale + PC + B^T part of the operator in one pass ("head"), B D w' in the MAXPY pass, the
+    // Givens step of iteration j-1 inside the head kernel of iteration j
+    p.schur = o.fused && c->bd.p && c->pc_type == SPK_PC_SCHUR;
+    // the same head kernel without a constraint block: Jacobi on K = A (the reference as written,
+    // SaddlePointProblem.c:66, and BASELINE config 2): VecScale + PCApply_Jacobi + deferred Givens
+    const bool jac = o.fused && !p.schur && c->pc_type == SPK_PC_JACOBI && m == 0 && c->even_all && c->nonempty_all &&
+                     c->inner_sweeps == 0;
+    p.head = p.schur || jac;
+    p.nn = p.schur ? 1 + m : 1;
+    p.bpk = p.schur && c->bd_packed ? 1 : 0;
+    p.bdp = p.schur ? (p.bpk ? c->bdpk.p : c->bd.p) : nullptr;
+    // single-reduction Gram-Schmidt (fused CGS without refinement): h = V^T w, q = B D w and w.w
+    // come out of ONE pass and ONE all-reduce; ||w'||^2 = w.w - |h|^2 and B D w' = q - sum h_i B D v_i
+    // follow without touching w' -- one collective per iteration instead of two.
+    // Opt-in (opts.single_reduce = 1): the subtraction cancels, see include/spk.h.
+    // The Jacobi head path (K = A) takes the same route with m = 0: ||w'||^2 = w.w - |h|^2 only.
+    // (MDot carries restart + m vectors: both must fit one reduction; a long restart runs its Givens step on its own.)
+    const bool cgs1 = o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER;
+    const bool single = p.head && cgs1 && o.single_reduce == 1 && !p.big && mk + m <= k::kMaxNv - 1;
     // AUTO: three launches on an UN-normalised basis -- MDot (raw inner products), MAXPY + norm + next PCApply, plain SpMV
     // with the Givens step and the new scale factor in one extra workgroup (GivensRider).  V~_j = h_{j,j-1} v_j: nothing
     // compounds, no vector is ever scaled in memory.  Either matrix format, any number of ranks, any transport.
-    const bool un3 = head && !single && o.orthog == SPK_ORTHOG_CGS && o.cgs_refine == SPK_REFINE_NEVER &&
-                     mk + c->m <= k::kMaxNv - 2 &&
+    const bool un3 = p.head && !single && cgs1 && mk + m <= k::kMaxNv - 2 &&
                      (form == SPK_ITER_UNNORM || form == SPK_ITER_AUTO || form == SPK_ITER_RESIDENT || form == SPK_ITER_GS_FUSED);
     // RESIDENT: one launch per restart cycle, the basis in registers (spk_k_resident.hip): what AUTO takes where it fits
     static const bool res_env_off = [] { const char *e = getenv("SPK_RESIDENT"); return e && !strcmp(e, "0"); }();
-    const int res_planes = !fused ? 0 : (bpk ? m / 2 : m);
+    const int res_planes = !p.schur ? 0 : (p.bpk ? m / 2 : m);
     // several ranks: every rank must take it (agreed at KSPSetUp: res_fit_all), the collectives must be the peer-store
     // backend's (they run inside the launch), and the halo rows must be contiguous send ranges
     const bool res_multi = c->comm->size() > 1;
     const bool res_rank_ok = !res_multi ? (c->peers.empty() && c->n_ghost == 0)
                                         : (c->res_fit_all && c->comm->fuses() && (c->peers.empty() || c->send_ranges.n > 0));
-    const bool resident = un3 && (form == SPK_ITER_RESIDENT || (form == SPK_ITER_AUTO && !res_env_off)) && res_rank_ok &&
-                          c->spmv_format == 1 && c->Adict.ok && c->Adict.bs == 2 && nl % 2 == 0 && mk >= (res_multi ? 3 : 2) &&
-                          k::resident_fits(c->Adict, c->num_cus, mk, res_planes);
-    if (resident) {
-        const size_t need = (size_t)k::resident_scratch_doubles(c->num_cus, mk);
-        if (c->res_P.n < need) c->res_P.alloc(need);
-    }
+    p.resident = un3 && (form == SPK_ITER_RESIDENT || (form == SPK_ITER_AUTO && !res_env_off)) && res_rank_ok &&
+                 c->spmv_format == 1 && c->Adict.ok && c->Adict.bs == 2 && nl % 2 == 0 && mk >= (res_multi ? 3 : 2) &&
+                 k::resident_fits(c->Adict, c->num_cus, mk, res_planes);
     // GS_FUSED (form 7): MDot and kernel B in one launch (every iteration of a cycle but its last) -- one rank, fat vectors,
     // every workgroup of the launch resident at once; what AUTO takes there
-    const bool gsf = un3 && !resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
-                     c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m);
-    if (gsf && !c->gs_tot.p) {
-        c->gs_tot.alloc(2 * k::kPartialLd);
-        k::arm_partials(c->gs_tot.p, c->gs_tot.n, s);
-    }
-    if (un3 && c->basis_sc.n < (size_t)mk + 2) c->basis_sc.alloc((size_t)mk + 2);
-    const int lam_in_dot = c->comm->rank() == 0 ? 1 : 0;
-    c->last_form = resident ? SPK_ITER_RESIDENT : gsf ? SPK_ITER_GS_FUSED : un3 ? SPK_ITER_UNNORM : head ? SPK_ITER_FOUR_LAUNCH : -1;
-    c->last_single = single ? 1 : 0;
+    p.gsf = un3 && !p.resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
+            c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m);
+    p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
+    p.orth = un3 ? FgmresPlan::kOrthUn3 : o.orthog == SPK_ORTHOG_MGS ? FgmresPlan::kOrthMgs
+           : single ? FgmresPlan::kOrthSingle : FgmresPlan::kOrthCgs;
+    p.form = p.resident ? SPK_ITER_RESIDENT : p.gsf ? SPK_ITER_GS_FUSED : un3 ? SPK_ITER_UNNORM : p.head ? SPK_ITER_FOUR_LAUNCH : -1;
+    return p;
+}
 
-    c->ka.tentative = single ? 1 : 0;
+// the plan's own buffers (after the solve's first launches: form 7's arming launch keeps its place in the stream)
+void ensure_plan_buffers(spk_ctx *c, const FgmresPlan &p, int mk)
+{
+    if (p.big && c->bigdots.n < 2 * ((size_t)mk + 4)) c->bigdots.alloc(2 * ((size_t)mk + 4));   // first and refinement pass
+    const size_t need = p.resident ? (size_t)k::resident_scratch_doubles(c->num_cus, mk) : 0;
+    if (c->res_P.n < need) c->res_P.alloc(need);
+    if (p.gsf && !c->gs_tot.p) {
+        c->gs_tot.alloc(2 * k::kPartialLd);
+        k::arm_partials(c->gs_tot.p, c->gs_tot.n, c->stream);
+    }
+    if (p.product == FgmresPlan::kUn3 && c->basis_sc.n < (size_t)mk + 2) c->basis_sc.alloc((size_t)mk + 2);
+}
+
+// One solve's constants and the views of its work space
+struct FgmresRun {
+    spk_ctx *c;
+    const FgmresPlan &p;
+    hipStream_t s;
+    int mk, m, lam_in_dot, nl;
+    int64_t N, ld, n_dot;
+    double *V, *Z, *sm, *sm2, *nrm2b, *w1side;
+    double *Vj(int j) const { return V + (size_t)ld * j; }
+    double *Zj(int j) const { return Z + (size_t)ld * j; }
+    // small[]: two parity sets so that a deferred Givens step (head paths) can still read iteration j-1's scalars while
+    // iteration j produces its own: dots at q*128, norm (+ B D w') at q*128+64; lambda entries of w, side copies at 400
+    double *dotsbuf(int q) const { return sm + (q & 1) * 128; }
+    double *nrmbuf(int q) const { return sm + (q & 1) * 128 + 64; }
+    double *wl(int q) const { return sm + 400 + (q & 1) * 8; }
+};
+
+// What an iteration hands to the next one and to the end of its cycle
+struct CycleState {
+    bool stop = false; int last = -1;               // last iteration whose Givens step is still pending (head paths)
+    bool head_done = false, prev_inhead = false;    // single reduction: the previous MAXPY ran this head (and halo)
+    int pend_loc = -1;                              // the Givens step handed to the cycle-end launch: iteration,
+    const double *pend_h = nullptr; double *pend_n = nullptr;   // Hessenberg column and norm
+};
+
+// w (+)= A z: the halo exchange (unless done already), then diagonal and off-rank columns in one kernel, either format
+void product(const FgmresRun &r, const double *z, double *w, bool halo_done, bool accumulate, const int32_t *done,
+             const k::GivensRider *rider = nullptr)
+{
+    spk_ctx *c = r.c;
+    if (!c->peers.empty() && !halo_done) {
+        if (c->send_ranges.n == 0) k::gather(z, c->send_idx.p, c->send_off.back(), c->send_buf.p, done, r.s);
+        c->comm->exchange(c->send_buf.p, c->peers, c->send_off, c->xghost.p, c->recv_off, r.s);
+    }
+    const k::OffDiag od = c->offdiag();
+    a_mult(c, z, w, nullptr, nullptr, done, accumulate, c->n_ghost > 0 ? &od : nullptr, rider);
+}
+
+// v_j = Vj(j) / ||.|| (in place), z_j = M^-1 v_j, Schur: w = B^T z1 (u part) | B z0 (lambda part); workgroup 0 also runs
+// the Givens step of iteration `givens` (< 0: none).  sr: the halo buffer is filled (and, from fused_halo, exchanged).
+void launch_head(const FgmresRun &r, int j, double *w, int givens, const k::SendRanges *sr, const int32_t *done, double *wl)
+{
+    spk_ctx *c = r.c;
+    if (r.p.schur)
+        k::fused_head(r.Vj(j), r.nrmbuf(j + 1), r.w1side, c->dinv.p, r.p.bdp, r.ld, c->shat.p, c->gram.p, c->schur_fact, r.nl,
+                      r.m, r.Zj(j), w, c->ka, givens, r.dotsbuf(j + 1), done, r.s, sr, r.p.bpk, wl);
+    else
+        k::fused_head(r.Vj(j), r.nrmbuf(j + 1), nullptr, c->dinv.p, nullptr, r.ld, nullptr, nullptr, SPK_SCHUR_LOWER, r.nl, 0,
+                      r.Zj(j), nullptr, c->ka, givens, r.dotsbuf(j + 1), done, r.s, sr);
+}
+
+// Forms 5, 6 and 7: product and orthogonalisation of iteration loc.  Returns true when the cycle ran as one launch.
+bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *done)
+{
+    spk_ctx *c = r.c;
+    const bool schur = r.p.schur;
+    double *w = r.Vj(loc + 1), *db = r.dotsbuf(loc), *nb = r.nrmbuf(loc);
+    if (loc == 0) {
+        // first iteration of a cycle: the classic head on the normalised r, then the plain product
+        k::SendRanges sr = c->send_ranges;
+        const bool inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
+        launch_head(r, 0, w, -1, sr.n > 0 ? &sr : nullptr, done, r.wl(0));
+        product(r, r.Zj(0), w, inhead, schur, done);
+    }
+    if (r.p.resident) {
+        // form 6: the rest of the cycle is ONE launch, iterations 0 .. mk-1 with the basis in registers
+        k::ResidentArgs a{};
+        a.mk = r.mk; a.m = schur ? r.m : 0; a.packed = r.p.bpk; a.fact = schur ? c->schur_fact : SPK_SCHUR_LOWER;
+        a.lam_in_dot = r.lam_in_dot; a.nl = r.nl; a.ld = r.ld; a.err = c->errw.p; a.ticks = c->fin_ticks;
+        a.V0 = r.Vj(0); a.V1 = r.Vj(1); a.Z = r.Z; a.dinv = c->dinv.p; a.bd = r.p.bdp; a.ldb = r.ld;
+        a.shat = c->shat.p; a.gram = c->gram.p; a.P = c->res_P.p; a.ka = c->ka; a.sc_out = c->basis_sc.p;
+        if (c->comm->size() > 1) {
+            // the launch's mk + 1 all-reduces and mk - 1 halo exchanges: consecutive sequence numbers, reserved now
+            a.sr0 = c->send_ranges;
+            a.sr1 = c->send_ranges;
+            if (!c->comm->resident_plan(r.mk + 1, c->peers.empty() ? 0 : r.mk - 1, a.ar, a.sr0, a.sr1, c->xghost.p))
+                fail(SPK_ERR_COMM, "fgmres: the communicator cannot carry a resident cycle (agreed at set-up, refused now)");
+            if (c->peers.empty()) a.sr0.n = a.sr1.n = 0;
+            if (c->n_ghost > 0) a.od = c->offdiag();
+        }
+        if (!k::cycle_resident(c->Adict, c->num_cus, a, done, r.s)) fail(SPK_ERR_STATE, "fgmres: resident cycle kernel refused its shape");
+        return true;
+    }
+    // raw inner products of the un-normalised basis with w~ (and B D w~); scaled where they are consumed
+    // (form 7: inside the launch of kernel B, below -- except behind the last iteration of a cycle)
+    const bool gs = r.p.gsf && loc + 1 < r.mk;
+    if (!gs) {
+        const bool one = loc + 1 + r.m <= 40, spl = r.p.bpk && one;
+        const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + (schur ? r.m : 0), k::kStatArDots) : k::PeerAR{};
+        k::mdot(r.V, r.ld, loc + 1, w, r.N, r.n_dot, c->fin(db, ar), done, r.s, schur ? (spl ? c->bdpk.p : c->bd.p) : nullptr,
+                schur ? r.m : 0, spl ? 1 : 0);
+        if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + (schur ? r.m : 0), r.s);
+    }
+    const k::PeerAR ar2 = c->comm->fused_allreduce(1, k::kStatArNorm);
+    k::IterB b{};
+    b.V = r.V; b.ldv = r.ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
+    b.w = w; b.dinv = c->dinv.p; b.bd = r.p.bdp; b.ldb = r.ld; b.shat = c->shat.p; b.gram = c->gram.p;
+    b.fact = schur ? c->schur_fact : SPK_SCHUR_LOWER;
+    b.nl = r.nl; b.m = r.m; b.packed = r.p.bpk;
+    b.zun = r.Zj(loc + 1); b.c = schur ? r.Vj(loc + 2) : nullptr; b.wl_in = r.wl(loc); b.wl_out = r.wl(loc + 1);
+    b.lam_in_dot = r.lam_in_dot;
+    b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
+    b.sc = c->basis_sc.p; b.hbuf = r.sm2; b.ka = c->ka; b.loc = loc;
+    // ||w'||^2 is left as one partial per workgroup: the rider of the product launch reduces it (and all-reduces
+    // it, peer-store) beside the row tiles -- the product of an un-normalised vector does not need the norm.
+    // (Not with an all-reduce that is a launch of its own, nor behind the last iteration of a cycle.)
+    const bool defer = loc + 1 < r.mk && (c->comm->size() == 1 || ar2.P);
+    b.defer_fin = defer ? 1 : 0; b.done = done;
+    k::SendRanges sr = c->send_ranges;
+    const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
+    if (sr.n > 0) b.sr = sr;
+    int fin_n;
+    if (gs) {
+        k::GsArgs g{};
+        g.V2 = schur ? (r.p.bpk ? c->bdpk.p : c->bd.p) : nullptr;
+        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk;
+        g.n2 = (r.N + 1) / 2; g.n_dot = r.n_dot;
+        g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
+        g.out = db;
+        g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
+        g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
+        g.fe = k::FinErr{c->errw.p, c->fin_ticks};
+        fin_n = k::gs_fused(b, g, r.s);
+        ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
+    } else {
+        fin_n = k::iter_maxpy_uhead(b, r.s);
+    }
+    if (!ar2.P && !defer) c->comm->allreduce_sum(nb, 1, r.s);
+    // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
+    k::GivensRider gr{c->ka, loc, r.sm2, nb, c->basis_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
+                      k::FinErr{c->errw.p, c->fin_ticks}, defer ? ar2 : k::PeerAR{}};
+    if (loc + 1 < r.mk) product(r, r.Zj(loc + 1), r.Vj(loc + 2), inb, schur, done, &gr);
+    else cs.pend_h = r.sm2, cs.pend_n = nb, cs.pend_loc = loc;   // no product behind it: the step runs in the cycle-end launch
+    return false;
+}
+
+// w = K z_j on the head paths: the head kernel (unless the previous MAXPY ran it), then the A product onto it
+void head_product(const FgmresRun &r, CycleState &cs, int loc, double *w, const int32_t *done)
+{
+    spk_ctx *c = r.c;
+    bool inhead = cs.prev_inhead;
+    if (!cs.head_done) {
+        k::SendRanges sr = c->send_ranges;
+        inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);   // the head does the whole exchange ...
+        // ... or, Schur, fills the packed halo buffer (the Jacobi path's op_mult gathers itself)
+        launch_head(r, loc, w, r.p.big ? -1 : loc - 1, sr.n > 0 && (r.p.schur || inhead) ? &sr : nullptr, done, nullptr);
+        cs.last = r.p.big ? -1 : loc;
+        if (r.p.schur && r.p.orth == FgmresPlan::kOrthSingle) k::copy_small(w + r.nl, r.wl(loc), r.m, done, r.s);
+    }
+    if (r.p.schur) product(r, r.Zj(loc), w, inhead, true, done);
+    else op_mult(c, r.Zj(loc), w, done, inhead);    // w = A z_j (halo inside, unless the head kernel did it)
+}
+
+// KSPGMRESModifiedGramSchmidtOrthogonalization: one dot + one axpy per basis vector
+void orth_mgs(const FgmresRun &r, int loc, double *w, double *db, double *nb, const int32_t *done)
+{
+    spk_ctx *c = r.c;
+    for (int j = 0; j <= loc; ++j) {
+        k::mdot(r.Vj(j), r.ld, 1, w, r.N, r.n_dot, c->fin(db + j), done, r.s);
+        c->comm->allreduce_sum(db + j, 1, r.s);
+        const bool lastv = j == loc;
+        k::maxpy(r.Vj(j), r.ld, 1, nullptr, db + j, -1.0, w, r.N, r.n_dot, c->fin(lastv ? nb : nullptr), done, r.s,
+                 lastv ? r.p.bdp : nullptr, r.ld, r.nl, r.m, lastv && r.p.schur ? r.w1side : nullptr, nullptr, r.p.bpk);
+    }
+    c->comm->allreduce_sum(nb, r.p.nn, r.s);
+}
+
+// single reduction: the MAXPY of iteration loc also runs the head of iteration loc+1 and the Givens step of iteration
+// loc (k::maxpy_head): three launches and one reduction per iteration
+void orth_single(const FgmresRun &r, CycleState &cs, int loc, double *w, double *db, double *nb, const int32_t *done)
+{
+    spk_ctx *c = r.c;
+    const int m = r.m;
+    const k::PeerAR ar = loc + 1 + m <= 40 ? c->comm->fused_allreduce(loc + 2 + m, k::kStatArDots) : k::PeerAR{};
+    // B D w from the same pass: the dense rows, or two halves per parity-interleaved plane
+    const bool spl = r.p.bpk && loc + 1 + m <= 40;
+    k::mdot(r.V, r.ld, loc + 1, w, r.N, r.n_dot, c->fin(db, ar), done, r.s, spl ? c->bdpk.p : c->bd.p, m, spl ? 1 : 0);
+    if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + m, r.s);
+    if (loc + 1 < r.mk) {
+        k::SendRanges sr = c->send_ranges;
+        cs.prev_inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
+        // Schur: the packed halo buffer is filled even without the peer backend; Jacobi: op_mult gathers
+        const k::SendRanges *srp = sr.n > 0 && (r.p.schur || cs.prev_inhead) ? &sr : nullptr;
+        k::maxpy_head(r.V, r.ld, loc + 1, db, c->ka.tb, nb, w, c->dinv.p, r.p.bdp, r.ld, c->shat.p, c->gram.p,
+                      r.p.schur ? c->schur_fact : SPK_SCHUR_LOWER, r.nl, m, r.Zj(loc + 1), r.p.schur ? r.Vj(loc + 2) : nullptr,
+                      r.w1side, r.wl(loc), r.wl(loc + 1), c->ka, loc, done, r.s, srp, r.p.bpk);
+        cs.head_done = true, cs.last = -1;  // its Givens step is done
+    } else {
+        k::PythArgs py{m, db, c->ka.tb, nb};
+        k::maxpy(r.V, r.ld, loc + 1, nullptr, db, -1.0, w, r.N, r.n_dot, c->fin(nullptr), done, r.s, nullptr, r.ld, r.nl, m,
+                 r.w1side, &py);
+        cs.head_done = false, cs.last = loc;
+    }
+}
+
+// One classical Gram-Schmidt pass, in chunks: h = V^T w into dots (every product with the SAME w), w -= V h, ||w||^2
+// (+ B D w') into nrm.  peer_ar: the all-reduces may ride in the finish of the two kernels (peer-store backend)
+void cgs_pass(const FgmresRun &r, int loc, double *w, double *dots, double *nrm, const int32_t *gate, bool peer_ar)
+{
+    spk_ctx *c = r.c;
+    const int chunk = r.p.chunk;
+    const k::PeerAR ar1 = peer_ar && loc + 1 <= 40 ? c->comm->fused_allreduce(loc + 2, k::kStatArDots) : k::PeerAR{};
+    for (int v0 = 0; v0 <= loc; v0 += chunk)
+        k::mdot(r.Vj(v0), r.ld, std::min(chunk, loc + 1 - v0), w, r.N, r.n_dot, c->fin(dots + v0, ar1), gate, r.s);
+    if (!ar1.P) c->comm->allreduce_sum(dots, loc + 2, r.s);
+    const k::PeerAR ar2 = peer_ar ? c->comm->fused_allreduce(r.p.nn, k::kStatArNorm) : k::PeerAR{};
+    for (int v0 = 0; v0 <= loc; v0 += chunk) {
+        const bool lastc = v0 + chunk > loc;
+        k::maxpy(r.Vj(v0), r.ld, std::min(chunk, loc + 1 - v0), nullptr, dots + v0, -1.0, w, r.N, r.n_dot,
+                 c->fin(lastc ? nrm : nullptr, ar2), gate, r.s, lastc ? r.p.bdp : nullptr, r.ld, r.nl, r.m,
+                 lastc && r.p.schur ? r.w1side : nullptr, nullptr, r.p.bpk);
+    }
+    if (!ar2.P) c->comm->allreduce_sum(nrm, r.p.nn, r.s);
+}
+
+// classical Gram-Schmidt, and the second pass on the device's own decision (-ksp_gmres_cgs_refinement_type; PETSc's
+// ||w'|| < ||h|| test for ifneeded)
+void orth_cgs(const FgmresRun &r, int loc, double *w, double *db, double *nb, const int32_t *done)
+{
+    cgs_pass(r, loc, w, db, nb, done, !r.p.big);
+    if (r.p.refine == SPK_REFINE_NEVER) return;
+    double *db2 = r.p.big ? r.c->bigdots.p + (size_t)r.mk + 4 : r.sm2;
+    k::krylov_refine_decide(r.c->ka, loc, r.p.refine, db, nb, db2, r.s);
+    cgs_pass(r, loc, w, db2, r.nrm2b, &r.c->kst.p->skip_refine, false);
+    k::krylov_refine_merge(r.c->ka, loc, db, db2, nb, r.nrm2b, r.p.nn, r.s);
+}
+}  // namespace
+
+void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_result *res, double *history,
+            int32_t history_cap)
+{
+    require_setup(c, "fgmres");
+    if (o.orthog != SPK_ORTHOG_CGS && o.orthog != SPK_ORTHOG_MGS) fail(SPK_ERR_ARG, "fgmres: unknown orthogonalisation %d", o.orthog);
+    if (o.cgs_refine < SPK_REFINE_NEVER || o.cgs_refine > SPK_REFINE_ALWAYS) fail(SPK_ERR_ARG, "fgmres: unknown cgs_refine %d", o.cgs_refine);
+    ensure_krylov(c, o);
+    const FgmresPlan p = plan_fgmres(c, o);
+    c->last_form = p.form;
+    c->last_single = p.orth == FgmresPlan::kOrthSingle ? 1 : 0;
+    hipStream_t s = c->stream;
+    const int mk = o.restart;
+    const int64_t N = (int64_t)c->n_local + c->m, ld = c->ld;
+    const int64_t n_dot = (int64_t)c->n_local + (c->comm->rank() == 0 ? c->m : 0);
+    const int32_t *done = &c->kst.p->done;
+    const double *inv_tt = &c->kst.p->inv_tt;
+    double *sm = c->small.p, *bn2 = sm + 384;   // small[]: FgmresRun's parity sets at 0..255, ||b||^2 at 384
+    const FgmresRun r{c, p, s, mk, c->m, c->comm->rank() == 0 ? 1 : 0, c->n_local, N, ld, n_dot,
+                      c->V.p, c->Z.p, sm, sm + 256, sm + 320, c->y1tmp.p + 48};
+    const bool un3 = p.product == FgmresPlan::kUn3;
+
+    SPK_HIP(hipStreamSynchronize(s));
+    const auto t0 = std::chrono::steady_clock::now();
+
+    // ||b|| for KSPConvergedDefault
+    k::sqnorm(b, n_dot, c->fin(bn2), nullptr, s);
+    c->comm->allreduce_sum(bn2, 1, s);
+    k::krylov_init(c->ka, o, bn2, s);
+
+    // initial residual into V0
+    if (o.guess_nonzero) op_mult(c, x, c->tmp.p, nullptr);
+    else SPK_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, s));
+    SPK_HIP(hipMemcpyAsync(r.Vj(0), b, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
+    if (o.guess_nonzero) k::axpby(-1.0, c->tmp.p, 1.0, r.Vj(0), N, nullptr, s);
+    ensure_plan_buffers(c, p, mk);
+
+    c->ka.tentative = p.orth == FgmresPlan::kOrthSingle ? 1 : 0;
     KrylovState st{};
-    int32_t errword = 0;
     int cycles = 0;
     // The solve's state reaches the host through pinned memory written by krylov_cycle_begin (no copy on the stream); the
     // host waits for the event behind that launch only after it has enqueued the start of the cycle (kAhead iterations),
@@ -1374,40 +1642,31 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     auto read_state = [&]() {
         SPK_HIP(hipEventSynchronize(c->state_ev));
         st = *ps;
-        errword = pe[0];
         pend_check = false;
         if (pe[1]) c->comm->check(s);         // a peer that never arrived: SPK_ERR_COMM instead of a wrong answer
-        if (errword) c->check_device_error();  // a reduction that timed out: SPK_ERR_HIP, not KSP_DIVERGED_NANORINF
+        if (pe[0]) c->check_device_error();     // a reduction that timed out: SPK_ERR_HIP, not KSP_DIVERGED_NANORINF
         return st.done != 0;
     };
     for (;;) {
         // ---- cycle start: ||r|| (parity slot 1 = "iteration -1"), convergence test, v0 = r/||r|| ----
         // (from the second cycle on the previous cycle's end has formed r = b - K x and these sums in one pass)
         if (cycles == 0) {
-            if (fused) k::sqnorm_bd(Vj(0), N, n_dot, c->bd.p, ld, nl, m, w1side, c->fin(nrmbuf(1)), done, s);
-            else k::sqnorm(Vj(0), n_dot, c->fin(nrmbuf(1)), done, s);
+            if (p.schur) k::sqnorm_bd(r.Vj(0), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s);
+            else k::sqnorm(r.Vj(0), n_dot, c->fin(r.nrmbuf(1)), done, s);
         }
-        c->comm->allreduce_sum(nrmbuf(1), nn, s);
+        c->comm->allreduce_sum(r.nrmbuf(1), p.nn, s);
         // (the kernel also reports the state it finds / leaves into pinned memory: the verdict on the PREVIOUS cycle and,
         // through its own convergence test on the true residual, on the solve -- read by the host at loc == kAhead)
         const k::StateReport report{ps, pe, c->errw.p, c->comm->error_dev()};
-        k::krylov_cycle_begin(c->ka, nrmbuf(1), s, (single || un3) ? c->ka.tb : nullptr, m,
+        k::krylov_cycle_begin(c->ka, r.nrmbuf(1), s, (un3 || p.orth == FgmresPlan::kOrthSingle) ? c->ka.tb : nullptr, r.m,
                               un3 ? c->basis_sc.p : nullptr, &report);
         SPK_HIP(hipEventRecord(c->state_ev, s));
         pend_check = true;
-        if (!head) k::scale_dev(Vj(0), N, inv_tt, done, s);
+        if (!p.head) k::scale_dev(r.Vj(0), N, inv_tt, done, s);
 
-        bool stop = false;
-        int last = -1;  // last iteration of this cycle whose Givens step is still pending (fused path)
+        CycleState cs;
         int64_t its_cap = INT64_MAX;   // iterations this cycle may still run before -ksp_max_it (known once the report is read)
-        int pend_loc = -1;   // ... handed to the cycle-end launch (its Hessenberg column and norm)
-        const double *pend_h = nullptr;
-        double *pend_n = nullptr;
-        // single-reduction mode: the MAXPY of iteration loc also runs the head of iteration loc+1 and the
-        // Givens step of iteration loc (k::maxpy_head): three launches and one reduction per iteration
-        bool head_done = false, prev_inhead = false;
-        auto wl = [&](int p) { return sm + 400 + (p & 1) * 8; };  // lambda entries of w, side copies
-        for (int loc = 0; loc < mk && !stop; ++loc) {
+        for (int loc = 0; loc < mk && !cs.stop; ++loc) {
             if (pend_check && loc == kAhead) {
                 if (read_state()) {   // the previous cycle ended the solve: what was enqueued of this one is gated off
                     finished = true;  // on the device
@@ -1419,280 +1678,49 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
             // (gated) launches beyond it
             if (loc >= its_cap) break;
             const int32_t *done = &c->kst.p->skip_iter;  // the gate of everything inside an iteration
-            double *w = Vj(loc + 1);
-            double *db = big ? c->bigdots.p : dotsbuf(loc), *nb = nrmbuf(loc);
+            double *w = r.Vj(loc + 1);
+            double *db = p.big ? c->bigdots.p : r.dotsbuf(loc), *nb = r.nrmbuf(loc);
             if (un3) {
-                // the product K z~ of a vector (halo, then diagonal and off-rank columns in one kernel), either format
-                auto product = [&](const double *zvec, double *wvec, bool halo_done, const k::GivensRider *rider = nullptr) {
-                    k::SendRanges srp = c->send_ranges;
-                    if (!c->peers.empty() && !halo_done) {
-                        if (srp.n == 0) k::gather(zvec, c->send_idx.p, c->send_off.back(), c->send_buf.p, done, s);
-                        c->comm->exchange(c->send_buf.p, c->peers, c->send_off, c->xghost.p, c->recv_off, s);
-                    }
-                    const k::OffDiag od = c->offdiag();
-                    const k::OffDiag *odp = c->n_ghost > 0 ? &od : nullptr;
-                    a_mult(c, zvec, wvec, nullptr, nullptr, done, fused, odp, rider);
-                };
-                if (loc == 0) {
-                    // first iteration of a cycle: the classic head on the normalised r, then the plain product
-                    k::SendRanges sr0 = c->send_ranges;
-                    const bool packed = sr0.n > 0;
-                    const bool inhead = packed && c->comm->fused_halo(sr0, c->xghost.p);
-                    if (fused)
-                        k::fused_head(Vj(0), nrmbuf(1), w1side, c->dinv.p, bdp, ld, c->shat.p, c->gram.p, c->schur_fact, nl, m,
-                                      Zj(0), w, c->ka, -1, dotsbuf(1), done, s, packed ? &sr0 : nullptr, bpk, wl(0));
-                    else
-                        k::fused_head(Vj(0), nrmbuf(1), nullptr, c->dinv.p, nullptr, ld, nullptr, nullptr, SPK_SCHUR_LOWER, nl, 0,
-                                      Zj(0), nullptr, c->ka, -1, dotsbuf(1), done, s, packed ? &sr0 : nullptr);
-                    product(Zj(0), w, inhead);
-                }
-                if (resident) {
-                    // the rest of the cycle is ONE launch: iterations 0 .. mk-1 with the basis in registers
-                    k::ResidentArgs r{};
-                    r.mk = mk; r.m = fused ? m : 0; r.packed = bpk; r.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
-                    r.lam_in_dot = lam_in_dot; r.nl = nl; r.ld = ld;
-                    r.V0 = Vj(0); r.V1 = Vj(1); r.Z = Z; r.dinv = c->dinv.p; r.bd = bdp; r.ldb = ld;
-                    r.shat = c->shat.p; r.gram = c->gram.p; r.P = c->res_P.p; r.ka = c->ka; r.sc_out = c->basis_sc.p;
-                    r.err = c->errw.p; r.ticks = c->fin_ticks;
-                    r.sr0 = k::SendRanges{};
-                    r.sr1 = k::SendRanges{};
-                    if (res_multi) {
-                        // the launch's mk + 1 all-reduces and mk - 1 halo exchanges: consecutive sequence numbers, reserved now
-                        r.sr0 = c->send_ranges;
-                        r.sr1 = c->send_ranges;
-                        if (!c->comm->resident_plan(mk + 1, c->peers.empty() ? 0 : mk - 1, r.ar, r.sr0, r.sr1, c->xghost.p))
-                            fail(SPK_ERR_COMM, "fgmres: the communicator cannot carry a resident cycle (agreed at set-up, refused now)");
-                        if (c->peers.empty()) r.sr0.n = r.sr1.n = 0;
-                        if (c->n_ghost > 0) r.od = c->offdiag();
-                    }
-                    if (!k::cycle_resident(c->Adict, c->num_cus, r, done, s)) fail(SPK_ERR_STATE, "fgmres: resident cycle kernel refused its shape");
-                    break;
-                }
-                // raw inner products of the un-normalised basis with w~ (and B D w~); scaled where they are consumed
-                // (form 7: inside the launch of kernel B, below -- except behind the last iteration of a cycle)
-                const bool gs = gsf && loc + 1 < mk;
-                if (!gs) {
-                    const bool one = loc + 1 + m <= 40;
-                    const bool spl = bpk && one;
-                    const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + (fused ? m : 0), k::kStatArDots) : k::PeerAR{};
-                    k::mdot(V, ld, loc + 1, w, N, n_dot, c->fin(db, ar), done, s, fused ? (spl ? c->bdpk.p : c->bd.p) : nullptr,
-                            fused ? m : 0, spl ? 1 : 0);
-                    if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + (fused ? m : 0), s);
-                }
-                const k::PeerAR ar2 = c->comm->fused_allreduce(1, k::kStatArNorm);
-                k::IterB b{};
-                b.V = V; b.ldv = ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
-                b.w = w; b.dinv = c->dinv.p; b.bd = bdp; b.ldb = ld; b.shat = c->shat.p; b.gram = c->gram.p;
-                b.fact = fused ? c->schur_fact : SPK_SCHUR_LOWER;
-                b.nl = nl; b.m = m; b.packed = bpk;
-                b.zun = Zj(loc + 1); b.c = fused ? Vj(loc + 2) : nullptr; b.wl_in = wl(loc); b.wl_out = wl(loc + 1);
-                b.lam_in_dot = lam_in_dot;
-                b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
-                b.sc = c->basis_sc.p; b.hbuf = sm2; b.ka = c->ka; b.loc = loc;
-                // ||w'||^2 is left as one partial per workgroup: the rider of the product launch reduces it (and all-reduces
-                // it, peer-store) beside the row tiles -- the product of an un-normalised vector does not need the norm.
-                // (Not with an all-reduce that is a launch of its own, nor behind the last iteration of a cycle.)
-                const bool defer = loc + 1 < mk && (c->comm->size() == 1 || ar2.P);
-                b.defer_fin = defer ? 1 : 0;
-                k::SendRanges sr = c->send_ranges;
-                const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
-                if (sr.n > 0) b.sr = sr;
-                b.done = done;
-                int fin_n;
-                if (gs) {
-                    k::GsArgs g{};
-                    g.V2 = fused ? (bpk ? c->bdpk.p : c->bd.p) : nullptr;
-                    g.cnt = loc + 1 + (fused ? m : 0);
-                    g.split = bpk;
-                    g.n2 = (N + 1) / 2; g.n_dot = n_dot;
-                    g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
-                    g.out = db;
-                    g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
-                    g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
-                    g.fe = k::FinErr{c->errw.p, c->fin_ticks};
-                    fin_n = k::gs_fused(b, g, s);
-                    ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
-                } else {
-                    fin_n = k::iter_maxpy_uhead(b, s);
-                }
-                if (!ar2.P && !defer) c->comm->allreduce_sum(nb, 1, s);
-                // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
-                k::GivensRider gr{c->ka, loc, sm2, nb, c->basis_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
-                                  k::FinErr{c->errw.p, c->fin_ticks}, defer ? ar2 : k::PeerAR{}};
-                if (loc + 1 < mk) product(Zj(loc + 1), Vj(loc + 2), inb, &gr);
-                else pend_h = sm2, pend_n = nb, pend_loc = loc;   // no product behind it: the step runs in the cycle-end launch
-                last = -1;
-            } else if (fused) {
-                // v_j = w'/||w'|| (in place), z_j = M^-1 v_j, w = B^T z1 (u part) | B z0 (lambda part);
-                // workgroup 0 also runs the Givens step of iteration loc-1
-                k::SendRanges sr = c->send_ranges;
-                const bool packed = sr.n > 0;   // head fills the halo buffer itself ...
-                bool inhead = prev_inhead;
-                if (!head_done) {
-                    inhead = packed && c->comm->fused_halo(sr, c->xghost.p);   // ... or does the whole exchange
-                    k::fused_head(Vj(loc), nrmbuf(loc + 1), w1side, c->dinv.p, bdp, ld, c->shat.p, c->gram.p,
-                                  c->schur_fact, nl, m, Zj(loc), w, c->ka, big ? -1 : loc - 1, dotsbuf(loc + 1), done, s,
-                                  packed ? &sr : nullptr, bpk);
-                    last = big ? -1 : loc;
-                    if (single) k::copy_small(w + nl, wl(loc), m, done, s);
-                }
-                // w += A z0 (halo exchange, then diagonal and off-rank columns in ONE kernel)
-                const k::OffDiag od = c->offdiag();
-                if (!c->peers.empty() && !inhead) {
-                    if (!packed) k::gather(Zj(loc), c->send_idx.p, c->send_off.back(), c->send_buf.p, done, s);
-                    c->comm->exchange(c->send_buf.p, c->peers, c->send_off, c->xghost.p, c->recv_off, s);
-                }
-                a_mult(c, Zj(loc), w, nullptr, nullptr, done, true, c->n_ghost > 0 ? &od : nullptr);
-            } else if (fusedj) {
-                bool inhead = prev_inhead;
-                if (!head_done) {
-                    k::SendRanges sr = c->send_ranges;
-                    inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
-                    k::fused_head(Vj(loc), nrmbuf(loc + 1), nullptr, c->dinv.p, nullptr, ld, nullptr, nullptr, SPK_SCHUR_LOWER,
-                                  nl, 0, Zj(loc), nullptr, c->ka, big ? -1 : loc - 1, dotsbuf(loc + 1), done, s, inhead ? &sr : nullptr);
-                    last = big ? -1 : loc;
-                }
-                op_mult(c, Zj(loc), w, done, inhead);    // w = A z_j (halo inside, unless the head kernel did it)
+                if (un3_iteration(r, cs, loc, done)) break;   // (form 6: the whole cycle was one launch)
             } else {
-                op_pc_apply(c, Vj(loc), Zj(loc), done);  // z_j = M^-1 v_j
-                op_mult(c, Zj(loc), w, done, false, true);   // w = K z_j (B^T z_1 of a general block: as PCApply left it)
-            }
-            if (un3) {
-                // (orthogonalisation done above, inside the launches)
-            } else if (o.orthog == SPK_ORTHOG_MGS) {
-                // KSPGMRESModifiedGramSchmidtOrthogonalization: one dot + one axpy per basis vector
-                for (int j = 0; j <= loc; ++j) {
-                    k::mdot(Vj(j), ld, 1, w, N, n_dot, c->fin(db + j), done, s);
-                    c->comm->allreduce_sum(db + j, 1, s);
-                    const bool lastv = j == loc;
-                    k::maxpy(Vj(j), ld, 1, nullptr, db + j, -1.0, w, N, n_dot, c->fin(lastv ? nb : nullptr), done, s,
-                             lastv ? bdp : nullptr, ld, nl, m, lastv && fused ? w1side : nullptr, nullptr, bpk);
-                }
-                c->comm->allreduce_sum(nb, nn, s);
-            } else if (single) {
-                const k::PeerAR ar = loc + 1 + m <= 40 ? c->comm->fused_allreduce(loc + 2 + m, k::kStatArDots) : k::PeerAR{};
-                // B D w from the same pass: the dense rows, or two halves per parity-interleaved plane
-                const bool spl = bpk && loc + 1 + m <= 40;
-                k::mdot(V, ld, loc + 1, w, N, n_dot, c->fin(db, ar), done, s, spl ? c->bdpk.p : c->bd.p, m, spl ? 1 : 0);
-                if (!ar.P) c->comm->allreduce_sum(db, loc + 2 + m, s);
-                if (loc + 1 < mk) {
-                    k::SendRanges sr = c->send_ranges;
-                    prev_inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
-                    // Schur: the packed halo buffer is filled even without the peer backend; Jacobi: op_mult gathers
-                    const k::SendRanges *srp = sr.n > 0 && (fused || prev_inhead) ? &sr : nullptr;
-                    k::maxpy_head(V, ld, loc + 1, db, c->ka.tb, nb, w, c->dinv.p, bdp, ld, c->shat.p, c->gram.p,
-                                  fused ? c->schur_fact : SPK_SCHUR_LOWER, nl, m, Zj(loc + 1), fused ? Vj(loc + 2) : nullptr,
-                                  w1side, wl(loc), wl(loc + 1), c->ka, loc, done, s, srp, bpk);
-                    head_done = true;
-                    last = -1;  // its Givens step is done
+                if (p.product == FgmresPlan::kStep) {
+                    op_pc_apply(c, r.Vj(loc), r.Zj(loc), done);     // z_j = M^-1 v_j
+                    op_mult(c, r.Zj(loc), w, done, false, true);   // w = K z_j (B^T z_1 of a general block: as PCApply left it)
                 } else {
-                    k::PythArgs py{m, db, c->ka.tb, nb};
-                    k::maxpy(V, ld, loc + 1, nullptr, db, -1.0, w, N, n_dot, c->fin(nullptr), done, s, nullptr, ld, nl, m,
-                             w1side, &py);
-                    head_done = false;
-                    last = loc;
+                    head_product(r, cs, loc, w, done);
                 }
-            } else if (big) {
-                // classical Gram-Schmidt in chunks: every inner product is taken with the SAME w before any update
-                for (int v0 = 0; v0 <= loc; v0 += 40) {
-                    const int cnt = std::min(40, loc + 1 - v0);
-                    k::mdot(Vj(v0), ld, cnt, w, N, n_dot, c->fin(db + v0), done, s);
+                if (p.orth == FgmresPlan::kOrthMgs) orth_mgs(r, loc, w, db, nb, done);
+                else if (p.orth == FgmresPlan::kOrthSingle) orth_single(r, cs, loc, w, db, nb, done);
+                else orth_cgs(r, loc, w, db, nb, done);
+                if (!p.head || p.big) {
+                    // Hessenberg column, Givens, convergence -- on the device; then v_{j+1} = w / ||w|| (the head kernel
+                    // of the next iteration does that scaling where there is one)
+                    k::krylov_givens(c->ka, loc, db, nb, s);
+                    if (!p.head) k::scale_dev(w, N, inv_tt, done, s);
                 }
-                c->comm->allreduce_sum(db, loc + 2, s);
-                for (int v0 = 0; v0 <= loc; v0 += 40) {
-                    const int cnt = std::min(40, loc + 1 - v0);
-                    const bool lastc = v0 + 40 > loc;
-                    k::maxpy(Vj(v0), ld, cnt, nullptr, db + v0, -1.0, w, N, n_dot, c->fin(lastc ? nb : nullptr), done, s,
-                             lastc ? bdp : nullptr, ld, nl, m, lastc && fused ? w1side : nullptr, nullptr, bpk);
-                }
-                c->comm->allreduce_sum(nb, nn, s);
-                if (o.cgs_refine != SPK_REFINE_NEVER) {
-                    // -ksp_gmres_cgs_refinement_type on a long restart: the second pass in the same chunks, on the device's
-                    // own decision (PETSc's ||w'|| < ||h|| test for ifneeded)
-                    const int32_t *skip = &c->kst.p->skip_refine;
-                    double *db2 = c->bigdots.p + (size_t)mk + 4;
-                    k::krylov_refine_decide(c->ka, loc, o.cgs_refine, db, nb, db2, s);
-                    for (int v0 = 0; v0 <= loc; v0 += 40) {
-                        const int cnt = std::min(40, loc + 1 - v0);
-                        k::mdot(Vj(v0), ld, cnt, w, N, n_dot, c->fin(db2 + v0), skip, s);
-                    }
-                    c->comm->allreduce_sum(db2, loc + 2, s);
-                    for (int v0 = 0; v0 <= loc; v0 += 40) {
-                        const int cnt = std::min(40, loc + 1 - v0);
-                        const bool lastc = v0 + 40 > loc;
-                        k::maxpy(Vj(v0), ld, cnt, nullptr, db2 + v0, -1.0, w, N, n_dot, c->fin(lastc ? nrm2b : nullptr), skip, s,
-                                 lastc ? bdp : nullptr, ld, nl, m, lastc && fused ? w1side : nullptr, nullptr, bpk);
-                    }
-                    c->comm->allreduce_sum(nrm2b, nn, s);
-                    k::krylov_refine_merge(c->ka, loc, db, db2, nb, nrm2b, nn, s);
-                }
-            } else {
-                // classical Gram-Schmidt: h = V^T w (one pass), w -= V h (+ ||w||^2 [+ B D w'] in the same pass)
-                // across ranks the all-reduces ride in the finish of the two kernels (peer-store backend)
-                const k::PeerAR ar1 = loc + 1 <= 40 ? c->comm->fused_allreduce(loc + 2, k::kStatArDots) : k::PeerAR{};
-                k::mdot(V, ld, loc + 1, w, N, n_dot, c->fin(db, ar1), done, s);
-                if (!ar1.P) c->comm->allreduce_sum(db, loc + 2, s);
-                const k::PeerAR ar2 = c->comm->fused_allreduce(nn, k::kStatArNorm);
-                k::maxpy(V, ld, loc + 1, nullptr, db, -1.0, w, N, n_dot, c->fin(nb, ar2), done, s, bdp, ld, nl, m,
-                         fused ? w1side : nullptr, nullptr, bpk);
-                if (!ar2.P) c->comm->allreduce_sum(nb, nn, s);
-                if (o.cgs_refine != SPK_REFINE_NEVER) {
-                    // second pass on the device's own decision (-ksp_gmres_cgs_refinement_type)
-                    const int32_t *skip = &c->kst.p->skip_refine;
-                    k::krylov_refine_decide(c->ka, loc, o.cgs_refine, db, nb, sm2, s);
-                    k::mdot(V, ld, loc + 1, w, N, n_dot, c->fin(sm2), skip, s);
-                    c->comm->allreduce_sum(sm2, loc + 2, s);
-                    k::maxpy(V, ld, loc + 1, nullptr, sm2, -1.0, w, N, n_dot, c->fin(nrm2b), skip, s, bdp, ld, nl, m,
-                             fused ? w1side : nullptr, nullptr, bpk);
-                    c->comm->allreduce_sum(nrm2b, nn, s);
-                    k::krylov_refine_merge(c->ka, loc, db, sm2, nb, nrm2b, nn, s);
-                }
-            }
-            if (!head || big) {
-                // Hessenberg column, Givens, convergence -- on the device; then v_{j+1} = w / ||w|| (the head kernel of the
-                // next iteration does that scaling where there is one)
-                k::krylov_givens(c->ka, loc, db, nb, s);
-                if (!head) k::scale_dev(w, N, inv_tt, done, s);
             }
             if (o.check_every > 0 && (loc + 1) % o.check_every == 0 && loc + 1 < mk) {
                 SPK_HIP(hipMemcpyAsync(&st, c->kst.p, sizeof st, hipMemcpyDeviceToHost, s));
                 SPK_HIP(hipStreamSynchronize(s));
-                stop = st.done != 0 || st.skip_iter != 0;  // fused path: lags by one iteration, the iterate does not care
+                cs.stop = st.done != 0 || st.skip_iter != 0;  // head paths: lags by one iteration, the iterate does not care
             }
         }
         if (finished || (pend_check && read_state())) break;   // (second form: cycles shorter than kAhead iterations)
-        // fused path: the Givens step of the cycle's last iteration has no head kernel to ride on
-        if (head && last >= 0) pend_h = dotsbuf(last), pend_n = nrmbuf(last), pend_loc = last;
+        // head paths: the Givens step of the cycle's last iteration has no head kernel to ride on
+        if (p.head && cs.last >= 0) cs.pend_h = r.dotsbuf(cs.last), cs.pend_n = r.nrmbuf(cs.last), cs.pend_loc = cs.last;
         // ---- x += Z y (KSPFGMRESBuildSoln); always runs, count comes from the device ----
-        {
-            k::GivensRider pend{c->ka, pend_loc, pend_h, pend_n, nullptr, nullptr, 0, k::FinErr{nullptr, 0}, k::PeerAR{}};
-            k::krylov_cycle_end(c->ka, s, un3 ? c->basis_sc.p : nullptr, mk, pend_loc >= 0 ? &pend : nullptr);
-        }
-        k::maxpy(Z, ld, mk, loc_done, c->ka.nrs, 1.0, x, N, 0, c->fin(nullptr), nullptr, s);
+        const k::GivensRider pend{c->ka, cs.pend_loc, cs.pend_h, cs.pend_n, nullptr, nullptr, 0, k::FinErr{nullptr, 0}, k::PeerAR{}};
+        k::krylov_cycle_end(c->ka, s, un3 ? c->basis_sc.p : nullptr, mk, cs.pend_loc >= 0 ? &pend : nullptr);
+        k::maxpy(r.Z, ld, mk, &c->kst.p->loc_done, c->ka.nrs, 1.0, x, N, 0, c->fin(nullptr), nullptr, s);
         // ---- true residual for the next cycle (KSPFGMRESResidual); skipped once done ----
         op_mult(c, x, c->tmp.p, done);
         // r = b - K x into V0 together with ||r||^2 (and B D r) for the start of the next cycle
-        if (fused) k::sqnorm_bd(Vj(0), N, n_dot, c->bd.p, ld, nl, m, w1side, c->fin(nrmbuf(1)), done, s, b, c->tmp.p);
-        else k::sqnorm_sub(b, c->tmp.p, Vj(0), N, n_dot, c->fin(nrmbuf(1)), done, s);
+        if (p.schur) k::sqnorm_bd(r.Vj(0), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s, b, c->tmp.p);
+        else k::sqnorm_sub(b, c->tmp.p, r.Vj(0), N, n_dot, c->fin(r.nrmbuf(1)), done, s);
         ++cycles;
         SPK_HIP(hipGetLastError());  // a rejected launch inside the cycle surfaces here, not as a wrong answer
     }
-    SPK_HIP(hipStreamSynchronize(s));  // (a speculative start of a cycle that will not run drains as no-ops)
-    c->comm->check(s);          // what was raised after the last report (once per solve: blocking reads)
-    c->check_device_error();
-    const auto t1 = std::chrono::steady_clock::now();
-
-    res->its = st.its;
-    res->reason = st.reason;
-    res->rnorm = st.rnorm;
-    res->rnorm0 = st.rnorm0;
-    res->cycles = cycles;
-    res->solve_seconds = std::chrono::duration<double>(t1 - t0).count();
-    int32_t nh = std::min<int32_t>(st.its + 1, c->ka.hist_cap);
-    if (!history) nh = 0;
-    nh = std::min(nh, history_cap);
-    if (nh > 0) SPK_HIP(hipMemcpy(history, c->ka.hist, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost));
-    res->hist_len = nh;
+    finish_solve(c, st, cycles, t0, c->ka.hist, c->ka.hist_cap, res, history, history_cap);
 }
 
 }  // namespace spk

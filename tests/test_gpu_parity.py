@@ -369,6 +369,22 @@ def test_long_restart_jacobi_head_path(spk, oracle):
         assert relerr(xa, xb) < 1e-7
 
 
+def test_restart_63_single_reduce_jacobi_head_path(spk, oracle):
+    """restart 63 on the Jacobi head path (K = A) is a long restart: single_reduce = 1 runs the two-reduction
+    fallback there, with the Givens step a launch of its own, and reports so."""
+    A, f = spk.AssembleOperator_Laplace(40, 28)
+    with spk.Context(0) as c:
+        c.set_block(spk.BLOCK_A00, A)
+        c.pc_setup(spk.PC_JACOBI)
+        x, info = c.fgmres(f, restart=63, rtol=1e-10, max_it=4000, single_reduce=1)
+        assert c.iteration_form() == (1, 0)
+    xo, io = oracle.fgmres(A, f, pc_type=oracle.PC_JACOBI, restart=63, rtol=1e-10, max_it=4000)
+    assert info["reason"] == io["reason"] == 2 and abs(info["its"] - io["its"]) <= 2
+    k = min(len(info["history"]), len(io["history"]), 150) - 1
+    assert np.allclose(info["history"][:k], io["history"][:k], rtol=1e-5)
+    assert relerr(x, xo) < 1e-7
+
+
 def test_single_reduction_jacobi_head_path(spk, oracle):
     """The same single-reduction route on the Jacobi head path (K = A, the reference as written):
     ||w'||^2 = w.w - |h|^2, MAXPY + VecScale + PCApply_Jacobi + Givens in one launch."""
