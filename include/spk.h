@@ -255,6 +255,62 @@ int spk_pc_setup(spk_ctx *ctx, int pc_type, int schur_fact);
  * lower-precision A^-1 is legitimate).  sweeps = 0 (default) keeps the plain diag(A)^-1.
  * Call before spk_pc_setup. */
 int spk_pc_set_inner(spk_ctx *ctx, int sweeps, double omega);
+/* Smoothed-aggregation algebraic multigrid standing for A^-1 (PETSc: -pc_type gamg on K = A, or
+ * -fieldsplit_0_pc_type gamg inside the Schur fieldsplit).  One V-cycle per application: nu smoothing steps
+ * (Chebyshev with Jacobi inside, or damped-Jacobi Richardson) before and after the coarse-grid correction,
+ * R = P^T, the coarsest operator inverted exactly (dense, at most SPK_AMG_MAX_COARSE equations).  The hierarchy
+ * is built on the host at spk_pc_setup from the A00 block the context holds (Vanek's greedy three-phase
+ * aggregation over the bs x bs node graph -- not PETSc's MIS coarsening; see DESIGN.md "Algebraic multigrid").
+ * spk_pc_set_amg(ctx, &o) before spk_pc_setup switches it on, NULL switches it off; SPK_PC_JACOBI then means
+ * M^-1 = one V-cycle on A (no B block), SPK_PC_SCHUR takes the V-cycle wherever it takes diag(A)^-1 (S^ stays
+ * diag(B diag(A)^-1 B^T)).  spk_fgmres runs it on the step-by-step path (spk_get_iteration_form reports -1).
+ * Out of scope, refused with SPK_ERR_UNSUPPORTED: more than one rank (at spk_pc_setup; the context stays usable),
+ * spk_minres with it, and FP32 inner sweeps beside it (spk_pc_set_inner > 0 and spk_pc_set_amg are exclusive). */
+enum { SPK_AMG_CHEBYSHEV = 0, SPK_AMG_RICHARDSON = 1 };
+#define SPK_AMG_MAX_LEVELS 16
+#define SPK_AMG_MAX_COARSE 1024
+typedef struct spk_amg_opts {
+    int32_t max_levels;       /* -pc_mg_levels                      (10; 1..SPK_AMG_MAX_LEVELS) */
+    int32_t coarse_eq_limit;  /* -pc_gamg_coarse_eq_limit           (50)  */
+    int32_t nsmooths;         /* -pc_gamg_agg_nsmooths              (1; 0 keeps the tentative prolongator) */
+    int32_t smoother;         /* -mg_levels_ksp_type: SPK_AMG_*     (chebyshev) */
+    double threshold;         /* -pc_gamg_threshold                 (0: every stored block is a strong connection) */
+    int32_t smooth_its;       /* -mg_levels_ksp_max_it              (2) */
+    int32_t block_size;       /* node size bs; 0 = detect 3, 2 or 1 from the pattern (0) */
+    double esteig[4];         /* -mg_levels_ksp_chebyshev_esteig a,b,c,d (0,0.1,0,1.1): the Chebyshev interval is
+                                 [a lmin + b lmax, c lmin + d lmax], lmin / lmax the extreme Ritz values of D^-1 A_l */
+    double richardson_scale;  /* -mg_levels_ksp_richardson_scale    (1.0) */
+} spk_amg_opts;
+void spk_default_amg_opts(spk_amg_opts *opts);
+int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
+typedef struct spk_amg_info {
+    int32_t levels, block_size;
+    int32_t rows[SPK_AMG_MAX_LEVELS];
+    int64_t nnz[SPK_AMG_MAX_LEVELS];
+    double lambda_max[SPK_AMG_MAX_LEVELS];   /* largest Ritz value of D^-1 A_l (the coarsest level: 0) */
+    double operator_complexity;              /* sum of nnz(A_l) / nnz(A_0) */
+    double setup_seconds;                    /* host build + upload */
+} spk_amg_info;
+/* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
+int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
+/* Test hook: one matrix of a level as CSR (sorted columns).  which: SPK_AMG_OP = A_l, SPK_AMG_PROLONG = P_l (rows of
+ * level l, columns of level l+1), SPK_AMG_TENTATIVE = the tentative prolongator of level l, SPK_AMG_COARSE_INV = the
+ * dense inverse of the coarsest operator (level = levels - 1) as full rows.  Call with rowptr / colidx / val NULL first
+ * for the sizes. */
+enum { SPK_AMG_OP = 0, SPK_AMG_PROLONG = 1, SPK_AMG_TENTATIVE = 2, SPK_AMG_COARSE_INV = 3 };
+int spk_get_amg_level(const spk_ctx *ctx, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
+                      int32_t *rowptr, int32_t *colidx, double *val);
+/* Host-only builder (no GPU): the same hierarchy from a square CSR matrix, for tests.  agg: the aggregate of every
+ * node of a level (-1: isolated, in no aggregate).  Errors: spk_last_error(NULL). */
+typedef struct spk_amg_hier spk_amg_hier;
+int spk_amg_build_host(int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                       const spk_amg_opts *opts, spk_amg_hier **out);
+int spk_amg_destroy_host(spk_amg_hier *h);
+int spk_amg_host_info(const spk_amg_hier *h, spk_amg_info *info);
+int spk_amg_host_level(const spk_amg_hier *h, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
+                       int32_t *rowptr, int32_t *colidx, double *val);
+int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, int32_t *agg);
+
 /* Copies S^ (m doubles) to the host, for inspection. */
 int spk_get_schur_diag(spk_ctx *ctx, double *shat);
 int spk_get_jacobi_diag(spk_ctx *ctx, double *dinv /* n_local */);

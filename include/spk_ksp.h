@@ -44,7 +44,7 @@ int SpkKSPSetOperators(SpkKSP ksp, const SpkMatCSR *A, const SpkMatCSR *B); /* K
  * DEVIATION from PETSc, on purpose: -ksp_type and -pc_type have NO default here.  PETSc would fall
  * back to gmres (left preconditioning) and ilu (bjacobi+ilu in parallel), neither of which this
  * library implements; SpkKSPSetUp / SpkKSPSolve return SPK_ERR_UNSUPPORTED with a message unless
- * "-ksp_type fgmres|minres" and "-pc_type jacobi|fieldsplit|none" were given.
+ * "-ksp_type fgmres|minres" and "-pc_type jacobi|fieldsplit|gamg|none" were given.
  * -ksp_type minres (spk_minres) takes -ksp_norm_type unpreconditioned (default) | natural and needs a symmetric
  * positive definite preconditioner: none, jacobi, or fieldsplit with -pc_fieldsplit_schur_fact_type diag and no
  * FP32 inner sweeps; SpkKSPSetUp refuses the others with SPK_ERR_UNSUPPORTED before it looks at the operators. */
@@ -60,6 +60,15 @@ int SpkKSPGetResidualNorm(SpkKSP ksp, double *rnorm);
 int SpkKSPGetResidualHistory(SpkKSP ksp, const double **hist, int32_t *n);
 int SpkKSPGetSolveTime(SpkKSP ksp, double *seconds);
 int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schur_fact);
+/* Multigrid options as read: fieldsplit0 = 0 the plain set (-pc_type gamg on K = A: -pc_gamg_threshold,
+ * -pc_gamg_agg_nsmooths, -pc_gamg_coarse_eq_limit, -pc_mg_levels, -mg_levels_ksp_type chebyshev|richardson,
+ * -mg_levels_ksp_max_it, -mg_levels_ksp_richardson_scale, -mg_levels_ksp_chebyshev_esteig a,b,c,d,
+ * -mg_levels_pc_type jacobi), 1 the same names with the -fieldsplit_0_ prefix (-fieldsplit_0_pc_type gamg inside
+ * -pc_type fieldsplit).  *selected = 1 when that gamg was asked for.  Unknown -mg_ options are refused like unknown
+ * -ksp_ ones.  -pc_type gamg with a B block, gamg with -ksp_type minres and gamg beside the FP32 inner sweeps are
+ * refused by SpkKSPSetUp with SPK_ERR_UNSUPPORTED.  (SpkKSPGetOptions reports -pc_type gamg as SPK_PC_JACOBI, the
+ * slot the V-cycle takes.) */
+int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);
 /* -ksp_type as set ("fgmres", "minres", or "" before KSPSetFromOptions gave one) and -ksp_norm_type (SPK_NORM_*) */
 int SpkKSPGetType(SpkKSP ksp, const char **type, int32_t *norm_type);
 int SpkKSPGetContext(SpkKSP ksp, spk_ctx **ctx);

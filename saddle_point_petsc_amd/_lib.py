@@ -62,6 +62,27 @@ class CommInfo(C.Structure):
     ]
 
 
+AMG_MAX_LEVELS = 16
+
+
+class AmgOpts(C.Structure):
+    """spk_amg_opts (include/spk.h)."""
+    _fields_ = [
+        ("max_levels", C.c_int32), ("coarse_eq_limit", C.c_int32), ("nsmooths", C.c_int32), ("smoother", C.c_int32),
+        ("threshold", C.c_double), ("smooth_its", C.c_int32), ("block_size", C.c_int32), ("esteig", C.c_double * 4),
+        ("richardson_scale", C.c_double),
+    ]
+
+
+class AmgInfo(C.Structure):
+    """spk_amg_info (include/spk.h)."""
+    _fields_ = [
+        ("levels", C.c_int32), ("block_size", C.c_int32), ("rows", C.c_int32 * AMG_MAX_LEVELS),
+        ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("lambda_max", C.c_double * AMG_MAX_LEVELS),
+        ("operator_complexity", C.c_double), ("setup_seconds", C.c_double),
+    ]
+
+
 class MatCSR(C.Structure):
     _fields_ = [
         ("row_begin", C.c_int64), ("nrows_local", C.c_int32), ("pad", C.c_int32),
@@ -142,6 +163,16 @@ def _load():
     L.spk_set_block.argtypes = [vp, C.c_int, i64, i32, i64, i32p, i32p, f64p]
     L.spk_pc_setup.argtypes = [vp, C.c_int, C.c_int]
     L.spk_pc_set_inner.argtypes = [vp, C.c_int, C.c_double]
+    L.spk_default_amg_opts.argtypes = [C.POINTER(AmgOpts)]
+    L.spk_default_amg_opts.restype = None
+    L.spk_pc_set_amg.argtypes = [vp, C.POINTER(AmgOpts)]
+    L.spk_get_amg_info.argtypes = [vp, C.POINTER(AmgInfo)]
+    L.spk_get_amg_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
+    L.spk_amg_build_host.argtypes = [i32, i32p, i32p, f64p, C.POINTER(AmgOpts), C.POINTER(vp)]
+    L.spk_amg_destroy_host.argtypes = [vp]
+    L.spk_amg_host_info.argtypes = [vp, C.POINTER(AmgInfo)]
+    L.spk_amg_host_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
+    L.spk_amg_host_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
     L.spk_get_schur_diag.argtypes = [vp, f64p]
     L.spk_get_jacobi_diag.argtypes = [vp, f64p]
     L.spk_get_bd_planes.argtypes = [vp, C.POINTER(i32)]
@@ -201,6 +232,7 @@ def _load():
     L.SpkKSPGetSolveTime.argtypes = [vp, C.POINTER(dbl)]
     L.SpkKSPGetOptions.argtypes = [vp, C.POINTER(Opts), C.POINTER(i32), C.POINTER(i32)]
     L.SpkKSPGetContext.argtypes = [vp, C.POINTER(vp)]
+    L.SpkKSPGetAMGOptions.argtypes = [vp, C.c_int, C.POINTER(AmgOpts), C.POINTER(i32)]
     L.SpkKSPGetType.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i32)]
     L.SpkKSPGetError.restype = C.c_char_p
     L.SpkKSPGetError.argtypes = [vp]

@@ -14,6 +14,9 @@ void rccl_unique_id(void *id128);
 }
 
 static thread_local std::string g_create_error;
+namespace spk {
+void set_create_error(const std::string &m) { g_create_error = m; }
+}
 
 #define SPK_TRY(ctx)                                                     \
     if (!(ctx)) return SPK_ERR_ARG;                                      \
@@ -274,9 +277,47 @@ int spk_pc_set_inner(spk_ctx *c, int sweeps, double omega)
 {
     SPK_TRY(c)
     if (sweeps < 0 || sweeps > 64 || !(omega > 0.0) || !(omega < 2.0)) spk::fail(SPK_ERR_ARG, "pc_set_inner: sweeps in [0,64], omega in (0,2)");
+    if (sweeps > 0 && c->amg_on)
+        spk::fail(SPK_ERR_UNSUPPORTED, "pc_set_inner: the multigrid preconditioner is set (spk_pc_set_amg); one inner solve "
+                  "stands for A^-1, not two -- call spk_pc_set_amg(ctx, NULL) first");
     c->inner_sweeps = sweeps;
     c->inner_omega = omega;
     c->pc_ready = false;
+    SPK_CATCH(c)
+}
+
+int spk_pc_set_amg(spk_ctx *c, const spk_amg_opts *o)
+{
+    SPK_TRY(c)
+    if (o) {
+        spk::amg_check_opts(*o);
+        if (c->inner_sweeps > 0)
+            spk::fail(SPK_ERR_UNSUPPORTED, "pc_set_amg: the FP32 inner sweeps are set (spk_pc_set_inner); one inner solve "
+                      "stands for A^-1, not two -- call spk_pc_set_inner(ctx, 0, omega) first");
+        c->amg_opts = *o;
+    }
+    c->amg_on = o != nullptr;
+    c->pc_ready = false;
+    SPK_CATCH(c)
+}
+
+int spk_get_amg_info(const spk_ctx *cc, spk_amg_info *info)
+{
+    spk_ctx *c = const_cast<spk_ctx *>(cc);
+    SPK_TRY(c)
+    if (!info) spk::fail(SPK_ERR_ARG, "null output");
+    if (!c->amg_h || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
+    c->amg_h->h.info(info);
+    SPK_CATCH(c)
+}
+
+int spk_get_amg_level(const spk_ctx *cc, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
+                      int32_t *rowptr, int32_t *colidx, double *val)
+{
+    spk_ctx *c = const_cast<spk_ctx *>(cc);
+    SPK_TRY(c)
+    if (!c->amg_h || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
+    c->amg_h->h.level(level, which, nrows, ncols, nnz, rowptr, colidx, val);
     SPK_CATCH(c)
 }
 

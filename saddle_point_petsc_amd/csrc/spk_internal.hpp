@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 
 #include "../../include/spk.h"
+#include "spk_amg.hpp"
 
 namespace spk {
 
@@ -717,7 +718,34 @@ void krylov_refine_decide(const KrylovArrays &ka, int loc, int mode, const doubl
                           double *dots2, hipStream_t s);
 void krylov_refine_merge(const KrylovArrays &ka, int loc, double *dots, const double *dots2, double *nrm,
                          const double *nrm_b, int nn, hipStream_t s);
+// smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
+void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
+void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
+                  double alpha, double beta, const int32_t *done, hipStream_t s);   // out = y + a D^-1 (b - A y) + b (y - yo)
+void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s);   // out = R (b - t)
+void amg_prolong_add(const CsrDev &P, const double *e, double *y, const int32_t *done, hipStream_t s);          // y += P e
+// y == nullptr: out = alpha dinv b (zero initial guess); else out = y + alpha dinv (b - t) + beta (y - yo) (yo null: 0)
+void amg_cheb_vec(int64_t n, const double *dinv, const double *b, const double *t, const double *y, const double *yo,
+                  double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
+// the fine level's fused step on the 2x2 row-type layout (false: A is not that layout, nothing launched)
+bool amg_cheb_dict2(const DictDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
+                    double alpha, double beta, const int32_t *done, hipStream_t s);
+void amg_dense(const double *C, int32_t n, const double *b, double *y, const int32_t *done, hipStream_t s);     // y = C b
+void amg_out(int mode, int64_t n, const double *src, double *dst, const int32_t *done, hipStream_t s);          // = / -=
 }  // namespace k
+
+// the device copy of the hierarchy (spk_amg.cpp): level 0 keeps the context's A layout and diag(A)^-1
+struct AmgLevelDev {
+    int32_t n = 0;
+    CsrDev A, P, R;                    // A: levels >= 1; P, R: all but the coarsest
+    DevBuf<double> dinv;               // levels >= 1
+    DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product
+    std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
+};
+struct AmgDev {
+    std::vector<AmgLevelDev> lv;
+    DevBuf<double> cinv;
+};
 
 }  // namespace spk
 
@@ -783,6 +811,11 @@ struct spk_ctx {
     int inner_sweeps = 0;
     double inner_omega = 1.0;
     spk::DevBuf<float> a32, d32, x32, y32a, y32b;
+    // smoothed-aggregation multigrid standing for A^-1 (spk_pc_set_amg; built at spk_pc_setup)
+    bool amg_on = false;
+    spk_amg_opts amg_opts{};
+    std::unique_ptr<spk_amg_hier> amg_h;
+    std::unique_ptr<spk::AmgDev> amg_d;
     spk::DevBuf<double> bigdots;   // Gram-Schmidt coefficients of restart lengths beyond the fused kernels' 62
 
     // scratch
@@ -848,6 +881,11 @@ void a_mult(spk_ctx *c, const double *x, double *y, const CsrDev *bt, const doub
 void op_mult(spk_ctx *c, const double *x, double *y, const int32_t *done, bool halo_done = false, bool reuse_bt = false);
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done);
 void pc_setup(spk_ctx *c, int pc_type, int schur_fact);
+// multigrid (spk_amg.cpp): the host hierarchy from the context's A00 (single rank) and its upload; one V-cycle,
+// mode 0: y = V x, mode 1: y -= V x
+std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);
+void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
+void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);
 void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,

@@ -1,0 +1,243 @@
+// spk_k_amg.hip -- the V-cycle of the smoothed-aggregation multigrid (-pc_type gamg; host side in spk_amg.cpp).
+// gfx950, wave64, FP64.  The levels >= 1 are CSR (sorted columns): eight lanes per row, each lane a fixed stride of
+// the row, the eight partial sums added in a fixed butterfly -- no atomics, the same bits on every run.  Every launch
+// takes the solver's `done` gate.
+#include "spk_dict.hpp"
+
+namespace spk {
+namespace k {
+
+namespace {
+constexpr int kAmgLanes = 8;                     // lanes per CSR row
+constexpr int kAmgRows = kThreads / kAmgLanes;   // rows per workgroup
+
+// sum over the row's entries of v * (x (- sub)) in the lane's slice, then over the eight lanes
+__device__ __forceinline__ double row_dot(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                          const double *__restrict__ v, const double *x, const double *sub, int32_t i,
+                                          int lane)
+{
+    double acc = 0.0;
+    const int32_t k1 = rp[i + 1];
+    if (sub)
+        for (int32_t k = rp[i] + lane; k < k1; k += kAmgLanes) { const int32_t c = ci[k]; acc += v[k] * (x[c] - sub[c]); }
+    else
+        for (int32_t k = rp[i] + lane; k < k1; k += kAmgLanes) acc += v[k] * x[ci[k]];
+    acc += __shfl_xor(acc, 4);
+    acc += __shfl_xor(acc, 2);
+    acc += __shfl_xor(acc, 1);
+    return acc;
+}
+}  // namespace
+
+// MODE 0: out = A x
+// MODE 1: out = y + alpha dinv (b - A y) + beta (y - yo)     (one Chebyshev / Richardson step; out may be yo, yo may be
+//         null: the zero initial guess)
+// MODE 2: out = A (x - sub)                                   (restriction of the residual: A = R, x = b, sub = A y)
+// MODE 3: out += A x                                          (prolongation + correction: A = P)
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void amg_csr_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                           const double *__restrict__ v, int32_t n, const double *x,
+                                                           const double *sub, const double *dinv, const double *b,
+                                                           const double *yo, double *out, double alpha, double beta,
+                                                           const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int lane = threadIdx.x % kAmgLanes;
+    const int32_t i = (int32_t)blockIdx.x * kAmgRows + (int32_t)(threadIdx.x / kAmgLanes);
+    if (i >= n) return;   // whole groups of eight leave together: the butterfly stays inside live lanes
+    const double d = row_dot(rp, ci, v, x, MODE == 2 ? sub : nullptr, i, lane);
+    if (lane != 0) return;
+    if (MODE == 0 || MODE == 2) out[i] = d;
+    else if (MODE == 3) out[i] += d;
+    else {
+        const double y = x[i];
+        double r = y + alpha * (dinv[i] * (b[i] - d));
+        if (beta != 0.0) r += beta * (y - (yo ? yo[i] : 0.0));   // yo null: the zero initial guess
+        out[i] = r;
+    }
+}
+
+// the fine level's vector pass behind the layout's own product t = A y:
+//   y == nullptr (zero initial guess): out = alpha dinv b;  else out = y + alpha dinv (b - t) + beta (y - yo)
+__global__ __launch_bounds__(kThreads) void amg_cheb_vec_kernel(int64_t n, const double *__restrict__ dinv,
+                                                                const double *__restrict__ b, const double *__restrict__ t,
+                                                                const double *y, const double *yo, double *out, double alpha,
+                                                                double beta, const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        if (!y) { out[i] = alpha * (dinv[i] * b[i]); continue; }
+        const double yi = y[i];
+        double r = yi + alpha * (dinv[i] * (b[i] - t[i]));
+        if (beta != 0.0) r += beta * (yi - (yo ? yo[i] : 0.0));
+        out[i] = r;
+    }
+}
+
+// the fine level's fused step on the 2x2 row-type layout (row types + deviation codes, spk_k_dict.hip): the product of a
+// block row and the three-term update in one pass, out = y + alpha dinv (b - A y) + beta (y - yo).  Modelled on
+// jacobi_sweep_f32_dict_kernel, in FP64: the values decoded exactly, the products summed per row in block order as
+// spmv_dict_kernel sums them.  One block row per thread, workgroups over XCD-contiguous chunks.  out may be yo (each
+// entry is read by its own thread before it is written), never y (the neighbours' rows read it).
+__global__ __launch_bounds__(kThreads) void amg_cheb_dict2_kernel(DictArgs d, const double *__restrict__ dinv,
+                                                                  const double *__restrict__ b, const double *__restrict__ y,
+                                                                  const double *yo, double *out, double alpha, double beta,
+                                                                  const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bx = (int)blockIdx.x;
+    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
+    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
+    if (c0 >= c1) return;
+    dict_load_lds(d, (d.nclass + 1) * 4, smem);
+    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
+    const int2 *tent = reinterpret_cast<const int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
+    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
+    const int32_t *fl = reinterpret_cast<const int32_t *>(smem + d.fld_off);
+    const double2 *y2 = reinterpret_cast<const double2 *>(y);
+    for (int ch = c0; ch < c1; ++ch) {
+        const int br = ch * kDictChunk + (int)threadIdx.x;
+        if (br >= d.nbrows) continue;
+        const int tc = (int)d.tid[br];
+        double s0 = 0.0, s1 = 0.0;
+        const int len = tlen[tc];
+        const int2 *te = tent + (size_t)tc * d.kmax;
+        constexpr int G = 10;   // a 2-D interior block row whole: five 16-byte code loads + nine gathers of y in flight
+        for (int k0 = 0; k0 < len; k0 += G) {
+            int2 e[G];
+            u64 w0[G];
+            double2 yv[G];
+#pragma unroll
+            for (int h = 0; h < G / 2; ++h) {
+                w0[2 * h] = w0[2 * h + 1] = 0ull;
+                if (k0 + 2 * h < len) dict_issue_pair2(d, (k0 >> 1) + h, br, w0[2 * h], w0[2 * h + 1]);
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const bool in = k0 + g < len;
+                e[g] = in ? te[k0 + g] : make_int2(0, 0);
+                yv[g] = in ? y2[(int64_t)br + e[g].x] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (k0 + g < len) {
+                    const double2 *cb = cv + (size_t)e[g].y * 4;
+                    const int32_t *fb = fl + (size_t)e[g].y * 4;
+                    const bool st = d.strad != 0;
+                    s0 += dict_decode(dict_field2(w0[g], fb[0], st), cb[0]) * yv[g].x;
+                    s0 += dict_decode(dict_field2(w0[g], fb[1], st), cb[1]) * yv[g].y;
+                    s1 += dict_decode(dict_field2(w0[g], fb[2], st), cb[2]) * yv[g].x;
+                    s1 += dict_decode(dict_field2(w0[g], fb[3], st), cb[3]) * yv[g].y;
+                }
+            }
+        }
+        const double2 yi = y2[br], bi = reinterpret_cast<const double2 *>(b)[br],
+                      di = reinterpret_cast<const double2 *>(dinv)[br];
+        double2 r;
+        r.x = yi.x + alpha * (di.x * (bi.x - s0));
+        r.y = yi.y + alpha * (di.y * (bi.y - s1));
+        if (beta != 0.0 && yo) {
+            const double2 oi = reinterpret_cast<const double2 *>(yo)[br];
+            r.x += beta * (yi.x - oi.x);
+            r.y += beta * (yi.y - oi.y);
+        } else if (beta != 0.0) {
+            r.x += beta * yi.x;
+            r.y += beta * yi.y;
+        }
+        reinterpret_cast<double2 *>(out)[br] = r;
+    }
+}
+
+// y = C b, C dense row-major n x n (the coarsest level's inverse): one wave per row, lane-strided sums, fixed butterfly
+__global__ __launch_bounds__(kThreads) void amg_dense_kernel(const double *__restrict__ C, int32_t n,
+                                                             const double *__restrict__ b, double *__restrict__ y,
+                                                             const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int lane = threadIdx.x % kWave;
+    const int32_t i = (int32_t)blockIdx.x * (kThreads / kWave) + (int32_t)(threadIdx.x / kWave);
+    if (i >= n) return;
+    double acc = 0.0;
+    for (int32_t j = lane; j < n; j += kWave) acc += C[(size_t)i * n + j] * b[j];
+    for (int off = kWave / 2; off > 0; off /= 2) acc += __shfl_xor(acc, off);
+    if (lane == 0) y[i] = acc;
+}
+
+// mode 0: dst = src; mode 1: dst -= src
+__global__ __launch_bounds__(kThreads) void amg_out_kernel(int mode, int64_t n, const double *__restrict__ src,
+                                                           double *__restrict__ dst, const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+        dst[i] = mode ? dst[i] - src[i] : src[i];
+}
+
+namespace {
+inline dim3 csr_grid(int32_t n) { return dim3((unsigned)std::max<int64_t>(((int64_t)n + kAmgRows - 1) / kAmgRows, 1)); }
+inline dim3 vec_grid1(int64_t n) { return dim3((unsigned)std::max<int64_t>(std::min<int64_t>((n + kThreads - 1) / kThreads, kMaxBlocks * 4), 1)); }
+}  // namespace
+
+void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s)
+{
+    if (A.nrows == 0) return;
+    hipLaunchKernelGGL(amg_csr_kernel<0>, csr_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p, A.nrows,
+                       x, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,
+                       out, 0.0, 0.0, done);
+}
+void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
+                  double alpha, double beta, const int32_t *done, hipStream_t s)
+{
+    if (A.nrows == 0) return;
+    hipLaunchKernelGGL(amg_csr_kernel<1>, csr_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p, A.nrows,
+                       y, (const double *)nullptr, dinv, b, yo, out, alpha, beta, done);
+}
+void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s)
+{
+    if (R.nrows == 0) return;
+    hipLaunchKernelGGL(amg_csr_kernel<2>, csr_grid(R.nrows), dim3(kThreads), 0, s, R.rowptr.p, R.colidx.p, R.val.p, R.nrows,
+                       b, t, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, out, 0.0, 0.0, done);
+}
+void amg_prolong_add(const CsrDev &P, const double *e, double *y, const int32_t *done, hipStream_t s)
+{
+    if (P.nrows == 0) return;
+    hipLaunchKernelGGL(amg_csr_kernel<3>, csr_grid(P.nrows), dim3(kThreads), 0, s, P.rowptr.p, P.colidx.p, P.val.p, P.nrows,
+                       e, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,
+                       y, 0.0, 0.0, done);
+}
+void amg_cheb_vec(int64_t n, const double *dinv, const double *b, const double *t, const double *y, const double *yo,
+                  double *out, double alpha, double beta, const int32_t *done, hipStream_t s)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(amg_cheb_vec_kernel, vec_grid1(n), dim3(kThreads), 0, s, n, dinv, b, t, y, yo, out, alpha, beta, done);
+}
+bool amg_cheb_dict2(const DictDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
+                    double alpha, double beta, const int32_t *done, hipStream_t s)
+{
+    if (!A.ok || A.bs != 2) return false;
+    if (A.nbrows == 0) return true;
+    int grid = 0;
+    DictArgs d = dict_args(A, &grid);
+    // one chunk per workgroup: the kernel does not pipeline its chunks (the 512 workgroups dict_args sizes for the
+    // pipelined product left it latency-bound: 45.6 us at 1024^2 against 21.8 + 9.9 for the product and the vector pass)
+    d.chunks_per_wg = 1;
+    d.chunks_per_xcd = (d.nchunks + 7) / 8;
+    grid = 8 * d.chunks_per_xcd;
+    hipLaunchKernelGGL(amg_cheb_dict2_kernel, dim3(grid), dim3(kThreads), (size_t)A.lds_bytes, s, d, dinv, b, y, yo, out, alpha,
+                       beta, done);
+    return true;
+}
+void amg_dense(const double *C, int32_t n, const double *b, double *y, const int32_t *done, hipStream_t s)
+{
+    if (n == 0) return;
+    const int rows = kThreads / kWave;
+    hipLaunchKernelGGL(amg_dense_kernel, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, s, C, n, b, y, done);
+}
+void amg_out(int mode, int64_t n, const double *src, double *dst, const int32_t *done, hipStream_t s)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(amg_out_kernel, vec_grid1(n), dim3(kThreads), 0, s, mode, n, src, dst, done);
+}
+
+}  // namespace k
+}  // namespace spk

@@ -1,6 +1,7 @@
 // spk_ksp.cpp -- KSP-shaped host facade over the C ABI (see include/spk_ksp.h):
 // the call sequence of /root/reference/src/SaddlePointProblem.c:65-72 with the
 // option names KSPSetFromOptions (:67) would read.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +18,10 @@ struct SpkKSP_s {
     int32_t inner_sweeps = 0;  // -fieldsplit_0_ksp_max_it with -fieldsplit_0_ksp_type richardson
     double inner_omega = 1.0;  // -fieldsplit_0_ksp_richardson_scale
     bool inner_richardson = false;
+    // smoothed-aggregation multigrid: -pc_type gamg (K = A) and -fieldsplit_0_pc_type gamg (the Schur split's A^-1),
+    // each with its own options (amg[0]: -pc_gamg_* / -pc_mg_* / -mg_levels_*, amg[1]: the same with -fieldsplit_0_)
+    bool pc_gamg = false, split0_gamg = false;
+    spk_amg_opts amg[2];
     bool have_ops = false, is_setup = false, has_B = false;
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
@@ -60,6 +65,57 @@ bool parse_bool(const char *s, bool *v)
     if (t == "0" || t == "false" || t == "no" || t == "off") { *v = false; return true; }
     return false;
 }
+// the multigrid options (key without its -fieldsplit_0_ prefix); *handled = false: not one of them
+int parse_amg(SpkKSP k, spk_amg_opts &o, const std::string &full, const std::string &key, const char *val, bool *handled)
+{
+    *handled = true;
+    auto need = [&](const char *what) -> int { return set_err(k, SPK_ERR_ARG, "option " + full + " needs " + what); };
+    int32_t iv = 0;
+    double dv = 0.0;
+    if (key == "-pc_gamg_threshold") {
+        if (!val || !parse_double(val, &dv) || !(dv >= 0.0)) return need("a real >= 0");
+        o.threshold = dv;
+    } else if (key == "-pc_gamg_agg_nsmooths") {
+        if (!val || !parse_int(val, &iv) || iv < 0 || iv > 4) return need("an integer 0..4");
+        o.nsmooths = iv;
+    } else if (key == "-pc_gamg_coarse_eq_limit") {
+        if (!val || !parse_int(val, &iv) || iv < 1) return need("an integer >= 1");
+        o.coarse_eq_limit = iv;
+    } else if (key == "-pc_mg_levels") {
+        if (!val || !parse_int(val, &iv) || iv < 1 || iv > SPK_AMG_MAX_LEVELS) return need("an integer 1..16");
+        o.max_levels = iv;
+    } else if (key == "-mg_levels_ksp_type") {
+        if (!val) return need("a type");
+        const std::string v(val);
+        if (v == "chebyshev") o.smoother = SPK_AMG_CHEBYSHEV;
+        else if (v == "richardson") o.smoother = SPK_AMG_RICHARDSON;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (chebyshev | richardson)");
+    } else if (key == "-mg_levels_ksp_max_it") {
+        if (!val || !parse_int(val, &iv) || iv < 1 || iv > 64) return need("an integer 1..64");
+        o.smooth_its = iv;
+    } else if (key == "-mg_levels_ksp_richardson_scale") {
+        if (!val || !parse_double(val, &dv) || !(dv > 0.0)) return need("a real > 0");
+        o.richardson_scale = dv;
+    } else if (key == "-mg_levels_ksp_chebyshev_esteig") {
+        double e[4];
+        const char *p = val;
+        for (int i = 0; i < 4; ++i) {
+            char *end = nullptr;
+            e[i] = p ? std::strtod(p, &end) : 0.0;
+            if (!p || end == p || !std::isfinite(e[i]) || (i < 3 ? *end != ',' : *end != 0)) return need("four reals a,b,c,d");
+            p = end + 1;
+        }
+        std::memcpy(o.esteig, e, sizeof e);
+    } else if (key == "-mg_levels_pc_type") {
+        if (!val) return need("a type");
+        if (std::string(val) != "jacobi") return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (jacobi)");
+    } else if (key.rfind("-mg_", 0) == 0) {
+        return set_err(k, SPK_ERR_UNSUPPORTED, "unknown solver option " + full);
+    } else {
+        *handled = false;
+    }
+    return SPK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -88,6 +144,8 @@ int SpkKSPCreate(int device, SpkKSP *out)
     *out = nullptr;
     SpkKSP k = new SpkKSP_s();
     spk_default_opts(&k->opts);
+    spk_default_amg_opts(&k->amg[0]);
+    spk_default_amg_opts(&k->amg[1]);
     std::memset(&k->result, 0, sizeof k->result);
     k->device = device;
     *out = k;
@@ -155,6 +213,14 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         };
         auto bad = [&]() -> int { return set_err(k, SPK_ERR_UNSUPPORTED, "option " + key + " " + (val ? val : "") + " is not supported"); };
         bool flag = true;
+        {   // multigrid options, plain or with the first split's prefix
+            const bool split0 = key.rfind("-fieldsplit_0_", 0) == 0;
+            const std::string sub = split0 ? "-" + key.substr(14) : key;
+            bool handled = false;
+            const int rc = parse_amg(k, k->amg[split0 ? 1 : 0], key, sub, val, &handled);
+            if (rc != SPK_OK) return rc;
+            if (handled) continue;
+        }
         if (key == "-ksp_type") {
             if (!val) return need("a type");
             const std::string v(val);
@@ -207,7 +273,9 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (v == "none") k->pc_type = SPK_PC_NONE;
             else if (v == "jacobi") k->pc_type = SPK_PC_JACOBI;
             else if (v == "fieldsplit") k->pc_type = SPK_PC_SCHUR;
+            else if (v == "gamg") k->pc_type = SPK_PC_JACOBI;   // Jacobi's slot, M^-1 = one V-cycle (K = A only)
             else return bad();
+            k->pc_gamg = v == "gamg";
             k->pc_type_given = true;
         } else if (key == "-pc_fieldsplit_type") {
             if (!val) return need("a type");
@@ -239,7 +307,13 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         } else if (key == "-fieldsplit_1_ksp_type") {
             if (!val) return need("a type");
             if (std::string(val) != "preonly") return bad();
-        } else if (key == "-fieldsplit_0_pc_type" || key == "-fieldsplit_1_pc_type") {
+        } else if (key == "-fieldsplit_0_pc_type") {
+            if (!val) return need("a type");
+            const std::string v(val);
+            if (v == "jacobi") k->split0_gamg = false;
+            else if (v == "gamg") k->split0_gamg = true;
+            else return bad();
+        } else if (key == "-fieldsplit_1_pc_type") {
             if (!val) return need("a type");
             if (std::string(val) != "jacobi") return bad();
         } else if (key == "-spk_single_reduce") {
@@ -258,6 +332,14 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
     return SPK_OK;
 }
 
+// which multigrid option set the selected preconditioner uses: 0 (-pc_type gamg), 1 (-fieldsplit_0_pc_type gamg), -1 none
+static int amg_active(SpkKSP k)
+{
+    if (k->pc_type == SPK_PC_JACOBI && k->pc_gamg) return 0;
+    if (k->pc_type == SPK_PC_SCHUR && k->split0_gamg) return 1;
+    return -1;
+}
+
 int SpkKSPSetUp(SpkKSP k)
 {
     if (!k) return SPK_ERR_ARG;
@@ -267,7 +349,7 @@ int SpkKSPSetUp(SpkKSP k)
                                                "preconditioner)");
     if (!k->pc_type_given)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -pc_type given; PETSc's default (ilu, bjacobi+ilu in parallel) is "
-                                               "not implemented -- pass -pc_type jacobi | fieldsplit | none");
+                                               "not implemented -- pass -pc_type jacobi | fieldsplit | gamg | none");
     // KSP / PC compatibility: option checks only, no GPU needed
     if (!k->minres && k->norm_type == SPK_NORM_NATURAL)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres; fgmres tests the "
@@ -280,10 +362,25 @@ int SpkKSPSetUp(SpkKSP k)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres needs a symmetric preconditioner and the FP32 inner "
                                                "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
                                                "pass -ksp_type fgmres");
+    const int amg_slot = amg_active(k);
+    if (k->minres && amg_slot >= 0)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (gamg) is not "
+                                               "implemented -- pass -ksp_type fgmres");
+    if (amg_slot >= 0 && k->inner_richardson && k->inner_sweeps > 0)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: gamg and the FP32 inner sweeps both stand for A^-1 -- drop "
+                                               "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
         return set_err(k, SPK_ERR_STATE, "KSPSetUp: -pc_type fieldsplit (schur) needs the constraint block B");
-    int rc = spk_pc_set_inner(k->ctx, k->inner_richardson ? k->inner_sweeps : 0, k->inner_omega);
+    if (k->pc_type == SPK_PC_JACOBI && k->pc_gamg && k->has_B)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -pc_type gamg is for K = A alone; the saddle matrix [A B^T; B 0] "
+                                               "(indefinite, zero (1,1) block) is not a multigrid target -- pass -pc_type "
+                                               "fieldsplit -fieldsplit_0_pc_type gamg");
+    int rc = amg_slot >= 0 ? SPK_OK : spk_pc_set_amg(k->ctx, nullptr);
+    if (rc != SPK_OK) return from_ctx(k, rc);
+    rc = spk_pc_set_inner(k->ctx, k->inner_richardson ? k->inner_sweeps : 0, k->inner_omega);
+    if (rc != SPK_OK) return from_ctx(k, rc);
+    if (amg_slot >= 0) rc = spk_pc_set_amg(k->ctx, &k->amg[amg_slot]);
     if (rc != SPK_OK) return from_ctx(k, rc);
     rc = spk_pc_setup(k->ctx, k->pc_type, k->schur_fact);
     if (rc != SPK_OK) return from_ctx(k, rc);
@@ -319,6 +416,20 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     else if (k->view)
         std::printf("KSP Object: type fgmres (MI355X device-resident), restart=%d, classical Gram-Schmidt, rtol=%g atol=%g divtol=%g max_it=%d, right preconditioning, pc=%d schur_fact=%d\n",
                     k->opts.restart, k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_type, k->schur_fact);
+    if (k->view && amg_active(k) >= 0) {
+        spk_amg_info ai;
+        if (spk_get_amg_info(k->ctx, &ai) == SPK_OK) {
+            const spk_amg_opts &o = k->amg[amg_active(k)];
+            std::printf("  PC gamg (smoothed aggregation, %s): %d levels, block size %d, operator complexity %.4f, set-up %.3f s\n",
+                        amg_active(k) ? "fieldsplit_0" : "K = A", ai.levels, ai.block_size, ai.operator_complexity, ai.setup_seconds);
+            std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
+                        o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
+                        o.nsmooths, o.coarse_eq_limit);
+            for (int l = 0; l < ai.levels; ++l)
+                std::printf("    level %d: rows %d nnz %lld lambda_max %.6g%s\n", l, ai.rows[l], (long long)ai.nnz[l],
+                            ai.lambda_max[l], l + 1 == ai.levels ? " (coarse: dense Cholesky inverse)" : "");
+        }
+    }
     return SPK_OK;
 }
 
@@ -339,6 +450,13 @@ int SpkKSPGetOptions(SpkKSP k, spk_opts *o, int32_t *pc, int32_t *sf)
     if (o) *o = k->opts;
     if (pc) *pc = k->pc_type;
     if (sf) *sf = k->schur_fact;
+    return SPK_OK;
+}
+int SpkKSPGetAMGOptions(SpkKSP k, int fieldsplit0, spk_amg_opts *o, int32_t *selected)
+{
+    if (!k || fieldsplit0 < 0 || fieldsplit0 > 1) return SPK_ERR_ARG;
+    if (o) *o = k->amg[fieldsplit0];
+    if (selected) *selected = fieldsplit0 ? k->split0_gamg : k->pc_gamg;
     return SPK_OK;
 }
 int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)

@@ -26,6 +26,9 @@ void minres(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
         fail(SPK_ERR_UNSUPPORTED, "minres needs a symmetric positive definite preconditioner: the Schur %s factorisation is not "
              "symmetric -- use -pc_fieldsplit_schur_fact_type diag (SPK_SCHUR_DIAG), or -ksp_type fgmres",
              c->schur_fact == SPK_SCHUR_LOWER ? "lower" : c->schur_fact == SPK_SCHUR_UPPER ? "upper" : "full");
+    if (c->amg_d && c->pc_type != SPK_PC_NONE)
+        fail(SPK_ERR_UNSUPPORTED, "minres with the multigrid preconditioner (gamg) is not implemented -- call "
+             "spk_pc_set_amg(ctx, NULL) before spk_pc_setup, or use -ksp_type fgmres");
     if (c->inner_sweeps > 0 && c->pc_type != SPK_PC_NONE)
         fail(SPK_ERR_UNSUPPORTED, "minres needs a symmetric preconditioner: the FP32 inner sweeps are not -- call "
              "spk_pc_set_inner(ctx, 0, omega) before spk_pc_setup (drop -fieldsplit_0_ksp_type richardson), or use -ksp_type fgmres");

@@ -981,6 +981,18 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     if (pc_type < SPK_PC_NONE || pc_type > SPK_PC_SCHUR) fail(SPK_ERR_ARG, "pc_setup: unknown pc_type %d", pc_type);
     if (pc_type == SPK_PC_SCHUR && !c->have_B) fail(SPK_ERR_STATE, "pc_setup: Schur fieldsplit needs the A10 block");
     if (schur_fact < SPK_SCHUR_DIAG || schur_fact > SPK_SCHUR_FULL) fail(SPK_ERR_ARG, "pc_setup: unknown schur_fact %d", schur_fact);
+    // multigrid standing for A^-1: one rank only (every rank sees the same communicator size: all refuse together), built
+    // on the host before anything of the context changes -- a refusal leaves it as it was
+    std::unique_ptr<spk_amg_hier> amg;
+    if (c->amg_on) {
+        if (c->comm->size() > 1)
+            fail(SPK_ERR_UNSUPPORTED, "pc_setup: the multigrid preconditioner (gamg) runs on one rank only; this communicator "
+                 "has %d -- multi-rank AMG is not implemented", c->comm->size());
+        if (pc_type == SPK_PC_NONE) fail(SPK_ERR_ARG, "pc_setup: the multigrid preconditioner needs pc_type jacobi or schur");
+        amg = amg_build_ctx(c);
+    }
+    c->amg_d.reset();
+    c->amg_h.reset();
     hipStream_t s = c->stream;
     c->ensure_scratch();
     c->ensure_vectors();
@@ -997,6 +1009,7 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     }
     c->dinv.alloc((size_t)c->n_local, 8);
     k::extract_diag_inv(c->Ad, c->dinv.p, s);
+    if (amg) amg_upload(c, std::move(amg));
     const int m = c->m;
     if (m > 0 && c->b_general) {
         // S^ = diag(B D B^T), row by row: short rows one wave each; the long rows as below (scatter + window kernel)
@@ -1071,7 +1084,7 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     // dense rows of B D for the fused path (Schur LOWER/FULL, even local size)
     c->bd.release();
     if (pc_type == SPK_PC_SCHUR && m > 0 && !c->b_general && (schur_fact == SPK_SCHUR_FULL || schur_fact == SPK_SCHUR_LOWER) &&
-        c->even_all && c->inner_sweeps == 0) {
+        c->even_all && c->inner_sweeps == 0 && !c->amg_d) {
         c->bd.alloc((size_t)c->ld * m, 16);
         k::build_bd(c->Bt, c->dinv.p, m, c->ld, c->bd.p, s);
         // rows 2q / 2q+1 on even / odd entries (x / y degrees of freedom): m/2 planes instead of m rows
@@ -1131,6 +1144,13 @@ static void inner_apply(spk_ctx *c, const double *x, double *y, int mode, const 
     k::cvt_f32_out(ya, y, mode, nl, done, s);
 }
 
+// y (op) A^ ^-1 x: one multigrid V-cycle or the FP32 sweeps, whichever stands for A^-1
+static void ahat_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done)
+{
+    if (c->amg_d) amg_apply(c, x, y, mode, done);
+    else inner_apply(c, x, y, mode, done);
+}
+
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done)
 {
     hipStream_t s = c->stream;
@@ -1141,31 +1161,31 @@ void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done)
     // result may take it from there
     c->bt_cached = (c->b_general && c->Bt.ntiles > 0 && m > 0 && c->pc_type == SPK_PC_SCHUR &&
                     (c->schur_fact == SPK_SCHUR_UPPER || c->schur_fact == SPK_SCHUR_FULL)) ? y1 : nullptr;
-    if (c->inner_sweeps > 0 && c->pc_type != SPK_PC_NONE) {
-        // same block algebra with the inner solve standing for diag(A)^-1
+    if ((c->inner_sweeps > 0 || c->amg_d) && c->pc_type != SPK_PC_NONE) {
+        // same block algebra with the inner solve (FP32 sweeps or a V-cycle) standing for diag(A)^-1
         if (c->pc_type == SPK_PC_JACOBI) {
-            inner_apply(c, x0, y0, 0, done);
+            ahat_apply(c, x0, y0, 0, done);
             k::copy_small(x1, y1, m, done, s);
             return;
         }
         switch (c->schur_fact) {
         case SPK_SCHUR_DIAG:
-            inner_apply(c, x0, y0, 0, done);
+            ahat_apply(c, x0, y0, 0, done);
             k::schur_y1(SPK_SCHUR_DIAG, m, x1, nullptr, c->shat.p, y1, done, s);
             break;
         case SPK_SCHUR_UPPER:
             k::schur_y1(SPK_SCHUR_UPPER, m, x1, nullptr, c->shat.p, y1, done, s);
             k::bt_update(2, c->Bt, c->dinv.p, x0, y1, c->tmp.p, done, s, c->b_general ? c->tmpb.p : nullptr);   // x0 - B^T y1
-            inner_apply(c, c->tmp.p, y0, 0, done);
+            ahat_apply(c, c->tmp.p, y0, 0, done);
             break;
         default:  // LOWER, FULL
-            inner_apply(c, x0, y0, 0, done);
+            ahat_apply(c, x0, y0, 0, done);
             apply_B(c, y0, nullptr, c->ttmp.p, done);
             c->comm->allreduce_sum(c->ttmp.p, m, s);
             k::schur_y1(c->schur_fact, m, x1, c->ttmp.p, c->shat.p, y1, done, s);
             if (c->schur_fact == SPK_SCHUR_FULL) {
                 k::bt_update(3, c->Bt, c->dinv.p, x0, y1, c->tmp.p, done, s, c->b_general ? c->tmpb.p : nullptr);   // B^T y1
-                inner_apply(c, c->tmp.p, y0, 1, done);                            // y0 -= A^ ^-1 B^T y1
+                ahat_apply(c, c->tmp.p, y0, 1, done);                            // y0 -= A^ ^-1 B^T y1
             }
             break;
         }
@@ -1307,7 +1327,7 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     // the same head kernel without a constraint block: Jacobi on K = A (the reference as written,
     // SaddlePointProblem.c:66, and BASELINE config 2): VecScale + PCApply_Jacobi + deferred Givens
     const bool jac = o.fused && !p.schur && c->pc_type == SPK_PC_JACOBI && m == 0 && c->even_all && c->nonempty_all &&
-                     c->inner_sweeps == 0;
+                     c->inner_sweeps == 0 && !c->amg_d;   // (a V-cycle, like the FP32 sweeps, runs on the step-by-step path)
     p.head = p.schur || jac;
     p.nn = p.schur ? 1 + m : 1;
     p.bpk = p.schur && c->bd_packed ? 1 : 0;

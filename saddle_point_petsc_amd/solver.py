@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, Opts, Result, MatCSR, SpkError
+from ._lib import lib, Opts, Result, MatCSR, SpkError, AmgOpts, AmgInfo
 
 PC_NONE, PC_JACOBI, PC_SCHUR = 0, 1, 2
 SCHUR_DIAG, SCHUR_LOWER, SCHUR_UPPER, SCHUR_FULL = 0, 1, 2, 3
@@ -24,6 +24,88 @@ def default_opts(**kw):
             raise TypeError(f"unknown solver option {k}")
         setattr(o, k, v)
     return o
+
+
+AMG_CHEBYSHEV, AMG_RICHARDSON = 0, 1
+AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV = 0, 1, 2, 3
+_SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
+
+
+def amg_opts(**kw):
+    """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson')."""
+    o = AmgOpts()
+    lib.spk_default_amg_opts(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown multigrid option {k}")
+        if k == "smoother" and isinstance(v, str):
+            v = _SMOOTHERS[v]
+        if k == "esteig":
+            v = (C.c_double * 4)(*v)
+        setattr(o, k, v)
+    return o
+
+
+def amg_opts_dict(o):
+    d = {k: getattr(o, k) for k, _ in AmgOpts._fields_}
+    d["esteig"] = tuple(o.esteig)
+    return d
+
+
+def _amg_info(ai):
+    L = ai.levels
+    return dict(levels=L, block_size=ai.block_size, rows=list(ai.rows[:L]), nnz=list(ai.nnz[:L]),
+                lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
+                setup_seconds=ai.setup_seconds)
+
+
+def _amg_matrix(fn, level, which):
+    """scipy-free CSR triple (rowptr, colidx, val, shape) of one matrix of a level, through a sized two-call getter."""
+    nr, nc, nz = C.c_int32(), C.c_int32(), C.c_int64()
+    fn(level, which, C.byref(nr), C.byref(nc), C.byref(nz), None, None, None)
+    rp = np.zeros(nr.value + 1, np.int32)
+    ci = np.zeros(nz.value, np.int32)
+    v = np.zeros(nz.value, np.float64)
+    fn(level, which, C.byref(nr), C.byref(nc), C.byref(nz), rp.ctypes.data, ci.ctypes.data, v.ctypes.data)
+    return rp, ci, v, (nr.value, nc.value)
+
+
+class AmgHierarchy:
+    """Host-only multigrid hierarchy (spk_amg_build_host): the set-up the context runs at spk_pc_setup, without a GPU."""
+
+    def __init__(self, A, **kw):
+        self.h = C.c_void_p()
+        o = amg_opts(**kw)
+        rc = lib.spk_amg_build_host(A.nrows, A.rowptr, A.colidx, A.val, C.byref(o), C.byref(self.h))
+        if rc != 0:
+            raise SpkError(rc, lib.spk_last_error(None).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SpkError(rc, lib.spk_last_error(None).decode())
+
+    def info(self):
+        ai = AmgInfo()
+        self._chk(lib.spk_amg_host_info(self.h, C.byref(ai)))
+        return _amg_info(ai)
+
+    def matrix(self, level, which=AMG_OP):
+        return _amg_matrix(lambda *a: self._chk(lib.spk_amg_host_level(self.h, *a)), level, which)
+
+    def aggregates(self, level):
+        n = C.c_int32()
+        self._chk(lib.spk_amg_host_aggregates(self.h, level, C.byref(n), None))
+        agg = np.zeros(n.value, np.int32)
+        self._chk(lib.spk_amg_host_aggregates(self.h, level, C.byref(n), agg.ctypes.data))
+        return agg
+
+    def close(self):
+        if self.h:
+            lib.spk_amg_destroy_host(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
 
 
 def unique_id():
@@ -184,10 +266,28 @@ class Context:
         self._chk(lib.spk_set_block(self.h, which, A.row_begin if which == BLOCK_A00 else 0, nrows,
                                     A.ncols, A.rowptr, A.colidx, A.val))
 
-    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0):
-        """inner_sweeps > 0: FP32 damped-Jacobi Richardson sweeps stand for diag(A)^-1."""
-        self._chk(lib.spk_pc_set_inner(self.h, inner_sweeps, inner_omega))
+    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None):
+        """inner_sweeps > 0: FP32 damped-Jacobi Richardson sweeps stand for diag(A)^-1.
+        amg: None (off), True (defaults) or a dict of spk_amg_opts fields: one smoothed-aggregation V-cycle stands
+        for A^-1 (PC_JACOBI: M^-1 on K = A; PC_SCHUR: inside the fieldsplit)."""
+        if amg is None or amg is False:
+            self._chk(lib.spk_pc_set_amg(self.h, None))
+            self._chk(lib.spk_pc_set_inner(self.h, inner_sweeps, inner_omega))
+        else:
+            self._chk(lib.spk_pc_set_inner(self.h, inner_sweeps, inner_omega))
+            o = amg_opts(**({} if amg is True else dict(amg)))
+            self._chk(lib.spk_pc_set_amg(self.h, C.byref(o)))
         self._chk(lib.spk_pc_setup(self.h, pc_type, schur_fact))
+
+    def amg_info(self):
+        """levels, rows / nnz / lambda_max per level, operator complexity, set-up seconds of the multigrid hierarchy."""
+        ai = AmgInfo()
+        self._chk(lib.spk_get_amg_info(self.h, C.byref(ai)))
+        return _amg_info(ai)
+
+    def amg_level(self, level, which=AMG_OP):
+        """(rowptr, colidx, val, shape) of A_l (AMG_OP), P_l (AMG_PROLONG), the tentative P_l or the coarse inverse."""
+        return _amg_matrix(lambda *a: self._chk(lib.spk_get_amg_level(self.h, *a)), level, which)
 
     def sizes(self):
         ng, nl, m, nnz, gh = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
@@ -432,6 +532,12 @@ class KSP:
         o, pc, sf = Opts(), C.c_int32(), C.c_int32()
         lib.SpkKSPGetOptions(self.h, C.byref(o), C.byref(pc), C.byref(sf))
         return o, pc.value, sf.value
+
+    def getAMGOptions(self, fieldsplit0=False):
+        """(options dict, selected) of the plain (-pc_type gamg) or the -fieldsplit_0_ multigrid option set."""
+        o, sel = AmgOpts(), C.c_int32()
+        self._chk(lib.SpkKSPGetAMGOptions(self.h, 1 if fieldsplit0 else 0, C.byref(o), C.byref(sel)))
+        return amg_opts_dict(o), bool(sel.value)
 
     def getType(self):
         """-ksp_type as set: 'fgmres', 'minres', or '' before setFromOptions gave one."""

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""The smoothed-aggregation multigrid preconditioner (-pc_type gamg) against Jacobi FGMRES and MINRES on one GPU, in
+one process:
+    python tools/gamg_bench.py [--grids 256 512 1024] [--rtol 1e-8] [--max-it 20000]
+Two systems: K = A (gamg in Jacobi's slot; FGMRES + Jacobi; MINRES + Jacobi) and the saddle system with Schur FULL
+(-fieldsplit_0_pc_type gamg; FGMRES + the plain Schur FULL; MINRES + Schur DIAG).  Per gamg row: host set-up time,
+levels, rows and operator complexity, the V-cycle's time (spk_pc_apply on device vectors, back to back) against its
+byte model per level, iterations and wall time to rtol.  One JSON line per row."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import saddle_point_petsc_amd as S  # noqa: E402
+
+PEAK = 8.0e12
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--grids", type=int, nargs="+", default=[256, 512, 1024])
+ap.add_argument("--rtol", type=float, default=1e-8)
+ap.add_argument("--max-it", type=int, default=20000)
+ap.add_argument("--gamg-only", action="store_true", help="leave out the Jacobi / MINRES rows (a short kernel trace)")
+a = ap.parse_args()
+
+
+def csr_bytes(nnz, n):
+    return 12 * nnz + 4 * (n + 1)
+
+
+def vcycle_model(c, info, nu):
+    """Bytes one V-cycle moves, per level, for Chebyshev smoothing (beta_0 = 0, beta_k != 0 after: the step reads y-).
+    A step from the zero guess (the first pre-smoothing step) moves dinv, b and out.  Level 0 on the 2x2 row-type
+    layout: the fused step streams the layout (spmv_info: codes + y gathered + out written) and dinv, b (, y-); other
+    layouts: the layout's product, then a pass over dinv, b, t, y (, y-), out.  Levels >= 1: CSR (12 B per entry + row
+    pointers), the fused step reads x, dinv, b (, y-) and writes out.  Per level besides: the residual product, the
+    restriction R (b - t) (R, b, t, the coarse b), the prolongation y += P e (P, y read and written, e); level 0 the
+    output copy; the coarsest level the dense inverse."""
+    L = info["levels"]
+    betas = [0] + [1] * (nu - 1)
+    steps_from_y = betas[1:] + betas   # pre-smoothing after its zero-guess step, then all of post-smoothing
+    fused0 = c.spmv_info()["format"] == "dict2x2"
+    per = []
+    for l in range(L):
+        n = info["rows"][l]
+        v = 8 * n
+        if l == L - 1:
+            per.append(8 * n * n + 2 * v)
+            continue
+        rp, ci, _, shp = c.amg_level(l, S.AMG_PROLONG)
+        pnnz, nc = len(ci), shp[1]
+        if l == 0:
+            prod = c.spmv_info()["layout_bytes"]
+            step = (lambda be: prod + 2 * v + be * v) if fused0 else (lambda be: prod + 5 * v + be * v)
+            res = prod
+        else:
+            prod = csr_bytes(info["nnz"][l], n)
+            step = lambda be: prod + 4 * v + be * v
+            res = prod + 2 * v
+        steps = 3 * v + sum(step(be) for be in steps_from_y)
+        restrict = csr_bytes(pnnz, nc) + 2 * v + 8 * nc
+        prolong = csr_bytes(pnnz, n) + 2 * v + 8 * nc
+        per.append(steps + res + restrict + prolong + (2 * v if l == 0 else 0))
+    fine_step = (c.spmv_info()["layout_bytes"] + 3 * 8 * info["rows"][0]) if fused0 else None
+    return per, fine_step
+
+
+def ctx(A, B, pc, fact, amg=None):
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    if B is not None:
+        c.set_block(S.BLOCK_A10, B)
+    t0 = time.perf_counter()
+    c.pc_setup(pc, fact, amg=amg)
+    return c, time.perf_counter() - t0
+
+
+def solve(c, rhs, solver, **kw):
+    fn = c.fgmres if solver == "fgmres" else c.minres
+    fn(rhs, rtol=0.0, abstol=0.0, max_it=5)   # first-use allocations
+    x, info = fn(rhs, rtol=a.rtol, max_it=a.max_it, **kw)
+    true = np.linalg.norm(rhs - c.mult(x)) / np.linalg.norm(rhs)
+    return dict(its=info["its"], reason=info["reason"], seconds=round(info["solve_seconds"], 4), true_rel_res=float(true))
+
+
+for grid in a.grids:
+    A, f = S.AssembleOperator_Laplace(grid)
+    B, g = S.AssembleOperator_Constraints(grid)
+    for system, Bk, rhs, pc, fact, fact_mr in (("A", None, f, S.PC_JACOBI, 0, 0),
+                                               ("saddle_full", B, np.concatenate([f, g]), S.PC_SCHUR, S.SCHUR_FULL,
+                                                S.SCHUR_DIAG)):
+        c, setup_wall = ctx(A, Bk, pc, fact, amg=True)
+        info = c.amg_info()
+        vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+        c.pc_setup(S.PC_JACOBI, 0, amg=True)   # the V-cycle alone (K = A slot) for the per-level model and timing
+        vc_only_ms = c.time_kernel("pc", warmup=5, reps=50)
+        model, fine_step = vcycle_model(c, info, 2)
+        c.close()
+        c, _ = ctx(A, Bk, pc, fact, amg=True)
+        conv = solve(c, rhs, "fgmres")
+        c.close()
+        tot = sum(model)
+        print(json.dumps(dict(system=system, grid=grid, solver="fgmres", pc="gamg", setup_seconds=round(setup_wall, 3),
+                              host_setup_seconds=round(info["setup_seconds"], 3), levels=info["levels"],
+                              rows=info["rows"], operator_complexity=round(info["operator_complexity"], 4),
+                              lambda_max=[round(x, 4) for x in info["lambda_max"]], pc_apply_us=round(vc_ms * 1e3, 1),
+                              vcycle_us=round(vc_only_ms * 1e3, 1), vcycle_model_bytes=tot, vcycle_model_per_level=model,
+                              vcycle_frac_peak=round(tot / (vc_only_ms * 1e-3) / PEAK, 3),
+                              fine_step_model_bytes=fine_step, **conv)), flush=True)
+        if a.gamg_only:
+            continue
+        c, _ = ctx(A, Bk, pc, fact)
+        print(json.dumps(dict(system=system, grid=grid, solver="fgmres", pc="jacobi" if Bk is None else "schur_full",
+                              **solve(c, rhs, "fgmres"))), flush=True)
+        c.close()
+        c, _ = ctx(A, Bk, pc, fact_mr)
+        print(json.dumps(dict(system=system, grid=grid, solver="minres", pc="jacobi" if Bk is None else "schur_diag",
+                              **solve(c, rhs, "minres"))), flush=True)
+        c.close()
