@@ -69,7 +69,8 @@ enum { SPK_SPMV_CSR = 0 };
 enum { SPK_CONVERGED_RTOL = 2, SPK_CONVERGED_ATOL = 3, SPK_CONVERGED_ITS = 4,
        SPK_CONVERGED_HAPPY_BREAKDOWN = 7, SPK_DIVERGED_NULL = -2,
        SPK_DIVERGED_ITS = -3, SPK_DIVERGED_DTOL = -4, SPK_DIVERGED_BREAKDOWN = -5,
-       SPK_DIVERGED_INDEFINITE_PC = -8, SPK_DIVERGED_NANORINF = -9, SPK_ITERATING = 0 };
+       SPK_DIVERGED_INDEFINITE_PC = -8, SPK_DIVERGED_NANORINF = -9, SPK_DIVERGED_INDEFINITE_MAT = -10,
+       SPK_ITERATING = 0 };
 
 /* Solver options = the slice of the PETSc options database the reference
  * exposes through KSPSetFromOptions (SaddlePointProblem.c:67).  Fill with
@@ -151,7 +152,7 @@ typedef struct spk_result {
     double rnorm0;          /* residual norm at iteration 0 */
     int32_t hist_len;       /* entries written to history[] */
     int32_t cycles;         /* restart cycles executed */
-    double solve_seconds;   /* wall time inside spk_fgmres / spk_minres, upload excluded */
+    double solve_seconds;   /* wall time inside spk_fgmres / spk_minres / spk_pipecg, upload excluded */
 } spk_result;
 
 /* ---- lifetime (KSPCreate / KSPDestroy, SaddlePointProblem.c:65,72) ------- */
@@ -265,7 +266,7 @@ int spk_pc_set_inner(spk_ctx *ctx, int sweeps, double omega);
  * M^-1 = one V-cycle on A (no B block), SPK_PC_SCHUR takes the V-cycle wherever it takes diag(A)^-1 (S^ stays
  * diag(B diag(A)^-1 B^T)).  spk_fgmres runs it on the step-by-step path (spk_get_iteration_form reports -1).
  * Out of scope, refused with SPK_ERR_UNSUPPORTED: more than one rank (at spk_pc_setup; the context stays usable),
- * spk_minres with it, and FP32 inner sweeps beside it (spk_pc_set_inner > 0 and spk_pc_set_amg are exclusive). */
+ * spk_minres with it (spk_pipecg takes it on K = A), and FP32 inner sweeps beside it (spk_pc_set_inner > 0 and spk_pc_set_amg are exclusive). */
 enum { SPK_AMG_CHEBYSHEV = 0, SPK_AMG_RICHARDSON = 1 };
 #define SPK_AMG_MAX_LEVELS 16
 #define SPK_AMG_MAX_COARSE 1024
@@ -351,6 +352,28 @@ int spk_fgmres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts
  * confirmed at the end; result.cycles = recurrence (re)starts. */
 enum { SPK_NORM_UNPRECONDITIONED = 0, SPK_NORM_NATURAL = 1 };
 int spk_minres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts, int norm_type,
+               spk_result *result, double *history, int32_t history_cap);
+
+/* KSP type pipecg: preconditioned pipelined CG (Ghysels-Vanroose 2014, Alg. 3; PETSc KSPPIPECG) on the device, for a
+ * symmetric positive definite K = A (no constraint block: a context with one is refused with SPK_ERR_UNSUPPORTED, the
+ * saddle matrix is indefinite -- use spk_minres) and PC none, Jacobi or the V-cycle (spk_pc_set_amg).  The Schur
+ * preconditioners and FP32 inner sweeps are refused with SPK_ERR_UNSUPPORTED.  A short recurrence with ONE reduction per
+ * iteration whose scalars are ready a pass before they are needed: with none / Jacobi an iteration is the product n = K m
+ * plus one pass that applies the eight updates (u = D r and q = D s formed in the pass, not stored), writes m = D w for
+ * the next product and reduces [<r, u>, <w, u>, r.r]; the scalar step runs in the finishing workgroup of that pass (one
+ * rank) or as a one-thread launch after the all-reduce, which goes behind the next product.  With the V-cycle,
+ * m = M^-1 w runs before the product and u, q are recurrences.  Its own work vectors (allocated on first use; nothing of
+ * spk_fgmres's or spk_minres's workspace or state is touched).
+ * norm_type: SPK_NORM_UNPRECONDITIONED (||b - K x||) or SPK_NORM_NATURAL (sqrt(<r, M^-1 r>)), tested by
+ * KSPConvergedDefault as in spk_minres.  A convergence (or -ksp_max_it) seen by the recurrence is confirmed on the true
+ * b - K x; if that misses ttol the recurrence restarts from the current x (residual replacement), so result.rnorm is
+ * always the true norm.  <r, M^-1 r> < 0 ends the solve with SPK_DIVERGED_INDEFINITE_PC, a non-positive step-length
+ * denominator (delta - beta gamma / alpha_old) with SPK_DIVERGED_INDEFINITE_MAT (reasons, not errors).
+ * opts: max_it, rtol, abstol, dtol, guess_nonzero, check_every, fused (0: PCApply as a launch of its own and the sums in
+ * a second pass, same recurrence and summation order); restart, orthog, cgs_refine, single_reduce and iteration_form are
+ * ignored.  history[0] = the initial residual norm, then one recurrence value per iteration; result.cycles =
+ * recurrence (re)starts. */
+int spk_pipecg(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts, int norm_type,
                spk_result *result, double *history, int32_t history_cap);
 
 /* How the LAST spk_fgmres on ctx launched its iterations: *form = the SPK_ITER_* actually run (AUTO resolved; options

@@ -180,6 +180,7 @@ def _load():
     L.spk_pc_apply.argtypes = [vp, f64p, f64p, C.c_int]
     L.spk_fgmres.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(Opts), C.POINTER(Result), vp, i32]
     L.spk_minres.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32]
+    L.spk_pipecg.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32]
     L.spk_vec_create.argtypes = [vp, i64, C.POINTER(vp)]
     L.spk_vec_destroy.argtypes = [vp, vp]
     L.spk_vec_set.argtypes = [vp, vp, f64p, i64]

@@ -112,8 +112,10 @@ int spk_destroy(spk_ctx *c)
         if (i == 0 && c->state_ev) (void)hipEventDestroy(c->state_ev);
         if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
         if (c->mr_ev[i]) (void)hipEventDestroy(c->mr_ev[i]);
+        if (c->pc_ev[i]) (void)hipEventDestroy(c->pc_ev[i]);
     }
     if (c->mr_pin) (void)hipHostFree(c->mr_pin);
+    if (c->pc_pin) (void)hipHostFree(c->pc_pin);
     for (hipEvent_t e : c->tp_ev) (void)hipEventDestroy(e);
     delete c;  // DevBuf destructors free device memory
     if (s) (void)hipStreamDestroy(s);
@@ -483,6 +485,31 @@ int spk_minres(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *
         SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
         if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
         spk::minres(c, rh, xs, *opts, norm_type, result, history, history_cap);
+        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+    }
+    SPK_CATCH(c)
+}
+
+int spk_pipecg(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *opts, int norm_type, spk_result *result,
+               double *history, int32_t history_cap)
+{
+    SPK_TRY(c)
+    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_pipecg: null argument");
+    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_pipecg: no operator");
+    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
+        spk::fail(SPK_ERR_ARG, "spk_pipecg: tolerances must be non-negative, max_it >= 0");
+    if (norm_type != SPK_NORM_UNPRECONDITIONED && norm_type != SPK_NORM_NATURAL)
+        spk::fail(SPK_ERR_ARG, "spk_pipecg: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", norm_type);
+    c->ensure_vectors();
+    const int64_t N = (int64_t)c->n_local + c->m;
+    std::memset(result, 0, sizeof *result);
+    if (mem == SPK_MEM_DEVICE) {
+        spk::pipecg(c, b, x, *opts, norm_type, result, history, history_cap);
+    } else {
+        double *xs = c->xsol.p, *rh = c->rhs.p;
+        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        spk::pipecg(c, rh, xs, *opts, norm_type, result, history, history_cap);
         SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
     }
     SPK_CATCH(c)

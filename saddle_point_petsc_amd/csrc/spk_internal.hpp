@@ -359,6 +359,19 @@ struct MinresState {
     double wx_ig, wx_a2, wx_a3, wx_ia1, wx_cx;  // w_{j+1} = (ig z_j - a3 w_{j-1} - a2 w_j) ia1 ;  x += cx w_{j+1}
 };
 
+// pipelined CG state (spk_pipecg): the convergence words of KrylovState (converged_default) and the scalar recurrence
+struct PipecgState {
+    KrylovState ks;
+    int32_t norm;     // SPK_NORM_*
+    int32_t first;    // the next pass is the first of a recurrence (z = n, s = w, p = u, q = m)
+    int32_t tent;     // ks.reason was set by the recurrence alone: confirmed on b - K x
+    int32_t starts;   // recurrence (re)starts
+    int32_t started;  // rnorm0 / ttol fixed
+    int32_t pad;
+    double alpha, beta;   // step lengths of the next pass
+    double gamma;         // <r, u> of the pass before it (gamma_old)
+};
+
 // kernel launch wrappers (spk_k_*.hip)
 namespace k {
 constexpr int kMaxNv = 64;       // max vectors in one mdot/maxpy launch; restart <= 62 takes the fused kernels
@@ -691,6 +704,27 @@ void minres_wd(int wx, const double *zp, const double *pp, double *wm, const dou
                const MinresState *ms, MrStep step, const Finish &f, const int32_t *done, hipStream_t s);
 void minres_init(MinresState *ms, const spk_opts &o, int norm, hipStream_t s);
 void minres_scalar(MrStep step, const double *sums, const int32_t *done, hipStream_t s);
+// pipelined CG (spk_k_pipecg.hip).  Scalar steps, run by the finishing workgroup of the pass that reduces their sums (one
+// rank) or by pipecg_scalar after the all-reduce: sums = [<r, u>, <w, u>, r.r]
+enum { kPcBnorm = 0, kPcBegin = 1, kPcStart = 2, kPcIter = 3 };
+struct PcStep {
+    PipecgState *ps;
+    int mode;            // kPc*, < 0: no step in the kernel (several ranks)
+    double *hist;
+    int32_t hist_cap;
+};
+// r = b - kx (kx == nullptr: r = b; b is read without its pad); u = uin, or D r (dinv; nullptr: r) written to uout when
+// given; sums (sums != 0) = [<r, u>, 0, r.r] over the first n_dot entries.  Not gated.
+void pipecg_begin(const double *b, const double *kx, double *r, const double *uin, double *uout, const double *dinv, int sums,
+                  int64_t n, int64_t n_dot, const PipecgState *ps, PcStep step, const Finish &f, hipStream_t s);
+// upd: z = n + b z, s = w + b s, p = u + b p, x += a p, r -= a s, w -= a z (first: no old z / s / p / q read), with urec
+// also q = m + b q, u -= a q; u == nullptr: u = D r (dinv; nullptr: u = r) in the pass; mout: D w written.  upd = 0:
+// only the sums (and mout) of the vectors as they are.  sums = [<r, u>, <w, u>, r.r]
+void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, double *s_, double *p, double *x, double *r,
+                 double *w, double *u, double *q, const double *m, double *mout, const double *dinv, int64_t n, int64_t n_dot,
+                 const PipecgState *ps, PcStep step, const Finish &f, const int32_t *done, hipStream_t s);
+void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s);
+void pipecg_scalar(PcStep step, const double *sums, const int32_t *done, hipStream_t s);
 void krylov_init(const KrylovArrays &ka, const spk_opts &o, const double *bnorm2, hipStream_t s);
 void krylov_cycle_begin(const KrylovArrays &ka, const double *nrm2, hipStream_t s, double *tb = nullptr, int m = 0,
                         double *sc = nullptr, const StateReport *report = nullptr);
@@ -856,6 +890,13 @@ struct spk_ctx {
     spk::DevBuf<spk::MinresState> mr_st;
     void *mr_pin = nullptr;                  // pinned landing place of the state read-back
     hipEvent_t mr_ev[2] = {nullptr, nullptr};
+    // pipelined CG workspace (spk_pipecg, allocated on first use; nothing of FGMRES's or MINRES's is touched)
+    int64_t pc_ld = 0;
+    spk::DevBuf<double> pc_vec;              // kPcVecs vectors of stride ld
+    spk::DevBuf<double> pc_out, pc_hist;     // reduced sums, residual history
+    spk::DevBuf<spk::PipecgState> pc_st;
+    void *pc_pin = nullptr;                  // pinned landing place of the state read-back
+    hipEvent_t pc_ev[2] = {nullptr, nullptr};
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist
     spk::DevBuf<spk::KrylovState> kst;
     spk::k::KrylovArrays ka{};
@@ -889,6 +930,8 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);
 void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,
+            double *history, int32_t history_cap);
+void pipecg(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,
             double *history, int32_t history_cap);
 // what the two drivers share: the checks they start with (an operator, KSPSetUp done) ...
 void require_setup(spk_ctx *c, const char *who);

@@ -1,0 +1,363 @@
+// spk_k_pipecg.hip -- the vector passes and the scalar step of the device-resident pipelined CG (spk_pipecg;
+// Ghysels-Vanroose 2014 Alg. 3 in the order of PETSc's KSPSolve_PIPECG), K = A only.
+// Per iteration (one rank, none / Jacobi):
+//   product       n = K m                                       (the product kernels, unchanged; m = w without a PC)
+//   pipecg_pass   z = n + b z, s = w + b s, p = u + b p, x += a p, r -= a s, w -= a z, u = D r, m = D w,
+//                 sums [<r, u>, <w, u>, r.r]                     finisher: the test, then alpha / beta of the next pass
+// With a diagonal M^-1 (none, Jacobi) u = D r and q = D s are formed in the pass and never stored.  With the V-cycle (or
+// opts.fused = 0) m = M^-1 w runs through op_pc_apply before the product; the V-cycle keeps u and q as recurrences
+// (q = m + b q, u -= a q), the step-by-step path recomputes u = M^-1 r with a launch of its own and takes the sums in a
+// second pass of this kernel, in the same order.
+// Summation orders are fixed (block partials + the sentinel finish of spk_device.hpp): identical solves, identical bits.
+#include "spk_device.hpp"
+
+namespace spk {
+namespace k {
+
+// One step of the scalar work; sums = the reduced [<r, u>, <w, u>, r.r] of the pass that ran before it.
+__device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, double *hist, int32_t hist_cap)
+{
+    KrylovState *st = &ps->ks;
+    const bool natural = ps->norm == SPK_NORM_NATURAL;
+    const double g = sums[0], d = sums[1];
+    const double rn = natural ? sqrt(fabs(g)) : sqrt(sums[2]);
+    if (mode == kPcBnorm) {   // [<M^-1 b, b>, -, b.b]: ||b|| in the norm of the test (-ksp_initial_guess_nonzero)
+        st->bnorm = rn;
+        return;
+    }
+    if (mode == kPcBegin) {   // r = b - K x, u = M^-1 r: start, confirmation, restart
+        st->rnorm = rn;
+        if (!ps->started) {
+            // KSPConvergedDefault at iteration 0: zero guess -> the initial residual, nonzero guess -> ||b|| (or the
+            // initial residual when b = 0), both in the norm of the test
+            ps->started = 1;
+            double snorm = rn;
+            if (st->guess_nonzero) {
+                snorm = st->bnorm;
+                if (snorm == 0.0) snorm = rn;
+            }
+            st->rnorm0 = rn;
+            st->cnorm0 = snorm;
+            st->ttol = fmax(st->rtol * snorm, st->abstol);
+            if (hist_cap > 0) hist[0] = rn;
+        } else if (st->done && !ps->tent) {
+            return;   // a final verdict of the recurrence (indefinite PC or matrix, breakdown, divergence) stands
+        }
+        int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
+        if (!reason && st->its >= st->max_it) reason = SPK_DIVERGED_ITS;
+        if (!reason && !(g > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;   // M^-1 r = 0 with r != 0
+        ps->tent = 0;
+        st->reason = reason;
+        if (reason) {
+            st->done = 1;
+            return;
+        }
+        ps->starts += 1;
+        st->done = 0;
+        return;
+    }
+    if (mode == kPcStart) {   // w = K u: the first step length of the recurrence
+        if (!(d > 0.0)) {
+            st->reason = isnan(d) ? SPK_DIVERGED_NANORINF : SPK_DIVERGED_INDEFINITE_MAT;
+            ps->tent = 0;
+            st->done = 1;
+            return;
+        }
+        ps->first = 1;
+        ps->alpha = g / d;
+        ps->beta = 0.0;
+        ps->gamma = g;
+        return;
+    }
+    // kPcIter: the pass has applied iteration its + 1; its test, then the scalars of the next pass
+    st->its += 1;
+    st->rnorm = rn;
+    if (st->its < hist_cap) hist[st->its] = rn;
+    int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
+    ps->tent = 0;
+    if (reason > 0) ps->tent = 1;   // the recurrence alone: b - K x confirms it
+    else if (!reason && st->its >= st->max_it) {
+        reason = SPK_DIVERGED_ITS;
+        ps->tent = 1;
+    }
+    if (!reason && !(g > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;
+    double beta = 0.0, den = 0.0;
+    if (!reason) {
+        beta = g / ps->gamma;
+        den = d - beta * g / ps->alpha;
+        // = <p, K p> gamma / alpha in exact arithmetic.  After the first pass of a recurrence its sign is the matrix's;
+        // later the recurrences of w, s, z (and u, q) have drifted from K u, K p, K s (the residual gap of pipelined CG)
+        // and the sign may flip on an SPD matrix: b - K x then decides (confirmation, or a restart that computes
+        // <K u, u> afresh)
+        if (isnan(den)) reason = SPK_DIVERGED_NANORINF;
+        else if (!(den > 0.0)) {
+            reason = SPK_DIVERGED_INDEFINITE_MAT;
+            ps->tent = !ps->first;
+        }
+    }
+    if (reason) {
+        st->reason = reason;
+        st->done = 1;
+        return;
+    }
+    ps->first = 0;
+    ps->beta = beta;
+    ps->alpha = g / den;
+    ps->gamma = g;
+}
+
+// block partials of three sums, then (last workgroup) the reduction and the scalar step
+__device__ __forceinline__ void pcg_finish(double a0, double a1, double a2, double *red, double *partials, double *out,
+                                           FinErr fe, PipecgState *ps, const PcStep &step)
+{
+    const double s0 = wave_sum(a0), s1 = wave_sum(a1), s2 = wave_sum(a2);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s0;
+        red[kVWaves + (threadIdx.x >> 6)] = s1;
+        red[2 * kVWaves + (threadIdx.x >> 6)] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVWaves; ++j) {
+            t0 += red[j];
+            t1 += red[kVWaves + j];
+            t2 += red[2 * kVWaves + j];
+        }
+        double *row = partials + (size_t)blockIdx.x * kPartialLd;
+        publish(row, t0);
+        publish(row + 1, t1);
+        publish(row + 2, t2);
+    }
+    if (!arrive_last(gridDim.x)) return;
+    final_reduce(partials, gridDim.x, kPartialLd, 3, red, fe);
+    if (threadIdx.x == 0) {
+        out[0] = red[0];
+        out[1] = red[1];
+        out[2] = red[2];
+        if (step.mode >= 0) pipecg_step(ps, step.mode, red, step.hist, step.hist_cap);
+    }
+}
+
+__device__ __forceinline__ double2 ldv(const double *p, int64_t i) { return reinterpret_cast<const double2 *>(p)[i]; }
+__device__ __forceinline__ void stv(double *p, int64_t i, double2 v) { reinterpret_cast<double2 *>(p)[i] = v; }
+
+// the pair (e, e + 1) of an unpadded caller vector (b): the entry past n is not read
+__device__ __forceinline__ double2 ld_tail(const double *p, int64_t e, int64_t n)
+{
+    double2 v;
+    v.x = e < n ? p[e] : 0.0;
+    v.y = e + 1 < n ? p[e + 1] : 0.0;
+    return v;
+}
+
+__device__ __forceinline__ double2 dscale(const double *dinv, int64_t i, double2 v)
+{
+    if (!dinv) return v;
+    const double2 d = ldv(dinv, i);
+    return double2{v.x * d.x, v.y * d.y};
+}
+
+struct BeginArgs {
+    const double *b, *kx;
+    double *r;
+    const double *uin;   // u = M^-1 r from a launch of its own (nullptr: u = D r here)
+    double *uout;        // u = D r written for the product (nullptr: not stored)
+    const double *dinv;
+    int sums;
+    int64_t n, n2, n_dot;
+    PipecgState *ps;
+    PcStep step;
+    double *partials, *out;
+    FinErr fe;
+};
+
+__global__ __launch_bounds__(kVT) void pipecg_begin_kernel(BeginArgs a)
+{
+    __shared__ double red[kVT];
+    double ag = 0.0, ar = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < a.n2; i += (int64_t)gridDim.x * kVT) {
+        const int64_t e = 2 * i;
+        double2 r = ld_tail(a.b, e, a.n);
+        if (a.kx) {
+            const double2 t = ldv(a.kx, i);
+            r.x -= t.x;
+            r.y -= t.y;
+        }
+        if (e + 1 >= a.n) r.y = 0.0;   // (the pad entry of an odd length stays zero)
+        stv(a.r, i, r);
+        const double2 u = a.uin ? ldv(a.uin, i) : dscale(a.dinv, i, r);
+        if (a.uout) stv(a.uout, i, u);
+        if (e < a.n_dot) {
+            ag += r.x * u.x;
+            ar += r.x * r.x;
+        }
+        if (e + 1 < a.n_dot) {
+            ag += r.y * u.y;
+            ar += r.y * r.y;
+        }
+    }
+    if (a.sums) pcg_finish(ag, 0.0, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+}
+
+void pipecg_begin(const double *b, const double *kx, double *r, const double *uin, double *uout, const double *dinv, int sums,
+                  int64_t n, int64_t n_dot, const PipecgState *ps, PcStep step, const Finish &f, hipStream_t s)
+{
+    const int64_t n2 = (n + 1) / 2;
+    BeginArgs a{b, kx, r, uin, uout, dinv, sums, n, n2, n_dot, const_cast<PipecgState *>(ps), step, f.partials, f.out,
+                FinErr{f.err, f.fin_ticks}};
+    hipLaunchKernelGGL(pipecg_begin_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
+}
+
+struct PassArgs {
+    int upd, urec, sums;
+    const double *nv;
+    double *z, *s, *p, *x, *r, *w;
+    double *u, *q;        // u: read (and with urec updated: u -= a q, q = m + b q); nullptr: u = D r in the pass
+    const double *m;      // urec: m = M^-1 w of the product's input
+    double *mout;         // m = D w written for the next product (nullptr: not stored)
+    const double *dinv;
+    int64_t n2, n_dot;
+    PipecgState *ps;
+    PcStep step;
+    double *partials, *out;
+    FinErr fe;
+    const int32_t *done;
+};
+
+// Every load of an element pair is issued before the arithmetic that needs it (8 streams in flight per thread on the
+// Jacobi path: n, z, w, s, p, x, r, dinv).
+__global__ __launch_bounds__(kVT) void pipecg_pass_kernel(PassArgs a)
+{
+    if (a.done && *a.done) return;
+    __shared__ double red[kVT];
+    double al = 0.0, be = 0.0;
+    int first = 0;
+    if (a.upd) {
+        al = a.ps->alpha;
+        be = a.ps->beta;
+        first = a.ps->first;
+    }
+    double ag = 0.0, ad = 0.0, ar = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < a.n2; i += (int64_t)gridDim.x * kVT) {
+        const int64_t e = 2 * i;
+        double2 w = ldv(a.w, i), r = ldv(a.r, i);
+        double2 u;
+        if (a.upd) {
+            const double2 nn = ldv(a.nv, i);
+            double2 x = ldv(a.x, i);
+            double2 z, s, p;
+            double2 dv = a.dinv ? ldv(a.dinv, i) : double2{1.0, 1.0};
+            double2 uo = a.u ? ldv(a.u, i) : r;
+            double2 mm{0.0, 0.0}, q{0.0, 0.0};
+            if (a.urec) mm = ldv(a.m, i);
+            if (first) {
+                z = nn;
+                s = w;
+                if (a.urec) q = mm;
+            } else {
+                z = ldv(a.z, i);
+                s = ldv(a.s, i);
+                p = ldv(a.p, i);
+                if (a.urec) q = ldv(a.q, i);
+                z.x = nn.x + be * z.x;
+                z.y = nn.y + be * z.y;
+                s.x = w.x + be * s.x;
+                s.y = w.y + be * s.y;
+                if (a.urec) {
+                    q.x = mm.x + be * q.x;
+                    q.y = mm.y + be * q.y;
+                }
+            }
+            if (!a.u && a.dinv) uo = double2{r.x * dv.x, r.y * dv.y};
+            if (first) p = uo;
+            else {
+                p.x = uo.x + be * p.x;
+                p.y = uo.y + be * p.y;
+            }
+            x.x += al * p.x;
+            x.y += al * p.y;
+            r.x -= al * s.x;
+            r.y -= al * s.y;
+            w.x -= al * z.x;
+            w.y -= al * z.y;
+            stv(a.z, i, z);
+            stv(a.s, i, s);
+            stv(a.p, i, p);
+            stv(a.x, i, x);
+            stv(a.r, i, r);
+            stv(a.w, i, w);
+            if (a.urec) {
+                uo.x -= al * q.x;
+                uo.y -= al * q.y;
+                stv(a.q, i, q);
+                stv(a.u, i, uo);
+                u = uo;
+            } else if (!a.u) {
+                u = a.dinv ? double2{r.x * dv.x, r.y * dv.y} : r;
+            } else {
+                u = uo;   // (the step-by-step path: stale, its sums come from the next pass)
+            }
+            if (a.mout) stv(a.mout, i, double2{w.x * dv.x, w.y * dv.y});
+        } else {
+            u = a.u ? ldv(a.u, i) : dscale(a.dinv, i, r);
+            if (a.mout) stv(a.mout, i, dscale(a.dinv, i, w));
+        }
+        if (e < a.n_dot) {
+            ag += r.x * u.x;
+            ad += w.x * u.x;
+            ar += r.x * r.x;
+        }
+        if (e + 1 < a.n_dot) {
+            ag += r.y * u.y;
+            ad += w.y * u.y;
+            ar += r.y * r.y;
+        }
+    }
+    if (a.sums) pcg_finish(ag, ad, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+}
+
+void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, double *s_, double *p, double *x, double *r,
+                 double *w, double *u, double *q, const double *m, double *mout, const double *dinv, int64_t n, int64_t n_dot,
+                 const PipecgState *ps, PcStep step, const Finish &f, const int32_t *done, hipStream_t s)
+{
+    const int64_t n2 = (n + 1) / 2;
+    PassArgs a{upd, urec, sums, nv, z, s_, p, x, r, w, u, q, m, mout, dinv, n2, n_dot, const_cast<PipecgState *>(ps), step,
+               f.partials, f.out, FinErr{f.err, f.fin_ticks}, done};
+    hipLaunchKernelGGL(pipecg_pass_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
+}
+
+__global__ void pipecg_init_kernel(PipecgState *ps, spk_opts o, int norm)
+{
+    if (threadIdx.x != 0) return;
+    PipecgState z{};
+    z.ks.max_it = o.max_it;
+    z.ks.rtol = o.rtol;
+    z.ks.abstol = o.abstol;
+    z.ks.dtol = o.dtol;
+    z.ks.guess_nonzero = o.guess_nonzero;
+    z.ks.ttol = o.abstol;
+    z.ks.done = 1;   // no iteration runs before the first kPcBegin
+    z.norm = norm;
+    *ps = z;
+}
+void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s)
+{
+    hipLaunchKernelGGL(pipecg_init_kernel, dim3(1), dim3(64), 0, s, ps, o, norm);
+}
+
+// several ranks: the step after the all-reduce of the sums (the iteration steps are gated like the passes)
+__global__ void pipecg_scalar_kernel(PcStep step, const double *sums, const int32_t *done)
+{
+    if (threadIdx.x != 0) return;
+    if (done && *done) return;
+    pipecg_step(step.ps, step.mode, sums, step.hist, step.hist_cap);
+}
+void pipecg_scalar(PcStep step, const double *sums, const int32_t *done, hipStream_t s)
+{
+    hipLaunchKernelGGL(pipecg_scalar_kernel, dim3(1), dim3(64), 0, s, step, sums, done);
+}
+
+}  // namespace k
+}  // namespace spk

@@ -26,7 +26,9 @@ struct SpkKSP_s {
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
     bool ksp_type_given = false, pc_type_given = false;
-    bool minres = false;                          // -ksp_type minres (else fgmres)
+    bool minres = false;                          // -ksp_type minres
+    bool pipecg = false;                          // -ksp_type pipecg (neither: fgmres)
+    bool pc_side_right = false;                   // -ksp_pc_side right was given
     int32_t norm_type = SPK_NORM_UNPRECONDITIONED;   // -ksp_norm_type
     bool monitor = false, print_reason = false, view = false;
     spk_result result;
@@ -133,6 +135,7 @@ const char *SpkKSPConvergedReasonName(int32_t r)
     case SPK_DIVERGED_BREAKDOWN: return "DIVERGED_BREAKDOWN";
     case SPK_DIVERGED_INDEFINITE_PC: return "DIVERGED_INDEFINITE_PC";
     case SPK_DIVERGED_NANORINF: return "DIVERGED_NANORINF";
+    case SPK_DIVERGED_INDEFINITE_MAT: return "DIVERGED_INDEFINITE_MAT";
     case SPK_ITERATING: return "CONVERGED_ITERATING";
     default: return "UNKNOWN";
     }
@@ -224,9 +227,9 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         if (key == "-ksp_type") {
             if (!val) return need("a type");
             const std::string v(val);
-            if (v == "fgmres") k->minres = false;
-            else if (v == "minres") k->minres = true;
-            else return bad();
+            if (v != "fgmres" && v != "minres" && v != "pipecg") return bad();
+            k->minres = v == "minres";
+            k->pipecg = v == "pipecg";
             k->ksp_type_given = true;
         } else if (key == "-ksp_rtol") {
             if (!val || !parse_double(val, &k->opts.rtol)) return need("a real");
@@ -255,11 +258,12 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         } else if (key == "-ksp_pc_side") {
             if (!val) return need("a side");
             if (std::string(val) != "right") return bad();
+            k->pc_side_right = true;   // fgmres's side; pipecg refuses it at KSPSetUp
         } else if (key == "-ksp_norm_type") {
             if (!val) return need("a type");
             const std::string v(val);
             if (v == "unpreconditioned") k->norm_type = SPK_NORM_UNPRECONDITIONED;
-            else if (v == "natural") k->norm_type = SPK_NORM_NATURAL;   // minres only (checked at KSPSetUp)
+            else if (v == "natural") k->norm_type = SPK_NORM_NATURAL;   // minres / pipecg only (checked at KSPSetUp)
             else return bad();
         } else if (key == "-ksp_monitor" || key == "-ksp_monitor_true_residual") {
             k->monitor = true;
@@ -351,9 +355,20 @@ int SpkKSPSetUp(SpkKSP k)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -pc_type given; PETSc's default (ilu, bjacobi+ilu in parallel) is "
                                                "not implemented -- pass -pc_type jacobi | fieldsplit | gamg | none");
     // KSP / PC compatibility: option checks only, no GPU needed
-    if (!k->minres && k->norm_type == SPK_NORM_NATURAL)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres; fgmres tests the "
-                                               "unpreconditioned norm -- drop -ksp_norm_type natural or pass -ksp_type minres");
+    if (!k->minres && !k->pipecg && k->norm_type == SPK_NORM_NATURAL)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres / pipecg; fgmres tests "
+                                               "the unpreconditioned norm -- drop -ksp_norm_type natural or pass -ksp_type minres");
+    if (k->pipecg && k->pc_type == SPK_PC_SCHUR)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg is for K = A and takes -pc_type none | jacobi | gamg; "
+                                               "the Schur fieldsplit belongs to the saddle matrix, which is indefinite -- pass "
+                                               "-ksp_type minres (diag) or fgmres");
+    if (k->pipecg && k->inner_richardson && k->inner_sweeps > 0)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg needs a symmetric preconditioner and the FP32 inner "
+                                               "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
+                                               "pass -ksp_type fgmres");
+    if (k->pipecg && k->pc_side_right)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg preconditions from the left only (as PETSc's "
+                                               "KSPPIPECG) -- drop -ksp_pc_side right");
     if (k->minres && k->pc_type == SPK_PC_SCHUR && k->schur_fact != SPK_SCHUR_DIAG)
         return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: -ksp_type minres needs a symmetric positive definite "
                        "preconditioner and the Schur ") + (k->schur_fact == SPK_SCHUR_LOWER ? "lower" : k->schur_fact == SPK_SCHUR_UPPER ?
@@ -370,6 +385,9 @@ int SpkKSPSetUp(SpkKSP k)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: gamg and the FP32 inner sweeps both stand for A^-1 -- drop "
                                                "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
+    if (k->pipecg && k->has_B)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg is for K = A (symmetric positive definite); the "
+                                               "saddle matrix [A B^T; B 0] is indefinite -- pass -ksp_type minres");
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
         return set_err(k, SPK_ERR_STATE, "KSPSetUp: -pc_type fieldsplit (schur) needs the constraint block B");
     if (k->pc_type == SPK_PC_JACOBI && k->pc_gamg && k->has_B)
@@ -401,7 +419,9 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     k->history.assign((size_t)(cap > (1 << 22) ? (1 << 22) : cap), 0.0);
     const int rc = k->minres ? spk_minres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
                                           (int32_t)k->history.size())
-                             : spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
+                   : k->pipecg ? spk_pipecg(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
+                                            (int32_t)k->history.size())
+                               : spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
     if (rc != SPK_OK) return from_ctx(k, rc);
     k->history.resize((size_t)k->result.hist_len);
     if (k->monitor)
@@ -409,7 +429,11 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->print_reason)
         std::printf("Linear solve %s due to %s iterations %d\n", k->result.reason > 0 ? "converged" : "did not converge",
                     SpkKSPConvergedReasonName(k->result.reason), k->result.its);
-    if (k->view && k->minres)
+    if (k->view && k->pipecg)
+        std::printf("KSP Object: type pipecg (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, left "
+                    "preconditioning, pc=%s\n", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol,
+                    k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none");
+    else if (k->view && k->minres)
         std::printf("KSP Object: type minres (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, pc=%d schur_fact=%d\n",
                     k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol, k->opts.abstol, k->opts.dtol,
                     k->opts.max_it, k->pc_type, k->schur_fact);
@@ -462,7 +486,7 @@ int SpkKSPGetAMGOptions(SpkKSP k, int fieldsplit0, spk_amg_opts *o, int32_t *sel
 int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)
 {
     if (!k) return SPK_ERR_ARG;
-    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : "fgmres";
+    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : k->pipecg ? "pipecg" : "fgmres";
     if (norm_type) *norm_type = k->norm_type;
     return SPK_OK;
 }

@@ -13,6 +13,7 @@ BLOCK_A00, BLOCK_A10 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1
 DIVERGED_INDEFINITE_PC = -8
+DIVERGED_INDEFINITE_MAT = -10
 _NORMS = {"unpreconditioned": NORM_UNPRECONDITIONED, "natural": NORM_NATURAL}
 
 
@@ -375,17 +376,33 @@ class Context:
         """MINRES on vectors that already live in device memory (vec_create)."""
         return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw)
 
-    def _minres(self, bp, xp, mem, norm, kw):
+    def _minres(self, bp, xp, mem, norm, kw, fn=None):
         if norm not in _NORMS:
             raise ValueError(f"norm must be one of {sorted(_NORMS)}")
         o = default_opts(**kw)
         res = Result()
         cap = int(min(o.max_it + 2, 1 << 22))
         hist = np.zeros(cap)
-        self._chk(lib.spk_minres(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap))
+        fn = lib.spk_minres if fn is None else fn
+        self._chk(fn(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap))
         return dict(its=res.its, reason=res.reason, rnorm=res.rnorm, rnorm0=res.rnorm0,
                     cycles=res.cycles, solve_seconds=res.solve_seconds,
                     history=hist[:res.hist_len].copy())
+
+    def pipecg(self, b, x0=None, norm="unpreconditioned", **kw):
+        """Preconditioned pipelined CG (spk_pipecg) on K = A with the context's PC (none, Jacobi or the V-cycle); norm:
+        "unpreconditioned" (||b - K x||) or "natural" (sqrt(<r, M^-1 r>)).  Same return as fgmres."""
+        b = np.ascontiguousarray(b, np.float64)
+        assert b.shape == (self._n(),)
+        x = np.zeros_like(b)
+        if x0 is not None:
+            x[:] = x0
+            kw["guess_nonzero"] = 1
+        return x, self._minres(b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw, lib.spk_pipecg)
+
+    def pipecg_device(self, b_dev, x_dev, norm="unpreconditioned", **kw):
+        """Pipelined CG on vectors that already live in device memory (vec_create)."""
+        return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw, lib.spk_pipecg)
 
     # ---- device-resident vectors (inputs already in HBM when a solve starts)
     def vec_create(self, host=None, n=None):
@@ -540,7 +557,7 @@ class KSP:
         return amg_opts_dict(o), bool(sel.value)
 
     def getType(self):
-        """-ksp_type as set: 'fgmres', 'minres', or '' before setFromOptions gave one."""
+        """-ksp_type as set: 'fgmres', 'minres', 'pipecg', or '' before setFromOptions gave one."""
         t, n = C.c_char_p(), C.c_int32()
         self._chk(lib.SpkKSPGetType(self.h, C.byref(t), C.byref(n)))
         return t.value.decode()
