@@ -376,6 +376,21 @@ int spk_minres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts
 int spk_pipecg(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts, int norm_type,
                spk_result *result, double *history, int32_t history_cap);
 
+/* KSP type pipecgrr: spk_pipecg with residual replacement (PETSc KSPPIPECGRR), same rules and refusals.  At the end of
+ * every chunk of opts.check_every iterations (16 when 0) of a recurrence the device computes t = K x and the measured
+ * gap ||(b - t) - r||; when it crosses tau ||r|| (above now, at or below at the check before in the recurrence) the
+ * recurrence vectors are recomputed from their definitions: r = b - t, u = M^-1 r, w = K u, s = K p, q = M^-1 s,
+ * z = K q, then gamma = <r, u>, delta = <w, u> and the next step lengths as after an iteration.  x, p and the scalar
+ * history are kept: a replacement is neither an iteration nor a start (result.cycles) and keeps the Krylov space that a
+ * restart throws away.  The check and the replacement are enqueued at every boundary and gated on the device (the
+ * host does not wait); without a replacement the check costs one product and one pass per chunk.  tau:
+ * spk_pipecgrr_set_tau (SPK_PIPECGRR_TAU_DEFAULT until set).  *replacements (may be null) = replacements run. */
+#define SPK_PIPECGRR_TAU_DEFAULT 1e-6
+int spk_pipecgrr(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts *opts, int norm_type,
+                 spk_result *result, double *history, int32_t history_cap, int32_t *replacements);
+/* tau of spk_pipecgrr on ctx: >= 0 and finite (0: a replacement at every crossing of a nonzero gap). */
+int spk_pipecgrr_set_tau(spk_ctx *ctx, double tau);
+
 /* How the LAST spk_fgmres on ctx launched its iterations: *form = the SPK_ITER_* actually run (AUTO resolved; options
  * the chosen form does not cover fall back, see spk_opts.iteration_form), or -1 for the step-by-step path (PCApply and
  * MatMult as launches of their own: unfused preconditioners, FP32 inner sweeps, general constraint blocks; a restart

@@ -44,14 +44,16 @@ int SpkKSPSetOperators(SpkKSP ksp, const SpkMatCSR *A, const SpkMatCSR *B); /* K
  * DEVIATION from PETSc, on purpose: -ksp_type and -pc_type have NO default here.  PETSc would fall
  * back to gmres (left preconditioning) and ilu (bjacobi+ilu in parallel), neither of which this
  * library implements; SpkKSPSetUp / SpkKSPSolve return SPK_ERR_UNSUPPORTED with a message unless
- * "-ksp_type fgmres|minres|pipecg" and "-pc_type jacobi|fieldsplit|gamg|none" were given.
+ * "-ksp_type fgmres|minres|pipecg|pipecgrr" and "-pc_type jacobi|fieldsplit|gamg|none" were given.
  * -ksp_type minres (spk_minres) takes -ksp_norm_type unpreconditioned (default) | natural and needs a symmetric
  * positive definite preconditioner: none, jacobi, or fieldsplit with -pc_fieldsplit_schur_fact_type diag and no
  * FP32 inner sweeps; SpkKSPSetUp refuses the others with SPK_ERR_UNSUPPORTED before it looks at the operators.
  * -ksp_type pipecg (spk_pipecg) takes the same two norms and -pc_type none | jacobi | gamg on K = A; SpkKSPSetUp refuses
  * it with SPK_ERR_UNSUPPORTED beside -pc_type fieldsplit, the FP32 inner sweeps or -ksp_pc_side right (left only, as
- * PETSc's KSPPIPECG) before it looks at the operators, and with a B block once they are set.  -ksp_type cg is not
- * implemented and stays refused. */
+ * PETSc's KSPPIPECG) before it looks at the operators, and with a B block once they are set.  -ksp_type pipecgrr
+ * (spk_pipecgrr, pipecg with residual replacement) follows the same rules, with "pipecgrr" in the messages, and takes
+ * -spk_pipecgrr_tau <tau >= 0> (SPK_PIPECGRR_TAU_DEFAULT); -ksp_view prints tau and the replacements of the last
+ * solve.  -ksp_type cg is not implemented and stays refused. */
 int SpkKSPSetFromOptions(SpkKSP ksp, int argc, const char *const *argv);    /* KSPSetFromOptions :67 */
 int SpkKSPSetUp(SpkKSP ksp);                                                /* KSPSetUp       :68 */
 /* b, x: host vectors of n_local + m values ([u ; lambda]) */
@@ -73,7 +75,8 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * refused by SpkKSPSetUp with SPK_ERR_UNSUPPORTED.  (SpkKSPGetOptions reports -pc_type gamg as SPK_PC_JACOBI, the
  * slot the V-cycle takes.) */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);
-/* -ksp_type as set ("fgmres", "minres", "pipecg", or "" before KSPSetFromOptions gave one) and -ksp_norm_type (SPK_NORM_*) */
+/* -ksp_type as set ("fgmres", "minres", "pipecg", "pipecgrr", or "" before KSPSetFromOptions gave one) and -ksp_norm_type
+ * (SPK_NORM_*) */
 int SpkKSPGetType(SpkKSP ksp, const char **type, int32_t *norm_type);
 int SpkKSPGetContext(SpkKSP ksp, spk_ctx **ctx);
 const char *SpkKSPGetError(SpkKSP ksp);

@@ -181,6 +181,8 @@ def _load():
     L.spk_fgmres.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(Opts), C.POINTER(Result), vp, i32]
     L.spk_minres.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32]
     L.spk_pipecg.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32]
+    L.spk_pipecgrr.argtypes = [vp, vp, vp, C.c_int, C.POINTER(Opts), C.c_int, C.POINTER(Result), vp, i32, C.POINTER(i32)]
+    L.spk_pipecgrr_set_tau.argtypes = [vp, dbl]
     L.spk_vec_create.argtypes = [vp, i64, C.POINTER(vp)]
     L.spk_vec_destroy.argtypes = [vp, vp]
     L.spk_vec_set.argtypes = [vp, vp, f64p, i64]

@@ -515,6 +515,41 @@ int spk_pipecg(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *
     SPK_CATCH(c)
 }
 
+int spk_pipecgrr(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *opts, int norm_type, spk_result *result,
+                 double *history, int32_t history_cap, int32_t *replacements)
+{
+    SPK_TRY(c)
+    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_pipecgrr: null argument");
+    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_pipecgrr: no operator");
+    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
+        spk::fail(SPK_ERR_ARG, "spk_pipecgrr: tolerances must be non-negative, max_it >= 0");
+    if (norm_type != SPK_NORM_UNPRECONDITIONED && norm_type != SPK_NORM_NATURAL)
+        spk::fail(SPK_ERR_ARG, "spk_pipecgrr: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", norm_type);
+    c->ensure_vectors();
+    const int64_t N = (int64_t)c->n_local + c->m;
+    std::memset(result, 0, sizeof *result);
+    int32_t nrep = 0;
+    if (mem == SPK_MEM_DEVICE) {
+        spk::pipecgrr(c, b, x, *opts, norm_type, c->pc_tau, result, history, history_cap, &nrep);
+    } else {
+        double *xs = c->xsol.p, *rh = c->rhs.p;
+        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        spk::pipecgrr(c, rh, xs, *opts, norm_type, c->pc_tau, result, history, history_cap, &nrep);
+        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+    }
+    if (replacements) *replacements = nrep;
+    SPK_CATCH(c)
+}
+
+int spk_pipecgrr_set_tau(spk_ctx *c, double tau)
+{
+    SPK_TRY(c)
+    if (!(tau >= 0.0) || !std::isfinite(tau)) spk::fail(SPK_ERR_ARG, "spk_pipecgrr_set_tau: tau = %g must be >= 0 and finite", tau);
+    c->pc_tau = tau;
+    SPK_CATCH(c)
+}
+
 int spk_debug_finish_timeout(spk_ctx *c, int timeout_ms)
 {
     SPK_TRY(c)

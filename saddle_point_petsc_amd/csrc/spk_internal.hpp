@@ -367,9 +367,13 @@ struct PipecgState {
     int32_t tent;     // ks.reason was set by the recurrence alone: confirmed on b - K x
     int32_t starts;   // recurrence (re)starts
     int32_t started;  // rnorm0 / ttol fixed
-    int32_t pad;
+    int32_t rr_idle;  // pipecgrr: 0 while a replacement asked for by the gap check is pending (the gate of its launches)
     double alpha, beta;   // step lengths of the next pass
     double gamma;         // <r, u> of the pass before it (gamma_old)
+    double alpha_old, gamma_old;   // alpha and gamma before the last iteration step (pipecgrr's replacement step)
+    double tau;                    // pipecgrr: replace when ||(b - K x) - r|| > tau ||r||
+    int32_t replacements;          // pipecgrr: residual replacements so far
+    int32_t rr_above;              // pipecgrr: the last gap check of this recurrence found the gap above tau ||r||
 };
 
 // kernel launch wrappers (spk_k_*.hip)
@@ -706,7 +710,9 @@ void minres_init(MinresState *ms, const spk_opts &o, int norm, hipStream_t s);
 void minres_scalar(MrStep step, const double *sums, const int32_t *done, hipStream_t s);
 // pipelined CG (spk_k_pipecg.hip).  Scalar steps, run by the finishing workgroup of the pass that reduces their sums (one
 // rank) or by pipecg_scalar after the all-reduce: sums = [<r, u>, <w, u>, r.r]
-enum { kPcBnorm = 0, kPcBegin = 1, kPcStart = 2, kPcIter = 3 };
+// pipecgrr adds kPcGap (sums = [||(b - K x) - r||^2, 0, r.r]: a replacement when the gap crosses tau ||r||, rr_idle = 0) and kPcReplace (the sums of the replaced
+// vectors: the next pass's scalars from gamma_old, alpha_old)
+enum { kPcBnorm = 0, kPcBegin = 1, kPcStart = 2, kPcIter = 3, kPcGap = 4, kPcReplace = 5 };
 struct PcStep {
     PipecgState *ps;
     int mode;            // kPc*, < 0: no step in the kernel (several ranks)
@@ -723,8 +729,16 @@ void pipecg_begin(const double *b, const double *kx, double *r, const double *ui
 void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, double *s_, double *p, double *x, double *r,
                  double *w, double *u, double *q, const double *m, double *mout, const double *dinv, int64_t n, int64_t n_dot,
                  const PipecgState *ps, PcStep step, const Finish &f, const int32_t *done, hipStream_t s);
-void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s);
+void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s, double tau = 0.0);
 void pipecg_scalar(PcStep step, const double *sums, const int32_t *done, hipStream_t s);
+// pipecgrr's gap check: sums = [||(b - t) - r||^2, 0, r.r] (t = K x; b read without its pad), then the step kPcGap.
+// Gated by done
+void pipecgrr_gap(const double *b, const double *t, const double *r, int64_t n, int64_t n_dot, const PipecgState *ps,
+                  PcStep step, const Finish &f, const int32_t *done, hipStream_t s);
+// pipecgrr's replacement fills, gated by gate: t != nullptr: r = a - t (a read without its pad); t == nullptr: r = a as it
+// is (not written).  Then uout = D r (dinv; nullptr: r) when uout is given
+void pipecgrr_fill(const double *a, const double *t, double *r, double *uout, const double *dinv, int64_t n,
+                   const int32_t *gate, hipStream_t s);
 void krylov_init(const KrylovArrays &ka, const spk_opts &o, const double *bnorm2, hipStream_t s);
 void krylov_cycle_begin(const KrylovArrays &ka, const double *nrm2, hipStream_t s, double *tb = nullptr, int m = 0,
                         double *sc = nullptr, const StateReport *report = nullptr);
@@ -897,6 +911,7 @@ struct spk_ctx {
     spk::DevBuf<spk::PipecgState> pc_st;
     void *pc_pin = nullptr;                  // pinned landing place of the state read-back
     hipEvent_t pc_ev[2] = {nullptr, nullptr};
+    double pc_tau = SPK_PIPECGRR_TAU_DEFAULT;   // spk_pipecgrr_set_tau
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist
     spk::DevBuf<spk::KrylovState> kst;
     spk::k::KrylovArrays ka{};
@@ -933,6 +948,9 @@ void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, i
             double *history, int32_t history_cap);
 void pipecg(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,
             double *history, int32_t history_cap);
+// pipelined CG with residual replacement: pipecg plus the gap check at every chunk boundary (tau > 0 or 0: always)
+void pipecgrr(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, double tau, spk_result *res,
+              double *history, int32_t history_cap, int32_t *replacements);
 // what the two drivers share: the checks they start with (an operator, KSPSetUp done) ...
 void require_setup(spk_ctx *c, const char *who);
 // ... and their end: drain the stream, raise a communicator or device error, fill res, copy the history (hist: device)

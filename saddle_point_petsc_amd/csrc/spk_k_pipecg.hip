@@ -9,6 +9,9 @@
 // (q = m + b q, u -= a q), the step-by-step path recomputes u = M^-1 r with a launch of its own and takes the sums in a
 // second pass of this kernel, in the same order.
 // Summation orders are fixed (block partials + the sentinel finish of spk_device.hpp): identical solves, identical bits.
+// pipecgrr (spk_pipecgrr) adds, at a chunk boundary, the gap check pipecgrr_gap after t = K x (step kPcGap: rr_idle), and
+// a replacement gated by rr_idle: pipecgrr_fill (r = b - t, u = D r), the products K u, K p, pipecgrr_fill (q = D s), K q,
+// then pipecg_pass with upd = 0 (the sums; m = D w) and the step kPcReplace.  The iteration passes are pipecg's.
 #include "spk_device.hpp"
 
 namespace spk {
@@ -56,6 +59,37 @@ __device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, doubl
         st->done = 0;
         return;
     }
+    if (mode == kPcGap) {   // [||(b - K x) - r||^2, -, r.r]: the measured residual gap against tau ||r||
+        // a replacement when the gap crosses tau ||r|| (van der Vorst - Ye): above now, at or below at the check before.
+        // A gap that stays above is the noise floor of fl(b - K x) near the attainable accuracy, which no replacement lowers
+        const int32_t above = sqrt(sums[0]) > ps->tau * sqrt(sums[2]);
+        ps->rr_idle = !(above && !ps->rr_above);
+        ps->rr_above = above;
+        return;
+    }
+    if (mode == kPcReplace) {   // r, u, w, s, q, z recomputed; the scalars of the next pass as after the last iteration
+        ps->rr_idle = 1;
+        ps->replacements += 1;
+        st->rnorm = rn;
+        int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : !(g > 0.0) ? SPK_DIVERGED_BREAKDOWN : 0;
+        double beta = 0.0, den = 0.0;
+        if (!reason) {
+            beta = g / ps->gamma_old;
+            den = d - beta * g / ps->alpha_old;
+            if (isnan(den)) reason = SPK_DIVERGED_NANORINF;
+            else if (!(den > 0.0)) reason = SPK_DIVERGED_INDEFINITE_MAT;   // b - K x decides, as after an iteration
+        }
+        if (reason) {
+            ps->tent = reason == SPK_DIVERGED_INDEFINITE_MAT;
+            st->reason = reason;
+            st->done = 1;
+            return;
+        }
+        ps->beta = beta;
+        ps->alpha = g / den;
+        ps->gamma = g;
+        return;
+    }
     if (mode == kPcStart) {   // w = K u: the first step length of the recurrence
         if (!(d > 0.0)) {
             st->reason = isnan(d) ? SPK_DIVERGED_NANORINF : SPK_DIVERGED_INDEFINITE_MAT;
@@ -64,6 +98,7 @@ __device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, doubl
             return;
         }
         ps->first = 1;
+        ps->rr_above = 0;
         ps->alpha = g / d;
         ps->beta = 0.0;
         ps->gamma = g;
@@ -101,6 +136,8 @@ __device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, doubl
         return;
     }
     ps->first = 0;
+    ps->alpha_old = ps->alpha;
+    ps->gamma_old = ps->gamma;
     ps->beta = beta;
     ps->alpha = g / den;
     ps->gamma = g;
@@ -328,7 +365,7 @@ void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, doubl
     hipLaunchKernelGGL(pipecg_pass_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
 }
 
-__global__ void pipecg_init_kernel(PipecgState *ps, spk_opts o, int norm)
+__global__ void pipecg_init_kernel(PipecgState *ps, spk_opts o, int norm, double tau)
 {
     if (threadIdx.x != 0) return;
     PipecgState z{};
@@ -340,11 +377,80 @@ __global__ void pipecg_init_kernel(PipecgState *ps, spk_opts o, int norm)
     z.ks.ttol = o.abstol;
     z.ks.done = 1;   // no iteration runs before the first kPcBegin
     z.norm = norm;
+    z.rr_idle = 1;
+    z.tau = tau;
     *ps = z;
 }
-void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s)
+void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s, double tau)
 {
-    hipLaunchKernelGGL(pipecg_init_kernel, dim3(1), dim3(64), 0, s, ps, o, norm);
+    hipLaunchKernelGGL(pipecg_init_kernel, dim3(1), dim3(64), 0, s, ps, o, norm, tau);
+}
+
+struct GapArgs {
+    const double *b, *t, *r;
+    int64_t n, n2, n_dot;
+    PipecgState *ps;
+    PcStep step;
+    double *partials, *out;
+    FinErr fe;
+    const int32_t *done;
+};
+
+// pipecgrr's gap check: reads b, t = K x and r once; [||(b - t) - r||^2, 0, r.r], then (one rank) the step kPcGap
+__global__ __launch_bounds__(kVT) void pipecgrr_gap_kernel(GapArgs a)
+{
+    if (a.done && *a.done) return;
+    __shared__ double red[kVT];
+    double ag = 0.0, ar = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < a.n2; i += (int64_t)gridDim.x * kVT) {
+        const int64_t e = 2 * i;
+        const double2 b = ld_tail(a.b, e, a.n), t = ldv(a.t, i), r = ldv(a.r, i);
+        const double gx = (b.x - t.x) - r.x, gy = (b.y - t.y) - r.y;
+        if (e < a.n_dot) {
+            ag += gx * gx;
+            ar += r.x * r.x;
+        }
+        if (e + 1 < a.n_dot) {
+            ag += gy * gy;
+            ar += r.y * r.y;
+        }
+    }
+    pcg_finish(ag, 0.0, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+}
+
+void pipecgrr_gap(const double *b, const double *t, const double *r, int64_t n, int64_t n_dot, const PipecgState *ps,
+                  PcStep step, const Finish &f, const int32_t *done, hipStream_t s)
+{
+    const int64_t n2 = (n + 1) / 2;
+    GapArgs a{b, t, r, n, n2, n_dot, const_cast<PipecgState *>(ps), step, f.partials, f.out, FinErr{f.err, f.fin_ticks},
+              done};
+    hipLaunchKernelGGL(pipecgrr_gap_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
+}
+
+// pipecgrr's replacement fills: r = a - t (t given) or r = a, then uout = D r
+__global__ __launch_bounds__(kVT) void pipecgrr_fill_kernel(const double *a, const double *t, double *r, double *uout,
+                                                            const double *dinv, int64_t n, int64_t n2, const int32_t *gate)
+{
+    if (*gate) return;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kVT) {
+        const int64_t e = 2 * i;
+        double2 v = ld_tail(a, e, n);
+        if (t) {
+            const double2 tt = ldv(t, i);
+            v.x -= tt.x;
+            v.y -= tt.y;
+            if (e + 1 >= n) v.y = 0.0;   // (the pad entry of an odd length stays zero)
+            stv(r, i, v);
+        }
+        if (uout) stv(uout, i, dscale(dinv, i, v));
+    }
+}
+
+void pipecgrr_fill(const double *a, const double *t, double *r, double *uout, const double *dinv, int64_t n,
+                   const int32_t *gate, hipStream_t s)
+{
+    const int64_t n2 = (n + 1) / 2;
+    hipLaunchKernelGGL(pipecgrr_fill_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a, t, r, uout, dinv, n, n2, gate);
 }
 
 // several ranks: the step after the all-reduce of the sums (the iteration steps are gated like the passes)

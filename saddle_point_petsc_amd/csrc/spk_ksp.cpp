@@ -27,7 +27,10 @@ struct SpkKSP_s {
     // not implemented here: a run that leaves them unset must be refused, not silently changed
     bool ksp_type_given = false, pc_type_given = false;
     bool minres = false;                          // -ksp_type minres
-    bool pipecg = false;                          // -ksp_type pipecg (neither: fgmres)
+    bool pipecg = false;                          // -ksp_type pipecg or pipecgrr (neither: fgmres)
+    bool pipecgrr = false;                        // -ksp_type pipecgrr (pipecg's rules, plus residual replacement)
+    double rr_tau = SPK_PIPECGRR_TAU_DEFAULT;     // -spk_pipecgrr_tau
+    int32_t replacements = 0;                     // of the last pipecgrr solve (-ksp_view)
     bool pc_side_right = false;                   // -ksp_pc_side right was given
     int32_t norm_type = SPK_NORM_UNPRECONDITIONED;   // -ksp_norm_type
     bool monitor = false, print_reason = false, view = false;
@@ -227,10 +230,15 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         if (key == "-ksp_type") {
             if (!val) return need("a type");
             const std::string v(val);
-            if (v != "fgmres" && v != "minres" && v != "pipecg") return bad();
+            if (v != "fgmres" && v != "minres" && v != "pipecg" && v != "pipecgrr") return bad();
             k->minres = v == "minres";
-            k->pipecg = v == "pipecg";
+            k->pipecg = v == "pipecg" || v == "pipecgrr";
+            k->pipecgrr = v == "pipecgrr";
             k->ksp_type_given = true;
+        } else if (key == "-spk_pipecgrr_tau") {
+            double dv = 0.0;
+            if (!val || !parse_double(val, &dv) || !(dv >= 0.0) || !std::isfinite(dv)) return need("a finite real >= 0");
+            k->rr_tau = dv;
         } else if (key == "-ksp_rtol") {
             if (!val || !parse_double(val, &k->opts.rtol)) return need("a real");
         } else if (key == "-ksp_atol") {
@@ -358,17 +366,18 @@ int SpkKSPSetUp(SpkKSP k)
     if (!k->minres && !k->pipecg && k->norm_type == SPK_NORM_NATURAL)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres / pipecg; fgmres tests "
                                                "the unpreconditioned norm -- drop -ksp_norm_type natural or pass -ksp_type minres");
+    const std::string pt = k->pipecgrr ? "pipecgrr" : "pipecg";
     if (k->pipecg && k->pc_type == SPK_PC_SCHUR)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg is for K = A and takes -pc_type none | jacobi | gamg; "
-                                               "the Schur fieldsplit belongs to the saddle matrix, which is indefinite -- pass "
-                                               "-ksp_type minres (diag) or fgmres");
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " is for K = A and takes -pc_type none | jacobi | "
+                                               "gamg; the Schur fieldsplit belongs to the saddle matrix, which is indefinite -- "
+                                               "pass -ksp_type minres (diag) or fgmres");
     if (k->pipecg && k->inner_richardson && k->inner_sweeps > 0)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg needs a symmetric preconditioner and the FP32 inner "
-                                               "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
-                                               "pass -ksp_type fgmres");
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " needs a symmetric preconditioner and the FP32 "
+                                               "inner sweeps are not -- drop -fieldsplit_0_ksp_type richardson / "
+                                               "-spk_inner_sweeps, or pass -ksp_type fgmres");
     if (k->pipecg && k->pc_side_right)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg preconditions from the left only (as PETSc's "
-                                               "KSPPIPECG) -- drop -ksp_pc_side right");
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " preconditions from the left only (as PETSc's "
+                                               "KSP" + (k->pipecgrr ? "PIPECGRR" : "PIPECG") + ") -- drop -ksp_pc_side right");
     if (k->minres && k->pc_type == SPK_PC_SCHUR && k->schur_fact != SPK_SCHUR_DIAG)
         return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: -ksp_type minres needs a symmetric positive definite "
                        "preconditioner and the Schur ") + (k->schur_fact == SPK_SCHUR_LOWER ? "lower" : k->schur_fact == SPK_SCHUR_UPPER ?
@@ -386,8 +395,8 @@ int SpkKSPSetUp(SpkKSP k)
                                                "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
     if (k->pipecg && k->has_B)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type pipecg is for K = A (symmetric positive definite); the "
-                                               "saddle matrix [A B^T; B 0] is indefinite -- pass -ksp_type minres");
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " is for K = A (symmetric positive definite); "
+                                               "the saddle matrix [A B^T; B 0] is indefinite -- pass -ksp_type minres");
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
         return set_err(k, SPK_ERR_STATE, "KSPSetUp: -pc_type fieldsplit (schur) needs the constraint block B");
     if (k->pc_type == SPK_PC_JACOBI && k->pc_gamg && k->has_B)
@@ -417,8 +426,14 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     }
     const int64_t cap = (int64_t)k->opts.max_it + 2;
     k->history.assign((size_t)(cap > (1 << 22) ? (1 << 22) : cap), 0.0);
+    if (k->pipecgrr) {
+        const int rc = spk_pipecgrr_set_tau(k->ctx, k->rr_tau);
+        if (rc != SPK_OK) return from_ctx(k, rc);
+    }
     const int rc = k->minres ? spk_minres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
                                           (int32_t)k->history.size())
+                   : k->pipecgrr ? spk_pipecgrr(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result,
+                                                k->history.data(), (int32_t)k->history.size(), &k->replacements)
                    : k->pipecg ? spk_pipecg(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
                                             (int32_t)k->history.size())
                                : spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
@@ -429,7 +444,13 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->print_reason)
         std::printf("Linear solve %s due to %s iterations %d\n", k->result.reason > 0 ? "converged" : "did not converge",
                     SpkKSPConvergedReasonName(k->result.reason), k->result.its);
-    if (k->view && k->pipecg)
+    if (k->view && k->pipecgrr)
+        std::printf("KSP Object: type pipecgrr (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, left "
+                    "preconditioning, pc=%s, residual replacement tau=%g, replacements=%d\n",
+                    k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol, k->opts.abstol, k->opts.dtol,
+                    k->opts.max_it, k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none", k->rr_tau,
+                    k->replacements);
+    else if (k->view && k->pipecg)
         std::printf("KSP Object: type pipecg (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, left "
                     "preconditioning, pc=%s\n", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol,
                     k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none");
@@ -486,7 +507,7 @@ int SpkKSPGetAMGOptions(SpkKSP k, int fieldsplit0, spk_amg_opts *o, int32_t *sel
 int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)
 {
     if (!k) return SPK_ERR_ARG;
-    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : k->pipecg ? "pipecg" : "fgmres";
+    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : k->pipecgrr ? "pipecgrr" : k->pipecg ? "pipecg" : "fgmres";
     if (norm_type) *norm_type = k->norm_type;
     return SPK_OK;
 }

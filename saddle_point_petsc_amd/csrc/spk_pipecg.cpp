@@ -3,7 +3,10 @@
 // The host only ENQUEUES iterations, each gated by the state's `done` word, and looks at the state (copied into pinned
 // memory behind an event) once per chunk of iterations while the next chunk is already queued.  The scalar recurrence
 // runs on the device (spk_k_pipecg.hip).  A convergence or -ksp_max_it seen by the recurrence ends the chunk loop; the
-// true residual b - K x then confirms it (kPcBegin), or restarts the recurrence from the current x (residual replacement).
+// true residual b - K x then confirms it (kPcBegin), or restarts the recurrence from the current x.
+// spk_pipecgrr runs the same loop and adds, at every chunk boundary, the gap check t = K x, ||(b - t) - r|| > tau ||r||,
+// and the replacement it may ask for (r, u, w, s, q, z from their definitions; x, p and the scalars' history kept), all
+// enqueued behind the chunk and gated on the device: the host never waits for the verdict.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -15,22 +18,23 @@ namespace spk {
 namespace {
 constexpr int kPcVecs = 11;   // n, z, s, p, x, r, w, m, u, q, K x
 constexpr int kPcChunk = 16;  // iterations per look at the state when opts.check_every = 0
-}
 
-void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, spk_result *res, double *history,
-            int32_t history_cap)
+// rr: pipecgrr with tau (the gap check and the replacement); nullptr: pipecg
+void run(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, spk_result *res, double *history,
+         int32_t history_cap, const double *rr, int32_t *replacements)
 {
-    require_setup(c, "pipecg");
-    if (norm != SPK_NORM_UNPRECONDITIONED && norm != SPK_NORM_NATURAL) fail(SPK_ERR_ARG, "pipecg: unknown norm type %d", norm);
+    const char *who = rr ? "pipecgrr" : "pipecg";
+    require_setup(c, who);
+    if (norm != SPK_NORM_UNPRECONDITIONED && norm != SPK_NORM_NATURAL) fail(SPK_ERR_ARG, "%s: unknown norm type %d", who, norm);
     if (c->m > 0)
-        fail(SPK_ERR_UNSUPPORTED, "pipecg is for K = A (symmetric positive definite); the saddle matrix [A B^T; B 0] is "
-             "indefinite -- use -ksp_type minres (spk_minres) or fgmres");
+        fail(SPK_ERR_UNSUPPORTED, "%s is for K = A (symmetric positive definite); the saddle matrix [A B^T; B 0] is "
+             "indefinite -- use -ksp_type minres (spk_minres) or fgmres", who);
     if (c->pc_type == SPK_PC_SCHUR)
-        fail(SPK_ERR_UNSUPPORTED, "pipecg takes the preconditioners none, Jacobi and gamg; the Schur fieldsplit needs a "
-             "constraint block -- use -ksp_type minres or fgmres");
+        fail(SPK_ERR_UNSUPPORTED, "%s takes the preconditioners none, Jacobi and gamg; the Schur fieldsplit needs a "
+             "constraint block -- use -ksp_type minres or fgmres", who);
     if (c->inner_sweeps > 0 && c->pc_type != SPK_PC_NONE)
-        fail(SPK_ERR_UNSUPPORTED, "pipecg needs a symmetric preconditioner: the FP32 inner sweeps are not -- call "
-             "spk_pc_set_inner(ctx, 0, omega) before spk_pc_setup, or use -ksp_type fgmres");
+        fail(SPK_ERR_UNSUPPORTED, "%s needs a symmetric preconditioner: the FP32 inner sweeps are not -- call "
+             "spk_pc_set_inner(ctx, 0, omega) before spk_pc_setup, or use -ksp_type fgmres", who);
     c->ensure_scratch();
     c->ensure_vectors();
     hipStream_t s = c->stream;
@@ -61,13 +65,15 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
     const bool diag = !gamg && o.fused != 0;
     const double *dinv = c->pc_type == SPK_PC_NONE ? nullptr : c->dinv.p;
     const k::Finish f = c->fin(out);
+    const k::Finish fg = c->fin(out + 4);   // pipecgrr's gap sums
 
     // one rank: the scalar step runs in the finishing workgroup of the pass; several: after the all-reduce of its sums
     auto step = [&](int mode) { return k::PcStep{ps, one ? mode : -1, hist, hist_cap}; };
-    auto after = [&](int mode, const int32_t *gate) {
+    auto after = [&](int mode, const int32_t *gate, double *sums = nullptr) {
         if (one) return;
-        c->comm->allreduce_sum(out, 3, s);
-        k::pipecg_scalar(k::PcStep{ps, mode, hist, hist_cap}, out, gate, s);
+        if (!sums) sums = out;
+        c->comm->allreduce_sum(sums, 3, s);
+        k::pipecg_scalar(k::PcStep{ps, mode, hist, hist_cap}, sums, gate, s);
     };
     // r = b - K x (kx: K x, nullptr: x = 0), u = M^-1 r, the sums [<r, u>, -, r.r] and the step `mode`.  Diagonal M:
     // u into M for the product w = K u that follows (none: the product reads r)
@@ -97,7 +103,7 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
         return pin[slot];
     };
 
-    k::pipecg_init(ps, o, norm, s);
+    k::pipecg_init(ps, o, norm, s, rr ? *rr : 0.0);
     if (o.guess_nonzero) begin(b, nullptr, k::kPcBnorm);   // ||b|| in the norm of the test: the reference of rtol
     const double *kx = nullptr;
     if (!o.guess_nonzero) {
@@ -122,12 +128,12 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
         const int64_t cap = (int64_t)o.max_it - st.ks.its;   // iterations this recurrence may run
         const int64_t chunk = o.check_every > 0 ? o.check_every : kPcChunk;
         int64_t pending = -1;
-        bool seen_done = false;
+        bool seen_done = false, owed = false;   // owed: the collective of the last pass (several ranks) is still to come
         for (int64_t j = 1; j <= cap && !seen_done; ++j) {
             if (!diag) op_pc_apply(c, W, M, done);   // m = M^-1 w
             op_mult(c, m_in, Nv, done);              // n = K m
             // several ranks: the collective of the previous pass goes behind this product, which needs only m
-            if (j > 1) after(k::kPcIter, done);
+            if (owed) after(k::kPcIter, done);
             if (gamg) {
                 k::pipecg_pass(1, 1, 1, Nv, Z, S, P, X, R, W, U, Q, M, nullptr, nullptr, N, n_dot, ps, step(k::kPcIter), f,
                                done, s);
@@ -141,6 +147,37 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
                 k::pipecg_pass(0, 0, 1, nullptr, Z, S, P, X, R, W, U, nullptr, nullptr, nullptr, dinv, N, n_dot, ps,
                                step(k::kPcIter), f, done, s);
             }
+            owed = true;
+            if (rr && j % chunk == 0 && j < cap) {
+                // ---- pipecgrr: the gap check; several ranks: the pass's collective goes behind the check product ----
+                op_mult(c, X, T, done);   // t = K x
+                after(k::kPcIter, done);
+                owed = false;
+                k::pipecgrr_gap(b, T, R, N, n_dot, ps, step(k::kPcGap), fg, done, s);
+                after(k::kPcGap, done, out + 4);
+                // ---- the replacement, gated by rr_idle: x, p, alpha_old, gamma_old are kept ----
+                const int32_t *idle = &ps->rr_idle;
+                if (diag) {
+                    k::pipecgrr_fill(b, T, R, dinv ? U : nullptr, dinv, N, idle, s);   // r = b - t, u = D r
+                    op_mult(c, dinv ? U : R, W, idle);                                 // w = K u
+                    op_mult(c, P, S, idle);                                            // s = K p
+                    if (dinv) k::pipecgrr_fill(S, nullptr, nullptr, Q, dinv, N, idle, s);   // q = D s
+                    op_mult(c, dinv ? Q : S, Z, idle);                                 // z = K q
+                    // [<r, u>, <w, u>, r.r], m = D w for the next product
+                    k::pipecg_pass(0, 0, 1, nullptr, Z, S, P, X, R, W, nullptr, nullptr, nullptr, dinv ? M : nullptr, dinv,
+                                   N, n_dot, ps, step(k::kPcReplace), f, idle, s);
+                } else {   // the V-cycle, or the step-by-step path: u = M^-1 r and q = M^-1 s as launches of their own
+                    k::pipecgrr_fill(b, T, R, nullptr, nullptr, N, idle, s);   // r = b - t
+                    op_pc_apply(c, R, U, idle);
+                    op_mult(c, U, W, idle);
+                    op_mult(c, P, S, idle);
+                    op_pc_apply(c, S, Q, idle);
+                    op_mult(c, Q, Z, idle);
+                    k::pipecg_pass(0, 0, 1, nullptr, Z, S, P, X, R, W, U, nullptr, nullptr, nullptr, dinv, N, n_dot, ps,
+                                   step(k::kPcReplace), f, idle, s);
+                }
+                after(k::kPcReplace, idle);
+            }
             if (j % chunk == 0 || j == cap) {
                 const int slot = (int)((j / chunk) & 1);
                 report(slot);
@@ -152,7 +189,7 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
                 }
             }
         }
-        if (cap >= 1) after(k::kPcIter, done);   // the last pass's collective (several ranks)
+        if (owed) after(k::kPcIter, done);   // the last pass's collective (several ranks)
         // ---- confirmation on b - K x (kPcBegin above: converged, -ksp_max_it, or a restart) ----
         op_mult(c, X, T, nullptr);
         kx = T;
@@ -160,6 +197,20 @@ void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
     }
     SPK_HIP(hipMemcpyAsync(x, X, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
     finish_solve(c, st.ks, st.starts, t0, hist, hist_cap, res, history, history_cap);
+    if (replacements) *replacements = st.replacements;
+}
+}  // namespace
+
+void pipecg(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, spk_result *res, double *history,
+            int32_t history_cap)
+{
+    run(c, b, x, o, norm, res, history, history_cap, nullptr, nullptr);
+}
+
+void pipecgrr(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, double tau, spk_result *res,
+              double *history, int32_t history_cap, int32_t *replacements)
+{
+    run(c, b, x, o, norm, res, history, history_cap, &tau, replacements);
 }
 
 }  // namespace spk

@@ -14,6 +14,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1
 DIVERGED_INDEFINITE_PC = -8
 DIVERGED_INDEFINITE_MAT = -10
+PIPECGRR_TAU_DEFAULT = 1e-6   # SPK_PIPECGRR_TAU_DEFAULT (include/spk.h)
 _NORMS = {"unpreconditioned": NORM_UNPRECONDITIONED, "natural": NORM_NATURAL}
 
 
@@ -376,7 +377,7 @@ class Context:
         """MINRES on vectors that already live in device memory (vec_create)."""
         return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw)
 
-    def _minres(self, bp, xp, mem, norm, kw, fn=None):
+    def _minres(self, bp, xp, mem, norm, kw, fn=None, extra=()):
         if norm not in _NORMS:
             raise ValueError(f"norm must be one of {sorted(_NORMS)}")
         o = default_opts(**kw)
@@ -384,7 +385,7 @@ class Context:
         cap = int(min(o.max_it + 2, 1 << 22))
         hist = np.zeros(cap)
         fn = lib.spk_minres if fn is None else fn
-        self._chk(fn(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap))
+        self._chk(fn(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap, *extra))
         return dict(its=res.its, reason=res.reason, rnorm=res.rnorm, rnorm0=res.rnorm0,
                     cycles=res.cycles, solve_seconds=res.solve_seconds,
                     history=hist[:res.hist_len].copy())
@@ -403,6 +404,30 @@ class Context:
     def pipecg_device(self, b_dev, x_dev, norm="unpreconditioned", **kw):
         """Pipelined CG on vectors that already live in device memory (vec_create)."""
         return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw, lib.spk_pipecg)
+
+    def pipecgrr(self, b, x0=None, norm="unpreconditioned", tau=None, **kw):
+        """Pipelined CG with residual replacement (spk_pipecgrr): pipecg plus, every check_every iterations, the gap
+        check ||(b - K x) - r|| against tau ||r|| and the replacement of r, u, w, s, q, z it may trigger.  tau: None keeps
+        the context's (PIPECGRR_TAU_DEFAULT until set).  Same return as pipecg, plus `replacements`."""
+        b = np.ascontiguousarray(b, np.float64)
+        assert b.shape == (self._n(),)
+        x = np.zeros_like(b)
+        if x0 is not None:
+            x[:] = x0
+            kw["guess_nonzero"] = 1
+        return x, self._pipecgrr(b.ctypes.data, x.ctypes.data, MEM_HOST, norm, tau, kw)
+
+    def pipecgrr_device(self, b_dev, x_dev, norm="unpreconditioned", tau=None, **kw):
+        """Pipelined CG with residual replacement on vectors that already live in device memory (vec_create)."""
+        return self._pipecgrr(b_dev, x_dev, MEM_DEVICE, norm, tau, kw)
+
+    def _pipecgrr(self, bp, xp, mem, norm, tau, kw):
+        if tau is not None:
+            self._chk(lib.spk_pipecgrr_set_tau(self.h, float(tau)))
+        nrep = C.c_int32(0)
+        info = self._minres(bp, xp, mem, norm, kw, lib.spk_pipecgrr, (C.byref(nrep),))
+        info["replacements"] = nrep.value
+        return info
 
     # ---- device-resident vectors (inputs already in HBM when a solve starts)
     def vec_create(self, host=None, n=None):
@@ -557,7 +582,7 @@ class KSP:
         return amg_opts_dict(o), bool(sel.value)
 
     def getType(self):
-        """-ksp_type as set: 'fgmres', 'minres', 'pipecg', or '' before setFromOptions gave one."""
+        """-ksp_type as set: 'fgmres', 'minres', 'pipecg', 'pipecgrr', or '' before setFromOptions gave one."""
         t, n = C.c_char_p(), C.c_int32()
         self._chk(lib.SpkKSPGetType(self.h, C.byref(t), C.byref(n)))
         return t.value.decode()
