@@ -38,6 +38,34 @@ void set_create_error(const std::string &m) { g_create_error = m; }
     }                                                                    \
     return SPK_OK;
 
+namespace {
+// What the four solver entry points share: the argument checks (norm_type: nullptr for fgmres), the result reset and,
+// for host vectors, the staging through the context's rhs / xsol.  run(b, x) solves on device vectors.
+template <class Run>
+void solve(spk_ctx *c, const char *name, const double *b, double *x, int mem, const spk_opts *opts, const int *norm_type,
+           spk_result *result, Run run)
+{
+    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "%s: null argument", name);
+    if (!c->have_A) spk::fail(SPK_ERR_STATE, "%s: no operator", name);
+    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
+        spk::fail(SPK_ERR_ARG, "%s: tolerances must be non-negative, max_it >= 0", name);
+    if (norm_type && *norm_type != SPK_NORM_UNPRECONDITIONED && *norm_type != SPK_NORM_NATURAL)
+        spk::fail(SPK_ERR_ARG, "%s: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", name, *norm_type);
+    c->ensure_vectors();
+    const int64_t N = (int64_t)c->n_local + c->m;
+    std::memset(result, 0, sizeof *result);
+    if (mem == SPK_MEM_DEVICE) {
+        run(b, x);
+    } else {
+        double *xs = c->xsol.p, *rh = c->rhs.p;
+        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+        run(rh, xs);
+        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int spk_version(void) { return SPK_VERSION; }
@@ -111,13 +139,9 @@ int spk_destroy(spk_ctx *c)
         if (i == 0 && c->pin_state) (void)hipHostFree(c->pin_state);
         if (i == 0 && c->state_ev) (void)hipEventDestroy(c->state_ev);
         if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
-        if (c->mr_ev[i]) (void)hipEventDestroy(c->mr_ev[i]);
-        if (c->pc_ev[i]) (void)hipEventDestroy(c->pc_ev[i]);
     }
-    if (c->mr_pin) (void)hipHostFree(c->mr_pin);
-    if (c->pc_pin) (void)hipHostFree(c->pc_pin);
     for (hipEvent_t e : c->tp_ev) (void)hipEventDestroy(e);
-    delete c;  // DevBuf destructors free device memory
+    delete c;  // DevBuf destructors free device memory, SolverWork's destructor its pinned slots and events
     if (s) (void)hipStreamDestroy(s);
     return SPK_OK;
 }
@@ -445,23 +469,8 @@ int spk_fgmres(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *
                double *history, int32_t history_cap)
 {
     SPK_TRY(c)
-    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_fgmres: null argument");
-    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_fgmres: no operator");
-    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
-        spk::fail(SPK_ERR_ARG, "spk_fgmres: tolerances must be non-negative, max_it >= 0");
-    c->ensure_vectors();
-    const int64_t N = (int64_t)c->n_local + c->m;
-    std::memset(result, 0, sizeof *result);
-    if (mem == SPK_MEM_DEVICE) {
-        spk::fgmres(c, b, x, *opts, result, history, history_cap);
-    } else {
-        spk_opts o = *opts;
-        double *xs = c->xsol.p, *rh = c->rhs.p;
-        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        if (o.guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        spk::fgmres(c, rh, xs, o, result, history, history_cap);
-        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
-    }
+    solve(c, "spk_fgmres", b, x, mem, opts, nullptr, result,
+          [&](const double *bd, double *xd) { spk::fgmres(c, bd, xd, *opts, result, history, history_cap); });
     SPK_CATCH(c)
 }
 
@@ -469,24 +478,8 @@ int spk_minres(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *
                double *history, int32_t history_cap)
 {
     SPK_TRY(c)
-    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_minres: null argument");
-    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_minres: no operator");
-    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
-        spk::fail(SPK_ERR_ARG, "spk_minres: tolerances must be non-negative, max_it >= 0");
-    if (norm_type != SPK_NORM_UNPRECONDITIONED && norm_type != SPK_NORM_NATURAL)
-        spk::fail(SPK_ERR_ARG, "spk_minres: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", norm_type);
-    c->ensure_vectors();
-    const int64_t N = (int64_t)c->n_local + c->m;
-    std::memset(result, 0, sizeof *result);
-    if (mem == SPK_MEM_DEVICE) {
-        spk::minres(c, b, x, *opts, norm_type, result, history, history_cap);
-    } else {
-        double *xs = c->xsol.p, *rh = c->rhs.p;
-        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        spk::minres(c, rh, xs, *opts, norm_type, result, history, history_cap);
-        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
-    }
+    solve(c, "spk_minres", b, x, mem, opts, &norm_type, result,
+          [&](const double *bd, double *xd) { spk::minres(c, bd, xd, *opts, norm_type, result, history, history_cap); });
     SPK_CATCH(c)
 }
 
@@ -494,24 +487,8 @@ int spk_pipecg(spk_ctx *c, const double *b, double *x, int mem, const spk_opts *
                double *history, int32_t history_cap)
 {
     SPK_TRY(c)
-    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_pipecg: null argument");
-    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_pipecg: no operator");
-    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
-        spk::fail(SPK_ERR_ARG, "spk_pipecg: tolerances must be non-negative, max_it >= 0");
-    if (norm_type != SPK_NORM_UNPRECONDITIONED && norm_type != SPK_NORM_NATURAL)
-        spk::fail(SPK_ERR_ARG, "spk_pipecg: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", norm_type);
-    c->ensure_vectors();
-    const int64_t N = (int64_t)c->n_local + c->m;
-    std::memset(result, 0, sizeof *result);
-    if (mem == SPK_MEM_DEVICE) {
-        spk::pipecg(c, b, x, *opts, norm_type, result, history, history_cap);
-    } else {
-        double *xs = c->xsol.p, *rh = c->rhs.p;
-        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        spk::pipecg(c, rh, xs, *opts, norm_type, result, history, history_cap);
-        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
-    }
+    solve(c, "spk_pipecg", b, x, mem, opts, &norm_type, result,
+          [&](const double *bd, double *xd) { spk::pipecg(c, bd, xd, *opts, norm_type, result, history, history_cap); });
     SPK_CATCH(c)
 }
 
@@ -519,25 +496,10 @@ int spk_pipecgrr(spk_ctx *c, const double *b, double *x, int mem, const spk_opts
                  double *history, int32_t history_cap, int32_t *replacements)
 {
     SPK_TRY(c)
-    if (!b || !x || !opts || !result) spk::fail(SPK_ERR_ARG, "spk_pipecgrr: null argument");
-    if (!c->have_A) spk::fail(SPK_ERR_STATE, "spk_pipecgrr: no operator");
-    if (!(opts->rtol >= 0) || !(opts->abstol >= 0) || !(opts->dtol > 0) || opts->max_it < 0)
-        spk::fail(SPK_ERR_ARG, "spk_pipecgrr: tolerances must be non-negative, max_it >= 0");
-    if (norm_type != SPK_NORM_UNPRECONDITIONED && norm_type != SPK_NORM_NATURAL)
-        spk::fail(SPK_ERR_ARG, "spk_pipecgrr: norm_type %d is neither SPK_NORM_UNPRECONDITIONED nor SPK_NORM_NATURAL", norm_type);
-    c->ensure_vectors();
-    const int64_t N = (int64_t)c->n_local + c->m;
-    std::memset(result, 0, sizeof *result);
     int32_t nrep = 0;
-    if (mem == SPK_MEM_DEVICE) {
-        spk::pipecgrr(c, b, x, *opts, norm_type, c->pc_tau, result, history, history_cap, &nrep);
-    } else {
-        double *xs = c->xsol.p, *rh = c->rhs.p;
-        SPK_HIP(hipMemcpy(rh, b, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        if (opts->guess_nonzero) SPK_HIP(hipMemcpy(xs, x, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-        spk::pipecgrr(c, rh, xs, *opts, norm_type, c->pc_tau, result, history, history_cap, &nrep);
-        SPK_HIP(hipMemcpy(x, xs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
-    }
+    solve(c, "spk_pipecgrr", b, x, mem, opts, &norm_type, result, [&](const double *bd, double *xd) {
+        spk::pipecgrr(c, bd, xd, *opts, norm_type, c->pc_tau, result, history, history_cap, &nrep);
+    });
     if (replacements) *replacements = nrep;
     SPK_CATCH(c)
 }

@@ -272,6 +272,140 @@ __device__ __forceinline__ int converged_default(double rnorm, const KrylovState
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// The frame MINRES and pipelined CG share (spk_k_minres.hip, spk_k_pipecg.hip): the finish of their passes, the ||b||
+// and start steps of the state's head, one init and one scalar kernel.  Each solver brings its vector passes and its
+// state_step (the per-iteration tests stay per solver: their reasons take precedence in different orders).
+// ---------------------------------------------------------------------------
+__device__ void state_step(MinresState *ms, int mode, const double *sums, double *hist, int32_t hist_cap);
+__device__ void state_step(PipecgState *ps, int mode, const double *sums, double *hist, int32_t hist_cap);
+
+// block partials of NS sums, then (last workgroup) the reduction into out[0..NS) and the scalar step.  state: the pass's
+// own pointer to the state (= step.state, already in registers: loading step.state instead moved the SGPR count)
+template <int NS, class S>
+__device__ __forceinline__ void state_finish(const double (&acc)[NS], double *red, double *partials, double *out, FinErr fe,
+                                             S *state, const Step<S> &step)
+{
+    double w[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) w[k] = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) red[k * kVWaves + (threadIdx.x >> 6)] = w[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) t[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVWaves; ++j) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) t[k] += red[k * kVWaves + j];
+        }
+        double *row = partials + (size_t)blockIdx.x * kPartialLd;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) publish(row + k, t[k]);
+    }
+    if (!arrive_last(gridDim.x)) return;
+    final_reduce(partials, gridDim.x, kPartialLd, NS, red, fe);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) out[k] = red[k];
+        if (step.mode >= 0) state_step(state, step.mode, red, step.hist, step.hist_cap);
+    }
+}
+
+// a residual norm in the norm of the test: dot = <M^-1 r, r>, sq = r.r
+__device__ __forceinline__ double head_norm(const SolverHead *h, double dot, double sq)
+{
+    return h->norm == SPK_NORM_NATURAL ? sqrt(fabs(dot)) : sqrt(sq);
+}
+
+// ||b|| in the norm of the test, the reference of rtol with a nonzero guess: dot = <M^-1 b, b>, sq = b.b
+__device__ __forceinline__ void head_bnorm(SolverHead *h, double dot, double sq) { h->ks.bnorm = head_norm(h, dot, sq); }
+
+// Start, confirmation, restart on r = b - K x: dot = <M^-1 r, r>, sq = r.r.  true: the recurrence (re)starts, the
+// solver then resets its own scalars
+__device__ __forceinline__ bool head_begin(SolverHead *h, double dot, double sq, double *hist, int32_t hist_cap)
+{
+    KrylovState *st = &h->ks;
+    const double rn = head_norm(h, dot, sq);
+    st->rnorm = rn;
+    if (!h->started) {
+        // KSPConvergedDefault at iteration 0, as krylov_cycle_begin: zero guess -> the initial residual, nonzero guess ->
+        // ||b|| (or the initial residual when b = 0), both in the norm of the test
+        h->started = 1;
+        double snorm = rn;
+        if (st->guess_nonzero) {
+            snorm = st->bnorm;
+            if (snorm == 0.0) snorm = rn;
+        }
+        st->rnorm0 = rn;
+        st->cnorm0 = snorm;
+        st->ttol = fmax(st->rtol * snorm, st->abstol);
+        if (hist_cap > 0) hist[0] = rn;
+    } else if (st->done && !h->tent) {
+        return false;   // a final verdict of the recurrence (indefinite PC or matrix, breakdown, divergence) stands
+    }
+    int reason = dot < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
+    if (!reason && st->its >= st->max_it) reason = SPK_DIVERGED_ITS;
+    if (!reason && !(dot > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;   // M^-1 r = 0 with r != 0
+    h->tent = 0;
+    st->reason = reason;
+    if (reason) {
+        st->done = 1;
+        return false;
+    }
+    h->starts += 1;
+    st->done = 0;
+    return true;
+}
+
+__device__ __forceinline__ void init_extra(MinresState &) {}
+__device__ __forceinline__ void init_extra(PipecgState &z, double tau)   // pipecgrr: no replacement pending, its tau
+{
+    z.rr_idle = 1;
+    z.tau = tau;
+}
+
+template <class S, class... Tau>
+__global__ void state_init_kernel(S *state, spk_opts o, int norm, Tau... tau)
+{
+    if (threadIdx.x != 0) return;
+    S z;
+    __builtin_memset(&z, 0, sizeof(S));   // (not S z{}: that left the MINRES state in scratch)
+    z.ks.max_it = o.max_it;
+    z.ks.rtol = o.rtol;
+    z.ks.abstol = o.abstol;
+    z.ks.dtol = o.dtol;
+    z.ks.guess_nonzero = o.guess_nonzero;
+    z.ks.ttol = o.abstol;
+    z.ks.done = 1;   // no iteration runs before the first start
+    z.norm = norm;
+    init_extra(z, tau...);
+    *state = z;
+}
+template <class S, class... Tau>
+void state_init(S *state, const spk_opts &o, int norm, hipStream_t s, Tau... tau)
+{
+    hipLaunchKernelGGL(state_init_kernel<S>, dim3(1), dim3(64), 0, s, state, o, norm, tau...);
+}
+
+// several ranks: the step after the all-reduce of the sums (the iteration steps are gated like the passes)
+template <class S>
+__global__ void state_scalar_kernel(Step<S> step, const double *sums, const int32_t *done)
+{
+    if (threadIdx.x != 0) return;
+    if (done && *done) return;
+    state_step(step.state, step.mode, sums, step.hist, step.hist_cap);
+}
+template <class S>
+void state_scalar(Step<S> step, const double *sums, const int32_t *done, hipStream_t s)
+{
+    hipLaunchKernelGGL(state_scalar_kernel<S>, dim3(1), dim3(64), 0, s, step, sums, done);
+}
+
 // One Arnoldi step's scalar work (KSPFGMRESUpdateHessenberg + KSPConvergedDefault), run by a
 // whole workgroup: the lanes stage the column and the stored rotations in LDS (parallel
 // loads), lane 0 runs the dependent chain out of LDS and writes the column back once.

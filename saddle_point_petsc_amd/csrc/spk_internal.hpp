@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -345,28 +346,28 @@ struct KrylovState {
     double tt;
 };
 
-// MINRES state (spk_minres): the convergence words of KrylovState (converged_default) and the scalar recurrence
-struct MinresState {
+// What the states of MINRES and pipelined CG share: the convergence words of KrylovState (converged_default) and the
+// start / confirmation bookkeeping of the shared frame (spk_device.hpp)
+struct SolverHead {
     KrylovState ks;
     int32_t norm;     // SPK_NORM_*
-    int32_t first;    // first iteration of a recurrence (v_0 = 0)
     int32_t tent;     // ks.reason was set by the recurrence alone: confirmed on b - K x
-    int32_t pend;     // reason to end with once the pending update is applied (happy breakdown)
     int32_t starts;   // recurrence (re)starts
     int32_t started;  // rnorm0 / ttol fixed
+};
+
+// MINRES state (spk_minres): the shared head and the scalar recurrence
+struct MinresState : SolverHead {
+    int32_t first;    // first iteration of a recurrence (v_0 = 0)
+    int32_t pend;     // reason to end with once the pending update is applied (happy breakdown)
     double gam, gam_prev, delta, eta, c0, c1, s0, s1;
     double vz_ig, vz_dg, vz_gg;                 // v_{j+1} = ig p - dg v_j - gg v_{j-1}   (p = K z_j, z_j not scaled)
     double wx_ig, wx_a2, wx_a3, wx_ia1, wx_cx;  // w_{j+1} = (ig z_j - a3 w_{j-1} - a2 w_j) ia1 ;  x += cx w_{j+1}
 };
 
-// pipelined CG state (spk_pipecg): the convergence words of KrylovState (converged_default) and the scalar recurrence
-struct PipecgState {
-    KrylovState ks;
-    int32_t norm;     // SPK_NORM_*
+// pipelined CG state (spk_pipecg): the shared head and the scalar recurrence
+struct PipecgState : SolverHead {
     int32_t first;    // the next pass is the first of a recurrence (z = n, s = w, p = u, q = m)
-    int32_t tent;     // ks.reason was set by the recurrence alone: confirmed on b - K x
-    int32_t starts;   // recurrence (re)starts
-    int32_t started;  // rnorm0 / ttol fixed
     int32_t rr_idle;  // pipecgrr: 0 while a replacement asked for by the gap check is pending (the gate of its launches)
     double alpha, beta;   // step lengths of the next pass
     double gamma;         // <r, u> of the pass before it (gamma_old)
@@ -374,6 +375,18 @@ struct PipecgState {
     double tau;                    // pipecgrr: replace when ||(b - K x) - r|| > tau ||r||
     int32_t replacements;          // pipecgrr: residual replacements so far
     int32_t rr_above;              // pipecgrr: the last gap check of this recurrence found the gap above tau ||r||
+};
+
+// Workspace of MINRES or pipelined CG (one each in the context, allocated on first use; nothing of FGMRES's or of the
+// other solver's is touched): the solver's vectors, the reduced sums, the residual history, the state and its read-back
+struct SolverWork {
+    DevBuf<double> vec;                    // the solver's vectors, stride ld, zero-filled: the pad entries stay zero
+    DevBuf<double> out, hist;              // reduced sums, residual history
+    DevBuf<unsigned char> state;           // MinresState / PipecgState
+    void *pin = nullptr;                   // pinned landing place of the state read-back (two slots)
+    hipEvent_t ev[2] = {nullptr, nullptr}; // behind the copy into each slot
+    void ensure(int64_t ld, int nvec, int32_t hist_cap, size_t state_bytes);
+    ~SolverWork();
 };
 
 // kernel launch wrappers (spk_k_*.hip)
@@ -687,54 +700,51 @@ bool cycle_resident(const DictDev &A, int num_cus, ResidentArgs r, const int32_t
 int64_t resident_scratch_doubles(int num_cus, int mk);
 bool resident_fits(const DictDev &A, int num_cus, int mk, int planes);   // planes: dense planes of B D the iteration streams
 int iter_maxpy_uhead(IterB b, hipStream_t s);   // returns the number of partial rows (GivensRider::fin_n)
-// MINRES (spk_k_minres.hip).  Scalar steps, run by the finishing workgroup of the pass that reduces their sums (one rank) or
-// by minres_scalar after the all-reduce: sums = [<.,.>, ||.||^2]
-enum { kMrBnorm = 0, kMrBegin = 1, kMrDelta = 2, kMrTest = 3, kMrRecur = 4 };
-struct MrStep {
-    MinresState *ms;
-    int mode;            // kMr*, < 0: no step in the kernel (several ranks)
+// MINRES and pipelined CG: a scalar step of the state S, run by the finishing workgroup of the pass that reduces its sums
+// (one rank) or by state_scalar after the all-reduce
+template <class S>
+struct Step {
+    S *state;
+    int mode;            // kMr* / kPc*, < 0: no step in the kernel (several ranks)
     double *hist;
     int32_t hist_cap;
 };
+// the state before the first start (S = PipecgState: tau, pipecgrr's threshold); the scalar step after the all-reduce
+// (the iteration steps are gated like the passes).  One kernel each for both states (spk_device.hpp)
+template <class S, class... Tau>
+void state_init(S *state, const spk_opts &o, int norm, hipStream_t s, Tau... tau);
+template <class S>
+void state_scalar(Step<S> step, const double *sums, const int32_t *done, hipStream_t s);
+// MINRES (spk_k_minres.hip).  sums = [<.,.>, ||.||^2]
+enum { kMrBnorm = 0, kMrBegin = 1, kMrDelta = 2, kMrTest = 3, kMrRecur = 4 };
 // v pass: v_{j+1} = ig p - dg v_j - gg v_{j-1} into vm (resid != 0: vm = r = p - vj, vj == nullptr: vm = p, r2 a
 // second copy); z = M^-1 v (z == nullptr: no PC in the pass); sums = [<z, v>, v.v (sq)] over the first n_dot entries
 void minres_vz(const double *p, const double *vj, double *vm, double *r2, double *z, const double *dinv, const double *shat,
-               int64_t nl, int64_t n, int64_t n_dot, int resid, int sq, const MinresState *ms, MrStep step, const Finish &f,
-               const int32_t *done, hipStream_t s);
+               int64_t nl, int64_t n, int64_t n_dot, int resid, int sq, const MinresState *ms, Step<MinresState> step,
+               const Finish &f, const int32_t *done, hipStream_t s);
 // lagged pass: (wx) w_{j+1} = (ig z_j - a3 w_{j-1} - a2 w_j) ia1 into wm, x += cx w_{j+1}; (kwm) the same for K w with
 // p_j, r -= cx K w_{j+1}; sums = [<da, db>, r.r (kwm) | db.db (sq)]
 void minres_wd(int wx, const double *zp, const double *pp, double *wm, const double *w, double *x, double *kwm,
                const double *kw, double *r, const double *da, const double *db, int sq, int64_t n, int64_t n_dot,
-               const MinresState *ms, MrStep step, const Finish &f, const int32_t *done, hipStream_t s);
-void minres_init(MinresState *ms, const spk_opts &o, int norm, hipStream_t s);
-void minres_scalar(MrStep step, const double *sums, const int32_t *done, hipStream_t s);
-// pipelined CG (spk_k_pipecg.hip).  Scalar steps, run by the finishing workgroup of the pass that reduces their sums (one
-// rank) or by pipecg_scalar after the all-reduce: sums = [<r, u>, <w, u>, r.r]
+               const MinresState *ms, Step<MinresState> step, const Finish &f, const int32_t *done, hipStream_t s);
+// pipelined CG (spk_k_pipecg.hip).  sums = [<r, u>, <w, u>, r.r]
 // pipecgrr adds kPcGap (sums = [||(b - K x) - r||^2, 0, r.r]: a replacement when the gap crosses tau ||r||, rr_idle = 0) and kPcReplace (the sums of the replaced
 // vectors: the next pass's scalars from gamma_old, alpha_old)
 enum { kPcBnorm = 0, kPcBegin = 1, kPcStart = 2, kPcIter = 3, kPcGap = 4, kPcReplace = 5 };
-struct PcStep {
-    PipecgState *ps;
-    int mode;            // kPc*, < 0: no step in the kernel (several ranks)
-    double *hist;
-    int32_t hist_cap;
-};
 // r = b - kx (kx == nullptr: r = b; b is read without its pad); u = uin, or D r (dinv; nullptr: r) written to uout when
 // given; sums (sums != 0) = [<r, u>, 0, r.r] over the first n_dot entries.  Not gated.
 void pipecg_begin(const double *b, const double *kx, double *r, const double *uin, double *uout, const double *dinv, int sums,
-                  int64_t n, int64_t n_dot, const PipecgState *ps, PcStep step, const Finish &f, hipStream_t s);
+                  int64_t n, int64_t n_dot, const PipecgState *ps, Step<PipecgState> step, const Finish &f, hipStream_t s);
 // upd: z = n + b z, s = w + b s, p = u + b p, x += a p, r -= a s, w -= a z (first: no old z / s / p / q read), with urec
 // also q = m + b q, u -= a q; u == nullptr: u = D r (dinv; nullptr: u = r) in the pass; mout: D w written.  upd = 0:
 // only the sums (and mout) of the vectors as they are.  sums = [<r, u>, <w, u>, r.r]
 void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, double *s_, double *p, double *x, double *r,
                  double *w, double *u, double *q, const double *m, double *mout, const double *dinv, int64_t n, int64_t n_dot,
-                 const PipecgState *ps, PcStep step, const Finish &f, const int32_t *done, hipStream_t s);
-void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s, double tau = 0.0);
-void pipecg_scalar(PcStep step, const double *sums, const int32_t *done, hipStream_t s);
+                 const PipecgState *ps, Step<PipecgState> step, const Finish &f, const int32_t *done, hipStream_t s);
 // pipecgrr's gap check: sums = [||(b - t) - r||^2, 0, r.r] (t = K x; b read without its pad), then the step kPcGap.
 // Gated by done
 void pipecgrr_gap(const double *b, const double *t, const double *r, int64_t n, int64_t n_dot, const PipecgState *ps,
-                  PcStep step, const Finish &f, const int32_t *done, hipStream_t s);
+                  Step<PipecgState> step, const Finish &f, const int32_t *done, hipStream_t s);
 // pipecgrr's replacement fills, gated by gate: t != nullptr: r = a - t (a read without its pad); t == nullptr: r = a as it
 // is (not written).  Then uout = D r (dinv; nullptr: r) when uout is given
 void pipecgrr_fill(const double *a, const double *t, double *r, double *uout, const double *dinv, int64_t n,
@@ -897,20 +907,7 @@ struct spk_ctx {
     uint32_t gs_seq = 0;
     int gs_occ[3] = {-1, -1, -1};    // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes), -1 unknown
     bool gs_fused_fits(int64_t nl, int m);   // fat vectors and every workgroup of the fused launch resident at once
-    // MINRES workspace (spk_minres, allocated on first use; FGMRES's V / Z / small / kst are not touched)
-    int64_t mr_ld = 0;
-    spk::DevBuf<double> mr_vec;              // kMrVecs vectors of stride ld
-    spk::DevBuf<double> mr_out, mr_hist;     // reduced sums, residual history
-    spk::DevBuf<spk::MinresState> mr_st;
-    void *mr_pin = nullptr;                  // pinned landing place of the state read-back
-    hipEvent_t mr_ev[2] = {nullptr, nullptr};
-    // pipelined CG workspace (spk_pipecg, allocated on first use; nothing of FGMRES's or MINRES's is touched)
-    int64_t pc_ld = 0;
-    spk::DevBuf<double> pc_vec;              // kPcVecs vectors of stride ld
-    spk::DevBuf<double> pc_out, pc_hist;     // reduced sums, residual history
-    spk::DevBuf<spk::PipecgState> pc_st;
-    void *pc_pin = nullptr;                  // pinned landing place of the state read-back
-    hipEvent_t pc_ev[2] = {nullptr, nullptr};
+    spk::SolverWork minres_work, pipecg_work;   // spk_minres; spk_pipecg and spk_pipecgrr
     double pc_tau = SPK_PIPECGRR_TAU_DEFAULT;   // spk_pipecgrr_set_tau
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist
     spk::DevBuf<spk::KrylovState> kst;
@@ -958,4 +955,84 @@ void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono
                   const double *hist, int32_t hist_cap, spk_result *res, double *history, int32_t history_cap);
 void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
                const int32_t *rowptr, const int32_t *colidx, const double *val);
+
+// The host side of the frame MINRES and pipelined CG share (spk_minres.cpp, spk_pipecg.cpp).  The host only ENQUEUES
+// iterations, each gated by the state's `done` word; the scalar steps run on the device.  The state is copied into a
+// pinned slot behind that slot's event and looked at once per chunk of iterations while the next chunk is already queued.
+template <class S>
+struct SolverFrame {
+    spk_ctx *c;
+    SolverWork &w;
+    int ns;                  // sums of a pass
+    S *st;                   // the state (device)
+    double *out, *hist;      // reduced sums, residual history (device)
+    int32_t hist_cap;
+    bool one;                // one rank: the scalar step runs in the finishing workgroup of the pass
+    bool look_now;           // opts.check_every > 0: a chunk's verdict is read at its end
+    int64_t chunk;           // iterations per look at the state
+    int64_t pending = -1;    // the slot whose verdict is still to be read
+    std::chrono::steady_clock::time_point t0;
+
+    SolverFrame(spk_ctx *c_, SolverWork &w_, int nvec, int ns_, const spk_opts &o, int64_t default_chunk)
+        : c(c_), w(w_), ns(ns_), look_now(o.check_every > 0), chunk(o.check_every > 0 ? o.check_every : default_chunk)
+    {
+        c->ensure_scratch();
+        c->ensure_vectors();
+        hist_cap = (int32_t)std::min<int64_t>((int64_t)std::max(o.max_it, 0) + 2, 1 << 22);
+        w.ensure(c->ld, nvec, hist_cap, sizeof(S));
+        st = (S *)w.state.p;
+        out = w.out.p;
+        hist = w.hist.p;
+        one = c->comm->size() == 1;
+        SPK_HIP(hipStreamSynchronize(c->stream));
+        t0 = std::chrono::steady_clock::now();
+    }
+    double *vec(int i) const { return w.vec.p + (size_t)c->ld * i; }
+    const int32_t *done() const { return &st->ks.done; }
+    // the step `mode` in the kernel of a pass (one rank; several: after); mode < 0: none
+    k::Step<S> step(int mode) const { return k::Step<S>{st, one ? mode : -1, hist, hist_cap}; }
+    // several ranks: the all-reduce of the pass's sums (default: out), then the step `mode`
+    void after(int mode, const int32_t *gate, double *sums = nullptr) const
+    {
+        if (one) return;
+        if (!sums) sums = out;
+        c->comm->allreduce_sum(sums, ns, c->stream);
+        k::state_scalar(k::Step<S>{st, mode, hist, hist_cap}, sums, gate, c->stream);
+    }
+    // a (re)start: the state as it is now
+    S start()
+    {
+        pending = -1;
+        report(0);
+        return look(0);
+    }
+    // after iteration j of a recurrence of at most cap iterations: at a chunk boundary the state is reported and a verdict
+    // read (look_now: this chunk's; otherwise the previous chunk's, while this one runs).  true: the solve is done
+    bool chunk_end(int64_t j, int64_t cap)
+    {
+        if (j % chunk != 0 && j != cap) return false;
+        const int slot = (int)((j / chunk) & 1);
+        report(slot);
+        if (look_now) return look(slot).ks.done != 0;
+        const bool seen = pending >= 0 && look((int)pending).ks.done != 0;
+        pending = slot;
+        return seen;
+    }
+    void finish(const S &s, spk_result *res, double *history, int32_t history_cap) const
+    {
+        finish_solve(c, s.ks, s.starts, t0, hist, hist_cap, res, history, history_cap);
+    }
+
+private:
+    void report(int slot)
+    {
+        SPK_HIP(hipMemcpyAsync((S *)w.pin + slot, st, sizeof(S), hipMemcpyDeviceToHost, c->stream));
+        SPK_HIP(hipEventRecord(w.ev[slot], c->stream));
+    }
+    S look(int slot)
+    {
+        SPK_HIP(hipEventSynchronize(w.ev[slot]));
+        return ((S *)w.pin)[slot];
+    }
+};
 }  // namespace spk

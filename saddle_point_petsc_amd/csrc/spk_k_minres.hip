@@ -12,52 +12,23 @@ namespace spk {
 namespace k {
 
 // One step of the scalar work; sums = the reduced [<.,.>, ||.||^2] of the pass that ran before it.
-__device__ void minres_step(MinresState *ms, int mode, const double *sums, double *hist, int32_t hist_cap)
+__device__ void state_step(MinresState *ms, int mode, const double *sums, double *hist, int32_t hist_cap)
 {
     KrylovState *st = &ms->ks;
     const bool natural = ms->norm == SPK_NORM_NATURAL;
-    if (mode == kMrBnorm) {   // [<M^-1 b, b>, b.b]: ||b|| in the norm of the test (-ksp_initial_guess_nonzero)
-        st->bnorm = sqrt(fabs(natural ? sums[0] : sums[1]));
+    if (mode == kMrBnorm) {   // [<M^-1 b, b>, b.b]
+        head_bnorm(ms, sums[0], sums[1]);
         return;
     }
     if (mode == kMrBegin) {   // [<z, r>, r.r] of r = b - K x: start, confirmation, restart
-        const double zr = sums[0];
-        const double rn = natural ? sqrt(fabs(zr)) : sqrt(sums[1]);
-        st->rnorm = rn;
-        if (!ms->started) {
-            // KSPConvergedDefault at iteration 0, as krylov_cycle_begin: zero guess -> the initial residual,
-            // nonzero guess -> ||b|| (or the initial residual when b = 0), both in the norm of the test
-            ms->started = 1;
-            double snorm = rn;
-            if (st->guess_nonzero) {
-                snorm = st->bnorm;
-                if (snorm == 0.0) snorm = rn;
-            }
-            st->rnorm0 = rn;
-            st->cnorm0 = snorm;
-            st->ttol = fmax(st->rtol * snorm, st->abstol);
-            if (hist_cap > 0) hist[0] = rn;
-        } else if (st->done && !ms->tent) {
-            return;   // a final verdict of the recurrence (indefinite PC, breakdown, divergence) stands
-        }
-        int reason = zr < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
-        if (!reason && st->its >= st->max_it) reason = SPK_DIVERGED_ITS;
-        if (!reason && !(zr > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;   // M^-1 r = 0 with r != 0
-        ms->tent = 0;
-        st->reason = reason;
-        if (reason) {
-            st->done = 1;
-            return;
-        }
-        ms->starts += 1;
+        if (!head_begin(ms, sums[0], sums[1], hist, hist_cap)) return;
         ms->first = 1;
         ms->pend = 0;
-        ms->gam = sqrt(zr);
+        ms->gam = sqrt(sums[0]);
         ms->gam_prev = 1.0;
         ms->eta = ms->gam;
         ms->c0 = ms->c1 = 1.0;
         ms->s0 = ms->s1 = 0.0;
-        st->done = 0;
         return;
     }
     if (mode == kMrDelta || mode == kMrTest) {
@@ -133,35 +104,6 @@ __device__ __forceinline__ double mr_pc(int64_t e, double v, int64_t nl, const d
     return shat ? v / shat[e - nl] : v;
 }
 
-// block partials of two sums, then (last workgroup) the reduction and the scalar step
-__device__ __forceinline__ void mr_finish(double acc0, double acc1, double *red, double *partials, double *out, FinErr fe,
-                                          MinresState *ms, const MrStep &step)
-{
-    const double s0 = wave_sum(acc0), s1 = wave_sum(acc1);
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = s0;
-        red[kVWaves + (threadIdx.x >> 6)] = s1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < kVWaves; ++j) {
-            t0 += red[j];
-            t1 += red[kVWaves + j];
-        }
-        publish(partials + (size_t)blockIdx.x * kPartialLd, t0);
-        publish(partials + (size_t)blockIdx.x * kPartialLd + 1, t1);
-    }
-    if (!arrive_last(gridDim.x)) return;
-    final_reduce(partials, gridDim.x, kPartialLd, 2, red, fe);
-    if (threadIdx.x == 0) {
-        out[0] = red[0];
-        out[1] = red[1];
-        if (step.mode >= 0) minres_step(ms, step.mode, red, step.hist, step.hist_cap);
-    }
-}
-
 struct VzArgs {
     const double *p, *vj;
     double *vm, *r2, *z;
@@ -169,7 +111,7 @@ struct VzArgs {
     int64_t nl, n, n2, n_dot;
     int resid, sq;
     MinresState *ms;
-    MrStep step;
+    Step<MinresState> step;
     double *partials, *out;
     FinErr fe;
     const int32_t *done;
@@ -220,12 +162,12 @@ __global__ __launch_bounds__(kVT) void minres_vz_kernel(VzArgs a)
             if (e + 1 < a.n_dot) acc1 += v.y * v.y;
         }
     }
-    mr_finish(acc0, acc1, red, a.partials, a.out, a.fe, a.ms, a.step);
+    state_finish<2>({acc0, acc1}, red, a.partials, a.out, a.fe, a.ms, a.step);
 }
 
 void minres_vz(const double *p, const double *vj, double *vm, double *r2, double *z, const double *dinv, const double *shat,
-               int64_t nl, int64_t n, int64_t n_dot, int resid, int sq, const MinresState *ms, MrStep step, const Finish &f,
-               const int32_t *done, hipStream_t s)
+               int64_t nl, int64_t n, int64_t n_dot, int resid, int sq, const MinresState *ms, Step<MinresState> step,
+               const Finish &f, const int32_t *done, hipStream_t s)
 {
     const int64_t n2 = (n + 1) / 2;
     VzArgs a{p, vj, vm, r2, z, dinv, shat, nl, n, n2, n_dot, resid, sq, const_cast<MinresState *>(ms), step,
@@ -245,7 +187,7 @@ struct WdArgs {
     int sq;
     int64_t n2, n_dot;
     MinresState *ms;
-    MrStep step;
+    Step<MinresState> step;
     double *partials, *out;
     FinErr fe;
     const int32_t *done;
@@ -303,12 +245,12 @@ __global__ __launch_bounds__(kVT) void minres_wd_kernel(WdArgs a)
             }
         }
     }
-    mr_finish(acc0, acc1, red, a.partials, a.out, a.fe, a.ms, a.step);
+    state_finish<2>({acc0, acc1}, red, a.partials, a.out, a.fe, a.ms, a.step);
 }
 
 void minres_wd(int wx, const double *zp, const double *pp, double *wm, const double *w, double *x, double *kwm,
                const double *kw, double *r, const double *da, const double *db, int sq, int64_t n, int64_t n_dot,
-               const MinresState *ms, MrStep step, const Finish &f, const int32_t *done, hipStream_t s)
+               const MinresState *ms, Step<MinresState> step, const Finish &f, const int32_t *done, hipStream_t s)
 {
     const int64_t n2 = (n + 1) / 2;
     WdArgs a{wx, zp, pp, wm, w, x, kwm, kw, r, da, db, sq, n2, n_dot, const_cast<MinresState *>(ms), step,
@@ -316,36 +258,8 @@ void minres_wd(int wx, const double *zp, const double *pp, double *wm, const dou
     hipLaunchKernelGGL(minres_wd_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
 }
 
-__global__ void minres_init_kernel(MinresState *ms, spk_opts o, int norm)
-{
-    if (threadIdx.x != 0) return;
-    MinresState z{};
-    z.ks.max_it = o.max_it;
-    z.ks.rtol = o.rtol;
-    z.ks.abstol = o.abstol;
-    z.ks.dtol = o.dtol;
-    z.ks.guess_nonzero = o.guess_nonzero;
-    z.ks.ttol = o.abstol;
-    z.ks.done = 1;   // no iteration runs before the first kMrBegin
-    z.norm = norm;
-    *ms = z;
-}
-void minres_init(MinresState *ms, const spk_opts &o, int norm, hipStream_t s)
-{
-    hipLaunchKernelGGL(minres_init_kernel, dim3(1), dim3(64), 0, s, ms, o, norm);
-}
-
-// several ranks: the step after the all-reduce of the sums (the iteration steps are gated like the passes)
-__global__ void minres_scalar_kernel(MrStep step, const double *sums, const int32_t *done)
-{
-    if (threadIdx.x != 0) return;
-    if (done && *done) return;
-    minres_step(step.ms, step.mode, sums, step.hist, step.hist_cap);
-}
-void minres_scalar(MrStep step, const double *sums, const int32_t *done, hipStream_t s)
-{
-    hipLaunchKernelGGL(minres_scalar_kernel, dim3(1), dim3(64), 0, s, step, sums, done);
-}
+template void state_init(MinresState *, const spk_opts &, int, hipStream_t);
+template void state_scalar(Step<MinresState>, const double *, const int32_t *, hipStream_t);
 
 }  // namespace k
 }  // namespace spk

@@ -18,45 +18,17 @@ namespace spk {
 namespace k {
 
 // One step of the scalar work; sums = the reduced [<r, u>, <w, u>, r.r] of the pass that ran before it.
-__device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, double *hist, int32_t hist_cap)
+__device__ void state_step(PipecgState *ps, int mode, const double *sums, double *hist, int32_t hist_cap)
 {
     KrylovState *st = &ps->ks;
-    const bool natural = ps->norm == SPK_NORM_NATURAL;
     const double g = sums[0], d = sums[1];
-    const double rn = natural ? sqrt(fabs(g)) : sqrt(sums[2]);
-    if (mode == kPcBnorm) {   // [<M^-1 b, b>, -, b.b]: ||b|| in the norm of the test (-ksp_initial_guess_nonzero)
-        st->bnorm = rn;
+    const double rn = head_norm(ps, g, sums[2]);
+    if (mode == kPcBnorm) {   // [<M^-1 b, b>, -, b.b]
+        head_bnorm(ps, g, sums[2]);
         return;
     }
     if (mode == kPcBegin) {   // r = b - K x, u = M^-1 r: start, confirmation, restart
-        st->rnorm = rn;
-        if (!ps->started) {
-            // KSPConvergedDefault at iteration 0: zero guess -> the initial residual, nonzero guess -> ||b|| (or the
-            // initial residual when b = 0), both in the norm of the test
-            ps->started = 1;
-            double snorm = rn;
-            if (st->guess_nonzero) {
-                snorm = st->bnorm;
-                if (snorm == 0.0) snorm = rn;
-            }
-            st->rnorm0 = rn;
-            st->cnorm0 = snorm;
-            st->ttol = fmax(st->rtol * snorm, st->abstol);
-            if (hist_cap > 0) hist[0] = rn;
-        } else if (st->done && !ps->tent) {
-            return;   // a final verdict of the recurrence (indefinite PC or matrix, breakdown, divergence) stands
-        }
-        int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
-        if (!reason && st->its >= st->max_it) reason = SPK_DIVERGED_ITS;
-        if (!reason && !(g > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;   // M^-1 r = 0 with r != 0
-        ps->tent = 0;
-        st->reason = reason;
-        if (reason) {
-            st->done = 1;
-            return;
-        }
-        ps->starts += 1;
-        st->done = 0;
+        head_begin(ps, g, sums[2], hist, hist_cap);
         return;
     }
     if (mode == kPcGap) {   // [||(b - K x) - r||^2, -, r.r]: the measured residual gap against tau ||r||
@@ -143,40 +115,6 @@ __device__ void pipecg_step(PipecgState *ps, int mode, const double *sums, doubl
     ps->gamma = g;
 }
 
-// block partials of three sums, then (last workgroup) the reduction and the scalar step
-__device__ __forceinline__ void pcg_finish(double a0, double a1, double a2, double *red, double *partials, double *out,
-                                           FinErr fe, PipecgState *ps, const PcStep &step)
-{
-    const double s0 = wave_sum(a0), s1 = wave_sum(a1), s2 = wave_sum(a2);
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = s0;
-        red[kVWaves + (threadIdx.x >> 6)] = s1;
-        red[2 * kVWaves + (threadIdx.x >> 6)] = s2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < kVWaves; ++j) {
-            t0 += red[j];
-            t1 += red[kVWaves + j];
-            t2 += red[2 * kVWaves + j];
-        }
-        double *row = partials + (size_t)blockIdx.x * kPartialLd;
-        publish(row, t0);
-        publish(row + 1, t1);
-        publish(row + 2, t2);
-    }
-    if (!arrive_last(gridDim.x)) return;
-    final_reduce(partials, gridDim.x, kPartialLd, 3, red, fe);
-    if (threadIdx.x == 0) {
-        out[0] = red[0];
-        out[1] = red[1];
-        out[2] = red[2];
-        if (step.mode >= 0) pipecg_step(ps, step.mode, red, step.hist, step.hist_cap);
-    }
-}
-
 __device__ __forceinline__ double2 ldv(const double *p, int64_t i) { return reinterpret_cast<const double2 *>(p)[i]; }
 __device__ __forceinline__ void stv(double *p, int64_t i, double2 v) { reinterpret_cast<double2 *>(p)[i] = v; }
 
@@ -205,7 +143,7 @@ struct BeginArgs {
     int sums;
     int64_t n, n2, n_dot;
     PipecgState *ps;
-    PcStep step;
+    Step<PipecgState> step;
     double *partials, *out;
     FinErr fe;
 };
@@ -235,11 +173,11 @@ __global__ __launch_bounds__(kVT) void pipecg_begin_kernel(BeginArgs a)
             ar += r.y * r.y;
         }
     }
-    if (a.sums) pcg_finish(ag, 0.0, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+    if (a.sums) state_finish<3>({ag, 0.0, ar}, red, a.partials, a.out, a.fe, a.ps, a.step);
 }
 
 void pipecg_begin(const double *b, const double *kx, double *r, const double *uin, double *uout, const double *dinv, int sums,
-                  int64_t n, int64_t n_dot, const PipecgState *ps, PcStep step, const Finish &f, hipStream_t s)
+                  int64_t n, int64_t n_dot, const PipecgState *ps, Step<PipecgState> step, const Finish &f, hipStream_t s)
 {
     const int64_t n2 = (n + 1) / 2;
     BeginArgs a{b, kx, r, uin, uout, dinv, sums, n, n2, n_dot, const_cast<PipecgState *>(ps), step, f.partials, f.out,
@@ -257,7 +195,7 @@ struct PassArgs {
     const double *dinv;
     int64_t n2, n_dot;
     PipecgState *ps;
-    PcStep step;
+    Step<PipecgState> step;
     double *partials, *out;
     FinErr fe;
     const int32_t *done;
@@ -352,12 +290,12 @@ __global__ __launch_bounds__(kVT) void pipecg_pass_kernel(PassArgs a)
             ar += r.y * r.y;
         }
     }
-    if (a.sums) pcg_finish(ag, ad, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+    if (a.sums) state_finish<3>({ag, ad, ar}, red, a.partials, a.out, a.fe, a.ps, a.step);
 }
 
 void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, double *s_, double *p, double *x, double *r,
                  double *w, double *u, double *q, const double *m, double *mout, const double *dinv, int64_t n, int64_t n_dot,
-                 const PipecgState *ps, PcStep step, const Finish &f, const int32_t *done, hipStream_t s)
+                 const PipecgState *ps, Step<PipecgState> step, const Finish &f, const int32_t *done, hipStream_t s)
 {
     const int64_t n2 = (n + 1) / 2;
     PassArgs a{upd, urec, sums, nv, z, s_, p, x, r, w, u, q, m, mout, dinv, n2, n_dot, const_cast<PipecgState *>(ps), step,
@@ -365,32 +303,11 @@ void pipecg_pass(int upd, int urec, int sums, const double *nv, double *z, doubl
     hipLaunchKernelGGL(pipecg_pass_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a);
 }
 
-__global__ void pipecg_init_kernel(PipecgState *ps, spk_opts o, int norm, double tau)
-{
-    if (threadIdx.x != 0) return;
-    PipecgState z{};
-    z.ks.max_it = o.max_it;
-    z.ks.rtol = o.rtol;
-    z.ks.abstol = o.abstol;
-    z.ks.dtol = o.dtol;
-    z.ks.guess_nonzero = o.guess_nonzero;
-    z.ks.ttol = o.abstol;
-    z.ks.done = 1;   // no iteration runs before the first kPcBegin
-    z.norm = norm;
-    z.rr_idle = 1;
-    z.tau = tau;
-    *ps = z;
-}
-void pipecg_init(PipecgState *ps, const spk_opts &o, int norm, hipStream_t s, double tau)
-{
-    hipLaunchKernelGGL(pipecg_init_kernel, dim3(1), dim3(64), 0, s, ps, o, norm, tau);
-}
-
 struct GapArgs {
     const double *b, *t, *r;
     int64_t n, n2, n_dot;
     PipecgState *ps;
-    PcStep step;
+    Step<PipecgState> step;
     double *partials, *out;
     FinErr fe;
     const int32_t *done;
@@ -415,11 +332,11 @@ __global__ __launch_bounds__(kVT) void pipecgrr_gap_kernel(GapArgs a)
             ar += r.y * r.y;
         }
     }
-    pcg_finish(ag, 0.0, ar, red, a.partials, a.out, a.fe, a.ps, a.step);
+    state_finish<3>({ag, 0.0, ar}, red, a.partials, a.out, a.fe, a.ps, a.step);
 }
 
 void pipecgrr_gap(const double *b, const double *t, const double *r, int64_t n, int64_t n_dot, const PipecgState *ps,
-                  PcStep step, const Finish &f, const int32_t *done, hipStream_t s)
+                  Step<PipecgState> step, const Finish &f, const int32_t *done, hipStream_t s)
 {
     const int64_t n2 = (n + 1) / 2;
     GapArgs a{b, t, r, n, n2, n_dot, const_cast<PipecgState *>(ps), step, f.partials, f.out, FinErr{f.err, f.fin_ticks},
@@ -453,17 +370,8 @@ void pipecgrr_fill(const double *a, const double *t, double *r, double *uout, co
     hipLaunchKernelGGL(pipecgrr_fill_kernel, dim3(vec_grid(n2)), dim3(kVT), 0, s, a, t, r, uout, dinv, n, n2, gate);
 }
 
-// several ranks: the step after the all-reduce of the sums (the iteration steps are gated like the passes)
-__global__ void pipecg_scalar_kernel(PcStep step, const double *sums, const int32_t *done)
-{
-    if (threadIdx.x != 0) return;
-    if (done && *done) return;
-    pipecg_step(step.ps, step.mode, sums, step.hist, step.hist_cap);
-}
-void pipecg_scalar(PcStep step, const double *sums, const int32_t *done, hipStream_t s)
-{
-    hipLaunchKernelGGL(pipecg_scalar_kernel, dim3(1), dim3(64), 0, s, step, sums, done);
-}
+template void state_init(PipecgState *, const spk_opts &, int, hipStream_t, double);
+template void state_scalar(Step<PipecgState>, const double *, const int32_t *, hipStream_t);
 
 }  // namespace k
 }  // namespace spk

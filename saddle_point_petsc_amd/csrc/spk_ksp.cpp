@@ -10,6 +10,12 @@
 
 #include "../../include/spk_ksp.h"
 
+namespace {
+// -ksp_type: an index into kKspTypes (pipecgrr is pipecg's rules plus residual replacement)
+enum { kFgmres, kMinres, kPipecg, kPipecgrr };
+const char *const kKspTypes[] = {"fgmres", "minres", "pipecg", "pipecgrr"};
+}  // namespace
+
 struct SpkKSP_s {
     spk_ctx *ctx = nullptr;  // created on first use so that option handling needs no GPU
     int device = 0;
@@ -25,10 +31,8 @@ struct SpkKSP_s {
     bool have_ops = false, is_setup = false, has_B = false;
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
-    bool ksp_type_given = false, pc_type_given = false;
-    bool minres = false;                          // -ksp_type minres
-    bool pipecg = false;                          // -ksp_type pipecg or pipecgrr (neither: fgmres)
-    bool pipecgrr = false;                        // -ksp_type pipecgrr (pipecg's rules, plus residual replacement)
+    int ksp_type = -1;                            // -ksp_type (kFgmres ...), -1: not given
+    bool pc_type_given = false;
     double rr_tau = SPK_PIPECGRR_TAU_DEFAULT;     // -spk_pipecgrr_tau
     int32_t replacements = 0;                     // of the last pipecgrr solve (-ksp_view)
     bool pc_side_right = false;                   // -ksp_pc_side right was given
@@ -229,12 +233,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
         }
         if (key == "-ksp_type") {
             if (!val) return need("a type");
-            const std::string v(val);
-            if (v != "fgmres" && v != "minres" && v != "pipecg" && v != "pipecgrr") return bad();
-            k->minres = v == "minres";
-            k->pipecg = v == "pipecg" || v == "pipecgrr";
-            k->pipecgrr = v == "pipecgrr";
-            k->ksp_type_given = true;
+            int t = kFgmres;
+            while (t <= kPipecgrr && std::strcmp(val, kKspTypes[t]) != 0) ++t;
+            if (t > kPipecgrr) return bad();
+            k->ksp_type = t;
         } else if (key == "-spk_pipecgrr_tau") {
             double dv = 0.0;
             if (!val || !parse_double(val, &dv) || !(dv >= 0.0) || !std::isfinite(dv)) return need("a finite real >= 0");
@@ -355,7 +357,7 @@ static int amg_active(SpkKSP k)
 int SpkKSPSetUp(SpkKSP k)
 {
     if (!k) return SPK_ERR_ARG;
-    if (!k->ksp_type_given)
+    if (k->ksp_type < 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -ksp_type given; PETSc's default (gmres, left preconditioning) is "
                                                "not implemented -- pass -ksp_type fgmres (or -ksp_type minres for a symmetric "
                                                "preconditioner)");
@@ -363,38 +365,40 @@ int SpkKSPSetUp(SpkKSP k)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -pc_type given; PETSc's default (ilu, bjacobi+ilu in parallel) is "
                                                "not implemented -- pass -pc_type jacobi | fieldsplit | gamg | none");
     // KSP / PC compatibility: option checks only, no GPU needed
-    if (!k->minres && !k->pipecg && k->norm_type == SPK_NORM_NATURAL)
+    const bool minres = k->ksp_type == kMinres, pipecgrr = k->ksp_type == kPipecgrr;
+    const bool pipecg = k->ksp_type == kPipecg || pipecgrr;
+    if (k->ksp_type == kFgmres && k->norm_type == SPK_NORM_NATURAL)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_norm_type natural is for -ksp_type minres / pipecg; fgmres tests "
                                                "the unpreconditioned norm -- drop -ksp_norm_type natural or pass -ksp_type minres");
-    const std::string pt = k->pipecgrr ? "pipecgrr" : "pipecg";
-    if (k->pipecg && k->pc_type == SPK_PC_SCHUR)
+    const std::string pt = kKspTypes[k->ksp_type];
+    if (pipecg && k->pc_type == SPK_PC_SCHUR)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " is for K = A and takes -pc_type none | jacobi | "
                                                "gamg; the Schur fieldsplit belongs to the saddle matrix, which is indefinite -- "
                                                "pass -ksp_type minres (diag) or fgmres");
-    if (k->pipecg && k->inner_richardson && k->inner_sweeps > 0)
+    if (pipecg && k->inner_richardson && k->inner_sweeps > 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " needs a symmetric preconditioner and the FP32 "
                                                "inner sweeps are not -- drop -fieldsplit_0_ksp_type richardson / "
                                                "-spk_inner_sweeps, or pass -ksp_type fgmres");
-    if (k->pipecg && k->pc_side_right)
+    if (pipecg && k->pc_side_right)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " preconditions from the left only (as PETSc's "
-                                               "KSP" + (k->pipecgrr ? "PIPECGRR" : "PIPECG") + ") -- drop -ksp_pc_side right");
-    if (k->minres && k->pc_type == SPK_PC_SCHUR && k->schur_fact != SPK_SCHUR_DIAG)
+                                               "KSP" + (pipecgrr ? "PIPECGRR" : "PIPECG") + ") -- drop -ksp_pc_side right");
+    if (minres && k->pc_type == SPK_PC_SCHUR && k->schur_fact != SPK_SCHUR_DIAG)
         return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: -ksp_type minres needs a symmetric positive definite "
                        "preconditioner and the Schur ") + (k->schur_fact == SPK_SCHUR_LOWER ? "lower" : k->schur_fact == SPK_SCHUR_UPPER ?
                        "upper" : "full") + " factorisation is not symmetric -- pass -pc_fieldsplit_schur_fact_type diag, or -ksp_type fgmres");
-    if (k->minres && k->pc_type != SPK_PC_NONE && k->inner_richardson && k->inner_sweeps > 0)
+    if (minres && k->pc_type != SPK_PC_NONE && k->inner_richardson && k->inner_sweeps > 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres needs a symmetric preconditioner and the FP32 inner "
                                                "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
                                                "pass -ksp_type fgmres");
     const int amg_slot = amg_active(k);
-    if (k->minres && amg_slot >= 0)
+    if (minres && amg_slot >= 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (gamg) is not "
                                                "implemented -- pass -ksp_type fgmres");
     if (amg_slot >= 0 && k->inner_richardson && k->inner_sweeps > 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: gamg and the FP32 inner sweeps both stand for A^-1 -- drop "
                                                "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
-    if (k->pipecg && k->has_B)
+    if (pipecg && k->has_B)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " is for K = A (symmetric positive definite); "
                                                "the saddle matrix [A B^T; B 0] is indefinite -- pass -ksp_type minres");
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
@@ -426,17 +430,21 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     }
     const int64_t cap = (int64_t)k->opts.max_it + 2;
     k->history.assign((size_t)(cap > (1 << 22) ? (1 << 22) : cap), 0.0);
-    if (k->pipecgrr) {
+    if (k->ksp_type == kPipecgrr) {
         const int rc = spk_pipecgrr_set_tau(k->ctx, k->rr_tau);
         if (rc != SPK_OK) return from_ctx(k, rc);
     }
-    const int rc = k->minres ? spk_minres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
-                                          (int32_t)k->history.size())
-                   : k->pipecgrr ? spk_pipecgrr(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result,
-                                                k->history.data(), (int32_t)k->history.size(), &k->replacements)
-                   : k->pipecg ? spk_pipecg(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, k->history.data(),
-                                            (int32_t)k->history.size())
-                               : spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, k->history.data(), (int32_t)k->history.size());
+    double *h = k->history.data();
+    const int32_t hn = (int32_t)k->history.size();
+    int rc = SPK_OK;
+    switch (k->ksp_type) {
+    case kMinres: rc = spk_minres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, h, hn); break;
+    case kPipecg: rc = spk_pipecg(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, h, hn); break;
+    case kPipecgrr:
+        rc = spk_pipecgrr(k->ctx, b, x, SPK_MEM_HOST, &k->opts, k->norm_type, &k->result, h, hn, &k->replacements);
+        break;
+    default: rc = spk_fgmres(k->ctx, b, x, SPK_MEM_HOST, &k->opts, &k->result, h, hn);
+    }
     if (rc != SPK_OK) return from_ctx(k, rc);
     k->history.resize((size_t)k->result.hist_len);
     if (k->monitor)
@@ -444,23 +452,23 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->print_reason)
         std::printf("Linear solve %s due to %s iterations %d\n", k->result.reason > 0 ? "converged" : "did not converge",
                     SpkKSPConvergedReasonName(k->result.reason), k->result.its);
-    if (k->view && k->pipecgrr)
-        std::printf("KSP Object: type pipecgrr (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, left "
-                    "preconditioning, pc=%s, residual replacement tau=%g, replacements=%d\n",
-                    k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol, k->opts.abstol, k->opts.dtol,
-                    k->opts.max_it, k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none", k->rr_tau,
-                    k->replacements);
-    else if (k->view && k->pipecg)
-        std::printf("KSP Object: type pipecg (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, left "
-                    "preconditioning, pc=%s\n", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol,
-                    k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none");
-    else if (k->view && k->minres)
-        std::printf("KSP Object: type minres (MI355X device-resident), %s norm, rtol=%g atol=%g divtol=%g max_it=%d, pc=%d schur_fact=%d\n",
-                    k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned", k->opts.rtol, k->opts.abstol, k->opts.dtol,
-                    k->opts.max_it, k->pc_type, k->schur_fact);
-    else if (k->view)
-        std::printf("KSP Object: type fgmres (MI355X device-resident), restart=%d, classical Gram-Schmidt, rtol=%g atol=%g divtol=%g max_it=%d, right preconditioning, pc=%d schur_fact=%d\n",
-                    k->opts.restart, k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it, k->pc_type, k->schur_fact);
+    if (k->view) {
+        std::printf("KSP Object: type %s (MI355X device-resident), ", kKspTypes[k->ksp_type]);
+        if (k->ksp_type == kFgmres)
+            std::printf("restart=%d, classical Gram-Schmidt, ", k->opts.restart);
+        else
+            std::printf("%s norm, ", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned");
+        std::printf("rtol=%g atol=%g divtol=%g max_it=%d, ", k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it);
+        const char *pc = k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none";
+        switch (k->ksp_type) {
+        case kFgmres: std::printf("right preconditioning, pc=%d schur_fact=%d\n", k->pc_type, k->schur_fact); break;
+        case kMinres: std::printf("pc=%d schur_fact=%d\n", k->pc_type, k->schur_fact); break;
+        case kPipecg: std::printf("left preconditioning, pc=%s\n", pc); break;
+        default:
+            std::printf("left preconditioning, pc=%s, residual replacement tau=%g, replacements=%d\n", pc, k->rr_tau,
+                        k->replacements);
+        }
+    }
     if (k->view && amg_active(k) >= 0) {
         spk_amg_info ai;
         if (spk_get_amg_info(k->ctx, &ai) == SPK_OK) {
@@ -507,7 +515,7 @@ int SpkKSPGetAMGOptions(SpkKSP k, int fieldsplit0, spk_amg_opts *o, int32_t *sel
 int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)
 {
     if (!k) return SPK_ERR_ARG;
-    if (type) *type = !k->ksp_type_given ? "" : k->minres ? "minres" : k->pipecgrr ? "pipecgrr" : k->pipecg ? "pipecg" : "fgmres";
+    if (type) *type = k->ksp_type < 0 ? "" : kKspTypes[k->ksp_type];
     if (norm_type) *norm_type = k->norm_type;
     return SPK_OK;
 }

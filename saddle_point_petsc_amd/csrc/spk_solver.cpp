@@ -1249,6 +1249,24 @@ void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono
     res->hist_len = nh;
 }
 
+void SolverWork::ensure(int64_t ld, int nvec, int32_t hist_cap, size_t state_bytes)
+{
+    if (vec.n != (size_t)ld * nvec) vec.alloc((size_t)ld * nvec);
+    if (hist.n < (size_t)hist_cap) hist.alloc((size_t)hist_cap);
+    if (!out.p) out.alloc(8);
+    if (!state.p) state.alloc(state_bytes);
+    if (!pin) SPK_HIP(hipHostMalloc(&pin, 2 * state_bytes, hipHostMallocDefault));
+    for (hipEvent_t &e : ev)
+        if (!e) SPK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+}
+
+SolverWork::~SolverWork()
+{
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (pin) (void)hipHostFree(pin);
+}
+
 // ---------------------------------------------------------------------------
 // KSPSolve_FGMRES, device resident
 // ---------------------------------------------------------------------------

@@ -371,20 +371,20 @@ class Context:
         if x0 is not None:
             x[:] = x0
             kw["guess_nonzero"] = 1
-        return x, self._minres(b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw)
+        return x, self._short_recurrence(lib.spk_minres, b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw)
 
     def minres_device(self, b_dev, x_dev, norm="unpreconditioned", **kw):
         """MINRES on vectors that already live in device memory (vec_create)."""
-        return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw)
+        return self._short_recurrence(lib.spk_minres, b_dev, x_dev, MEM_DEVICE, norm, kw)
 
-    def _minres(self, bp, xp, mem, norm, kw, fn=None, extra=()):
+    def _short_recurrence(self, fn, bp, xp, mem, norm, kw, extra=()):
+        """One solve of spk_minres, spk_pipecg or spk_pipecgrr (fn; extra: its arguments after the history)."""
         if norm not in _NORMS:
             raise ValueError(f"norm must be one of {sorted(_NORMS)}")
         o = default_opts(**kw)
         res = Result()
         cap = int(min(o.max_it + 2, 1 << 22))
         hist = np.zeros(cap)
-        fn = lib.spk_minres if fn is None else fn
         self._chk(fn(self.h, bp, xp, mem, C.byref(o), _NORMS[norm], C.byref(res), hist.ctypes.data, cap, *extra))
         return dict(its=res.its, reason=res.reason, rnorm=res.rnorm, rnorm0=res.rnorm0,
                     cycles=res.cycles, solve_seconds=res.solve_seconds,
@@ -399,11 +399,11 @@ class Context:
         if x0 is not None:
             x[:] = x0
             kw["guess_nonzero"] = 1
-        return x, self._minres(b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw, lib.spk_pipecg)
+        return x, self._short_recurrence(lib.spk_pipecg, b.ctypes.data, x.ctypes.data, MEM_HOST, norm, kw)
 
     def pipecg_device(self, b_dev, x_dev, norm="unpreconditioned", **kw):
         """Pipelined CG on vectors that already live in device memory (vec_create)."""
-        return self._minres(b_dev, x_dev, MEM_DEVICE, norm, kw, lib.spk_pipecg)
+        return self._short_recurrence(lib.spk_pipecg, b_dev, x_dev, MEM_DEVICE, norm, kw)
 
     def pipecgrr(self, b, x0=None, norm="unpreconditioned", tau=None, **kw):
         """Pipelined CG with residual replacement (spk_pipecgrr): pipecg plus, every check_every iterations, the gap
@@ -425,7 +425,7 @@ class Context:
         if tau is not None:
             self._chk(lib.spk_pipecgrr_set_tau(self.h, float(tau)))
         nrep = C.c_int32(0)
-        info = self._minres(bp, xp, mem, norm, kw, lib.spk_pipecgrr, (C.byref(nrep),))
+        info = self._short_recurrence(lib.spk_pipecgrr, bp, xp, mem, norm, kw, (C.byref(nrep),))
         info["replacements"] = nrep.value
         return info
 

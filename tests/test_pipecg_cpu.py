@@ -14,12 +14,14 @@ from test_minres_cpu import scipy_K
 
 
 def pipecg_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=10000, norm="unpreconditioned", urec=True,
-               iterates=None):
+               tau=None, check_every=16, iterates=None):
     """Preconditioned pipelined CG as spk_pipecg runs it (include/spk.h): K, M are callables (operator, M^-1).  urec:
     u and q kept as recurrences (u -= alpha q; the V-cycle path); False: u = M^-1 r recomputed after every update (the
     diagonal path, where the pass forms u = D r).  The test is KSPConvergedDefault in the chosen norm; a convergence or
     max_it seen by the recurrence is confirmed on b - K x, and the recurrence restarts from x when that misses.
-    iterates: a list that receives x after every iteration.  Returns x and a dict like Context.pipecg."""
+    tau (None: pipecg, no gap check): spk_pipecgrr's residual replacement, see test_pipecgrr_cpu.pipecgrr_ref.
+    iterates: a list that receives x after every iteration.  Returns x and a dict like Context.pipecg, plus
+    `replacements` and `replaced`: the iteration counts after which a replacement ran."""
     natural = norm == "natural"
     x = np.zeros_like(b) if x0 is None else np.array(x0, float)
 
@@ -27,7 +29,7 @@ def pipecg_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=10000
         return np.sqrt(abs(g)) if natural else np.linalg.norm(r)
 
     bnorm = nrm(b, M(b) @ b) if x0 is not None else 0.0
-    hist, its, starts, reason, final = [], 0, 0, 0, False
+    hist, its, starts, reason, final, replaced = [], 0, 0, 0, False, []
     r = b - K(x)
     u = M(r)
     gamma = r @ u
@@ -62,6 +64,7 @@ def pipecg_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=10000
             reason = -10
             break
         alpha, beta, gamma_old, first = gamma / delta, 0.0, gamma, True
+        j, above = 0, False
         while True:
             m = M(w)
             n = K(m)
@@ -77,6 +80,7 @@ def pipecg_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=10000
                 iterates.append(x.copy())
             gamma, delta = r @ u, w @ u
             its += 1
+            j += 1
             rn = nrm(r, gamma)
             hist.append(rn)
             reason = -8 if gamma < 0 else conv(rn)
@@ -93,11 +97,40 @@ def pipecg_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=10000
             if not den > 0:   # after the first pass: the residual gap, b - K x decides (confirmation or restart)
                 reason, final = -10, first
                 break
+            alpha_old, gamma_oold = alpha, gamma_old
             alpha, gamma_old, first = gamma / den, gamma, False
+            if tau is None or j % check_every:
+                continue
+            # ---- the gap check, and the replacement it may trigger ----
+            t = K(x)
+            was, above = above, bool(np.linalg.norm((b - t) - r) > tau * np.linalg.norm(r))
+            if was or not above:
+                continue
+            replaced.append(its)
+            r = b - t
+            u = M(r)
+            w = K(u)
+            s = K(p)
+            q = M(s)
+            z = K(q)
+            gamma, delta = r @ u, w @ u
+            if gamma < 0:
+                reason, final = -8, True
+            elif not gamma > 0:
+                reason, final = -5, True
+            if reason:
+                break
+            beta = gamma / gamma_oold
+            den = delta - beta * gamma / alpha_old
+            if not den > 0:
+                reason = -10
+                break
+            alpha, gamma_old = gamma / den, gamma
         r = b - K(x)
         u = M(r)
         gamma = r @ u
-    return x, dict(its=its, reason=reason, rnorm=rn, rnorm0=rnorm0, cycles=starts, history=np.array(hist))
+    return x, dict(its=its, reason=reason, rnorm=rn, rnorm0=rnorm0, cycles=starts, history=np.array(hist),
+                   replacements=len(replaced), replaced=replaced)
 
 
 def pcg_textbook(K, M, b, its):

@@ -11,6 +11,7 @@ import pytest
 
 from conftest import ROOT, relerr
 from test_minres_cpu import scipy_K
+from test_pipecg_cpu import pipecg_ref
 
 TAU = 1e-6   # -spk_pipecgrr_tau default (chosen on this reference)
 
@@ -25,115 +26,8 @@ def pipecgrr_ref(K, M, b, x0=None, rtol=1e-8, abstol=1e-50, dtol=1e4, max_it=100
     from their definitions, keeps x and p, and forms beta and alpha from the fresh gamma = <r, u>, delta = <w, u> as after
     a normal iteration.  It is no iteration and no start.  Returns x and a dict like Context.pipecgrr, with `replaced`:
     the iteration counts after which a replacement ran."""
-    natural = norm == "natural"
-    x = np.zeros_like(b) if x0 is None else np.array(x0, float)
-
-    def nrm(r, g):
-        return np.sqrt(abs(g)) if natural else np.linalg.norm(r)
-
-    bnorm = nrm(b, M(b) @ b) if x0 is not None else 0.0
-    hist, its, starts, reason, final, replaced = [], 0, 0, 0, False, []
-    r = b - K(x)
-    u = M(r)
-    gamma = r @ u
-    rn = nrm(r, gamma)
-    rnorm0 = rn
-    cnorm0 = bnorm if (x0 is not None and bnorm != 0.0) else rn
-    ttol = max(rtol * cnorm0, abstol)
-    hist.append(rn)
-
-    def conv(v):
-        if not np.isfinite(v):
-            return -9
-        if v <= ttol:
-            return 3 if v < abstol else 2
-        return -4 if v >= dtol * cnorm0 else 0
-
-    while True:
-        rn = nrm(r, gamma)
-        if final:
-            break
-        reason = -8 if gamma < 0 else conv(rn)
-        if not reason and its >= max_it:
-            reason = -3
-        if not reason and not gamma > 0:
-            reason = -5
-        if reason:
-            break
-        starts += 1
-        w = K(u)
-        delta = w @ u
-        if not delta > 0:
-            reason = -10
-            break
-        alpha, beta, gamma_old, first = gamma / delta, 0.0, gamma, True
-        j, above = 0, False
-        while True:
-            m = M(w)
-            n = K(m)
-            if first:
-                z, q, s, p = n.copy(), m.copy(), w.copy(), u.copy()
-            else:
-                z, q, s, p = n + beta * z, m + beta * q, w + beta * s, u + beta * p
-            x = x + alpha * p
-            r = r - alpha * s
-            u = u - alpha * q if urec else M(r)
-            w = w - alpha * z
-            if iterates is not None:
-                iterates.append(x.copy())
-            gamma, delta = r @ u, w @ u
-            its += 1
-            j += 1
-            rn = nrm(r, gamma)
-            hist.append(rn)
-            reason = -8 if gamma < 0 else conv(rn)
-            if reason < 0:
-                final = True
-            elif not reason and its >= max_it:
-                reason = -3
-            if not reason and not gamma > 0:
-                reason, final = -5, True
-            if reason:
-                break
-            beta = gamma / gamma_old
-            den = delta - beta * gamma / alpha
-            if not den > 0:   # after the first pass: the residual gap, b - K x decides (confirmation or restart)
-                reason, final = -10, first
-                break
-            alpha_old, gamma_oold = alpha, gamma_old
-            alpha, gamma_old, first = gamma / den, gamma, False
-            if j % check_every:
-                continue
-            # ---- the gap check, and the replacement it may trigger ----
-            t = K(x)
-            was, above = above, bool(np.linalg.norm((b - t) - r) > tau * np.linalg.norm(r))
-            if was or not above:
-                continue
-            replaced.append(its)
-            r = b - t
-            u = M(r)
-            w = K(u)
-            s = K(p)
-            q = M(s)
-            z = K(q)
-            gamma, delta = r @ u, w @ u
-            if gamma < 0:
-                reason, final = -8, True
-            elif not gamma > 0:
-                reason, final = -5, True
-            if reason:
-                break
-            beta = gamma / gamma_oold
-            den = delta - beta * gamma / alpha_old
-            if not den > 0:
-                reason = -10
-                break
-            alpha, gamma_old = gamma / den, gamma
-        r = b - K(x)
-        u = M(r)
-        gamma = r @ u
-    return x, dict(its=its, reason=reason, rnorm=rn, rnorm0=rnorm0, cycles=starts, history=np.array(hist),
-                   replacements=len(replaced), replaced=replaced)
+    return pipecg_ref(K, M, b, x0=x0, rtol=rtol, abstol=abstol, dtol=dtol, max_it=max_it, norm=norm, urec=urec, tau=tau,
+                      check_every=check_every, iterates=iterates)
 
 
 def pcg_textbook_its(K, M, b, rtol, norm="unpreconditioned", max_it=100000):
