@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace spk {
 namespace k {
@@ -617,22 +618,60 @@ inline WsShape ws_shape(int64_t n2)
     return v;
 }
 
+// The keep set of form 7 (gs_fused_kernel): operands of the workgroup's FIRST tile that VecMDot's pass has in registers
+// and kernel B's pass reads again -- w~ (raw), the parity planes of B D, V_0 .. V_{KV-1} -- stay on chip between the two
+// passes instead of being fetched from HBM a second time.  Items are numbered in that order; item k < KR lives in
+// registers, the others in the workgroup's LDS (one double2 per lane and u: lane-private, no barrier needed).  Every
+// index is a compile-time constant once the loops around put/get are unrolled, and the first tile is told by a flag
+// inside the tile loops: a copy of the loop body for it costs > 35 VGPRs in either pass (scratch at MP = 4).  So register
+// items must be dead before kernel B's tile loop (w~ and the planes are: they move into its prefetch arrays ahead of the
+// loop); the kept basis vectors are read inside the loop and live in LDS.  NoKeep (the default of both bodies) keeps
+// nothing and compiles to the code without a keep set.
+struct NoKeep {
+    static constexpr int KW = 0, KP = 0, KV = 0;
+    static constexpr bool any = false;
+    __device__ __forceinline__ void put(int, int, double2) {}
+    __device__ __forceinline__ double2 get(int, int) const { return double2{0.0, 0.0}; }
+};
+template <int T, int U, int KW_, int KP_, int KV_, int KR_>
+struct KeepSet {
+    static constexpr int KW = KW_, KP = KP_, KV = KV_, KR = KR_, N = KW_ + KP_ + KV_, KL = N > KR_ ? N - KR_ : 0;
+    static constexpr bool any = N > 0;
+    double2 r[KR_ > 0 ? KR_ : 1][U];
+    double2 *l;   // KL * U * T double2 of LDS
+    __device__ __forceinline__ void put(int k, int u, double2 v)
+    {
+        if (k < KR) r[k][u] = v;
+        else l[((k - KR) * U + u) * T + threadIdx.x] = v;
+    }
+    __device__ __forceinline__ double2 get(int k, int u) const
+    {
+        return k < KR ? r[k][u] : l[((k - KR) * U + u) * T + threadIdx.x];
+    }
+};
+
 // VecMDot body (mdot_kernel, gs_fused_kernel): the workgroup's tiles (tile = blockIdx.x + k gridDim.x of T x U double2),
 // all nv dot products V_i . w in ONE pass over w (kept in registers), w.w in slot nv (with_ww); the workgroup's sums
 // are published to partials[blockIdx.x][0..nv] for the reducer.  lds: max(W (NG 8 + 1), T) doubles.
-template <int NG, int T, int G, bool NT, int U>
+// keep: the first tile leaves its operands in the keep set (needs gridDim.x whole tiles in n2).  With split, its kept
+// planes are loaded ONCE: their slots in the groups turn into dead ones and their dot products, the same sums over u of
+// the same values, are added behind the groups.  No order of additions changes.
+template <int NG, int T, int G, bool NT, int U, class Keep = NoKeep>
 __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t ldv, int nv,
                                            const double *__restrict__ V2, int nv1,
                                            const double *__restrict__ w, int64_t n2,
                                            int64_t n_dot, double *__restrict__ partials,
-                                           int with_ww, int split, double *lds)
+                                           int with_ww, int split, double *lds, Keep *keep = nullptr)
 {
     constexpr int NA = NG * 8 + 1, W = T / kWave, TILE2 = T * U;
+    constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
     double acc[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) acc[i] = 0.0;
 
     for (int64_t tile = blockIdx.x; tile * TILE2 < n2; tile += gridDim.x) {
+        const bool KF = Keep::any && tile == (int64_t)blockIdx.x;   // the first tile leaves its operands behind
+        const bool kpl = KF && KP > 0 && split && nv > nv1;   // this tile's planes go through the keep set
         double2 wv[U];
         int64_t idx[U];
 #pragma unroll
@@ -640,11 +679,24 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
             idx[u] = tile * TILE2 + u * T + threadIdx.x;
             if (idx[u] < n2) {
                 wv[u] = ld2(w, idx[u]);
+                if (KF && KW) keep->put(0, u, wv[u]);
                 if (2 * idx[u] >= n_dot) wv[u].x = 0.0;
                 if (2 * idx[u] + 1 >= n_dot) wv[u].y = 0.0;
             } else {
                 wv[u].x = wv[u].y = 0.0;
                 idx[u] = 0;  // safe address, zero weight
+            }
+        }
+        if (kpl) {
+#pragma unroll
+            for (int q = 0; q < KP; ++q) {
+                const bool live = nv1 + 2 * q < nv;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    double2 e{0.0, 0.0};
+                    if (live) e = ld2s<NT>(V2 + (size_t)q * ldv, idx[u]);
+                    keep->put(KW + q, u, e);
+                }
             }
         }
 #pragma unroll
@@ -657,7 +709,8 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
                 for (int v = 0; v < G; ++v) {
                     // a slot past nv loads ONE broadcast address (w[0..1], weight 0) instead of a
                     // vector tile: the group stays branch-free and costs no bandwidth
-                    const bool live = g0 + v < nv;
+                    // (so does the slot of a kept plane: its dot product follows behind the groups)
+                    const bool live = g0 + v < nv && !(kpl && g0 + v >= nv1 && ((g0 + v - nv1) >> 1) < KP);
                     const int ic = live ? g0 + v : 0;
                     // vectors nv1.. come from a second slab (the rows of B D in the single-reduction mode);
                     // split: that slab holds parity-interleaved planes, "vector" j is half j & 1 of plane j / 2
@@ -668,9 +721,10 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
                 }
 #pragma unroll
                 for (int v = 0; v < G; ++v) {
-                    const double mk = (g0 + v < nv) ? 1.0 : 0.0;
+                    const bool live = g0 + v < nv && !(kpl && g0 + v >= nv1 && ((g0 + v - nv1) >> 1) < KP);
+                    const double mk = live ? 1.0 : 0.0;
                     double d = 0.0;
-                    if (split && g0 + v >= nv1 && g0 + v < nv) {  // wave-uniform
+                    if (split && g0 + v >= nv1 && live) {  // wave-uniform
                         if ((g0 + v - nv1) & 1) {
 #pragma unroll
                             for (int u = 0; u < U; ++u) d += a[v][u].y * wv[u].y;
@@ -683,6 +737,37 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
                         for (int u = 0; u < U; ++u) d += a[v][u].x * wv[u].x + a[v][u].y * wv[u].y;
                     }
                     acc[g0 + v] += mk * d;
+                }
+                if (KF && g0 < KV) {  // behind the group's sums: a store of a loaded value waits for it
+#pragma unroll
+                    for (int v = 0; v < G; ++v) {
+                        if (g0 + v < KV && g0 + v < nv1) {
+#pragma unroll
+                            for (int u = 0; u < U; ++u) keep->put(KW + KP + g0 + v, u, a[v][u]);
+                        }
+                    }
+                }
+            }
+        }
+        if (kpl) {
+#pragma unroll
+            for (int q = 0; q < KP; ++q) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int slot = nv1 + 2 * q + h;
+                    if (slot < nv) {  // wave-uniform
+                        double d = 0.0;
+                        if (h) {
+#pragma unroll
+                            for (int u = 0; u < U; ++u) d += keep->get(KW + q, u).y * wv[u].y;
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < U; ++u) d += keep->get(KW + q, u).x * wv[u].x;
+                        }
+#pragma unroll
+                        for (int i = 0; i < NA - 1; ++i)
+                            if (i == slot) acc[i] += d;
+                    }
                 }
             }
         }

@@ -667,6 +667,7 @@ struct IterB {
 struct GsArgs {
     const double *V2;    // planes of B D (parity-interleaved when split)
     int cnt, split;      // cnt = nv + m values (<= 40), w.w after them
+    int keep;            // the first tile's operands stay on chip between the two passes (FgmresPlan::gs_keep)
     int64_t n2, n_dot;   // MDot's length in double2 (the multiplier entries included), entries that count
     double *partials;    // MDot's partial rows (column offset 1 of the context's partials)
     double *out;         // the reduced [h, q, w.w] (as mdot's Finish::out)
@@ -674,7 +675,7 @@ struct GsArgs {
     FinErr fe;
 };
 int gs_fused(IterB b, GsArgs g, hipStream_t s);
-int gs_fused_occupancy(int ng, int m);   // workgroups of the fused kernel that fit one CU
+int gs_fused_occupancy(int ng, int m, bool keep);   // workgroups of the fused kernel (with / without its keep set) that fit one CU
 int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
 // Resident restart cycle (spk_k_resident.hip): ONE launch runs iterations 0 .. mk-1 of a cycle with the basis in registers
 // (single rank, row-type layout with 2x2 blocks, <= 512 block rows per CU, restart <= 30, <= 4 planes of B D).  On entry
@@ -905,8 +906,8 @@ struct spk_ctx {
     int num_cus = 0;                 // compute units of the device (grid of the resident cycle kernel)
     spk::DevBuf<double> gs_tot;      // form 7: two armed lines of MDot totals (the launch reads one, arms the other)
     uint32_t gs_seq = 0;
-    int gs_occ[3] = {-1, -1, -1};    // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes), -1 unknown
-    bool gs_fused_fits(int64_t nl, int m);   // fat vectors and every workgroup of the fused launch resident at once
+    int gs_occ[6] = {-1, -1, -1, -1, -1, -1};   // form 7: workgroups of the fused kernel per CU (none / <= 4 / <= 8 planes; 3..5: with its keep set), -1 unknown
+    bool gs_fused_fits(int64_t nl, int m, bool keep);   // fat vectors and every workgroup of the fused launch resident at once
     spk::SolverWork minres_work, pipecg_work;   // spk_minres; spk_pipecg and spk_pipecgrr
     double pc_tau = SPK_PIPECGRR_TAU_DEFAULT;   // spk_pipecgrr_set_tau
     spk::DevBuf<double> kry_d;  // H, cc, ss, rs, nrs, hcol, hist

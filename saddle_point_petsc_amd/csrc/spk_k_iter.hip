@@ -24,9 +24,14 @@ namespace k {
 // The body of kernel B (iter_maxpy_uhead_kernel, gs_fused_kernel).  scalar_wg: the workgroup that also writes the
 // multiplier entries of w', z~, c~, tb, the Hessenberg column and the multiplier entries' share of ||w'||^2 (a workgroup
 // of its own in kernel B, one of the streaming ones in the fused launch); dots(i): the reduced [h, q] value i.
-template <int T, int G, int U, int MP, class Dots>
-__device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg, Dots dots)
+// keep (form 7 only, see KeepSet): the first tile takes w~, the parity planes and V_0 .. V_{KV-1} from the keep set; its
+// loads ahead of the scalar prologue are D^-1 and the first group behind the kept vectors.  Groups, slots past nv and
+// the order of every addition are those of the other tiles.
+template <int T, int G, int U, int MP, class Dots, class Keep = NoKeep>
+__device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg, Dots dots, Keep *keep = nullptr)
 {
+    constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
+    static_assert(KV % G == 0, "whole groups of basis vectors are kept");
     const int32_t dn = __builtin_nontemporal_load(b.done);  // looked at behind the first loads (see mdot_ws16_kernel)
     __shared__ double hs[kMaxNv], lam[kMaxNv * 8], ys[8], wraws[8], tus[8];
     __shared__ double red[T];
@@ -43,7 +48,9 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     // planes of B D and the first group of basis vectors depend on none of it, and the prologue is a chain of two
     // memory round trips of its own (kernel of 16 us on the 1/8 slab, 8 us of them not bytes)
     constexpr bool PRE = U * (MP > 0 ? MP : 1) <= 16;  // planes of B D fetched ahead too, where the registers allow (not 512 x 4 x 8 rows)
-    double2 wv[U], dv[U], pe[PRE ? NP : 1][U], t0[G][U];
+    static_assert(KP == 0 || (PRE && KP <= NP / 2), "kept planes are parity planes fetched ahead");
+    const bool kpl = KP > 0 && b.packed && m > 0;   // (as in mdot_tiles: the first tile's planes are in the keep set)
+    double2 wv[U], dv[U], pe[PRE ? NP : 1][U], t0[G][U], tdead;
     int64_t idx[U];
     bool ok[U];
     int64_t tile = bx;
@@ -58,26 +65,38 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             }
         }
     };
-    auto load_tile = [&](int64_t tl) {
+    auto load_tile = [&](int64_t tl, bool KF) {   // KF: the kept tile
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             idx[u] = tl * (T * U) + u * T + threadIdx.x;
             ok[u] = idx[u] < n2;
             if (!ok[u]) idx[u] = 0;
-            wv[u] = ld2(b.w, idx[u]);
+            wv[u] = KF && KW ? keep->get(0, u) : ld2(b.w, idx[u]);
             dv[u] = ld2(b.dinv, idx[u]);
         }
-        if (MP > 0 && PRE) load_planes();
+        if (MP > 0 && PRE) {
+            if (KF && kpl) {
+#pragma unroll
+                for (int q = 0; q < NP; ++q) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) pe[q][u] = q < KP ? keep->get(KW + q, u) : double2{0.0, 0.0};
+                }
+            } else {
+                load_planes();
+            }
+        }
+        if (KF && KV > 0) tdead = ld2s<true>(b.V, 0);   // what a slot past nv loads
+        const int v0 = KF ? KV : 0;   // the first group that is not kept
 #pragma unroll
         for (int v = 0; v < G; ++v) {
-            const bool live = v < nv;
-            const double *Vi = b.V + (size_t)(live ? v : 0) * b.ldv;
+            const bool live = v0 + v < nv;
+            const double *Vi = b.V + (size_t)(live ? v0 + v : 0) * b.ldv;
 #pragma unroll
             for (int u = 0; u < U; ++u) t0[v][u] = ld2s<true>(Vi, live ? idx[u] : 0);
         }
     };
     bool have = is_main && tile * (T * U) < n2;
-    if (have) load_tile(tile);
+    if (have) load_tile(tile, Keep::any);
 
     // ---- scalars, derived by every workgroup from the reduced [h, q]; all their loads first
     double lamv = 0.0;
@@ -194,7 +213,9 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         return;
     }
     double nrm = 0.0;
+    bool KF = Keep::any;   // the tile at hand is the first one: its kept basis vectors come out of the keep set
     while (have) {
+        const int v0 = KF ? KV : 0;
         double2 sv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) sv[u].x = sv[u].y = 0.0;
@@ -237,17 +258,34 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                 }
             }
         }
-        // first group of basis vectors: already here
+        // kept basis vectors, in the groups of the other tiles (a group past the first runs only below nv)
 #pragma unroll
-        for (int v = 0; v < G; ++v) {
-            const double ai = v < nv ? -hs[v] : 0.0;
+        for (int s = 0; s < KV; ++s) {
+            if (KF && (s < G || s / G * G < nv)) {  // wave-uniform
+                const bool live = s < nv;
+                const double ai = live ? -hs[s] : 0.0;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                wv[u].x += ai * t0[v][u].x;
-                wv[u].y += ai * t0[v][u].y;
+                for (int u = 0; u < U; ++u) {
+                    double2 tk = tdead;
+                    if (live) tk = keep->get(KW + KP + s, u);
+                    wv[u].x += ai * tk.x;
+                    wv[u].y += ai * tk.y;
+                }
             }
         }
-        for (int g0 = G; g0 < nv; g0 += G) {
+        // first group of basis vectors that is not kept: already here
+        if (v0 == 0 || v0 < nv) {
+#pragma unroll
+            for (int v = 0; v < G; ++v) {
+                const double ai = v0 + v < nv ? -hs[v0 + v] : 0.0;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    wv[u].x += ai * t0[v][u].x;
+                    wv[u].y += ai * t0[v][u].y;
+                }
+            }
+        }
+        for (int g0 = v0 + G; g0 < nv; g0 += G) {
             double2 t[G][U];
             double ai[G];
 #pragma unroll
@@ -314,13 +352,14 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         tile += gmain;
         have = tile * (T * U) < n2;
         if (have) {
-            load_tile(tile);
+            load_tile(tile, false);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 wv[u].x *= s_w;
                 wv[u].y *= s_w;
             }
         }
+        KF = false;
     }
     // ||w'||^2 of this workgroup's entries.  The partial goes to slot bx -- the FIRST TILE this workgroup
     // streamed -- so that the reducer adds the partials in tile order whichever way the grid was walked
@@ -391,6 +430,7 @@ int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial 
 //      with the sentinel (a value is its own flag; the launch arms the OTHER of two lines for the next launch);
 //   3. every workgroup requests its first tile of kernel B, then waits for the totals it needs, and runs kernel B's body;
 //      kernel B's scalar workgroup duties go to workgroup grid - 2 (one that streams the fewest MDot tiles).
+// The operands of a workgroup's first tile, the same tile in both passes, stay on chip between them (GsKeep below).
 // The tile mapping and every summation order are those of the two launches: the results are the same bits.  The waits
 // need every workgroup resident at once (gs_fused_occupancy) and are bounded: a wait that gives up raises the context's
 // execution-error word.
@@ -416,14 +456,29 @@ struct TotalsWait {   // kernel B's dots(i): spins (bounded) while the totals li
 
 constexpr int kGsT = 512, kGsU = 4, kGsG = 4;   // vec_shape's fat shape (mdot_kernel<NG, 512, 4, true, 4>, kernel B <512, 4, 4, MP>)
 
+// The keep set of instantiation <NG, MP> (GsArgs::keep; without it an empty one): w~ and, where kernel B fetches them
+// ahead (MP = 4), the two parity planes in registers, V_0 .. V_3 in LDS (4 x 32 KiB beside 12 992 B; a fifth does not
+// fit 160 KiB).  Sized by the compiler's resource remark on gfx950 (tests/test_gs_keep_resources_cpu.py):
+// no scratch, <= 256 registers for every instantiation -- <5, 4> with the planes kept spills 19 VGPRs, so it keeps
+// w~ and the basis vectors only.
 template <int NG, int MP>
+struct GsKeep {
+    static constexpr int KP = MP == 4 && NG <= 4 ? 2 : 0, KV = 4;
+    using type = KeepSet<kGsT, kGsU, 1, KP, KV, 1 + KP>;
+};
+
+template <int NG, int MP, bool KEEP>
 __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
 {
     constexpr int NA = NG * 8 + 1, W = kGsT / kWave;
+    using Keep = typename std::conditional<KEEP, typename GsKeep<NG, MP>::type, KeepSet<kGsT, kGsU, 0, 0, 0, 0>>::type;
     __shared__ double lds[(W * NA > kGsT) ? W * NA : kGsT];
+    __shared__ double2 klds[Keep::KL > 0 ? Keep::KL * kGsU * kGsT : 1];
+    Keep keep;
+    keep.l = klds;
     if (blockIdx.x == 0 && threadIdx.x < kWave) publish(g.tot_next + threadIdx.x, __longlong_as_double((long long)kSentinelBits));
     if (*b.done) return;
-    mdot_tiles<NG, kGsT, kGsG, true, kGsU>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1, g.split, lds);
+    mdot_tiles<NG, kGsT, kGsG, true, kGsU>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1, g.split, lds, &keep);
     if (arrive_last(gridDim.x)) {
         const int k = g.cnt + 1;
         final_reduce(g.partials, gridDim.x, kPartialLd, k, lds, g.fe);
@@ -432,7 +487,7 @@ __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
             publish(g.tot + threadIdx.x, lds[threadIdx.x]);
         }
     }
-    maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe});
+    maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe}, &keep);
 }
 
 #define SPK_GS_SWITCH(NGV, MPV, CASE)                                                        \
@@ -442,11 +497,14 @@ __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
     case 18: CASE(1, 8); case 28: CASE(2, 8); case 38: CASE(3, 8); case 48: CASE(4, 8); default: CASE(5, 8); \
     }
 
-int gs_fused_occupancy(int ng, int m)
+int gs_fused_occupancy(int ng, int m, bool keep)
 {
     const int mp = m == 0 ? 0 : (m <= 4 ? 4 : 8);
     int nb = 0;
-#define SPK_GS_OCC(NG, MP) SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP>, kGsT, 0)); break
+#define SPK_GS_OCC(NG, MP)                                                                                          \
+    if (keep) SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, true>, kGsT, 0));  \
+    else SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, false>, kGsT, 0));      \
+    break
     SPK_GS_SWITCH(ng, mp, SPK_GS_OCC)
 #undef SPK_GS_OCC
     return nb;
@@ -469,7 +527,10 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s)
     b.gmain = (int)grid;
     const int ng = (g.cnt + 7) / 8 > 0 ? (g.cnt + 7) / 8 : 1;
     const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
-#define SPK_GS_LAUNCH(NG, MP) hipLaunchKernelGGL((gs_fused_kernel<NG, MP>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); break
+#define SPK_GS_LAUNCH(NG, MP)                                                                                       \
+    if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);  \
+    else hipLaunchKernelGGL((gs_fused_kernel<NG, MP, false>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);        \
+    break
     SPK_GS_SWITCH(ng, mp, SPK_GS_LAUNCH)
 #undef SPK_GS_LAUNCH
     return b.gmain;

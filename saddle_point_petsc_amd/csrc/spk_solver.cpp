@@ -53,14 +53,14 @@ void spk_ctx::check_device_error()
                       "sums within %.1f s): execution failure, the result of this call is not valid", fin_ticks / 1e8);
 }
 
-bool spk_ctx::gs_fused_fits(int64_t nl, int m)
+bool spk_ctx::gs_fused_fits(int64_t nl, int m, bool keep)
 {
     const int64_t grid = k::gs_fused_grid(nl);
     if (!grid) return false;
-    const int mi = m == 0 ? 0 : (m <= 4 ? 1 : 2);
+    const int mi = (m == 0 ? 0 : (m <= 4 ? 1 : 2)) + (keep ? 3 : 0);
     if (gs_occ[mi] < 0) {   // blocks per CU of the fused kernel at its real block size and LDS: the fewest over its instantiations
         int occ = 1 << 30;
-        for (int ng = 1; ng <= 5; ++ng) occ = std::min(occ, k::gs_fused_occupancy(ng, m));
+        for (int ng = 1; ng <= 5; ++ng) occ = std::min(occ, k::gs_fused_occupancy(ng, m, keep));
         gs_occ[mi] = occ;
     }
     return (int64_t)gs_occ[mi] * num_cus >= grid;
@@ -1311,6 +1311,7 @@ struct FgmresPlan {
     bool schur, head;     // a head kernel scales v_j, runs the Givens step of j-1; Schur: B D w' out of the last MAXPY
     bool big;             // restart > kMaxNv - 2: the Givens step is a launch of its own
     bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
+    int gs_keep;          // form 7: the first tile's operands stay on chip between its two passes (SPK_GS_KEEP=0: not, for tests)
     int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
     int nn, bpk, form;    // norm (+ B D w') out of the last MAXPY; B D as m/2 parity planes; what is reported
     const double *bdp;    // the B D rows the kernels stream (Schur)
@@ -1376,8 +1377,11 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
                  k::resident_fits(c->Adict, c->num_cus, mk, res_planes);
     // GS_FUSED (form 7): MDot and kernel B in one launch (every iteration of a cycle but its last) -- one rank, fat vectors,
     // every workgroup of the launch resident at once; what AUTO takes there
+    // (the knob is read per solve, so that a test can flip it between two solves of one context)
+    const char *keep_env = getenv("SPK_GS_KEEP");
+    p.gs_keep = keep_env && !strcmp(keep_env, "0") ? 0 : 1;
     p.gsf = un3 && !p.resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
-            c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m);
+            c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m, p.gs_keep != 0);
     p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
     p.orth = un3 ? FgmresPlan::kOrthUn3 : o.orthog == SPK_ORTHOG_MGS ? FgmresPlan::kOrthMgs
            : single ? FgmresPlan::kOrthSingle : FgmresPlan::kOrthCgs;
@@ -1513,7 +1517,7 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     if (gs) {
         k::GsArgs g{};
         g.V2 = schur ? (r.p.bpk ? c->bdpk.p : c->bd.p) : nullptr;
-        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk;
+        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk; g.keep = r.p.gs_keep;
         g.n2 = (r.N + 1) / 2; g.n_dot = r.n_dot;
         g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
         g.out = db;
