@@ -557,6 +557,8 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
 }
 
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
+// (n_local % 2: never false here -- the 2x2 blocked copy the row types are built over exists only for an even n_local;
+// the condition states what amg_cheb_dict2 needs rather than guarding a case that occurs)
 static bool fused_fine(const spk_ctx *c)
 {
     return c->spmv_format != 0 && c->Adict.ok && c->Adict.bs == 2 && c->n_ghost == 0 && c->n_local % 2 == 0;

@@ -351,7 +351,8 @@ __device__ __forceinline__ bool head_begin(SolverHead *h, double dot, double sq,
     }
     int reason = dot < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : converged_default(rn, st);
     if (!reason && st->its >= st->max_it) reason = SPK_DIVERGED_ITS;
-    if (!reason && !(dot > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;   // M^-1 r = 0 with r != 0
+    // M^-1 r = 0 with r != 0; a NaN that reached only M^-1 r (a NaN in diag(A)) leaves ||r|| finite in the unpreconditioned norm
+    if (!reason && !(dot > 0.0)) reason = isnan(dot) ? SPK_DIVERGED_NANORINF : SPK_DIVERGED_BREAKDOWN;
     h->tent = 0;
     st->reason = reason;
     if (reason) {

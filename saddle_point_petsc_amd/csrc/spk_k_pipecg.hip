@@ -43,7 +43,7 @@ __device__ void state_step(PipecgState *ps, int mode, const double *sums, double
         ps->rr_idle = 1;
         ps->replacements += 1;
         st->rnorm = rn;
-        int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : !(g > 0.0) ? SPK_DIVERGED_BREAKDOWN : 0;
+        int reason = g < 0.0 ? SPK_DIVERGED_INDEFINITE_PC : isnan(g) ? SPK_DIVERGED_NANORINF : !(g > 0.0) ? SPK_DIVERGED_BREAKDOWN : 0;
         double beta = 0.0, den = 0.0;
         if (!reason) {
             beta = g / ps->gamma_old;
@@ -87,7 +87,7 @@ __device__ void state_step(PipecgState *ps, int mode, const double *sums, double
         reason = SPK_DIVERGED_ITS;
         ps->tent = 1;
     }
-    if (!reason && !(g > 0.0)) reason = SPK_DIVERGED_BREAKDOWN;
+    if (!reason && !(g > 0.0)) reason = isnan(g) ? SPK_DIVERGED_NANORINF : SPK_DIVERGED_BREAKDOWN;
     double beta = 0.0, den = 0.0;
     if (!reason) {
         beta = g / ps->gamma;

@@ -80,11 +80,47 @@ def vcycle_ref(A, P, Ci, lam, b, smoother="chebyshev", smooth_its=2, esteig=(0, 
     return rec(0, np.asarray(b, np.float64))
 
 
-@pytest.fixture(scope="module", params=[16, 32, 64])
+def general_spd(n, seed):
+    """A general (non-grid) symmetric strictly diagonally dominant operator: 1-7 negative off-diagonals per row before
+    symmetrising, no block structure, no Dirichlet rows.  Returns the CSR for the product and the scipy matrix."""
+    rng = np.random.default_rng(seed)
+    rows, cols, vals = [], [], []
+    for i in range(n):
+        c = rng.choice(n, int(rng.integers(1, 8)), replace=False)
+        c = c[c != i]
+        rows += [i] * len(c); cols += list(c); vals += list(-0.3 * np.abs(rng.standard_normal(len(c))))
+    O = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
+    O = O + O.T                                            # symmetric pattern, negative off-diagonals
+    d = np.asarray(abs(O).sum(1)).ravel() + 0.05 + rng.random(n)   # strictly diagonally dominant
+    A = (O + sp.diags(d)).tocsr(); A.sort_indices()
+    return S.CSR(A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.copy(), n), A
+
+
+def _grid(A):
+    return A, sp.csr_matrix((A.val, A.colidx, A.rowptr), shape=(A.nrows, A.nrows))
+
+
+# Operators off the square 2-D grid (test_gpu_offgrid.py runs the device on the same ones): name -> (builder of
+# (CSR, scipy), builder options, block size the builder must report, whether Dirichlet (isolated) nodes exist)
+OFFGRID_BUILT = {
+    "cube_odd": (lambda: _grid(S.AssembleOperator_Laplace3D(9, 9, 11)[0]), {}, 3, True),
+    "gen1001": (lambda: general_spd(1001, 1001), {}, 1, False),
+    "odd33_bs1": (lambda: _grid(S.AssembleOperator_Laplace(33, 33)[0]), dict(block_size=1), 1, True),
+    "strip": (lambda: _grid(S.AssembleOperator_Laplace(50, 7)[0]), {}, 2, True),
+}
+
+
+@pytest.fixture(scope="module", params=[16, 32, 64] + list(OFFGRID_BUILT))
 def built(request):
-    A, f, Asp = laplace(request.param)
-    h = S.AmgHierarchy(A)
-    yield request.param, A, Asp, h
+    """(name, A, scipy A, hierarchy, block size expected, has isolated nodes)"""
+    if isinstance(request.param, int):
+        A, f, Asp = laplace(request.param)
+        kw, bs, iso = {}, 2, True
+    else:
+        make, kw, bs, iso = OFFGRID_BUILT[request.param]
+        A, Asp = make()
+    h = S.AmgHierarchy(A, **kw)
+    yield request.param, A, Asp, h, bs, iso
     h.close()
 
 
@@ -98,22 +134,26 @@ def _isolated_nodes(Asp, bs):
 
 
 def test_aggregates_cover_every_connected_node_once(built):
-    _, A, Asp, h = built
+    _, A, Asp, h, bs, has_iso = built
     info = h.info()
-    assert info["block_size"] == 2 and info["levels"] >= 2
+    assert info["block_size"] == bs and info["levels"] >= 2
     agg = h.aggregates(0)
-    iso = _isolated_nodes(Asp, 2)
-    assert iso.any()                                # the Dirichlet nodes are there ...
+    assert len(agg) * bs == A.nrows
+    iso = _isolated_nodes(Asp, bs)
+    if has_iso:
+        assert iso.any()                            # the Dirichlet nodes are there ...
+    else:
+        assert not iso.any()                        # (a general operator has none)
     assert np.all(agg[iso] == -1)                   # ... and lie in no aggregate
     assert np.all(agg[~iso] >= 0)                   # every other node lies in exactly one (one index per node)
     na = agg.max() + 1
     assert np.all(np.bincount(agg[agg >= 0], minlength=na) > 0)
     Pt = to_sp(h.matrix(0, S.AMG_TENTATIVE))
-    assert Pt.shape == (A.nrows, 2 * na)
+    assert Pt.shape == (A.nrows, bs * na)
 
 
 def test_tentative_prolongator_is_orthonormal(built):
-    _, _, _, h = built
+    h = built[3]
     for l in range(h.info()["levels"] - 1):
         Pt = to_sp(h.matrix(l, S.AMG_TENTATIVE))
         G = (Pt.T @ Pt).toarray()
@@ -121,7 +161,7 @@ def test_tentative_prolongator_is_orthonormal(built):
 
 
 def test_coarse_operators_are_galerkin_and_symmetric(built):
-    _, _, _, h = built
+    h = built[3]
     info = h.info()
     for l in range(info["levels"] - 1):
         Al, P, Ac = (to_sp(h.matrix(l, S.AMG_OP)), to_sp(h.matrix(l, S.AMG_PROLONG)), to_sp(h.matrix(l + 1, S.AMG_OP)))
@@ -132,7 +172,7 @@ def test_coarse_operators_are_galerkin_and_symmetric(built):
 
 
 def test_lambda_max_from_below_within_ten_percent(built):
-    _, _, _, h = built
+    h = built[3]
     info = h.info()
     for l in range(info["levels"] - 1):
         Al = to_sp(h.matrix(l, S.AMG_OP))
@@ -151,6 +191,25 @@ def test_levels_stop_at_coarse_eq_limit(limit):
     assert rows[-1] <= limit and all(r > limit for r in rows[:-1])
     h2 = S.AmgHierarchy(A, coarse_eq_limit=limit, max_levels=2)
     assert h2.info()["levels"] == 2
+
+
+def test_one_level_hierarchy_and_block_sizes_that_do_not_divide():
+    """Seven rows are below coarse_eq_limit: one level, only the dense coarse inverse.  A block size that does not
+    divide the number of rows is refused, not rounded."""
+    A7, A7sp = general_spd(7, 7)
+    h = S.AmgHierarchy(A7)
+    info = h.info()
+    assert info["levels"] == 1 and info["rows"] == [7]
+    Ci = to_sp(h.matrix(0, S.AMG_COARSE_INV)).toarray()
+    assert np.abs(Ci @ A7sp.toarray() - np.eye(7)).max() < 1e-13
+    h.close()
+    A1001, _ = general_spd(1001, 1001)
+    A700, _ = S.AssembleOperator_Laplace(50, 7)
+    for A, bs in ((A1001, 2), (A700, 3)):
+        assert A.nrows % bs
+        with pytest.raises(SpkError) as e:
+            S.AmgHierarchy(A, block_size=bs)
+        assert e.value.code == SPK_ERR_ARG and "does not divide" in str(e.value)
 
 
 def test_two_builds_are_byte_identical():
