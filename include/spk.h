@@ -260,14 +260,18 @@ int spk_pc_set_inner(spk_ctx *ctx, int sweeps, double omega);
  * -fieldsplit_0_pc_type gamg inside the Schur fieldsplit).  One V-cycle per application: nu smoothing steps
  * (Chebyshev with Jacobi inside, or damped-Jacobi Richardson) before and after the coarse-grid correction,
  * R = P^T, the coarsest operator inverted exactly (dense, at most SPK_AMG_MAX_COARSE equations).  The hierarchy
- * is built on the host at spk_pc_setup from the A00 block the context holds (Vanek's greedy three-phase
- * aggregation over the bs x bs node graph -- not PETSc's MIS coarsening; see DESIGN.md "Algebraic multigrid").
+ * is built at spk_pc_setup from the A00 block the context holds (Vanek's greedy three-phase aggregation over the
+ * bs x bs node graph -- not PETSc's MIS coarsening; see DESIGN.md "Algebraic multigrid"): on the host and uploaded
+ * (setup = SPK_AMG_SETUP_HOST, the default), or on the device from the context's CSR copy of A00
+ * (SPK_AMG_SETUP_DEVICE: node graph, Lanczos, the sparse products and the transposes are kernels; only the greedy
+ * aggregation and the dense coarse Cholesky stay on the host, so the aggregates and every pattern are the host's).
  * spk_pc_set_amg(ctx, &o) before spk_pc_setup switches it on, NULL switches it off; SPK_PC_JACOBI then means
  * M^-1 = one V-cycle on A (no B block), SPK_PC_SCHUR takes the V-cycle wherever it takes diag(A)^-1 (S^ stays
  * diag(B diag(A)^-1 B^T)).  spk_fgmres runs it on the step-by-step path (spk_get_iteration_form reports -1).
  * Out of scope, refused with SPK_ERR_UNSUPPORTED: more than one rank (at spk_pc_setup; the context stays usable),
  * spk_minres with it (spk_pipecg takes it on K = A), and FP32 inner sweeps beside it (spk_pc_set_inner > 0 and spk_pc_set_amg are exclusive). */
 enum { SPK_AMG_CHEBYSHEV = 0, SPK_AMG_RICHARDSON = 1 };
+enum { SPK_AMG_SETUP_HOST = 0, SPK_AMG_SETUP_DEVICE = 1 };
 #define SPK_AMG_MAX_LEVELS 16
 #define SPK_AMG_MAX_COARSE 1024
 typedef struct spk_amg_opts {
@@ -281,6 +285,8 @@ typedef struct spk_amg_opts {
     double esteig[4];         /* -mg_levels_ksp_chebyshev_esteig a,b,c,d (0,0.1,0,1.1): the Chebyshev interval is
                                  [a lmin + b lmax, c lmin + d lmax], lmin / lmax the extreme Ritz values of D^-1 A_l */
     double richardson_scale;  /* -mg_levels_ksp_richardson_scale    (1.0) */
+    int32_t setup;            /* -spk_gamg_setup host|device: SPK_AMG_SETUP_* (host); spk_amg_build_host takes either
+                                 and builds on the host */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -290,17 +296,20 @@ typedef struct spk_amg_info {
     int64_t nnz[SPK_AMG_MAX_LEVELS];
     double lambda_max[SPK_AMG_MAX_LEVELS];   /* largest Ritz value of D^-1 A_l (the coarsest level: 0) */
     double operator_complexity;              /* sum of nnz(A_l) / nnz(A_0) */
-    double setup_seconds;                    /* host build + upload */
+    double setup_seconds;                    /* host build + upload; device build: its wall time up to a device synchronise */
+    int32_t setup;                           /* where this hierarchy was built: SPK_AMG_SETUP_* */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
 /* Test hook: one matrix of a level as CSR (sorted columns).  which: SPK_AMG_OP = A_l, SPK_AMG_PROLONG = P_l (rows of
  * level l, columns of level l+1), SPK_AMG_TENTATIVE = the tentative prolongator of level l, SPK_AMG_COARSE_INV = the
  * dense inverse of the coarsest operator (level = levels - 1) as full rows.  Call with rowptr / colidx / val NULL first
- * for the sizes. */
+ * for the sizes.  A device-built hierarchy is downloaded on demand, one matrix per call. */
 enum { SPK_AMG_OP = 0, SPK_AMG_PROLONG = 1, SPK_AMG_TENTATIVE = 2, SPK_AMG_COARSE_INV = 3 };
 int spk_get_amg_level(const spk_ctx *ctx, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
                       int32_t *rowptr, int32_t *colidx, double *val);
+/* Test hook: the aggregate of every node of a level of the context's hierarchy (-1: isolated); agg NULL for the size. */
+int spk_get_amg_aggregates(const spk_ctx *ctx, int level, int32_t *nnodes, int32_t *agg);
 /* Host-only builder (no GPU): the same hierarchy from a square CSR matrix, for tests.  agg: the aggregate of every
  * node of a level (-1: isolated, in no aggregate).  Errors: spk_last_error(NULL). */
 typedef struct spk_amg_hier spk_amg_hier;

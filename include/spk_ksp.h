@@ -68,6 +68,7 @@ int SpkKSPGetSolveTime(SpkKSP ksp, double *seconds);
 int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schur_fact);
 /* Multigrid options as read: fieldsplit0 = 0 the plain set (-pc_type gamg on K = A: -pc_gamg_threshold,
  * -pc_gamg_agg_nsmooths, -pc_gamg_coarse_eq_limit, -pc_mg_levels, -mg_levels_ksp_type chebyshev|richardson,
+ * -spk_gamg_setup host|device (where the hierarchy is built; -ksp_view names it),
  * -mg_levels_ksp_max_it, -mg_levels_ksp_richardson_scale, -mg_levels_ksp_chebyshev_esteig a,b,c,d,
  * -mg_levels_pc_type jacobi), 1 the same names with the -fieldsplit_0_ prefix (-fieldsplit_0_pc_type gamg inside
  * -pc_type fieldsplit).  *selected = 1 when that gamg was asked for.  Unknown -mg_ options are refused like unknown

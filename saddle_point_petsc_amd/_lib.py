@@ -70,7 +70,7 @@ class AmgOpts(C.Structure):
     _fields_ = [
         ("max_levels", C.c_int32), ("coarse_eq_limit", C.c_int32), ("nsmooths", C.c_int32), ("smoother", C.c_int32),
         ("threshold", C.c_double), ("smooth_its", C.c_int32), ("block_size", C.c_int32), ("esteig", C.c_double * 4),
-        ("richardson_scale", C.c_double),
+        ("richardson_scale", C.c_double), ("setup", C.c_int32),
     ]
 
 
@@ -79,7 +79,7 @@ class AmgInfo(C.Structure):
     _fields_ = [
         ("levels", C.c_int32), ("block_size", C.c_int32), ("rows", C.c_int32 * AMG_MAX_LEVELS),
         ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("lambda_max", C.c_double * AMG_MAX_LEVELS),
-        ("operator_complexity", C.c_double), ("setup_seconds", C.c_double),
+        ("operator_complexity", C.c_double), ("setup_seconds", C.c_double), ("setup", C.c_int32),
     ]
 
 
@@ -168,6 +168,7 @@ def _load():
     L.spk_pc_set_amg.argtypes = [vp, C.POINTER(AmgOpts)]
     L.spk_get_amg_info.argtypes = [vp, C.POINTER(AmgInfo)]
     L.spk_get_amg_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
+    L.spk_get_amg_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
     L.spk_amg_build_host.argtypes = [i32, i32p, i32p, f64p, C.POINTER(AmgOpts), C.POINTER(vp)]
     L.spk_amg_destroy_host.argtypes = [vp]
     L.spk_amg_host_info.argtypes = [vp, C.POINTER(AmgInfo)]

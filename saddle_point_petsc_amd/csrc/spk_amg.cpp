@@ -1,5 +1,6 @@
-// spk_amg.cpp -- smoothed-aggregation algebraic multigrid (-pc_type gamg): the hierarchy, built on the host at
-// KSPSetUp from the A00 CSR, its upload, and the V-cycle's launch sequence (kernels: spk_k_amg.hip).
+// spk_amg.cpp -- smoothed-aggregation algebraic multigrid (-pc_type gamg): the hierarchy, built at KSPSetUp from the
+// A00 CSR on the host and uploaded (the default) or on the device (-spk_gamg_setup device: amg_build_device, kernels:
+// spk_k_amg_setup.hip), and the V-cycle's launch sequence (kernels: spk_k_amg.hip).
 //
 // Every step is deterministic (fixed traversal orders, no hashing of pointers, a fixed Lanczos start vector): two
 // builds of the same matrix give the same bytes, and so do two V-cycles.  DESIGN.md "Algebraic multigrid" has the
@@ -160,6 +161,30 @@ int sturm_count(const std::vector<double> &al, const std::vector<double> &be, do
     return cnt;
 }
 
+// extreme eigenvalues of the Lanczos tridiagonal (al, be[1..k)) by Sturm bisection: lmax from below, lmin from above
+void ritz_extremes(const std::vector<double> &al, const std::vector<double> &be, double *lmin, double *lmax)
+{
+    double glo = al[0], ghi = al[0];   // Gershgorin bounds of the tridiagonal
+    for (size_t i = 0; i < al.size(); ++i) {
+        const double r = (i ? std::fabs(be[i]) : 0.0) + (i + 1 < al.size() ? std::fabs(be[i + 1]) : 0.0);
+        glo = std::min(glo, al[i] - r);
+        ghi = std::max(ghi, al[i] + r);
+    }
+    const int m = (int)al.size();
+    double lo = glo, hi = ghi;
+    for (int it = 0; it < 200 && hi - lo > 1e-15 * std::max(1.0, std::fabs(hi)); ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (sturm_count(al, be, mid) >= m) hi = mid; else lo = mid;
+    }
+    *lmax = lo;   // below the largest Ritz value
+    lo = glo, hi = ghi;
+    for (int it = 0; it < 200 && hi - lo > 1e-15 * std::max(1.0, std::fabs(hi)); ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (sturm_count(al, be, mid) >= 1) hi = mid; else lo = mid;
+    }
+    *lmin = hi;
+}
+
 // extreme Ritz values of D^-1 A after `steps` Lanczos steps on the similar D^-1/2 A D^-1/2, from a fixed start vector.
 // Ritz values lie inside the spectrum: both estimates approach from within (lmax from below).
 void lanczos(const HostCsr &A, const std::vector<double> &dinv, int steps, double *lmin, double *lmax)
@@ -199,25 +224,7 @@ void lanczos(const HostCsr &A, const std::vector<double> &dinv, int steps, doubl
         qp.swap(q);
         for (int32_t i = 0; i < n; ++i) q[(size_t)i] = w[(size_t)i] / nb;
     }
-    double glo = al[0], ghi = al[0];   // Gershgorin bounds of the tridiagonal
-    for (size_t i = 0; i < al.size(); ++i) {
-        const double r = (i ? std::fabs(be[i]) : 0.0) + (i + 1 < al.size() ? std::fabs(be[i + 1]) : 0.0);
-        glo = std::min(glo, al[i] - r);
-        ghi = std::max(ghi, al[i] + r);
-    }
-    const int m = (int)al.size();
-    double lo = glo, hi = ghi;
-    for (int it = 0; it < 200 && hi - lo > 1e-15 * std::max(1.0, std::fabs(hi)); ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (sturm_count(al, be, mid) >= m) hi = mid; else lo = mid;
-    }
-    *lmax = lo;   // below the largest Ritz value
-    lo = glo, hi = ghi;
-    for (int it = 0; it < 200 && hi - lo > 1e-15 * std::max(1.0, std::fabs(hi)); ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (sturm_count(al, be, mid) >= 1) hi = mid; else lo = mid;
-    }
-    *lmin = hi;
+    ritz_extremes(al, be, lmin, lmax);
 }
 
 // strong-connection graph of the bs x bs nodes (sorted neighbour lists, the node itself left out)
@@ -371,6 +378,8 @@ void amg_check_opts(const spk_amg_opts &o)
     for (double e : o.esteig)
         if (!std::isfinite(e)) fail(SPK_ERR_ARG, "amg: esteig factors must be finite");
     if (!(o.richardson_scale > 0.0) || !std::isfinite(o.richardson_scale)) fail(SPK_ERR_ARG, "amg: richardson_scale must be > 0");
+    if (o.setup != SPK_AMG_SETUP_HOST && o.setup != SPK_AMG_SETUP_DEVICE)
+        fail(SPK_ERR_ARG, "amg: setup %d is neither SPK_AMG_SETUP_HOST (0) nor SPK_AMG_SETUP_DEVICE (1)", o.setup);
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
@@ -511,6 +520,25 @@ static void upload_host_csr(CsrDev &D, const HostCsr &H)
     D.val.upload(H.v.data(), H.v.size(), 4);
 }
 
+// the smoothing steps of a level from its Chebyshev interval [lo, hi]
+static void smoother_coeffs(AmgLevelDev &D, const spk_amg_opts &o, double lo, double hi)
+{
+    const int nu = o.smooth_its;
+    D.alpha.assign((size_t)nu, o.richardson_scale);
+    D.beta.assign((size_t)nu, 0.0);
+    if (o.smoother == SPK_AMG_CHEBYSHEV) {   // Saad, Alg. 12.1: d_k = rho_k rho_{k-1} d_{k-1} + 2 rho_k / delta D^-1 r_k
+        const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+        double rho = 1.0 / sigma;
+        D.alpha[0] = 1.0 / theta;
+        for (int k = 1; k < nu; ++k) {
+            const double rn = 1.0 / (2.0 * sigma - rho);
+            D.alpha[(size_t)k] = 2.0 * rn / delta;
+            D.beta[(size_t)k] = rn * rho;
+            rho = rn;
+        }
+    }
+}
+
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
 {
     const auto t0 = std::chrono::steady_clock::now();
@@ -534,26 +562,369 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
         if (l == 0) D.t.alloc(nv, 16);
         upload_host_csr(D.P, H.P);
         upload_host_csr(D.R, H.R);
-        const int nu = h.o.smooth_its;
-        D.alpha.assign((size_t)nu, h.o.richardson_scale);
-        D.beta.assign((size_t)nu, 0.0);
-        if (h.o.smoother == SPK_AMG_CHEBYSHEV) {   // Saad, Alg. 12.1: d_k = rho_k rho_{k-1} d_{k-1} + 2 rho_k / delta D^-1 r_k
-            const double theta = 0.5 * (H.hi + H.lo), delta = 0.5 * (H.hi - H.lo), sigma = theta / delta;
-            double rho = 1.0 / sigma;
-            D.alpha[0] = 1.0 / theta;
-            for (int k = 1; k < nu; ++k) {
-                const double rn = 1.0 / (2.0 * sigma - rho);
-                D.alpha[(size_t)k] = 2.0 * rn / delta;
-                D.beta[(size_t)k] = rn * rho;
-                rho = rn;
-            }
-        }
+        smoother_coeffs(D, h.o, H.lo, H.hi);
     }
     d->cinv.upload(h.cinv.data(), h.cinv.size());
     SPK_HIP(hipDeviceSynchronize());
     hp->h.setup_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     c->amg_d = std::move(d);
     c->amg_h = std::move(hp);
+}
+
+// ---------------------------------------------------------------------------
+// the same hierarchy built on the device (-spk_gamg_setup device; kernels: spk_k_amg_setup.hip).  Per level: node graph
+// -> host (the greedy aggregation is sequential by definition and runs unchanged, so the aggregates and every pattern
+// are the host build's) -> tentative prolongator, Lanczos, the products and transposes as kernels.  Only the graph,
+// the aggregates, the Lanczos scalars and the coarsest operator cross the bus.
+// ---------------------------------------------------------------------------
+namespace {
+
+int32_t scan_counts(const int32_t *cnt, int32_t n, int32_t *out, hipStream_t s)   // out[0..n]; returns out[n]
+{
+    DevBuf<int32_t> scr;
+    scr.alloc_raw((size_t)n / 2048 + 8);
+    k::exclusive_scan_i32(cnt, n, out, scr.p, s);
+    int32_t tot = 0;
+    SPK_HIP(hipMemcpyAsync(&tot, out + n, sizeof tot, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    return tot;
+}
+
+void dev_csr_values(CsrDev &C, int64_t nnz)
+{
+    C.nnz = nnz;
+    C.colidx.alloc_raw((size_t)nnz, 4);
+    C.val.alloc_raw((size_t)nnz, 4);
+}
+
+void dev_csr_copy(CsrDev &C, const CsrDev &A, hipStream_t s)
+{
+    C.nrows = A.nrows;
+    C.ncols = A.ncols;
+    C.rowptr.alloc_raw((size_t)A.nrows + 1, 8);
+    dev_csr_values(C, A.nnz);
+    SPK_HIP(hipMemcpyAsync(C.rowptr.p, A.rowptr.p, sizeof(int32_t) * ((size_t)A.nrows + 1), hipMemcpyDeviceToDevice, s));
+    if (A.nnz) {
+        SPK_HIP(hipMemcpyAsync(C.colidx.p, A.colidx.p, sizeof(int32_t) * (size_t)A.nnz, hipMemcpyDeviceToDevice, s));
+        SPK_HIP(hipMemcpyAsync(C.val.p, A.val.p, sizeof(double) * (size_t)A.nnz, hipMemcpyDeviceToDevice, s));
+    }
+}
+
+// C = A B (sorted columns, no entry dropped, each entry summed in A's stored order, then B's)
+void dev_spgemm(CsrDev &C, const CsrDev &A, const CsrDev &B, hipStream_t s)
+{
+    const int32_t n = A.nrows;
+    C.nrows = n;
+    C.ncols = B.ncols;
+    DevBuf<int32_t> bound, off, cnt, sc;
+    DevBuf<double> sv;
+    DevBuf<unsigned long long> tot;
+    bound.alloc_raw((size_t)n, 8);
+    off.alloc_raw((size_t)n + 1, 8);
+    cnt.alloc_raw((size_t)n, 8);
+    tot.alloc(1);
+    k::amgs_spgemm_bound(A, B, bound.p, tot.p, s);
+    unsigned long long slots = 0;
+    SPK_HIP(hipMemcpyAsync(&slots, tot.p, sizeof slots, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    if (slots > (unsigned long long)INT32_MAX)
+        fail(SPK_ERR_UNSUPPORTED, "amg: a sparse product of the device set-up needs %llu scratch slots, more than its 32-bit "
+             "offsets address -- use -spk_gamg_setup host", slots);
+    scan_counts(bound.p, n, off.p, s);
+    sc.alloc_raw((size_t)slots, 4);
+    sv.alloc_raw((size_t)slots, 4);
+    k::amgs_spgemm_expand(A, B, off.p, sc.p, sv.p, cnt.p, s);
+    C.rowptr.alloc_raw((size_t)n + 1, 8);
+    dev_csr_values(C, scan_counts(cnt.p, n, C.rowptr.p, s));
+    k::amgs_compact(n, off.p, C.rowptr.p, sc.p, sv.p, C.colidx.p, C.val.p, s);
+    SPK_HIP(hipStreamSynchronize(s));   // the scratch goes out of scope
+}
+
+// C = a A + b diag(scale) B over the union pattern
+void dev_add(CsrDev &C, double a, const CsrDev &A, double b, const CsrDev &B, const double *scale, hipStream_t s)
+{
+    const int32_t n = A.nrows;
+    C.nrows = n;
+    C.ncols = A.ncols;
+    DevBuf<int32_t> cnt;
+    cnt.alloc_raw((size_t)n, 8);
+    k::amgs_add(a, A, b, B, scale, nullptr, nullptr, nullptr, cnt.p, s);
+    C.rowptr.alloc_raw((size_t)n + 1, 8);
+    dev_csr_values(C, scan_counts(cnt.p, n, C.rowptr.p, s));
+    k::amgs_add(a, A, b, B, scale, C.rowptr.p, C.colidx.p, C.val.p, nullptr, s);
+    SPK_HIP(hipStreamSynchronize(s));
+}
+
+void dev_transpose(CsrDev &T, const CsrDev &A, hipStream_t s)
+{
+    T.nrows = A.ncols;
+    T.ncols = A.nrows;
+    DevBuf<int32_t> cnt, pos;
+    cnt.alloc_raw((size_t)T.nrows, 8);
+    pos.alloc_raw((size_t)T.nrows, 8);
+    SPK_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (size_t)T.nrows, s));
+    k::amgs_col_count(A.colidx.p, A.nnz, cnt.p, s);
+    T.rowptr.alloc_raw((size_t)T.nrows + 1, 8);
+    dev_csr_values(T, scan_counts(cnt.p, T.nrows, T.rowptr.p, s));
+    SPK_HIP(hipMemcpyAsync(pos.p, T.rowptr.p, sizeof(int32_t) * (size_t)T.nrows, hipMemcpyDeviceToDevice, s));
+    k::amgs_transpose_fill(A, pos.p, T.colidx.p, T.val.p, s);
+    k::amgs_sort_rows(T.rowptr.p, T.colidx.p, T.val.p, T.nrows, s);
+    SPK_HIP(hipStreamSynchronize(s));
+}
+
+HostCsr dev_csr_download(const CsrDev &A, bool values, hipStream_t s)
+{
+    HostCsr H;
+    H.nrows = A.nrows;
+    H.ncols = A.ncols;
+    H.rp.resize((size_t)A.nrows + 1);
+    SPK_HIP(hipMemcpyAsync(H.rp.data(), A.rowptr.p, sizeof(int32_t) * H.rp.size(), hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    H.ci.resize((size_t)H.rp[(size_t)A.nrows]);
+    H.v.resize(H.ci.size());
+    if (!H.ci.empty()) {
+        SPK_HIP(hipMemcpyAsync(H.ci.data(), A.colidx.p, sizeof(int32_t) * H.ci.size(), hipMemcpyDeviceToHost, s));
+        if (values) SPK_HIP(hipMemcpyAsync(H.v.data(), A.val.p, sizeof(double) * H.v.size(), hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+    }
+    return H;
+}
+
+// the 30 Lanczos steps of `lanczos` with the level's own product (level 0: the context's layout, else the CSR kernel);
+// the two sums of a step come back to the host, which keeps the tridiagonal and the break rule
+void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, int steps, double *lmin, double *lmax)
+{
+    hipStream_t s = c->stream;
+    DevBuf<double> sv, q, qp, w, t, aw, res;
+    for (DevBuf<double> *b : {&sv, &q, &qp, &w, &t, &aw}) b->alloc((size_t)nv, 16);
+    res.alloc(8);
+    const k::Finish f = c->fin(res.p);
+    auto sum = [&]() {
+        double h = 0.0;
+        SPK_HIP(hipMemcpyAsync(&h, res.p, sizeof h, hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+        return h;
+    };
+    k::amgs_lz_init(n, dinv, sv.p, q.p, f, s);
+    const double nq = std::sqrt(sum());
+    k::amgs_lz_scale(n, nq, q.p, sv.p, q.p, t.p, s);
+    std::vector<double> al, be{0.0};
+    const int kk = (int)std::min<int64_t>(steps, n);
+    double *qc = q.p, *qo = qp.p;
+    for (int j = 0; j < kk; ++j) {
+        if (A) k::amg_spmv(*A, t.p, aw.p, nullptr, s);
+        else a_mult(c, t.p, aw.p, nullptr, nullptr, nullptr, false, nullptr);
+        k::amgs_lz_dot(n, sv.p, aw.p, w.p, qc, f, s);
+        const double a = sum();
+        al.push_back(a);
+        k::amgs_lz_update(n, a, be.back(), qc, qo, w.p, f, s);
+        const double nb = std::sqrt(sum());
+        if (j + 1 == kk || nb <= 1e-12 * std::fabs(a)) break;
+        be.push_back(nb);
+        std::swap(qc, qo);
+        k::amgs_lz_scale(n, nb, w.p, sv.p, qc, t.p, s);
+    }
+    c->check_device_error();
+    ritz_extremes(al, be, lmin, lmax);
+}
+
+}  // namespace
+
+std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    spk_amg_opts o = c->amg_opts;
+    amg_check_opts(o);
+    hipStream_t s = c->stream;
+    c->ensure_scratch();
+    const int32_t n0 = c->n_local;
+    if (n0 <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
+    const int64_t ld = ((int64_t)c->n_local + c->m + 255) / 256 * 256;   // as ensure_vectors pads the context's vectors
+
+    // sorted columns: the context's CSR as it is when every row ascends, else a sorted copy
+    CsrDev A0s;
+    const CsrDev *A0 = &c->Ad;
+    {
+        DevBuf<int32_t> flag;
+        flag.alloc(1);
+        k::amgs_rows_sorted(c->Ad.rowptr.p, c->Ad.colidx.p, n0, flag.p, s);
+        int32_t unsorted = 0;
+        SPK_HIP(hipMemcpyAsync(&unsorted, flag.p, sizeof unsorted, hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+        if (unsorted) {
+            dev_csr_copy(A0s, c->Ad, s);
+            k::amgs_sort_rows(A0s.rowptr.p, A0s.colidx.p, A0s.val.p, n0, s);
+            A0 = &A0s;
+        }
+    }
+    if (o.block_size == 0 && c->Adict.ok) o.block_size = c->Adict.bs;   // the blocking the context found
+    else if (o.block_size == 0 && c->spmv_format == 1) o.block_size = 2;
+    else if (o.block_size == 0 && c->spmv_format == 2) o.block_size = 3;
+    const int bs = o.block_size > 0 ? o.block_size : detect_bs(dev_csr_download(*A0, false, s));
+    if (n0 % bs) fail(SPK_ERR_ARG, "amg: block_size %d does not divide %d rows", bs, (int)n0);
+
+    auto d = std::make_unique<AmgDev>();
+    d->device_built = true;
+    spk_amg_info &info = d->info;
+    std::memset(&info, 0, sizeof info);
+    d->lv.reserve((size_t)o.max_levels);
+    d->lv.emplace_back();
+    d->lv[0].n = n0;
+    DevBuf<double> dinv0;   // diag(A_0)^-1 as pc_setup computes it into the context afterwards
+    dinv0.alloc((size_t)n0, 8);
+    k::extract_diag_inv(c->Ad, dinv0.p, s);
+    info.rows[0] = n0;
+    info.nnz[0] = A0->nnz;
+    for (;;) {
+        const size_t l = d->lv.size() - 1;
+        const CsrDev &A = l == 0 ? *A0 : d->lv[l].A;
+        const int32_t n = A.nrows, nn = n / bs;
+        bool last = n <= o.coarse_eq_limit || (int)d->lv.size() == o.max_levels;
+        std::vector<int32_t> gp, gi, agg;
+        int32_t na = 0;
+        if (!last) {   // the node graph: norms of the diagonal blocks, count, scan, fill; then to the host
+            DevBuf<double> dn;
+            DevBuf<int32_t> cnt, gpd, gid;
+            dn.alloc_raw((size_t)nn, 8);
+            cnt.alloc_raw((size_t)nn, 8);
+            gpd.alloc_raw((size_t)nn + 1, 8);
+            k::amgs_node_norms(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, dn.p, s);
+            k::amgs_graph(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, o.threshold, dn.p, nullptr, cnt.p, s);
+            const int32_t ne = scan_counts(cnt.p, nn, gpd.p, s);
+            gid.alloc_raw((size_t)ne, 8);
+            k::amgs_graph(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, o.threshold, dn.p, gpd.p, gid.p, s);
+            gp.resize((size_t)nn + 1);
+            gi.resize((size_t)ne);
+            SPK_HIP(hipMemcpyAsync(gp.data(), gpd.p, sizeof(int32_t) * gp.size(), hipMemcpyDeviceToHost, s));
+            if (ne) SPK_HIP(hipMemcpyAsync(gi.data(), gid.p, sizeof(int32_t) * gi.size(), hipMemcpyDeviceToHost, s));
+            SPK_HIP(hipStreamSynchronize(s));
+            na = aggregate(gp, gi, agg);
+            last = na == 0 || (int64_t)na * bs >= n;   // no coarsening left
+        }
+        if (last) break;
+        AmgLevelDev &L = d->lv[l];
+        const double *dinv = l == 0 ? dinv0.p : L.dinv.p;
+        double lmin = 0.0, lmax = 0.0;
+        dev_lanczos(c, l == 0 ? nullptr : &A, n, l == 0 ? ld : (int64_t)n, dinv, kLanczosSteps, &lmin, &lmax);
+        info.lambda_max[l] = lmax;
+        const double lo = o.esteig[0] * lmin + o.esteig[1] * lmax, hi = o.esteig[2] * lmin + o.esteig[3] * lmax;
+        if (o.smoother == SPK_AMG_CHEBYSHEV && !(lo > 0.0 && hi > lo))
+            fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", lo, hi, (int)l);
+        smoother_coeffs(L, o, lo, hi);
+        {   // tentative prolongator: 1/sqrt(|aggregate|) comes from the host, like the aggregates
+            std::vector<int32_t> size((size_t)na, 0);
+            for (int32_t a : agg) if (a >= 0) ++size[(size_t)a];
+            std::vector<double> inv((size_t)na);
+            for (int32_t a = 0; a < na; ++a) inv[(size_t)a] = 1.0 / std::sqrt((double)size[(size_t)a]);
+            DevBuf<int32_t> aggd, cnt;
+            DevBuf<double> invd;
+            aggd.upload(agg.data(), agg.size(), 8);
+            invd.upload(inv.data(), inv.size(), 8);
+            cnt.alloc_raw((size_t)n, 8);
+            CsrDev &T = L.Ptent;
+            T.nrows = n;
+            T.ncols = na * bs;
+            k::amgs_tent_count(aggd.p, n, bs, cnt.p, s);
+            T.rowptr.alloc_raw((size_t)n + 1, 8);
+            dev_csr_values(T, scan_counts(cnt.p, n, T.rowptr.p, s));
+            k::amgs_tent_fill(aggd.p, invd.p, n, bs, T.rowptr.p, T.colidx.p, T.val.p, s);
+            SPK_HIP(hipStreamSynchronize(s));
+        }
+        L.agg = std::move(agg);
+        dev_csr_copy(L.P, L.Ptent, s);
+        const double omega = 4.0 / (3.0 * lmax);
+        for (int it = 0; it < o.nsmooths; ++it) {   // P = (I - omega D^-1 A) P
+            CsrDev AP, Pn;
+            dev_spgemm(AP, A, L.P, s);
+            dev_add(Pn, 1.0, L.P, -omega, AP, dinv, s);
+            L.P = std::move(Pn);
+        }
+        dev_transpose(L.R, L.P, s);
+        CsrDev Acs;
+        {
+            CsrDev AP, Ac, AcT;
+            dev_spgemm(AP, A, L.P, s);
+            dev_spgemm(Ac, L.R, AP, s);
+            dev_transpose(AcT, Ac, s);
+            dev_add(Acs, 0.5, Ac, 0.5, AcT, nullptr, s);   // exactly symmetric (the products agree to rounding)
+        }
+        d->lv.emplace_back();   // (reserved: the levels never move)
+        AmgLevelDev &N = d->lv.back();
+        N.A = std::move(Acs);
+        N.n = N.A.nrows;
+        N.dinv.alloc((size_t)N.n, 8);
+        k::extract_diag_inv(N.A, N.dinv.p, s);
+        info.rows[l + 1] = N.n;
+        info.nnz[l + 1] = N.A.nnz;
+    }
+    const size_t L = d->lv.size();
+    const CsrDev &AC = L == 1 ? *A0 : d->lv[L - 1].A;
+    if (AC.nrows > SPK_AMG_MAX_COARSE)
+        fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
+             "most %d -- raise -pc_mg_levels or -pc_gamg_threshold 0", (int)AC.nrows, (int)L, SPK_AMG_MAX_COARSE);
+    {
+        const std::vector<double> cinv = coarse_inverse(dev_csr_download(AC, true, s));
+        d->cinv.upload(cinv.data(), cinv.size());
+    }
+    for (size_t l = 0; l < L; ++l) {   // the V-cycle's vectors, as amg_upload sizes them
+        AmgLevelDev &D = d->lv[l];
+        const size_t nv = l == 0 ? (size_t)ld : (size_t)D.n;
+        if (l > 0) D.b.alloc(nv, 8);
+        D.ya.alloc(nv, 16);
+        D.yb.alloc(nv, 16);
+        if (l == 0 && L > 1) D.t.alloc(nv, 16);
+    }
+    info.levels = (int32_t)L;
+    info.block_size = bs;
+    double tot = 0.0;
+    for (size_t l = 0; l < L; ++l) tot += (double)info.nnz[l];
+    info.operator_complexity = tot / (double)std::max<int64_t>(info.nnz[0], 1);
+    info.setup = SPK_AMG_SETUP_DEVICE;
+    SPK_HIP(hipDeviceSynchronize());
+    info.setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return d;
+}
+
+void amg_dev_level(spk_ctx *c, int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
+                   double *val)
+{
+    const AmgDev &d = *c->amg_d;
+    const int L = (int)d.lv.size();
+    hipStream_t s = c->stream;
+    if (l < 0 || l >= L) fail(SPK_ERR_ARG, "amg: level %d outside [0,%d)", l, L);
+    if (which == SPK_AMG_COARSE_INV) {
+        if (l != L - 1) fail(SPK_ERR_ARG, "amg: the coarse inverse lives on level %d", L - 1);
+        const int32_t n = d.lv[(size_t)l].n;
+        if (nrows) *nrows = n;
+        if (ncols) *ncols = n;
+        if (nnz) *nnz = (int64_t)n * n;
+        for (int32_t i = 0; rowptr && i <= n; ++i) rowptr[i] = i * n;
+        for (int64_t k = 0; colidx && k < (int64_t)n * n; ++k) colidx[k] = (int32_t)(k % n);
+        if (val) SPK_HIP(hipMemcpy(val, d.cinv.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
+        return;
+    }
+    if (which != SPK_AMG_OP && which != SPK_AMG_PROLONG && which != SPK_AMG_TENTATIVE) fail(SPK_ERR_ARG, "amg: unknown matrix %d", which);
+    if (which != SPK_AMG_OP && l == L - 1) fail(SPK_ERR_ARG, "amg: the coarsest level has no prolongator");
+    const CsrDev &M = which == SPK_AMG_OP ? (l == 0 ? c->Ad : d.lv[(size_t)l].A)
+                    : which == SPK_AMG_PROLONG ? d.lv[(size_t)l].P : d.lv[(size_t)l].Ptent;
+    if (nrows) *nrows = M.nrows;
+    if (ncols) *ncols = M.ncols;
+    if (nnz) *nnz = M.nnz;
+    if (!rowptr && !colidx && !val) return;
+    HostCsr H = dev_csr_download(M, true, s);
+    if (which == SPK_AMG_OP && l == 0) sort_rows(H);   // the context's CSR keeps the caller's order
+    if (rowptr) std::memcpy(rowptr, H.rp.data(), sizeof(int32_t) * H.rp.size());
+    if (colidx && H.nnz()) std::memcpy(colidx, H.ci.data(), sizeof(int32_t) * H.ci.size());
+    if (val && H.nnz()) std::memcpy(val, H.v.data(), sizeof(double) * H.v.size());
+}
+
+void amg_dev_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg)
+{
+    const AmgDev &d = *c->amg_d;
+    if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no aggregates", l);
+    const auto &a = d.lv[(size_t)l].agg;
+    if (nnodes) *nnodes = (int32_t)a.size();
+    if (agg) std::memcpy(agg, a.data(), sizeof(int32_t) * a.size());
 }
 
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
@@ -637,6 +1008,7 @@ void spk_default_amg_opts(spk_amg_opts *o)
     o->esteig[2] = 0.0;
     o->esteig[3] = 1.1;
     o->richardson_scale = 1.0;
+    o->setup = SPK_AMG_SETUP_HOST;
 }
 
 #define SPK_HOST_TRY try {

@@ -56,6 +56,16 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n;
+            o.p = nullptr; o.n = 0;
+        }
+        return *this;
+    }
     ~DevBuf() { release(); }
     void release()
     {
@@ -791,12 +801,38 @@ bool amg_cheb_dict2(const DictDev &A, const double *dinv, const double *b, const
                     double alpha, double beta, const int32_t *done, hipStream_t s);
 void amg_dense(const double *C, int32_t n, const double *b, double *y, const int32_t *done, hipStream_t s);     // y = C b
 void amg_out(int mode, int64_t n, const double *src, double *dst, const int32_t *done, hipStream_t s);          // = / -=
+// the multigrid set-up on the device (spk_k_amg_setup.hip); no launch takes the `done` gate
+void amgs_rows_sorted(const int32_t *rp, const int32_t *ci, int32_t n, int32_t *flag, hipStream_t s);   // *flag |= 1: a row descends
+void amgs_sort_rows(const int32_t *rp, int32_t *ci, double *v, int32_t n, hipStream_t s);
+void amgs_node_norms(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double *dn, hipStream_t s);
+// gp null: out[I] = strong neighbours of node I; else the neighbours at out[gp[I]..), ascending
+void amgs_graph(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double theta, const double *dn,
+                const int32_t *gp, int32_t *out, hipStream_t s);
+void amgs_tent_count(const int32_t *agg, int32_t nrows, int bs, int32_t *cnt, hipStream_t s);
+void amgs_tent_fill(const int32_t *agg, const double *inv, int32_t nrows, int bs, const int32_t *rp, int32_t *ci, double *v,
+                    hipStream_t s);
+// C = A B: bound[i] = slots row i may need, *total += their sum; expand into the slices at off[i]; compact behind rp
+void amgs_spgemm_bound(const CsrDev &A, const CsrDev &B, int32_t *bound, unsigned long long *total, hipStream_t s);
+void amgs_spgemm_expand(const CsrDev &A, const CsrDev &B, const int32_t *off, int32_t *sc, double *sv, int32_t *cnt, hipStream_t s);
+void amgs_compact(int32_t n, const int32_t *off, const int32_t *rp, const int32_t *sc, const double *sv, int32_t *ci, double *v,
+                  hipStream_t s);
+// C = a A + b diag(scale) B over the union pattern (scale null: 1); crp null: cnt[i] = length of row i, else the fill
+void amgs_add(double a, const CsrDev &A, double b, const CsrDev &B, const double *scale, const int32_t *crp, int32_t *cci,
+              double *cv, int32_t *cnt, hipStream_t s);
+void amgs_col_count(const int32_t *ci, int64_t nnz, int32_t *cnt, hipStream_t s);
+void amgs_transpose_fill(const CsrDev &A, int32_t *pos, int32_t *tci, double *tv, hipStream_t s);   // rows unsorted: amgs_sort_rows
+void amgs_lz_init(int64_t n, const double *dinv, double *sv, double *q, const Finish &f, hipStream_t s);
+void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, double *q, double *t, hipStream_t s);
+void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double *w, const double *q, const Finish &f, hipStream_t s);
+void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s);
 }  // namespace k
 
 // the device copy of the hierarchy (spk_amg.cpp): level 0 keeps the context's A layout and diag(A)^-1
 struct AmgLevelDev {
     int32_t n = 0;
     CsrDev A, P, R;                    // A: levels >= 1; P, R: all but the coarsest
+    CsrDev Ptent;                      // device-built hierarchies only (test hook)
+    std::vector<int32_t> agg;          // device-built hierarchies only: the aggregates the host step returned
     DevBuf<double> dinv;               // levels >= 1
     DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
@@ -804,6 +840,8 @@ struct AmgLevelDev {
 struct AmgDev {
     std::vector<AmgLevelDev> lv;
     DevBuf<double> cinv;
+    bool device_built = false;   // built by amg_build_device: there is no host hierarchy beside it
+    spk_amg_info info{};         // device-built hierarchies only
 };
 
 }  // namespace spk
@@ -939,6 +977,12 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact);
 // mode 0: y = V x, mode 1: y -= V x
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
+// the same hierarchy built on the device from c->Ad (-spk_gamg_setup device); touches nothing of the context but its
+// reduction scratch.  amg_dev_level / amg_dev_aggregates: the test hooks' downloads
+std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c);
+void amg_dev_level(spk_ctx *c, int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
+                   double *val);
+void amg_dev_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

@@ -1,0 +1,437 @@
+// spk_k_amg_setup.hip -- the multigrid set-up on the device (-spk_gamg_setup device; host sequencing: amg_build_device
+// in spk_amg.cpp).  gfx950, wave64, FP64.  Node graph, tentative prolongator, Lanczos vector passes, CSR x CSR, union
+// add and transpose.  Set-up runs before any solve: no launch here takes the solver's `done` gate.
+//
+// Every kernel is deterministic.  The sparse kernels work one row (or node) per thread in the host builder's traversal
+// order, and where the host's result depends on the order and rounding of a sum (the strong-connection test, the
+// entries of the products) the sum is written with unfused multiplies and adds in that order: the x86-64 host build has
+// no FMA, the device contracts by default.  Integer atomics allocate slots only where a sort follows; there are no
+// floating-point atomics.
+#include "spk_device.hpp"
+
+namespace spk {
+namespace k {
+
+namespace {
+inline dim3 row_grid(int64_t n) { return dim3((unsigned)std::max<int64_t>((n + kThreads - 1) / kThreads, 1)); }
+inline int lz_grid(int64_t n) { return (int)std::max<int64_t>(std::min<int64_t>((n + kVT - 1) / kVT, kVecMaxBlocks), 1); }
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// sorted columns
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_rows_sorted_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                                    int32_t n, int32_t *flag)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    bool bad = false;
+    for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k) bad = bad || ci[k - 1] > ci[k];
+    if (bad) atomicOr(flag, 1);
+}
+
+// insertion sort of every row by column, one row per thread (any row length; rows are short or nearly sorted here)
+__global__ __launch_bounds__(kThreads) void amgs_sort_rows_kernel(const int32_t *__restrict__ rp, int32_t *ci, double *v, int32_t n)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    const int32_t k0 = rp[i], k1 = rp[i + 1];
+    for (int32_t k = k0 + 1; k < k1; ++k) {
+        const int32_t c = ci[k];
+        if (ci[k - 1] <= c) continue;
+        const double x = v[k];
+        int32_t t = k;
+        for (; t > k0 && ci[t - 1] > c; --t) {
+            ci[t] = ci[t - 1];
+            v[t] = v[t - 1];
+        }
+        ci[t] = c;
+        v[t] = x;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// strong-connection graph of the bs x bs nodes (node_graph of the host builder): one node per thread, a bs-way merge
+// over the node's sorted rows -- the neighbours come out ascending, and the squares of a block are added row by row,
+// entry by entry, as the host adds them
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_node_norms_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                                   const double *__restrict__ v, int32_t nn, int bs,
+                                                                   double *__restrict__ dn)
+{
+    const int32_t I = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (I >= nn) return;
+    double acc = 0.0;
+    for (int32_t r = I * bs; r < (I + 1) * bs; ++r)
+        for (int32_t k = rp[r]; k < rp[r + 1]; ++k)
+            if (ci[k] / bs == I) acc = __dadd_rn(acc, __dmul_rn(v[k], v[k]));
+    dn[I] = __dsqrt_rn(acc);
+}
+
+// FILL = false: out[I] = number of strong neighbours; FILL = true: the neighbours at out[gp[I]..)
+template <bool FILL>
+__global__ __launch_bounds__(kThreads) void amgs_graph_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                              const double *__restrict__ v, int32_t nn, int bs, double theta,
+                                                              const double *__restrict__ dn, const int32_t *__restrict__ gp,
+                                                              int32_t *__restrict__ out)
+{
+    const int32_t I = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (I >= nn) return;
+    int32_t p[3] = {0, 0, 0}, e[3] = {0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        if (r < bs) {
+            p[r] = rp[I * bs + r];
+            e[r] = rp[I * bs + r + 1];
+        }
+    const double dI = dn[I];
+    const int32_t base = FILL ? gp[I] : 0;
+    int32_t cnt = 0;
+    for (;;) {
+        int32_t J = INT32_MAX;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            if (p[r] < e[r]) J = min(J, ci[p[r]] / bs);
+        if (J == INT32_MAX) break;
+        double acc = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            while (p[r] < e[r] && ci[p[r]] / bs == J) {
+                const double a = v[p[r]];
+                acc = __dadd_rn(acc, __dmul_rn(a, a));
+                ++p[r];
+            }
+        if (J == I) continue;
+        if (__dsqrt_rn(acc) > __dmul_rn(theta, __dsqrt_rn(__dmul_rn(dI, dn[J])))) {
+            if (FILL) out[base + cnt] = J;
+            ++cnt;
+        }
+    }
+    if (!FILL) out[I] = cnt;
+}
+
+// ---------------------------------------------------------------------------
+// tentative prolongator from the aggregates: row node * bs + c holds inv[aggregate] in column aggregate * bs + c
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_tent_count_kernel(const int32_t *__restrict__ agg, int32_t nrows, int bs,
+                                                                   int32_t *__restrict__ cnt)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i < nrows) cnt[i] = agg[i / bs] >= 0 ? 1 : 0;
+}
+__global__ __launch_bounds__(kThreads) void amgs_tent_fill_kernel(const int32_t *__restrict__ agg, const double *__restrict__ inv,
+                                                                  int32_t nrows, int bs, const int32_t *__restrict__ rp,
+                                                                  int32_t *__restrict__ ci, double *__restrict__ v)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= nrows) return;
+    const int32_t a = agg[i / bs];
+    if (a < 0) return;
+    ci[rp[i]] = a * bs + i % bs;
+    v[rp[i]] = inv[a];
+}
+
+// ---------------------------------------------------------------------------
+// C = A B, one row per thread.  bound: what a row can hold at most (its number of products, or every column of B);
+// expand: the row's slice of the scratch keeps a sorted list of (column, sum) -- a product finds its column by bisection
+// or opens it by shifting the tail -- so each entry is summed in A's stored order, then B's, from 0, as the host's dense
+// accumulator sums it; compact: the slices packed behind the scanned counts.  Correct for any row length (a long row
+// costs its thread time, nothing else).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_spgemm_bound_kernel(const int32_t *__restrict__ arp, const int32_t *__restrict__ aci,
+                                                                     const int32_t *__restrict__ brp, int32_t n, int32_t ncols_b,
+                                                                     int32_t *__restrict__ bound, unsigned long long *total)
+{
+    __shared__ unsigned long long blk;
+    if (threadIdx.x == 0) blk = 0ull;
+    __syncthreads();
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i < n) {
+        int64_t s = 0;
+        for (int32_t k = arp[i]; k < arp[i + 1]; ++k) s += brp[aci[k] + 1] - brp[aci[k]];
+        if (s > ncols_b) s = ncols_b;
+        bound[i] = (int32_t)s;
+        atomicAdd(&blk, (unsigned long long)s);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && blk) atomicAdd(total, blk);
+}
+
+__global__ __launch_bounds__(kThreads) void amgs_spgemm_expand_kernel(const int32_t *__restrict__ arp, const int32_t *__restrict__ aci,
+                                                                      const double *__restrict__ av, const int32_t *__restrict__ brp,
+                                                                      const int32_t *__restrict__ bci, const double *__restrict__ bv,
+                                                                      int32_t n, const int32_t *__restrict__ off, int32_t *sc,
+                                                                      double *sv, int32_t *__restrict__ cnt)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    int32_t *c = sc + (size_t)off[i];
+    double *w = sv + (size_t)off[i];
+    int32_t len = 0;
+    for (int32_t k = arp[i]; k < arp[i + 1]; ++k) {
+        const int32_t r = aci[k];
+        const double a = av[k];
+        for (int32_t q = brp[r]; q < brp[r + 1]; ++q) {
+            const int32_t j = bci[q];
+            const double p = __dmul_rn(a, bv[q]);
+            int32_t lo = 0, hi = len;
+            if (len > 0 && c[len - 1] < j) lo = len;   // the common case: columns arrive ascending
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (c[mid] < j) lo = mid + 1; else hi = mid;
+            }
+            if (lo < len && c[lo] == j) {
+                w[lo] = __dadd_rn(w[lo], p);
+            } else {
+                for (int32_t t = len; t > lo; --t) {
+                    c[t] = c[t - 1];
+                    w[t] = w[t - 1];
+                }
+                c[lo] = j;
+                w[lo] = __dadd_rn(0.0, p);
+                ++len;
+            }
+        }
+    }
+    cnt[i] = len;
+}
+
+__global__ __launch_bounds__(kThreads) void amgs_compact_kernel(int32_t n, const int32_t *__restrict__ off, const int32_t *__restrict__ rp,
+                                                                const int32_t *__restrict__ sc, const double *__restrict__ sv,
+                                                                int32_t *__restrict__ ci, double *__restrict__ v)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    const int32_t k0 = rp[i], len = rp[i + 1] - k0;
+    const size_t o = (size_t)off[i];
+    for (int32_t t = 0; t < len; ++t) {
+        ci[k0 + t] = sc[o + t];
+        v[k0 + t] = sv[o + t];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// C = a A + b diag(scale) B over the union of the sorted patterns (scale null: 1), one row per thread
+// FILL = false: cnt[i] = the row's length; FILL = true: the row at crp[i]
+// ---------------------------------------------------------------------------
+template <bool FILL>
+__global__ __launch_bounds__(kThreads) void amgs_add_kernel(int32_t n, double a, const int32_t *__restrict__ arp,
+                                                            const int32_t *__restrict__ aci, const double *__restrict__ av, double b,
+                                                            const int32_t *__restrict__ brp, const int32_t *__restrict__ bci,
+                                                            const double *__restrict__ bv, const double *__restrict__ scale,
+                                                            const int32_t *__restrict__ crp, int32_t *__restrict__ cci,
+                                                            double *__restrict__ cv, int32_t *__restrict__ cnt)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    int32_t p = arp[i], q = brp[i], o = FILL ? crp[i] : 0;
+    const int32_t pe = arp[i + 1], qe = brp[i + 1];
+    const double sc = scale ? scale[i] : 1.0;
+    while (p < pe || q < qe) {
+        const int32_t ca = p < pe ? aci[p] : INT32_MAX, cb = q < qe ? bci[q] : INT32_MAX;
+        if (FILL) {
+            double x;
+            if (ca == cb) x = __dadd_rn(__dmul_rn(a, av[p]), __dmul_rn(b, scale ? __dmul_rn(bv[q], sc) : bv[q]));
+            else if (ca < cb) x = __dmul_rn(a, av[p]);
+            else x = __dmul_rn(b, scale ? __dmul_rn(bv[q], sc) : bv[q]);
+            cci[o] = ca < cb ? ca : cb;
+            cv[o] = x;
+        }
+        if (ca <= cb) ++p;
+        if (cb <= ca) ++q;
+        ++o;
+    }
+    if (!FILL) cnt[i] = o;
+}
+
+// ---------------------------------------------------------------------------
+// transpose: entries per column (integer atomics), scan, slots handed out by integer atomics, then every row of the
+// result sorted by column -- the columns of a row are distinct, so the result does not depend on who got which slot
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_col_count_kernel(const int32_t *__restrict__ ci, int64_t nnz, int32_t *cnt)
+{
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (k < nnz) atomicAdd(cnt + ci[k], 1);
+}
+__global__ __launch_bounds__(kThreads) void amgs_transpose_fill_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                                       const double *__restrict__ v, int32_t n, int32_t *pos,
+                                                                       int32_t *__restrict__ tci, double *__restrict__ tv)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+        const int32_t p = atomicAdd(pos + ci[k], 1);
+        tci[p] = i;
+        tv[p] = v[k];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Lanczos on D^-1/2 A D^-1/2 (lanczos of the host builder): the vector steps as fused passes, each with one sum,
+// reduced in a fixed order by the sentinel finish (spk_device.hpp)
+// ---------------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ void lz_finish(double acc, double *red, double *partials, double *out, FinErr fe)
+{
+    const double s = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVWaves; ++j) t += red[j];
+        publish(partials + (size_t)blockIdx.x * kPartialLd, t);
+    }
+    if (!arrive_last(gridDim.x)) return;
+    final_reduce(partials, gridDim.x, kPartialLd, 1, red, fe);
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+}  // namespace
+
+// sv = sqrt|dinv|, q = the integer-hash start vector (not yet normalised), out[0] = q.q
+__global__ __launch_bounds__(kVT) void amgs_lz_init_kernel(int64_t n, const double *__restrict__ dinv, double *__restrict__ sv,
+                                                           double *__restrict__ q, double *partials, double *out, FinErr fe)
+{
+    __shared__ double red[kVT];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        sv[i] = sqrt(fabs(dinv[i]));
+        uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
+        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+        const double x = 0.5 + (double)(h & 0xffffu) / 65536.0;
+        q[i] = x;
+        acc += x * x;
+    }
+    lz_finish(acc, red, partials, out, fe);
+}
+// q = w / nb, t = sv q   (w may be q)
+__global__ __launch_bounds__(kVT) void amgs_lz_scale_kernel(int64_t n, double nb, const double *w, const double *__restrict__ sv,
+                                                            double *q, double *__restrict__ t)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = w[i] / nb;
+        q[i] = x;
+        t[i] = sv[i] * x;
+    }
+}
+// w = sv aw, out[0] = w.q
+__global__ __launch_bounds__(kVT) void amgs_lz_dot_kernel(int64_t n, const double *__restrict__ sv, const double *__restrict__ aw,
+                                                          double *__restrict__ w, const double *__restrict__ q, double *partials,
+                                                          double *out, FinErr fe)
+{
+    __shared__ double red[kVT];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = sv[i] * aw[i];
+        w[i] = x;
+        acc += x * q[i];
+    }
+    lz_finish(acc, red, partials, out, fe);
+}
+// w -= a q + be qp, out[0] = w.w
+__global__ __launch_bounds__(kVT) void amgs_lz_update_kernel(int64_t n, double a, double be, const double *__restrict__ q,
+                                                             const double *__restrict__ qp, double *__restrict__ w, double *partials,
+                                                             double *out, FinErr fe)
+{
+    __shared__ double red[kVT];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = w[i] - (a * q[i] + be * qp[i]);
+        w[i] = x;
+        acc += x * x;
+    }
+    lz_finish(acc, red, partials, out, fe);
+}
+
+// ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
+void amgs_rows_sorted(const int32_t *rp, const int32_t *ci, int32_t n, int32_t *flag, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(amgs_rows_sorted_kernel, row_grid(n), dim3(kThreads), 0, s, rp, ci, n, flag);
+}
+void amgs_sort_rows(const int32_t *rp, int32_t *ci, double *v, int32_t n, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(amgs_sort_rows_kernel, row_grid(n), dim3(kThreads), 0, s, rp, ci, v, n);
+}
+void amgs_node_norms(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double *dn, hipStream_t s)
+{
+    if (nn > 0) hipLaunchKernelGGL(amgs_node_norms_kernel, row_grid(nn), dim3(kThreads), 0, s, rp, ci, v, nn, bs, dn);
+}
+void amgs_graph(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double theta, const double *dn,
+                const int32_t *gp, int32_t *out, hipStream_t s)
+{
+    if (nn <= 0) return;
+    if (gp) hipLaunchKernelGGL(amgs_graph_kernel<true>, row_grid(nn), dim3(kThreads), 0, s, rp, ci, v, nn, bs, theta, dn, gp, out);
+    else hipLaunchKernelGGL(amgs_graph_kernel<false>, row_grid(nn), dim3(kThreads), 0, s, rp, ci, v, nn, bs, theta, dn, gp, out);
+}
+void amgs_tent_count(const int32_t *agg, int32_t nrows, int bs, int32_t *cnt, hipStream_t s)
+{
+    if (nrows > 0) hipLaunchKernelGGL(amgs_tent_count_kernel, row_grid(nrows), dim3(kThreads), 0, s, agg, nrows, bs, cnt);
+}
+void amgs_tent_fill(const int32_t *agg, const double *inv, int32_t nrows, int bs, const int32_t *rp, int32_t *ci, double *v,
+                    hipStream_t s)
+{
+    if (nrows > 0) hipLaunchKernelGGL(amgs_tent_fill_kernel, row_grid(nrows), dim3(kThreads), 0, s, agg, inv, nrows, bs, rp, ci, v);
+}
+void amgs_spgemm_bound(const CsrDev &A, const CsrDev &B, int32_t *bound, unsigned long long *total, hipStream_t s)
+{
+    if (A.nrows > 0)
+        hipLaunchKernelGGL(amgs_spgemm_bound_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, B.rowptr.p,
+                           A.nrows, B.ncols, bound, total);
+}
+void amgs_spgemm_expand(const CsrDev &A, const CsrDev &B, const int32_t *off, int32_t *sc, double *sv, int32_t *cnt, hipStream_t s)
+{
+    if (A.nrows > 0)
+        hipLaunchKernelGGL(amgs_spgemm_expand_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p,
+                           B.rowptr.p, B.colidx.p, B.val.p, A.nrows, off, sc, sv, cnt);
+}
+void amgs_compact(int32_t n, const int32_t *off, const int32_t *rp, const int32_t *sc, const double *sv, int32_t *ci, double *v,
+                  hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(amgs_compact_kernel, row_grid(n), dim3(kThreads), 0, s, n, off, rp, sc, sv, ci, v);
+}
+void amgs_add(double a, const CsrDev &A, double b, const CsrDev &B, const double *scale, const int32_t *crp, int32_t *cci,
+              double *cv, int32_t *cnt, hipStream_t s)
+{
+    const int32_t n = A.nrows;
+    if (n <= 0) return;
+    if (crp)
+        hipLaunchKernelGGL(amgs_add_kernel<true>, row_grid(n), dim3(kThreads), 0, s, n, a, A.rowptr.p, A.colidx.p, A.val.p, b,
+                           B.rowptr.p, B.colidx.p, B.val.p, scale, crp, cci, cv, cnt);
+    else
+        hipLaunchKernelGGL(amgs_add_kernel<false>, row_grid(n), dim3(kThreads), 0, s, n, a, A.rowptr.p, A.colidx.p, A.val.p, b,
+                           B.rowptr.p, B.colidx.p, B.val.p, scale, crp, cci, cv, cnt);
+}
+void amgs_col_count(const int32_t *ci, int64_t nnz, int32_t *cnt, hipStream_t s)
+{
+    if (nnz > 0) hipLaunchKernelGGL(amgs_col_count_kernel, row_grid(nnz), dim3(kThreads), 0, s, ci, nnz, cnt);
+}
+void amgs_transpose_fill(const CsrDev &A, int32_t *pos, int32_t *tci, double *tv, hipStream_t s)
+{
+    if (A.nrows > 0)
+        hipLaunchKernelGGL(amgs_transpose_fill_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p,
+                           A.nrows, pos, tci, tv);
+}
+void amgs_lz_init(int64_t n, const double *dinv, double *sv, double *q, const Finish &f, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_init_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, dinv, sv, q, f.partials, f.out,
+                       FinErr{f.err, f.fin_ticks});
+}
+void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, double *q, double *t, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_scale_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, nb, w, sv, q, t);
+}
+void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double *w, const double *q, const Finish &f, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_dot_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, sv, aw, w, q, f.partials, f.out,
+                       FinErr{f.err, f.fin_ticks});
+}
+void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_update_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, a, be, q, qp, w, f.partials, f.out,
+                       FinErr{f.err, f.fin_ticks});
+}
+
+}  // namespace k
+}  // namespace spk

@@ -115,6 +115,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, const std::string &full, const std::str
             p = end + 1;
         }
         std::memcpy(o.esteig, e, sizeof e);
+    } else if (key == "-spk_gamg_setup") {
+        if (!val) return need("host or device");
+        const std::string v(val);
+        if (v == "host") o.setup = SPK_AMG_SETUP_HOST;
+        else if (v == "device") o.setup = SPK_AMG_SETUP_DEVICE;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (host | device)");
     } else if (key == "-mg_levels_pc_type") {
         if (!val) return need("a type");
         if (std::string(val) != "jacobi") return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (jacobi)");
@@ -473,8 +479,9 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
         spk_amg_info ai;
         if (spk_get_amg_info(k->ctx, &ai) == SPK_OK) {
             const spk_amg_opts &o = k->amg[amg_active(k)];
-            std::printf("  PC gamg (smoothed aggregation, %s): %d levels, block size %d, operator complexity %.4f, set-up %.3f s\n",
-                        amg_active(k) ? "fieldsplit_0" : "K = A", ai.levels, ai.block_size, ai.operator_complexity, ai.setup_seconds);
+            std::printf("  PC gamg (smoothed aggregation, %s): %d levels, block size %d, operator complexity %.4f, set-up %.3f s on the %s\n",
+                        amg_active(k) ? "fieldsplit_0" : "K = A", ai.levels, ai.block_size, ai.operator_complexity, ai.setup_seconds,
+                        ai.setup == SPK_AMG_SETUP_DEVICE ? "device" : "host");
             std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
                         o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
                         o.nsmooths, o.coarse_eq_limit);

@@ -984,12 +984,14 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     // multigrid standing for A^-1: one rank only (every rank sees the same communicator size: all refuse together), built
     // on the host before anything of the context changes -- a refusal leaves it as it was
     std::unique_ptr<spk_amg_hier> amg;
+    std::unique_ptr<AmgDev> amg_dev;   // -spk_gamg_setup device: built on the device, equally before anything changes
     if (c->amg_on) {
         if (c->comm->size() > 1)
             fail(SPK_ERR_UNSUPPORTED, "pc_setup: the multigrid preconditioner (gamg) runs on one rank only; this communicator "
                  "has %d -- multi-rank AMG is not implemented", c->comm->size());
         if (pc_type == SPK_PC_NONE) fail(SPK_ERR_ARG, "pc_setup: the multigrid preconditioner needs pc_type jacobi or schur");
-        amg = amg_build_ctx(c);
+        if (c->amg_opts.setup == SPK_AMG_SETUP_DEVICE) amg_dev = amg_build_device(c);
+        else amg = amg_build_ctx(c);
     }
     c->amg_d.reset();
     c->amg_h.reset();
@@ -1010,6 +1012,7 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     c->dinv.alloc((size_t)c->n_local, 8);
     k::extract_diag_inv(c->Ad, c->dinv.p, s);
     if (amg) amg_upload(c, std::move(amg));
+    if (amg_dev) c->amg_d = std::move(amg_dev);
     const int m = c->m;
     if (m > 0 && c->b_general) {
         // S^ = diag(B D B^T), row by row: short rows one wave each; the long rows as below (scatter + window kernel)

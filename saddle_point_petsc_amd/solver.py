@@ -30,11 +30,14 @@ def default_opts(**kw):
 
 AMG_CHEBYSHEV, AMG_RICHARDSON = 0, 1
 AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV = 0, 1, 2, 3
+AMG_SETUP_HOST, AMG_SETUP_DEVICE = 0, 1
 _SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
+_SETUPS = {"host": AMG_SETUP_HOST, "device": AMG_SETUP_DEVICE}
 
 
 def amg_opts(**kw):
-    """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson')."""
+    """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
+    'host' / 'device')."""
     o = AmgOpts()
     lib.spk_default_amg_opts(C.byref(o))
     for k, v in kw.items():
@@ -42,6 +45,8 @@ def amg_opts(**kw):
             raise TypeError(f"unknown multigrid option {k}")
         if k == "smoother" and isinstance(v, str):
             v = _SMOOTHERS[v]
+        if k == "setup" and isinstance(v, str):
+            v = _SETUPS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         setattr(o, k, v)
@@ -58,7 +63,7 @@ def _amg_info(ai):
     L = ai.levels
     return dict(levels=L, block_size=ai.block_size, rows=list(ai.rows[:L]), nnz=list(ai.nnz[:L]),
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
-                setup_seconds=ai.setup_seconds)
+                setup_seconds=ai.setup_seconds, setup=ai.setup)
 
 
 def _amg_matrix(fn, level, which):
@@ -286,6 +291,14 @@ class Context:
         ai = AmgInfo()
         self._chk(lib.spk_get_amg_info(self.h, C.byref(ai)))
         return _amg_info(ai)
+
+    def amg_aggregates(self, level):
+        """The aggregate of every node of a level of the context's hierarchy (-1: isolated)."""
+        n = C.c_int32()
+        self._chk(lib.spk_get_amg_aggregates(self.h, level, C.byref(n), None))
+        agg = np.zeros(n.value, np.int32)
+        self._chk(lib.spk_get_amg_aggregates(self.h, level, C.byref(n), agg.ctypes.data))
+        return agg
 
     def amg_level(self, level, which=AMG_OP):
         """(rowptr, colidx, val, shape) of A_l (AMG_OP), P_l (AMG_PROLONG), the tentative P_l or the coarse inverse."""

@@ -1,0 +1,340 @@
+"""The multigrid hierarchy built on the device (-spk_gamg_setup device) against the host-only builder
+(spk_amg_build_host) with the same options: the aggregates and every pattern exactly, the entries to bounds derived from
+the length of the sums (nsmooths = 0) and from the measured sensitivity of the host builder to lambda_max (nsmooths = 1),
+the V-cycle over the device-built hierarchy against the numpy restatement, determinism, solves, the context afterwards,
+and the set-up time against the host build's.
+
+Operators: the smallest on which each part can go wrong -- 16^2 / 64^2 grids (bs 2, isolated Dirichlet nodes, 2 and 4
+levels), cube_odd (bs 3), gen1001 (bs 1, no structure), strip (off the square grid), odd33_bs1 (forced bs 1), a hub
+operator (three rows coupled to 400 others each: the long rows of the products and of the transposes), and the 64^2 grid
+with the columns of every row shuffled (the sort step)."""
+import functools
+import os
+import subprocess
+import tempfile
+import threading
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import scipy.sparse.linalg as spl
+
+import saddle_point_petsc_amd as S
+from test_amg_cpu import OFFGRID_BUILT, general_spd, hierarchy_mats, vcycle_ref
+
+pytestmark = pytest.mark.gpu
+SPK_ERR_UNSUPPORTED = -6
+
+
+def _csr(M):
+    M = M.tocsr()
+    M.sort_indices()
+    return S.CSR(M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data.copy(), M.shape[0])
+
+
+def _hub():
+    """general_spd(1001) plus three rows coupled symmetrically to 400 others each; the diagonal raised by the added
+    absolute row sums keeps strict dominance."""
+    _, A = general_spd(1001, 77)
+    rng = np.random.default_rng(78)
+    rows, cols, vals = [], [], []
+    for h in (10, 500, 990):
+        c = rng.choice(1001, 400, replace=False)
+        c = c[c != h]
+        rows += [h] * len(c); cols += list(c); vals += list(-0.01 - 0.02 * rng.random(len(c)))
+    H = sp.csr_matrix((vals, (rows, cols)), shape=A.shape)
+    H = H + H.T
+    M = (A + H + sp.diags(np.asarray(abs(H).sum(1)).ravel())).tocsr()
+    M.sum_duplicates()
+    assert (2 * M.diagonal() > np.asarray(abs(M).sum(1)).ravel()).all()
+    return _csr(M)
+
+
+def _shuffled(n):
+    """the n^2 grid with the columns of every row in a random order (the same matrix)"""
+    A = S.AssembleOperator_Laplace(n)[0]
+    rng = np.random.default_rng(5)
+    ci, v = A.colidx.copy(), A.val.copy()
+    for i in range(A.nrows):
+        k0, k1 = A.rowptr[i], A.rowptr[i + 1]
+        p = rng.permutation(k1 - k0)
+        ci[k0:k1], v[k0:k1] = ci[k0:k1][p], v[k0:k1][p]
+    assert (np.diff(ci) < 0).sum() > A.nrows       # more descents than row boundaries: rows really descend
+    return S.CSR(A.rowptr.copy(), ci, v, A.nrows)
+
+
+OPERATORS = {
+    "grid16": (lambda: S.AssembleOperator_Laplace(16)[0], {}, 2),
+    "grid64": (lambda: S.AssembleOperator_Laplace(64)[0], {}, 2),
+    "cube_odd": (lambda: OFFGRID_BUILT["cube_odd"][0]()[0], {}, 3),
+    "gen1001": (lambda: OFFGRID_BUILT["gen1001"][0]()[0], {}, 1),
+    "gen1001_thr": (lambda: OFFGRID_BUILT["gen1001"][0]()[0], dict(threshold=0.05), 1),
+    "strip": (lambda: OFFGRID_BUILT["strip"][0]()[0], {}, 2),
+    "odd33_bs1": (lambda: OFFGRID_BUILT["odd33_bs1"][0]()[0], dict(block_size=1), 1),
+    "hub": (_hub, {}, 1),
+    "shuffled64": (lambda: _shuffled(64), {}, 2),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _operator(name):
+    return OPERATORS[name][0]()
+
+
+def _ctx(A, B=None, pc=None, fact=None, amg=None):
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    if B is not None:
+        c.set_block(S.BLOCK_A10, B)
+    c.pc_setup(S.PC_JACOBI if pc is None else pc, S.SCHUR_FULL if fact is None else fact, amg=amg)
+    return c
+
+
+def _export(get, aggs, info):
+    """every matrix and the aggregates of a hierarchy as raw CSR triples"""
+    L = info["levels"]
+    out = dict(A=[get(l, S.AMG_OP) for l in range(L)], P=[get(l, S.AMG_PROLONG) for l in range(L - 1)],
+               T=[get(l, S.AMG_TENTATIVE) for l in range(L - 1)], agg=[aggs(l) for l in range(L - 1)],
+               cinv=get(L - 1, S.AMG_COARSE_INV)[2])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(name, nsmooths):
+    """(device info, device export, host info, host export) of one operator, built once for all the tests"""
+    A = _operator(name)
+    kw = dict(OPERATORS[name][1], nsmooths=nsmooths)
+    with _ctx(A, amg=dict(kw, setup="device")) as c:
+        di = c.amg_info()
+        dev = _export(c.amg_level, c.amg_aggregates, di)
+    h = S.AmgHierarchy(A, **kw)
+    hi = h.info()
+    host = _export(h.matrix, h.aggregates, hi)
+    h.close()
+    return di, dev, hi, host
+
+
+def _same_pattern(a, b, what):
+    assert a[3] == b[3], what
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), what
+
+
+def _close(a, b, tol, what):
+    scale = np.abs(b).max()
+    err = np.abs(a - b).max() / scale
+    print(f"{what}: max deviation {err:.3e} of the largest entry (bound {tol:g})")
+    assert err <= tol, what
+
+
+@pytest.mark.parametrize("nsmooths", [0, 1])
+@pytest.mark.parametrize("name", list(OPERATORS))
+def test_aggregates_and_patterns_are_the_host_builds(name, nsmooths):
+    di, dev, hi, host = _pair(name, nsmooths)
+    assert di["setup"] == S.AMG_SETUP_DEVICE and hi["setup"] == S.AMG_SETUP_HOST
+    assert di["levels"] == hi["levels"] and di["block_size"] == hi["block_size"] == OPERATORS[name][2]
+    assert di["rows"] == hi["rows"] and di["nnz"] == hi["nnz"]
+    assert di["levels"] >= 2
+    for l in range(di["levels"]):
+        _same_pattern(dev["A"][l], host["A"][l], f"A_{l}")
+    for l in range(di["levels"] - 1):
+        assert np.array_equal(dev["agg"][l], host["agg"][l]), f"aggregates of level {l}"
+        _same_pattern(dev["P"][l], host["P"][l], f"P_{l}")
+        _same_pattern(dev["T"][l], host["T"][l], f"tentative P_{l}")
+        assert dev["T"][l][2].tobytes() == host["T"][l][2].tobytes(), f"tentative P_{l} values"
+
+
+@pytest.mark.parametrize("name", list(OPERATORS))
+def test_entries_without_prolongator_smoothing(name):
+    """nsmooths = 0: no eigenvalue enters the operators.  An entry is a sum of at most ~160 products, so another order
+    moves it by at most ~160 eps sum|terms| ~ 1e-13 max|A|; six levels compound, a factor 10 on top: 1e-12."""
+    di, dev, hi, host = _pair(name, 0)
+    assert np.array_equal(dev["A"][0][2], host["A"][0][2])
+    for l in range(di["levels"]):
+        _close(dev["A"][l][2], host["A"][l][2], 1e-12, f"{name} A_{l}")
+    for l in range(di["levels"] - 1):
+        assert dev["P"][l][2].tobytes() == host["T"][l][2].tobytes()
+
+
+@pytest.mark.parametrize("name", list(OPERATORS))
+def test_entries_with_prolongator_smoothing(name):
+    """nsmooths = 1: lambda_max to 1e-12 relative (a reordered Lanczos moves it by < 2e-15); scaling lambda_max by
+    1 + 1e-12 in the host builder moves A_l, P_l by < 8e-12 and the coarse inverse by < 8.2e-12 of their largest entries:
+    1e-11 for the matrices, 1e-10 behind the Cholesky."""
+    di, dev, hi, host = _pair(name, 1)
+    for l in range(di["levels"] - 1):
+        rel = abs(di["lambda_max"][l] - hi["lambda_max"][l]) / hi["lambda_max"][l]
+        print(f"{name} lambda_max[{l}]: {di['lambda_max'][l]!r} (host {hi['lambda_max'][l]!r}), relative {rel:.3e}")
+        assert rel <= 1e-12
+    assert di["lambda_max"][-1] == 0.0
+    for l in range(di["levels"]):
+        _close(dev["A"][l][2], host["A"][l][2], 1e-11, f"{name} A_{l}")
+    for l in range(di["levels"] - 1):
+        _close(dev["P"][l][2], host["P"][l][2], 1e-11, f"{name} P_{l}")
+    _close(dev["cinv"], host["cinv"], 1e-10, f"{name} coarse inverse")
+
+
+@pytest.mark.parametrize("name,opts", [("grid64", {}), ("grid64", dict(smooth_its=3, nsmooths=0)), ("cube_odd", {})],
+                         ids=["grid64-default", "grid64-its3-nsmooths0", "cube_odd"])
+def test_one_vcycle_on_the_device_built_hierarchy_matches_numpy(name, opts):
+    A = _operator(name)
+    x = np.random.default_rng(7).standard_normal(A.nrows)
+    with _ctx(A, amg=dict(opts, setup="device")) as c:
+        info = c.amg_info()
+        y = c.pc_apply(x)
+        assert np.array_equal(y, c.pc_apply(x))
+        mats = hierarchy_mats(c.amg_level, info)
+    assert info["setup"] == S.AMG_SETUP_DEVICE
+    kw = {k: v for k, v in opts.items() if k in ("smoother", "smooth_its", "richardson_scale")}
+    ref = vcycle_ref(*mats, info["lambda_max"], x, **kw)
+    assert np.linalg.norm(y - ref) <= 1e-12 * np.linalg.norm(ref)
+
+
+def test_two_device_builds_give_the_same_bytes():
+    A = _operator("grid64")
+    x = np.random.default_rng(11).standard_normal(A.nrows)
+    got = []
+    for _ in range(2):
+        with _ctx(A, amg=dict(setup="device")) as c:
+            info = c.amg_info()
+            got.append((info, _export(c.amg_level, c.amg_aggregates, info), c.pc_apply(x)))
+    (i1, e1, y1), (i2, e2, y2) = got
+    assert i1["lambda_max"] == i2["lambda_max"] and i1["rows"] == i2["rows"]
+    for key in ("A", "P", "T"):
+        for a, b in zip(e1[key], e2[key]):
+            assert all(np.array_equal(u, v) for u, v in zip(a[:3], b[:3])), key
+    assert all(np.array_equal(a, b) for a, b in zip(e1["agg"], e2["agg"]))
+    assert np.array_equal(e1["cinv"], e2["cinv"]) and np.array_equal(y1, y2)
+
+
+@pytest.mark.parametrize("n", [64, 256])
+def test_fgmres_with_device_setup_matches_spsolve_and_the_host_route(n):
+    A, f = S.AssembleOperator_Laplace(n)
+    Asp = sp.csr_matrix((A.val, A.colidx, A.rowptr), shape=(A.nrows, A.nrows))
+    with _ctx(A, amg=dict(setup="device")) as c:
+        x, info = c.fgmres(f, rtol=1e-10, max_it=200)
+        assert c.amg_info()["setup"] == S.AMG_SETUP_DEVICE
+    with _ctx(A, amg=True) as c:
+        _, host = c.fgmres(f, rtol=1e-10, max_it=200)
+        assert c.amg_info()["setup"] == S.AMG_SETUP_HOST
+    assert info["reason"] == 2 and host["reason"] == 2
+    xd = spl.spsolve(Asp.tocsc(), f)
+    assert np.linalg.norm(x - xd) <= 1e-8 * np.linalg.norm(xd)
+    print(f"{n}^2: {info['its']} iterations with device set-up, {host['its']} with host set-up")
+    assert abs(info["its"] - host["its"]) <= 1
+
+
+def test_saddle_full_and_pipecg_with_device_setup():
+    A, f = S.AssembleOperator_Laplace(64)
+    B, g = S.AssembleOperator_Constraints(64)
+    rhs = np.concatenate([f, g])
+    with _ctx(A, B, S.PC_SCHUR, S.SCHUR_FULL, amg=dict(setup="device")) as c:
+        x, info = c.fgmres(rhs, rtol=1e-8, max_it=2000)
+        r = rhs - c.mult(x)
+    assert info["reason"] == 2 and np.linalg.norm(r) <= 1e-7 * np.linalg.norm(rhs)
+    Asp = sp.csr_matrix((A.val, A.colidx, A.rowptr), shape=(A.nrows, A.nrows))
+    with _ctx(A, amg=dict(setup="device")) as c:
+        x, info = c.pipecg(f, rtol=1e-8, max_it=500)
+    assert info["reason"] == 2
+    assert np.linalg.norm(f - Asp @ x) <= 1e-7 * np.linalg.norm(f)
+
+
+def test_runner_names_the_device():
+    exe = os.path.join(os.path.dirname(S.LIB_PATH), "saddle_point_run")
+    out = subprocess.run([exe, "-da_grid_x", "64", "-da_grid_y", "64", "-ksp_rtol", "1e-8", "-ksp_converged_reason",
+                          "-no_vtk", "-saddle", "0", "-ksp_type", "fgmres", "-pc_type", "gamg", "-spk_gamg_setup", "device",
+                          "-ksp_view"], capture_output=True, text=True, timeout=120, cwd=tempfile.mkdtemp())
+    assert out.returncode == 0, out.stdout + out.stderr
+    line = [ln for ln in out.stdout.splitlines() if "PC gamg" in ln]
+    assert "converged due to CONVERGED_RTOL" in out.stdout and line and "device" in line[0], out.stdout
+
+
+def test_jacobi_afterwards_and_the_facade():
+    A, f = S.AssembleOperator_Laplace(64)
+    with _ctx(A, amg=dict(setup="device")) as c:
+        c.fgmres(f, rtol=1e-8)
+        c.pc_setup(S.PC_JACOBI)
+        with pytest.raises(S.SpkError):
+            c.amg_info()
+        xj, ij = c.fgmres(f, rtol=1e-8, max_it=2000)
+    with _ctx(A) as c:
+        xf, fresh = c.fgmres(f, rtol=1e-8, max_it=2000)
+    assert np.array_equal(xj, xf) and np.array_equal(ij["history"], fresh["history"])
+    k = S.KSP()
+    k.setOperators(A)
+    k.setFromOptions("-ksp_type fgmres -ksp_rtol 1e-8 -pc_type gamg -spk_gamg_setup device")
+    x = k.solve(f)
+    assert k.getConvergedReason() == 2
+    k.destroy()
+    with _ctx(A, amg=dict(setup="device")) as c:
+        xc, _ = c.fgmres(f, rtol=1e-8)
+    assert np.array_equal(x, xc)
+
+
+def test_two_rank_group_refused_and_usable_with_device_setup():
+    n, P = 64, 2
+    A, f = S.AssembleOperator_Laplace(n)
+    grp = S.LocalGroup(P)
+    codes, its, errs = [None] * P, [None] * P, []
+
+    def work(r):
+        try:
+            b, e = S.partition_slab(n, n, r, P)
+            As, _ = S.AssembleOperator_Laplace(n, n, b, e)
+            c = S.Context(0)
+            c.comm_init_local(grp, r)
+            c.set_block(S.BLOCK_A00, As)
+            try:
+                c.pc_setup(S.PC_JACOBI, amg=dict(setup="device"))
+            except S.SpkError as ex:
+                codes[r] = (ex.code, str(ex))
+            c.pc_setup(S.PC_JACOBI)                        # the context stays usable
+            _, info = c.fgmres(f[b:e], rtol=1e-8, max_it=3000)
+            its[r] = info
+            c.close()
+        except Exception as ex:  # noqa: BLE001
+            errs.append(ex)
+            raise
+
+    th = [threading.Thread(target=work, args=(r,)) for r in range(P)]
+    [t.start() for t in th]
+    [t.join(timeout=300) for t in th]
+    grp.close()
+    assert not errs, errs
+    for code in codes:
+        assert code is not None and code[0] == SPK_ERR_UNSUPPORTED and "one rank" in code[1]
+    assert all(i["reason"] == 2 for i in its) and its[0]["its"] == its[1]["its"]
+
+
+def test_coarsest_level_above_the_dense_limit_is_refused_alike():
+    A = S.AssembleOperator_Laplace(128)[0]
+    with pytest.raises(S.SpkError) as host:
+        S.AmgHierarchy(A, max_levels=2)
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    with pytest.raises(S.SpkError) as dev:
+        c.pc_setup(S.PC_JACOBI, amg=dict(setup="device", max_levels=2))
+    assert dev.value.code == host.value.code == SPK_ERR_UNSUPPORTED
+    tail = lambda e: str(e)[str(e).index("the coarsest level keeps"):]   # noqa: E731
+    assert tail(dev.value) == tail(host.value)
+    c.pc_setup(S.PC_JACOBI, amg=dict(setup="device"))      # the context stays usable
+    assert c.amg_info()["levels"] >= 3
+    c.close()
+
+
+def test_device_setup_takes_less_than_half_the_host_time():
+    """512^2, one process, one warm-up build of each route first.  93 % of the host time sits in level-0 phases that the
+    device route runs as kernels; what stays on the host is under 1 %: a ratio above one half means a product or the
+    Lanczos did not really move."""
+    A = S.AssembleOperator_Laplace(512)[0]
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    t = {}
+    for rep in range(2):
+        for route in ("host", "device"):
+            c.pc_setup(S.PC_JACOBI, amg=dict(setup=route))
+            info = c.amg_info()
+            assert info["setup"] == (S.AMG_SETUP_DEVICE if route == "device" else S.AMG_SETUP_HOST)
+            t[route] = info["setup_seconds"]
+    c.close()
+    print(f"512^2 set-up: host {t['host']:.4f} s, device {t['device']:.4f} s, ratio {t['device'] / t['host']:.3f}")
+    assert t["device"] < 0.5 * t["host"]

@@ -3,8 +3,9 @@
 one process:
     python tools/gamg_bench.py [--grids 256 512 1024] [--rtol 1e-8] [--max-it 20000]
 Two systems: K = A (gamg in Jacobi's slot; FGMRES + Jacobi; MINRES + Jacobi) and the saddle system with Schur FULL
-(-fieldsplit_0_pc_type gamg; FGMRES + the plain Schur FULL; MINRES + Schur DIAG).  Per gamg row: host set-up time,
-levels, rows and operator complexity, the V-cycle's time (spk_pc_apply on device vectors, back to back) against its
+(-fieldsplit_0_pc_type gamg; FGMRES + the plain Schur FULL; MINRES + Schur DIAG).  Per gamg row: set-up time of both
+routes (host build + upload, and -spk_gamg_setup device; each after one warm-up build, in this process) with the
+iterations and time of the solve on the device-built hierarchy, levels, rows and operator complexity, the V-cycle's time (spk_pc_apply on device vectors, back to back) against its
 byte model per level, iterations and wall time to rtol.  One JSON line per row."""
 import argparse
 import json
@@ -23,6 +24,8 @@ ap.add_argument("--grids", type=int, nargs="+", default=[256, 512, 1024])
 ap.add_argument("--rtol", type=float, default=1e-8)
 ap.add_argument("--max-it", type=int, default=20000)
 ap.add_argument("--gamg-only", action="store_true", help="leave out the Jacobi / MINRES rows (a short kernel trace)")
+ap.add_argument("--setup-only", choices=["host", "device", "both"], help="only build the K = A hierarchy (after one "
+                "warm-up build of each route asked for) and print one line per grid: a kernel trace of the set-up alone")
 a = ap.parse_args()
 
 
@@ -85,8 +88,28 @@ def solve(c, rhs, solver, **kw):
     return dict(its=info["its"], reason=info["reason"], seconds=round(info["solve_seconds"], 4), true_rel_res=float(true))
 
 
+def setup_times(A, Bk, pc, fact, routes=("host", "device")):
+    """set-up seconds of each route on one context (spk_amg_info.setup_seconds), after one warm-up build of each"""
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    if Bk is not None:
+        c.set_block(S.BLOCK_A10, Bk)
+    t = {}
+    for rep in range(2):
+        for route in routes:
+            c.pc_setup(pc, fact, amg=dict(setup=route))
+            t[route] = c.amg_info()["setup_seconds"]
+    c.close()
+    return t
+
+
 for grid in a.grids:
     A, f = S.AssembleOperator_Laplace(grid)
+    if a.setup_only:
+        routes = ("host", "device") if a.setup_only == "both" else (a.setup_only,)
+        t = setup_times(A, None, S.PC_JACOBI, 0, routes)
+        print(json.dumps(dict(system="A", grid=grid, **{r + "_setup_seconds": round(v, 4) for r, v in t.items()})), flush=True)
+        continue
     B, g = S.AssembleOperator_Constraints(grid)
     for system, Bk, rhs, pc, fact, fact_mr in (("A", None, f, S.PC_JACOBI, 0, 0),
                                                ("saddle_full", B, np.concatenate([f, g]), S.PC_SCHUR, S.SCHUR_FULL,
@@ -101,9 +124,17 @@ for grid in a.grids:
         c, _ = ctx(A, Bk, pc, fact, amg=True)
         conv = solve(c, rhs, "fgmres")
         c.close()
+        routes = setup_times(A, Bk, pc, fact)
+        c, _ = ctx(A, Bk, pc, fact, amg=dict(setup="device"))
+        dconv = solve(c, rhs, "fgmres")
+        c.close()
         tot = sum(model)
         print(json.dumps(dict(system=system, grid=grid, solver="fgmres", pc="gamg", setup_seconds=round(setup_wall, 3),
-                              host_setup_seconds=round(info["setup_seconds"], 3), levels=info["levels"],
+                              host_setup_seconds=round(info["setup_seconds"], 3),
+                              host_setup_warm_seconds=round(routes["host"], 4),
+                              device_setup_warm_seconds=round(routes["device"], 4),
+                              device_setup_its=dconv["its"], device_setup_solve_seconds=dconv["seconds"],
+                              levels=info["levels"],
                               rows=info["rows"], operator_complexity=round(info["operator_complexity"], 4),
                               lambda_max=[round(x, 4) for x in info["lambda_max"]], pc_apply_us=round(vc_ms * 1e3, 1),
                               vcycle_us=round(vc_only_ms * 1e3, 1), vcycle_model_bytes=tot, vcycle_model_per_level=model,
