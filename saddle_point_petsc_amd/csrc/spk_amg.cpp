@@ -1,6 +1,7 @@
 // spk_amg.cpp -- smoothed-aggregation algebraic multigrid (-pc_type gamg): the hierarchy, built at KSPSetUp from the
-// A00 CSR on the host and uploaded (the default) or on the device (-spk_gamg_setup device: amg_build_device, kernels:
-// spk_k_amg_setup.hip), and the V-cycle's launch sequence (kernels: spk_k_amg.hip).
+// A00 block by one loop (build_levels) over two routes -- HostRoute: on the host, then uploaded (the default); DevRoute:
+// on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the V-cycle's launch sequence (kernels:
+// spk_k_amg.hip).
 //
 // Every step is deterministic (fixed traversal orders, no hashing of pointers, a fixed Lanczos start vector): two
 // builds of the same matrix give the same bytes, and so do two V-cycles.  DESIGN.md "Algebraic multigrid" has the
@@ -185,9 +186,11 @@ void ritz_extremes(const std::vector<double> &al, const std::vector<double> &be,
     *lmin = hi;
 }
 
-// extreme Ritz values of D^-1 A after `steps` Lanczos steps on the similar D^-1/2 A D^-1/2, from a fixed start vector.
+constexpr int kLanczosSteps = 30;
+
+// extreme Ritz values of D^-1 A after kLanczosSteps Lanczos steps on the similar D^-1/2 A D^-1/2, from a fixed start vector.
 // Ritz values lie inside the spectrum: both estimates approach from within (lmax from below).
-void lanczos(const HostCsr &A, const std::vector<double> &dinv, int steps, double *lmin, double *lmax)
+void lanczos(const HostCsr &A, const std::vector<double> &dinv, double *lmin, double *lmax)
 {
     const int32_t n = A.nrows;
     std::vector<double> s((size_t)n), q((size_t)n), qp((size_t)n, 0.0), w((size_t)n), t((size_t)n);
@@ -202,7 +205,7 @@ void lanczos(const HostCsr &A, const std::vector<double> &dinv, int steps, doubl
     nq = std::sqrt(nq);
     for (double &x : q) x /= nq;
     std::vector<double> al, be{0.0};
-    const int k = (int)std::min<int64_t>(steps, n);
+    const int k = (int)std::min<int64_t>(kLanczosSteps, n);
     for (int j = 0; j < k; ++j) {
         for (int32_t i = 0; i < n; ++i) t[(size_t)i] = s[(size_t)i] * q[(size_t)i];
         double a = 0.0;
@@ -361,7 +364,121 @@ std::vector<double> coarse_inverse(const HostCsr &A)
     return X;
 }
 
-constexpr int kLanczosSteps = 30;
+using Clock = std::chrono::steady_clock;
+double seconds_since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+// The set-up, stated once: the level loop with every rule of the algorithm and the whole of `info`.  A route supplies
+// what differs between the host and the device -- where the matrices live and what computes them:
+//   rows(l), nnz(l) of A_l;  graph(l, bs, theta, gp, gi): the strong-connection graph of its nodes, in host vectors
+//   ritz(l, &lmin, &lmax): the extreme Ritz values of D^-1 A_l (a level has its D^-1 from when it is appended)
+//   set_interval(l, lo, hi): keeps what the smoother of level l needs
+//   coarsen(l, bs, agg, na, omega, nsmooths): keeps agg; tentative P, nsmooths times P <- (I - omega D^-1 A) P, R = P^T;
+//                                             appends level l+1 with A = (RAP + (RAP)^T) / 2 and its D^-1
+//   coarsest(): the last operator as a HostCsr;  set_coarse_inverse(x): keeps its dense inverse
+// t0: when the caller began (its own preparation counts into info.setup_seconds).
+template <class Route>
+void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::time_point t0, spk_amg_info &info)
+{
+    if (r.rows(0) % bs) fail(SPK_ERR_ARG, "amg: block_size %d does not divide %d rows", bs, (int)r.rows(0));
+    std::memset(&info, 0, sizeof info);
+    double tot = 0.0;
+    int l = 0;
+    for (;; ++l) {
+        const int32_t n = r.rows(l);
+        info.rows[l] = n;
+        info.nnz[l] = r.nnz(l);
+        tot += (double)info.nnz[l];
+        if (n <= o.coarse_eq_limit || l + 1 == o.max_levels) break;
+        std::vector<int32_t> gp, gi, agg;
+        r.graph(l, bs, o.threshold, gp, gi);
+        const int32_t na = aggregate(gp, gi, agg);
+        if (na == 0 || (int64_t)na * bs >= n) break;   // no coarsening left
+        double lmin = 0.0, lmax = 0.0;
+        r.ritz(l, &lmin, &lmax);
+        info.lambda_max[l] = lmax;
+        const double lo = o.esteig[0] * lmin + o.esteig[1] * lmax, hi = o.esteig[2] * lmin + o.esteig[3] * lmax;
+        if (o.smoother == SPK_AMG_CHEBYSHEV && !(lo > 0.0 && hi > lo))
+            fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", lo, hi, l);
+        r.set_interval(l, lo, hi);
+        r.coarsen(l, bs, std::move(agg), na, 4.0 / (3.0 * lmax), o.nsmooths);
+    }
+    info.levels = l + 1;
+    if (r.rows(l) > SPK_AMG_MAX_COARSE)
+        fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
+             "most %d -- raise -pc_mg_levels or -pc_gamg_threshold 0", (int)r.rows(l), info.levels, SPK_AMG_MAX_COARSE);
+    r.set_coarse_inverse(coarse_inverse(r.coarsest()));
+    info.block_size = bs;
+    info.operator_complexity = tot / (double)std::max<int64_t>(info.nnz[0], 1);
+    info.setup = setup;
+    info.setup_seconds = seconds_since(t0);
+}
+
+// the host route: every matrix a HostCsr of h.lv (level 0 and its D^-1 are there before the loop runs)
+struct HostRoute {
+    AmgHier &h;
+    AmgLevel &lv(int l) const { return h.lv[(size_t)l]; }
+    int32_t rows(int l) const { return lv(l).A.nrows; }
+    int64_t nnz(int l) const { return lv(l).A.nnz(); }
+    void graph(int l, int bs, double theta, std::vector<int32_t> &gp, std::vector<int32_t> &gi) const { node_graph(lv(l).A, bs, theta, gp, gi); }
+    void ritz(int l, double *lmin, double *lmax) const { lanczos(lv(l).A, lv(l).dinv, lmin, lmax); }
+    void set_interval(int l, double lo, double hi) const { lv(l).lo = lo, lv(l).hi = hi; }
+    void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths) const
+    {
+        AmgLevel &L = lv(l);
+        L.agg = std::move(agg);
+        L.Ptent = tentative(L.agg, na, bs);
+        L.P = L.Ptent;
+        for (int s = 0; s < nsmooths; ++s) {   // P = (I - omega D^-1 A) P
+            HostCsr AP = spgemm(L.A, L.P);
+            for (int32_t i = 0; i < AP.nrows; ++i)
+                for (int32_t k = AP.rp[(size_t)i]; k < AP.rp[(size_t)i + 1]; ++k) AP.v[(size_t)k] *= L.dinv[(size_t)i];
+            L.P = add(1.0, L.P, -omega, AP);
+        }
+        L.R = transpose(L.P);
+        HostCsr Ac = spgemm(L.R, spgemm(L.A, L.P));
+        h.lv.emplace_back();   // (L dangles from here)
+        h.lv.back().A = add(0.5, Ac, 0.5, transpose(Ac));   // exactly symmetric (the products agree to rounding)
+        h.lv.back().dinv = diag_inv(h.lv.back().A);
+    }
+    const HostCsr &coarsest() const { return h.lv.back().A; }
+    void set_coarse_inverse(std::vector<double> cinv) const { h.cinv = std::move(cinv); }
+};
+
+// the test hooks' copy-out, shared by the host hierarchy and the download of a device-built one
+void csr_out(const HostCsr &M, const CsrOut &o)
+{
+    o.sizes(M.nrows, M.ncols, M.nnz());
+    if (o.rowptr) std::memcpy(o.rowptr, M.rp.data(), sizeof(int32_t) * M.rp.size());
+    if (o.colidx && M.nnz()) std::memcpy(o.colidx, M.ci.data(), sizeof(int32_t) * M.ci.size());
+    if (o.val && M.nnz()) std::memcpy(o.val, M.v.data(), sizeof(double) * M.v.size());
+}
+
+// SPK_AMG_COARSE_INV: the dense n x n inverse as full CSR rows
+void coarse_inv_out(int32_t n, const double *cinv, const CsrOut &o)
+{
+    o.sizes(n, n, (int64_t)n * n);
+    for (int32_t i = 0; o.rowptr && i <= n; ++i) o.rowptr[i] = i * n;
+    for (int64_t k = 0; o.colidx && k < (int64_t)n * n; ++k) o.colidx[k] = (int32_t)(k % n);
+    if (o.val) std::memcpy(o.val, cinv, sizeof(double) * (size_t)n * n);
+}
+
+// what a query for matrix `which` of level l refuses on a hierarchy of L levels
+void check_level_query(int L, int l, int which)
+{
+    if (l < 0 || l >= L) fail(SPK_ERR_ARG, "amg: level %d outside [0,%d)", l, L);
+    if (which == SPK_AMG_COARSE_INV && l != L - 1) fail(SPK_ERR_ARG, "amg: the coarse inverse lives on level %d", L - 1);
+    if (which < SPK_AMG_OP || which > SPK_AMG_COARSE_INV) fail(SPK_ERR_ARG, "amg: unknown matrix %d", which);
+    if ((which == SPK_AMG_PROLONG || which == SPK_AMG_TENTATIVE) && l == L - 1) fail(SPK_ERR_ARG, "amg: the coarsest level has no prolongator");
+}
+
+template <class Levels>   // of AmgLevel or AmgLevelDev: both keep `agg`
+void aggregates_out(const Levels &lv, int l, int32_t *nnodes, int32_t *agg)
+{
+    if (l < 0 || l + 1 >= (int)lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no aggregates", l);
+    const std::vector<int32_t> &a = lv[(size_t)l].agg;
+    if (nnodes) *nnodes = (int32_t)a.size();
+    if (agg) std::memcpy(agg, a.data(), sizeof(int32_t) * a.size());
+}
 
 }  // namespace
 
@@ -384,101 +501,25 @@ void amg_check_opts(const spk_amg_opts &o)
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     amg_check_opts(o);
     if (A.nrows != A.ncols || A.nrows <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
     sort_rows(A);
     h = AmgHier{};
     h.o = o;
-    h.bs = o.block_size > 0 ? o.block_size : detect_bs(A);
-    if (A.nrows % h.bs) fail(SPK_ERR_ARG, "amg: block_size %d does not divide %d rows", h.bs, (int)A.nrows);
     h.lv.emplace_back();
-    h.lv.back().A = std::move(A);
-    for (;;) {
-        const size_t l = h.lv.size() - 1;
-        bool last = h.lv[l].A.nrows <= o.coarse_eq_limit || (int)h.lv.size() == o.max_levels;
-        std::vector<int32_t> gp, gi, agg;
-        int32_t na = 0;
-        if (!last) {
-            node_graph(h.lv[l].A, h.bs, o.threshold, gp, gi);
-            na = aggregate(gp, gi, agg);
-            last = na == 0 || (int64_t)na * h.bs >= h.lv[l].A.nrows;   // no coarsening left
-        }
-        if (last) break;
-        AmgLevel &L = h.lv[l];
-        L.agg = std::move(agg);
-        L.dinv = diag_inv(L.A);
-        lanczos(L.A, L.dinv, kLanczosSteps, &L.lmin, &L.lmax);
-        L.lo = o.esteig[0] * L.lmin + o.esteig[1] * L.lmax;
-        L.hi = o.esteig[2] * L.lmin + o.esteig[3] * L.lmax;
-        if (o.smoother == SPK_AMG_CHEBYSHEV && !(L.lo > 0.0 && L.hi > L.lo))
-            fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", L.lo, L.hi, (int)l);
-        L.Ptent = tentative(L.agg, na, h.bs);
-        L.P = L.Ptent;
-        const double omega = 4.0 / (3.0 * L.lmax);
-        for (int s = 0; s < o.nsmooths; ++s) {   // P = (I - omega D^-1 A) P
-            HostCsr AP = spgemm(L.A, L.P);
-            for (int32_t i = 0; i < AP.nrows; ++i)
-                for (int32_t k = AP.rp[(size_t)i]; k < AP.rp[(size_t)i + 1]; ++k) AP.v[(size_t)k] *= L.dinv[(size_t)i];
-            L.P = add(1.0, L.P, -omega, AP);
-        }
-        L.R = transpose(L.P);
-        HostCsr Ac = spgemm(L.R, spgemm(L.A, L.P));
-        Ac = add(0.5, Ac, 0.5, transpose(Ac));   // exactly symmetric (the products agree to rounding)
-        h.lv.emplace_back();
-        h.lv.back().A = std::move(Ac);
-    }
-    AmgLevel &C = h.lv.back();
-    if (C.A.nrows > SPK_AMG_MAX_COARSE)
-        fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
-             "most %d -- raise -pc_mg_levels or -pc_gamg_threshold 0", (int)C.A.nrows, (int)h.lv.size(), SPK_AMG_MAX_COARSE);
-    C.dinv = diag_inv(C.A);
-    h.cinv = coarse_inverse(C.A);
-    h.setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    h.lv[0].A = std::move(A);
+    h.lv[0].dinv = diag_inv(h.lv[0].A);
+    HostRoute r{h};
+    build_levels(r, o.block_size > 0 ? o.block_size : detect_bs(h.lv[0].A), o, SPK_AMG_SETUP_HOST, t0, h.info);
 }
 
-void AmgHier::info(spk_amg_info *out) const
+void AmgHier::level(int l, int which, const CsrOut &out) const
 {
-    std::memset(out, 0, sizeof *out);
-    out->levels = (int32_t)lv.size();
-    out->block_size = bs;
-    double tot = 0.0;
-    for (size_t l = 0; l < lv.size(); ++l) {
-        out->rows[l] = lv[l].A.nrows;
-        out->nnz[l] = lv[l].A.nnz();
-        out->lambda_max[l] = lv[l].lmax;
-        tot += (double)lv[l].A.nnz();
-    }
-    out->operator_complexity = tot / (double)std::max<int64_t>(lv[0].A.nnz(), 1);
-    out->setup_seconds = setup_seconds;
-}
-
-void AmgHier::level(int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
-                    double *val) const
-{
-    const int L = (int)lv.size();
-    if (l < 0 || l >= L) fail(SPK_ERR_ARG, "amg: level %d outside [0,%d)", l, L);
-    if (which == SPK_AMG_COARSE_INV) {
-        if (l != L - 1) fail(SPK_ERR_ARG, "amg: the coarse inverse lives on level %d", L - 1);
-        const int32_t n = lv[(size_t)l].A.nrows;
-        if (nrows) *nrows = n;
-        if (ncols) *ncols = n;
-        if (nnz) *nnz = (int64_t)n * n;
-        for (int32_t i = 0; rowptr && i <= n; ++i) rowptr[i] = i * n;
-        for (int64_t k = 0; colidx && k < (int64_t)n * n; ++k) colidx[k] = (int32_t)(k % n);
-        if (val) std::memcpy(val, cinv.data(), sizeof(double) * cinv.size());
-        return;
-    }
-    const HostCsr *M = which == SPK_AMG_OP ? &lv[(size_t)l].A : which == SPK_AMG_PROLONG ? &lv[(size_t)l].P
-                     : which == SPK_AMG_TENTATIVE ? &lv[(size_t)l].Ptent : nullptr;
-    if (!M) fail(SPK_ERR_ARG, "amg: unknown matrix %d", which);
-    if (which != SPK_AMG_OP && l == L - 1) fail(SPK_ERR_ARG, "amg: the coarsest level has no prolongator");
-    if (nrows) *nrows = M->nrows;
-    if (ncols) *ncols = M->ncols;
-    if (nnz) *nnz = M->nnz();
-    if (rowptr) std::memcpy(rowptr, M->rp.data(), sizeof(int32_t) * M->rp.size());
-    if (colidx && M->nnz()) std::memcpy(colidx, M->ci.data(), sizeof(int32_t) * M->ci.size());
-    if (val && M->nnz()) std::memcpy(val, M->v.data(), sizeof(double) * M->v.size());
+    check_level_query((int)lv.size(), l, which);
+    const AmgLevel &V = lv[(size_t)l];
+    if (which == SPK_AMG_COARSE_INV) coarse_inv_out(V.A.nrows, cinv.data(), out);
+    else csr_out(which == SPK_AMG_OP ? V.A : which == SPK_AMG_PROLONG ? V.P : V.Ptent, out);
 }
 
 }  // namespace spk
@@ -488,25 +529,38 @@ void AmgHier::level(int l, int which, int32_t *nrows, int32_t *ncols, int64_t *n
 // ---------------------------------------------------------------------------
 namespace spk {
 
+// the node size the options ask for, else the blocking the context found for its A layout (0: detect from the pattern)
+static int ctx_block_size(const spk_ctx *c, const spk_amg_opts &o)
+{
+    if (o.block_size > 0) return o.block_size;
+    if (c->Adict.ok) return c->Adict.bs;
+    return c->spmv_format == 1 ? 2 : c->spmv_format == 2 ? 3 : 0;
+}
+
+static HostCsr dev_csr_download(const CsrDev &A, bool values, hipStream_t s)
+{
+    HostCsr H;
+    H.nrows = A.nrows;
+    H.ncols = A.ncols;
+    H.rp.resize((size_t)A.nrows + 1);
+    SPK_HIP(hipMemcpyAsync(H.rp.data(), A.rowptr.p, sizeof(int32_t) * H.rp.size(), hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    H.ci.resize((size_t)H.rp[(size_t)A.nrows]);
+    H.v.resize(H.ci.size());
+    if (!H.ci.empty()) {
+        SPK_HIP(hipMemcpyAsync(H.ci.data(), A.colidx.p, sizeof(int32_t) * H.ci.size(), hipMemcpyDeviceToHost, s));
+        if (values) SPK_HIP(hipMemcpyAsync(H.v.data(), A.val.p, sizeof(double) * H.v.size(), hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+    }
+    return H;
+}
+
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c)
 {
-    const int32_t n = c->n_local;
-    HostCsr A;
-    A.nrows = A.ncols = n;
-    A.rp.resize((size_t)n + 1);
-    SPK_HIP(hipMemcpy(A.rp.data(), c->Ad.rowptr.p, sizeof(int32_t) * A.rp.size(), hipMemcpyDeviceToHost));
-    A.ci.resize((size_t)A.rp[(size_t)n]);
-    A.v.resize(A.ci.size());
-    if (!A.ci.empty()) {
-        SPK_HIP(hipMemcpy(A.ci.data(), c->Ad.colidx.p, sizeof(int32_t) * A.ci.size(), hipMemcpyDeviceToHost));
-        SPK_HIP(hipMemcpy(A.v.data(), c->Ad.val.p, sizeof(double) * A.v.size(), hipMemcpyDeviceToHost));
-    }
     spk_amg_opts o = c->amg_opts;
-    if (o.block_size == 0 && c->Adict.ok) o.block_size = c->Adict.bs;   // the blocking the context found
-    else if (o.block_size == 0 && c->spmv_format == 1) o.block_size = 2;
-    else if (o.block_size == 0 && c->spmv_format == 2) o.block_size = 3;
+    o.block_size = ctx_block_size(c, o);
     auto h = std::make_unique<spk_amg_hier>();
-    amg_build(h->h, std::move(A), o);
+    amg_build(h->h, dev_csr_download(c->Ad, true, c->stream), o);
     return h;
 }
 
@@ -520,7 +574,7 @@ static void upload_host_csr(CsrDev &D, const HostCsr &H)
     D.val.upload(H.v.data(), H.v.size(), 4);
 }
 
-// the smoothing steps of a level from its Chebyshev interval [lo, hi]
+// the smoothing steps of a level from its interval [lo, hi]
 static void smoother_coeffs(AmgLevelDev &D, const spk_amg_opts &o, double lo, double hi)
 {
     const int nu = o.smooth_its;
@@ -539,9 +593,25 @@ static void smoother_coeffs(AmgLevelDev &D, const spk_amg_opts &o, double lo, do
     }
 }
 
+// the V-cycle's vectors; level 0 takes the context's padded length, as the layouts' products want them.  Both callers
+// pass c->ld, the device build even before pc_setup's own ensure_vectors: every set_block ends in ensure_vectors and
+// nothing else changes n_local or m, so c->ld is current whenever the context holds an operator (pc_setup asks for one).
+static void alloc_cycle_vectors(AmgDev &d, int64_t ld)
+{
+    const size_t L = d.lv.size();
+    for (size_t l = 0; l < L; ++l) {
+        AmgLevelDev &D = d.lv[l];
+        const size_t nv = l == 0 ? (size_t)ld : (size_t)D.n;
+        if (l > 0) D.b.alloc(nv, 8);
+        D.ya.alloc(nv, 16);
+        D.yb.alloc(nv, 16);
+        if (l == 0 && L > 1) D.t.alloc(nv, 16);
+    }
+}
+
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     const AmgHier &h = hp->h;
     auto d = std::make_unique<AmgDev>();
     const size_t L = h.lv.size();
@@ -550,32 +620,29 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
         const AmgLevel &H = h.lv[l];
         AmgLevelDev &D = d->lv[l];
         D.n = H.A.nrows;
-        const size_t nv = l == 0 ? (size_t)c->ld : (size_t)D.n;   // the fine level's vectors as the layouts' products want them
         if (l > 0) {
             upload_host_csr(D.A, H.A);
             D.dinv.upload(H.dinv.data(), H.dinv.size(), 8);
-            D.b.alloc(nv, 8);
         }
-        D.ya.alloc(nv, 16);
-        D.yb.alloc(nv, 16);
         if (l + 1 == L) break;
-        if (l == 0) D.t.alloc(nv, 16);
         upload_host_csr(D.P, H.P);
         upload_host_csr(D.R, H.R);
         smoother_coeffs(D, h.o, H.lo, H.hi);
     }
     d->cinv.upload(h.cinv.data(), h.cinv.size());
+    alloc_cycle_vectors(*d, c->ld);
     SPK_HIP(hipDeviceSynchronize());
-    hp->h.setup_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    d->info = h.info;
+    d->info.setup_seconds += seconds_since(t0);
     c->amg_d = std::move(d);
     c->amg_h = std::move(hp);
 }
 
 // ---------------------------------------------------------------------------
-// the same hierarchy built on the device (-spk_gamg_setup device; kernels: spk_k_amg_setup.hip).  Per level: node graph
-// -> host (the greedy aggregation is sequential by definition and runs unchanged, so the aggregates and every pattern
-// are the host build's) -> tentative prolongator, Lanczos, the products and transposes as kernels.  Only the graph,
-// the aggregates, the Lanczos scalars and the coarsest operator cross the bus.
+// the device route (-spk_gamg_setup device; kernels: spk_k_amg_setup.hip).  Per level: node graph -> host (the greedy
+// aggregation is sequential by definition and runs unchanged, so the aggregates and every pattern are the host
+// route's) -> tentative prolongator, Lanczos, the products and transposes as kernels.  Only the graph, the aggregates,
+// the Lanczos scalars and the coarsest operator cross the bus.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -672,27 +739,9 @@ void dev_transpose(CsrDev &T, const CsrDev &A, hipStream_t s)
     SPK_HIP(hipStreamSynchronize(s));
 }
 
-HostCsr dev_csr_download(const CsrDev &A, bool values, hipStream_t s)
-{
-    HostCsr H;
-    H.nrows = A.nrows;
-    H.ncols = A.ncols;
-    H.rp.resize((size_t)A.nrows + 1);
-    SPK_HIP(hipMemcpyAsync(H.rp.data(), A.rowptr.p, sizeof(int32_t) * H.rp.size(), hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    H.ci.resize((size_t)H.rp[(size_t)A.nrows]);
-    H.v.resize(H.ci.size());
-    if (!H.ci.empty()) {
-        SPK_HIP(hipMemcpyAsync(H.ci.data(), A.colidx.p, sizeof(int32_t) * H.ci.size(), hipMemcpyDeviceToHost, s));
-        if (values) SPK_HIP(hipMemcpyAsync(H.v.data(), A.val.p, sizeof(double) * H.v.size(), hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipStreamSynchronize(s));
-    }
-    return H;
-}
-
 // the 30 Lanczos steps of `lanczos` with the level's own product (level 0: the context's layout, else the CSR kernel);
 // the two sums of a step come back to the host, which keeps the tridiagonal and the break rule
-void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, int steps, double *lmin, double *lmax)
+void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, double *lmin, double *lmax)
 {
     hipStream_t s = c->stream;
     DevBuf<double> sv, q, qp, w, t, aw, res;
@@ -709,7 +758,7 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
     const double nq = std::sqrt(sum());
     k::amgs_lz_scale(n, nq, q.p, sv.p, q.p, t.p, s);
     std::vector<double> al, be{0.0};
-    const int kk = (int)std::min<int64_t>(steps, n);
+    const int kk = (int)std::min<int64_t>(kLanczosSteps, n);
     double *qc = q.p, *qo = qp.p;
     for (int j = 0; j < kk; ++j) {
         if (A) k::amg_spmv(*A, t.p, aw.p, nullptr, s);
@@ -728,89 +777,64 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
     ritz_extremes(al, be, lmin, lmax);
 }
 
-}  // namespace
-
-std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
+// the context's CSR as it is when every row ascends, else a sorted copy in `copy`
+const CsrDev &sorted_rows(spk_ctx *c, CsrDev &copy)
 {
-    const auto t0 = std::chrono::steady_clock::now();
-    spk_amg_opts o = c->amg_opts;
-    amg_check_opts(o);
     hipStream_t s = c->stream;
-    c->ensure_scratch();
-    const int32_t n0 = c->n_local;
-    if (n0 <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
-    const int64_t ld = ((int64_t)c->n_local + c->m + 255) / 256 * 256;   // as ensure_vectors pads the context's vectors
+    DevBuf<int32_t> flag;
+    flag.alloc(1);
+    k::amgs_rows_sorted(c->Ad.rowptr.p, c->Ad.colidx.p, c->n_local, flag.p, s);
+    int32_t unsorted = 0;
+    SPK_HIP(hipMemcpyAsync(&unsorted, flag.p, sizeof unsorted, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    if (!unsorted) return c->Ad;
+    dev_csr_copy(copy, c->Ad, s);
+    k::amgs_sort_rows(copy.rowptr.p, copy.colidx.p, copy.val.p, c->n_local, s);
+    return copy;
+}
 
-    // sorted columns: the context's CSR as it is when every row ascends, else a sorted copy
-    CsrDev A0s;
-    const CsrDev *A0 = &c->Ad;
+// the device route: every matrix a CsrDev of d.lv.  Level 0 is special, throughout and only here: its operator is A0 (the
+// context's CSR or the sorted copy), its D^-1 is dinv0 (pc_setup computes the context's afterwards), its Lanczos product
+// the context's layout over vectors of the padded length; with one level it is the coarsest too.
+struct DevRoute {
+    spk_ctx *c;
+    AmgDev &d;
+    const spk_amg_opts &o;
+    const CsrDev &A0;
+    const double *dinv0;
+    hipStream_t s;
+    const CsrDev &A(int l) const { return l == 0 ? A0 : d.lv[(size_t)l].A; }
+    const double *dinv(int l) const { return l == 0 ? dinv0 : d.lv[(size_t)l].dinv.p; }
+    int32_t rows(int l) const { return A(l).nrows; }
+    int64_t nnz(int l) const { return A(l).nnz; }
+
+    // norms of the diagonal blocks, count, scan, fill; then to the host
+    void graph(int l, int bs, double theta, std::vector<int32_t> &gp, std::vector<int32_t> &gi) const
     {
-        DevBuf<int32_t> flag;
-        flag.alloc(1);
-        k::amgs_rows_sorted(c->Ad.rowptr.p, c->Ad.colidx.p, n0, flag.p, s);
-        int32_t unsorted = 0;
-        SPK_HIP(hipMemcpyAsync(&unsorted, flag.p, sizeof unsorted, hipMemcpyDeviceToHost, s));
+        const CsrDev &M = A(l);
+        const int32_t nn = M.nrows / bs;
+        DevBuf<double> dn;
+        DevBuf<int32_t> cnt, gpd, gid;
+        dn.alloc_raw((size_t)nn, 8);
+        cnt.alloc_raw((size_t)nn, 8);
+        gpd.alloc_raw((size_t)nn + 1, 8);
+        k::amgs_node_norms(M.rowptr.p, M.colidx.p, M.val.p, nn, bs, dn.p, s);
+        k::amgs_graph(M.rowptr.p, M.colidx.p, M.val.p, nn, bs, theta, dn.p, nullptr, cnt.p, s);
+        const int32_t ne = scan_counts(cnt.p, nn, gpd.p, s);
+        gid.alloc_raw((size_t)ne, 8);
+        k::amgs_graph(M.rowptr.p, M.colidx.p, M.val.p, nn, bs, theta, dn.p, gpd.p, gid.p, s);
+        gp.resize((size_t)nn + 1);
+        gi.resize((size_t)ne);
+        SPK_HIP(hipMemcpyAsync(gp.data(), gpd.p, sizeof(int32_t) * gp.size(), hipMemcpyDeviceToHost, s));
+        if (ne) SPK_HIP(hipMemcpyAsync(gi.data(), gid.p, sizeof(int32_t) * gi.size(), hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
-        if (unsorted) {
-            dev_csr_copy(A0s, c->Ad, s);
-            k::amgs_sort_rows(A0s.rowptr.p, A0s.colidx.p, A0s.val.p, n0, s);
-            A0 = &A0s;
-        }
     }
-    if (o.block_size == 0 && c->Adict.ok) o.block_size = c->Adict.bs;   // the blocking the context found
-    else if (o.block_size == 0 && c->spmv_format == 1) o.block_size = 2;
-    else if (o.block_size == 0 && c->spmv_format == 2) o.block_size = 3;
-    const int bs = o.block_size > 0 ? o.block_size : detect_bs(dev_csr_download(*A0, false, s));
-    if (n0 % bs) fail(SPK_ERR_ARG, "amg: block_size %d does not divide %d rows", bs, (int)n0);
-
-    auto d = std::make_unique<AmgDev>();
-    d->device_built = true;
-    spk_amg_info &info = d->info;
-    std::memset(&info, 0, sizeof info);
-    d->lv.reserve((size_t)o.max_levels);
-    d->lv.emplace_back();
-    d->lv[0].n = n0;
-    DevBuf<double> dinv0;   // diag(A_0)^-1 as pc_setup computes it into the context afterwards
-    dinv0.alloc((size_t)n0, 8);
-    k::extract_diag_inv(c->Ad, dinv0.p, s);
-    info.rows[0] = n0;
-    info.nnz[0] = A0->nnz;
-    for (;;) {
-        const size_t l = d->lv.size() - 1;
-        const CsrDev &A = l == 0 ? *A0 : d->lv[l].A;
-        const int32_t n = A.nrows, nn = n / bs;
-        bool last = n <= o.coarse_eq_limit || (int)d->lv.size() == o.max_levels;
-        std::vector<int32_t> gp, gi, agg;
-        int32_t na = 0;
-        if (!last) {   // the node graph: norms of the diagonal blocks, count, scan, fill; then to the host
-            DevBuf<double> dn;
-            DevBuf<int32_t> cnt, gpd, gid;
-            dn.alloc_raw((size_t)nn, 8);
-            cnt.alloc_raw((size_t)nn, 8);
-            gpd.alloc_raw((size_t)nn + 1, 8);
-            k::amgs_node_norms(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, dn.p, s);
-            k::amgs_graph(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, o.threshold, dn.p, nullptr, cnt.p, s);
-            const int32_t ne = scan_counts(cnt.p, nn, gpd.p, s);
-            gid.alloc_raw((size_t)ne, 8);
-            k::amgs_graph(A.rowptr.p, A.colidx.p, A.val.p, nn, bs, o.threshold, dn.p, gpd.p, gid.p, s);
-            gp.resize((size_t)nn + 1);
-            gi.resize((size_t)ne);
-            SPK_HIP(hipMemcpyAsync(gp.data(), gpd.p, sizeof(int32_t) * gp.size(), hipMemcpyDeviceToHost, s));
-            if (ne) SPK_HIP(hipMemcpyAsync(gi.data(), gid.p, sizeof(int32_t) * gi.size(), hipMemcpyDeviceToHost, s));
-            SPK_HIP(hipStreamSynchronize(s));
-            na = aggregate(gp, gi, agg);
-            last = na == 0 || (int64_t)na * bs >= n;   // no coarsening left
-        }
-        if (last) break;
-        AmgLevelDev &L = d->lv[l];
-        const double *dinv = l == 0 ? dinv0.p : L.dinv.p;
-        double lmin = 0.0, lmax = 0.0;
-        dev_lanczos(c, l == 0 ? nullptr : &A, n, l == 0 ? ld : (int64_t)n, dinv, kLanczosSteps, &lmin, &lmax);
-        info.lambda_max[l] = lmax;
-        const double lo = o.esteig[0] * lmin + o.esteig[1] * lmax, hi = o.esteig[2] * lmin + o.esteig[3] * lmax;
-        if (o.smoother == SPK_AMG_CHEBYSHEV && !(lo > 0.0 && hi > lo))
-            fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", lo, hi, (int)l);
-        smoother_coeffs(L, o, lo, hi);
+    void ritz(int l, double *lmin, double *lmax) const { dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax); }
+    void set_interval(int l, double lo, double hi) { smoother_coeffs(d.lv[(size_t)l], o, lo, hi); }
+    void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths)
+    {
+        AmgLevelDev &L = d.lv[(size_t)l];
+        const int32_t n = rows(l);
         {   // tentative prolongator: 1/sqrt(|aggregate|) comes from the host, like the aggregates
             std::vector<int32_t> size((size_t)na, 0);
             for (int32_t a : agg) if (a >= 0) ++size[(size_t)a];
@@ -832,99 +856,78 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
         }
         L.agg = std::move(agg);
         dev_csr_copy(L.P, L.Ptent, s);
-        const double omega = 4.0 / (3.0 * lmax);
-        for (int it = 0; it < o.nsmooths; ++it) {   // P = (I - omega D^-1 A) P
+        for (int it = 0; it < nsmooths; ++it) {   // P = (I - omega D^-1 A) P
             CsrDev AP, Pn;
-            dev_spgemm(AP, A, L.P, s);
-            dev_add(Pn, 1.0, L.P, -omega, AP, dinv, s);
+            dev_spgemm(AP, A(l), L.P, s);
+            dev_add(Pn, 1.0, L.P, -omega, AP, dinv(l), s);
             L.P = std::move(Pn);
         }
         dev_transpose(L.R, L.P, s);
-        CsrDev Acs;
-        {
-            CsrDev AP, Ac, AcT;
-            dev_spgemm(AP, A, L.P, s);
-            dev_spgemm(Ac, L.R, AP, s);
-            dev_transpose(AcT, Ac, s);
-            dev_add(Acs, 0.5, Ac, 0.5, AcT, nullptr, s);   // exactly symmetric (the products agree to rounding)
-        }
-        d->lv.emplace_back();   // (reserved: the levels never move)
-        AmgLevelDev &N = d->lv.back();
-        N.A = std::move(Acs);
+        CsrDev AP, Ac, AcT;
+        dev_spgemm(AP, A(l), L.P, s);
+        dev_spgemm(Ac, L.R, AP, s);
+        dev_transpose(AcT, Ac, s);
+        d.lv.emplace_back();   // (reserved)
+        AmgLevelDev &N = d.lv.back();
+        dev_add(N.A, 0.5, Ac, 0.5, AcT, nullptr, s);   // exactly symmetric (the products agree to rounding)
         N.n = N.A.nrows;
         N.dinv.alloc((size_t)N.n, 8);
         k::extract_diag_inv(N.A, N.dinv.p, s);
-        info.rows[l + 1] = N.n;
-        info.nnz[l + 1] = N.A.nnz;
     }
-    const size_t L = d->lv.size();
-    const CsrDev &AC = L == 1 ? *A0 : d->lv[L - 1].A;
-    if (AC.nrows > SPK_AMG_MAX_COARSE)
-        fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
-             "most %d -- raise -pc_mg_levels or -pc_gamg_threshold 0", (int)AC.nrows, (int)L, SPK_AMG_MAX_COARSE);
-    {
-        const std::vector<double> cinv = coarse_inverse(dev_csr_download(AC, true, s));
-        d->cinv.upload(cinv.data(), cinv.size());
-    }
-    for (size_t l = 0; l < L; ++l) {   // the V-cycle's vectors, as amg_upload sizes them
-        AmgLevelDev &D = d->lv[l];
-        const size_t nv = l == 0 ? (size_t)ld : (size_t)D.n;
-        if (l > 0) D.b.alloc(nv, 8);
-        D.ya.alloc(nv, 16);
-        D.yb.alloc(nv, 16);
-        if (l == 0 && L > 1) D.t.alloc(nv, 16);
-    }
-    info.levels = (int32_t)L;
-    info.block_size = bs;
-    double tot = 0.0;
-    for (size_t l = 0; l < L; ++l) tot += (double)info.nnz[l];
-    info.operator_complexity = tot / (double)std::max<int64_t>(info.nnz[0], 1);
-    info.setup = SPK_AMG_SETUP_DEVICE;
+    HostCsr coarsest() const { return dev_csr_download(A((int)d.lv.size() - 1), true, s); }
+    void set_coarse_inverse(const std::vector<double> &cinv) { d.cinv.upload(cinv.data(), cinv.size()); }
+};
+
+}  // namespace
+
+std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
+{
+    const auto t0 = Clock::now();
+    const spk_amg_opts &o = c->amg_opts;
+    amg_check_opts(o);
+    c->ensure_scratch();
+    if (c->n_local <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
+    CsrDev copy;
+    const CsrDev &A0 = sorted_rows(c, copy);
+    const int cbs = ctx_block_size(c, o), bs = cbs > 0 ? cbs : detect_bs(dev_csr_download(A0, false, c->stream));
+    auto d = std::make_unique<AmgDev>();
+    d->lv.reserve((size_t)o.max_levels);   // the levels own device buffers and never move
+    d->lv.emplace_back();
+    d->lv[0].n = c->n_local;
+    DevBuf<double> dinv0;
+    dinv0.alloc((size_t)c->n_local, 8);
+    k::extract_diag_inv(c->Ad, dinv0.p, c->stream);
+    DevRoute r{c, *d, o, A0, dinv0.p, c->stream};
+    build_levels(r, bs, o, SPK_AMG_SETUP_DEVICE, t0, d->info);
+    alloc_cycle_vectors(*d, c->ld);
     SPK_HIP(hipDeviceSynchronize());
-    info.setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    d->info.setup_seconds = seconds_since(t0);   // the vectors count too, up to the synchronise
     return d;
 }
 
-void amg_dev_level(spk_ctx *c, int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
-                   double *val)
+// the test hooks: the host hierarchy where pc_setup kept one, else one download from the device-built levels
+void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out)
 {
+    if (c->amg_h) return c->amg_h->h.level(l, which, out);
     const AmgDev &d = *c->amg_d;
-    const int L = (int)d.lv.size();
-    hipStream_t s = c->stream;
-    if (l < 0 || l >= L) fail(SPK_ERR_ARG, "amg: level %d outside [0,%d)", l, L);
+    check_level_query((int)d.lv.size(), l, which);
+    const AmgLevelDev &V = d.lv[(size_t)l];
     if (which == SPK_AMG_COARSE_INV) {
-        if (l != L - 1) fail(SPK_ERR_ARG, "amg: the coarse inverse lives on level %d", L - 1);
-        const int32_t n = d.lv[(size_t)l].n;
-        if (nrows) *nrows = n;
-        if (ncols) *ncols = n;
-        if (nnz) *nnz = (int64_t)n * n;
-        for (int32_t i = 0; rowptr && i <= n; ++i) rowptr[i] = i * n;
-        for (int64_t k = 0; colidx && k < (int64_t)n * n; ++k) colidx[k] = (int32_t)(k % n);
-        if (val) SPK_HIP(hipMemcpy(val, d.cinv.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
-        return;
+        std::vector<double> cinv(out.val ? (size_t)V.n * V.n : 0);
+        if (out.val) SPK_HIP(hipMemcpy(cinv.data(), d.cinv.p, sizeof(double) * cinv.size(), hipMemcpyDeviceToHost));
+        return coarse_inv_out(V.n, cinv.data(), out);
     }
-    if (which != SPK_AMG_OP && which != SPK_AMG_PROLONG && which != SPK_AMG_TENTATIVE) fail(SPK_ERR_ARG, "amg: unknown matrix %d", which);
-    if (which != SPK_AMG_OP && l == L - 1) fail(SPK_ERR_ARG, "amg: the coarsest level has no prolongator");
-    const CsrDev &M = which == SPK_AMG_OP ? (l == 0 ? c->Ad : d.lv[(size_t)l].A)
-                    : which == SPK_AMG_PROLONG ? d.lv[(size_t)l].P : d.lv[(size_t)l].Ptent;
-    if (nrows) *nrows = M.nrows;
-    if (ncols) *ncols = M.ncols;
-    if (nnz) *nnz = M.nnz;
-    if (!rowptr && !colidx && !val) return;
-    HostCsr H = dev_csr_download(M, true, s);
+    const CsrDev &M = which == SPK_AMG_OP ? (l == 0 ? c->Ad : V.A) : which == SPK_AMG_PROLONG ? V.P : V.Ptent;
+    if (!out.rowptr && !out.colidx && !out.val) return out.sizes(M.nrows, M.ncols, M.nnz);   // nothing to download
+    HostCsr H = dev_csr_download(M, true, c->stream);
     if (which == SPK_AMG_OP && l == 0) sort_rows(H);   // the context's CSR keeps the caller's order
-    if (rowptr) std::memcpy(rowptr, H.rp.data(), sizeof(int32_t) * H.rp.size());
-    if (colidx && H.nnz()) std::memcpy(colidx, H.ci.data(), sizeof(int32_t) * H.ci.size());
-    if (val && H.nnz()) std::memcpy(val, H.v.data(), sizeof(double) * H.v.size());
+    csr_out(H, out);
 }
 
-void amg_dev_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg)
+void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg)
 {
-    const AmgDev &d = *c->amg_d;
-    if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no aggregates", l);
-    const auto &a = d.lv[(size_t)l].agg;
-    if (nnodes) *nnodes = (int32_t)a.size();
-    if (agg) std::memcpy(agg, a.data(), sizeof(int32_t) * a.size());
+    if (c->amg_h) aggregates_out(c->amg_h->h.lv, l, nnodes, agg);
+    else aggregates_out(c->amg_d->lv, l, nnodes, agg);
 }
 
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
@@ -1046,7 +1049,7 @@ int spk_amg_destroy_host(spk_amg_hier *h)
 int spk_amg_host_info(const spk_amg_hier *h, spk_amg_info *info)
 {
     if (!h || !info) return SPK_ERR_ARG;
-    h->h.info(info);
+    *info = h->h.info;
     return SPK_OK;
 }
 
@@ -1055,7 +1058,7 @@ int spk_amg_host_level(const spk_amg_hier *h, int level, int which, int32_t *nro
 {
     if (!h) return SPK_ERR_ARG;
     SPK_HOST_TRY
-    h->h.level(level, which, nrows, ncols, nnz, rowptr, colidx, val);
+    h->h.level(level, which, {nrows, ncols, nnz, rowptr, colidx, val});
     SPK_HOST_CATCH
 }
 
@@ -1063,10 +1066,7 @@ int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, i
 {
     if (!h) return SPK_ERR_ARG;
     SPK_HOST_TRY
-    if (level < 0 || level + 1 >= (int)h->h.lv.size()) spk::fail(SPK_ERR_ARG, "amg: level %d has no aggregates", level);
-    const auto &a = h->h.lv[(size_t)level].agg;
-    if (nnodes) *nnodes = (int32_t)a.size();
-    if (agg) std::memcpy(agg, a.data(), sizeof(int32_t) * a.size());
+    spk::aggregates_out(h->h.lv, level, nnodes, agg);
     SPK_HOST_CATCH
 }
 

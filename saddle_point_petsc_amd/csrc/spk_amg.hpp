@@ -15,25 +15,29 @@ struct HostCsr {
     int64_t nnz() const { return (int64_t)ci.size(); }
 };
 
+// where a test hook copies one matrix to; any pointer may be null
+struct CsrOut {
+    int32_t *nrows, *ncols;
+    int64_t *nnz;
+    int32_t *rowptr, *colidx;
+    double *val;
+    void sizes(int32_t nr, int32_t nc, int64_t nz) const { if (nrows) *nrows = nr; if (ncols) *ncols = nc; if (nnz) *nnz = nz; }
+};
+
 struct AmgLevel {
     HostCsr A;              // A_l
     HostCsr Ptent, P, R;    // to level l+1 (empty on the coarsest level); R = P^T
     std::vector<double> dinv;
     std::vector<int32_t> agg;   // aggregate of every node (-1: isolated)
-    double lmin = 0.0, lmax = 0.0;
     double lo = 0.0, hi = 0.0;  // Chebyshev interval
 };
 
 struct AmgHier {
     spk_amg_opts o{};
-    int bs = 1;
     std::vector<AmgLevel> lv;
     std::vector<double> cinv;   // dense inverse of the coarsest A, row-major
-    double setup_seconds = 0.0;
-    void info(spk_amg_info *out) const;
-    // copy one matrix of a level out (see spk_get_amg_level)
-    void level(int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
-               double *val) const;
+    spk_amg_info info{};        // as the set-up loop filled it (setup_seconds: the host build)
+    void level(int l, int which, const CsrOut &out) const;   // copy one matrix of a level out (see spk_get_amg_level)
 };
 
 // throws spk::Error

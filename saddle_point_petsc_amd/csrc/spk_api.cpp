@@ -327,15 +327,19 @@ int spk_pc_set_amg(spk_ctx *c, const spk_amg_opts *o)
     SPK_CATCH(c)
 }
 
+// both set-up routes leave c->amg_d behind
+static void need_amg(const spk_ctx *c)
+{
+    if (!c->amg_d || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
+}
+
 int spk_get_amg_info(const spk_ctx *cc, spk_amg_info *info)
 {
     spk_ctx *c = const_cast<spk_ctx *>(cc);
     SPK_TRY(c)
     if (!info) spk::fail(SPK_ERR_ARG, "null output");
-    const bool dev = c->amg_d && c->amg_d->device_built;
-    if ((!c->amg_h && !dev) || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
-    if (dev) *info = c->amg_d->info;
-    else c->amg_h->h.info(info);
+    need_amg(c);
+    *info = c->amg_d->info;
     SPK_CATCH(c)
 }
 
@@ -344,10 +348,8 @@ int spk_get_amg_level(const spk_ctx *cc, int level, int which, int32_t *nrows, i
 {
     spk_ctx *c = const_cast<spk_ctx *>(cc);
     SPK_TRY(c)
-    const bool dev = c->amg_d && c->amg_d->device_built;
-    if ((!c->amg_h && !dev) || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
-    if (dev) spk::amg_dev_level(c, level, which, nrows, ncols, nnz, rowptr, colidx, val);
-    else c->amg_h->h.level(level, which, nrows, ncols, nnz, rowptr, colidx, val);
+    need_amg(c);
+    spk::amg_ctx_level(c, level, which, {nrows, ncols, nnz, rowptr, colidx, val});
     SPK_CATCH(c)
 }
 
@@ -355,16 +357,8 @@ int spk_get_amg_aggregates(const spk_ctx *cc, int level, int32_t *nnodes, int32_
 {
     spk_ctx *c = const_cast<spk_ctx *>(cc);
     SPK_TRY(c)
-    const bool dev = c->amg_d && c->amg_d->device_built;
-    if ((!c->amg_h && !dev) || !c->pc_ready) spk::fail(SPK_ERR_STATE, "no multigrid hierarchy: spk_pc_set_amg, then spk_pc_setup");
-    if (dev) {
-        spk::amg_dev_aggregates(c, level, nnodes, agg);
-    } else {
-        if (level < 0 || level + 1 >= (int)c->amg_h->h.lv.size()) spk::fail(SPK_ERR_ARG, "amg: level %d has no aggregates", level);
-        const auto &a = c->amg_h->h.lv[(size_t)level].agg;
-        if (nnodes) *nnodes = (int32_t)a.size();
-        if (agg) std::memcpy(agg, a.data(), sizeof(int32_t) * a.size());
-    }
+    need_amg(c);
+    spk::amg_ctx_aggregates(c, level, nnodes, agg);
     SPK_CATCH(c)
 }
 

@@ -840,8 +840,7 @@ struct AmgLevelDev {
 struct AmgDev {
     std::vector<AmgLevelDev> lv;
     DevBuf<double> cinv;
-    bool device_built = false;   // built by amg_build_device: there is no host hierarchy beside it
-    spk_amg_info info{};         // device-built hierarchies only
+    spk_amg_info info{};         // what spk_get_amg_info returns, on both routes
 };
 
 }  // namespace spk
@@ -978,11 +977,11 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact);
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
 // the same hierarchy built on the device from c->Ad (-spk_gamg_setup device); touches nothing of the context but its
-// reduction scratch.  amg_dev_level / amg_dev_aggregates: the test hooks' downloads
+// reduction scratch and leaves c->amg_h null: "built on the device" is c->amg_d && !c->amg_h
 std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c);
-void amg_dev_level(spk_ctx *c, int l, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz, int32_t *rowptr, int32_t *colidx,
-                   double *val);
-void amg_dev_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
+// the test hooks on either route: the host hierarchy's copy, or a download from the device-built levels
+void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
+void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

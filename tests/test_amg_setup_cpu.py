@@ -1,6 +1,6 @@
 """The set-up route of the multigrid hierarchy (spk_amg_opts.setup, -spk_gamg_setup host|device) without a GPU: the
 default, the round trip through the Python options, the refusal of an unknown route, the host-only builder (which
-accepts either route and builds on the host) and the KSP facade's option."""
+accepts either route and builds on the host), the KSP facade's option, and what the level accessors refuse."""
 import numpy as np
 import pytest
 
@@ -50,6 +50,51 @@ def test_host_builder_takes_either_route_and_builds_on_the_host():
             assert np.array_equal(h.aggregates(l), d.aggregates(l))
     h.close()
     d.close()
+
+
+def refused_queries(matrix, aggregates, L):
+    """The eight queries the accessors refuse on a hierarchy of L levels, through matrix(level, which) and
+    aggregates(level): {name: (code, message)}."""
+    calls = {
+        "level -1": lambda: matrix(-1, S.AMG_OP),
+        "level L": lambda: matrix(L, S.AMG_OP),
+        "matrix 99": lambda: matrix(0, 99),
+        "prolongator of the coarsest": lambda: matrix(L - 1, S.AMG_PROLONG),
+        "tentative of the coarsest": lambda: matrix(L - 1, S.AMG_TENTATIVE),
+        "coarse inverse on level 0": lambda: matrix(0, S.AMG_COARSE_INV),
+        "aggregates of the coarsest": lambda: aggregates(L - 1),
+        "aggregates of level -1": lambda: aggregates(-1),
+    }
+    got = {}
+    for name, call in calls.items():
+        with pytest.raises(SpkError) as e:
+            call()
+        got[name] = (e.value.code, str(e.value))
+    return got
+
+
+REFUSED_16 = {   # laplace(16): 2 levels
+    "level -1": "amg: level -1 outside [0,2)",
+    "level L": "amg: level 2 outside [0,2)",
+    "matrix 99": "amg: unknown matrix 99",
+    "prolongator of the coarsest": "amg: the coarsest level has no prolongator",
+    "tentative of the coarsest": "amg: the coarsest level has no prolongator",
+    "coarse inverse on level 0": "amg: the coarse inverse lives on level 1",
+    "aggregates of the coarsest": "amg: level 1 has no aggregates",
+    "aggregates of level -1": "amg: level -1 has no aggregates",
+}
+
+
+def test_level_accessors_refuse_what_is_not_there():
+    A, _, _ = laplace(16)
+    h = S.AmgHierarchy(A)
+    info = h.info()
+    assert info["levels"] == 2 and info["rows"] == [512, 50] and info["block_size"] == 2
+    got = refused_queries(h.matrix, h.aggregates, 2)
+    h.close()
+    assert set(got) == set(REFUSED_16)
+    for name, (code, msg) in got.items():
+        assert code == SPK_ERR_ARG and msg == f"libspk error {SPK_ERR_ARG}: {REFUSED_16[name]}", name
 
 
 @pytest.mark.parametrize("prefix", ["", "-fieldsplit_0_"])

@@ -2,7 +2,7 @@
 (spk_amg_build_host) with the same options: the aggregates and every pattern exactly, the entries to bounds derived from
 the length of the sums (nsmooths = 0) and from the measured sensitivity of the host builder to lambda_max (nsmooths = 1),
 the V-cycle over the device-built hierarchy against the numpy restatement, determinism, solves, the context afterwards,
-and the set-up time against the host build's.
+what the accessors refuse on either route, and the set-up time against the host build's.
 
 Operators: the smallest on which each part can go wrong -- 16^2 / 64^2 grids (bs 2, isolated Dirichlet nodes, 2 and 4
 levels), cube_odd (bs 3), gen1001 (bs 1, no structure), strip (off the square grid), odd33_bs1 (forced bs 1), a hub
@@ -21,9 +21,10 @@ import scipy.sparse.linalg as spl
 
 import saddle_point_petsc_amd as S
 from test_amg_cpu import OFFGRID_BUILT, general_spd, hierarchy_mats, vcycle_ref
+from test_amg_setup_cpu import REFUSED_16, refused_queries
 
 pytestmark = pytest.mark.gpu
-SPK_ERR_UNSUPPORTED = -6
+SPK_ERR_ARG, SPK_ERR_STATE, SPK_ERR_UNSUPPORTED = -1, -3, -6
 
 
 def _csr(M):
@@ -319,6 +320,29 @@ def test_coarsest_level_above_the_dense_limit_is_refused_alike():
     c.pc_setup(S.PC_JACOBI, amg=dict(setup="device"))      # the context stays usable
     assert c.amg_info()["levels"] >= 3
     c.close()
+
+
+def test_accessors_refuse_alike_on_both_routes():
+    A = _operator("grid16")
+    h = S.AmgHierarchy(A)
+    want = refused_queries(h.matrix, h.aggregates, h.info()["levels"])
+    h.close()
+    assert {k: v[1].split(": ", 1)[1] for k, v in want.items()} == REFUSED_16
+    infos = {}
+    for route in ("host", "device"):
+        with _ctx(A, amg=dict(setup=route)) as c:
+            infos[route] = c.amg_info()
+            got = refused_queries(c.amg_level, c.amg_aggregates, infos[route]["levels"])
+        assert got == want, route
+        assert all(code == SPK_ERR_ARG for code, _ in got.values())
+    hi, di = infos["host"], infos["device"]
+    assert all(hi[k] == di[k] for k in ("levels", "rows", "nnz", "block_size"))
+    assert (hi["setup"], di["setup"]) == (S.AMG_SETUP_HOST, S.AMG_SETUP_DEVICE)
+    with _ctx(A) as c:                                     # pc_setup ran without amg
+        for call in (c.amg_info, lambda: c.amg_level(0), lambda: c.amg_aggregates(0)):
+            with pytest.raises(S.SpkError) as e:
+                call()
+            assert e.value.code == SPK_ERR_STATE and "no multigrid hierarchy" in str(e.value)
 
 
 def test_device_setup_takes_less_than_half_the_host_time():
