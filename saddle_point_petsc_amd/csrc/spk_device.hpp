@@ -601,6 +601,124 @@ inline GivensRider no_rider()
     return g;
 }
 
+// ---------------------------------------------------------------------------
+// The frame of the A-block product kernels  y (+)= A x (+ B^T lambda) (+ off-rank part)  (spk_k_spmv.hip, spk_k_dict.hip,
+// spk_k_dict3.hip).  A layout supplies its own sum of A x per row, its early load of y and its store; what stands around
+// them -- the gate and the rider, the workgroup's place on its XCD, the row's off-rank and B^T terms, the launch -- is here.
+// ---------------------------------------------------------------------------
+// what a row adds to its sum of A x: B^T rows times lam (bt_rowptr == nullptr: none) and the off-rank columns
+struct RowTail {
+    const int32_t *bt_rowptr, *bt_colidx;
+    const double *bt_val, *lam;
+    OffDiag od;
+};
+
+// the gate, then the rider in workgroup 0 of a RIDE launch (lds: see givens_rider).  Returns the workgroup's number among
+// those that hold rows, -1: nothing (more) to do
+template <bool RIDE>
+__device__ __forceinline__ int product_prologue(const int32_t *done, const GivensRider &gr, double *lds)
+{
+    if (done && *done) return -1;
+    if (RIDE && blockIdx.x == 0) {  // a pending Givens step beside the rows
+        givens_rider(gr, lds);
+        return -1;
+    }
+    return (int)blockIdx.x - (RIDE ? 1 : 0);
+}
+// workgroups b, b+8, ... share an XCD (round-robin dispatch): each XCD gets a contiguous run of row tiles, so the x window
+// stays in ITS L2
+__device__ __forceinline__ int xcd_tile(int bx, int tiles_per_xcd) { return (bx & 7) * tiles_per_xcd + (bx >> 3); }
+
+// s += off-rank columns of the row (ghost values already exchanged), then (bt) its B^T entries times lam, each in stored
+// order, one fused multiply-add per entry: the ONE spelling of these sums, so every layout gives the same bits.
+// (In place: with s passed and returned by value the pipelined 2x2 kernel is scheduled into 222 VGPRs instead of 168.)
+__device__ __forceinline__ void row_tail_bt(const RowTail &t, int k, int k1, double &s)
+{
+    for (; k < k1; ++k) s = __builtin_fma(t.bt_val[k], t.lam[t.bt_colidx[k]], s);
+}
+__device__ __forceinline__ void row_tail_add(const RowTail &t, int64_t row, double &s, bool bt)
+{
+    if (t.od.rowptr)
+        for (int k = t.od.rowptr[row]; k < t.od.rowptr[row + 1]; ++k) s = __builtin_fma(t.od.val[k], t.od.xg[t.od.colidx[k]], s);
+    if (bt) row_tail_bt(t, t.bt_rowptr[row], t.bt_rowptr[row + 1], s);
+}
+// The first B^T entries of a row fetched early, behind the matrix stream, not at the end of the kernel (MatMult on the nest
+// operator, 1024^2: 80.2 us against 68.5 for the product without them); a longer row takes the rest in add().
+// row_tail_add(t, row, s, false) followed by add(t, s) is row_tail_add(t, row, s, true), bit for bit.
+constexpr int kBtPre = 4;
+struct BtPre {
+    int k0, k1;
+    double v[kBtPre], l[kBtPre];
+    __device__ __forceinline__ void load(const RowTail &t, int64_t row)
+    {
+        k0 = t.bt_rowptr[row];
+        k1 = t.bt_rowptr[row + 1];
+#pragma unroll
+        for (int j = 0; j < kBtPre; ++j) {
+            const bool in = k0 + j < k1;
+            v[j] = in ? t.bt_val[k0 + j] : 0.0;
+            l[j] = in ? t.lam[t.bt_colidx[k0 + j]] : 0.0;
+        }
+    }
+    __device__ __forceinline__ void add(const RowTail &t, double &s) const
+    {
+#pragma unroll
+        for (int j = 0; j < kBtPre; ++j)
+            if (k0 + j < k1) s = __builtin_fma(v[j], l[j], s);
+        row_tail_bt(t, k0 + kBtPre, k1, s);
+    }
+};
+
+// the damped-Jacobi update of the FP32 sweeps on the same layouts, every operation rounded on its own (the oracle's float loop)
+__device__ __forceinline__ float sweep_update(float y, float omega, float d, float x, float s)
+{
+#pragma clang fp contract(off)
+    return y + ((omega * d) * (x - s));
+}
+
+// Host side: what every product launcher works out from its arguments before it launches
+struct ProductLaunch {
+    RowTail tail;
+    GivensRider gr;
+    const int32_t *done;
+    int nride;          // workgroups in front of those that hold rows
+    bool acc, ride, bt;
+    size_t rider_lds;   // dynamic LDS the rider needs in its workgroup (kernels without static LDS of that size)
+};
+// a rank without rows: the rider without tiles, and nothing else to launch
+inline bool product_is_empty(int64_t nrows, const GivensRider *rider, const int32_t *done, hipStream_t s)
+{
+    if (nrows == 0 && rider) givens_rider_alone(*rider, done, s);
+    return nrows == 0;
+}
+inline ProductLaunch make_product_launch(const CsrDev *bt, const double *lam, const OffDiag *od, const GivensRider *rider,
+                                         const int32_t *done, bool accumulate)
+{
+    // (B^T rows: MatMult on the nest operator, never the iteration's launch)
+    if (bt && rider) fail(SPK_ERR_ARG, "A-block product: B^T rows and a rider in one launch");
+    ProductLaunch p{};
+    p.tail = RowTail{bt ? bt->rowptr.p : nullptr, bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam,
+                     od ? *od : OffDiag{nullptr, nullptr, nullptr, nullptr}};
+    p.gr = rider ? *rider : no_rider();
+    p.done = done;
+    p.nride = rider ? 1 : 0;
+    p.acc = accumulate;
+    p.ride = rider != nullptr;
+    p.bt = bt != nullptr;
+    p.rider_lds = rider ? sizeof(double) * (size_t)(kThreads + 4 * (kMaxNv + 2) + 4) : 0;
+    return p;
+}
+// f(ACC, RIDE, BT) as std::bool_constant values, for the six combinations a product is launched in
+template <class F>
+inline void dispatch_product(bool acc, bool ride, bool bt, F &&f)
+{
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (bt) acc ? f(Y{}, N{}, Y{}) : f(N{}, N{}, Y{});
+    else if (acc) ride ? f(Y{}, Y{}, N{}) : f(Y{}, N{}, N{});
+    else ride ? f(N{}, Y{}, N{}) : f(N{}, N{}, N{});
+}
+
 // tile length (double2 per lane) and grid of the wave-split forms: about one tile per workgroup
 struct WsShape {
     int U, grid;

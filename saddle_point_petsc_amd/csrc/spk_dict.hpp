@@ -46,6 +46,44 @@ __device__ __forceinline__ void dict_load_lds(const DictArgs &d, int nclsvals, c
     for (int i = threadIdx.x; i < nclsvals; i += blockDim.x) fl[i] = d.fld[i];
     __syncthreads();
 }
+// ... and where they lie there: lengths of the row types, their {offset, class} entries, {base, 2^g} of the class entries,
+// the per-class bit fields
+struct DictTables {
+    const int32_t *tlen;
+    int2 *tent;
+    const double2 *cv;
+    const int32_t *fl;
+};
+__device__ __forceinline__ DictTables dict_tables(const DictArgs &d, char *smem)
+{
+    return DictTables{reinterpret_cast<const int32_t *>(smem), reinterpret_cast<int2 *>(smem + 4 * ((d.ntype + 1) & ~1)),
+                      reinterpret_cast<const double2 *>(smem + d.cls_off), reinterpret_cast<const int32_t *>(smem + d.fld_off)};
+}
+// chunks [c0, c1) of workgroup bx (false: none).  Workgroups b, b+8, ... share an XCD: each XCD gets a contiguous run of
+// chunks, so the x window stays in ITS L2
+__device__ __forceinline__ bool dict_chunk_range(const DictArgs &d, int bx, int &c0, int &c1)
+{
+    c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
+    c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
+    return c0 < c1;
+}
+// the pipelined kernels (row types of at most KM blocks): the LDS copy of the row types as the issue stage wants it -- byte
+// offsets (stride bytes per block column) instead of block columns; beyond a row's length an offset outside the buffer
+// and the null class
+template <int KM>
+__device__ __forceinline__ void dict_prepare_types(const DictArgs &d, const DictTables &T, int stride)
+{
+    for (int i = threadIdx.x; i < d.ntype * KM; i += kThreads) {
+        const int t = i / KM, k = i - t * KM;
+        int2 e = T.tent[i];
+        if (k < T.tlen[t]) e.x *= stride;
+        else e = make_int2((int)0x80000000u, d.nclass);
+        T.tent[i] = e;
+    }
+    __syncthreads();
+}
+// ... and this thread's block row of chunk ch, the last one beyond the end (re-read, not computed)
+__device__ __forceinline__ int dict_rowof(const DictArgs &d, int ch) { return min(ch * kDictChunk + (int)threadIdx.x, d.nbrows - 1); }
 
 // The stored form of a block: its bs*bs integer deviations k (value = base + k 2^g), each as a two's-complement BIT FIELD
 // of the width its class entry needs (1 .. 31 bits; the widths of a class fit 64 bits for 2x2 blocks, twice 64 for 3x3

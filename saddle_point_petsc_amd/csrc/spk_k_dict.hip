@@ -30,31 +30,18 @@ namespace k {
 // U3 (3x3 blocks only): 0 = per-class fields, 1..3 = one field layout for all classes (dict_field3u)
 template <int BS, bool ACC, bool RIDE, bool BT, int U3>
 __global__ __launch_bounds__(kThreads) void spmv_dict_kernel(DictArgs d, const double *__restrict__ x, double *__restrict__ y,
-                                                             const int32_t *__restrict__ bt_rowptr,
-                                                             const int32_t *__restrict__ bt_colidx,
-                                                             const double *__restrict__ bt_val, const double *__restrict__ lam,
-                                                             OffDiag od, const int32_t *__restrict__ done, GivensRider gr)
+                                                             RowTail tail, const int32_t *__restrict__ done, GivensRider gr)
 {
 #pragma clang fp contract(off)  // every product rounded on its own, as in the CSR loop the sums are compared with
-    if (done && *done) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (RIDE && blockIdx.x == 0) {  // the rider: a pending Givens step beside the row chunks (its LDS: the table space)
-        givens_rider(gr, reinterpret_cast<double *>(smem));
-        return;
-    }
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    // workgroups b, b+8, ... share an XCD: each XCD gets a contiguous run of chunks, so the x window stays in ITS L2
-    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
-    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
-    if (c0 >= c1) return;
+    const int bx = product_prologue<RIDE>(done, gr, reinterpret_cast<double *>(smem));  // (the rider's LDS: the table space)
+    int c0, c1;
+    if (bx < 0 || !dict_chunk_range(d, bx, c0, c1)) return;
     // what does not depend on the tables is requested before they are copied
     int br = c0 * kDictChunk + (int)threadIdx.x;
     int tidn = br < d.nbrows ? (int)d.tid[br] : -1;
     dict_load_lds(d, (d.nclass + 1) * BS * BS, smem);
-    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
-    const int2 *tent = reinterpret_cast<const int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
-    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
-    const int32_t *fl = reinterpret_cast<const int32_t *>(smem + d.fld_off);
+    const DictTables T = dict_tables(d, smem);
 
     for (int ch = c0; ch < c1; ++ch) {
         const int tc = tidn;
@@ -76,25 +63,14 @@ __global__ __launch_bounds__(kThreads) void spmv_dict_kernel(DictArgs d, const d
                 for (int r = 0; r < BS; ++r) yacc[r] = y[(int64_t)BS * brc + r];
             }
         }
-        // B^T lambda of these rows (MatMult on the nest operator): first entries requested early (see spmv_bcsr_kernel)
-        constexpr int kBtPre = 4;
-        int kb0[BS], kb1[BS];
-        double btv[BS][kBtPre], btl[BS][kBtPre];
+        // B^T lambda of these rows (MatMult on the nest operator): first entries requested early (BtPre)
+        BtPre pre[BS];
         if (BT) {
 #pragma unroll
-            for (int r = 0; r < BS; ++r) {
-                kb0[r] = bt_rowptr[(int64_t)BS * brc + r];
-                kb1[r] = bt_rowptr[(int64_t)BS * brc + r + 1];
-#pragma unroll
-                for (int j = 0; j < kBtPre; ++j) {
-                    const bool in = kb0[r] + j < kb1[r];
-                    btv[r][j] = in ? bt_val[kb0[r] + j] : 0.0;
-                    btl[r][j] = in ? lam[bt_colidx[kb0[r] + j]] : 0.0;
-                }
-            }
+            for (int r = 0; r < BS; ++r) pre[r].load(tail, (int64_t)BS * brc + r);
         }
-        const int len = tlen[tc];
-        const int2 *te = tent + (size_t)tc * d.kmax;
+        const int len = T.tlen[tc];
+        const int2 *te = T.tent + (size_t)tc * d.kmax;
         // blocks whose loads are in flight together: a 2-D interior row whole (five 16-byte code loads + nine gathers of x);
         // 3x3: nine (a third of an interior row; measured on the 256 x 256 x 32 slab: 264 us with three, 244-259 with five,
         // 224-229 with nine)
@@ -130,8 +106,8 @@ __global__ __launch_bounds__(kThreads) void spmv_dict_kernel(DictArgs d, const d
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (k0 + g < len) {
-                    const double2 *cb = cv + (size_t)e[g].y * (BS * BS);
-                    const int32_t *fb = fl + (size_t)e[g].y * (BS * BS);
+                    const double2 *cb = T.cv + (size_t)e[g].y * (BS * BS);
+                    const int32_t *fb = T.fl + (size_t)e[g].y * (BS * BS);
 #pragma unroll
                     for (int r = 0; r < BS; ++r)
 #pragma unroll
@@ -145,17 +121,8 @@ __global__ __launch_bounds__(kThreads) void spmv_dict_kernel(DictArgs d, const d
         }
 #pragma unroll
         for (int r = 0; r < BS; ++r) {
-            const int64_t row = (int64_t)BS * brc + r;
-            // (off-rank and B^T terms: fused multiply-adds, as the compiler contracts them in the blocked and CSR kernels --
-            // every layout gives the same bits on these rows too)
-            if (od.rowptr)  // off-rank columns of this row (ghost values already exchanged)
-                for (int k = od.rowptr[row]; k < od.rowptr[row + 1]; ++k) s[r] = __builtin_fma(od.val[k], od.xg[od.colidx[k]], s[r]);
-            if (BT) {
-#pragma unroll
-                for (int j = 0; j < kBtPre; ++j)
-                    if (kb0[r] + j < kb1[r]) s[r] = __builtin_fma(btv[r][j], btl[r][j], s[r]);
-                for (int k = kb0[r] + kBtPre; k < kb1[r]; ++k) s[r] = __builtin_fma(bt_val[k], lam[bt_colidx[k]], s[r]);
-            }
+            row_tail_add(tail, (int64_t)BS * brc + r, s[r], false);
+            if (BT) pre[r].add(tail, s[r]);
             if (ACC) s[r] += yacc[r];
         }
         if (BS == 2) {
@@ -221,42 +188,19 @@ __device__ __forceinline__ void dict2_issue(const DictArgs &d, __amdgpu_buffer_r
 
 template <bool ACC, bool RIDE, bool BT, int KM, bool UNI>
 __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const double *__restrict__ x, double *__restrict__ y,
-                                                              const int32_t *__restrict__ bt_rowptr,
-                                                              const int32_t *__restrict__ bt_colidx,
-                                                              const double *__restrict__ bt_val, const double *__restrict__ lam,
-                                                              OffDiag od, const int32_t *__restrict__ done, GivensRider gr)
+                                                              RowTail tail, const int32_t *__restrict__ done, GivensRider gr)
 {
 #pragma clang fp contract(off)
-    if (done && *done) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (RIDE && blockIdx.x == 0) {
-        givens_rider(gr, reinterpret_cast<double *>(smem));
-        return;
-    }
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
-    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
-    if (c0 >= c1) return;
-    const int last = d.nbrows - 1;
-    auto rowof = [&](int ch) { return min(ch * kDictChunk + (int)threadIdx.x, last); };
+    const int bx = product_prologue<RIDE>(done, gr, reinterpret_cast<double *>(smem));
+    int c0, c1;
+    if (bx < 0 || !dict_chunk_range(d, bx, c0, c1)) return;
     // row types of the first two chunks: requested before the tables are copied
-    int tA = (int)d.tid[rowof(c0)];
-    int tB = (int)d.tid[rowof(c0 + 1)];
+    int tA = (int)d.tid[dict_rowof(d, c0)];
+    int tB = (int)d.tid[dict_rowof(d, c0 + 1)];
     dict_load_lds(d, (d.nclass + 1) * 4, smem);
-    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
-    int2 *tent = reinterpret_cast<int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
-    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
-    const int32_t *fl = reinterpret_cast<const int32_t *>(smem + d.fld_off);
-    // the LDS copy of the row types as the issue stage wants it: byte offsets of x; beyond a row's length an offset
-    // outside the buffer and the null class
-    for (int i = threadIdx.x; i < d.ntype * KM; i += kThreads) {
-        const int t = i / KM, k = i - t * KM;
-        int2 e = tent[i];
-        if (k < tlen[t]) e.x *= 16;
-        else e = make_int2((int)0x80000000u, d.nclass);
-        tent[i] = e;
-    }
-    __syncthreads();
+    const DictTables T = dict_tables(d, smem);
+    dict_prepare_types<KM>(d, T, 16);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x), 0, 16 * d.nbrows, 0x00020000);
 
     Dict2Stage<KM, ACC> SA, SB;
@@ -265,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
         double s[2] = {0.0, 0.0};
 #pragma unroll
         for (int g = 0; g < KM; ++g) {
-            const double2 *cb = cv + (size_t)S.cls[g] * 4;
+            const double2 *cb = T.cv + (size_t)S.cls[g] * 4;
             if (UNI) {
                 // one field layout for every class (DictArgs::uw): entries 0 / 2 at the bottom of the low / high half,
                 // 1 / 3 at the top -- one instruction each, no table read
@@ -275,21 +219,17 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
                 s[1] += dict_decode(__builtin_amdgcn_sbfe(hi, 0u, (unsigned)d.uw[2]), cb[2]) * S.xv[g].x;
                 s[1] += dict_decode(hi >> (32 - d.uw[3]), cb[3]) * S.xv[g].y;
             } else {
-                const int32_t *fb = fl + (size_t)S.cls[g] * 4;
+                const int32_t *fb = T.fl + (size_t)S.cls[g] * 4;
                 s[0] += dict_decode(dict_field2(S.w[g], fb[0]), cb[0]) * S.xv[g].x;
                 s[0] += dict_decode(dict_field2(S.w[g], fb[1]), cb[1]) * S.xv[g].y;
                 s[1] += dict_decode(dict_field2(S.w[g], fb[2]), cb[2]) * S.xv[g].x;
                 s[1] += dict_decode(dict_field2(S.w[g], fb[3]), cb[3]) * S.xv[g].y;
             }
         }
-        if (brc > last) return;
+        if (brc >= d.nbrows) return;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            const int64_t row = 2 * (int64_t)brc + r;
-            if (od.rowptr)
-                for (int k = od.rowptr[row]; k < od.rowptr[row + 1]; ++k) s[r] = __builtin_fma(od.val[k], od.xg[od.colidx[k]], s[r]);
-            if (BT)
-                for (int k = bt_rowptr[row]; k < bt_rowptr[row + 1]; ++k) s[r] = __builtin_fma(bt_val[k], lam[bt_colidx[k]], s[r]);
+            row_tail_add(tail, 2 * (int64_t)brc + r, s[r], BT);
             if (ACC) s[r] += r == 0 ? S.yv.x : S.yv.y;
         }
         double2 o;
@@ -298,16 +238,16 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
         reinterpret_cast<double2 *>(y)[brc] = o;
     };
 
-    dict2_issue<KM, ACC>(d, xr, y, tent, tA, rowof(c0), SA);
-    tA = (int)d.tid[rowof(c0 + 2)];
+    dict2_issue<KM, ACC>(d, xr, y, T.tent, tA, dict_rowof(d, c0), SA);
+    tA = (int)d.tid[dict_rowof(d, c0 + 2)];
     for (int ch = c0;; ch += 2) {
         // loads of the next chunk (and the row type of the one after it), then this chunk's arithmetic
-        dict2_issue<KM, ACC>(d, xr, y, tent, tB, rowof(ch + 1), SB);
-        tB = (int)d.tid[rowof(ch + 3)];
+        dict2_issue<KM, ACC>(d, xr, y, T.tent, tB, dict_rowof(d, ch + 1), SB);
+        tB = (int)d.tid[dict_rowof(d, ch + 3)];
         compute(ch, SA);
         if (ch + 1 >= c1) break;
-        dict2_issue<KM, ACC>(d, xr, y, tent, tA, rowof(ch + 2), SA);
-        tA = (int)d.tid[rowof(ch + 4)];
+        dict2_issue<KM, ACC>(d, xr, y, T.tent, tA, dict_rowof(d, ch + 2), SA);
+        tA = (int)d.tid[dict_rowof(d, ch + 4)];
         compute(ch + 1, SB);
         if (ch + 2 >= c1) break;
     }
@@ -316,63 +256,28 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
 void spmv_dict(const DictDev &A, const double *x, double *y, const CsrDev *bt, const double *lam, const int32_t *done,
                hipStream_t s, bool accumulate, const OffDiag *odp, const GivensRider *rider)
 {
-    if (A.nbrows == 0) {
-        if (rider) givens_rider_alone(*rider, done, s);
-        return;
-    }
+    if (product_is_empty(A.nbrows, rider, done, s)) return;
     if (spmv_dict3(A, x, y, bt, lam, done, s, accumulate, odp, rider)) return;   // 27-point row types, one field layout: pipelined
+    const ProductLaunch p = make_product_launch(bt, lam, odp, rider, done, accumulate);
     int grid = 0;
     const DictArgs d = dict_args(A, &grid);
-    const OffDiag od = odp ? *odp : OffDiag{nullptr, nullptr, nullptr, nullptr};
-    const GivensRider gr = rider ? *rider : no_rider();
-    const int nride = rider ? 1 : 0;
     // LDS: the tables; a launch with a rider needs the rider's scratch in block 0
-    size_t lds = (size_t)A.lds_bytes;
-    if (rider) lds = std::max(lds, sizeof(double) * (size_t)(kThreads + 4 * (kMaxNv + 2) + 4));
-#define SPK_LAUNCH_DICT_U(BS, ACC, RIDE, BTF, U3)                                                                               \
-    SPK_LAUNCH_PRODUCT((spmv_dict_kernel<BS, ACC, RIDE, BTF, U3>), dim3(grid + nride), dim3(kThreads), lds, s, d, x, y,        \
-                       bt ? bt->rowptr.p : nullptr, bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od, done, gr)
-#define SPK_LAUNCH_DICT(BS, ACC, RIDE, BTF)                                                                                     \
-    do {                                                                                                                        \
-        if (BS == 2 || A.uniform3 == 0) SPK_LAUNCH_DICT_U(BS, ACC, RIDE, BTF, 0);                                               \
-        else if (A.uniform3 == 1) SPK_LAUNCH_DICT_U(3, ACC, RIDE, BTF, 1);                                                      \
-        else if (A.uniform3 == 2) SPK_LAUNCH_DICT_U(3, ACC, RIDE, BTF, 2);                                                      \
-        else SPK_LAUNCH_DICT_U(3, ACC, RIDE, BTF, 3);                                                                           \
-    } while (0)
-#define SPK_DISPATCH_DICT(BS)                                                                                                   \
-    if (bt) {                                                                                                                   \
-        if (rider) fail(SPK_ERR_ARG, "spmv_dict: B^T rows and a rider in one launch");                                         \
-        if (accumulate) SPK_LAUNCH_DICT(BS, true, false, true);                                                                 \
-        else SPK_LAUNCH_DICT(BS, false, false, true);                                                                           \
-    } else if (accumulate) {                                                                                                    \
-        if (rider) SPK_LAUNCH_DICT(BS, true, true, false);                                                                      \
-        else SPK_LAUNCH_DICT(BS, true, false, false);                                                                           \
-    } else {                                                                                                                    \
-        if (rider) SPK_LAUNCH_DICT(BS, false, true, false);                                                                     \
-        else SPK_LAUNCH_DICT(BS, false, false, false);                                                                          \
-    }
-    if (A.bs == 2 && A.kmax == 9 && A.nbrows < (1 << 27) && !A.straddle) {
-        // row types of the 9-point stencil: the pipelined kernel
-#pragma push_macro("SPK_LAUNCH_DICT")
-#undef SPK_LAUNCH_DICT
-#define SPK_LAUNCH_DICT(BS_, ACC, RIDE, BTF)                                                                                    \
-    do {                                                                                                                        \
-        if (A.uniform)                                                                                                          \
-            SPK_LAUNCH_PRODUCT((spmv_dict2_kernel<ACC, RIDE, BTF, 9, true>), dim3(grid + nride), dim3(kThreads), lds, s, d, x, \
-                               y, bt ? bt->rowptr.p : nullptr, bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od,  \
-                               done, gr);                                                                                       \
-        else                                                                                                                    \
-            SPK_LAUNCH_PRODUCT((spmv_dict2_kernel<ACC, RIDE, BTF, 9, false>), dim3(grid + nride), dim3(kThreads), lds, s, d, x,\
-                               y, bt ? bt->rowptr.p : nullptr, bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od,  \
-                               done, gr);                                                                                       \
-    } while (0)
-        SPK_DISPATCH_DICT(2)
-#pragma pop_macro("SPK_LAUNCH_DICT")
-    } else if (A.bs == 2) { SPK_DISPATCH_DICT(2) }
-    else { SPK_DISPATCH_DICT(3) }
-#undef SPK_DISPATCH_DICT
-#undef SPK_LAUNCH_DICT
-#undef SPK_LAUNCH_DICT_U
+    const size_t lds = std::max((size_t)A.lds_bytes, p.rider_lds);
+    // row types of the 9-point stencil: the pipelined kernel
+    const bool pipelined = A.bs == 2 && A.kmax == 9 && A.nbrows < (1 << 27) && !A.straddle;
+    dispatch_product(p.acc, p.ride, p.bt, [&](auto acc, auto ride, auto btf) {
+        constexpr bool ACC = acc.value, RIDE = ride.value, BTF = btf.value;
+        auto launch = [&](auto kern) {
+            SPK_LAUNCH_PRODUCT(kern, dim3(grid + p.nride), dim3(kThreads), lds, s, d, x, y, p.tail, p.done, p.gr);
+        };
+        if (pipelined && A.uniform) launch(spmv_dict2_kernel<ACC, RIDE, BTF, 9, true>);
+        else if (pipelined) launch(spmv_dict2_kernel<ACC, RIDE, BTF, 9, false>);
+        else if (A.bs == 2) launch(spmv_dict_kernel<2, ACC, RIDE, BTF, 0>);
+        else if (A.uniform3 == 0) launch(spmv_dict_kernel<3, ACC, RIDE, BTF, 0>);
+        else if (A.uniform3 == 1) launch(spmv_dict_kernel<3, ACC, RIDE, BTF, 1>);
+        else if (A.uniform3 == 2) launch(spmv_dict_kernel<3, ACC, RIDE, BTF, 2>);
+        else launch(spmv_dict_kernel<3, ACC, RIDE, BTF, 3>);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -389,15 +294,10 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict_kernel(DictArg
 #pragma clang fp contract(off)  // every product and sum below is rounded on its own (the oracle's float loop)
     if (done && *done) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int bx = (int)blockIdx.x;
-    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
-    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
-    if (c0 >= c1) return;
+    int c0, c1;
+    if (!dict_chunk_range(d, (int)blockIdx.x, c0, c1)) return;
     dict_load_lds(d, (d.nclass + 1) * BS * BS, smem);
-    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
-    const int2 *tent = reinterpret_cast<const int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
-    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
-    const int32_t *fl = reinterpret_cast<const int32_t *>(smem + d.fld_off);
+    const DictTables T = dict_tables(d, smem);
     for (int ch = c0; ch < c1; ++ch) {
         const int br = ch * kDictChunk + (int)threadIdx.x;
         if (br >= d.nbrows) continue;
@@ -405,8 +305,8 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict_kernel(DictArg
         float s[BS];
 #pragma unroll
         for (int r = 0; r < BS; ++r) s[r] = 0.0f;
-        const int len = tlen[tc];
-        const int2 *te = tent + (size_t)tc * d.kmax;
+        const int len = T.tlen[tc];
+        const int2 *te = T.tent + (size_t)tc * d.kmax;
         constexpr int G = BS == 2 ? 10 : 3;
         for (int k0 = 0; k0 < len; k0 += G) {
             int2 e[G];
@@ -433,8 +333,8 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict_kernel(DictArg
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (k0 + g < len) {
-                    const double2 *cb = cv + (size_t)e[g].y * (BS * BS);
-                    const int32_t *fb = fl + (size_t)e[g].y * (BS * BS);
+                    const double2 *cb = T.cv + (size_t)e[g].y * (BS * BS);
+                    const int32_t *fb = T.fl + (size_t)e[g].y * (BS * BS);
 #pragma unroll
                     for (int r = 0; r < BS; ++r)
 #pragma unroll
@@ -449,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict_kernel(DictArg
 #pragma unroll
         for (int r = 0; r < BS; ++r) {
             const int64_t row = (int64_t)BS * br + r;
-            yout[row] = yin[row] + ((omega * d32[row]) * (x32[row] - s[r]));
+            yout[row] = sweep_update(yin[row], omega, d32[row], x32[row], s[r]);
         }
     }
 }

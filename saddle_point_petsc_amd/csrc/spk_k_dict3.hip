@@ -24,18 +24,28 @@ namespace k {
 constexpr int kD3G = 9;        // blocks per group
 constexpr int kD3Groups = 3;   // groups per block row (27 positions)
 
-// the LDS copy of the row types as the issue stage wants it: byte offsets (stride bytes per block column) instead of block
-// columns; beyond a row's length an offset outside the buffer and the null class
-__device__ __forceinline__ void dict3_prepare_types(const DictArgs &d, const int32_t *tlen, int2 *tent, int stride)
+// The two register stages over the groups of a workgroup's chunks [c0, c1) (group q: chunk c0 + q / 3, positions 9 (q % 3) ...):
+// issue(t, brr, g, S) requests group g of block row brr, whose row type is t, into S; compute(q, S) takes group q from S.
+// tA: the row type of the first block row (requested by the caller before the tables are copied); the row type a group
+// needs is requested one group ahead (two registers, alternating with the stages)
+template <class Stage, class Issue, class Compute>
+__device__ __forceinline__ void dict3_two_stage(const DictArgs &d, int c0, int c1, int tA, Issue issue, Compute compute)
 {
-    for (int i = threadIdx.x; i < d.ntype * 27; i += kThreads) {
-        const int t = i / 27, k = i - t * 27;
-        int2 e = tent[i];
-        if (k < tlen[t]) e.x *= stride;
-        else e = make_int2((int)0x80000000u, d.nclass);
-        tent[i] = e;
+    const int nq = (c1 - c0) * kD3Groups;
+    auto rowq = [&](int q) { return dict_rowof(d, c0 + q / kD3Groups); };
+    int tB = tA;
+    Stage SA, SB;
+    issue(tA, rowq(0), 0, SA);
+    for (int q = 0;; q += 2) {
+        tA = (int)d.tid[rowq(q + 2)];
+        issue(tB, rowq(q + 1), (q + 1) % kD3Groups, SB);
+        compute(q, SA);
+        if (q + 1 >= nq) break;
+        tB = (int)d.tid[rowq(q + 3)];
+        issue(tA, rowq(q + 2), (q + 2) % kD3Groups, SA);
+        compute(q + 1, SB);
+        if (q + 2 >= nq) break;
     }
-    __syncthreads();
 }
 
 template <bool ACC>
@@ -80,43 +90,27 @@ __device__ __forceinline__ void dict3_issue(const DictArgs &d, __amdgpu_buffer_r
 
 template <bool ACC, bool RIDE, bool BT, int U3>
 __global__ __launch_bounds__(kThreads) void spmv_dict3_kernel(DictArgs d, const double *__restrict__ x, double *__restrict__ y,
-                                                              const int32_t *__restrict__ bt_rowptr,
-                                                              const int32_t *__restrict__ bt_colidx,
-                                                              const double *__restrict__ bt_val, const double *__restrict__ lam,
-                                                              OffDiag od, const int32_t *__restrict__ done, GivensRider gr)
+                                                              RowTail tail, const int32_t *__restrict__ done, GivensRider gr)
 {
 #pragma clang fp contract(off)
-    if (done && *done) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (RIDE && blockIdx.x == 0) {
-        givens_rider(gr, reinterpret_cast<double *>(smem));
-        return;
-    }
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
-    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
-    if (c0 >= c1) return;
-    const int last = d.nbrows - 1;
-    auto rowof = [&](int ch) { return min(ch * kDictChunk + (int)threadIdx.x, last); };
-    // the row type a group needs is requested one group ahead (two registers, alternating with the stages)
-    int tA = (int)d.tid[rowof(c0)];
-    int tB = tA;
+    const int bx = product_prologue<RIDE>(done, gr, reinterpret_cast<double *>(smem));
+    int c0, c1;
+    if (bx < 0 || !dict_chunk_range(d, bx, c0, c1)) return;
+    const int tA = (int)d.tid[dict_rowof(d, c0)];
     dict_load_lds(d, (d.nclass + 1) * 9, smem);
-    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
-    int2 *tent = reinterpret_cast<int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
-    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
-    dict3_prepare_types(d, tlen, tent, 24);
+    const DictTables T = dict_tables(d, smem);
+    dict_prepare_types<27>(d, T, 24);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x), 0, 24 * d.nbrows, 0x00020000);
 
-    Dict3Stage<ACC> SA, SB;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    const int nq = (c1 - c0) * kD3Groups;
+    auto issue = [&](int tc, int brr, int g, Dict3Stage<ACC> &S) { dict3_issue<ACC>(d, xr, y, T.tent, tc, brr, g, S); };
     auto compute = [&](int q, const Dict3Stage<ACC> &S) {
         const int g = q % kD3Groups;
         if (g == 0) s0 = s1 = s2 = 0.0;
 #pragma unroll
         for (int j = 0; j < kD3G; ++j) {
-            const double2 *cb = cv + (size_t)S.cls[j] * 9;
+            const double2 *cb = T.cv + (size_t)S.cls[j] * 9;
             s0 += dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 0), cb[0]) * S.x0[j];
             s0 += dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 1), cb[1]) * S.x1[j];
             s0 += dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 2), cb[2]) * S.x2[j];
@@ -129,33 +123,17 @@ __global__ __launch_bounds__(kThreads) void spmv_dict3_kernel(DictArgs d, const 
         }
         if (g != kD3Groups - 1) return;
         const int brc = (c0 + q / kD3Groups) * kDictChunk + (int)threadIdx.x;
-        if (brc > last) return;
+        if (brc >= d.nbrows) return;
         double s[3] = {s0, s1, s2};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const int64_t row = 3 * (int64_t)brc + r;
-            if (od.rowptr)
-                for (int k = od.rowptr[row]; k < od.rowptr[row + 1]; ++k) s[r] = __builtin_fma(od.val[k], od.xg[od.colidx[k]], s[r]);
-            if (BT)
-                for (int k = bt_rowptr[row]; k < bt_rowptr[row + 1]; ++k) s[r] = __builtin_fma(bt_val[k], lam[bt_colidx[k]], s[r]);
+            row_tail_add(tail, row, s[r], BT);
             if (ACC) s[r] += r == 0 ? S.y0 : r == 1 ? S.y1 : S.y2;
             y[row] = s[r];
         }
     };
-    // group q: chunk c0 + q / 3, group q % 3
-    auto chunk_of = [&](int q) { return c0 + q / kD3Groups; };
-
-    dict3_issue<ACC>(d, xr, y, tent, tA, rowof(c0), 0, SA);
-    for (int q = 0;; q += 2) {
-        tA = (int)d.tid[rowof(chunk_of(q + 2))];
-        dict3_issue<ACC>(d, xr, y, tent, tB, rowof(chunk_of(q + 1)), (q + 1) % kD3Groups, SB);
-        compute(q, SA);
-        if (q + 1 >= nq) break;
-        tB = (int)d.tid[rowof(chunk_of(q + 3))];
-        dict3_issue<ACC>(d, xr, y, tent, tA, rowof(chunk_of(q + 2)), (q + 2) % kD3Groups, SA);
-        compute(q + 1, SB);
-        if (q + 2 >= nq) break;
-    }
+    dict3_two_stage<Dict3Stage<ACC>>(d, c0, c1, tA, issue, compute);
 }
 
 static bool dict3_applies(const DictDev &A)
@@ -187,33 +165,17 @@ bool spmv_dict3(const DictDev &A, const double *x, double *y, const CsrDev *bt, 
     if (!dict3_applies(A) || A.nbrows == 0) return false;
     int grid = 0;
     const DictArgs d = dict3_args(A, &grid);
-    const OffDiag od = odp ? *odp : OffDiag{nullptr, nullptr, nullptr, nullptr};
-    const GivensRider gr = rider ? *rider : no_rider();
-    const int nride = rider ? 1 : 0;
-    size_t lds = (size_t)A.lds_bytes;
-    if (rider) lds = std::max(lds, sizeof(double) * (size_t)(kThreads + 4 * (kMaxNv + 2) + 4));
-#define SPK_L3U(ACC, RIDE, BTF, U3)                                                                                             \
-    SPK_LAUNCH_PRODUCT((spmv_dict3_kernel<ACC, RIDE, BTF, U3>), dim3(grid + nride), dim3(kThreads), lds, s, d, x, y,           \
-                       bt ? bt->rowptr.p : nullptr, bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od, done, gr)
-#define SPK_L3(ACC, RIDE, BTF)                                                                                                  \
-    do {                                                                                                                        \
-        if (A.uniform3 == 1) SPK_L3U(ACC, RIDE, BTF, 1);                                                                        \
-        else if (A.uniform3 == 2) SPK_L3U(ACC, RIDE, BTF, 2);                                                                   \
-        else SPK_L3U(ACC, RIDE, BTF, 3);                                                                                        \
-    } while (0)
-    if (bt) {
-        if (rider) fail(SPK_ERR_ARG, "spmv_dict3: B^T rows and a rider in one launch");
-        if (accumulate) SPK_L3(true, false, true);
-        else SPK_L3(false, false, true);
-    } else if (accumulate) {
-        if (rider) SPK_L3(true, true, false);
-        else SPK_L3(true, false, false);
-    } else {
-        if (rider) SPK_L3(false, true, false);
-        else SPK_L3(false, false, false);
-    }
-#undef SPK_L3
-#undef SPK_L3U
+    const ProductLaunch p = make_product_launch(bt, lam, odp, rider, done, accumulate);
+    const size_t lds = std::max((size_t)A.lds_bytes, p.rider_lds);
+    dispatch_product(p.acc, p.ride, p.bt, [&](auto acc, auto ride, auto btf) {
+        constexpr bool ACC = acc.value, RIDE = ride.value, BTF = btf.value;
+        auto launch = [&](auto kern) {
+            SPK_LAUNCH_PRODUCT(kern, dim3(grid + p.nride), dim3(kThreads), lds, s, d, x, y, p.tail, p.done, p.gr);
+        };
+        if (A.uniform3 == 1) launch(spmv_dict3_kernel<ACC, RIDE, BTF, 1>);
+        else if (A.uniform3 == 2) launch(spmv_dict3_kernel<ACC, RIDE, BTF, 2>);
+        else launch(spmv_dict3_kernel<ACC, RIDE, BTF, 3>);
+    });
     return true;
 }
 
@@ -261,30 +223,22 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict3_kernel(DictAr
 #pragma clang fp contract(off)
     if (done && *done) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int bx = (int)blockIdx.x;
-    const int c0 = ((bx & 7) * d.chunks_per_xcd + (bx >> 3) * d.chunks_per_wg);
-    const int c1 = min(min(c0 + d.chunks_per_wg, ((bx & 7) + 1) * d.chunks_per_xcd), d.nchunks);
-    if (c0 >= c1) return;
-    const int last = d.nbrows - 1;
-    auto rowof = [&](int ch) { return min(ch * kDictChunk + (int)threadIdx.x, last); };
-    int tA = (int)d.tid[rowof(c0)];
-    int tB = tA;
+    int c0, c1;
+    if (!dict_chunk_range(d, (int)blockIdx.x, c0, c1)) return;
+    const int tA = (int)d.tid[dict_rowof(d, c0)];
     dict_load_lds(d, (d.nclass + 1) * 9, smem);
-    const int32_t *tlen = reinterpret_cast<const int32_t *>(smem);
-    int2 *tent = reinterpret_cast<int2 *>(smem + 4 * ((d.ntype + 1) & ~1));
-    const double2 *cv = reinterpret_cast<const double2 *>(smem + d.cls_off);
-    dict3_prepare_types(d, tlen, tent, 12);
+    const DictTables T = dict_tables(d, smem);
+    dict_prepare_types<27>(d, T, 12);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(yin), 0, 12 * d.nbrows, 0x00020000);
 
-    Dict3StageF SA, SB;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    const int nq = (c1 - c0) * kD3Groups;
+    auto issue = [&](int tc, int brr, int g, Dict3StageF &S) { dict3_issue_f(d, yr, T.tent, tc, brr, g, S); };
     auto compute = [&](int q, const Dict3StageF &S) {
         const int g = q % kD3Groups;
         if (g == 0) s0 = s1 = s2 = 0.0f;
 #pragma unroll
         for (int j = 0; j < kD3G; ++j) {
-            const double2 *cb = cv + (size_t)S.cls[j] * 9;
+            const double2 *cb = T.cv + (size_t)S.cls[j] * 9;
             s0 = s0 + (float)dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 0), cb[0]) * S.x0[j];
             s0 = s0 + (float)dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 1), cb[1]) * S.x1[j];
             s0 = s0 + (float)dict_decode(dict_field3u<U3>(S.w0[j], S.w1[j], d, 2), cb[2]) * S.x2[j];
@@ -297,27 +251,15 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict3_kernel(DictAr
         }
         if (g != kD3Groups - 1) return;
         const int brc = (c0 + q / kD3Groups) * kDictChunk + (int)threadIdx.x;
-        if (brc > last) return;
+        if (brc >= d.nbrows) return;
         const float s[3] = {s0, s1, s2};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const int64_t row = 3 * (int64_t)brc + r;
-            yout[row] = yin[row] + ((omega * d32[row]) * (x32[row] - s[r]));
+            yout[row] = sweep_update(yin[row], omega, d32[row], x32[row], s[r]);
         }
     };
-    auto chunk_of = [&](int q) { return c0 + q / kD3Groups; };
-
-    dict3_issue_f(d, yr, tent, tA, rowof(c0), 0, SA);
-    for (int q = 0;; q += 2) {
-        tA = (int)d.tid[rowof(chunk_of(q + 2))];
-        dict3_issue_f(d, yr, tent, tB, rowof(chunk_of(q + 1)), (q + 1) % kD3Groups, SB);
-        compute(q, SA);
-        if (q + 1 >= nq) break;
-        tB = (int)d.tid[rowof(chunk_of(q + 3))];
-        dict3_issue_f(d, yr, tent, tA, rowof(chunk_of(q + 2)), (q + 2) % kD3Groups, SA);
-        compute(q + 1, SB);
-        if (q + 2 >= nq) break;
-    }
+    dict3_two_stage<Dict3StageF>(d, c0, c1, tA, issue, compute);
 }
 
 bool jacobi_sweep_f32_dict3(const DictDev &A, const float *d32, float omega, const float *x32, const float *yin, float *yout,

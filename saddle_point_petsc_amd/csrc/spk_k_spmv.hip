@@ -36,22 +36,15 @@ template <bool NT, int TILE, int T, bool RIDE>
 __global__ __launch_bounds__(T) void spmv_stream_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
     const double *__restrict__ val, const int32_t *__restrict__ tile_row, int ntiles,
-    int tiles_per_xcd, const double *__restrict__ x, double *__restrict__ y,
-    const int32_t *__restrict__ bt_rowptr, const int32_t *__restrict__ bt_colidx,
-    const double *__restrict__ bt_val, const double *__restrict__ lam, int accumulate, OffDiag od,
+    int tiles_per_xcd, const double *__restrict__ x, double *__restrict__ y, RowTail tail, int accumulate,
     const int32_t *__restrict__ done, GivensRider gr)
 {
-    if (done && *done) return;
     __shared__ double prod[TILE + 8];
-    if (RIDE && blockIdx.x == 0) {  // the rider: a pending Givens step beside the tiles (its LDS: the product buffer)
-        givens_rider(gr, prod);
-        return;
-    }
-    // workgroups b, b+8, ... share an XCD (round-robin dispatch): give each XCD
-    // a contiguous run of row tiles so the x window stays in ITS L2.
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    const int t = (bx & 7) * tiles_per_xcd + (bx >> 3);
+    const int bx = product_prologue<RIDE>(done, gr, prod);  // (the rider's LDS: the product buffer)
+    if (bx < 0) return;
+    const int t = xcd_tile(bx, tiles_per_xcd);
     if ((bx >> 3) >= tiles_per_xcd || t >= ntiles) return;
+    const bool bt = tail.bt_rowptr != nullptr;
 
     const int r0 = tile_row[t], r1 = tile_row[t + 1];
     const int nz0 = rowptr[r0], nz1 = rowptr[r1];
@@ -70,10 +63,7 @@ __global__ __launch_bounds__(T) void spmv_stream_kernel(
         if (threadIdx.x == 0) {
             out1 = 0.0;
             for (int j = 0; j < T / 64; ++j) out1 += red[j];
-            if (od.rowptr)
-                for (int k = od.rowptr[r0]; k < od.rowptr[r0 + 1]; ++k) out1 += od.val[k] * od.xg[od.colidx[k]];
-            if (bt_rowptr)
-                for (int k = bt_rowptr[r0]; k < bt_rowptr[r0 + 1]; ++k) out1 += bt_val[k] * lam[bt_colidx[k]];
+            row_tail_add(tail, r0, out1, bt);
             if (accumulate) out1 += y[r0];
             y[r0] = out1;
         }
@@ -121,10 +111,7 @@ __global__ __launch_bounds__(T) void spmv_stream_kernel(
     if (r < r1) {
         double s = 0.0;
         for (int k = k0; k < k1; ++k) s += prod[k];
-        if (od.rowptr)  // off-rank columns of this row (ghost values already exchanged)
-            for (int k = od.rowptr[r]; k < od.rowptr[r + 1]; ++k) s += od.val[k] * od.xg[od.colidx[k]];
-        if (bt_rowptr)
-            for (int k = bt_rowptr[r]; k < bt_rowptr[r + 1]; ++k) s += bt_val[k] * lam[bt_colidx[k]];
+        row_tail_add(tail, r, s, bt);
         if (accumulate) s += yacc;  // y pre-loaded with B^T lambda by the fused PC kernel
         y[r] = s;
     }
@@ -133,21 +120,14 @@ __global__ __launch_bounds__(T) void spmv_stream_kernel(
 void spmv(const CsrDev &A, const double *x, double *y, const CsrDev *bt, const double *lam,
           const int32_t *done, hipStream_t s, bool accumulate, const OffDiag *od, const GivensRider *rider)
 {
-    if (A.nrows == 0) {
-        if (rider) givens_rider_alone(*rider, done, s);
-        return;
-    }
+    if (product_is_empty(A.nrows, rider, done, s)) return;
+    const ProductLaunch p = make_product_launch(bt, lam, od, rider, done, accumulate);
     const int tpx = (A.ntiles + 7) / 8;
-    const OffDiag o = od ? *od : OffDiag{nullptr, nullptr, nullptr, nullptr};
-    const GivensRider gr = rider ? *rider : no_rider();
-    if (rider)
-        SPK_LAUNCH_PRODUCT((spmv_stream_kernel<false, kCsrTile, kThreads, true>), dim3(tpx * 8 + 1), dim3(kThreads), 0, s,
-                           A.rowptr.p, A.colidx.p, A.val.p, A.tile_row.p, A.ntiles, tpx, x, y, bt ? bt->rowptr.p : nullptr,
-                           bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, accumulate ? 1 : 0, o, done, gr);
-    else
-        SPK_LAUNCH_PRODUCT((spmv_stream_kernel<false, kCsrTile, kThreads, false>), dim3(tpx * 8), dim3(kThreads), 0, s,
-                           A.rowptr.p, A.colidx.p, A.val.p, A.tile_row.p, A.ntiles, tpx, x, y, bt ? bt->rowptr.p : nullptr,
-                           bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, accumulate ? 1 : 0, o, done, gr);
+    dispatch_product(p.acc, p.ride, p.bt, [&](auto, auto ride, auto) {  // (ACC and B^T rows: run-time arguments here)
+        SPK_LAUNCH_PRODUCT((spmv_stream_kernel<false, kCsrTile, kThreads, ride.value>), dim3(tpx * 8 + p.nride), dim3(kThreads), 0,
+                           s, A.rowptr.p, A.colidx.p, A.val.p, A.tile_row.p, A.ntiles, tpx, x, y, p.tail, p.acc ? 1 : 0, p.done,
+                           p.gr);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -180,18 +160,12 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr_kernel(
     const int32_t *__restrict__ browptr, const int32_t *__restrict__ bcol,
     const double *__restrict__ vtop, const double *__restrict__ vbot,
     const int32_t *__restrict__ tile_brow, int ntiles, int tiles_per_xcd,
-    const double *__restrict__ x, double *__restrict__ y, const int32_t *__restrict__ bt_rowptr,
-    const int32_t *__restrict__ bt_colidx, const double *__restrict__ bt_val,
-    const double *__restrict__ lam, OffDiag od, const int32_t *__restrict__ done, GivensRider gr)
+    const double *__restrict__ x, double *__restrict__ y, RowTail tail, const int32_t *__restrict__ done, GivensRider gr)
 {
-    if (done && *done) return;
     __shared__ double prod[kBTile * 4];
-    if (RIDE && blockIdx.x == 0) {  // the rider: a pending Givens step beside the tiles (its LDS: the product buffer)
-        givens_rider(gr, prod);
-        return;
-    }
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    const int t = (bx & 7) * tiles_per_xcd + (bx >> 3);
+    const int bx = product_prologue<RIDE>(done, gr, prod);  // (the rider's LDS: the product buffer)
+    if (bx < 0) return;
+    const int t = xcd_tile(bx, tiles_per_xcd);
     if (t >= ntiles) return;
     const int br0 = tile_brow[t], br1 = tile_brow[t + 1];
     const int b0 = browptr[br0], b1 = browptr[br1];
@@ -216,10 +190,7 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr_kernel(
         if (threadIdx.x < 2) {
             const int r = 2 * br0 + threadIdx.x;
             double o = ((red[4 * threadIdx.x] + red[4 * threadIdx.x + 1]) + red[4 * threadIdx.x + 2]) + red[4 * threadIdx.x + 3];
-            if (od.rowptr)
-                for (int k = od.rowptr[r]; k < od.rowptr[r + 1]; ++k) o += od.val[k] * od.xg[od.colidx[k]];
-            if (bt_rowptr)
-                for (int k = bt_rowptr[r]; k < bt_rowptr[r + 1]; ++k) o += bt_val[k] * lam[bt_colidx[k]];
+            row_tail_add(tail, r, o, BT);
             if (ACC) o += y[r];
             y[r] = o;
         }
@@ -251,22 +222,9 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr_kernel(
             bo[i] = ld2s<NT>(vbot, b0 + q);
         }
     }
-    // B^T lambda of this row (MatMult on the nest operator: the restart's true residual, spk_mult): its first entries
-    // are fetched now, behind the matrix stream, not at the end of the kernel (1024^2: 80.2 us against 68.5 for the
-    // product without them); a longer row takes the rest in the row phase
-    constexpr int kBtPre = 4;
-    int kb0 = 0, kb1 = 0;
-    double btv[kBtPre], btl[kBtPre];
-    if (BT && rowok) {
-        kb0 = bt_rowptr[2 * br0 + lr];
-        kb1 = bt_rowptr[2 * br0 + lr + 1];
-#pragma unroll
-        for (int j = 0; j < kBtPre; ++j) {
-            const bool in = kb0 + j < kb1;
-            btv[j] = in ? bt_val[kb0 + j] : 0.0;
-            btl[j] = in ? lam[bt_colidx[kb0 + j]] : 0.0;
-        }
-    }
+    // B^T lambda of this row (MatMult on the nest operator: the restart's true residual, spk_mult): requested now (BtPre)
+    BtPre pre;
+    if (BT && rowok) pre.load(tail, 2 * br0 + lr);
 #pragma unroll
     for (int i = 0; i < kSteps; ++i) {
         const int q = i * kThreads + threadIdx.x;
@@ -292,14 +250,8 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr_kernel(
             s += p.y;
         }
         const int r = 2 * br0 + lr;
-        if (od.rowptr)  // off-rank columns of this row (ghost values already exchanged)
-            for (int k = od.rowptr[r]; k < od.rowptr[r + 1]; ++k) s += od.val[k] * od.xg[od.colidx[k]];
-        if (BT) {
-#pragma unroll
-            for (int j = 0; j < kBtPre; ++j)
-                if (kb0 + j < kb1) s += btv[j] * btl[j];
-            for (int k = kb0 + kBtPre; k < kb1; ++k) s += bt_val[k] * lam[bt_colidx[k]];
-        }
+        row_tail_add(tail, r, s, false);
+        if (BT) pre.add(tail, s);
         if (ACC) s += yacc;
         y[r] = s;
     }
@@ -308,32 +260,15 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr_kernel(
 void spmv_bcsr(const BcsrDev &A, const double *x, double *y, const CsrDev *bt, const double *lam,
                const int32_t *done, hipStream_t s, bool accumulate, const OffDiag *odp, const GivensRider *rider)
 {
-    if (A.nbrows == 0) {
-        if (rider) givens_rider_alone(*rider, done, s);
-        return;
-    }
+    if (product_is_empty(A.nbrows, rider, done, s)) return;
+    const ProductLaunch p = make_product_launch(bt, lam, odp, rider, done, accumulate);
     const int tpx = (A.ntiles + 7) / 8;
-    const OffDiag od = odp ? *odp : OffDiag{nullptr, nullptr, nullptr, nullptr};
-    const GivensRider gr = rider ? *rider : no_rider();
-    const int nride = rider ? 1 : 0;
     // non-temporal loads on the matrix planes (read once per SpMV): 70.7 -> 61.3 us in the same run
     // (the rider is a template flag: the plain product keeps its registers and its 16 KB of LDS)
-#define SPK_LAUNCH_BCSR(ACC, RIDE, BTF)                                                                                         \
-    SPK_LAUNCH_PRODUCT((spmv_bcsr_kernel<true, ACC, RIDE, BTF>), dim3(tpx * 8 + nride), dim3(kThreads), 0, s, A.browptr.p, A.bcol.p, \
-                       A.vtop.p, A.vbot.p, A.tile_brow.p, A.ntiles, tpx, x, y, bt ? bt->rowptr.p : nullptr,                \
-                       bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od, done, gr)
-    if (bt) {   // (MatMult on the nest operator: never the iteration's launch, no rider)
-        if (rider) fail(SPK_ERR_ARG, "spmv_bcsr: B^T rows and a rider in one launch");
-        if (accumulate) SPK_LAUNCH_BCSR(true, false, true);
-        else SPK_LAUNCH_BCSR(false, false, true);
-    } else if (accumulate) {
-        if (rider) SPK_LAUNCH_BCSR(true, true, false);
-        else SPK_LAUNCH_BCSR(true, false, false);
-    } else {
-        if (rider) SPK_LAUNCH_BCSR(false, true, false);
-        else SPK_LAUNCH_BCSR(false, false, false);
-    }
-#undef SPK_LAUNCH_BCSR
+    dispatch_product(p.acc, p.ride, p.bt, [&](auto acc, auto ride, auto btf) {
+        SPK_LAUNCH_PRODUCT((spmv_bcsr_kernel<true, acc.value, ride.value, btf.value>), dim3(tpx * 8 + p.nride), dim3(kThreads), 0, s,
+                           A.browptr.p, A.bcol.p, A.vtop.p, A.vbot.p, A.tile_brow.p, A.ntiles, tpx, x, y, p.tail, p.done, p.gr);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -360,18 +295,12 @@ template <bool ACC, bool RIDE>
 __global__ __launch_bounds__(kThreads) void spmv_bcsr3_kernel(
     const int32_t *__restrict__ browptr, const int32_t *__restrict__ bcol, const double *__restrict__ v, int64_t ldp,
     const int32_t *__restrict__ tile_brow, int ntiles, int tiles_per_xcd, const double *__restrict__ x,
-    double *__restrict__ y, const int32_t *__restrict__ bt_rowptr, const int32_t *__restrict__ bt_colidx,
-    const double *__restrict__ bt_val, const double *__restrict__ lam, OffDiag od, const int32_t *__restrict__ done,
-    GivensRider gr)
+    double *__restrict__ y, RowTail tail, const int32_t *__restrict__ done, GivensRider gr)
 {
-    if (done && *done) return;
     __shared__ double prod[kB3Tile * 9];
-    if (RIDE && blockIdx.x == 0) {  // the rider: a pending Givens step beside the tiles (its LDS: the product buffer)
-        givens_rider(gr, prod);
-        return;
-    }
-    const int bx = (int)blockIdx.x - (RIDE ? 1 : 0);
-    const int t = (bx & 7) * tiles_per_xcd + (bx >> 3);
+    const int bx = product_prologue<RIDE>(done, gr, prod);  // (the rider's LDS: the product buffer)
+    if (bx < 0) return;
+    const int t = xcd_tile(bx, tiles_per_xcd);
     if (t >= ntiles) return;
     const int br0 = tile_brow[t], br1 = tile_brow[t + 1];
     const int b0 = browptr[br0], b1 = browptr[br1];
@@ -397,10 +326,7 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr3_kernel(
         if (threadIdx.x < 3) {
             const int r = 3 * br0 + threadIdx.x;
             double o = ((red[4 * threadIdx.x] + red[4 * threadIdx.x + 1]) + red[4 * threadIdx.x + 2]) + red[4 * threadIdx.x + 3];
-            if (od.rowptr)
-                for (int k = od.rowptr[r]; k < od.rowptr[r + 1]; ++k) o += od.val[k] * od.xg[od.colidx[k]];
-            if (bt_rowptr)
-                for (int k = bt_rowptr[r]; k < bt_rowptr[r + 1]; ++k) o += bt_val[k] * lam[bt_colidx[k]];
+            row_tail_add(tail, r, o, tail.bt_rowptr != nullptr);
             if (ACC) o += y[r];
             y[r] = o;
         }
@@ -445,10 +371,7 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr3_kernel(
             s += p[2];
         }
         const int r = 3 * br0 + lr;
-        if (od.rowptr)  // off-rank columns of this row (ghost values already exchanged)
-            for (int k = od.rowptr[r]; k < od.rowptr[r + 1]; ++k) s += od.val[k] * od.xg[od.colidx[k]];
-        if (bt_rowptr)
-            for (int k = bt_rowptr[r]; k < bt_rowptr[r + 1]; ++k) s += bt_val[k] * lam[bt_colidx[k]];
+        row_tail_add(tail, r, s, tail.bt_rowptr != nullptr);
         if (ACC) s += yacc;
         y[r] = s;
     }
@@ -457,26 +380,13 @@ __global__ __launch_bounds__(kThreads) void spmv_bcsr3_kernel(
 void spmv_bcsr3(const Bcsr3Dev &A, const double *x, double *y, const CsrDev *bt, const double *lam,
                 const int32_t *done, hipStream_t s, bool accumulate, const OffDiag *odp, const GivensRider *rider)
 {
-    if (A.nbrows == 0) {
-        if (rider) givens_rider_alone(*rider, done, s);
-        return;
-    }
+    if (product_is_empty(A.nbrows, rider, done, s)) return;
+    const ProductLaunch p = make_product_launch(bt, lam, odp, rider, done, accumulate);
     const int tpx = (A.ntiles + 7) / 8;
-    const OffDiag od = odp ? *odp : OffDiag{nullptr, nullptr, nullptr, nullptr};
-    const GivensRider gr = rider ? *rider : no_rider();
-    const int nride = rider ? 1 : 0;
-#define SPK_LAUNCH_B3(ACC, RIDE)                                                                                          \
-    SPK_LAUNCH_PRODUCT((spmv_bcsr3_kernel<ACC, RIDE>), dim3(tpx * 8 + nride), dim3(kThreads), 0, s, A.browptr.p, A.bcol.p, \
-                       A.v.p, A.ldp, A.tile_brow.p, A.ntiles, tpx, x, y, bt ? bt->rowptr.p : nullptr,                    \
-                       bt ? bt->colidx.p : nullptr, bt ? bt->val.p : nullptr, lam, od, done, gr)
-    if (accumulate) {
-        if (rider) SPK_LAUNCH_B3(true, true);
-        else SPK_LAUNCH_B3(true, false);
-    } else {
-        if (rider) SPK_LAUNCH_B3(false, true);
-        else SPK_LAUNCH_B3(false, false);
-    }
-#undef SPK_LAUNCH_B3
+    dispatch_product(p.acc, p.ride, p.bt, [&](auto acc, auto ride, auto) {  // (B^T rows: a run-time check here)
+        SPK_LAUNCH_PRODUCT((spmv_bcsr3_kernel<acc.value, ride.value>), dim3(tpx * 8 + p.nride), dim3(kThreads), 0, s, A.browptr.p,
+                           A.bcol.p, A.v.p, A.ldp, A.tile_brow.p, A.ntiles, tpx, x, y, p.tail, p.done, p.gr);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -749,7 +659,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_kernel(
 {
 #pragma clang fp contract(off)  // every product and sum below is rounded on its own (the oracle's float loop)
     if (done && *done) return;
-    const int t = (blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
+    const int t = xcd_tile((int)blockIdx.x, tiles_per_xcd);
     if (t >= ntiles) return;
     __shared__ float prod[kCsrTile + 8];
     const int r0 = tile_row[t], r1 = tile_row[t + 1];
@@ -767,7 +677,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_kernel(
             __syncthreads();
         }
         if (threadIdx.x == 0)
-            yout[r0] = yin[r0] + ((omega * d32[r0]) * (x32[r0] - red[0]));
+            yout[r0] = sweep_update(yin[r0], omega, d32[r0], x32[r0], red[0]);
         return;
     }
     constexpr int kSteps = kCsrTile / (kThreads * 4);
@@ -791,7 +701,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_kernel(
         const int k0 = rowptr[r] - a0, k1 = rowptr[r + 1] - a0;
         float s = 0.0f;
         for (int k = k0; k < k1; ++k) s = (s + prod[k]);
-        yout[r] = yin[r] + ((omega * d32[r]) * (x32[r] - s));
+        yout[r] = sweep_update(yin[r], omega, d32[r], x32[r], s);
     }
 }
 void jacobi_sweep_f32(const CsrDev &A, const float *val32, const float *d32, float omega, const float *x32,
@@ -813,7 +723,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b2_kernel(
 {
 #pragma clang fp contract(off)  // every product and sum below is rounded on its own (the oracle's float loop)
     if (done && *done) return;
-    const int t = (blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
+    const int t = xcd_tile((int)blockIdx.x, tiles_per_xcd);
     if (t >= ntiles) return;
     __shared__ float prod[kBTile * 4];
     const int br0 = tile_brow[t], br1 = tile_brow[t + 1];
@@ -829,7 +739,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b2_kernel(
                 s = (s + (vv[2 * (int64_t)q] * yin[2 * (int64_t)c]));
                 s = (s + (vv[2 * (int64_t)q + 1] * yin[2 * (int64_t)c + 1]));
             }
-            yout[r] = yin[r] + ((omega * d32[r]) * (x32[r] - s));
+            yout[r] = sweep_update(yin[r], omega, d32[r], x32[r], s);
         }
         return;
     }
@@ -862,7 +772,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b2_kernel(
             s = (s + p.y);
         }
         const int r = 2 * br0 + lr;
-        yout[r] = yin[r] + ((omega * d32[r]) * (x32[r] - s));
+        yout[r] = sweep_update(yin[r], omega, d32[r], x32[r], s);
     }
 }
 void jacobi_sweep_f32_b2(const BcsrDev &A, const float *d32, float omega, const float *x32, const float *yin, float *yout,
@@ -883,7 +793,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b3_kernel(
 {
 #pragma clang fp contract(off)  // every product and sum below is rounded on its own (the oracle's float loop)
     if (done && *done) return;
-    const int t = (blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
+    const int t = xcd_tile((int)blockIdx.x, tiles_per_xcd);
     if (t >= ntiles) return;
     __shared__ float prod[kB3Tile * 9];
     const int br0 = tile_brow[t], br1 = tile_brow[t + 1];
@@ -899,7 +809,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b3_kernel(
                 s = (s + (v32[(3 * rr + 1) * ldp + q] * yin[3 * (int64_t)c + 1]));
                 s = (s + (v32[(3 * rr + 2) * ldp + q] * yin[3 * (int64_t)c + 2]));
             }
-            yout[r] = yin[r] + ((omega * d32[r]) * (x32[r] - s));
+            yout[r] = sweep_update(yin[r], omega, d32[r], x32[r], s);
         }
         return;
     }
@@ -931,7 +841,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_b3_kernel(
             s = (s + p[2]);
         }
         const int r = 3 * br0 + lr;
-        yout[r] = yin[r] + ((omega * d32[r]) * (x32[r] - s));
+        yout[r] = sweep_update(yin[r], omega, d32[r], x32[r], s);
     }
 }
 void jacobi_sweep_f32_b3(const Bcsr3Dev &A, const float *d32, float omega, const float *x32, const float *yin, float *yout,
