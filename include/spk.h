@@ -464,6 +464,17 @@ int spk_time_kernel(spk_ctx *ctx, const char *which, int nv, int warmup, int rep
  * re-arms its reduction buffer and stays usable. */
 int spk_debug_finish_timeout(spk_ctx *ctx, int timeout_ms);
 
+/* Test hook: one 512-thread workgroup takes the eight wave sums of each of na values (in[i * 512 + t]: value i of thread
+ * t; na one of VecMDot's accumulator counts 9, 17, 25, 33, 41) with the one-value shuffle chain and with the multi-value
+ * reduction of form 7's launch.  out[w * na + i]: wave w's sum of value i by the chain, out[8 * na + w * na + i] by the
+ * multi-value reduction (16 na doubles).  The two halves must hold the same bits. */
+int spk_debug_wave_sums(spk_ctx *ctx, int na, const double *in, double *out);
+
+/* Developer hook (library built with `make GS_STAMPS=1`; SPK_ERR_STATE otherwise): the phase time stamps of form 7's fused
+ * Gram-Schmidt launches of the solves so far, out[(loc * 256 + workgroup) * 8 + phase] in 100 MHz ticks of one device-wide
+ * counter (64 x 256 x 8 values; per loc the last launch that ran; phases in csrc/spk_gs_stamps.hpp; 0: never written). */
+int spk_debug_gs_stamps(spk_ctx *ctx, uint64_t *out);
+
 /* Test hook: the bound of every device-side wait for another workgroup's data (cross-workgroup reductions, the resident
  * cycle kernel's exchanges) in 100 MHz ticks; 0 restores the default (4 s).  A bound of one tick makes the next solve fail
  * in the MIDDLE of a cycle with SPK_ERR_HIP -- what a lost workgroup would cause -- so that tests can check that the context

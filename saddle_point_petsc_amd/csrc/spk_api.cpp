@@ -541,6 +541,31 @@ int spk_debug_finish_timeout(spk_ctx *c, int timeout_ms)
     SPK_CATCH(c)
 }
 
+int spk_debug_wave_sums(spk_ctx *c, int na, const double *in, double *out)
+{
+    SPK_TRY(c)
+    if (!in || !out) spk::fail(SPK_ERR_ARG, "spk_debug_wave_sums: null argument");
+    if (na < 9 || na > 41 || (na - 1) % 8) spk::fail(SPK_ERR_ARG, "spk_debug_wave_sums: na = %d is none of 9, 17, 25, 33, 41", na);
+    spk::DevBuf<double> din, dout;
+    din.upload(in, (size_t)na * 512);
+    dout.alloc((size_t)16 * na);
+    spk::k::wave_sums_probe(na, din.p, dout.p, c->stream);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    SPK_HIP(hipMemcpy(out, dout.p, (size_t)16 * na * sizeof(double), hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_gs_stamps(spk_ctx *c, uint64_t *out)
+{
+    SPK_TRY(c)
+    if (!out) spk::fail(SPK_ERR_ARG, "spk_debug_gs_stamps: null argument");
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stamps are 64-bit");
+    if (!spk::k::gs_stamps(reinterpret_cast<unsigned long long *>(out)))
+        spk::fail(SPK_ERR_STATE, "spk_debug_gs_stamps: the library was not built with GS_STAMPS=1");
+    SPK_CATCH(c)
+}
+
 int spk_debug_set_wait_bound(spk_ctx *c, uint32_t ticks)
 {
     if (!c) return SPK_ERR_ARG;

@@ -3,6 +3,7 @@
 // Device code only: include from .hip files.
 #pragma once
 #include "spk_internal.hpp"
+#include "spk_gs_stamps.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -28,6 +29,71 @@ __device__ __forceinline__ double wave_sum(double v)
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
     return v;
+}
+
+// N wave sums together, without the LDS permutes of __shfl_down (12 per value above: with N = 41 the chains of a
+// workgroup's eight waves queue ~4 000 of them on one LDS pipe behind the last byte of a reducing pass).  For every
+// value the tree is the one lane 0 of wave_sum's chain produces: lanes 32 apart are added first, then 16, 8, 4, 2, 1.
+// At each level a lane keeps one value of a pair and hands the other one to its partner, so level k works on N / 2^k
+// values: ~N exchange-and-adds instead of 6 N.  Which lane of a pair holds a sum does not matter to its bits (IEEE
+// addition commutes; no NaN payloads are involved).  The moves are v_permlane32_swap / v_permlane16_swap (gfx950) and
+// DPP; xor 4 inside a row is quad_perm [3,2,1,0] followed by row_half_mirror.
+// On return lane l holds the sum of value wave_sum_owner(l) in v[0], where that is below N.
+__device__ __forceinline__ int wave_sum_owner(int lane) { return (int)(__brev((unsigned)lane) >> 26); }
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// SW = 32: the upper half-wave of a trades places with the lower half-wave of b; 16: odd rows of a, even rows of b
+template <int SW>
+__device__ __forceinline__ void lane_swap(double &a, double &b)
+{
+    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
+    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
+    const auto l = SW == 32 ? __builtin_amdgcn_permlane32_swap(alo, blo, false, false) : __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
+    const auto h = SW == 32 ? __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false) : __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
+    a = __hiloint2double((int)h[0], (int)l[0]);
+    b = __hiloint2double((int)h[1], (int)l[1]);
+}
+template <int OFF, int N>
+__device__ __forceinline__ void wave_sum_level(double (&v)[N], int n, int lane)   // n values in, (n + 1) / 2 out
+{
+#pragma unroll
+    for (int j = 0; j < (N + 1) / 2; ++j) {
+        if (2 * j < n) {   // compile-time once unrolled
+            double a = v[2 * j], b = v[2 * j + 1 < n ? 2 * j + 1 : 2 * j];   // an odd one out pairs with itself
+            if (OFF >= 16) {
+                lane_swap<OFF>(a, b);   // lower lanes: a and the partner's a; upper lanes: the partner's b and b
+                v[j] = a + b;
+            } else {
+                const bool up = lane & OFF;
+                const double mine = up ? b : a, give = up ? a : b;
+                double got;
+                if (OFF == 8) got = dpp_move<0x128>(give);                        // row_ror:8
+                else if (OFF == 4) got = dpp_move<0x141>(dpp_move<0x1b>(give));   // quad_perm:[3,2,1,0], row_half_mirror
+                else if (OFF == 2) got = dpp_move<0x4e>(give);                    // quad_perm:[2,3,0,1]
+                else got = dpp_move<0xb1>(give);                                  // quad_perm:[1,0,3,2]
+                v[j] = mine + got;
+            }
+        }
+    }
+}
+template <int N>
+__device__ __forceinline__ void wave_sum_multi(double (&v)[N])
+{
+    static_assert(N >= 1 && N <= 64, "one value per lane at the end");
+    const int lane = threadIdx.x & 63;
+    constexpr int n1 = (N + 1) / 2, n2 = (n1 + 1) / 2, n3 = (n2 + 1) / 2, n4 = (n3 + 1) / 2, n5 = (n4 + 1) / 2;
+    wave_sum_level<32>(v, N, lane);
+    wave_sum_level<16>(v, n1, lane);
+    wave_sum_level<8>(v, n2, lane);
+    wave_sum_level<4>(v, n3, lane);
+    wave_sum_level<2>(v, n4, lane);
+    wave_sum_level<1>(v, n5, lane);
 }
 
 // streamed-once operands: non-temporal 16-byte loads (global_load_dwordx4 ... nt);
@@ -748,14 +814,14 @@ inline WsShape ws_shape(int64_t n2)
 // nothing and compiles to the code without a keep set.
 struct NoKeep {
     static constexpr int KW = 0, KP = 0, KV = 0;
-    static constexpr bool any = false;
+    static constexpr bool any = false, fused = false;
     __device__ __forceinline__ void put(int, int, double2) {}
     __device__ __forceinline__ double2 get(int, int) const { return double2{0.0, 0.0}; }
 };
 template <int T, int U, int KW_, int KP_, int KV_, int KR_>
 struct KeepSet {
     static constexpr int KW = KW_, KP = KP_, KV = KV_, KR = KR_, N = KW_ + KP_ + KV_, KL = N > KR_ ? N - KR_ : 0;
-    static constexpr bool any = N > 0;
+    static constexpr bool any = N > 0, fused = true;   // fused: a KeepSet (an empty one too) is form 7's launch
     double2 r[KR_ > 0 ? KR_ : 1][U];
     double2 *l;   // KL * U * T double2 of LDS
     __device__ __forceinline__ void put(int k, int u, double2 v)
@@ -775,12 +841,15 @@ struct KeepSet {
 // keep: the first tile leaves its operands in the keep set (needs gridDim.x whole tiles in n2).  With split, its kept
 // planes are loaded ONCE: their slots in the groups turn into dead ones and their dot products, the same sums over u of
 // the same values, are added behind the groups.  No order of additions changes.
-template <int NG, int T, int G, bool NT, int U, class Keep = NoKeep>
-__device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t ldv, int nv,
+// FUSED (gs_fused_kernel): gate is the launch's `done` word, requested by the caller and looked at behind the first
+// tile's first loads (a gated workgroup returns true: nothing added, nothing published); the wave sums are taken by
+// wave_sum_multi (the same trees as wave_sum, which mdot_kernel keeps: forms 5 and 7 agree to the bit).
+template <int NG, int T, int G, bool NT, int U, class Keep = NoKeep, bool FUSED = false>
+__device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t ldv, int nv,
                                            const double *__restrict__ V2, int nv1,
                                            const double *__restrict__ w, int64_t n2,
                                            int64_t n_dot, double *__restrict__ partials,
-                                           int with_ww, int split, double *lds, Keep *keep = nullptr)
+                                           int with_ww, int split, double *lds, Keep *keep = nullptr, int32_t gate = 0)
 {
     constexpr int NA = NG * 8 + 1, W = T / kWave, TILE2 = T * U;
     constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
@@ -838,6 +907,13 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
 #pragma unroll
                     for (int u = 0; u < U; ++u) a[v][u] = ld2s<NT>(Vi, live ? idx[u] : 0);
                 }
+                if (FUSED && g0 == 0 && tile == (int64_t)blockIdx.x) {
+                    // the first tile's loads are in flight; the empty statement pins the look at the gate HERE (the test
+                    // is loop-invariant: hoisted ahead of the loop it waits for the gate before the first request)
+                    asm volatile("" : "+v"(gate));
+                    if (__builtin_amdgcn_readfirstlane(gate)) return true;
+                    GS_STAMP_COPY(kGsEntry, kGsEntryRaw);
+                }
 #pragma unroll
                 for (int v = 0; v < G; ++v) {
                     const bool live = g0 + v < nv && !(kpl && g0 + v >= nv1 && ((g0 + v - nv1) >> 1) < KP);
@@ -857,6 +933,7 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
                     }
                     acc[g0 + v] += mk * d;
                 }
+                if (FUSED && g0 == 0 && tile == (int64_t)blockIdx.x) GS_STAMP(kGsFirstLoads);
                 if (KF && g0 < KV) {  // behind the group's sums: a store of a loaded value waits for it
 #pragma unroll
                     for (int v = 0; v < G; ++v) {
@@ -893,10 +970,17 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
     }
     // workgroup sums -> partials[block][i]; w.w goes to slot nv
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (FUSED) GS_STAMP(kGsTilesDone);
+    if (FUSED) {
+        wave_sum_multi(acc);
+        const int i = wave_sum_owner(lane);
+        if (i < NA) lds[wave * NA + i] = acc[0];
+    } else {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const double s = wave_sum(acc[i]);
-        if (lane == 0) lds[wave * NA + i] = s;
+        for (int i = 0; i < NA; ++i) {
+            const double s = wave_sum(acc[i]);
+            if (lane == 0) lds[wave * NA + i] = s;
+        }
     }
     __syncthreads();
     if (threadIdx.x < NA) {
@@ -908,6 +992,8 @@ __device__ __forceinline__ void mdot_tiles(const double *__restrict__ V, int64_t
         if (i < nv) publish(row + i, s);
         else if (i == NA - 1 && with_ww) publish(row + nv, s);
     }
+    if (FUSED) GS_STAMP(kGsPublished);
+    return false;
 }
 
 // Workgroup shape of the reducing vector kernels: big vectors get 512 threads x 4 double2

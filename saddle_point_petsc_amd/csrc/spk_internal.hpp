@@ -413,6 +413,8 @@ void arm_partials(double *p, size_t n, hipStream_t s);
 // test hook: a reduction with a partial that never arrives (see spk_debug_finish_timeout)
 struct Finish;
 void finish_probe(const Finish &f, hipStream_t s);
+// test hook: the wave sums of na x 512 values by wave_sum and by wave_sum_multi (see spk_debug_wave_sums)
+void wave_sums_probe(int na, const double *in, double *out, hipStream_t s);
 
 // where a reducing kernel leaves its result: block partials (armed with the sentinel of the
 // "last block reduces" protocol, spk_device.hpp) and the output slot
@@ -671,8 +673,9 @@ struct IterB {
     KrylovArrays ka;
     int loc;
     int defer_fin;       // publish the partials of ||w'||^2 and leave: the rider of the next product launch reduces them
+    int dead_out;        // the cycle's last iteration: nobody reads w', z~, c~ (x += Z y takes Z_0 .. Z_{mk-1}, r comes from x): not stored
 };
-// Form 7: VecMDot and kernel B in one launch (gs_fused_kernel).  b as for iter_maxpy_uhead (dots unused, defer_fin set,
+// Form 7: VecMDot and kernel B in one launch (gs_fused_kernel).  b as for iter_maxpy_uhead (dots unused; defer_fin set except behind a cycle's last iteration,
 // one rank); MDot's operands below.  Returns the number of partial rows of ||w'||^2 (GivensRider::fin_n).
 struct GsArgs {
     const double *V2;    // planes of B D (parity-interleaved when split)
@@ -687,6 +690,8 @@ struct GsArgs {
 int gs_fused(IterB b, GsArgs g, hipStream_t s);
 int gs_fused_occupancy(int ng, int m, bool keep);   // workgroups of the fused kernel (with / without its keep set) that fit one CU
 int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
+// GS_STAMPS=1 builds: the launches' phase time stamps, 64 iterations x 256 workgroups x 8 (spk_gs_stamps.hpp); false otherwise
+bool gs_stamps(unsigned long long *out);
 // Resident restart cycle (spk_k_resident.hip): ONE launch runs iterations 0 .. mk-1 of a cycle with the basis in registers
 // (single rank, row-type layout with 2x2 blocks, <= 512 block rows per CU, restart <= 30, <= 4 planes of B D).  On entry
 // V0 = v_0 (normalised), V1 = K z_0; Z_1.. are written; the Krylov scalars end up where krylov_cycle_end expects them.

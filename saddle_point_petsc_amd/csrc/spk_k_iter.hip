@@ -23,7 +23,9 @@ namespace k {
 // ---------------------------------------------------------------------------
 // The body of kernel B (iter_maxpy_uhead_kernel, gs_fused_kernel).  scalar_wg: the workgroup that also writes the
 // multiplier entries of w', z~, c~, tb, the Hessenberg column and the multiplier entries' share of ||w'||^2 (a workgroup
-// of its own in kernel B, one of the streaming ones in the fused launch); dots(i): the reduced [h, q] value i.
+// of its own in kernel B, one of the streaming ones in the fused launch); dots(i, j, a, c): the reduced [h, q] values i
+// and j into a and c (an index < 0: none, the value stays) -- in form 7 a wait, so both are requested before either is
+// looked at and every load that does not depend on them is requested first.
 // keep (form 7 only, see KeepSet): the first tile takes w~, the parity planes and V_0 .. V_{KV-1} from the keep set; its
 // loads ahead of the scalar prologue are D^-1 and the first group behind the kept vectors.  Groups, slots past nv and
 // the order of every addition are those of the other tiles.
@@ -111,13 +113,13 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     const double s_w = b.sc[nv - 1];   // w = s_w w~
     if (threadIdx.x < kWave) {
         const int i = threadIdx.x;
-        hi_pre = i < nv ? dots(i) : 0.0;
         sci = i < nv ? b.sc[i] : 0.0;
 #pragma unroll
         for (int r = 0; r < 8; ++r) tbv_pre[r] = (r < m && i < nv) ? b.tb[i * 8 + r] : 0.0;
-        qv_pre = (i < m) ? dots(nv + i) : 0.0;
+        dots(i < nv ? i : -1, i < m ? nv + i : -1, hi_pre, qv_pre);
     }
     if (dn) return;
+    if (Keep::fused) GS_STAMP(kGsTotalsSeen);
     if (threadIdx.x < kWave) {  // lane i owns basis vector i (nv <= 63)
         const int i = threadIdx.x;
         // un-normalised basis: h_i = sc_i s_w (V~_i . w~); the MAXPY coefficient of V~_i and the weight of B D V~_i is h_i sc_i
@@ -156,6 +158,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     double yv[NP];
 #pragma unroll
     for (int r = 0; r < NP; ++r) yv[r] = MP > 0 ? ys[r] : 0.0;
+    if (Keep::fused) GS_STAMP(kGsPrologueDone);
     if (have) {  // w = s_w w~
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -171,9 +174,11 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             double w1 = tus[r];
             if (b.fact == SPK_SCHUR_FULL)
                 for (int q = 0; q < m; ++q) w1 -= b.gram[r * m + q] * ys[q];
-            b.w[b.nl + r] = wraws[r];
-            b.zun[b.nl + r] = ys[r];
-            b.c[b.nl + r] = w1;
+            if (!b.dead_out) {
+                b.w[b.nl + r] = wraws[r];
+                b.zun[b.nl + r] = ys[r];
+                b.c[b.nl + r] = w1;
+            }
             b.tb[(size_t)nv * 8 + r] = tus[r];  // un-normalised: scaled by sc where it is read
             b.wl_out[r] = w1;
         }
@@ -187,6 +192,10 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             // row tiles: this launch ends with its last streaming workgroup -- no publish -> re-read tail
             if (threadIdx.x == 0) publish(b.partials + (size_t)gmain * kPartialLd, lam2);
             if (!is_main) return;   // (the fused launch: this workgroup streams its tiles too)
+        } else if (Keep::fused) {
+            // the fused launch behind the cycle's last iteration: this workgroup streams its tiles first and reduces the
+            // norm behind them, below (lam is dead behind the prologue: it carries the multiplier entries' share there)
+            if (threadIdx.x == 0) lam[0] = lam2;
         } else {
             final_reduce(b.partials, gmain, kPartialLd, 1, red, FinErr{b.err, b.fin_ticks});
             if (threadIdx.x == 0) red[0] = red[0] + lam2;
@@ -321,12 +330,14 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                 }
                 // streamed out past the L2 (non-temporal stores): nobody on this XCD reads them again before the kernel
                 // boundary writes them back anyway (same box, alternating: 512^2 60.6 -> 59.1 us per iteration, 1024^2 203.3 -> 202.1, 1/8 slab 39.3 -> 39.0)
-                st2nt(b.w, i, wv[u]);
-                st2nt(b.zun, i, zz);
-                if (MP > 0) {
-                    cc.x = sv[u].x / dv[u].x;
-                    cc.y = sv[u].y / dv[u].y;
-                    st2nt(b.c, i, cc);
+                if (!b.dead_out) {
+                    st2nt(b.w, i, wv[u]);
+                    st2nt(b.zun, i, zz);
+                    if (MP > 0) {
+                        cc.x = sv[u].x / dv[u].x;
+                        cc.y = sv[u].y / dv[u].y;
+                        st2nt(b.c, i, cc);
+                    }
                 }
                 for (int q = 0; q < b.sr.n; ++q) {
                     const int64_t e = 2 * i - b.sr.r0[q];
@@ -364,6 +375,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     // ||w'||^2 of this workgroup's entries.  The partial goes to slot bx -- the FIRST TILE this workgroup
     // streamed -- so that the reducer adds the partials in tile order whichever way the grid was walked
     // (bit-identical norms with and without the peer-store halo in the same launch)
+    if (Keep::fused) GS_STAMP(kGsBTilesDone);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double sw = wave_sum(nrm);
     if (lane == 0) red[wave] = sw;
@@ -374,12 +386,22 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         for (int j = 0; j < T / kWave; ++j) tsum += red[j];
         publish(b.partials + (size_t)bx * kPartialLd, tsum);
     }
+    if (Keep::fused && (int)blockIdx.x == scalar_wg && !b.defer_fin) {
+        // no product follows the cycle's last iteration, so no rider reduces the norm: kernel B's own order (the partials
+        // in tile order, then the multiplier entries' share), here behind this workgroup's tiles
+        __syncthreads();
+        final_reduce(b.partials, gmain, kPartialLd, 1, red, FinErr{b.err, b.fin_ticks});
+        if (threadIdx.x == 0) b.out[0] = red[0] + lam[0];
+    }
 }
 template <int T, int G, int U, int MP>
 __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
 {
     const int nhalo = b.sr.peer ? (2 * b.sr.nrecv + T - 1) / T : 0;
-    maxpy_uhead_tiles<T, G, U, MP>(b, b.gmain + nhalo, [&](int i) { return b.dots[i]; });
+    maxpy_uhead_tiles<T, G, U, MP>(b, b.gmain + nhalo, [&](int i, int j, double &a, double &c) {
+        if (i >= 0) a = b.dots[i];
+        if (j >= 0) c = b.dots[j];
+    });
 }
 
 int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial rows its norm is spread over (defer_fin)
@@ -435,22 +457,25 @@ int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial 
 // need every workgroup resident at once (gs_fused_occupancy) and are bounded: a wait that gives up raises the context's
 // execution-error word.
 // ---------------------------------------------------------------------------
-struct TotalsWait {   // kernel B's dots(i): spins (bounded) while the totals line still holds the sentinel
+struct TotalsWait {   // kernel B's dots: spins (bounded) while a value it needs still is the sentinel of the totals line
     const double *tot;
     FinErr fe;
-    __device__ double operator()(int i) const
+    __device__ void operator()(int i, int j, double &a, double &c) const
     {
-        double v = peek(tot + i);
-        if (is_sentinel(v)) {
+        // both values are requested together: one round trip behind the reducer's publish, not one per value
+        double v = i >= 0 ? peek(tot + i) : 0.0, q = j >= 0 ? peek(tot + j) : 0.0;
+        if (is_sentinel(v) || is_sentinel(q)) {
             const unsigned long long t0 = wall_clock64();
             do {
                 __builtin_amdgcn_s_sleep(1);
-                v = peek(tot + i);
-            } while (is_sentinel(v) && wall_clock64() - t0 < (unsigned long long)fe.ticks &&
+                if (i >= 0) v = peek(tot + i);
+                if (j >= 0) q = peek(tot + j);
+            } while ((is_sentinel(v) || is_sentinel(q)) && wall_clock64() - t0 < (unsigned long long)fe.ticks &&
                      !(fe.err && __hip_atomic_load(fe.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-            if (is_sentinel(v) && fe.err) __hip_atomic_store(fe.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((is_sentinel(v) || is_sentinel(q)) && fe.err) __hip_atomic_store(fe.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        return v;
+        if (i >= 0) a = v;
+        if (j >= 0) c = q;
     }
 };
 
@@ -476,9 +501,14 @@ __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
     __shared__ double2 klds[Keep::KL > 0 ? Keep::KL * kGsU * kGsT : 1];
     Keep keep;
     keep.l = klds;
+    GS_STAMP(kGsEntryRaw);
     if (blockIdx.x == 0 && threadIdx.x < kWave) publish(g.tot_next + threadIdx.x, __longlong_as_double((long long)kSentinelBits));
-    if (*b.done) return;
-    mdot_tiles<NG, kGsT, kGsG, true, kGsU>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1, g.split, lds, &keep);
+    // the gate is requested here and looked at behind the first tile's first loads (as kernel B's body does): a gated
+    // launch still ends after one round trip, with nothing published and the armed totals line untouched
+    const int32_t dn = __builtin_nontemporal_load(b.done);
+    if (mdot_tiles<NG, kGsT, kGsG, true, kGsU, Keep, true>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1, g.split,
+                                                           lds, &keep, dn))
+        return;
     if (arrive_last(gridDim.x)) {
         const int k = g.cnt + 1;
         final_reduce(g.partials, gridDim.x, kPartialLd, k, lds, g.fe);
@@ -522,11 +552,12 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s)
     const int64_t grid = gs_fused_grid(b.nl);
     const VecShape vs = vec_shape(g.n2);
     if (!grid || vs.T != kGsT || vs.U != kGsU || vs.grid != grid) fail(SPK_ERR_STATE, "gs_fused: not the fat vector shape");
-    if (!b.defer_fin || b.ar.P || b.sr.n || b.sr.peer) fail(SPK_ERR_STATE, "gs_fused: one rank, norm reduced by the rider only");
+    if (b.ar.P || b.sr.n || b.sr.peer) fail(SPK_ERR_STATE, "gs_fused: one rank only");
     if (g.cnt > 40 || b.nv + b.m > kMaxNv - 1) fail(SPK_ERR_ARG, "gs_fused: %d values exceed one reduction", g.cnt);
     b.gmain = (int)grid;
     const int ng = (g.cnt + 7) / 8 > 0 ? (g.cnt + 7) / 8 : 1;
     const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+    gs_stamps_aim(b.loc, (int)grid, s);   // (GS_STAMPS=1 builds only)
 #define SPK_GS_LAUNCH(NG, MP)                                                                                       \
     if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);  \
     else hipLaunchKernelGGL((gs_fused_kernel<NG, MP, false>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);        \
@@ -536,6 +567,8 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s)
     return b.gmain;
 }
 #undef SPK_GS_SWITCH
+
+bool gs_stamps(unsigned long long *out) { return gs_stamps_fetch(out); }
 
 }  // namespace k
 }  // namespace spk

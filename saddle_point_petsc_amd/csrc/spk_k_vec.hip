@@ -34,6 +34,36 @@ void finish_probe(const Finish &f, hipStream_t s)
     hipLaunchKernelGGL(finish_probe_kernel, dim3(4), dim3(256), 0, s, f.partials, f.out, FinErr{f.err, f.fin_ticks});
 }
 
+// Test hook (spk_debug_wave_sums): one 512-thread workgroup takes the eight wave sums of each of NA values (in[i * 512 + t]:
+// value i of thread t) twice, with wave_sum per value and with wave_sum_multi: out[w * NA + i], then the same at 8 NA.
+template <int NA>
+__global__ __launch_bounds__(512) void wave_sums_probe_kernel(const double *__restrict__ in, double *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) acc[i] = in[i * 512 + threadIdx.x];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const double s = wave_sum(acc[i]);
+        if (lane == 0) out[wave * NA + i] = s;
+    }
+    wave_sum_multi(acc);
+    const int i = wave_sum_owner(lane);
+    if (i < NA) out[8 * NA + wave * NA + i] = acc[0];
+}
+void wave_sums_probe(int na, const double *in, double *out, hipStream_t s)
+{
+    switch (na) {
+    case 9: hipLaunchKernelGGL(wave_sums_probe_kernel<9>, dim3(1), dim3(512), 0, s, in, out); break;
+    case 17: hipLaunchKernelGGL(wave_sums_probe_kernel<17>, dim3(1), dim3(512), 0, s, in, out); break;
+    case 25: hipLaunchKernelGGL(wave_sums_probe_kernel<25>, dim3(1), dim3(512), 0, s, in, out); break;
+    case 33: hipLaunchKernelGGL(wave_sums_probe_kernel<33>, dim3(1), dim3(512), 0, s, in, out); break;
+    case 41: hipLaunchKernelGGL(wave_sums_probe_kernel<41>, dim3(1), dim3(512), 0, s, in, out); break;
+    default: fail(SPK_ERR_ARG, "wave_sums_probe: na = %d is none of VecMDot's 9, 17, 25, 33, 41", na);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // B x for the short-and-wide constraint block (4 rows of ~n/2 entries): one
 // workgroup per (column window, row), 16-byte loads of the row's entries in the

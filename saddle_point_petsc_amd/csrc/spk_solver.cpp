@@ -1378,7 +1378,7 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     p.resident = un3 && (form == SPK_ITER_RESIDENT || (form == SPK_ITER_AUTO && !res_env_off)) && res_rank_ok &&
                  c->spmv_format == 1 && c->Adict.ok && c->Adict.bs == 2 && nl % 2 == 0 && mk >= (res_multi ? 3 : 2) &&
                  k::resident_fits(c->Adict, c->num_cus, mk, res_planes);
-    // GS_FUSED (form 7): MDot and kernel B in one launch (every iteration of a cycle but its last) -- one rank, fat vectors,
+    // GS_FUSED (form 7): MDot and kernel B in one launch -- one rank, fat vectors,
     // every workgroup of the launch resident at once; what AUTO takes there
     // (the knob is read per solve, so that a test can flip it between two solves of one context)
     const char *keep_env = getenv("SPK_GS_KEEP");
@@ -1489,8 +1489,9 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
         return true;
     }
     // raw inner products of the un-normalised basis with w~ (and B D w~); scaled where they are consumed
-    // (form 7: inside the launch of kernel B, below -- except behind the last iteration of a cycle)
-    const bool gs = r.p.gsf && loc + 1 < r.mk;
+    // (form 7: inside the launch of kernel B, below)
+    // (the cycle's last iteration too, where its loc + 1 + m values fit MDot's 40 accumulators)
+    const bool gs = r.p.gsf && (loc + 1 < r.mk || loc + 1 + (schur ? r.m : 0) <= 40);
     if (!gs) {
         const bool one = loc + 1 + r.m <= 40, spl = r.p.bpk && one;
         const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + (schur ? r.m : 0), k::kStatArDots) : k::PeerAR{};
@@ -1513,6 +1514,7 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     // (Not with an all-reduce that is a launch of its own, nor behind the last iteration of a cycle.)
     const bool defer = loc + 1 < r.mk && (c->comm->size() == 1 || ar2.P);
     b.defer_fin = defer ? 1 : 0; b.done = done;
+    b.dead_out = loc + 1 == r.mk ? 1 : 0;   // no iteration of this cycle follows
     k::SendRanges sr = c->send_ranges;
     const bool inb = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
     if (sr.n > 0) b.sr = sr;

@@ -253,6 +253,22 @@ class Context:
         """Test hook: a reduction with a partial that never arrives; raises SpkError (SPK_ERR_HIP)."""
         self._chk(lib.spk_debug_finish_timeout(self.h, timeout_ms))
 
+    def debug_wave_sums(self, vals):
+        """Test hook: na x 512 inputs -> (2, 8, na) wave sums, [0] by wave_sum per value, [1] by wave_sum_multi."""
+        vals = np.ascontiguousarray(vals, np.float64)
+        na = vals.shape[0]
+        if vals.shape != (na, 512):
+            raise ValueError("debug_wave_sums: na x 512 values")
+        out = np.zeros(16 * na)
+        self._chk(lib.spk_debug_wave_sums(self.h, na, vals.reshape(-1), out))
+        return out.reshape(2, 8, na)
+
+    def debug_gs_stamps(self):
+        """Developer hook (GS_STAMPS=1 builds): (64, 256, 8) time stamps of the fused Gram-Schmidt launches, 100 MHz ticks."""
+        out = np.zeros(64 * 256 * 8, np.uint64)
+        self._chk(lib.spk_debug_gs_stamps(self.h, out))
+        return out.reshape(64, 256, 8)
+
     def time_products(self, max_launches):
         """HIP events around the product launches of the next solves' iterations (0: off); see include/spk.h"""
         self._chk(lib.spk_debug_time_products(self.h, max_launches))
