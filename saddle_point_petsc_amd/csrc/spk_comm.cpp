@@ -66,6 +66,8 @@ struct spk_local_group {
 };
 
 namespace spk {
+void Comm::memcpy_self(const void *in, void *out, size_t b) { std::memcpy(out, in, b); }
+
 namespace {
 
 // ---------------------------------------------------------------------------

@@ -2,14 +2,18 @@
 //
 // Layering (MI355X-first, not PETSc's):
 //   spk_api.cpp      C ABI entry points, argument checks, error strings
-//   spk_solver.cpp   device-resident FGMRES: the host only ENQUEUES a restart
-//                    cycle; Hessenberg/Givens/convergence live on the device
+//   spk_solver.cpp   the products, PCApply and the device-resident FGMRES: the host only ENQUEUES a
+//                    restart cycle; Hessenberg/Givens/convergence live on the device
+//   spk_operator.cpp KSPSetOperators / KSPSetUp, the device half: uploads, blocked copies, dictionary rounds,
+//                    collectives of the halo plan, Schur diagonal
+//   spk_host.hpp/.cpp the host-pure half of the set-up (no HIP; compiles without ROCm): errors, host arrays, row-slab
+//                    split, ghost numbering, halo plan, dictionary field layout, windows and transpose of B
 //   spk_k_*.hip      hand-written gfx950 kernels (HBM-bound, FP64, no MFMA): spmv (+ set-up, FP32 sweeps), vec (MDot,
 //                    MAXPY, PC pieces), krylov (scalar work, head kernels), iter (fused iteration), comm (peer-store
 //                    launches); spk_device.hpp = the device helpers they share
 //   spk_comm.cpp     collectives: peer-store windows over xGMI on top of RCCL (one process per
 //                    GPU); host-callback and in-process backends for 1-GPU rehearsals
-//   spk_partition.cpp host-only row-slab split + halo plan
+//   spk_partition.cpp C entry points of the row-slab partition and split
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,19 +28,10 @@
 
 #include <hip/hip_ext.h>
 
-#include "../../include/spk.h"
+#include "spk_host.hpp"
 #include "spk_amg.hpp"
 
 namespace spk {
-
-// ---------------------------------------------------------------------------
-// errors
-// ---------------------------------------------------------------------------
-struct Error {
-    int code;
-    std::string msg;
-};
-[[noreturn]] void fail(int code, const char *fmt, ...);
 
 #define SPK_HIP(call)                                                                  \
     do {                                                                               \
@@ -150,8 +145,6 @@ struct Bcsr3Dev {
 // (hashing on the device, then EVERY value decoded and compared bit by bit); a matrix that does not fit (too many classes
 // or types, a row beyond kDictMaxK blocks, deviations that are not small multiples of one power of two or do not fit the
 // words, tables beyond the LDS budget) keeps the plain blocked layout.
-constexpr int kDictMaxK = 32;      // blocks per block row
-namespace k { constexpr int kDictAcrossHost = 1 << 30; }   // = kDictAcross (spk_dict.hpp, device side)
 struct DictDev {
     int bs = 0;
     int32_t nbrows = 0, ntype = 0, nclass = 0, kmax = 0;
@@ -306,38 +299,6 @@ Comm *make_host_comm(int rank, int nranks, const spk_host_comm &cb);
 // wraps `inner` (kept for set-up traffic and as the fallback) with the peer-store backend when every
 // rank can map every other rank's window; returns `inner` itself otherwise (*why says why)
 Comm *make_peer_comm(Comm *inner, int device, std::string *why);
-
-// ---------------------------------------------------------------------------
-// host-side partition results
-// ---------------------------------------------------------------------------
-// uninitialised host array (std::vector would zero hundreds of MB on one thread first)
-template <class T>
-struct HostBuf {
-    std::unique_ptr<T[]> p;
-    size_t n = 0;
-    void alloc(size_t count)
-    {
-        p.reset(new T[count ? count : 1]);
-        n = count;
-    }
-    T *data() { return p.get(); }
-    const T *data() const { return p.get(); }
-    size_t size() const { return n; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-};
-// fn(begin, end, thread) over [0, n) on up to `hardware threads` host threads
-void parallel_for(int64_t n, const std::function<void(int64_t, int64_t, int)> &fn, int max_threads = 0);
-
-struct SplitCsr {
-    HostBuf<int32_t> d_rowptr, d_colidx, o_rowptr, o_colidx;
-    HostBuf<double> d_val, o_val;
-    std::vector<int32_t> garray;
-    bool bad_column = false;  // a column outside [0, ncols_global)
-    int32_t bad_value = 0;
-};
-void split_csr(int64_t row_begin, int32_t nrows_local, const int32_t *rowptr,
-               const int32_t *colidx, const double *val, SplitCsr &out, int64_t ncols_global = -1);
 
 // ---------------------------------------------------------------------------
 // Krylov state that lives in device memory (one per context)
@@ -976,7 +937,7 @@ void a_mult(spk_ctx *c, const double *x, double *y, const CsrDev *bt, const doub
             const k::OffDiag *od, const k::GivensRider *rider = nullptr);
 void op_mult(spk_ctx *c, const double *x, double *y, const int32_t *done, bool halo_done = false, bool reuse_bt = false);
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done);
-void pc_setup(spk_ctx *c, int pc_type, int schur_fact);
+void pc_setup(spk_ctx *c, int pc_type, int schur_fact);   // (spk_operator.cpp, like set_block below)
 // multigrid (spk_amg.cpp): the host hierarchy from the context's A00 (single rank) and its upload; one V-cycle,
 // mode 0: y = V x, mode 1: y -= V x
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);

@@ -679,7 +679,7 @@ bool resident_fits(const DictDev &A, int num_cus, int mk, int np)
     return resident_lds_bytes(A, res_threads(rpw)) <= 160 * 1024;
 }
 
-// host side: arguments checked by the caller (spk_solver.cpp: resident_fits)
+// host side: arguments checked by the caller (spk_operator.cpp: resident_fits)
 bool cycle_resident(const DictDev &A, int num_cus, ResidentArgs r, const int32_t *done, hipStream_t s)
 {
     const int np = r.m == 0 ? 0 : (r.packed ? r.m / 2 : r.m);

@@ -1,4 +1,5 @@
-// spk_solver.cpp -- operator, preconditioner and the device-resident FGMRES.
+// spk_solver.cpp -- applying the operator and the preconditioner, and the device-resident FGMRES
+// (their set-up: spk_operator.cpp).
 //
 // Replaces what executes below KSPSolve(ksp, f, *u) at
 // /root/reference/src/SaddlePointProblem.c:70 when the reference is run with
@@ -117,308 +118,6 @@ void spk_ctx::upload_staged(void *dst, const void *src, size_t bytes)
 
 namespace spk {
 
-// ---------------------------------------------------------------------------
-// KSPSetOperators: upload one block (SaddlePointProblem.c:66; the nest at :45-60)
-// ---------------------------------------------------------------------------
-// host array -> fresh device buffer through the pinned staging pipeline (large arrays), pad zeroed
-template <class T>
-static void up(spk_ctx *c, DevBuf<T> &d, const T *h, size_t count, size_t pad)
-{
-    d.alloc_raw(count, pad);
-    c->upload_staged(d.p, h, count * sizeof(T));
-}
-
-template <class VR, class VI, class VD>
-static void upload_csr(spk_ctx *c, CsrDev &D, int32_t nrows, int32_t ncols, const VR &rowptr, const VI &colidx, const VD &val,
-                       bool tiles)
-{
-    D.nrows = nrows;
-    D.ncols = ncols;
-    D.nnz = (int64_t)colidx.size();
-    up(c, D.rowptr, rowptr.data(), rowptr.size(), 8);
-    up(c, D.colidx, colidx.data(), colidx.size(), 16);
-    up(c, D.val, val.data(), val.size(), 16);
-    if (tiles) {
-        std::vector<int32_t> tr;
-        k::build_tiles(rowptr.data(), nrows, tr);
-        D.ntiles = (int32_t)tr.size() - 1;
-        D.tile_row.upload(tr.data(), tr.size(), 8);
-    }
-}
-
-// Collective agreement on a set-up step (KSPSetOperators is collective, as in PETSc): every rank
-// reports whether its LOCAL part succeeded; when any rank failed, ALL ranks throw -- the failing one its
-// own message, the others a note naming it -- so nobody is left waiting inside the next collective.
-static void agree_or_fail(spk_ctx *c, const Error *mine, const char *step)
-{
-    const int P = c->comm->size();
-    if (P > 1) {
-        std::vector<int32_t> all((size_t)P, 0);
-        const int32_t ok = mine ? 0 : 1;
-        c->comm->host_allgather(&ok, all.data(), sizeof ok);
-        if (!mine)
-            for (int r = 0; r < P; ++r)
-                if (!all[(size_t)r])
-                    fail(SPK_ERR_COMM, "%s: rank %d failed its local part; the collective set-up is abandoned on every rank", step, r);
-    }
-    if (mine) throw *mine;
-}
-
-// Row types + deviation codes over the blocked copy just built (DictDev, spk_internal.hpp): block classes, then row
-// types, proposed by hashing on the device; granule and range of every class entry; codes; every value decoded and compared
-// bit by bit.  Leaves Adict.ok = false (the blocked kernels stay) for matrices that do not fit.  brp: the block row
-// pointers on the host.
-static void build_dict(spk_ctx *c, int bs, const int32_t *brp)
-{
-    DictDev &D = c->Adict;
-    D.ok = false;
-    D.tid.release(); D.tab.release(); D.cls.release(); D.fld.release(); D.codes.release(); D.zpad.release();
-    const char *fmt = getenv("SPK_SPMV_FORMAT");
-    if (fmt && (!strcmp(fmt, "csr") || !strcmp(fmt, "bcsr"))) return;
-    static const bool verbose = getenv("SPK_DICT_VERBOSE") != nullptr;
-    auto refuse = [&](const char *why, long a = 0, long b = 0) {
-        D.tid.release(); D.tab.release(); D.cls.release(); D.fld.release(); D.codes.release(); D.zpad.release();
-        if (verbose) fprintf(stderr, "[spk] row types + codes refused: %s (%ld, %ld)\n", why, a, b);
-    };
-    hipStream_t s = c->stream;
-    const int32_t nbr = bs == 2 ? c->Ab.nbrows : c->Ab3.nbrows;
-    const int64_t nb = bs == 2 ? c->Ab.nblocks : c->Ab3.nblocks;
-    const int32_t *browptr = bs == 2 ? c->Ab.browptr.p : c->Ab3.browptr.p, *bcol = bs == 2 ? c->Ab.bcol.p : c->Ab3.bcol.p;
-    const double *v0 = bs == 2 ? c->Ab.vtop.p : c->Ab3.v.p, *v1 = bs == 2 ? c->Ab.vbot.p : nullptr;
-    const int64_t ldp = bs == 2 ? 0 : c->Ab3.ldp;
-    const int bb = bs * bs;
-    if (nbr == 0 || nb == 0 || nb > INT32_MAX) return refuse("empty or too many blocks", nbr, (long)nb);
-    DevBuf<unsigned long long> keys, dmax;
-    DevBuf<int32_t> rep, slot, ctl, slot2id_d, rep_d, bad, gexp;
-    keys.alloc_raw(k::kDictSlots);
-    rep.alloc_raw(k::kDictSlots);
-    ctl.alloc_raw(4);
-    bad.alloc(4);
-    slot2id_d.alloc_raw(k::kDictSlots);
-    rep_d.alloc_raw(std::max(k::kDictMaxPat, k::kDictMaxBlk));
-    std::vector<unsigned long long> hk(k::kDictSlots);
-    std::vector<int32_t> hr(k::kDictSlots), s2i(k::kDictSlots), reps;
-    int32_t hctl[4];
-    // one round of "hash, read the table back, number the classes by their first member": returns the class count or -1
-    auto classes = [&]() -> int {
-        SPK_HIP(hipMemcpyAsync(hctl, ctl.p, sizeof hctl, hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipMemcpyAsync(hk.data(), keys.p, sizeof(unsigned long long) * k::kDictSlots, hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipMemcpyAsync(hr.data(), rep.p, sizeof(int32_t) * k::kDictSlots, hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipStreamSynchronize(s));
-        if (hctl[1]) return -1;
-        std::vector<std::pair<int32_t, int32_t>> used;   // (first member, slot)
-        for (int i = 0; i < k::kDictSlots; ++i)
-            if (hk[(size_t)i]) used.push_back({hr[(size_t)i], i});
-        std::sort(used.begin(), used.end());
-        std::fill(s2i.begin(), s2i.end(), -1);
-        reps.clear();
-        for (size_t i = 0; i < used.size(); ++i) {
-            s2i[(size_t)used[i].second] = (int32_t)i;
-            reps.push_back(used[i].first);
-        }
-        SPK_HIP(hipMemcpyAsync(slot2id_d.p, s2i.data(), sizeof(int32_t) * k::kDictSlots, hipMemcpyHostToDevice, s));
-        SPK_HIP(hipMemcpyAsync(rep_d.p, reps.data(), sizeof(int32_t) * reps.size(), hipMemcpyHostToDevice, s));
-        SPK_HIP(hipStreamSynchronize(s));
-        return (int)reps.size();
-    };
-    auto reset = [&]() {
-        SPK_HIP(hipMemsetAsync(keys.p, 0, sizeof(unsigned long long) * k::kDictSlots, s));
-        SPK_HIP(hipMemsetAsync(rep.p, 0x7f, sizeof(int32_t) * k::kDictSlots, s));
-        SPK_HIP(hipMemsetAsync(ctl.p, 0, sizeof(int32_t) * 4, s));
-    };
-    // ---- block classes: blocks equal up to ~1e-6 absolute; base = the first member; granule and range per entry
-    slot.alloc_raw((size_t)nb, 8);
-    reset();
-    k::dict_hash_blocks(bs, v0, v1, ldp, nb, keys.p, rep.p, slot.p, ctl.p, k::kDictMaxBlk, s);
-    const int ncls = classes();
-    if (ncls <= 0) return refuse("block classes beyond the table", hctl[0], hctl[1]);
-    D.cls.alloc_raw((size_t)(ncls + 1) * bb * 2, 8);
-    gexp.alloc_raw((size_t)ncls * bb, 8);
-    dmax.alloc((size_t)ncls * bb, 8);
-    SPK_HIP(hipMemsetAsync(gexp.p, 0x7f, sizeof(int32_t) * (size_t)ncls * bb, s));
-    k::dict_class_stats(bs, v0, v1, ldp, nb, rep_d.p, ncls, slot2id_d.p, slot.p, D.cls.p, gexp.p, dmax.p, bad.p, s);   // slot[q] := class
-    std::vector<int32_t> hg((size_t)ncls * bb);
-    std::vector<unsigned long long> hm((size_t)ncls * bb);
-    std::vector<double> hcls((size_t)(ncls + 1) * bb * 2, 0.0);   // (the null class behind the found ones: zeros)
-    int32_t hbad = 1;
-    SPK_HIP(hipMemcpyAsync(hg.data(), gexp.p, sizeof(int32_t) * hg.size(), hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipMemcpyAsync(hm.data(), dmax.p, sizeof(unsigned long long) * hm.size(), hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipMemcpyAsync(hcls.data(), D.cls.p, sizeof(double) * (size_t)ncls * bb * 2, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipMemcpyAsync(&hbad, bad.p, sizeof hbad, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    if (hbad) return refuse("a deviation from its class base is not exactly representable");
-    // bit fields: entry (class, e) gets the width its largest deviation needs (two's complement), the fields of a block are
-    // packed into one 64-bit word (2x2 blocks) or two (3x3: a field never straddles the words)
-    std::vector<int32_t> hfld((size_t)(ncls + 1) * bb, 1 << 8);   // (null class: one bit at offset 0)
-    std::vector<int> hwid((size_t)ncls * bb, 1);
-    std::vector<double> hscale((size_t)ncls * bb, 1.0);
-    for (int i = 0; i < ncls * bb; ++i) {
-        if (hg[(size_t)i] < 0x7f000000) {   // some member deviates: granule = the finest bit in use
-            if (hg[(size_t)i] < -1000 || hg[(size_t)i] > 1000) return refuse("deviation granule out of range", i, hg[(size_t)i]);
-            const double scale = std::ldexp(1.0, hg[(size_t)i]);
-            double mag;
-            std::memcpy(&mag, &hm[(size_t)i], sizeof mag);
-            const double kabs = mag / scale;
-            if (!(kabs <= 1.0e9)) return refuse("a class entry scatters beyond 31-bit codes", i, (long)hg[(size_t)i]);
-            int width = 2;
-            while ((double)((1ll << (width - 1)) - 1) < kabs) ++width;
-            hwid[(size_t)i] = width;
-            hscale[(size_t)i] = scale;
-        }
-    }
-    // 2x2: one layout for all classes where the widest need per entry allows it (1024^2: 19 + 13 | 13 + 19 bits)
-    D.uniform = false;
-    if (bs == 2 && !getenv("SPK_DICT_NOUNIFORM")) {
-        int uw[4] = {1, 1, 1, 1};
-        for (int cl = 0; cl < ncls; ++cl)
-            for (int e = 0; e < 4; ++e) uw[e] = std::max(uw[e], hwid[(size_t)cl * 4 + e]);
-        if (uw[0] + uw[1] <= 32 && uw[2] + uw[3] <= 32) {
-            D.uniform = true;
-            for (int e = 0; e < 4; ++e) D.uw[e] = uw[e];
-            const uint32_t f[4] = {0u | ((uint32_t)uw[0] << 8), (uint32_t)(32 - uw[1]) | ((uint32_t)uw[1] << 8),
-                                   0x80000000u | ((uint32_t)uw[2] << 8), 0x80000000u | (uint32_t)(32 - uw[3]) | ((uint32_t)uw[3] << 8)};
-            for (int cl = 0; cl <= ncls; ++cl)   // (the null class too: any field of a zero word decodes to 0)
-                for (int e = 0; e < 4; ++e) hfld[(size_t)cl * 4 + e] = (int32_t)f[e];
-        }
-    }
-    // 3x3: the same idea over the two words of a block; the entries of the second word are one of three fixed sets
-    D.uniform3 = 0;
-    if (bs == 3 && !getenv("SPK_DICT_NOUNIFORM")) {
-        int uw[9];
-        for (int e = 0; e < 9; ++e) {
-            uw[e] = 1;
-            for (int cl = 0; cl < ncls; ++cl) uw[e] = std::max(uw[e], hwid[(size_t)cl * 9 + e]);
-        }
-        for (int split = 1; split <= 3 && !D.uniform3; ++split) {
-            auto in_w1 = [&](int e) { return split == 1 ? e >= 5 : split == 2 ? e >= 4 : (e == 4 || e >= 6); };
-            int used[2] = {0, 0};
-            for (int e = 0; e < 9; ++e) used[in_w1(e) ? 1 : 0] += uw[e];
-            if (used[0] > 64 || used[1] > 64) continue;
-            D.uniform3 = split;
-            int sh[2] = {0, 0};
-            for (int e = 0; e < 9; ++e) {
-                const int wd = in_w1(e) ? 1 : 0;
-                for (int cl = 0; cl <= ncls; ++cl) hfld[(size_t)cl * 9 + e] = sh[wd] | (uw[e] << 8) | (wd << 16);
-                D.u3l[e] = 64 - sh[wd] - uw[e];
-                D.u3r[e] = 32 - uw[e];
-                sh[wd] += uw[e];
-            }
-        }
-    }
-    D.straddle = false;
-    for (int cl = 0; cl < ncls; ++cl) {
-        int used[2] = {0, 0}, word = 0;
-        if (bs == 2 && !D.uniform) {
-            // no packing of this class's fields inside the halves, but 64 bits suffice: back to back, a field across
-            // the halves flagged (the plain kernels extract it with 64-bit shifts)
-            const int *w = &hwid[(size_t)cl * 4];
-            const bool fits_halves = w[0] + w[1] <= 32 && w[2] + w[3] <= 32;
-            if (!fits_halves && w[0] + w[1] + w[2] + w[3] <= 64) {
-                int sh = 0;
-                for (int e = 0; e < 4; ++e) {
-                    const int i = cl * 4 + e;
-                    const bool across = sh < 32 && sh + w[e] > 32;
-                    hfld[(size_t)i] = across ? (int32_t)((uint32_t)sh | ((uint32_t)w[e] << 8) | (uint32_t)k::kDictAcrossHost)
-                                             : (int32_t)((uint32_t)(sh & 31) | ((uint32_t)w[e] << 8) | (sh >= 32 ? 0x80000000u : 0u));
-                    D.straddle = D.straddle || across;
-                    sh += w[e];
-                    hcls[(size_t)2 * i + 1] = hscale[(size_t)i];
-                }
-                continue;
-            }
-        }
-        for (int e = 0; e < bb; ++e) {
-            const int i = cl * bb + e;
-            const double scale = hscale[(size_t)i];
-            const int width = hwid[(size_t)i];
-            if (D.uniform || D.uniform3) {
-                hcls[(size_t)2 * i + 1] = scale;
-                continue;
-            }
-            // 2x2: two 32-bit halves of one word, a field inside one half (hardware bit-field extract); 3x3: two 64-bit words
-            const int cap = bs == 2 ? 32 : 64;
-            if (used[word] + width > cap) ++word;
-            if (word > 1) return refuse("the codes of a block class do not fit its word(s)", cl, used[0] + used[1] + width);
-            hfld[(size_t)i] = bs == 2 ? (int32_t)((uint32_t)used[word] | ((uint32_t)width << 8) | (word ? 0x80000000u : 0u))
-                                      : (used[word] | (width << 8) | (word << 16));
-            used[word] += width;
-            hcls[(size_t)2 * i + 1] = scale;
-        }
-    }
-    SPK_HIP(hipMemcpyAsync(D.cls.p, hcls.data(), sizeof(double) * hcls.size(), hipMemcpyHostToDevice, s));
-    D.fld.alloc_raw((size_t)(ncls + 1) * bb, 8);
-    D.zpad.alloc(8, 8);
-    SPK_HIP(hipMemcpyAsync(D.fld.p, hfld.data(), sizeof(int32_t) * hfld.size(), hipMemcpyHostToDevice, s));
-    // ---- row types
-    DevBuf<int32_t> rslot;
-    rslot.alloc_raw((size_t)nbr, 8);
-    reset();
-    k::dict_hash_rows(browptr, bcol, slot.p, nbr, keys.p, rep.p, rslot.p, ctl.p, k::kDictMaxPat, kDictMaxK, s);
-    const int ntype = classes();
-    if (ntype <= 0) return refuse("row types beyond the table, or a row beyond kDictMaxK blocks", hctl[0], hctl[1]);
-    int kmax = 1;
-    for (int32_t r : reps) kmax = std::max(kmax, brp[(size_t)r + 1] - brp[(size_t)r]);
-    const int tab_ints = ((ntype + 1) & ~1) + 2 * ntype * kmax;
-    const int lds_bytes = ((((4 * tab_ints + 15) & ~15) + 16 * (ncls + 1) * bb + 4 * (ncls + 1) * bb) + 15) & ~15;
-    if (lds_bytes > k::kDictLdsMax) return refuse("tables beyond the LDS budget", lds_bytes, ntype);
-    D.tab.alloc((size_t)tab_ints, 8);
-    D.tid.alloc_raw((size_t)nbr, 64);
-    k::dict_fill_rows(browptr, bcol, slot.p, nbr, rep_d.p, ntype, kmax, slot2id_d.p, rslot.p, D.tab.p, D.tid.p, bad.p, s);
-    std::vector<int32_t> htab((size_t)tab_ints);
-    SPK_HIP(hipMemcpyAsync(htab.data(), D.tab.p, sizeof(int32_t) * htab.size(), hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipMemcpyAsync(&hbad, bad.p, sizeof hbad, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    if (hbad) return refuse("row type verification failed (hash collision)", ntype, ncls);
-    // ---- code planes (DictArgs::plane_off): 2x2 blocks -- positions 2p, 2p+1 side by side in plane p; 3x3 -- plane k
-    const int64_t nbr_pad = ((int64_t)nbr + 15) & ~(int64_t)15;
-    int64_t off = 0;
-    // (the planes are read side by side, row r of each at the same time: a skew of 17 x 256 B per plane keeps planes whose
-    // size is a power of two -- 16 MiB each at 1024^2 -- from landing on one memory channel together)
-    static const int64_t skew = [] { const char *e = getenv("SPK_DICT_SKEW"); return e ? (int64_t)atoll(e) : (int64_t)(17 * 256); }();
-    for (int kk = 0; kk < kDictMaxK; ++kk) {
-        off += kk ? skew : 0;
-        D.plane_off[kk] = off;
-        if (bs == 2) {
-            if (2 * kk + 1 < kmax) off += 16 * nbr_pad;
-            else if (2 * kk < kmax) off += 8 * nbr_pad;
-        } else if (kk < kmax) {
-            off += 16 * nbr_pad;
-        }
-    }
-    D.codes.alloc((size_t)off, 64);
-    D.bs = bs;
-    D.nbrows = nbr;
-    D.nblocks = nb;
-    D.ntype = ntype;
-    D.nclass = ncls;
-    D.kmax = kmax;
-    D.lds_bytes = lds_bytes;
-    D.code_bytes = (int64_t)(bs == 2 ? 8 : 16) * nb;   // bytes of codes one product reads: every stored block once
-    k::dict_encode_verify(D, browptr, bcol, slot.p, v0, v1, ldp, bad.p, s);
-    SPK_HIP(hipMemcpyAsync(&hbad, bad.p, sizeof hbad, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    if (hbad) return refuse("a decoded value differs from the stored one", ntype, ncls);
-    D.ok = true;
-    if (verbose) {
-        int wmax = 0;
-        for (int cl = 0; cl < ncls; ++cl) {
-            int tot = 0;
-            for (int e = 0; e < bb; ++e) tot += (hfld[(size_t)cl * bb + e] >> 8) & 255;
-            wmax = std::max(wmax, tot);
-        }
-        fprintf(stderr, "[spk] row types + codes: %d block rows, %d types (<= %d blocks), %d classes of %d x %d (<= %d bits of codes per block), "
-                        "%d B of LDS, %.1f B of codes per block row%s\n", nbr, ntype, kmax, ncls, bs, bs, wmax, lds_bytes, (double)D.code_bytes / nbr,
-                D.uniform || D.uniform3 ? ", one field layout for all classes" : "");
-        fprintf(stderr, "[spk]   widest need per block entry:");
-        for (int e = 0; e < bb; ++e) {
-            int w = 1;
-            for (int cl = 0; cl < ncls; ++cl) w = std::max(w, hwid[(size_t)cl * bb + e]);
-            fprintf(stderr, " %d", w);
-        }
-        fprintf(stderr, "\n");
-    }
-}
-
 namespace k {
 LaunchTimer &launch_timer()
 {
@@ -443,480 +142,6 @@ void a_mult(spk_ctx *c, const double *x, double *y, const CsrDev *bt, const doub
     else if (c->spmv_format == 2) k::spmv_bcsr3(c->Ab3, x, y, bt, lam, done, s, accumulate, od, rider);
     else if (c->spmv_format == 1) k::spmv_bcsr(c->Ab, x, y, bt, lam, done, s, accumulate, od, rider);
     else k::spmv(c->Ad, x, y, bt, lam, done, s, accumulate, od, rider);
-}
-
-static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
-                        const int32_t *rowptr, const int32_t *colidx, const double *val)
-{
-    std::vector<int32_t> garray;   // sorted global numbers of the off-rank columns (MatMPIAIJ's garray)
-    Error local{0, ""};
-    try {  // ---- local part: validation, upload, split and blocking on the device (no collective inside)
-    if (rowptr[0] != 0) fail(SPK_ERR_ARG, "A00: rowptr[0] must be 0");
-    if (row_begin < 0 || row_begin + nrows_local > ncols_global)
-        fail(SPK_ERR_ARG, "A00: rows [%lld,%lld) outside the %lld x %lld block", (long long)row_begin,
-             (long long)(row_begin + nrows_local), (long long)ncols_global, (long long)ncols_global);
-    for (int32_t r = 0; r < nrows_local; ++r)
-        if (rowptr[r + 1] < rowptr[r]) fail(SPK_ERR_ARG, "A00: rowptr not monotone at row %d", r);
-
-    hipStream_t s = c->stream;
-    const int32_t n = nrows_local;
-    const int64_t nnz = rowptr[n];
-    const int64_t lo = row_begin, hi = row_begin + n;
-    // the caller's slab as it is, once
-    DevBuf<int32_t> rp_in, ci_in, cnt, orp, scratch, flags;
-    DevBuf<double> va_in;
-    rp_in.alloc_raw((size_t)n + 1, 8);
-    ci_in.alloc_raw((size_t)nnz, 16);
-    va_in.alloc_raw((size_t)nnz, 16);
-    c->upload_staged(rp_in.p, rowptr, sizeof(int32_t) * ((size_t)n + 1));
-    c->upload_staged(ci_in.p, colidx, sizeof(int32_t) * (size_t)nnz);
-    c->upload_staged(va_in.p, val, sizeof(double) * (size_t)nnz);
-    // off-rank entries per row (and the column range check), exclusive scan
-    cnt.alloc_raw((size_t)n, 8);
-    orp.alloc_raw((size_t)n + 1, 8);
-    scratch.alloc_raw((size_t)n / 2048 + 8);
-    flags.alloc(4);
-    k::csr_count_off(rp_in.p, ci_in.p, n, lo, hi, ncols_global, cnt.p, flags.p, s);
-    k::exclusive_scan_i32(cnt.p, n, orp.p, scratch.p, s);
-    int32_t hflags[4] = {0, 0, 0, 0}, noff = 0;
-    SPK_HIP(hipMemcpyAsync(hflags, flags.p, sizeof hflags, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipMemcpyAsync(&noff, orp.p + n, sizeof noff, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    if (hflags[0]) fail(SPK_ERR_ARG, "A00: column %d out of range [0,%lld)", hflags[1], (long long)ncols_global);
-    // validation passed: from here on the previous operator is being replaced (a refused block, above,
-    // leaves it in place and usable)
-    c->have_A = false;
-    c->pc_ready = false;
-    if (c->n_global != ncols_global || c->row_begin != row_begin || c->n_local != nrows_local) {
-        // another row range: a constraint block set before belongs to the old one (its column slice and every
-        // array sized by it); KSPSetOperators has to bring the new A10 as well
-        c->have_B = false;
-        c->m = 0;
-        c->b_general = false;
-        c->m_wide = 0;
-        c->bd.release();
-        c->bdpk.release();
-    }
-    c->n_global = ncols_global;
-    c->row_begin = row_begin;
-    c->n_local = nrows_local;
-    const int64_t nnzd = nnz - noff;
-    CsrDev &Ad = c->Ad;
-    Ad.nrows = n;
-    Ad.ncols = n;
-    Ad.nnz = nnzd;
-    Ad.rowptr.alloc_raw((size_t)n + 1, 8);
-    Ad.colidx.alloc_raw((size_t)nnzd, 16);
-    Ad.val.alloc_raw((size_t)nnzd, 16);
-    c->Ao.nrows = 0;
-    c->Ao.ncols = 0;
-    c->Ao.nnz = noff;
-    c->Ao.colidx.alloc_raw((size_t)noff, 16);
-    c->Ao.val.alloc_raw((size_t)noff, 16);
-    k::csr_split(rp_in.p, ci_in.p, va_in.p, n, lo, hi, orp.p, Ad.rowptr.p, Ad.colidx.p, Ad.val.p, c->Ao.colidx.p, c->Ao.val.p, s);
-    // what the host still needs: the diagonal block's row pointers (tile tables are a greedy scan of them) and the
-    // few off-rank entries (ghost numbering, halo plan)
-    HostBuf<int32_t> drp;
-    drp.alloc((size_t)n + 1);
-    std::vector<int32_t> orp_h, ocol_h((size_t)noff);
-    if (noff > 0) {
-        orp_h.resize((size_t)n + 1);
-        SPK_HIP(hipMemcpyAsync(orp_h.data(), orp.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipMemcpyAsync(ocol_h.data(), c->Ao.colidx.p, sizeof(int32_t) * (size_t)noff, hipMemcpyDeviceToHost, s));
-        SPK_HIP(hipStreamSynchronize(s));
-        parallel_for((int64_t)n + 1, [&](int64_t r0, int64_t r1, int) {
-            for (int64_t r = r0; r < r1; ++r) drp[(size_t)r] = rowptr[r] - orp_h[(size_t)r];
-        });
-    } else {
-        parallel_for((int64_t)n + 1, [&](int64_t r0, int64_t r1, int) {
-            for (int64_t r = r0; r < r1; ++r) drp[(size_t)r] = rowptr[r];
-        });
-    }
-    {
-        std::vector<int32_t> tr;
-        k::build_tiles(drp.data(), n, tr);
-        Ad.ntiles = (int32_t)tr.size() - 1;
-        Ad.tile_row.upload(tr.data(), tr.size(), 8);
-    }
-    // ghost numbering: sorted unique global columns, off-rank column indices rewritten to ghost numbers
-    garray.assign(ocol_h.begin(), ocol_h.end());
-    std::sort(garray.begin(), garray.end());
-    garray.erase(std::unique(garray.begin(), garray.end()), garray.end());
-    c->n_ghost = (int32_t)garray.size();
-    if (noff > 0) {
-        for (auto &g : ocol_h) g = (int32_t)(std::lower_bound(garray.begin(), garray.end(), g) - garray.begin());
-        SPK_HIP(hipMemcpyAsync(c->Ao.colidx.p, ocol_h.data(), sizeof(int32_t) * (size_t)noff, hipMemcpyHostToDevice, s));
-        SPK_HIP(hipStreamSynchronize(s));
-    }
-    // off-rank block: compressed to the rows that have entries (FP32 sweeps), and over all rows (SpMV epilogue)
-    {
-        std::vector<int32_t> rows, corp(1, 0);
-        if (noff > 0)
-            for (int32_t r = 0; r < n; ++r)
-                if (orp_h[(size_t)r + 1] > orp_h[(size_t)r]) {
-                    rows.push_back(r);
-                    corp.push_back(orp_h[(size_t)r + 1]);
-                }
-        c->Ao.nrows = (int32_t)rows.size();
-        c->Ao.ncols = c->n_ghost;
-        c->Ao.rowptr.upload(corp.data(), corp.size(), 8);
-        c->ao_rows.upload(rows.data(), rows.size(), 8);
-        c->ao_rowptr_full.release();
-        if (c->n_ghost > 0) std::swap(c->ao_rowptr_full.p, orp.p), std::swap(c->ao_rowptr_full.n, orp.n);
-    }
-
-    // 2x2-blocked copy when every row pair shares its pattern and columns pair up (dof-2 grids): verified
-    // and filled by one kernel, block row br starting at block rowptr[2 br] / 4
-    {
-        BcsrDev &Ab = c->Ab;
-        c->Adict.ok = false;
-        Ab.ok = false;
-        Ab.nbrows = 0;
-        Ab.ntiles = 0;
-        if (n % 2 == 0 && n > 0 && nnzd % 4 == 0) {
-            const int32_t nbr = n / 2;
-            Ab.browptr.alloc_raw((size_t)nbr + 1, 8);
-            Ab.bcol.alloc_raw((size_t)(nnzd / 4), 16);
-            Ab.vtop.alloc_raw((size_t)(nnzd / 2), 32);
-            Ab.vbot.alloc_raw((size_t)(nnzd / 2), 32);
-            SPK_HIP(hipMemsetAsync(flags.p, 0, sizeof(int32_t) * 4, s));
-            k::bcsr_fill(Ad.rowptr.p, Ad.colidx.p, Ad.val.p, nbr, Ab.browptr.p, Ab.bcol.p, Ab.vtop.p, Ab.vbot.p, flags.p, s);
-            SPK_HIP(hipMemcpyAsync(hflags, flags.p, sizeof hflags, hipMemcpyDeviceToHost, s));
-            SPK_HIP(hipStreamSynchronize(s));
-            if (!hflags[0]) {
-                HostBuf<int32_t> brp;
-                brp.alloc((size_t)nbr + 1);
-                parallel_for((int64_t)nbr + 1, [&](int64_t b0, int64_t b1, int) {
-                    for (int64_t br = b0; br < b1; ++br) brp[(size_t)br] = drp[(size_t)(2 * br)] / 4;
-                });
-                Ab.nbrows = nbr;
-                Ab.nblocks = nnzd / 4;
-                std::vector<int32_t> tb;
-                k::build_btiles(brp.data(), Ab.nbrows, tb);
-                Ab.ntiles = (int32_t)tb.size() - 1;
-                Ab.tile_brow.upload(tb.data(), tb.size(), 8);
-                Ab.ok = true;
-                build_dict(c, 2, brp.data());
-            } else {
-                Ab.browptr.release(); Ab.bcol.release(); Ab.vtop.release(); Ab.vbot.release();
-            }
-        }
-        // 3x3-blocked copy for dof-3 grids (the 3-D generator: 81 entries per row in 27 blocks), same verification
-        Bcsr3Dev &A3 = c->Ab3;
-        A3.ok = false;
-        A3.nbrows = 0;
-        A3.ntiles = 0;
-        A3.v32.release();
-        if (!Ab.ok && n % 3 == 0 && n > 0 && nnzd % 9 == 0) {
-            const int32_t nbr = n / 3;
-            const int64_t nb = nnzd / 9;
-            A3.ldp = (nb + 1 + 7) & ~(int64_t)7;
-            A3.browptr.alloc_raw((size_t)nbr + 1, 8);
-            A3.bcol.alloc_raw((size_t)nb, 16);
-            A3.v.alloc_raw((size_t)(9 * A3.ldp), 32);
-            SPK_HIP(hipMemsetAsync(flags.p, 0, sizeof(int32_t) * 4, s));
-            k::bcsr3_fill(Ad.rowptr.p, Ad.colidx.p, Ad.val.p, nbr, A3.browptr.p, A3.bcol.p, A3.v.p, A3.ldp, flags.p, s);
-            SPK_HIP(hipMemcpyAsync(hflags, flags.p, sizeof hflags, hipMemcpyDeviceToHost, s));
-            SPK_HIP(hipStreamSynchronize(s));
-            if (!hflags[0]) {
-                HostBuf<int32_t> brp;
-                brp.alloc((size_t)nbr + 1);
-                parallel_for((int64_t)nbr + 1, [&](int64_t b0, int64_t b1, int) {
-                    for (int64_t br = b0; br < b1; ++br) brp[(size_t)br] = drp[(size_t)(3 * br)] / 9;
-                });
-                std::vector<int32_t> tb;
-                k::build_b3tiles(brp.data(), nbr, tb);
-                A3.nbrows = nbr;
-                A3.nblocks = nb;
-                A3.ntiles = (int32_t)tb.size() - 1;
-                A3.tile_brow.upload(tb.data(), tb.size(), 8);
-                A3.ok = true;
-                build_dict(c, 3, brp.data());
-            } else {
-                A3.browptr.release(); A3.bcol.release(); A3.v.release();
-            }
-        } else {
-            A3.browptr.release(); A3.bcol.release(); A3.v.release();
-        }
-        const char *fmt = getenv("SPK_SPMV_FORMAT");
-        const bool csr_forced = fmt && !strcmp(fmt, "csr");
-        c->spmv_format = csr_forced ? 0 : (Ab.ok ? 1 : (A3.ok ? 2 : 0));
-    }
-    } catch (const Error &e) {
-        local = e;
-    } catch (const std::exception &e) {
-        local = Error{SPK_ERR_NOMEM, e.what()};
-    }
-    agree_or_fail(c, local.code ? &local : nullptr, "A00");
-
-    // ---- halo plan (VecScatter of MatMult_MPIAIJ) ----
-    const int P = c->comm->size(), me = c->comm->rank();
-    c->peers.clear();
-    c->send_off.assign(1, 0);
-    c->recv_off.assign(1, 0);
-    std::vector<int32_t> send_idx;
-    if (P > 1) {
-        std::vector<int64_t> mine = {row_begin, row_begin + nrows_local}, all((size_t)2 * P);
-        c->comm->host_allgather(mine.data(), all.data(), 2 * sizeof(int64_t));
-        for (int r = 1; r < P; ++r)
-            if (all[2 * r] != all[2 * r - 1]) fail(SPK_ERR_ARG, "A00: row slabs must tile [0,n) in rank order");
-        std::vector<std::vector<char>> ghosts;
-        c->comm->host_allgatherv(garray.data(), garray.size() * sizeof(int32_t), ghosts);
-        for (int p = 0; p < P; ++p) {
-            if (p == me) continue;
-            // what I receive from p: my ghosts inside p's range (contiguous in sorted garray)
-            const int64_t plo = all[2 * p], phi = all[2 * p + 1];
-            int64_t nrecv = 0;
-            for (int32_t g : garray) nrecv += (g >= plo && g < phi);
-            // what I send to p: p's ghosts inside my range, in p's order
-            const int32_t *pg = (const int32_t *)ghosts[(size_t)p].data();
-            const size_t npg = ghosts[(size_t)p].size() / sizeof(int32_t);
-            int64_t nsend = 0;
-            for (size_t i = 0; i < npg; ++i)
-                if (pg[i] >= row_begin && pg[i] < row_begin + nrows_local) {
-                    send_idx.push_back((int32_t)(pg[i] - row_begin));
-                    ++nsend;
-                }
-            if (nsend == 0 && nrecv == 0) continue;
-            c->peers.push_back(p);
-            c->send_off.push_back(c->send_off.back() + nsend);
-            c->recv_off.push_back(c->recv_off.back() + nrecv);
-        }
-    } else if (c->n_ghost != 0) {
-        fail(SPK_ERR_ARG, "A00: %d columns fall outside the local rows but there is only one rank", c->n_ghost);
-    }
-    local = Error{0, ""};
-    try {  // ---- local again: the rest of the plan and its uploads; agreed on before the collective setup_halo
-    if (P > 1 && c->recv_off.back() != c->n_ghost) fail(SPK_ERR_ARG, "A00: ghost columns not owned by any rank");
-    c->send_idx.upload(send_idx.data(), send_idx.size(), 8);
-    c->send_buf.alloc(send_idx.size(), 8);
-    // (the off-rank part in "SpMV epilogue" form -- row pointers over all local rows -- is the scan result kept above)
-    // halo rows as contiguous ranges (slab partitions): lets the producer of z fill send_buf itself
-    c->send_ranges = k::SendRanges{};
-    {
-        bool ok = !c->peers.empty() && c->peers.size() <= 4;
-        for (size_t p = 0; ok && p < c->peers.size(); ++p) {
-            const int64_t a = c->send_off[p], b = c->send_off[p + 1];
-            for (int64_t i = a + 1; ok && i < b; ++i) ok = send_idx[(size_t)i] == send_idx[(size_t)i - 1] + 1;
-            if (ok) {
-                c->send_ranges.r0[p] = b > a ? send_idx[(size_t)a] : 0;
-                c->send_ranges.len[p] = (int32_t)(b - a);
-                c->send_ranges.off[p] = (int32_t)a;
-            }
-        }
-        if (ok) {
-            c->send_ranges.n = (int)c->peers.size();
-            c->send_ranges.buf = c->send_buf.p;
-        }
-    }
-    c->xghost.alloc((size_t)c->n_ghost, 8);
-    } catch (const Error &e) {
-        local = e;
-    } catch (const std::exception &e) {
-        local = Error{SPK_ERR_NOMEM, e.what()};
-    }
-    agree_or_fail(c, local.code ? &local : nullptr, "A00 (halo plan)");
-    c->comm->setup_halo(c->n_ghost, c->peers, c->send_off, c->recv_off);  // collective
-    c->have_A = true;
-    c->pc_ready = false;
-    c->ensure_vectors();
-}
-
-static void set_block_B(spk_ctx *c, int32_t m, int64_t ncols_global, const int32_t *rowptr,
-                        const int32_t *colidx, const double *val)
-{
-    if (!c->have_A) fail(SPK_ERR_STATE, "A10: set SPK_BLOCK_A00 first");
-    c->bt_cached = nullptr;
-    if (ncols_global != c->n_global) fail(SPK_ERR_ARG, "A10: %lld columns, A00 has %lld", (long long)ncols_global, (long long)c->n_global);
-    if (m < 0) fail(SPK_ERR_ARG, "A10: negative row count");
-    if ((int64_t)c->n_local + m > INT32_MAX - 1024) fail(SPK_ERR_UNSUPPORTED, "A10: n_local + m exceeds 32-bit vector indices");
-    for (int32_t r = 0; r < m; ++r)
-        if (rowptr[r + 1] < rowptr[r]) fail(SPK_ERR_ARG, "A10: rowptr not monotone at row %d", r);
-    const int32_t nl = c->n_local;
-    const int64_t lo = c->row_begin, hi = lo + nl;
-    // local column numbers, ascending inside each row
-    // (threaded over the entries: the reference's 4 rows hold ~n/2 entries each -- 4 M at 1024^2)
-    HostBuf<int32_t> col;
-    HostBuf<double> v;
-    col.alloc((size_t)rowptr[m]);
-    v.alloc((size_t)rowptr[m]);
-    {
-        // a flag of its own per thread: any int32 -- -1 included -- can be the offending column number
-        std::vector<char> bad(64, 0);
-        std::vector<int32_t> badcol(64, 0);
-        parallel_for(rowptr[m], [&](int64_t a, int64_t b, int t) {
-            for (int64_t k = a; k < b; ++k) {
-                const int32_t g = colidx[k];
-                if (g < lo || g >= hi) bad[(size_t)t] = 1, badcol[(size_t)t] = g;
-                col[(size_t)k] = (int32_t)(g - lo);
-                v[(size_t)k] = val[k];
-            }
-        });
-        for (size_t t = 0; t < bad.size(); ++t)
-            if (bad[t])
-                fail(SPK_ERR_ARG, "A10: column %d not owned by this rank [%lld,%lld)", badcol[t], (long long)lo, (long long)hi);
-        for (int32_t r = 0; r < m; ++r) {   // PETSc rows come sorted: nothing to do then
-            const int32_t k0 = rowptr[r], k1 = rowptr[r + 1];
-            if (std::is_sorted(col.data() + k0, col.data() + k1)) continue;
-            std::vector<int32_t> perm((size_t)(k1 - k0));
-            std::iota(perm.begin(), perm.end(), 0);
-            std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return col[(size_t)(k0 + a)] < col[(size_t)(k0 + b)]; });
-            std::vector<int32_t> c2((size_t)(k1 - k0));
-            std::vector<double> v2((size_t)(k1 - k0));
-            for (int32_t i = 0; i < k1 - k0; ++i) {
-                c2[(size_t)i] = col[(size_t)(k0 + perm[(size_t)i])];
-                v2[(size_t)i] = v[(size_t)(k0 + perm[(size_t)i])];
-            }
-            std::copy(c2.begin(), c2.end(), col.data() + k0);
-            std::copy(v2.begin(), v2.end(), v.data() + k0);
-        }
-    }
-    // Which rows go through the column-window (long-row) kernel: all of them for m <= 8 (the reference's 4
-    // rows, the fused dense-plane path); for a general block only its LONG rows (local entries beyond
-    // kWideRowNnz; at most 8, the longest first) -- the rest is a CSR by rows for the stream kernel.
-    constexpr int32_t kWideRowNnz = 8192;
-    c->b_general = m > 8;
-    std::vector<int32_t> wide;
-    if (!c->b_general) {
-        for (int32_t r = 0; r < m; ++r) wide.push_back(r);
-    } else {
-        std::vector<int32_t> cand;
-        for (int32_t r = 0; r < m; ++r)
-            if (rowptr[r + 1] - rowptr[r] > kWideRowNnz) cand.push_back(r);
-        std::sort(cand.begin(), cand.end(), [&](int32_t a, int32_t b) {
-            const int32_t la = rowptr[a + 1] - rowptr[a], lb = rowptr[b + 1] - rowptr[b];
-            return la != lb ? la > lb : a < b;
-        });
-        if (cand.size() > 8) cand.resize(8);
-        std::sort(cand.begin(), cand.end());
-        wide = cand;
-    }
-    const int32_t mw = (int32_t)wide.size();
-    c->m_wide = mw;
-    c->wide_rows_h = wide;
-    c->wide_rows.upload(wide.data(), wide.size(), 8);
-    // column windows over the wide rows (concatenated in `wide` order)
-    WideDev &B = c->B;
-    B.m = mw;
-    B.ncols = nl;
-    std::vector<int32_t> wcol_own, wrp(1, 0);
-    std::vector<double> wv_own;
-    const int32_t *wcol = col.data();
-    const double *wv = v.data();
-    if (!c->b_general) {  // every row, in order: the arrays as they are
-        for (int32_t r = 0; r < m; ++r) wrp.push_back(rowptr[r + 1]);
-    } else {
-        for (int32_t r : wide) {
-            wcol_own.insert(wcol_own.end(), col.data() + rowptr[r], col.data() + rowptr[r + 1]);
-            wv_own.insert(wv_own.end(), v.data() + rowptr[r], v.data() + rowptr[r + 1]);
-            wrp.push_back((int32_t)wcol_own.size());
-        }
-        wcol = wcol_own.data();
-        wv = wv_own.data();
-    }
-    B.nnz = wrp.back();
-    int32_t win = 8192;
-    while ((int64_t)(nl + win - 1) / win > k::kMaxBlocks) win *= 2;
-    // small local sizes: narrower windows, so that the launch still has ~128 workgroups (a rank's 1/8 slab of the
-    // 1024^2 grid got 32 workgroups on 256 CUs: 12.6 us for 6 MB)
-    while (win > 1024 && (int64_t)(nl + win - 1) / win < 128) win /= 2;
-    B.win = win;
-    B.nwin = mw > 0 ? (nl + win - 1) / win : 0;
-    std::vector<int32_t> winptr((size_t)(B.nwin + 1) * (size_t)std::max(mw, 1));
-    for (int32_t r = 0; r < mw; ++r) {
-        const int32_t *b = wcol + wrp[(size_t)r], *e = wcol + wrp[(size_t)r + 1];
-        for (int32_t w = 0; w <= B.nwin; ++w) {
-            const int64_t c0 = (int64_t)w * win;
-            winptr[(size_t)w * mw + r] = wrp[(size_t)r] + (int32_t)(std::lower_bound(b, e, (int32_t)std::min<int64_t>(c0, nl)) - b);
-        }
-    }
-    up(c, B.colidx, wcol, (size_t)B.nnz, 16);
-    up(c, B.val, wv, (size_t)B.nnz, 16);
-    B.winptr.upload(winptr.data(), winptr.size(), 8);
-    // the general block by rows (its long rows left empty: the window kernel fills their results in)
-    c->Bc.rowptr.release(); c->Bc.colidx.release(); c->Bc.val.release(); c->Bc.tile_row.release();
-    c->Bc.nrows = c->Bc.ncols = c->Bc.ntiles = 0;
-    c->Bc.nnz = 0;
-    if (c->b_general) {
-        std::vector<char> is_wide((size_t)m, 0);
-        for (int32_t r : wide) is_wide[(size_t)r] = 1;
-        std::vector<int32_t> crp((size_t)m + 1, 0), cci;
-        std::vector<double> cv;
-        for (int32_t r = 0; r < m; ++r) {
-            if (!is_wide[(size_t)r]) {
-                cci.insert(cci.end(), col.data() + rowptr[r], col.data() + rowptr[r + 1]);
-                cv.insert(cv.end(), v.data() + rowptr[r], v.data() + rowptr[r + 1]);
-            }
-            crp[(size_t)r + 1] = (int32_t)cci.size();
-        }
-        upload_csr(c, c->Bc, m, nl, crp, cci, cv, true);
-    }
-    if ((size_t)m + 64 > c->y1tmp.n) c->y1tmp.alloc((size_t)m + 64);
-    if ((size_t)m + 64 > c->ttmp.n) c->ttmp.alloc((size_t)m + 64);
-
-    // B^T by rows (n_local x m), entries of a row ordered by constraint index
-    // (threads own disjoint column ranges and walk the sorted rows' entries inside them: counts, then fill in
-    // row order -- the same arrays as a sequential counting sort)
-    std::vector<int32_t> trp((size_t)nl + 1, 0), tci((size_t)rowptr[m]);
-    std::vector<double> tv((size_t)rowptr[m]);
-    auto row_range = [&](int32_t r, int64_t c0, int64_t c1, int32_t &b, int32_t &e) {
-        const int32_t *rb = col.data() + rowptr[r], *re = col.data() + rowptr[r + 1];
-        b = rowptr[r] + (int32_t)(std::lower_bound(rb, re, (int32_t)c0) - rb);
-        e = rowptr[r] + (int32_t)(std::lower_bound(rb, re, (int32_t)c1) - rb);
-    };
-    parallel_for(nl, [&](int64_t c0, int64_t c1, int) {
-        for (int32_t r = 0; r < m; ++r) {
-            int32_t b, e;
-            row_range(r, c0, c1, b, e);
-            for (int32_t k = b; k < e; ++k) trp[(size_t)col[(size_t)k] + 1]++;
-        }
-    });
-    for (int32_t i = 0; i < nl; ++i) trp[(size_t)i + 1] += trp[(size_t)i];
-    {
-        HostBuf<int32_t> fill;
-        fill.alloc((size_t)nl + 1);
-        parallel_for(nl, [&](int64_t c0, int64_t c1, int) {
-            for (int64_t i = c0; i < c1; ++i) fill[(size_t)i] = trp[(size_t)i];
-            for (int32_t r = 0; r < m; ++r) {
-                int32_t b, e;
-                row_range(r, c0, c1, b, e);
-                for (int32_t k = b; k < e; ++k) {
-                    const int32_t p = fill[(size_t)col[(size_t)k]]++;
-                    tci[(size_t)p] = r;
-                    tv[(size_t)p] = v[(size_t)k];
-                }
-            }
-        });
-    }
-    upload_csr(c, c->Bt, nl, m, trp, tci, tv, c->b_general);   // (a general block: tiles for the stream kernel)
-    c->m = m;
-    c->have_B = m > 0;
-    c->pc_ready = false;
-    c->ensure_vectors();
-    if (c->b_general && c->tmpb.n < (size_t)c->ld) c->tmpb.alloc((size_t)c->ld);   // scratch of the B^T products (bt_update)
-}
-
-void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
-               const int32_t *rowptr, const int32_t *colidx, const double *val)
-{
-    if (!rowptr || (!colidx && rowptr[nrows_local] > 0) || (!val && rowptr[nrows_local] > 0))
-        fail(SPK_ERR_ARG, "set_block: null array");
-    if (nrows_local < 0) fail(SPK_ERR_ARG, "set_block: negative row count");
-    c->ensure_scratch();
-    if (which == SPK_BLOCK_A00) set_block_A(c, row_begin, nrows_local, ncols_global, rowptr, colidx, val);
-    else if (which == SPK_BLOCK_A10) {
-        // no collective inside, but every rank sets its column slice: agree on the outcome so that a rank
-        // whose slice was refused does not leave the others to run into the next collective alone
-        Error local{0, ""};
-        try {
-            set_block_B(c, nrows_local, ncols_global, rowptr, colidx, val);
-        } catch (const Error &e) {
-            local = e;
-        } catch (const std::exception &e) {
-            local = Error{SPK_ERR_NOMEM, e.what()};
-        }
-        agree_or_fail(c, local.code ? &local : nullptr, "A10");
-    } else fail(SPK_ERR_ARG, "set_block: unknown block %d", which);
 }
 
 // out[r] = B_r . (x .* scale)  over this rank's columns (scale == nullptr: B_r . x); MatMult on the (1,0) block.
@@ -970,155 +195,6 @@ void op_mult(spk_ctx *c, const double *x, double *y, const int32_t *done, bool h
         apply_B(c, x, nullptr, y + nl, done);
         c->comm->allreduce_sum(y + nl, m, s);
     }
-}
-
-// ---------------------------------------------------------------------------
-// KSPSetUp / PCSetUp: diag(A)^-1, S^ = diag(B diag(A)^-1 B^T)
-// ---------------------------------------------------------------------------
-void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
-{
-    if (!c->have_A) fail(SPK_ERR_STATE, "pc_setup: no A00 block");
-    if (pc_type < SPK_PC_NONE || pc_type > SPK_PC_SCHUR) fail(SPK_ERR_ARG, "pc_setup: unknown pc_type %d", pc_type);
-    if (pc_type == SPK_PC_SCHUR && !c->have_B) fail(SPK_ERR_STATE, "pc_setup: Schur fieldsplit needs the A10 block");
-    if (schur_fact < SPK_SCHUR_DIAG || schur_fact > SPK_SCHUR_FULL) fail(SPK_ERR_ARG, "pc_setup: unknown schur_fact %d", schur_fact);
-    // multigrid standing for A^-1: one rank only (every rank sees the same communicator size: all refuse together), built
-    // on the host before anything of the context changes -- a refusal leaves it as it was
-    std::unique_ptr<spk_amg_hier> amg;
-    std::unique_ptr<AmgDev> amg_dev;   // -spk_gamg_setup device: built on the device, equally before anything changes
-    if (c->amg_on) {
-        if (c->comm->size() > 1)
-            fail(SPK_ERR_UNSUPPORTED, "pc_setup: the multigrid preconditioner (gamg) runs on one rank only; this communicator "
-                 "has %d -- multi-rank AMG is not implemented", c->comm->size());
-        if (pc_type == SPK_PC_NONE) fail(SPK_ERR_ARG, "pc_setup: the multigrid preconditioner needs pc_type jacobi or schur");
-        if (c->amg_opts.setup == SPK_AMG_SETUP_DEVICE) amg_dev = amg_build_device(c);
-        else amg = amg_build_ctx(c);
-    }
-    c->amg_d.reset();
-    c->amg_h.reset();
-    hipStream_t s = c->stream;
-    c->ensure_scratch();
-    c->ensure_vectors();
-    {   // which iteration path the solve takes must not depend on one rank's slab (KSPSetUp is collective)
-        const int P = c->comm->size();
-        const int32_t mine = (c->n_local % 2 == 0 ? 1 : 0) | (c->n_local > 0 ? 2 : 0);
-        std::vector<int32_t> all((size_t)P, mine);
-        if (P > 1) c->comm->host_allgather(&mine, all.data(), sizeof mine);
-        c->even_all = c->nonempty_all = true;
-        for (int32_t v : all) {
-            c->even_all = c->even_all && (v & 1);
-            c->nonempty_all = c->nonempty_all && (v & 2);
-        }
-    }
-    c->dinv.alloc((size_t)c->n_local, 8);
-    k::extract_diag_inv(c->Ad, c->dinv.p, s);
-    if (amg) amg_upload(c, std::move(amg));
-    if (amg_dev) c->amg_d = std::move(amg_dev);
-    const int m = c->m;
-    if (m > 0 && c->b_general) {
-        // S^ = diag(B D B^T), row by row: short rows one wave each; the long rows as below (scatter + window kernel)
-        c->gram.release();
-        c->shat.alloc((size_t)m, 8);
-        k::schur_diag_rows(c->Bc, c->dinv.p, c->shat.p, s);
-        if (c->m_wide > 0) {
-            const int mw = c->m_wide;
-            DevBuf<double> grow;
-            grow.alloc((size_t)mw);
-            SPK_HIP(hipMemsetAsync(c->tmp.p, 0, sizeof(double) * (size_t)c->ld, s));
-            std::vector<int32_t> wp((size_t)(c->B.nwin + 1) * mw);
-            SPK_HIP(hipMemcpy(wp.data(), c->B.winptr.p, wp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            for (int r = 0; r < mw; ++r) {
-                const int k0 = wp[(size_t)r], k1 = wp[(size_t)c->B.nwin * mw + r];
-                k::scatter_row(c->B.colidx.p, c->B.val.p, k0, k1, c->dinv.p, c->tmp.p, s);
-                k::wide_dot(c->B, c->tmp.p, c->fin(grow.p), nullptr, s);          // row r of the long rows' Gram matrix
-                SPK_HIP(hipMemcpyAsync(c->shat.p + c->wide_rows_h[(size_t)r], grow.p + r, sizeof(double), hipMemcpyDeviceToDevice, s));
-                k::scatter_row(c->B.colidx.p, c->B.val.p, k0, k1, nullptr, c->tmp.p, s);
-            }
-            SPK_HIP(hipStreamSynchronize(s));
-        }
-        c->comm->allreduce_sum(c->shat.p, m, s);
-        SPK_HIP(hipStreamSynchronize(s));
-    } else if (m > 0) {
-        c->gram.alloc((size_t)m * m);
-        c->shat.alloc((size_t)m);
-        // row r of B .* dinv scattered densely, then B * that = G[r, :]
-        SPK_HIP(hipMemsetAsync(c->tmp.p, 0, sizeof(double) * (size_t)c->ld, s));
-        std::vector<int32_t> wp((size_t)(c->B.nwin + 1) * m);
-        SPK_HIP(hipMemcpy(wp.data(), c->B.winptr.p, wp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int r = 0; r < m; ++r) {
-            const int k0 = wp[(size_t)r], k1 = wp[(size_t)c->B.nwin * m + r];
-            k::scatter_row(c->B.colidx.p, c->B.val.p, k0, k1, c->dinv.p, c->tmp.p, s);
-            k::wide_dot(c->B, c->tmp.p, c->fin(c->gram.p + (size_t)r * m), nullptr, s);
-            k::scatter_row(c->B.colidx.p, c->B.val.p, k0, k1, nullptr, c->tmp.p, s);
-        }
-        c->comm->allreduce_sum(c->gram.p, m * m, s);
-        SPK_HIP(hipStreamSynchronize(s));
-        std::vector<double> G((size_t)m * m), sh((size_t)m);
-        SPK_HIP(hipMemcpy(G.data(), c->gram.p, G.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int r = 0; r < m; ++r) sh[(size_t)r] = G[(size_t)r * m + r];
-        SPK_HIP(hipMemcpy(c->shat.p, sh.data(), sh.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    // FP32 copies for the inner solve
-    c->a32.release(); c->d32.release(); c->x32.release(); c->y32a.release(); c->y32b.release();
-    c->Ab3.v32.release();
-    c->Ab.vtop32.release();
-    c->Ab.vbot32.release();
-    const bool dict = c->spmv_format != 0 && c->Adict.ok;   // (the sweeps then decode the codes and round to single precision)
-    if (c->inner_sweeps > 0 && !dict && c->spmv_format == 1) {   // ... or the 2x2-blocked value planes
-        c->Ab.vtop32.alloc_raw((size_t)(2 * c->Ab.nblocks + 8), 32);
-        c->Ab.vbot32.alloc_raw((size_t)(2 * c->Ab.nblocks + 8), 32);
-        k::cvt_vals_f32(c->Ab.vtop.p, c->Ab.vtop32.p, 2 * c->Ab.nblocks, s);
-        k::cvt_vals_f32(c->Ab.vbot.p, c->Ab.vbot32.p, 2 * c->Ab.nblocks, s);
-    }
-    if (c->inner_sweeps > 0 && !dict && c->spmv_format == 2) {   // the sweeps read the 3x3-blocked planes in single precision
-        c->Ab3.v32.alloc_raw((size_t)(9 * c->Ab3.ldp), 32);
-        k::cvt_vals_f32(c->Ab3.v.p, c->Ab3.v32.p, 9 * c->Ab3.ldp, s);
-    }
-    if (c->inner_sweeps > 0 && c->spmv_format == 0) {
-        c->a32.alloc((size_t)c->Ad.nnz, 32);
-        k::cvt_vals_f32(c->Ad.val.p, c->a32.p, c->Ad.nnz, s);
-    }
-    if (c->inner_sweeps > 0) {
-        c->d32.alloc((size_t)c->n_local, 8);
-        c->x32.alloc((size_t)c->n_local, 8);
-        c->y32a.alloc((size_t)c->n_local, 8);
-        c->y32b.alloc((size_t)c->n_local, 8);
-        k::cvt_vals_f32(c->dinv.p, c->d32.p, c->n_local, s);
-    }
-    // dense rows of B D for the fused path (Schur LOWER/FULL, even local size)
-    c->bd.release();
-    if (pc_type == SPK_PC_SCHUR && m > 0 && !c->b_general && (schur_fact == SPK_SCHUR_FULL || schur_fact == SPK_SCHUR_LOWER) &&
-        c->even_all && c->inner_sweeps == 0 && !c->amg_d) {
-        c->bd.alloc((size_t)c->ld * m, 16);
-        k::build_bd(c->Bt, c->dinv.p, m, c->ld, c->bd.p, s);
-        // rows 2q / 2q+1 on even / odd entries (x / y degrees of freedom): m/2 planes instead of m rows
-        c->bdpk.release();
-        c->bd_packed = false;
-        if (m % 2 == 0 && !getenv("SPK_BD_DENSE")) {
-            c->bdpk.alloc((size_t)c->ld * (m / 2), 16);
-            DevBuf<int32_t> bad;
-            bad.alloc(1);
-            k::pack_bd(c->bd.p, c->ld, c->n_local, m, c->bdpk.p, bad.p, s);
-            int32_t hb = 1;
-            SPK_HIP(hipMemcpyAsync(&hb, bad.p, sizeof hb, hipMemcpyDeviceToHost, s));
-            SPK_HIP(hipStreamSynchronize(s));
-            c->bd_packed = hb == 0;
-            if (!c->bd_packed) c->bdpk.release();
-        }
-    }
-    SPK_HIP(hipStreamSynchronize(s));
-    c->pc_type = pc_type;
-    c->schur_fact = schur_fact;
-    {   // does EVERY rank's slab fit the resident cycle kernel (restart <= 30)?  agreed here, like the iteration path above
-        const int planes = !c->bd.p ? 0 : (c->bd_packed ? m / 2 : m);
-        const int32_t mine = (c->spmv_format == 1 && c->Adict.ok && c->Adict.bs == 2 && c->n_local % 2 == 0 &&
-                              k::resident_fits(c->Adict, c->num_cus, 30, planes)) ? 1 : 0;
-        const int P = c->comm->size();
-        std::vector<int32_t> all((size_t)P, mine);
-        if (P > 1) c->comm->host_allgather(&mine, all.data(), sizeof mine);
-        c->res_fit_all = true;
-        for (int32_t v : all) c->res_fit_all = c->res_fit_all && v != 0;
-    }
-    c->pc_ready = true;
 }
 
 // ---------------------------------------------------------------------------

@@ -283,6 +283,43 @@ def test_dictionary_row_slabs(spk, oracle, monkeypatch):
     assert np.allclose(y[cut], y_ref[cut], rtol=1e-13, atol=1e-15)
 
 
+def test_operators_of_different_kinds_in_turn(spk, monkeypatch):
+    """One context gets a dof-2 grid (2x2 blocks), a dof-3 grid (3x3 blocks), a 5-row tridiagonal matrix (odd n: CSR
+    only) and the first grid again: after every KSPSetOperators the layout and the product are those of a fresh context
+    (nothing of the previous blocked copy or dictionary survives), and the solve on the last one is a fresh context's bit
+    for bit.  (test_gpu_parity.py::test_peer_store_operators_set_again walks grid -> larger grid -> grid on two ranks: one
+    kind of operator throughout.)"""
+    monkeypatch.delenv("SPK_SPMV_FORMAT", raising=False)
+    A2, f = spk.AssembleOperator_Laplace(4, 4)
+    A3, _ = spk.AssembleOperator_Laplace3D(3, 3, 3)
+    T = spk.CSR(np.array([0, 2, 5, 8, 11, 13], np.int32), np.array([0, 1, 0, 1, 2, 1, 2, 3, 2, 3, 4, 3, 4], np.int32),
+                np.array([2.0, -1.0, -1.0, 2.5, -1.0, -1.0, 3.0, -1.0, -1.0, 3.5, -1.0, -1.0, 4.0]), 5)
+    B, g = spk.AssembleOperator_Constraints(4, 4)
+    rhs = np.concatenate([f, g])
+    assert A2.nrows == 32 and A3.nrows == 81
+
+    def solve(c):
+        c.set_block(spk.BLOCK_A10, B)
+        c.pc_setup(spk.PC_SCHUR, spk.SCHUR_FULL)
+        return c.fgmres(rhs, rtol=1e-10)
+    formats = []
+    with spk.Context(0) as c:
+        for A in (A2, A3, T, A2):
+            x = _x(A.nrows, 21)
+            c.set_block(spk.BLOCK_A00, A)
+            with spk.Context(0) as fresh:
+                fresh.set_block(spk.BLOCK_A00, A)
+                assert c.spmv_info()["format"] == fresh.spmv_info()["format"]
+                assert np.array_equal(c.mult(x)[:A.nrows], fresh.mult(x)[:A.nrows])
+            formats.append(c.spmv_info()["format"])
+        xs, info = solve(c)
+    assert formats[2] == "csr" and formats[0] == formats[3] and len(set(formats)) == 3, formats
+    with spk.Context(0) as fresh:
+        fresh.set_block(spk.BLOCK_A00, A2)
+        xf, inf = solve(fresh)
+    assert info["reason"] == 2 and np.array_equal(xs, xf) and np.array_equal(info["history"], inf["history"])
+
+
 def test_constraint_block_column_validation(spk):
     """A10 with a column number of exactly -1 (the value a sentinel once used) or n is refused with SPK_ERR_ARG and the
     operator set before stays usable."""
