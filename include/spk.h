@@ -470,6 +470,52 @@ int spk_debug_finish_timeout(spk_ctx *ctx, int timeout_ms);
  * multi-value reduction (16 na doubles).  The two halves must hold the same bits. */
 int spk_debug_wave_sums(spk_ctx *ctx, int na, const double *in, double *out);
 
+/* Test hooks for the Gram-Schmidt kernels (tests/test_gpu_vec_kernels.py): each takes host arrays, runs the PRODUCTION host
+ * wrapper (k::mdot, k::maxpy, k::sqnorm_bd, k::pack_bd, k::fused_head) with every argument the solver passes, and copies the
+ * results back.  Vectors are given densely (row i at V + i * n) and live on the device with stride ld = roundup(n, 256);
+ * entries [n, ld) of every vector hold `pad`.  done: -1 passes a null pointer, 0 / 1 a device word holding that value.
+ * Outputs a launch may leave alone are pre-filled with SPK_DEBUG_MARKER. */
+#define SPK_DEBUG_MARKER (-7777777.0)
+/* out (13 values): ws_shape {on, U, grid}, vec_shape(n2) {T, U, G, grid} and vec_shape(n2, maxpy) {T, U, G, grid} of a
+ * vector of n entries, then the knobs SPK_VEC_WS16 and SPK_VEC_DEEP as this process reads them. */
+int spk_debug_vec_shape(spk_ctx *ctx, int64_t n, int32_t *out);
+typedef struct spk_debug_mdot_opts {
+    int64_t n, n_dot;
+    int32_t nv, nv2;   /* vectors of V; results of the second slab V2 (split: nv2 / 2 parity planes, else nv2 dense rows) */
+    int32_t split, done;
+    double pad;
+} spk_debug_mdot_opts;
+/* out: nv + nv2 + 1 values (the dot products, then w.w) */
+int spk_debug_mdot(spk_ctx *ctx, const spk_debug_mdot_opts *o, const double *V, const double *V2, const double *w, double *out);
+typedef struct spk_debug_maxpy_opts {
+    int64_t n, n_dot, n_bd;
+    double sign, pad;
+    int32_t nv, nv_live;   /* nv_live >= 0: a device word holding it is passed as nv_dev (nv is the larger host count) */
+    int32_t want_norm;     /* 0: Finish::out = NULL */
+    int32_t m, bd_mode;    /* bd_mode 0: no planes, 1: m dense rows, 2: m / 2 parity planes */
+    int32_t w1side, pyth, done;
+} spk_debug_maxpy_opts;
+/* w: n entries in and out; bd: the planes (bd_mode rows of n); dots: nv_live + m + 1 reduced values and tb: (nv + 1) x 8,
+ * in and out (pyth only); red: 1 + m reduced values; w1side: m; nrm_out: 1 + m (pyth only) */
+int spk_debug_maxpy(spk_ctx *ctx, const spk_debug_maxpy_opts *o, const double *V, const double *a, double *w, const double *bd,
+                    const double *dots, double *tb, double *red, double *w1side, double *nrm_out);
+/* k::sqnorm_bd: x of n entries (sa, sb != NULL: x = sa - sb is formed, x is output only), m dense planes bd of n entries;
+ * red: 1 + m, w1side: m */
+int spk_debug_cycle_norm(spk_ctx *ctx, int64_t n, int64_t n_dot, int64_t n_bd, int32_t m, double pad, double *x, const double *sa,
+                         const double *sb, const double *bd, double *red, double *w1side);
+/* k::pack_bd: m dense rows of n entries -> m / 2 planes (bdp: (m / 2) x n) and the `bad` word */
+int spk_debug_pack_bd(spk_ctx *ctx, int64_t n, int32_t m, const double *bd, double *bdp, int32_t *bad);
+typedef struct spk_debug_head_opts {
+    int64_t nl;            /* even */
+    int32_t m, packed, fact, jacobi, want_wl, reserved;
+    double pad;
+} spk_debug_head_opts;
+/* k::fused_head with loc_prev = -1, no SendRanges and a zero `done` word.  v: nl + m in and out; nrm: 1 + m; w1raw, shat: m;
+ * dinv: nl; bd: m rows (packed: m / 2) of nl; gram: m x m; z, c: nl + m out (jacobi: c is not passed, m = 0); wl: m */
+int spk_debug_cycle_head(spk_ctx *ctx, const spk_debug_head_opts *o, double *v, const double *nrm, const double *w1raw,
+                         const double *dinv, const double *bd, const double *shat, const double *gram, double *z, double *c,
+                         double *wl);
+
 /* Developer hook (library built with `make GS_STAMPS=1`; SPK_ERR_STATE otherwise): the phase time stamps of form 7's fused
  * Gram-Schmidt launches of the solves so far, out[(loc * 256 + workgroup) * 8 + phase] in 100 MHz ticks of one device-wide
  * counter (64 x 256 x 8 values; per loc the last launch that ran; phases in csrc/spk_gs_stamps.hpp; 0: never written). */

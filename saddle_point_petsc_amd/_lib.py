@@ -91,6 +91,25 @@ class MatCSR(C.Structure):
     ]
 
 
+class DebugMdotOpts(C.Structure):
+    """spk_debug_mdot_opts (include/spk.h)."""
+    _fields_ = [("n", C.c_int64), ("n_dot", C.c_int64), ("nv", C.c_int32), ("nv2", C.c_int32), ("split", C.c_int32),
+                ("done", C.c_int32), ("pad", C.c_double)]
+
+
+class DebugMaxpyOpts(C.Structure):
+    """spk_debug_maxpy_opts (include/spk.h)."""
+    _fields_ = [("n", C.c_int64), ("n_dot", C.c_int64), ("n_bd", C.c_int64), ("sign", C.c_double), ("pad", C.c_double),
+                ("nv", C.c_int32), ("nv_live", C.c_int32), ("want_norm", C.c_int32), ("m", C.c_int32), ("bd_mode", C.c_int32),
+                ("w1side", C.c_int32), ("pyth", C.c_int32), ("done", C.c_int32)]
+
+
+class DebugHeadOpts(C.Structure):
+    """spk_debug_head_opts (include/spk.h)."""
+    _fields_ = [("nl", C.c_int64), ("m", C.c_int32), ("packed", C.c_int32), ("fact", C.c_int32), ("jacobi", C.c_int32),
+                ("want_wl", C.c_int32), ("reserved", C.c_int32), ("pad", C.c_double)]
+
+
 def hip_runtimes_mapped():
     """Paths of every libamdhip64 mapped into this process (two = two HIP runtimes: the second finds no device)."""
     try:
@@ -159,6 +178,12 @@ def _load():
     L.spk_debug_finish_timeout.argtypes = [vp, C.c_int]
     L.spk_debug_set_wait_bound.argtypes = [vp, C.c_uint32]
     L.spk_debug_wave_sums.argtypes = [vp, C.c_int, f64p, f64p]
+    L.spk_debug_vec_shape.argtypes = [vp, i64, i32p]
+    L.spk_debug_mdot.argtypes = [vp, C.POINTER(DebugMdotOpts), vp, vp, f64p, f64p]
+    L.spk_debug_maxpy.argtypes = [vp, C.POINTER(DebugMaxpyOpts), vp, f64p, f64p, vp, vp, vp, f64p, vp, vp]
+    L.spk_debug_cycle_norm.argtypes = [vp, i64, i64, i64, i32, dbl, f64p, vp, vp, vp, f64p, vp]
+    L.spk_debug_pack_bd.argtypes = [vp, i64, i32, f64p, vp, C.POINTER(i32)]
+    L.spk_debug_cycle_head.argtypes = [vp, C.POINTER(DebugHeadOpts), f64p, f64p, vp, f64p, vp, vp, vp, f64p, vp, vp]
     L.spk_debug_gs_stamps.argtypes = [vp, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")]
     L.spk_debug_time_products.argtypes = [vp, C.c_int32]
     L.spk_get_product_timing.argtypes = [vp, C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -555,6 +555,198 @@ int spk_debug_wave_sums(spk_ctx *c, int na, const double *in, double *out)
     SPK_CATCH(c)
 }
 
+// ---- Gram-Schmidt kernel hooks: host arrays in, the production wrapper, results out -------------------------------
+namespace {
+int64_t dbg_ld(int64_t n) { return (n + 255) / 256 * 256; }
+// rows of n entries -> device rows of stride ld, entries [n, ld) = pad (one slack row of zeros behind the last)
+void dbg_upload(spk::DevBuf<double> &d, const double *h, int rows, int64_t n, int64_t ld, double pad)
+{
+    d.alloc_raw((size_t)ld * (size_t)std::max(rows, 1), 256);
+    std::vector<double> row((size_t)ld, pad);
+    for (int i = 0; i < std::max(rows, 1); ++i) {
+        if (i < rows && h) std::memcpy(row.data(), h + (size_t)i * (size_t)n, sizeof(double) * (size_t)n);
+        SPK_HIP(hipMemcpy(d.p + (size_t)ld * i, row.data(), sizeof(double) * (size_t)ld, hipMemcpyHostToDevice));
+    }
+}
+void dbg_fill(spk::DevBuf<double> &d, size_t count, double v)
+{
+    std::vector<double> h(count, v);
+    d.upload(h.data(), count, 8);
+}
+// done: -1 -> null, else a device word holding the value
+const int32_t *dbg_done(spk::DevBuf<int32_t> &d, int32_t done)
+{
+    if (done < 0) return nullptr;
+    d.upload(&done, 1, 3);
+    return d.p;
+}
+}  // namespace
+
+int spk_debug_vec_shape(spk_ctx *c, int64_t n, int32_t *out)
+{
+    SPK_TRY(c)
+    if (!out || n <= 0) spk::fail(SPK_ERR_ARG, "spk_debug_vec_shape: bad arguments");
+    spk::k::vec_shapes_probe(n, out);
+    SPK_CATCH(c)
+}
+
+int spk_debug_mdot(spk_ctx *c, const spk_debug_mdot_opts *o, const double *V, const double *V2, const double *w, double *out)
+{
+    SPK_TRY(c)
+    if (!o || !w || !out || o->n <= 0 || o->n_dot < 0 || o->n_dot > o->n || o->nv < 0 || o->nv2 < 0 ||
+        o->nv + o->nv2 > spk::k::kMaxNv - 1 || (o->nv && !V) || (o->nv2 && !V2) || (o->split && (o->nv2 & 1)) || o->done > 1)
+        spk::fail(SPK_ERR_ARG, "spk_debug_mdot: bad arguments");
+    c->ensure_scratch();
+    const int64_t n = o->n, ld = dbg_ld(n);
+    const int rows2 = o->split ? o->nv2 / 2 : o->nv2, k = o->nv + o->nv2 + 1;
+    spk::DevBuf<double> dV, dV2, dw, dout;
+    spk::DevBuf<int32_t> ddone;
+    dbg_upload(dV, V, o->nv, n, ld, o->pad);
+    dbg_upload(dV2, V2, rows2, n, ld, o->pad);
+    dbg_upload(dw, w, 1, n, ld, o->pad);
+    dbg_fill(dout, (size_t)k, SPK_DEBUG_MARKER);
+    const int32_t *done = dbg_done(ddone, o->done);
+    spk::k::mdot(dV.p, ld, o->nv, dw.p, n, o->n_dot, c->fin(dout.p), done, c->stream, o->nv2 ? dV2.p : nullptr, o->nv2, o->split);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    c->check_device_error();
+    SPK_HIP(hipMemcpy(out, dout.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_maxpy(spk_ctx *c, const spk_debug_maxpy_opts *o, const double *V, const double *a, double *w, const double *bd,
+                    const double *dots, double *tb, double *red, double *w1side, double *nrm_out)
+{
+    SPK_TRY(c)
+    if (!o || !w || !a || !red || o->n <= 0 || o->n_dot < 0 || o->n_dot > o->n || o->nv < 0 || o->nv > spk::k::kMaxNv - 1 ||
+        o->nv_live > o->nv || (o->nv && !V) || o->m < 0 || o->m > 8 || o->bd_mode < 0 || o->bd_mode > 2 ||
+        (o->bd_mode && (!bd || o->m == 0)) || (o->bd_mode == 2 && (o->m & 1)) || o->n_bd < 0 || o->n_bd > o->n ||
+        (o->w1side && (!w1side || o->n_bd + o->m > o->n)) || (o->pyth && (!dots || !tb || !nrm_out)) || o->done > 1)
+        spk::fail(SPK_ERR_ARG, "spk_debug_maxpy: bad arguments");
+    c->ensure_scratch();
+    const int64_t n = o->n, ld = dbg_ld(n);
+    const int m = o->m, rows = o->bd_mode == 2 ? m / 2 : (o->bd_mode == 1 ? m : 0);
+    const int live = o->nv_live >= 0 ? o->nv_live : o->nv;
+    spk::DevBuf<double> dV, dw, da, dbd, ddots, dtb, dred, dside, dnrm;
+    spk::DevBuf<int32_t> ddone, dnv;
+    dbg_upload(dV, V, o->nv, n, ld, o->pad);
+    dbg_upload(dw, w, 1, n, ld, o->pad);
+    dbg_upload(dbd, bd, rows, n, ld, o->pad);
+    da.upload(a, (size_t)o->nv, 8);
+    dbg_fill(dred, (size_t)(1 + m), SPK_DEBUG_MARKER);
+    dbg_fill(dside, (size_t)std::max(m, 1), SPK_DEBUG_MARKER);
+    dbg_fill(dnrm, (size_t)(1 + m), SPK_DEBUG_MARKER);
+    spk::k::PythArgs py{};
+    py.m = -1;
+    if (o->pyth) {
+        ddots.upload(dots, (size_t)(live + m + 1), 8);
+        dtb.upload(tb, (size_t)(o->nv + 1) * 8, 8);
+        py = spk::k::PythArgs{m, ddots.p, dtb.p, dnrm.p};
+    }
+    if (o->nv_live >= 0) dnv.upload(&o->nv_live, 1, 3);
+    const int32_t *done = dbg_done(ddone, o->done);
+    spk::k::maxpy(dV.p, ld, o->nv, o->nv_live >= 0 ? dnv.p : nullptr, da.p, o->sign, dw.p, n, o->n_dot,
+                  c->fin(o->want_norm ? dred.p : nullptr), done, c->stream, rows ? dbd.p : nullptr, ld, o->n_bd, m,
+                  o->w1side ? dside.p : nullptr, o->pyth ? &py : nullptr, o->bd_mode == 2);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    c->check_device_error();
+    SPK_HIP(hipMemcpy(w, dw.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(red, dred.p, sizeof(double) * (size_t)(1 + m), hipMemcpyDeviceToHost));
+    if (w1side && m) SPK_HIP(hipMemcpy(w1side, dside.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    if (o->pyth) {
+        SPK_HIP(hipMemcpy(nrm_out, dnrm.p, sizeof(double) * (size_t)(1 + m), hipMemcpyDeviceToHost));
+        SPK_HIP(hipMemcpy(tb, dtb.p, sizeof(double) * (size_t)(o->nv + 1) * 8, hipMemcpyDeviceToHost));
+    }
+    SPK_CATCH(c)
+}
+
+int spk_debug_cycle_norm(spk_ctx *c, int64_t n, int64_t n_dot, int64_t n_bd, int32_t m, double pad, double *x, const double *sa,
+                         const double *sb, const double *bd, double *red, double *w1side)
+{
+    SPK_TRY(c)
+    if (!x || !red || n <= 0 || n_dot < 0 || n_dot > n || n_bd < 0 || n_bd + m > n || m < 0 || m > 8 || (m && (!bd || !w1side)) ||
+        (!sa != !sb))
+        spk::fail(SPK_ERR_ARG, "spk_debug_cycle_norm: bad arguments");
+    c->ensure_scratch();
+    const int64_t ld = dbg_ld(n);
+    spk::DevBuf<double> dx, dsa, dsb, dbd, dred, dside;
+    dbg_upload(dx, sa ? nullptr : x, 1, n, ld, pad);
+    if (sa) {
+        dbg_upload(dsa, sa, 1, n, ld, pad);
+        dbg_upload(dsb, sb, 1, n, ld, pad);
+    }
+    dbg_upload(dbd, bd, m, n, ld, pad);
+    dbg_fill(dred, (size_t)(1 + m), SPK_DEBUG_MARKER);
+    dbg_fill(dside, (size_t)std::max<int>(m, 1), SPK_DEBUG_MARKER);
+    spk::k::sqnorm_bd(dx.p, n, n_dot, dbd.p, ld, n_bd, m, dside.p, c->fin(dred.p), nullptr, c->stream, sa ? dsa.p : nullptr,
+                      sa ? dsb.p : nullptr);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    c->check_device_error();
+    SPK_HIP(hipMemcpy(x, dx.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(red, dred.p, sizeof(double) * (size_t)(1 + m), hipMemcpyDeviceToHost));
+    if (m) SPK_HIP(hipMemcpy(w1side, dside.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_pack_bd(spk_ctx *c, int64_t n, int32_t m, const double *bd, double *bdp, int32_t *bad)
+{
+    SPK_TRY(c)
+    if (!bd || !bad || n <= 0 || m < 1 || m > 8 || (m > 1 && !bdp)) spk::fail(SPK_ERR_ARG, "spk_debug_pack_bd: bad arguments");
+    const int64_t ld = dbg_ld(n);
+    spk::DevBuf<double> dbd, dbdp;
+    spk::DevBuf<int32_t> dbad;
+    dbg_upload(dbd, bd, m, n, ld, 0.0);
+    dbg_upload(dbdp, nullptr, m / 2, n, ld, SPK_DEBUG_MARKER);
+    dbad.alloc(4);
+    spk::k::pack_bd(dbd.p, ld, n, m, dbdp.p, dbad.p, c->stream);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    for (int q = 0; q < m / 2; ++q)
+        SPK_HIP(hipMemcpy(bdp + (size_t)q * (size_t)n, dbdp.p + (size_t)q * ld, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(bad, dbad.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_cycle_head(spk_ctx *c, const spk_debug_head_opts *o, double *v, const double *nrm, const double *w1raw,
+                         const double *dinv, const double *bd, const double *shat, const double *gram, double *z, double *cvec,
+                         double *wl)
+{
+    SPK_TRY(c)
+    if (!o || !v || !nrm || !dinv || !z || o->nl < 2 || (o->nl & 1) || o->m < 0 || o->m > 8 || (o->packed && (o->m & 1)) ||
+        (o->jacobi ? o->m != 0 : !cvec) || (o->m && (!w1raw || !bd || !shat || !gram)) || (o->want_wl && !wl) ||
+        (o->fact != SPK_SCHUR_LOWER && o->fact != SPK_SCHUR_FULL))
+        spk::fail(SPK_ERR_ARG, "spk_debug_cycle_head: bad arguments");
+    const int64_t nl = o->nl, n = nl + o->m, ld = dbg_ld(n);
+    const int m = o->m, rows = o->packed ? m / 2 : m;
+    spk::DevBuf<double> dv, dz, dc, ddinv, dbd, dnrm, dw1, dshat, dgram, dwl;
+    spk::DevBuf<int32_t> ddone;
+    dbg_upload(dv, v, 1, n, ld, o->pad);
+    dbg_upload(dz, nullptr, 1, n, ld, SPK_DEBUG_MARKER);
+    dbg_upload(dc, nullptr, 1, n, ld, SPK_DEBUG_MARKER);
+    dbg_upload(ddinv, dinv, 1, nl, ld, o->pad);
+    {   // the planes cover the nl entries of the A block; what lies behind them is padding
+        dbd.alloc_raw((size_t)ld * (size_t)std::max(rows, 1), 256);
+        std::vector<double> row((size_t)ld, o->pad);
+        for (int i = 0; i < rows; ++i) {
+            std::memcpy(row.data(), bd + (size_t)i * (size_t)nl, sizeof(double) * (size_t)nl);
+            SPK_HIP(hipMemcpy(dbd.p + (size_t)ld * i, row.data(), sizeof(double) * (size_t)ld, hipMemcpyHostToDevice));
+        }
+    }
+    dnrm.upload(nrm, (size_t)(1 + m), 8);
+    dw1.upload(w1raw, (size_t)m, 8);
+    dshat.upload(shat, (size_t)m, 8);
+    dgram.upload(gram, (size_t)m * m, 8);
+    dbg_fill(dwl, (size_t)std::max(m, 1), SPK_DEBUG_MARKER);
+    const int32_t *done = dbg_done(ddone, 0);   // the kernel dereferences its gate word unconditionally
+    spk::k::fused_head(dv.p, dnrm.p, m ? dw1.p : nullptr, ddinv.p, m ? dbd.p : nullptr, ld, m ? dshat.p : nullptr,
+                       m ? dgram.p : nullptr, o->fact, nl, m, dz.p, o->jacobi ? nullptr : dc.p, spk::k::KrylovArrays{}, -1, nullptr,
+                       done, c->stream, nullptr, o->packed, o->want_wl ? dwl.p : nullptr);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    SPK_HIP(hipMemcpy(v, dv.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(z, dz.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    if (cvec) SPK_HIP(hipMemcpy(cvec, dc.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    if (o->want_wl && m) SPK_HIP(hipMemcpy(wl, dwl.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
 int spk_debug_gs_stamps(spk_ctx *c, uint64_t *out)
 {
     SPK_TRY(c)

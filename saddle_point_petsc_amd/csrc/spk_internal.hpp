@@ -376,6 +376,8 @@ struct Finish;
 void finish_probe(const Finish &f, hipStream_t s);
 // test hook: the wave sums of na x 512 values by wave_sum and by wave_sum_multi (see spk_debug_wave_sums)
 void wave_sums_probe(int na, const double *in, double *out, hipStream_t s);
+// test hook: the launch shapes mdot / maxpy pick for n entries and the two knobs they read (see spk_debug_vec_shape)
+void vec_shapes_probe(int64_t n, int32_t *out);
 
 // where a reducing kernel leaves its result: block partials (armed with the sentinel of the
 // "last block reduces" protocol, spk_device.hpp) and the output slot

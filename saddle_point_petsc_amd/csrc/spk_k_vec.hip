@@ -64,6 +64,18 @@ void wave_sums_probe(int na, const double *in, double *out, hipStream_t s)
     }
 }
 
+// Test hook (spk_debug_vec_shape): the shapes mdot and maxpy below pick for a vector of n entries, and their two knobs.
+void vec_shapes_probe(int64_t n, int32_t *out)
+{
+    const int64_t n2 = (n + 1) / 2;
+    const WsShape ws = ws_shape(n2);
+    const VecShape vs = vec_shape(n2), vm = vec_shape(n2, true);
+    const char *e16 = getenv("SPK_VEC_WS16"), *ed = getenv("SPK_VEC_DEEP");
+    const int32_t v[13] = {ws.on, ws.U, ws.grid, vs.T, vs.U, vs.G, vs.grid, vm.T, vm.U, vm.G, vm.grid,
+                           e16 ? atoi(e16) : 1, ed ? atoi(ed) : 0};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
+}
+
 // ---------------------------------------------------------------------------
 // B x for the short-and-wide constraint block (4 rows of ~n/2 entries): one
 // workgroup per (column window, row), 16-byte loads of the row's entries in the
@@ -452,11 +464,10 @@ void mdot(const double *V, int64_t ldv, int nv, const double *w, int64_t n, int6
             continue;
         }
 #define SPK_MDOT_ARGS ng, vs.grid, s, Vp, ldv, cnt, V2p, nv1, w, n2, n_dot, pp, last, oo, f.ar, split, FinErr{f.err, f.fin_ticks}, done
+        // (vec_shape without its maxpy flag always gives G = 4)
         if (vs.T == 512) mdot_launch<512, 4, 4>(SPK_MDOT_ARGS);
         else if (vs.U == 4) mdot_launch<256, 4, 4>(SPK_MDOT_ARGS);
-        else if (vs.U == 2 && vs.G == 8) mdot_launch<256, 2, 8>(SPK_MDOT_ARGS);
         else if (vs.U == 2) mdot_launch<256, 2, 4>(SPK_MDOT_ARGS);
-        else if (vs.G == 8) mdot_launch<256, 1, 8>(SPK_MDOT_ARGS);
         else mdot_launch<256, 1, 4>(SPK_MDOT_ARGS);
 #undef SPK_MDOT_ARGS
         v0 += 40;
@@ -658,18 +669,16 @@ void maxpy(const double *V, int64_t ldv, int nv, const int32_t *nv_dev, const do
     // MP > 0 also switches on the lambda side copy; in single-reduction mode bd is not read
     const int mp = ((bd || pyth) && m > 0) ? (m <= 4 ? 4 : 8) : 0;
 #define SPK_MAXPY_ARGS mp, vs.grid, s, V, ldv, nv, nv_dev, a, coef_sign, w, n2, n_dot, f, bd, ldb, n_bd, m, w1side, py, packed, done
+    // (vec_shape with its maxpy flag gives T = 512, U = 4, G = 4 or T = 256, U <= 2, G = 8, nothing else)
     if (vs.T == 512) maxpy_launch<512, 4, 4>(SPK_MAXPY_ARGS);
-    else if (vs.U == 4) maxpy_launch<256, 4, 4>(SPK_MAXPY_ARGS);
     // thin forms (small vectors), SPK_VEC_DEEP=1 only: the whole basis in ONE group of loads.  Measured SLOWER
     // on the 1/8 slab (30 vectors: 13.2 us against 11.6 with groups of 8; 214 VGPRs leave two waves per SIMD):
     // kept as a knob, off
-    else if (vs.U == 2 && vs.G == 8 && nv > 8 && deep) maxpy_launch<256, 2, 16>(SPK_MAXPY_ARGS);
-    else if (vs.U == 2 && vs.G == 8) maxpy_launch<256, 2, 8>(SPK_MAXPY_ARGS);
-    else if (vs.U == 2) maxpy_launch<256, 2, 4>(SPK_MAXPY_ARGS);
-    else if (vs.G == 8 && nv > 16 && deep) maxpy_launch<256, 1, 32>(SPK_MAXPY_ARGS);
-    else if (vs.G == 8 && nv > 8 && deep) maxpy_launch<256, 1, 16>(SPK_MAXPY_ARGS);
-    else if (vs.G == 8) maxpy_launch<256, 1, 8>(SPK_MAXPY_ARGS);
-    else maxpy_launch<256, 1, 4>(SPK_MAXPY_ARGS);
+    else if (vs.U == 2 && nv > 8 && deep) maxpy_launch<256, 2, 16>(SPK_MAXPY_ARGS);
+    else if (vs.U == 2) maxpy_launch<256, 2, 8>(SPK_MAXPY_ARGS);
+    else if (nv > 16 && deep) maxpy_launch<256, 1, 32>(SPK_MAXPY_ARGS);
+    else if (nv > 8 && deep) maxpy_launch<256, 1, 16>(SPK_MAXPY_ARGS);
+    else maxpy_launch<256, 1, 8>(SPK_MAXPY_ARGS);
 #undef SPK_MAXPY_ARGS
 }
 

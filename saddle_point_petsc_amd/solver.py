@@ -263,6 +263,116 @@ class Context:
         self._chk(lib.spk_debug_wave_sums(self.h, na, vals.reshape(-1), out))
         return out.reshape(2, 8, na)
 
+    # ---- test hooks of the Gram-Schmidt kernels (include/spk.h): host arrays in, the production wrapper, results out ----
+    @staticmethod
+    def _f64(a, shape=None):
+        a = np.ascontiguousarray(a, np.float64)
+        if shape is not None and a.shape != tuple(shape):
+            raise ValueError(f"expected an array of shape {tuple(shape)}, got {a.shape}")
+        return a
+
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+    def debug_vec_shape(self, n):
+        """Launch shapes of a vector of n entries: dict(ws=(on, U, grid), mdot=(T, U, G, grid), maxpy=(T, U, G, grid),
+        ws16=knob, deep=knob)."""
+        out = np.zeros(13, np.int32)
+        self._chk(lib.spk_debug_vec_shape(self.h, n, out))
+        o = [int(x) for x in out]
+        return dict(ws=tuple(o[0:3]), mdot=tuple(o[3:7]), maxpy=tuple(o[7:11]), ws16=o[11], deep=o[12])
+
+    def debug_mdot(self, V, w, n_dot=None, V2=None, split=0, done=-1, pad=0.0):
+        """k::mdot: V (nv, n), w (n,), V2 (nv2, n) dense rows or, with split, (nv2 / 2, n) parity planes.
+        Returns the nv + nv2 + 1 outputs (SPK_DEBUG_MARKER where the launch wrote nothing)."""
+        from ._lib import DebugMdotOpts
+        w = self._f64(w)
+        n = w.shape[0]
+        V = self._f64(V, (np.shape(V)[0], n))
+        rows2 = 0 if V2 is None else np.shape(V2)[0]
+        V2 = None if V2 is None else self._f64(V2, (rows2, n))
+        nv, nv2 = V.shape[0], (2 * rows2 if split else rows2)
+        o = DebugMdotOpts(n, n if n_dot is None else n_dot, nv, nv2, int(split), int(done), float(pad))
+        out = np.zeros(nv + nv2 + 1)
+        self._chk(lib.spk_debug_mdot(self.h, C.byref(o), self._ptr(V), self._ptr(V2), w, out))
+        return out
+
+    def debug_maxpy(self, V, a, w, sign=1.0, n_dot=None, nv_live=-1, want_norm=1, bd=None, packed=0, n_bd=0, m=0,
+                    w1side=0, pyth=None, done=-1, pad=0.0):
+        """k::maxpy: V (nv, n), a (nv,), w (n,); bd: (m, n) dense rows or, packed, (m / 2, n) parity planes;
+        pyth: dict(dots=(nv_live + m + 1,), tb=(nv + 1, 8)) switches the single-reduction rider on.
+        Returns dict(w, red (1 + m), w1side (m), nrm_out (1 + m), tb)."""
+        from ._lib import DebugMaxpyOpts
+        w = self._f64(w).copy()
+        n = w.shape[0]
+        V = self._f64(V, (np.shape(V)[0], n))
+        nv = V.shape[0]
+        a = self._f64(a, (nv,))
+        mode = 0 if bd is None else (2 if packed else 1)
+        bd = None if bd is None else self._f64(bd, ((m // 2 if packed else m), n))
+        live = nv if nv_live < 0 else nv_live
+        dots = tb = None
+        if pyth is not None:
+            dots = self._f64(pyth["dots"], (live + m + 1,))
+            tb = self._f64(pyth["tb"], (nv + 1, 8)).copy()
+        o = DebugMaxpyOpts(n, n if n_dot is None else n_dot, n_bd, float(sign), float(pad), nv, nv_live, int(want_norm), m, mode,
+                           int(w1side), int(pyth is not None), int(done))
+        red, side, nrm_out = np.zeros(1 + m), np.zeros(max(m, 1)), np.zeros(1 + m)
+        self._chk(lib.spk_debug_maxpy(self.h, C.byref(o), self._ptr(V), a, w, self._ptr(bd), self._ptr(dots), self._ptr(tb), red,
+                                      self._ptr(side), self._ptr(nrm_out)))
+        return dict(w=w, red=red, w1side=side[:m], nrm_out=nrm_out, tb=tb)
+
+    def debug_cycle_norm(self, x, bd, n_bd, n_dot=None, sub=None, pad=0.0):
+        """k::sqnorm_bd: x (n,), bd (m, n) dense planes; sub = (sa, sb): x = sa - sb is formed on the way.
+        Returns dict(x, red (1 + m), w1side (m))."""
+        bd = self._f64(bd)
+        m = bd.shape[0]
+        sa = sb = None
+        if sub is not None:
+            sa, sb = self._f64(sub[0]), self._f64(sub[1])
+            x = np.zeros_like(sa)
+        x = self._f64(x).copy()
+        n = x.shape[0]
+        if m and bd.shape != (m, n):
+            raise ValueError("debug_cycle_norm: bd must be (m, n)")
+        red, side = np.zeros(1 + m), np.zeros(max(m, 1))
+        self._chk(lib.spk_debug_cycle_norm(self.h, n, n if n_dot is None else n_dot, n_bd, m, float(pad), x, self._ptr(sa),
+                                           self._ptr(sb), self._ptr(bd) if m else None, red, self._ptr(side)))
+        return dict(x=x, red=red, w1side=side[:m])
+
+    def debug_pack_bd(self, bd):
+        """k::pack_bd: bd (m, n) dense rows -> ((m // 2, n) planes, bad word)."""
+        bd = self._f64(bd)
+        m, n = bd.shape
+        bdp = np.zeros((max(m // 2, 1), n))
+        bad = C.c_int32(-1)
+        self._chk(lib.spk_debug_pack_bd(self.h, n, m, bd, self._ptr(bdp), C.byref(bad)))
+        return bdp[:m // 2], bad.value
+
+    def debug_cycle_head(self, v, nrm, dinv, w1raw=None, bd=None, shat=None, gram=None, fact=SCHUR_FULL, packed=0, jacobi=False,
+                         want_wl=False, pad=0.0):
+        """k::fused_head (no Givens rider, no halo): v (nl + m,), nrm (1 + m,), dinv (nl,), bd (m, nl) dense rows or, packed,
+        (m / 2, nl) planes.  Returns dict(v, z, c, wl); c is None for the Jacobi head."""
+        from ._lib import DebugHeadOpts
+        dinv = self._f64(dinv)
+        nl = dinv.shape[0]
+        nrm = self._f64(nrm)
+        m = nrm.shape[0] - 1
+        v = self._f64(v, (nl + m,)).copy()
+        if m:
+            w1raw, shat, gram = self._f64(w1raw, (m,)), self._f64(shat, (m,)), self._f64(gram, (m, m))
+            bd = self._f64(bd, ((m // 2 if packed else m), nl))
+        else:
+            w1raw = shat = gram = bd = None
+        z = np.zeros(nl + m)
+        c = None if jacobi else np.zeros(nl + m)
+        wl = np.zeros(max(m, 1))
+        o = DebugHeadOpts(nl, m, int(packed), int(fact), int(bool(jacobi)), int(bool(want_wl)), 0, float(pad))
+        self._chk(lib.spk_debug_cycle_head(self.h, C.byref(o), v, nrm, self._ptr(w1raw), dinv, self._ptr(bd), self._ptr(shat),
+                                           self._ptr(gram), z, self._ptr(c), self._ptr(wl)))
+        return dict(v=v, z=z, c=c, wl=wl[:m] if want_wl else None)
+
     def debug_gs_stamps(self):
         """Developer hook (GS_STAMPS=1 builds): (64, 256, 8) time stamps of the fused Gram-Schmidt launches, 100 MHz ticks."""
         out = np.zeros(64 * 256 * 8, np.uint64)

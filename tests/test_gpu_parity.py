@@ -152,8 +152,12 @@ def test_schur_diag_known_answer(spk, appendix_b):
 @pytest.mark.parametrize("n,nv", [(1, 1), (7, 3), (2047, 8), (2048, 9), (4099, 17), (100000, 31), (300001, 40), (65536, 0),
                                   (140001, 5), (262144, 13), (600000, 22), (1200001, 33)])
 def test_mdot_maxpy(ctx, n, nv):
-    """Every form of the two kernels: wave-split MDOT with 2 / 4 / 8 double2 per lane and 4 / 8 / 12
-    vectors per wave, thin-workgroup MAXPY, the streaming forms of both (>= 1 M entries), ragged tails."""
+    """The plain call of the two kernels (n_dot = n, one slab, no planes, sign +1, norm wanted, no gate word) in a default
+    process: the sixteen-wave MDOT (mdot_ws16_kernel) with 2 / 4 / 8 double2 per lane and 1 / 2 / 3 vectors per wave, the
+    thin-workgroup MAXPY (256 threads, 8 vectors in flight, 1 and 2 double2 per thread), and the streaming forms of both at
+    one size (1200001 entries, 33 vectors: NG = 5), ragged tails.  The four-wave MDOT, the 256-thread streaming MDOT and the
+    deep MAXPY run only under their knobs; they, every other argument and every other group count are held by
+    test_gpu_vec_kernels.py."""
     rng = np.random.default_rng(n + nv)
     V = rng.standard_normal((max(nv, 1), n))[:nv]
     w = rng.standard_normal(n)
