@@ -321,6 +321,26 @@ int spk_amg_host_level(const spk_amg_hier *h, int level, int which, int32_t *nro
                        int32_t *rowptr, int32_t *colidx, double *val);
 int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, int32_t *agg);
 
+/* What stands for the Schur complement in SPK_PC_SCHUR (PETSc: -pc_fieldsplit_schur_precondition):
+ *   SPK_SCHUR_PRE_SELFP_DIAG (default): S^ = diag(B diag(A)^-1 B^T), divided by entry by entry;
+ *   SPK_SCHUR_PRE_FULL: the exact complement S = B A^ ^-1 B^T of the A^ ^-1 the split applies -- the V-cycle itself with
+ *     spk_pc_set_amg, diag(A)^-1 without -- as a dense m x m matrix, Cholesky-factored on the host at spk_pc_setup
+ *     (PETSc: -pc_fieldsplit_schur_precondition full -fieldsplit_1_pc_type cholesky).  The set-up also keeps the m dense
+ *     columns W = A^ ^-1 B^T, so every factorisation applies A^ ^-1 ONCE:
+ *         t = W^T x0 ;  DIAG y1 = S^-1 x1 ;  LOWER / FULL y1 = S^-1 (t - x1) ;  UPPER y1 = -S^-1 x1 ;
+ *         y0 = A^ ^-1 x0  (DIAG, LOWER)  |  A^ ^-1 x0 - W y1  (UPPER, FULL).
+ *     With FULL the application is the exact inverse of [A^ B^T; B 0].  spk_fgmres runs it on the step-by-step path,
+ *     spk_minres (DIAG, diag(A)^-1) with the preconditioner as a step of its own.
+ * Sticky like spk_pc_set_inner: call before spk_pc_setup; no effect unless pc_type is SPK_PC_SCHUR.  Refused at
+ * spk_pc_setup with SPK_ERR_UNSUPPORTED (the context stays usable): more than 8 constraint rows, more than one rank,
+ * FP32 inner sweeps beside it (not a linear operator in FP64), and an S that is not positive definite (rank-deficient B). */
+enum { SPK_SCHUR_PRE_SELFP_DIAG = 0, SPK_SCHUR_PRE_FULL = 1 };
+int spk_pc_set_schur_pre(spk_ctx *ctx, int pre);
+/* Copies the dense S (symmetrised, as it was factored) to the host; SPK_ERR_STATE unless the last spk_pc_setup built one. */
+int spk_get_schur_matrix(spk_ctx *ctx, double *S /* m*m, row-major */);
+/* Wall seconds the last spk_pc_setup spent on W, S and the factor (0 without a dense S).  For measurements. */
+int spk_get_schur_setup_seconds(const spk_ctx *ctx, double *seconds);
+
 /* Copies S^ (m doubles) to the host, for inspection. */
 int spk_get_schur_diag(spk_ctx *ctx, double *shat);
 int spk_get_jacobi_diag(spk_ctx *ctx, double *dinv /* n_local */);
@@ -503,6 +523,12 @@ int spk_debug_maxpy(spk_ctx *ctx, const spk_debug_maxpy_opts *o, const double *V
  * red: 1 + m, w1side: m */
 int spk_debug_cycle_norm(spk_ctx *ctx, int64_t n, int64_t n_dot, int64_t n_bd, int32_t m, double pad, double *x, const double *sa,
                          const double *sb, const double *bd, double *red, double *w1side);
+/* k::schur_w_dot / schur_w_y1 / schur_w_out as op_pc_apply chains them for one factorisation (fact: SPK_SCHUR_*): W: m planes
+ * of nl entries, L: the Cholesky factor (m x m, lower), x: nl + m entries.  UPPER / FULL: y0 = s - W y1 with s = src (nl
+ * entries), dinv .* x0 (dinv given) or x0.  y: the WHOLE padded output row, (nl + m) rounded up to 256 entries, filled
+ * with SPK_DEBUG_MARKER before the launches (DIAG / LOWER leave y0 at the marker: their A^-1 x0 is not this file's). */
+int spk_debug_schur_w(spk_ctx *ctx, int64_t nl, int32_t m, int32_t fact, int32_t done, double pad, const double *W, const double *L,
+                      const double *x, const double *src, const double *dinv, double *y);
 /* k::pack_bd: m dense rows of n entries -> m / 2 planes (bdp: (m / 2) x n) and the `bad` word */
 int spk_debug_pack_bd(spk_ctx *ctx, int64_t n, int32_t m, const double *bd, double *bdp, int32_t *bad);
 typedef struct spk_debug_head_opts {

@@ -79,6 +79,11 @@ int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t
 /* -ksp_type as set ("fgmres", "minres", "pipecg", "pipecgrr", or "" before KSPSetFromOptions gave one) and -ksp_norm_type
  * (SPK_NORM_*) */
 int SpkKSPGetType(SpkKSP ksp, const char **type, int32_t *norm_type);
+/* -pc_fieldsplit_schur_precondition selfp | full (SPK_SCHUR_PRE_*) and -fieldsplit_1_pc_type as they resolve: *dense_split1
+ * = 0 for jacobi (entry-by-entry division by S^), 1 for cholesky | lu (the dense factor of the exact S).  Left out,
+ * -fieldsplit_1_pc_type follows the precondition: jacobi for selfp, cholesky for full.  full with jacobi and selfp with
+ * cholesky | lu are refused by SpkKSPSetUp with SPK_ERR_UNSUPPORTED before any GPU work. */
+int SpkKSPGetSchurPre(SpkKSP ksp, int32_t *schur_pre, int32_t *dense_split1);
 int SpkKSPGetContext(SpkKSP ksp, spk_ctx **ctx);
 const char *SpkKSPGetError(SpkKSP ksp);
 const char *SpkKSPConvergedReasonName(int32_t reason);

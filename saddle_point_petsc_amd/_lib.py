@@ -182,6 +182,7 @@ def _load():
     L.spk_debug_mdot.argtypes = [vp, C.POINTER(DebugMdotOpts), vp, vp, f64p, f64p]
     L.spk_debug_maxpy.argtypes = [vp, C.POINTER(DebugMaxpyOpts), vp, f64p, f64p, vp, vp, vp, f64p, vp, vp]
     L.spk_debug_cycle_norm.argtypes = [vp, i64, i64, i64, i32, dbl, f64p, vp, vp, vp, f64p, vp]
+    L.spk_debug_schur_w.argtypes = [vp, i64, i32, i32, i32, dbl, f64p, f64p, f64p, vp, vp, f64p]
     L.spk_debug_pack_bd.argtypes = [vp, i64, i32, f64p, vp, C.POINTER(i32)]
     L.spk_debug_cycle_head.argtypes = [vp, C.POINTER(DebugHeadOpts), f64p, f64p, vp, f64p, vp, vp, vp, f64p, vp, vp]
     L.spk_debug_gs_stamps.argtypes = [vp, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")]
@@ -201,6 +202,9 @@ def _load():
     L.spk_amg_host_info.argtypes = [vp, C.POINTER(AmgInfo)]
     L.spk_amg_host_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
     L.spk_amg_host_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
+    L.spk_pc_set_schur_pre.argtypes = [vp, C.c_int]
+    L.spk_get_schur_matrix.argtypes = [vp, f64p]
+    L.spk_get_schur_setup_seconds.argtypes = [vp, C.POINTER(dbl)]
     L.spk_get_schur_diag.argtypes = [vp, f64p]
     L.spk_get_jacobi_diag.argtypes = [vp, f64p]
     L.spk_get_bd_planes.argtypes = [vp, C.POINTER(i32)]
@@ -265,6 +269,7 @@ def _load():
     L.SpkKSPGetContext.argtypes = [vp, C.POINTER(vp)]
     L.SpkKSPGetAMGOptions.argtypes = [vp, C.c_int, C.POINTER(AmgOpts), C.POINTER(i32)]
     L.SpkKSPGetType.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i32)]
+    L.SpkKSPGetSchurPre.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.SpkKSPGetError.restype = C.c_char_p
     L.SpkKSPGetError.argtypes = [vp]
     L.SpkKSPConvergedReasonName.restype = C.c_char_p

@@ -962,7 +962,7 @@ static double *smooth(spk_ctx *c, AmgLevelDev &D, int l, const double *b, double
     return y;
 }
 
-void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done)
+void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last)
 {
     hipStream_t s = c->stream;
     AmgDev &d = *c->amg_d;
@@ -985,7 +985,8 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
         k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
         cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done);
     }
-    k::amg_out(mode, c->n_local, cur[0], y, done, s);
+    if (last) *last = cur[0];   // the caller's own pass reads the iterate where it lies
+    else k::amg_out(mode, c->n_local, cur[0], y, done, s);
 }
 
 }  // namespace spk

@@ -362,6 +362,33 @@ int spk_get_amg_aggregates(const spk_ctx *cc, int level, int32_t *nnodes, int32_
     SPK_CATCH(c)
 }
 
+int spk_pc_set_schur_pre(spk_ctx *c, int pre)
+{
+    SPK_TRY(c)
+    if (pre != SPK_SCHUR_PRE_SELFP_DIAG && pre != SPK_SCHUR_PRE_FULL) spk::fail(SPK_ERR_ARG, "pc_set_schur_pre: unknown value %d", pre);
+    if (pre != c->schur_pre) c->pc_ready = false;
+    c->schur_pre = pre;
+    SPK_CATCH(c)
+}
+
+int spk_get_schur_matrix(spk_ctx *c, double *S)
+{
+    SPK_TRY(c)
+    if (!S) spk::fail(SPK_ERR_ARG, "null output");
+    if (!c->pc_ready || !c->schur_dense)
+        spk::fail(SPK_ERR_STATE, "no dense Schur complement: spk_pc_set_schur_pre(ctx, SPK_SCHUR_PRE_FULL), then spk_pc_setup "
+                  "with SPK_PC_SCHUR");
+    std::copy(c->schur_S.begin(), c->schur_S.end(), S);
+    SPK_CATCH(c)
+}
+
+int spk_get_schur_setup_seconds(const spk_ctx *c, double *seconds)
+{
+    if (!c || !seconds) return SPK_ERR_ARG;
+    *seconds = c->schur_dense ? c->schur_setup_seconds : 0.0;
+    return SPK_OK;
+}
+
 int spk_get_schur_diag(spk_ctx *c, double *shat)
 {
     SPK_TRY(c)
@@ -383,7 +410,7 @@ int spk_get_jacobi_diag(spk_ctx *c, double *dinv)
 int spk_get_bd_planes(const spk_ctx *c, int32_t *planes)
 {
     if (!c || !planes) return SPK_ERR_ARG;
-    *planes = !c->bd.p ? 0 : (c->bd_packed ? c->m / 2 : c->m);
+    *planes = !c->bd.p || c->schur_dense ? 0 : (c->bd_packed ? c->m / 2 : c->m);   // (a dense S keeps its W there: not the fused path)
     return SPK_OK;
 }
 
@@ -684,6 +711,34 @@ int spk_debug_cycle_norm(spk_ctx *c, int64_t n, int64_t n_dot, int64_t n_bd, int
     SPK_HIP(hipMemcpy(x, dx.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     SPK_HIP(hipMemcpy(red, dred.p, sizeof(double) * (size_t)(1 + m), hipMemcpyDeviceToHost));
     if (m) SPK_HIP(hipMemcpy(w1side, dside.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_schur_w(spk_ctx *c, int64_t nl, int32_t m, int32_t fact, int32_t done, double pad, const double *W, const double *L,
+                      const double *x, const double *src, const double *dinv, double *y)
+{
+    SPK_TRY(c)
+    if (!W || !L || !x || !y || nl <= 0 || m < 1 || m > 8 || fact < SPK_SCHUR_DIAG || fact > SPK_SCHUR_FULL || (src && dinv))
+        spk::fail(SPK_ERR_ARG, "spk_debug_schur_w: bad arguments");
+    c->ensure_scratch();
+    const int64_t ld = dbg_ld(nl + m);
+    spk::DevBuf<double> dW, dL, dx, dsrc, ddinv, dy;
+    spk::DevBuf<int32_t> ddone;
+    dbg_upload(dW, W, m, nl, ld, 0.0);   // the planes' contract: zero beyond the local rows
+    dL.upload(L, (size_t)m * m, 8);
+    dbg_upload(dx, x, 1, nl + m, ld, pad);
+    if (src) dbg_upload(dsrc, src, 1, nl, ld, pad);
+    if (dinv) dbg_upload(ddinv, dinv, 1, nl, ld, pad);
+    dbg_upload(dy, nullptr, 1, nl + m, ld, SPK_DEBUG_MARKER);
+    const int32_t *gate = dbg_done(ddone, done);
+    const spk::k::SchurW w{dW.p, ld, m, dL.p};
+    if (fact == SPK_SCHUR_DIAG || fact == SPK_SCHUR_UPPER) spk::k::schur_w_y1(w, fact, dx.p + nl, dy.p + nl, gate, c->stream);
+    else spk::k::schur_w_dot(w, dx.p, nl, dx.p + nl, dy.p + nl, c->fin(nullptr), gate, c->stream);
+    if (fact == SPK_SCHUR_UPPER || fact == SPK_SCHUR_FULL)
+        spk::k::schur_w_out(w, src ? dsrc.p : dx.p, dinv ? ddinv.p : nullptr, dy.p + nl, dy.p, nl, gate, c->stream);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    c->check_device_error();
+    SPK_HIP(hipMemcpy(y, dy.p, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost));
     SPK_CATCH(c)
 }
 

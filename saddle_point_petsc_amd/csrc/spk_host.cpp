@@ -5,6 +5,7 @@
 // No HIP call and no ROCm header in this file: it is exercised by the CPU-only tests.
 #include "spk_host.hpp"
 
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
@@ -436,6 +437,28 @@ void transpose_rows(int32_t m, int32_t nl, const int32_t *rowptr, const int32_t 
             }
         }
     }, max_threads);
+}
+
+// (G + G^T) / 2 into S, its Cholesky factor (lower, row-major, zeros above) into L.  A pivot at or below the rounding of
+// its own subtraction (64 eps S_jj) counts as zero: the rows of B are then linearly dependent to working precision.
+int schur_dense_factor(int m, const double *G, double *S, double *L)
+{
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) S[(size_t)i * m + j] = 0.5 * (G[(size_t)i * m + j] + G[(size_t)j * m + i]);
+    std::fill(L, L + (size_t)m * m, 0.0);
+    for (int j = 0; j < m; ++j) {
+        double d = S[(size_t)j * m + j];
+        for (int k = 0; k < j; ++k) d -= L[(size_t)j * m + k] * L[(size_t)j * m + k];
+        if (!(d > 64.0 * DBL_EPSILON * S[(size_t)j * m + j])) return j;
+        d = std::sqrt(d);
+        L[(size_t)j * m + j] = d;
+        for (int i = j + 1; i < m; ++i) {
+            double s = S[(size_t)i * m + j];
+            for (int k = 0; k < j; ++k) s -= L[(size_t)i * m + k] * L[(size_t)j * m + k];
+            L[(size_t)i * m + j] = s / d;
+        }
+    }
+    return -1;
 }
 
 }  // namespace spk

@@ -112,4 +112,9 @@ void gather_rows(int32_t m, const int32_t *rowptr, const int32_t *col, const dou
 void transpose_rows(int32_t m, int32_t nl, const int32_t *rowptr, const int32_t *col, const double *v, int32_t *trp, int32_t *tci,
                     double *tv, int max_threads = 0);
 
+// ---- the dense Schur complement of a few constraint rows (spk_pc_set_schur_pre) ----
+// G: m x m as computed; S = (G + G^T) / 2; L: its Cholesky factor (lower, row-major).  Returns -1, or the first pivot that
+// is not positive beyond rounding (S is not positive definite: linearly dependent rows of B)
+int schur_dense_factor(int m, const double *G, double *S, double *L);
+
 }  // namespace spk

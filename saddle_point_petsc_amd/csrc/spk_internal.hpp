@@ -565,6 +565,23 @@ void cvt_vals_f32(const double *v, float *v32, int64_t n, hipStream_t s);
 void schur_y1(int fact, int m, const double *x1, const double *t, const double *shat, double *y1,
               const int32_t *done, hipStream_t s);
 void copy_small(const double *src, double *dst, int n, const int32_t *done, hipStream_t s);
+// The exact Schur complement of m <= 8 constraint rows (spk_k_schurw.hip; spk_pc_set_schur_pre): W = the m dense columns
+// of A^ ^-1 B^T as planes of stride ldw (zero beyond the local rows), L = the Cholesky factor of S = B W (lower, row-major)
+struct SchurW {
+    const double *W;
+    int64_t ldw;
+    int m;
+    const double *L;
+};
+// y1 = S^-1 (W^T x0 - x1) in one pass over x0 and the m planes (fact LOWER / FULL; the signs are schur_y1's); the
+// finishing workgroup solves with L.  f.out is not used
+void schur_w_dot(const SchurW &w, const double *x0, int64_t nl, const double *x1, double *y1, const Finish &f,
+                 const int32_t *done, hipStream_t s);
+// y1 = S^-1 x1 (DIAG) | -S^-1 x1 (UPPER): one wave
+void schur_w_y1(const SchurW &w, int fact, const double *x1, double *y1, const int32_t *done, hipStream_t s);
+// y0 = src - sum_r y1_r W_r over nl entries (dinv != nullptr: dinv .* src stands for src)
+void schur_w_out(const SchurW &w, const double *src, const double *dinv, const double *y1, double *y0, int64_t nl,
+                 const int32_t *done, hipStream_t s);
 
 // Krylov scalar kernels (single wave)
 // where krylov_cycle_begin reports the solve's state to the host (pinned, device-visible memory)
@@ -871,6 +888,14 @@ struct spk_ctx {
     spk::DevBuf<double> bd;                // the m rows of B D as dense vectors of stride ld (fused Schur path)
     spk::DevBuf<double> bdpk;              // the same as m/2 parity-interleaved planes, when the rows allow
     bool bd_packed = false;
+    // the exact Schur complement of a few rows (spk_pc_set_schur_pre): asked for / built by the last set-up.  W = A^ ^-1 B^T:
+    // the V-cycle's columns in sw, or -- A^ = diag(A) -- the planes of bd (then built for every factorisation)
+    int schur_pre = SPK_SCHUR_PRE_SELFP_DIAG;
+    bool schur_dense = false;
+    spk::DevBuf<double> sw, sfac;          // m planes of stride ld; the Cholesky factor of S (m x m, lower)
+    std::vector<double> schur_S;           // S as factored (host, m x m)
+    double schur_setup_seconds = 0.0;      // what W, S and the factor added to the last set-up
+    spk::k::SchurW schur_w() const { return spk::k::SchurW{amg_d ? sw.p : bd.p, ld, m, sfac.p}; }
     // FP32 inner solve (0 sweeps = plain diag(A)^-1)
     int inner_sweeps = 0;
     double inner_omega = 1.0;
@@ -939,9 +964,11 @@ void a_mult(spk_ctx *c, const double *x, double *y, const CsrDev *bt, const doub
             const k::OffDiag *od, const k::GivensRider *rider = nullptr);
 void op_mult(spk_ctx *c, const double *x, double *y, const int32_t *done, bool halo_done = false, bool reuse_bt = false);
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done);
+// out[r] = B_r . (x .* scale) over this rank's columns (scale == nullptr: B_r . x); no all-reduce
+void apply_B(spk_ctx *c, const double *x, const double *scale, double *out, const int32_t *done);
 void pc_setup(spk_ctx *c, int pc_type, int schur_fact);   // (spk_operator.cpp, like set_block below)
 // multigrid (spk_amg.cpp): the host hierarchy from the context's A00 (single rank) and its upload; one V-cycle,
-// mode 0: y = V x, mode 1: y -= V x
+// mode 0: y = V x, mode 1: y -= V x; last != nullptr: y is not written, *last = the buffer of the hierarchy that holds V x
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
 // the same hierarchy built on the device from c->Ad (-spk_gamg_setup device); touches nothing of the context but its
@@ -950,7 +977,7 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c);
 // the test hooks on either route: the host hierarchy's copy, or a download from the device-built levels
 void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
-void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done);
+void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last = nullptr);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);
 void minres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, int norm, spk_result *res,

@@ -27,8 +27,11 @@ struct SpkKSP_s {
     // smoothed-aggregation multigrid: -pc_type gamg (K = A) and -fieldsplit_0_pc_type gamg (the Schur split's A^-1),
     // each with its own options (amg[0]: -pc_gamg_* / -pc_mg_* / -mg_levels_*, amg[1]: the same with -fieldsplit_0_)
     bool pc_gamg = false, split0_gamg = false;
+    int32_t schur_pre = SPK_SCHUR_PRE_SELFP_DIAG;   // -pc_fieldsplit_schur_precondition selfp | full
+    int split1_pc = -1;                             // -fieldsplit_1_pc_type: 0 jacobi, 1 cholesky | lu, -1 follows schur_pre
     spk_amg_opts amg[2];
     bool have_ops = false, is_setup = false, has_B = false;
+    int32_t n_rows_B = 0;   // m (-ksp_view)
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
     int ksp_type = -1;                            // -ksp_type (kFgmres ...), -1: not given
@@ -205,10 +208,12 @@ int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
     rc = spk_set_block(k->ctx, SPK_BLOCK_A00, A->row_begin, A->nrows_local, A->ncols_global, A->rowptr, A->colidx, A->val);
     if (rc != SPK_OK) return from_ctx(k, rc);
     k->has_B = false;
+    k->n_rows_B = 0;
     if (B) {
         rc = spk_set_block(k->ctx, SPK_BLOCK_A10, 0, B->nrows_local, B->ncols_global, B->rowptr, B->colidx, B->val);
         if (rc != SPK_OK) return from_ctx(k, rc);
         k->has_B = B->nrows_local > 0;
+        k->n_rows_B = B->nrows_local;
     }
     k->have_ops = true;
     k->is_setup = false;
@@ -310,7 +315,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             else return bad();
         } else if (key == "-pc_fieldsplit_schur_precondition") {
             if (!val) return need("a type");
-            if (std::string(val) != "selfp") return bad();
+            const std::string v(val);
+            if (v == "selfp") k->schur_pre = SPK_SCHUR_PRE_SELFP_DIAG;
+            else if (v == "full") k->schur_pre = SPK_SCHUR_PRE_FULL;   // the exact S of a few rows, dense (checked at KSPSetUp)
+            else return bad();
         } else if (key == "-pc_fieldsplit_detect_saddle_point") {
             /* implied by the nest */
         } else if (key == "-fieldsplit_0_ksp_type") {
@@ -335,7 +343,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             else return bad();
         } else if (key == "-fieldsplit_1_pc_type") {
             if (!val) return need("a type");
-            if (std::string(val) != "jacobi") return bad();
+            const std::string v(val);
+            if (v == "jacobi") k->split1_pc = 0;
+            else if (v == "cholesky" || v == "lu") k->split1_pc = 1;   // both: the dense factor of S
+            else return bad();
         } else if (key == "-spk_single_reduce") {
             if (!val || !parse_int(val, &k->opts.single_reduce)) return need("an integer (0 off, 1 on)");
         } else if (key == "-spk_iteration_form") {
@@ -351,6 +362,9 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
     k->is_setup = false;
     return SPK_OK;
 }
+
+// -fieldsplit_1_pc_type as it resolves: given, or following -pc_fieldsplit_schur_precondition
+static int split1_dense(SpkKSP k) { return k->split1_pc >= 0 ? k->split1_pc : (k->schur_pre == SPK_SCHUR_PRE_FULL ? 1 : 0); }
 
 // which multigrid option set the selected preconditioner uses: 0 (-pc_type gamg), 1 (-fieldsplit_0_pc_type gamg), -1 none
 static int amg_active(SpkKSP k)
@@ -396,6 +410,19 @@ int SpkKSPSetUp(SpkKSP k)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres needs a symmetric preconditioner and the FP32 inner "
                                                "sweeps are not -- drop -fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or "
                                                "pass -ksp_type fgmres");
+    if (k->pc_type == SPK_PC_SCHUR && k->schur_pre == SPK_SCHUR_PRE_FULL && !split1_dense(k))
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -pc_fieldsplit_schur_precondition full keeps the exact Schur complement "
+                                               "as a dense matrix and -fieldsplit_1_pc_type jacobi would use its diagonal only "
+                                               "-- pass -fieldsplit_1_pc_type cholesky (or lu), or "
+                                               "-pc_fieldsplit_schur_precondition selfp");
+    if (k->pc_type == SPK_PC_SCHUR && k->schur_pre == SPK_SCHUR_PRE_SELFP_DIAG && split1_dense(k))
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -fieldsplit_1_pc_type cholesky | lu factors a dense Schur complement "
+                                               "and -pc_fieldsplit_schur_precondition selfp keeps diag(B diag(A)^-1 B^T) only "
+                                               "-- pass -pc_fieldsplit_schur_precondition full, or -fieldsplit_1_pc_type jacobi");
+    if (k->pc_type == SPK_PC_SCHUR && k->schur_pre == SPK_SCHUR_PRE_FULL && k->inner_richardson && k->inner_sweeps > 0)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -pc_fieldsplit_schur_precondition full needs a linear A^-1 and the FP32 "
+                                               "inner sweeps are not one in FP64 -- drop -fieldsplit_0_ksp_type richardson / "
+                                               "-spk_inner_sweeps, or pass -pc_fieldsplit_schur_precondition selfp");
     const int amg_slot = amg_active(k);
     if (minres && amg_slot >= 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (gamg) is not "
@@ -418,6 +445,8 @@ int SpkKSPSetUp(SpkKSP k)
     rc = spk_pc_set_inner(k->ctx, k->inner_richardson ? k->inner_sweeps : 0, k->inner_omega);
     if (rc != SPK_OK) return from_ctx(k, rc);
     if (amg_slot >= 0) rc = spk_pc_set_amg(k->ctx, &k->amg[amg_slot]);
+    if (rc != SPK_OK) return from_ctx(k, rc);
+    rc = spk_pc_set_schur_pre(k->ctx, k->schur_pre);
     if (rc != SPK_OK) return from_ctx(k, rc);
     rc = spk_pc_setup(k->ctx, k->pc_type, k->schur_fact);
     if (rc != SPK_OK) return from_ctx(k, rc);
@@ -475,6 +504,18 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                         k->replacements);
         }
     }
+    if (k->view && k->pc_type == SPK_PC_SCHUR) {
+        double secs = 0.0;
+        const bool full = k->schur_pre == SPK_SCHUR_PRE_FULL;
+        spk_get_schur_setup_seconds(k->ctx, &secs);
+        if (full)
+            std::printf("  PC fieldsplit: schur_precondition full, m = %d constraint rows, S = B A^-1 B^T dense (%s), "
+                        "fieldsplit_1 cholesky, set-up %.6f s\n", (int)k->n_rows_B, amg_active(k) >= 0 ? "A^-1 = the V-cycle" :
+                        "A^-1 = diag(A)^-1", secs);
+        else
+            std::printf("  PC fieldsplit: schur_precondition selfp, m = %d constraint rows, S^ = diag(B diag(A)^-1 B^T), "
+                        "fieldsplit_1 jacobi\n", (int)k->n_rows_B);
+    }
     if (k->view && amg_active(k) >= 0) {
         spk_amg_info ai;
         if (spk_get_amg_info(k->ctx, &ai) == SPK_OK) {
@@ -524,6 +565,13 @@ int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)
     if (!k) return SPK_ERR_ARG;
     if (type) *type = k->ksp_type < 0 ? "" : kKspTypes[k->ksp_type];
     if (norm_type) *norm_type = k->norm_type;
+    return SPK_OK;
+}
+int SpkKSPGetSchurPre(SpkKSP k, int32_t *pre, int32_t *dense_split1)
+{
+    if (!k) return SPK_ERR_ARG;
+    if (pre) *pre = k->schur_pre;
+    if (dense_split1) *dense_split1 = split1_dense(k);
     return SPK_OK;
 }
 int SpkKSPGetContext(SpkKSP k, spk_ctx **c) { if (!k || !c) return SPK_ERR_ARG; *c = k->ctx; return SPK_OK; }

@@ -35,7 +35,7 @@ void minres(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm,
     MinresState *ms = F.st;
     const int32_t *done = F.done();
     const bool unprec = norm == SPK_NORM_UNPRECONDITIONED;
-    const bool fused = o.fused != 0;
+    const bool fused = o.fused != 0 && !c->schur_dense;   // a dense S: the preconditioner as a step of its own
     const double *dinv = c->pc_type == SPK_PC_NONE ? nullptr : c->dinv.p;
     const double *shat = c->pc_type == SPK_PC_SCHUR ? c->shat.p : nullptr;
     const k::Finish f = c->fin(F.out);

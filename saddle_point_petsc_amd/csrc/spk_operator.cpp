@@ -718,6 +718,52 @@ static void bd_planes(spk_ctx *c, int pc_type, int schur_fact)
     }
 }
 
+// The exact Schur complement of a few rows (spk_pc_set_schur_pre): W = A^ ^-1 B^T as m dense planes -- column r is one
+// V-cycle on B^T e_r, or, A^ = diag(A), the plane build_bd writes -- then S = B W column by column, symmetrised and
+// Cholesky-factored on the host; the factor goes to the device.  Throws when S is not positive definite.
+static void schur_dense_build(spk_ctx *c)
+{
+    hipStream_t s = c->stream;
+    const int m = c->m;
+    const auto t0 = std::chrono::steady_clock::now();
+    const double *W = nullptr;
+    if (c->amg_d) {
+        std::vector<double> eye((size_t)m * m, 0.0);
+        for (int r = 0; r < m; ++r) eye[(size_t)r * m + r] = 1.0;
+        DevBuf<double> e;
+        e.upload(eye.data(), eye.size());
+        c->sw.alloc((size_t)c->ld * m, 16);   // zero-filled: the V-cycle writes the local rows, the pad stays zero
+        for (int r = 0; r < m; ++r) {
+            k::bt_update(3, c->Bt, c->dinv.p, nullptr, e.p + (size_t)r * m, c->tmp.p, nullptr, s);   // B^T e_r
+            amg_apply(c, c->tmp.p, c->sw.p + (size_t)c->ld * r, 0, nullptr);
+        }
+        W = c->sw.p;
+    } else {
+        // D B^T is what the fused path streams as `bd`: one copy serves both (here for every factorisation and any parity)
+        c->sw.release();
+        c->bdpk.release();
+        c->bd_packed = false;
+        c->bd.alloc((size_t)c->ld * m, 16);
+        k::build_bd(c->Bt, c->dinv.p, m, c->ld, c->bd.p, s);
+        W = c->bd.p;
+    }
+    DevBuf<double> g;
+    g.alloc((size_t)m * m);
+    for (int r = 0; r < m; ++r) apply_B(c, W + (size_t)c->ld * r, nullptr, g.p + (size_t)r * m, nullptr);   // column r of S
+    std::vector<double> G((size_t)m * m), L((size_t)m * m);
+    SPK_HIP(hipMemcpyAsync(G.data(), g.p, sizeof(double) * G.size(), hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    c->check_device_error();
+    c->schur_S.assign((size_t)m * m, 0.0);
+    const int bad = schur_dense_factor(m, G.data(), c->schur_S.data(), L.data());
+    if (bad >= 0)
+        fail(SPK_ERR_UNSUPPORTED, "pc_setup: the exact Schur complement S = B A^-1 B^T (%d x %d) is not positive definite at "
+             "pivot %d: the constraint rows are linearly dependent (rank-deficient B) -- remove the redundant row, or "
+             "keep -pc_fieldsplit_schur_precondition selfp", m, m, bad);
+    c->sfac.upload(L.data(), L.size());
+    c->schur_setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
 void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
 {
     if (!c->have_A) fail(SPK_ERR_STATE, "pc_setup: no A00 block");
@@ -726,6 +772,21 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     if (schur_fact < SPK_SCHUR_DIAG || schur_fact > SPK_SCHUR_FULL) fail(SPK_ERR_ARG, "pc_setup: unknown schur_fact %d", schur_fact);
     // multigrid standing for A^-1: one rank only (every rank sees the same communicator size: all refuse together), built
     // on the host before anything of the context changes -- a refusal leaves it as it was
+    // the exact Schur complement (spk_pc_set_schur_pre): its limits, equally before anything changes
+    const bool dense = pc_type == SPK_PC_SCHUR && c->schur_pre == SPK_SCHUR_PRE_FULL;
+    if (dense) {
+        if (c->b_general || c->m > 8)
+            fail(SPK_ERR_UNSUPPORTED, "pc_setup: the exact Schur complement (schur_precondition full) is dense and kept for at "
+                 "most 8 constraint rows; this block has %d%s -- keep -pc_fieldsplit_schur_precondition selfp", (int)c->m,
+                 c->b_general ? " (a general sparse block)" : "");
+        if (c->comm->size() > 1)
+            fail(SPK_ERR_UNSUPPORTED, "pc_setup: the exact Schur complement (schur_precondition full) runs on one rank only; "
+                 "this communicator has %d", c->comm->size());
+        if (c->inner_sweeps > 0)
+            fail(SPK_ERR_UNSUPPORTED, "pc_setup: the exact Schur complement (schur_precondition full) needs a linear A^-1 and "
+                 "the FP32 inner sweeps are not one in FP64 -- call spk_pc_set_inner(ctx, 0, omega), or keep "
+                 "-pc_fieldsplit_schur_precondition selfp");
+    }
     std::unique_ptr<spk_amg_hier> amg;
     std::unique_ptr<AmgDev> amg_dev;   // -spk_gamg_setup device: built on the device, equally before anything changes
     if (c->amg_on) {
@@ -752,6 +813,22 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     if (c->m > 0) schur_diag(c);
     fp32_copies(c);
     bd_planes(c, pc_type, schur_fact);
+    c->schur_dense = false;
+    c->pc_ready = false;
+    if (dense) {
+        try {
+            schur_dense_build(c);
+        } catch (...) {   // a set-up without a preconditioner: released, the context takes the next spk_pc_setup
+            c->sw.release(); c->sfac.release(); c->bd.release();
+            c->schur_S.clear();
+            throw;
+        }
+        c->schur_dense = true;
+    } else {
+        c->sw.release(); c->sfac.release();
+        c->schur_S.clear();
+        c->schur_setup_seconds = 0.0;
+    }
     SPK_HIP(hipStreamSynchronize(s));
     c->pc_type = pc_type;
     c->schur_fact = schur_fact;

@@ -147,7 +147,7 @@ void a_mult(spk_ctx *c, const double *x, double *y, const CsrDev *bt, const doub
 // out[r] = B_r . (x .* scale)  over this rank's columns (scale == nullptr: B_r . x); MatMult on the (1,0) block.
 // m <= 8: the column-window kernel for every row.  General block: short rows row by row through the CSR
 // stream kernel, its few long rows through the window kernel (results scattered to their row numbers).
-static void apply_B(spk_ctx *c, const double *x, const double *scale, double *out, const int32_t *done)
+void apply_B(spk_ctx *c, const double *x, const double *scale, double *out, const int32_t *done)
 {
     hipStream_t s = c->stream;
     if (!c->b_general) {
@@ -230,12 +230,41 @@ static void ahat_apply(spk_ctx *c, const double *x, double *y, int mode, const i
     else inner_apply(c, x, y, mode, done);
 }
 
+// The Schur fieldsplit with the exact complement of a few rows (spk_pc_set_schur_pre): S dense and factored, W = A^ ^-1 B^T
+// kept.  t = W^T x0 needs x0 alone, so the multiplier step comes first; A^ ^-1 is applied once in every factorisation.
+static void schur_dense_apply(spk_ctx *c, const double *x, double *y, const int32_t *done)
+{
+    hipStream_t s = c->stream;
+    const int32_t nl = c->n_local;
+    const int fact = c->schur_fact;
+    const k::SchurW w = c->schur_w();
+    double *y1 = y + nl;
+    if (fact == SPK_SCHUR_DIAG || fact == SPK_SCHUR_UPPER) k::schur_w_y1(w, fact, x + nl, y1, done, s);
+    else k::schur_w_dot(w, x, nl, x + nl, y1, c->fin(nullptr), done, s);
+    const bool update = fact == SPK_SCHUR_UPPER || fact == SPK_SCHUR_FULL;   // y0 = A^ ^-1 x0 - W y1
+    if (c->amg_d && update) {
+        const double *last = nullptr;   // the V-cycle's last iterate, read where it lies instead of amg_out's copy
+        amg_apply(c, x, y, 0, done, &last);
+        k::schur_w_out(w, last, nullptr, y1, y, nl, done, s);
+    } else if (c->amg_d) {
+        amg_apply(c, x, y, 0, done);
+    } else if (update) {
+        k::schur_w_out(w, x, c->dinv.p, y1, y, nl, done, s);
+    } else {
+        k::jacobi(c->dinv.p, x, y, nl, done, s);
+    }
+}
+
 void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done)
 {
     hipStream_t s = c->stream;
     const int32_t nl = c->n_local, m = c->m;
     const double *x0 = x, *x1 = x + nl;
     double *y0 = y, *y1 = y + nl;
+    if (c->schur_dense && c->pc_type == SPK_PC_SCHUR) {
+        c->bt_cached = nullptr;
+        return schur_dense_apply(c, x, y, done);
+    }
     // general block, UPPER / FULL: the last thing written to the scratch vector is B^T y1 (bt_update) -- op_mult on the
     // result may take it from there
     c->bt_cached = (c->b_general && c->Bt.ntiles > 0 && m > 0 && c->pc_type == SPK_PC_SCHUR &&
@@ -421,7 +450,8 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     p.refine = o.cgs_refine;
     // fused Schur path: VecScale + PC + B^T part of the operator in one pass ("head"), B D w' in the MAXPY pass, the
     // Givens step of iteration j-1 inside the head kernel of iteration j
-    p.schur = o.fused && c->bd.p && c->pc_type == SPK_PC_SCHUR;
+    // (a dense Schur complement, like the V-cycle and the FP32 sweeps, runs on the step-by-step path: its bd planes are W)
+    p.schur = o.fused && c->bd.p && c->pc_type == SPK_PC_SCHUR && !c->schur_dense;
     // the same head kernel without a constraint block: Jacobi on K = A (the reference as written,
     // SaddlePointProblem.c:66, and BASELINE config 2): VecScale + PCApply_Jacobi + deferred Givens
     const bool jac = o.fused && !p.schur && c->pc_type == SPK_PC_JACOBI && m == 0 && c->even_all && c->nonempty_all &&

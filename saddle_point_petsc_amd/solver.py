@@ -16,6 +16,8 @@ DIVERGED_INDEFINITE_PC = -8
 DIVERGED_INDEFINITE_MAT = -10
 PIPECGRR_TAU_DEFAULT = 1e-6   # SPK_PIPECGRR_TAU_DEFAULT (include/spk.h)
 _NORMS = {"unpreconditioned": NORM_UNPRECONDITIONED, "natural": NORM_NATURAL}
+SCHUR_PRE_SELFP_DIAG, SCHUR_PRE_FULL = 0, 1
+_SCHUR_PRES = {"selfp": SCHUR_PRE_SELFP_DIAG, "full": SCHUR_PRE_FULL}
 
 
 def default_opts(**kw):
@@ -341,6 +343,19 @@ class Context:
                                            self._ptr(sb), self._ptr(bd) if m else None, red, self._ptr(side)))
         return dict(x=x, red=red, w1side=side[:m])
 
+    def debug_schur_w(self, W, L, x, fact=SCHUR_FULL, src=None, dinv=None, done=-1, pad=0.0):
+        """The dense-Schur kernels as op_pc_apply chains them: W (m, nl) planes, L (m, m) Cholesky factor, x (nl + m,).
+        Returns the whole padded output row (SPK_DEBUG_MARKER where nothing was written)."""
+        W = self._f64(W)
+        m, nl = W.shape
+        L = self._f64(L, (m, m))
+        x = self._f64(x, (nl + m,))
+        src = None if src is None else self._f64(src, (nl,))
+        dinv = None if dinv is None else self._f64(dinv, (nl,))
+        y = np.zeros((nl + m + 255) // 256 * 256)
+        self._chk(lib.spk_debug_schur_w(self.h, nl, m, int(fact), int(done), float(pad), W, L, x, self._ptr(src), self._ptr(dinv), y))
+        return y
+
     def debug_pack_bd(self, bd):
         """k::pack_bd: bd (m, n) dense rows -> ((m // 2, n) planes, bad word)."""
         bd = self._f64(bd)
@@ -399,10 +414,15 @@ class Context:
         self._chk(lib.spk_set_block(self.h, which, A.row_begin if which == BLOCK_A00 else 0, nrows,
                                     A.ncols, A.rowptr, A.colidx, A.val))
 
-    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None):
+    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None, schur_pre="selfp"):
         """inner_sweeps > 0: FP32 damped-Jacobi Richardson sweeps stand for diag(A)^-1.
         amg: None (off), True (defaults) or a dict of spk_amg_opts fields: one smoothed-aggregation V-cycle stands
-        for A^-1 (PC_JACOBI: M^-1 on K = A; PC_SCHUR: inside the fieldsplit)."""
+        for A^-1 (PC_JACOBI: M^-1 on K = A; PC_SCHUR: inside the fieldsplit).
+        schur_pre: "selfp" (S^ = diag(B diag(A)^-1 B^T)) or "full" (the exact S = B A^ ^-1 B^T of at most 8 rows, dense
+        and Cholesky-factored; PC_SCHUR only)."""
+        if schur_pre not in _SCHUR_PRES:
+            raise ValueError(f"schur_pre must be one of {sorted(_SCHUR_PRES)}")
+        self._chk(lib.spk_pc_set_schur_pre(self.h, _SCHUR_PRES[schur_pre]))
         if amg is None or amg is False:
             self._chk(lib.spk_pc_set_amg(self.h, None))
             self._chk(lib.spk_pc_set_inner(self.h, inner_sweeps, inner_omega))
@@ -460,6 +480,18 @@ class Context:
         out = np.zeros(self.sizes()["m"])
         self._chk(lib.spk_get_schur_diag(self.h, out))
         return out
+
+    def schur_matrix(self):
+        """The dense S = B A^ ^-1 B^T (m x m) the last pc_setup(..., schur_pre="full") factored."""
+        m = self.sizes()["m"]
+        out = np.zeros(m * m)
+        self._chk(lib.spk_get_schur_matrix(self.h, out))
+        return out.reshape(m, m)
+
+    def schur_setup_seconds(self):
+        v = C.c_double()
+        self._chk(lib.spk_get_schur_setup_seconds(self.h, C.byref(v)))
+        return v.value
 
     def bd_planes(self):
         v = C.c_int32()
@@ -719,6 +751,12 @@ class KSP:
         o, sel = AmgOpts(), C.c_int32()
         self._chk(lib.SpkKSPGetAMGOptions(self.h, 1 if fieldsplit0 else 0, C.byref(o), C.byref(sel)))
         return amg_opts_dict(o), bool(sel.value)
+
+    def getSchurPre(self):
+        """(-pc_fieldsplit_schur_precondition, -fieldsplit_1_pc_type) as they resolve: ('selfp' | 'full', 'jacobi' | 'cholesky')."""
+        p, d = C.c_int32(), C.c_int32()
+        self._chk(lib.SpkKSPGetSchurPre(self.h, C.byref(p), C.byref(d)))
+        return {v: k for k, v in _SCHUR_PRES.items()}[p.value], "cholesky" if d.value else "jacobi"
 
     def getType(self):
         """-ksp_type as set: 'fgmres', 'minres', 'pipecg', 'pipecgrr', or '' before setFromOptions gave one."""

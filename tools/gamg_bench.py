@@ -6,7 +6,12 @@ Two systems: K = A (gamg in Jacobi's slot; FGMRES + Jacobi; MINRES + Jacobi) and
 (-fieldsplit_0_pc_type gamg; FGMRES + the plain Schur FULL; MINRES + Schur DIAG).  Per gamg row: set-up time of both
 routes (host build + upload, and -spk_gamg_setup device; each after one warm-up build, in this process) with the
 iterations and time of the solve on the device-built hierarchy, levels, rows and operator complexity, the V-cycle's time (spk_pc_apply on device vectors, back to back) against its
-byte model per level, iterations and wall time to rtol.  One JSON line per row."""
+byte model per level, iterations and wall time to rtol.  One JSON line per row.
+    python tools/gamg_bench.py --schur-full [--reps 3]
+The saddle system with FULL + gamg under both Schur preconditions, from one context per grid: after one warm-up set-up and
+solve of each, --reps alternating rounds of selfp (S^ = diag(B diag(A)^-1 B^T), today's rows) and full (the exact dense
+S = B V B^T, schur_pre="full").  Per row: iterations and solve time to rtol, the true residual, microseconds per PCApply
+(back to back on device vectors), what W and S added to the set-up, and K = A's iteration count on the same grid."""
 import argparse
 import json
 import os
@@ -26,6 +31,9 @@ ap.add_argument("--max-it", type=int, default=20000)
 ap.add_argument("--gamg-only", action="store_true", help="leave out the Jacobi / MINRES rows (a short kernel trace)")
 ap.add_argument("--setup-only", choices=["host", "device", "both"], help="only build the K = A hierarchy (after one "
                 "warm-up build of each route asked for) and print one line per grid: a kernel trace of the set-up alone")
+ap.add_argument("--schur-full", action="store_true", help="only the saddle rows of FULL + gamg, selfp and the exact Schur "
+                "complement alternating in one process")
+ap.add_argument("--reps", type=int, default=3, help="--schur-full: alternating rounds after the warm-up round")
 a = ap.parse_args()
 
 
@@ -103,8 +111,36 @@ def setup_times(A, Bk, pc, fact, routes=("host", "device")):
     return t
 
 
+def schur_full_rows(grid, A, f):
+    B, g = S.AssembleOperator_Constraints(grid)
+    rhs = np.concatenate([f, g])
+    c, _ = ctx(A, None, S.PC_JACOBI, 0, amg=True)
+    ka = solve(c, f, "fgmres")
+    c.close()
+    c = S.Context(0)
+    c.set_block(S.BLOCK_A00, A)
+    c.set_block(S.BLOCK_A10, B)
+    for rep in range(-1, a.reps):   # -1: the warm-up round (first-use allocations of either mode), not printed
+        for pre in ("selfp", "full"):
+            t0 = time.perf_counter()
+            c.pc_setup(S.PC_SCHUR, S.SCHUR_FULL, amg=True, schur_pre=pre)
+            setup_wall = time.perf_counter() - t0
+            conv = solve(c, rhs, "fgmres")
+            pc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            print(json.dumps(dict(system="saddle_full", grid=grid, solver="fgmres", pc="gamg", schur_pre=pre, rep=rep,
+                                  setup_seconds=round(setup_wall, 4), schur_setup_seconds=round(c.schur_setup_seconds(), 6),
+                                  pc_apply_us=round(pc_ms * 1e3, 1), ka_its=ka["its"], ka_seconds=ka["seconds"], **conv)),
+                  flush=True)
+    c.close()
+
+
 for grid in a.grids:
     A, f = S.AssembleOperator_Laplace(grid)
+    if a.schur_full:
+        schur_full_rows(grid, A, f)
+        continue
     if a.setup_only:
         routes = ("host", "device") if a.setup_only == "both" else (a.setup_only,)
         t = setup_times(A, None, S.PC_JACOBI, 0, routes)
