@@ -310,11 +310,40 @@ int spk_get_amg_level(const spk_ctx *ctx, int level, int which, int32_t *nrows, 
                       int32_t *rowptr, int32_t *colidx, double *val);
 /* Test hook: the aggregate of every node of a level of the context's hierarchy (-1: isolated); agg NULL for the size. */
 int spk_get_amg_aggregates(const spk_ctx *ctx, int level, int32_t *nnodes, int32_t *agg);
+/* Reuse of the interpolation (PETSc: -pc_gamg_reuse_interpolation).  Sticky like spk_pc_set_schur_pre, default 0.  With
+ * reuse on, a spk_pc_setup that finds a hierarchy an earlier set-up built with reuse on, the same spk_amg_opts (field by
+ * field, route and block size included), the same local size and padded vector length, and a diagonal A00 block with the
+ * pattern that hierarchy was built on REFRESHES it instead of building it: the aggregates, the tentative and the smoothed
+ * prolongators, the restrictions and every sparsity pattern stay, bit for bit (the omega inside P_l is not revisited);
+ * every A_{l+1} = ((R_l A_l P_l) + (R_l A_l P_l)^T) / 2, every D_l^-1, the Ritz values with the Chebyshev intervals and
+ * coefficients, and the dense coarse inverse are computed again from the new values, on the route that built (host: the
+ * host products and an upload of values; device: three kernels per level into buffers the build kept, in the build's
+ * summation order -- unchanged values give the build's bits; an A00 multiplied by a power of two gives the build's
+ * lambda_max to the bit and a V-cycle scaled by exactly its inverse: the Lanczos and the coarse Cholesky run on the
+ * operator scaled back to the binade it was built in).  The case is a time step, a Newton step or a coefficient
+ * sweep on a fixed mesh.  Anything else is a full build, silently.  To compare patterns the set-up keeps a device copy of
+ * rowptr / colidx as the context stores them (about 150 MB at 1024 x 1024, bs 2; the same pattern in another column order
+ * counts as different), and the device route the patterns and values of A_l P_l and R_l A_l P_l; reuse = 0 releases
+ * both and leaves the hierarchy.  A refresh fails where a build would (an empty Chebyshev interval, a coarse operator that
+ * is not positive definite: SPK_ERR_ARG); the half-refreshed hierarchy is then dropped and the context is without a
+ * preconditioner until the next spk_pc_setup, which builds.  Everything behind the hierarchy (diag(A)^-1, S^, the B D
+ * planes, W / S / the factor of SPK_SCHUR_PRE_FULL) is set up behind a refresh as behind a build.  With reuse never
+ * set, spk_pc_setup does what it did before this option existed. */
+int spk_pc_set_amg_reuse(spk_ctx *ctx, int reuse);
+/* *refreshed: 1 when the last spk_pc_setup refreshed the hierarchy, 0 when it built it; *seconds: the wall time of that
+ * refresh or build (the pattern comparison and the pattern copy included), up to a device synchronise.  Either may be
+ * NULL.  SPK_ERR_STATE without a hierarchy. */
+int spk_get_amg_reuse_info(const spk_ctx *ctx, int32_t *refreshed, double *seconds);
 /* Host-only builder (no GPU): the same hierarchy from a square CSR matrix, for tests.  agg: the aggregate of every
  * node of a level (-1: isolated, in no aggregate).  Errors: spk_last_error(NULL). */
 typedef struct spk_amg_hier spk_amg_hier;
 int spk_amg_build_host(int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *val,
                        const spk_amg_opts *opts, spk_amg_hier **out);
+/* The refresh of spk_pc_set_amg_reuse on a host hierarchy: val holds the new values of the same pattern, rowptr[n] of them
+ * in the CSR order spk_amg_build_host was given -- the call has no length to check: passing that many is the caller's
+ * part (AmgHierarchy.refresh of the Python package checks it); read the result through the spk_amg_host_* calls.  After a failure
+ * (SPK_ERR_ARG, as from the build) the hierarchy is empty: only spk_amg_destroy_host remains. */
+int spk_amg_refresh_host(spk_amg_hier *h, const double *val);
 int spk_amg_destroy_host(spk_amg_hier *h);
 int spk_amg_host_info(const spk_amg_hier *h, spk_amg_info *info);
 int spk_amg_host_level(const spk_amg_hier *h, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,

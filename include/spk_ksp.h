@@ -76,6 +76,12 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * refused by SpkKSPSetUp with SPK_ERR_UNSUPPORTED.  (SpkKSPGetOptions reports -pc_type gamg as SPK_PC_JACOBI, the
  * slot the V-cycle takes.) */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);
+/* -pc_gamg_reuse_interpolation <bool> (fieldsplit0 = 1: -fieldsplit_0_pc_gamg_reuse_interpolation) as read; default
+ * false, a name without a value means true.  On: SpkKSPSetUp passes spk_pc_set_amg_reuse(ctx, 1), so a second
+ * SpkKSPSetOperators with new values on the same pattern followed by SpkKSPSetUp (or SpkKSPSolve) on the same SpkKSP
+ * refreshes the hierarchy instead of building it (-ksp_view says which the last set-up did).  Given for a gamg that is
+ * not selected, SpkKSPSetUp refuses it with SPK_ERR_UNSUPPORTED. */
+int SpkKSPGetAMGReuse(SpkKSP ksp, int fieldsplit0, int32_t *reuse);
 /* -ksp_type as set ("fgmres", "minres", "pipecg", "pipecgrr", or "" before KSPSetFromOptions gave one) and -ksp_norm_type
  * (SPK_NORM_*) */
 int SpkKSPGetType(SpkKSP ksp, const char **type, int32_t *norm_type);

@@ -198,7 +198,10 @@ def _load():
     L.spk_get_amg_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
     L.spk_get_amg_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
     L.spk_amg_build_host.argtypes = [i32, i32p, i32p, f64p, C.POINTER(AmgOpts), C.POINTER(vp)]
+    L.spk_amg_refresh_host.argtypes = [vp, vp]
     L.spk_amg_destroy_host.argtypes = [vp]
+    L.spk_pc_set_amg_reuse.argtypes = [vp, C.c_int]
+    L.spk_get_amg_reuse_info.argtypes = [vp, C.POINTER(i32), C.POINTER(dbl)]
     L.spk_amg_host_info.argtypes = [vp, C.POINTER(AmgInfo)]
     L.spk_amg_host_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
     L.spk_amg_host_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
@@ -268,6 +271,7 @@ def _load():
     L.SpkKSPGetOptions.argtypes = [vp, C.POINTER(Opts), C.POINTER(i32), C.POINTER(i32)]
     L.SpkKSPGetContext.argtypes = [vp, C.POINTER(vp)]
     L.SpkKSPGetAMGOptions.argtypes = [vp, C.c_int, C.POINTER(AmgOpts), C.POINTER(i32)]
+    L.SpkKSPGetAMGReuse.argtypes = [vp, C.c_int, C.POINTER(i32)]
     L.SpkKSPGetType.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i32)]
     L.SpkKSPGetSchurPre.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.SpkKSPGetError.restype = C.c_char_p

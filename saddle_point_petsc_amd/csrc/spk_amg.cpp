@@ -2,6 +2,8 @@
 // A00 block by one loop (build_levels) over two routes -- HostRoute: on the host, then uploaded (the default); DevRoute:
 // on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the V-cycle's launch sequence (kernels:
 // spk_k_amg.hip).
+// With reuse on (spk_pc_set_amg_reuse) a second, shorter loop (refresh_levels) over the same two routes puts new values
+// of A00 through a hierarchy whose aggregates, prolongators and patterns stay.
 //
 // Every step is deterministic (fixed traversal orders, no hashing of pointers, a fixed Lanczos start vector): two
 // builds of the same matrix give the same bytes, and so do two V-cycles.  DESIGN.md "Algebraic multigrid" has the
@@ -19,18 +21,21 @@ void set_create_error(const std::string &m);   // spk_api.cpp: what spk_last_err
 
 namespace {
 
-// columns sorted within each row (the caller's order is arbitrary)
-void sort_rows(HostCsr &A)
+// columns sorted within each row (the caller's order is arbitrary); perm: where every sorted entry stood
+void sort_rows(HostCsr &A, std::vector<int32_t> *perm = nullptr)
 {
-    std::vector<std::pair<int32_t, double>> row;
+    struct Entry { int32_t first; double second; int32_t from; };
+    std::vector<Entry> row;
+    if (perm) perm->resize(A.ci.size());
     for (int32_t i = 0; i < A.nrows; ++i) {
         const int32_t k0 = A.rp[(size_t)i], k1 = A.rp[(size_t)i + 1];
         row.clear();
-        for (int32_t k = k0; k < k1; ++k) row.emplace_back(A.ci[(size_t)k], A.v[(size_t)k]);
+        for (int32_t k = k0; k < k1; ++k) row.push_back({A.ci[(size_t)k], A.v[(size_t)k], k});
         std::sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
         for (int32_t k = k0; k < k1; ++k) {
             A.ci[(size_t)k] = row[(size_t)(k - k0)].first;
             A.v[(size_t)k] = row[(size_t)(k - k0)].second;
+            if (perm) (*perm)[(size_t)k] = row[(size_t)(k - k0)].from;
         }
     }
 }
@@ -190,11 +195,14 @@ constexpr int kLanczosSteps = 30;
 
 // extreme Ritz values of D^-1 A after kLanczosSteps Lanczos steps on the similar D^-1/2 A D^-1/2, from a fixed start vector.
 // Ritz values lie inside the spectrum: both estimates approach from within (lmax from below).
-void lanczos(const HostCsr &A, const std::vector<double> &dinv, double *lmin, double *lmax)
+// a_scale: a power of two; the steps run on a_scale A (every product with it is exact, and 1 changes no bit).  The refresh
+// passes the one that brings A back to the binade it was built in, so that an operator rescaled by a power of two --
+// where sqrt(d / 2) is no power-of-two multiple of sqrt(d) -- gives the Ritz values of the build to the bit.
+void lanczos(const HostCsr &A, const std::vector<double> &dinv, double *lmin, double *lmax, double a_scale = 1.0)
 {
     const int32_t n = A.nrows;
     std::vector<double> s((size_t)n), q((size_t)n), qp((size_t)n, 0.0), w((size_t)n), t((size_t)n);
-    for (int32_t i = 0; i < n; ++i) s[(size_t)i] = std::sqrt(std::fabs(dinv[(size_t)i]));
+    for (int32_t i = 0; i < n; ++i) s[(size_t)i] = std::sqrt(std::fabs(dinv[(size_t)i] / a_scale));
     double nq = 0.0;
     for (int32_t i = 0; i < n; ++i) {   // integer hash: the same start vector on every machine
         uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
@@ -212,7 +220,7 @@ void lanczos(const HostCsr &A, const std::vector<double> &dinv, double *lmin, do
         for (int32_t i = 0; i < n; ++i) {
             double acc = 0.0;
             for (int32_t p = A.rp[(size_t)i]; p < A.rp[(size_t)i + 1]; ++p) acc += A.v[(size_t)p] * t[(size_t)A.ci[(size_t)p]];
-            w[(size_t)i] = s[(size_t)i] * acc;
+            w[(size_t)i] = s[(size_t)i] * (acc * a_scale);
             a += w[(size_t)i] * q[(size_t)i];
         }
         al.push_back(a);
@@ -324,13 +332,14 @@ HostCsr tentative(const std::vector<int32_t> &agg, int32_t na, int bs)
     return P;
 }
 
-// dense inverse of the SPD coarsest operator through Cholesky (symmetrised)
-std::vector<double> coarse_inverse(const HostCsr &A)
+// dense inverse of the SPD coarsest operator through Cholesky (symmetrised); a_scale as in lanczos: the factor is that
+// of a_scale A and the inverse is scaled back, both exactly
+std::vector<double> coarse_inverse(const HostCsr &A, double a_scale = 1.0)
 {
     const int32_t n = A.nrows;
     std::vector<double> L((size_t)n * n, 0.0), X((size_t)n * n, 0.0);
     for (int32_t i = 0; i < n; ++i)
-        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k) L[(size_t)i * n + A.ci[(size_t)k]] = A.v[(size_t)k];
+        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k) L[(size_t)i * n + A.ci[(size_t)k]] = A.v[(size_t)k] * a_scale;
     for (int32_t j = 0; j < n; ++j) {
         double d = L[(size_t)j * n + j];
         for (int32_t k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
@@ -361,11 +370,36 @@ std::vector<double> coarse_inverse(const HostCsr &A)
             const double s = 0.5 * (X[(size_t)i * n + j] + X[(size_t)j * n + i]);
             X[(size_t)i * n + j] = X[(size_t)j * n + i] = s;
         }
+    if (a_scale != 1.0)
+        for (double &x : X) x *= a_scale;
     return X;
 }
 
 using Clock = std::chrono::steady_clock;
 double seconds_since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+// sum |D_0^-1|: exactly homogeneous under a power of two (every partial sum scales with it), so its binade tells by
+// which power of two an operator was rescaled since the build
+double abs_sum(const std::vector<double> &x)
+{
+    double t = 0.0;
+    for (double v : x) t += std::fabs(v);
+    return t;
+}
+// the power of two that brings an operator with this sum |D^-1| back to the binade of the one with sum `built`
+double binade_scale(double built, double now)
+{
+    if (!(built > 0.0) || !(now > 0.0) || !std::isfinite(built) || !std::isfinite(now)) return 1.0;
+    return std::ldexp(1.0, std::ilogb(now) - std::ilogb(built));   // A grew by 2^k: |D^-1| shrank by it, A is scaled by 2^-k
+}
+
+// the smoother's interval on level l from the extreme Ritz values: the esteig rule and its refusal, for both loops
+void smoother_interval(const spk_amg_opts &o, int l, double lmin, double lmax, double *lo, double *hi)
+{
+    *lo = o.esteig[0] * lmin + o.esteig[1] * lmax, *hi = o.esteig[2] * lmin + o.esteig[3] * lmax;
+    if (o.smoother == SPK_AMG_CHEBYSHEV && !(*lo > 0.0 && *hi > *lo))
+        fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", *lo, *hi, l);
+}
 
 // The set-up, stated once: the level loop with every rule of the algorithm and the whole of `info`.  A route supplies
 // what differs between the host and the device -- where the matrices live and what computes them:
@@ -396,9 +430,8 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
         double lmin = 0.0, lmax = 0.0;
         r.ritz(l, &lmin, &lmax);
         info.lambda_max[l] = lmax;
-        const double lo = o.esteig[0] * lmin + o.esteig[1] * lmax, hi = o.esteig[2] * lmin + o.esteig[3] * lmax;
-        if (o.smoother == SPK_AMG_CHEBYSHEV && !(lo > 0.0 && hi > lo))
-            fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", lo, hi, l);
+        double lo = 0.0, hi = 0.0;
+        smoother_interval(o, l, lmin, lmax, &lo, &hi);
         r.set_interval(l, lo, hi);
         r.coarsen(l, bs, std::move(agg), na, 4.0 / (3.0 * lmax), o.nsmooths);
     }
@@ -413,14 +446,45 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
     info.setup_seconds = seconds_since(t0);
 }
 
+// The refresh (spk_pc_set_amg_reuse), stated once: new values in A_0 and its D^-1, everything that was decided from the old
+// ones kept -- the aggregates, P_tent, P_l (with the omega that smoothed it), R_l and every pattern.  Per level the Ritz
+// values and the interval by the build's rule, then
+//   regalerkin(l): A_{l+1} = (R A_l P + (R A_l P)^T) / 2 on its pattern, and its D^-1
+// a_scale: the power of two by which the route's Lanczos and the coarse Cholesky see every A_l scaled (binade_scale)
+// and at the end the coarse inverse.  levels(): of the kept hierarchy; check(): throws when a kernel reported an error.
+// A throw leaves the hierarchy half-refreshed: the caller drops it.
+template <class Route>
+void refresh_levels(Route &r, const spk_amg_opts &o, Clock::time_point t0, spk_amg_info &info)
+{
+    const int L = r.levels();
+    double tot = 0.0;
+    for (int l = 0;; ++l) {
+        info.rows[l] = r.rows(l);
+        info.nnz[l] = r.nnz(l);
+        tot += (double)info.nnz[l];
+        if (l + 1 == L) break;
+        double lmin = 0.0, lmax = 0.0, lo = 0.0, hi = 0.0;
+        r.ritz(l, &lmin, &lmax);
+        info.lambda_max[l] = lmax;
+        smoother_interval(o, l, lmin, lmax, &lo, &hi);
+        r.set_interval(l, lo, hi);
+        r.regalerkin(l);
+    }
+    r.check();
+    r.set_coarse_inverse(coarse_inverse(r.coarsest(), r.a_scale));
+    info.operator_complexity = tot / (double)std::max<int64_t>(info.nnz[0], 1);
+    info.setup_seconds = seconds_since(t0);
+}
+
 // the host route: every matrix a HostCsr of h.lv (level 0 and its D^-1 are there before the loop runs)
 struct HostRoute {
     AmgHier &h;
+    double a_scale = 1.0;   // the refresh's (see lanczos)
     AmgLevel &lv(int l) const { return h.lv[(size_t)l]; }
     int32_t rows(int l) const { return lv(l).A.nrows; }
     int64_t nnz(int l) const { return lv(l).A.nnz(); }
     void graph(int l, int bs, double theta, std::vector<int32_t> &gp, std::vector<int32_t> &gi) const { node_graph(lv(l).A, bs, theta, gp, gi); }
-    void ritz(int l, double *lmin, double *lmax) const { lanczos(lv(l).A, lv(l).dinv, lmin, lmax); }
+    void ritz(int l, double *lmin, double *lmax) const { lanczos(lv(l).A, lv(l).dinv, lmin, lmax, a_scale); }
     void set_interval(int l, double lo, double hi) const { lv(l).lo = lo, lv(l).hi = hi; }
     void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths) const
     {
@@ -440,6 +504,18 @@ struct HostRoute {
         h.lv.back().A = add(0.5, Ac, 0.5, transpose(Ac));   // exactly symmetric (the products agree to rounding)
         h.lv.back().dinv = diag_inv(h.lv.back().A);
     }
+    int levels() const { return (int)h.lv.size(); }
+    void regalerkin(int l) const
+    {
+        AmgLevel &L = lv(l), &N = lv(l + 1);
+        const HostCsr Ac = spgemm(L.R, spgemm(L.A, L.P));
+        HostCsr An = add(0.5, Ac, 0.5, transpose(Ac));
+        if (An.rp != N.A.rp || An.ci != N.A.ci)   // (no product drops an entry: the patterns follow from the kept ones)
+            fail(SPK_ERR_STATE, "amg: the refreshed operator of level %d has another pattern than the kept one", l + 1);
+        N.A.v = std::move(An.v);
+        N.dinv = diag_inv(N.A);
+    }
+    void check() const {}
     const HostCsr &coarsest() const { return h.lv.back().A; }
     void set_coarse_inverse(std::vector<double> cinv) const { h.cinv = std::move(cinv); }
 };
@@ -504,14 +580,35 @@ void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
     const auto t0 = Clock::now();
     amg_check_opts(o);
     if (A.nrows != A.ncols || A.nrows <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
-    sort_rows(A);
+    std::vector<int32_t> perm;
+    sort_rows(A, &perm);
     h = AmgHier{};
     h.o = o;
+    h.perm = std::move(perm);
     h.lv.emplace_back();
     h.lv[0].A = std::move(A);
     h.lv[0].dinv = diag_inv(h.lv[0].A);
+    h.dinv_sum = abs_sum(h.lv[0].dinv);
     HostRoute r{h};
     build_levels(r, o.block_size > 0 ? o.block_size : detect_bs(h.lv[0].A), o, SPK_AMG_SETUP_HOST, t0, h.info);
+}
+
+void amg_refresh(AmgHier &h, const double *val)
+{
+    const auto t0 = Clock::now();
+    if (h.lv.empty()) fail(SPK_ERR_STATE, "amg: no hierarchy to refresh (an earlier refresh failed)");
+    AmgLevel &F = h.lv[0];
+    for (size_t k = 0; k < F.A.v.size(); ++k) F.A.v[k] = val[(size_t)h.perm[k]];
+    F.dinv = diag_inv(F.A);
+    HostRoute r{h, binade_scale(h.dinv_sum, abs_sum(F.dinv))};
+    try {
+        refresh_levels(r, h.o, t0, h.info);
+    } catch (...) {   // half-refreshed: never to be read or applied
+        h.lv.clear();
+        h.cinv.clear();
+        std::memset(&h.info, 0, sizeof h.info);
+        throw;
+    }
 }
 
 void AmgHier::level(int l, int which, const CsrOut &out) const
@@ -609,6 +706,25 @@ static void alloc_cycle_vectors(AmgDev &d, int64_t ld)
     }
 }
 
+// reuse on: what the next set-up compares before it refreshes -- the options, the sizes and a device copy of the
+// diagonal block's pattern as the context stores it
+static void keep_pattern(spk_ctx *c, AmgDev &d)
+{
+    if (!d.reuse) d.reuse = std::make_unique<AmgReuse>();
+    AmgReuse &ru = *d.reuse;
+    ru.o = c->amg_opts;
+    ru.bs = ctx_block_size(c, c->amg_opts);
+    ru.n = c->n_local;
+    ru.nnz = c->Ad.nnz;
+    ru.ld = c->ld;
+    ru.rowptr.alloc_raw((size_t)ru.n + 1);
+    ru.colidx.alloc_raw((size_t)ru.nnz);
+    ru.flag.alloc(2);
+    SPK_HIP(hipMemcpyAsync(ru.rowptr.p, c->Ad.rowptr.p, sizeof(int32_t) * ((size_t)ru.n + 1), hipMemcpyDeviceToDevice, c->stream));
+    if (ru.nnz)
+        SPK_HIP(hipMemcpyAsync(ru.colidx.p, c->Ad.colidx.p, sizeof(int32_t) * (size_t)ru.nnz, hipMemcpyDeviceToDevice, c->stream));
+}
+
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
 {
     const auto t0 = Clock::now();
@@ -631,6 +747,7 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
     }
     d->cinv.upload(h.cinv.data(), h.cinv.size());
     alloc_cycle_vectors(*d, c->ld);
+    if (c->amg_reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info = h.info;
     d->info.setup_seconds += seconds_since(t0);
@@ -741,7 +858,8 @@ void dev_transpose(CsrDev &T, const CsrDev &A, hipStream_t s)
 
 // the 30 Lanczos steps of `lanczos` with the level's own product (level 0: the context's layout, else the CSR kernel);
 // the two sums of a step come back to the host, which keeps the tridiagonal and the break rule
-void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, double *lmin, double *lmax)
+void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, double *lmin, double *lmax,
+                 double a_scale = 1.0)
 {
     hipStream_t s = c->stream;
     DevBuf<double> sv, q, qp, w, t, aw, res;
@@ -754,7 +872,7 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
         SPK_HIP(hipStreamSynchronize(s));
         return h;
     };
-    k::amgs_lz_init(n, dinv, sv.p, q.p, f, s);
+    k::amgs_lz_init(n, dinv, 1.0 / a_scale, sv.p, q.p, f, s);
     const double nq = std::sqrt(sum());
     k::amgs_lz_scale(n, nq, q.p, sv.p, q.p, t.p, s);
     std::vector<double> al, be{0.0};
@@ -763,7 +881,7 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
     for (int j = 0; j < kk; ++j) {
         if (A) k::amg_spmv(*A, t.p, aw.p, nullptr, s);
         else a_mult(c, t.p, aw.p, nullptr, nullptr, nullptr, false, nullptr);
-        k::amgs_lz_dot(n, sv.p, aw.p, w.p, qc, f, s);
+        k::amgs_lz_dot(n, sv.p, aw.p, a_scale, w.p, qc, f, s);
         const double a = sum();
         al.push_back(a);
         k::amgs_lz_update(n, a, be.back(), qc, qo, w.p, f, s);
@@ -775,6 +893,18 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
     }
     c->check_device_error();
     ritz_extremes(al, be, lmin, lmax);
+}
+
+// sum |x| in the fixed order of the sentinel finish (abs_sum of the host: exactly homogeneous under a power of two)
+double dev_abs_sum(spk_ctx *c, const double *x, int32_t n, DevBuf<double> &res)
+{
+    hipStream_t s = c->stream;
+    k::amgs_abs_sum(n, x, c->fin(res.p), s);
+    double h = 0.0;
+    SPK_HIP(hipMemcpyAsync(&h, res.p, sizeof h, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    c->check_device_error();
+    return h;
 }
 
 // the context's CSR as it is when every row ascends, else a sorted copy in `copy`
@@ -803,6 +933,9 @@ struct DevRoute {
     const CsrDev &A0;
     const double *dinv0;
     hipStream_t s;
+    bool keep = false;        // reuse on: coarsen keeps A_l P_l and R_l A_l P_l for regalerkin
+    int32_t *err = nullptr;   // regalerkin's error word
+    double a_scale = 1.0;     // the refresh's (see lanczos)
     const CsrDev &A(int l) const { return l == 0 ? A0 : d.lv[(size_t)l].A; }
     const double *dinv(int l) const { return l == 0 ? dinv0 : d.lv[(size_t)l].dinv.p; }
     int32_t rows(int l) const { return A(l).nrows; }
@@ -829,7 +962,7 @@ struct DevRoute {
         if (ne) SPK_HIP(hipMemcpyAsync(gi.data(), gid.p, sizeof(int32_t) * gi.size(), hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
     }
-    void ritz(int l, double *lmin, double *lmax) const { dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax); }
+    void ritz(int l, double *lmin, double *lmax) const { dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax, a_scale); }
     void set_interval(int l, double lo, double hi) { smoother_coeffs(d.lv[(size_t)l], o, lo, hi); }
     void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths)
     {
@@ -873,6 +1006,28 @@ struct DevRoute {
         N.n = N.A.nrows;
         N.dinv.alloc((size_t)N.n, 8);
         k::extract_diag_inv(N.A, N.dinv.p, s);
+        if (keep) {
+            AmgLevelDev &K = d.lv[(size_t)l];
+            K.AP = std::move(AP);
+            K.Ac = std::move(Ac);
+        }
+    }
+    int levels() const { return (int)d.lv.size(); }
+    // three launches into buffers the build left: nothing is allocated, counted or scanned
+    void regalerkin(int l)
+    {
+        AmgLevelDev &L = d.lv[(size_t)l], &N = d.lv[(size_t)l + 1];
+        k::amgs_spgemm_numeric(A(l), L.P, L.AP, err, s);
+        k::amgs_spgemm_numeric(L.R, L.AP, L.Ac, err, s);
+        k::amgs_symmetrise_numeric(L.Ac, N.A, err, s);
+        k::extract_diag_inv(N.A, N.dinv.p, s);
+    }
+    void check() const
+    {
+        int32_t bad = 0;
+        SPK_HIP(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+        if (bad) fail(SPK_ERR_STATE, "amg: a product of the refresh has no slot in the kept pattern");
     }
     HostCsr coarsest() const { return dev_csr_download(A((int)d.lv.size() - 1), true, s); }
     void set_coarse_inverse(const std::vector<double> &cinv) { d.cinv.upload(cinv.data(), cinv.size()); }
@@ -887,22 +1042,105 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
     amg_check_opts(o);
     c->ensure_scratch();
     if (c->n_local <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
-    CsrDev copy;
-    const CsrDev &A0 = sorted_rows(c, copy);
-    const int cbs = ctx_block_size(c, o), bs = cbs > 0 ? cbs : detect_bs(dev_csr_download(A0, false, c->stream));
     auto d = std::make_unique<AmgDev>();
+    if (c->amg_reuse) d->reuse = std::make_unique<AmgReuse>();   // level 0's sorted copy and D^-1 outlive the build
+    CsrDev copy_here;
+    DevBuf<double> dinv0_here;
+    CsrDev &copy = d->reuse ? d->reuse->sorted : copy_here;
+    DevBuf<double> &dinv0 = d->reuse ? d->reuse->dinv0 : dinv0_here;
+    const CsrDev &A0 = sorted_rows(c, copy);
+    if (d->reuse) d->reuse->use_sorted = &A0 == &copy;
+    const int cbs = ctx_block_size(c, o), bs = cbs > 0 ? cbs : detect_bs(dev_csr_download(A0, false, c->stream));
     d->lv.reserve((size_t)o.max_levels);   // the levels own device buffers and never move
     d->lv.emplace_back();
     d->lv[0].n = c->n_local;
-    DevBuf<double> dinv0;
     dinv0.alloc((size_t)c->n_local, 8);
     k::extract_diag_inv(c->Ad, dinv0.p, c->stream);
-    DevRoute r{c, *d, o, A0, dinv0.p, c->stream};
+    if (d->reuse) {
+        d->reuse->sum.alloc(8);
+        d->reuse->dinv_sum = dev_abs_sum(c, dinv0.p, c->n_local, d->reuse->sum);
+    }
+    DevRoute r{c, *d, o, A0, dinv0.p, c->stream, d->reuse != nullptr, nullptr};
     build_levels(r, bs, o, SPK_AMG_SETUP_DEVICE, t0, d->info);
     alloc_cycle_vectors(*d, c->ld);
+    if (d->reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info.setup_seconds = seconds_since(t0);   // the vectors count too, up to the synchronise
     return d;
+}
+
+bool amg_can_refresh(spk_ctx *c)
+{
+    if (!c->amg_reuse || !c->amg_on || !c->amg_d || !c->amg_d->reuse) return false;
+    AmgReuse &ru = *c->amg_d->reuse;
+    const spk_amg_opts &a = c->amg_opts, &b = ru.o;
+    bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
+                a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
+                a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup;
+    for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
+    if (!same || ctx_block_size(c, a) != ru.bs || c->n_local != ru.n || c->Ad.nnz != ru.nnz || c->ld != ru.ld) return false;
+    if ((a.setup == SPK_AMG_SETUP_HOST) != (c->amg_h != nullptr)) return false;
+    hipStream_t s = c->stream;
+    SPK_HIP(hipMemsetAsync(ru.flag.p, 0, 2 * sizeof(int32_t), s));
+    k::amgs_pattern_equal(ru.rowptr.p, c->Ad.rowptr.p, (int64_t)ru.n + 1, ru.flag.p, s);
+    k::amgs_pattern_equal(ru.colidx.p, c->Ad.colidx.p, ru.nnz, ru.flag.p, s);
+    int32_t differ = 1;
+    SPK_HIP(hipMemcpyAsync(&differ, ru.flag.p, sizeof differ, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    return differ == 0;
+}
+
+void amg_refresh_ctx(spk_ctx *c)
+{
+    const auto t0 = Clock::now();
+    hipStream_t s = c->stream;
+    AmgDev &d = *c->amg_d;
+    AmgReuse &ru = *d.reuse;
+    const size_t L = d.lv.size();
+    if (c->amg_h) {   // the host route: the values down, the host refresh, the values of the levels up
+        AmgHier &h = c->amg_h->h;
+        std::vector<double> val((size_t)c->Ad.nnz);
+        if (!val.empty()) SPK_HIP(hipMemcpyAsync(val.data(), c->Ad.val.p, sizeof(double) * val.size(), hipMemcpyDeviceToHost, s));
+        SPK_HIP(hipStreamSynchronize(s));
+        amg_refresh(h, val.data());
+        for (size_t l = 0; l < L; ++l) {
+            const AmgLevel &H = h.lv[l];
+            AmgLevelDev &D = d.lv[l];
+            if (l > 0) {
+                if (H.A.nnz()) SPK_HIP(hipMemcpyAsync(D.A.val.p, H.A.v.data(), sizeof(double) * H.A.v.size(), hipMemcpyHostToDevice, s));
+                SPK_HIP(hipMemcpyAsync(D.dinv.p, H.dinv.data(), sizeof(double) * H.dinv.size(), hipMemcpyHostToDevice, s));
+            }
+            if (l + 1 < L) smoother_coeffs(D, h.o, H.lo, H.hi);
+        }
+        SPK_HIP(hipMemcpyAsync(d.cinv.p, h.cinv.data(), sizeof(double) * h.cinv.size(), hipMemcpyHostToDevice, s));
+        SPK_HIP(hipDeviceSynchronize());   // (the host vectors are pageable: the copies have left them by now anyway)
+        d.info = h.info;
+    } else {
+        c->ensure_scratch();
+        if (ru.use_sorted) {   // the build's sorted copy of level 0 again, in its buffers
+            if (ru.nnz) {
+                SPK_HIP(hipMemcpyAsync(ru.sorted.colidx.p, c->Ad.colidx.p, sizeof(int32_t) * (size_t)ru.nnz, hipMemcpyDeviceToDevice, s));
+                SPK_HIP(hipMemcpyAsync(ru.sorted.val.p, c->Ad.val.p, sizeof(double) * (size_t)ru.nnz, hipMemcpyDeviceToDevice, s));
+            }
+            k::amgs_sort_rows(ru.sorted.rowptr.p, ru.sorted.colidx.p, ru.sorted.val.p, ru.n, s);
+        }
+        k::extract_diag_inv(c->Ad, ru.dinv0.p, s);
+        const double a_scale = binade_scale(ru.dinv_sum, dev_abs_sum(c, ru.dinv0.p, ru.n, ru.sum));
+        DevRoute r{c, d, ru.o, ru.use_sorted ? ru.sorted : c->Ad, ru.dinv0.p, s, true, ru.flag.p + 1, a_scale};
+        refresh_levels(r, ru.o, t0, d.info);
+        SPK_HIP(hipDeviceSynchronize());
+    }
+    d.info.setup_seconds = seconds_since(t0);
+}
+
+void amg_drop_reuse(spk_ctx *c)
+{
+    if (!c->amg_d || !c->amg_d->reuse) return;
+    c->amg_d->reuse.reset();
+    for (AmgLevelDev &D : c->amg_d->lv) {
+        D.AP = CsrDev{};
+        D.Ac = CsrDev{};
+    }
 }
 
 // the test hooks: the host hierarchy where pc_setup kept one, else one download from the device-built levels
@@ -1038,6 +1276,14 @@ int spk_amg_build_host(int32_t n, const int32_t *rowptr, const int32_t *colidx, 
     auto h = std::make_unique<spk_amg_hier>();
     spk::amg_build(h->h, std::move(A), *o);
     *out = h.release();
+    SPK_HOST_CATCH
+}
+
+int spk_amg_refresh_host(spk_amg_hier *h, const double *val)
+{
+    if (!h || !val) return SPK_ERR_ARG;
+    SPK_HOST_TRY
+    spk::amg_refresh(h->h, val);
     SPK_HOST_CATCH
 }
 

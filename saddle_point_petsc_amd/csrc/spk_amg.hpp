@@ -37,12 +37,17 @@ struct AmgHier {
     std::vector<AmgLevel> lv;
     std::vector<double> cinv;   // dense inverse of the coarsest A, row-major
     spk_amg_info info{};        // as the set-up loop filled it (setup_seconds: the host build)
+    double dinv_sum = 0.0;      // sum |D_0^-1| at the build: its binade is the refresh's reference (amg_refresh)
+    std::vector<int32_t> perm;  // sorted position of level 0 -> index in the CSR arrays the caller gave (amg_refresh)
     void level(int l, int which, const CsrOut &out) const;   // copy one matrix of a level out (see spk_get_amg_level)
 };
 
 // throws spk::Error
 void amg_check_opts(const spk_amg_opts &o);
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o);
+// new values (in the order of the arrays amg_build was given) on the kept aggregates, prolongators and patterns: every
+// A_l, D_l^-1, interval and the coarse inverse again.  A throw leaves h empty.
+void amg_refresh(AmgHier &h, const double *val);
 
 }  // namespace spk
 

@@ -362,6 +362,24 @@ int spk_get_amg_aggregates(const spk_ctx *cc, int level, int32_t *nnodes, int32_
     SPK_CATCH(c)
 }
 
+int spk_pc_set_amg_reuse(spk_ctx *c, int reuse)
+{
+    SPK_TRY(c)
+    c->amg_reuse = reuse != 0;
+    if (!c->amg_reuse) spk::amg_drop_reuse(c);   // the pattern copy and the refresh's buffers go; the hierarchy stays
+    SPK_CATCH(c)
+}
+
+int spk_get_amg_reuse_info(const spk_ctx *cc, int32_t *refreshed, double *seconds)
+{
+    spk_ctx *c = const_cast<spk_ctx *>(cc);
+    SPK_TRY(c)
+    need_amg(c);
+    if (refreshed) *refreshed = c->amg_refreshed ? 1 : 0;
+    if (seconds) *seconds = c->amg_reuse_seconds;
+    SPK_CATCH(c)
+}
+
 int spk_pc_set_schur_pre(spk_ctx *c, int pre)
 {
     SPK_TRY(c)

@@ -806,9 +806,16 @@ void amgs_add(double a, const CsrDev &A, double b, const CsrDev &B, const double
               double *cv, int32_t *cnt, hipStream_t s);
 void amgs_col_count(const int32_t *ci, int64_t nnz, int32_t *cnt, hipStream_t s);
 void amgs_transpose_fill(const CsrDev &A, int32_t *pos, int32_t *tci, double *tv, hipStream_t s);   // rows unsorted: amgs_sort_rows
-void amgs_lz_init(int64_t n, const double *dinv, double *sv, double *q, const Finish &f, hipStream_t s);
+// the refresh: *flag |= 1 where a and b differ; the values of C = A B and of N = (Ac + Ac^T) / 2 on their kept sorted
+// patterns in the build's summation order (*err |= 1: a product without a slot; nothing is written outside the row)
+void amgs_pattern_equal(const int32_t *a, const int32_t *b, int64_t n, int32_t *flag, hipStream_t s);
+void amgs_spgemm_numeric(const CsrDev &A, const CsrDev &B, CsrDev &C, int32_t *err, hipStream_t s);
+void amgs_symmetrise_numeric(const CsrDev &Ac, CsrDev &N, int32_t *err, hipStream_t s);
+// dscale, ascale: powers of two (1 on a build) -- sv = sqrt|dinv dscale|, w = sv (aw ascale): the steps on ascale A
+void amgs_lz_init(int64_t n, const double *dinv, double dscale, double *sv, double *q, const Finish &f, hipStream_t s);
+void amgs_abs_sum(int64_t n, const double *x, const Finish &f, hipStream_t s);   // f.out[0] = sum |x|
 void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, double *q, double *t, hipStream_t s);
-void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double *w, const double *q, const Finish &f, hipStream_t s);
+void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double ascale, double *w, const double *q, const Finish &f, hipStream_t s);
 void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s);
 }  // namespace k
 
@@ -817,15 +824,32 @@ struct AmgLevelDev {
     int32_t n = 0;
     CsrDev A, P, R;                    // A: levels >= 1; P, R: all but the coarsest
     CsrDev Ptent;                      // device-built hierarchies only (test hook)
+    CsrDev AP, Ac;                     // device-built with reuse on: A_l P_l and R_l A_l P_l, patterns and the refresh's value buffers
     std::vector<int32_t> agg;          // device-built hierarchies only: the aggregates the host step returned
     DevBuf<double> dinv;               // levels >= 1
     DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
 };
+// what a set-up with reuse on (spk_pc_set_amg_reuse) keeps beside the hierarchy, so that the next one can refresh it
+struct AmgReuse {
+    spk_amg_opts o{};                  // as spk_pc_set_amg gave them
+    int bs = 0;                        // the node size the context resolved (0: detected from the pattern)
+    int32_t n = 0;
+    int64_t nnz = 0, ld = 0;
+    DevBuf<int32_t> rowptr, colidx;    // the diagonal block's pattern the hierarchy was built on, as the context stores it
+    DevBuf<int32_t> flag;              // [0]: the patterns differ; [1]: a numeric kernel of the refresh missed a slot
+    // the device route's level 0: the sorted copy of the context's CSR where its rows do not ascend, and D_0^-1
+    CsrDev sorted;
+    bool use_sorted = false;
+    DevBuf<double> dinv0;
+    double dinv_sum = 0.0;             // sum |D_0^-1| at the build (its binade: by which power of two A00 was rescaled since)
+    DevBuf<double> sum;                // where the kernel leaves that sum
+};
 struct AmgDev {
     std::vector<AmgLevelDev> lv;
     DevBuf<double> cinv;
     spk_amg_info info{};         // what spk_get_amg_info returns, on both routes
+    std::unique_ptr<AmgReuse> reuse;   // null unless built with reuse on
 };
 
 }  // namespace spk
@@ -905,6 +929,10 @@ struct spk_ctx {
     spk_amg_opts amg_opts{};
     std::unique_ptr<spk_amg_hier> amg_h;
     std::unique_ptr<spk::AmgDev> amg_d;
+    // spk_pc_set_amg_reuse: a set-up on an unchanged pattern refreshes the hierarchy's values instead of building it;
+    // what the last set-up did, and its wall time (spk_get_amg_reuse_info)
+    bool amg_reuse = false, amg_refreshed = false;
+    double amg_reuse_seconds = 0.0;
     spk::DevBuf<double> bigdots;   // Gram-Schmidt coefficients of restart lengths beyond the fused kernels' 62
 
     // scratch
@@ -974,6 +1002,13 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
 // the same hierarchy built on the device from c->Ad (-spk_gamg_setup device); touches nothing of the context but its
 // reduction scratch and leaves c->amg_h null: "built on the device" is c->amg_d && !c->amg_h
 std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c);
+// reuse (spk_pc_set_amg_reuse).  amg_can_refresh: reuse is on and the context's hierarchy was built with it, from these
+// options, on this size and this pattern (one kernel compares).  amg_refresh_ctx: new values on every kept pattern, on the
+// route that built; throws what the build would, the hierarchy is then half-refreshed and the caller drops it.
+// amg_drop_reuse: releases what only a refresh needs.
+bool amg_can_refresh(spk_ctx *c);
+void amg_refresh_ctx(spk_ctx *c);
+void amg_drop_reuse(spk_ctx *c);
 // the test hooks on either route: the host hierarchy's copy, or a download from the device-built levels
 void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);

@@ -1,6 +1,7 @@
 // spk_k_amg_setup.hip -- the multigrid set-up on the device (-spk_gamg_setup device; host sequencing: amg_build_device
 // in spk_amg.cpp).  gfx950, wave64, FP64.  Node graph, tentative prolongator, Lanczos vector passes, CSR x CSR, union
-// add and transpose.  Set-up runs before any solve: no launch here takes the solver's `done` gate.
+// add and transpose; for the refresh of a kept hierarchy (amg_refresh_ctx) the pattern comparison and the numeric
+// product and symmetrisation on known patterns.  Set-up runs before any solve: no launch here takes the solver's `done` gate.
 //
 // Every kernel is deterministic.  The sparse kernels work one row (or node) per thread in the host builder's traversal
 // order, and where the host's result depends on the order and rounding of a sum (the strong-connection test, the
@@ -267,6 +268,99 @@ __global__ __launch_bounds__(kThreads) void amgs_transpose_fill_kernel(const int
 }
 
 // ---------------------------------------------------------------------------
+// the refresh (spk_pc_set_amg_reuse): new values on the patterns a build kept.  Nothing is counted, scanned or
+// allocated; a thread writes inside its own row only, and what cannot happen on patterns that belong together (a column
+// outside the matrix, a product without a slot) sets err[0] instead of a store
+// ---------------------------------------------------------------------------
+// flag |= 1 where two int32 arrays differ (the pattern a hierarchy was built on against the context's)
+__global__ __launch_bounds__(kThreads) void amgs_pattern_equal_kernel(const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                                      int64_t n, int32_t *flag)
+{
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (k < n && a[k] != b[k]) atomicOr(flag, 1);
+}
+
+namespace {
+// position of column j in the ascending ci[lo, hi), or -1
+__device__ __forceinline__ int32_t find_col(const int32_t *__restrict__ ci, int32_t lo, int32_t hi, int32_t j)
+{
+    const int32_t end = hi;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (ci[mid] < j) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && ci[lo] == j ? lo : -1;
+}
+// __dmul_rn / __dadd_rn as the expand kernel compiles them: a multiply and an add of their own.  The header's versions are
+// a plain * and +, which the compiler contracts where a product has one use -- as it has here, and has not there
+__device__ __forceinline__ double mul_unfused(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ double add_unfused(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x + y;
+}
+}  // namespace
+
+// the values of C = A B on C's sorted pattern, one row per thread: the products in the order of amgs_spgemm_expand_kernel
+// (A's stored order, then B's; unfused; every entry summed from 0), so unchanged values give the build's bits
+__global__ __launch_bounds__(kThreads) void amgs_spgemm_numeric_kernel(const int32_t *__restrict__ arp, const int32_t *__restrict__ aci,
+                                                                       const double *__restrict__ av, const int32_t *__restrict__ brp,
+                                                                       const int32_t *__restrict__ bci, const double *__restrict__ bv,
+                                                                       int32_t n, int32_t nrows_b, const int32_t *__restrict__ crp,
+                                                                       const int32_t *__restrict__ cci, double *cv, int32_t *err)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    const int32_t k0 = crp[i], k1 = crp[i + 1];
+    for (int32_t t = k0; t < k1; ++t) cv[t] = 0.0;
+    bool bad = false;
+    for (int32_t k = arp[i]; k < arp[i + 1]; ++k) {
+        const int32_t r = aci[k];
+        if (r < 0 || r >= nrows_b) { bad = true; continue; }
+        const double a = av[k];
+        for (int32_t q = brp[r]; q < brp[r + 1]; ++q) {
+            const double p = mul_unfused(a, bv[q]);
+            const int32_t t = find_col(cci, k0, k1, bci[q]);
+            if (t < 0) bad = true;
+            else cv[t] = add_unfused(cv[t], p);
+        }
+    }
+    if (bad) atomicOr(err, 1);
+}
+
+// N = (Ac + Ac^T) / 2 on N's sorted pattern, one row per thread: N(i,j) from Ac(i,j) and Ac(j,i) with the expressions of
+// amgs_add_kernel<true> at a = b = 0.5 (an absent entry contributes nothing) -- the build's bits again, fused or not:
+// a product with 0.5 is exact
+__global__ __launch_bounds__(kThreads) void amgs_symmetrise_numeric_kernel(const int32_t *__restrict__ crp, const int32_t *__restrict__ cci,
+                                                                           const double *__restrict__ cv, int32_t n,
+                                                                           const int32_t *__restrict__ nrp, const int32_t *__restrict__ nci,
+                                                                           double *__restrict__ nv, int32_t *err)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
+    if (i >= n) return;
+    bool bad = false;
+    for (int32_t t = nrp[i]; t < nrp[i + 1]; ++t) {
+        const int32_t j = nci[t];
+        double x = 0.0;
+        if (j < 0 || j >= n) {
+            bad = true;
+        } else {
+            const int32_t p = find_col(cci, crp[i], crp[i + 1], j), q = find_col(cci, crp[j], crp[j + 1], i);
+            if (p >= 0 && q >= 0) x = __dadd_rn(__dmul_rn(0.5, cv[p]), __dmul_rn(0.5, cv[q]));
+            else if (p >= 0) x = __dmul_rn(0.5, cv[p]);
+            else if (q >= 0) x = __dmul_rn(0.5, cv[q]);
+            else bad = true;
+        }
+        nv[t] = x;
+    }
+    if (bad) atomicOr(err, 1);
+}
+
+// ---------------------------------------------------------------------------
 // Lanczos on D^-1/2 A D^-1/2 (lanczos of the host builder): the vector steps as fused passes, each with one sum,
 // reduced in a fixed order by the sentinel finish (spk_device.hpp)
 // ---------------------------------------------------------------------------
@@ -288,14 +382,25 @@ __device__ __forceinline__ void lz_finish(double acc, double *red, double *parti
 }
 }  // namespace
 
-// sv = sqrt|dinv|, q = the integer-hash start vector (not yet normalised), out[0] = q.q
-__global__ __launch_bounds__(kVT) void amgs_lz_init_kernel(int64_t n, const double *__restrict__ dinv, double *__restrict__ sv,
-                                                           double *__restrict__ q, double *partials, double *out, FinErr fe)
+// out[0] = sum |x|
+__global__ __launch_bounds__(kVT) void amgs_abs_sum_kernel(int64_t n, const double *__restrict__ x, double *partials, double *out,
+                                                           FinErr fe)
+{
+    __shared__ double red[kVT];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) acc += fabs(x[i]);
+    lz_finish(acc, red, partials, out, fe);
+}
+// sv = sqrt|dinv dscale| (dscale: a power of two, 1 on a build), q = the integer-hash start vector (not yet normalised),
+// out[0] = q.q
+__global__ __launch_bounds__(kVT) void amgs_lz_init_kernel(int64_t n, const double *__restrict__ dinv, double dscale,
+                                                           double *__restrict__ sv, double *__restrict__ q, double *partials,
+                                                           double *out, FinErr fe)
 {
     __shared__ double red[kVT];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        sv[i] = sqrt(fabs(dinv[i]));
+        sv[i] = sqrt(fabs(dinv[i] * dscale));
         uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
         h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
         const double x = 0.5 + (double)(h & 0xffffu) / 65536.0;
@@ -314,15 +419,15 @@ __global__ __launch_bounds__(kVT) void amgs_lz_scale_kernel(int64_t n, double nb
         t[i] = sv[i] * x;
     }
 }
-// w = sv aw, out[0] = w.q
+// w = sv (aw ascale) (ascale: a power of two, 1 on a build: the product with it is exact), out[0] = w.q
 __global__ __launch_bounds__(kVT) void amgs_lz_dot_kernel(int64_t n, const double *__restrict__ sv, const double *__restrict__ aw,
-                                                          double *__restrict__ w, const double *__restrict__ q, double *partials,
+                                                          double ascale, double *__restrict__ w, const double *__restrict__ q, double *partials,
                                                           double *out, FinErr fe)
 {
     __shared__ double red[kVT];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        const double x = sv[i] * aw[i];
+        const double x = sv[i] * (aw[i] * ascale);
         w[i] = x;
         acc += x * q[i];
     }
@@ -413,18 +518,38 @@ void amgs_transpose_fill(const CsrDev &A, int32_t *pos, int32_t *tci, double *tv
         hipLaunchKernelGGL(amgs_transpose_fill_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p,
                            A.nrows, pos, tci, tv);
 }
-void amgs_lz_init(int64_t n, const double *dinv, double *sv, double *q, const Finish &f, hipStream_t s)
+void amgs_pattern_equal(const int32_t *a, const int32_t *b, int64_t n, int32_t *flag, hipStream_t s)
 {
-    hipLaunchKernelGGL(amgs_lz_init_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, dinv, sv, q, f.partials, f.out,
+    if (n > 0) hipLaunchKernelGGL(amgs_pattern_equal_kernel, row_grid(n), dim3(kThreads), 0, s, a, b, n, flag);
+}
+void amgs_spgemm_numeric(const CsrDev &A, const CsrDev &B, CsrDev &C, int32_t *err, hipStream_t s)
+{
+    if (A.nrows > 0)
+        hipLaunchKernelGGL(amgs_spgemm_numeric_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p,
+                           B.rowptr.p, B.colidx.p, B.val.p, A.nrows, B.nrows, C.rowptr.p, C.colidx.p, C.val.p, err);
+}
+void amgs_symmetrise_numeric(const CsrDev &Ac, CsrDev &N, int32_t *err, hipStream_t s)
+{
+    if (N.nrows > 0)
+        hipLaunchKernelGGL(amgs_symmetrise_numeric_kernel, row_grid(N.nrows), dim3(kThreads), 0, s, Ac.rowptr.p, Ac.colidx.p, Ac.val.p,
+                           N.nrows, N.rowptr.p, N.colidx.p, N.val.p, err);
+}
+void amgs_lz_init(int64_t n, const double *dinv, double dscale, double *sv, double *q, const Finish &f, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_init_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, dinv, dscale, sv, q, f.partials, f.out,
                        FinErr{f.err, f.fin_ticks});
+}
+void amgs_abs_sum(int64_t n, const double *x, const Finish &f, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_abs_sum_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, x, f.partials, f.out, FinErr{f.err, f.fin_ticks});
 }
 void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, double *q, double *t, hipStream_t s)
 {
     hipLaunchKernelGGL(amgs_lz_scale_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, nb, w, sv, q, t);
 }
-void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double *w, const double *q, const Finish &f, hipStream_t s)
+void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double ascale, double *w, const double *q, const Finish &f, hipStream_t s)
 {
-    hipLaunchKernelGGL(amgs_lz_dot_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, sv, aw, w, q, f.partials, f.out,
+    hipLaunchKernelGGL(amgs_lz_dot_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, sv, aw, ascale, w, q, f.partials, f.out,
                        FinErr{f.err, f.fin_ticks});
 }
 void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s)

@@ -30,6 +30,7 @@ struct SpkKSP_s {
     int32_t schur_pre = SPK_SCHUR_PRE_SELFP_DIAG;   // -pc_fieldsplit_schur_precondition selfp | full
     int split1_pc = -1;                             // -fieldsplit_1_pc_type: 0 jacobi, 1 cholesky | lu, -1 follows schur_pre
     spk_amg_opts amg[2];
+    bool amg_reuse[2] = {false, false};             // -pc_gamg_reuse_interpolation, plain and with -fieldsplit_0_
     bool have_ops = false, is_setup = false, has_B = false;
     int32_t n_rows_B = 0;   // m (-ksp_view)
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
@@ -78,7 +79,7 @@ bool parse_bool(const char *s, bool *v)
     return false;
 }
 // the multigrid options (key without its -fieldsplit_0_ prefix); *handled = false: not one of them
-int parse_amg(SpkKSP k, spk_amg_opts &o, const std::string &full, const std::string &key, const char *val, bool *handled)
+int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, const std::string &key, const char *val, bool *handled)
 {
     *handled = true;
     auto need = [&](const char *what) -> int { return set_err(k, SPK_ERR_ARG, "option " + full + " needs " + what); };
@@ -93,6 +94,10 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, const std::string &full, const std::str
     } else if (key == "-pc_gamg_coarse_eq_limit") {
         if (!val || !parse_int(val, &iv) || iv < 1) return need("an integer >= 1");
         o.coarse_eq_limit = iv;
+    } else if (key == "-pc_gamg_reuse_interpolation") {
+        bool b = true;   // (given without a value: on)
+        if (val && !parse_bool(val, &b)) return need("a boolean");
+        reuse = b;
     } else if (key == "-pc_mg_levels") {
         if (!val || !parse_int(val, &iv) || iv < 1 || iv > SPK_AMG_MAX_LEVELS) return need("an integer 1..16");
         o.max_levels = iv;
@@ -238,7 +243,7 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             const bool split0 = key.rfind("-fieldsplit_0_", 0) == 0;
             const std::string sub = split0 ? "-" + key.substr(14) : key;
             bool handled = false;
-            const int rc = parse_amg(k, k->amg[split0 ? 1 : 0], key, sub, val, &handled);
+            const int rc = parse_amg(k, k->amg[split0 ? 1 : 0], k->amg_reuse[split0 ? 1 : 0], key, sub, val, &handled);
             if (rc != SPK_OK) return rc;
             if (handled) continue;
         }
@@ -430,6 +435,12 @@ int SpkKSPSetUp(SpkKSP k)
     if (amg_slot >= 0 && k->inner_richardson && k->inner_sweeps > 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: gamg and the FP32 inner sweeps both stand for A^-1 -- drop "
                                                "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
+    for (int slot = 0; slot < 2; ++slot)
+        if (k->amg_reuse[slot] && slot != amg_slot)
+            return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: ") + (slot ? "-fieldsplit_0_pc_gamg_reuse_interpolation" :
+                           "-pc_gamg_reuse_interpolation") + " keeps the prolongators of a multigrid hierarchy and " +
+                           (slot ? "-fieldsplit_0_pc_type gamg inside -pc_type fieldsplit" : "-pc_type gamg") +
+                           " is not selected -- select it, or drop the option");
     if (!k->have_ops) return set_err(k, SPK_ERR_STATE, "KSPSetUp: KSPSetOperators has not been called");
     if (pipecg && k->has_B)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " is for K = A (symmetric positive definite); "
@@ -445,6 +456,8 @@ int SpkKSPSetUp(SpkKSP k)
     rc = spk_pc_set_inner(k->ctx, k->inner_richardson ? k->inner_sweeps : 0, k->inner_omega);
     if (rc != SPK_OK) return from_ctx(k, rc);
     if (amg_slot >= 0) rc = spk_pc_set_amg(k->ctx, &k->amg[amg_slot]);
+    if (rc != SPK_OK) return from_ctx(k, rc);
+    rc = spk_pc_set_amg_reuse(k->ctx, amg_slot >= 0 && k->amg_reuse[amg_slot] ? 1 : 0);
     if (rc != SPK_OK) return from_ctx(k, rc);
     rc = spk_pc_set_schur_pre(k->ctx, k->schur_pre);
     if (rc != SPK_OK) return from_ctx(k, rc);
@@ -526,6 +539,10 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
             std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
                         o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
                         o.nsmooths, o.coarse_eq_limit);
+            int32_t refreshed = 0;
+            double secs = 0.0;
+            if (k->amg_reuse[amg_active(k)] && spk_get_amg_reuse_info(k->ctx, &refreshed, &secs) == SPK_OK)
+                std::printf("    reuse_interpolation: the last set-up %s the hierarchy in %.3f s\n", refreshed ? "refreshed" : "built", secs);
             for (int l = 0; l < ai.levels; ++l)
                 std::printf("    level %d: rows %d nnz %lld lambda_max %.6g%s\n", l, ai.rows[l], (long long)ai.nnz[l],
                             ai.lambda_max[l], l + 1 == ai.levels ? " (coarse: dense Cholesky inverse)" : "");
@@ -558,6 +575,12 @@ int SpkKSPGetAMGOptions(SpkKSP k, int fieldsplit0, spk_amg_opts *o, int32_t *sel
     if (!k || fieldsplit0 < 0 || fieldsplit0 > 1) return SPK_ERR_ARG;
     if (o) *o = k->amg[fieldsplit0];
     if (selected) *selected = fieldsplit0 ? k->split0_gamg : k->pc_gamg;
+    return SPK_OK;
+}
+int SpkKSPGetAMGReuse(SpkKSP k, int fieldsplit0, int32_t *reuse)
+{
+    if (!k || !reuse || fieldsplit0 < 0 || fieldsplit0 > 1) return SPK_ERR_ARG;
+    *reuse = k->amg_reuse[fieldsplit0] ? 1 : 0;
     return SPK_OK;
 }
 int SpkKSPGetType(SpkKSP k, const char **type, int32_t *norm_type)

@@ -789,16 +789,38 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     }
     std::unique_ptr<spk_amg_hier> amg;
     std::unique_ptr<AmgDev> amg_dev;   // -spk_gamg_setup device: built on the device, equally before anything changes
+    // reuse on and nothing but A00's values changed: the hierarchy the context holds is refreshed where it lies.  A refresh
+    // that throws leaves it half-done: dropped, and the context without a preconditioner until the next spk_pc_setup
+    bool refreshed = false;
+    double amg_seconds = 0.0;
+    const auto amg_t0 = std::chrono::steady_clock::now();
+    auto amg_lap = [&](std::chrono::steady_clock::time_point t) { amg_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
     if (c->amg_on) {
         if (c->comm->size() > 1)
             fail(SPK_ERR_UNSUPPORTED, "pc_setup: the multigrid preconditioner (gamg) runs on one rank only; this communicator "
                  "has %d -- multi-rank AMG is not implemented", c->comm->size());
         if (pc_type == SPK_PC_NONE) fail(SPK_ERR_ARG, "pc_setup: the multigrid preconditioner needs pc_type jacobi or schur");
-        if (c->amg_opts.setup == SPK_AMG_SETUP_DEVICE) amg_dev = amg_build_device(c);
-        else amg = amg_build_ctx(c);
+        refreshed = amg_can_refresh(c);
+        if (refreshed) {
+            try {
+                amg_refresh_ctx(c);
+            } catch (...) {
+                c->amg_d.reset();
+                c->amg_h.reset();
+                c->pc_ready = false;
+                throw;
+            }
+        } else if (c->amg_opts.setup == SPK_AMG_SETUP_DEVICE) {
+            amg_dev = amg_build_device(c);
+        } else {
+            amg = amg_build_ctx(c);
+        }
+        amg_lap(amg_t0);
     }
-    c->amg_d.reset();
-    c->amg_h.reset();
+    if (!refreshed) {
+        c->amg_d.reset();
+        c->amg_h.reset();
+    }
     hipStream_t s = c->stream;
     c->ensure_scratch();
     c->ensure_vectors();
@@ -808,8 +830,14 @@ void pc_setup(spk_ctx *c, int pc_type, int schur_fact)
     c->nonempty_all = (slabs & 2) != 0;
     c->dinv.alloc((size_t)c->n_local, 8);
     k::extract_diag_inv(c->Ad, c->dinv.p, s);
-    if (amg) amg_upload(c, std::move(amg));
+    if (amg) {
+        const auto t = std::chrono::steady_clock::now();
+        amg_upload(c, std::move(amg));
+        amg_lap(t);
+    }
     if (amg_dev) c->amg_d = std::move(amg_dev);
+    c->amg_refreshed = refreshed;
+    c->amg_reuse_seconds = amg_seconds;
     if (c->m > 0) schur_diag(c);
     fp32_copies(c);
     bd_planes(c, pc_type, schur_fact);

@@ -33,6 +33,7 @@ def default_opts(**kw):
 AMG_CHEBYSHEV, AMG_RICHARDSON = 0, 1
 AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV = 0, 1, 2, 3
 AMG_SETUP_HOST, AMG_SETUP_DEVICE = 0, 1
+SPK_ERR_ARG = -1   # include/spk.h
 _SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
 _SETUPS = {"host": AMG_SETUP_HOST, "device": AMG_SETUP_DEVICE}
 
@@ -88,6 +89,7 @@ class AmgHierarchy:
         rc = lib.spk_amg_build_host(A.nrows, A.rowptr, A.colidx, A.val, C.byref(o), C.byref(self.h))
         if rc != 0:
             raise SpkError(rc, lib.spk_last_error(None).decode())
+        self._nnz = int(A.rowptr[A.nrows])
 
     def _chk(self, rc):
         if rc != 0:
@@ -100,6 +102,18 @@ class AmgHierarchy:
 
     def matrix(self, level, which=AMG_OP):
         return _amg_matrix(lambda *a: self._chk(lib.spk_amg_host_level(self.h, *a)), level, which)
+
+    def refresh(self, val):
+        """New values on the same pattern (spk_amg_refresh_host), in the order of the A.val this hierarchy was built
+        from: the aggregates, the prolongators and every pattern stay; the coarse operators, the intervals and the coarse
+        inverse are computed again.  None or another length: SPK_ERR_ARG."""
+        if val is None:
+            self._chk(lib.spk_amg_refresh_host(self.h, None))
+            return
+        v = np.ascontiguousarray(val, np.float64)
+        if v.shape != (self._nnz,):
+            raise SpkError(SPK_ERR_ARG, f"amg refresh: {v.size} values for a pattern of {self._nnz} entries")
+        self._chk(lib.spk_amg_refresh_host(self.h, v.ctypes.data))
 
     def aggregates(self, level):
         n = C.c_int32()
@@ -414,15 +428,19 @@ class Context:
         self._chk(lib.spk_set_block(self.h, which, A.row_begin if which == BLOCK_A00 else 0, nrows,
                                     A.ncols, A.rowptr, A.colidx, A.val))
 
-    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None, schur_pre="selfp"):
+    def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None, schur_pre="selfp",
+                 amg_reuse=False):
         """inner_sweeps > 0: FP32 damped-Jacobi Richardson sweeps stand for diag(A)^-1.
         amg: None (off), True (defaults) or a dict of spk_amg_opts fields: one smoothed-aggregation V-cycle stands
         for A^-1 (PC_JACOBI: M^-1 on K = A; PC_SCHUR: inside the fieldsplit).
         schur_pre: "selfp" (S^ = diag(B diag(A)^-1 B^T)) or "full" (the exact S = B A^ ^-1 B^T of at most 8 rows, dense
-        and Cholesky-factored; PC_SCHUR only)."""
+        and Cholesky-factored; PC_SCHUR only).
+        amg_reuse: a set-up that finds the hierarchy of an earlier amg_reuse=True set-up, the same options and an A00
+        of the same pattern refreshes its values and keeps the prolongators (spk_pc_set_amg_reuse; amg_reuse_info())."""
         if schur_pre not in _SCHUR_PRES:
             raise ValueError(f"schur_pre must be one of {sorted(_SCHUR_PRES)}")
         self._chk(lib.spk_pc_set_schur_pre(self.h, _SCHUR_PRES[schur_pre]))
+        self._chk(lib.spk_pc_set_amg_reuse(self.h, 1 if amg_reuse else 0))
         if amg is None or amg is False:
             self._chk(lib.spk_pc_set_amg(self.h, None))
             self._chk(lib.spk_pc_set_inner(self.h, inner_sweeps, inner_omega))
@@ -437,6 +455,12 @@ class Context:
         ai = AmgInfo()
         self._chk(lib.spk_get_amg_info(self.h, C.byref(ai)))
         return _amg_info(ai)
+
+    def amg_reuse_info(self):
+        """Whether the last pc_setup refreshed the hierarchy (True) or built it, and the wall seconds of that."""
+        r, t = C.c_int32(), C.c_double()
+        self._chk(lib.spk_get_amg_reuse_info(self.h, C.byref(r), C.byref(t)))
+        return dict(refreshed=bool(r.value), seconds=t.value)
 
     def amg_aggregates(self, level):
         """The aggregate of every node of a level of the context's hierarchy (-1: isolated)."""
@@ -751,6 +775,12 @@ class KSP:
         o, sel = AmgOpts(), C.c_int32()
         self._chk(lib.SpkKSPGetAMGOptions(self.h, 1 if fieldsplit0 else 0, C.byref(o), C.byref(sel)))
         return amg_opts_dict(o), bool(sel.value)
+
+    def getAMGReuse(self, fieldsplit0=False):
+        """-pc_gamg_reuse_interpolation (or its -fieldsplit_0_ form) as read."""
+        v = C.c_int32()
+        self._chk(lib.SpkKSPGetAMGReuse(self.h, 1 if fieldsplit0 else 0, C.byref(v)))
+        return bool(v.value)
 
     def getSchurPre(self):
         """(-pc_fieldsplit_schur_precondition, -fieldsplit_1_pc_type) as they resolve: ('selfp' | 'full', 'jacobi' | 'cholesky')."""

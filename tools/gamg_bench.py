@@ -11,7 +11,17 @@ byte model per level, iterations and wall time to rtol.  One JSON line per row.
 The saddle system with FULL + gamg under both Schur preconditions, from one context per grid: after one warm-up set-up and
 solve of each, --reps alternating rounds of selfp (S^ = diag(B diag(A)^-1 B^T), today's rows) and full (the exact dense
 S = B V B^T, schur_pre="full").  Per row: iterations and solve time to rtol, the true residual, microseconds per PCApply
-(back to back on device vectors), what W and S added to the set-up, and K = A's iteration count on the same grid."""
+(back to back on device vectors), what W and S added to the set-up, and K = A's iteration count on the same grid.
+    python tools/gamg_bench.py --refresh [--setup-only host|device|both] [--reps 5] [--out profiles/FILE.jsonl]
+The refresh of the hierarchy (amg_reuse=True, -pc_gamg_reuse_interpolation) against a full build in the same process on
+the same values, K = A, per grid and route on one context: one warm-up build, then --reps rounds of
+  full build on the new values with reuse off (what every set-up did before the option) -> solve,
+  build on the old values with reuse on (not compared: it only leaves a hierarchy to refresh) ,
+  refresh to the new values -> solve.
+The new values are the old ones scaled by s[row] s[col], s = 1 + 0.5 sin(2 pi i / n) cos(3 pi j / n) per node.  Per row:
+median, minimum and maximum of the set-up seconds (spk_get_amg_reuse_info: the hierarchy alone, up to a device
+synchronise) and of the whole pc_setup, and iterations and time of the solves to rtol.  --setup-only leaves the solves
+out and names the routes (a kernel trace of build and refresh alone); --out appends the lines to a file as well."""
 import argparse
 import json
 import os
@@ -33,8 +43,13 @@ ap.add_argument("--setup-only", choices=["host", "device", "both"], help="only b
                 "warm-up build of each route asked for) and print one line per grid: a kernel trace of the set-up alone")
 ap.add_argument("--schur-full", action="store_true", help="only the saddle rows of FULL + gamg, selfp and the exact Schur "
                 "complement alternating in one process")
-ap.add_argument("--reps", type=int, default=3, help="--schur-full: alternating rounds after the warm-up round")
+ap.add_argument("--reps", type=int, default=None, help="alternating rounds after the warm-up round (--schur-full: 3, --refresh: 5)")
+ap.add_argument("--refresh", action="store_true", help="only the refresh of the K = A hierarchy against a full build on the "
+                "same values, both routes (or those of --setup-only, then without the solves)")
+ap.add_argument("--out", help="--refresh: append the JSON lines to this file too")
 a = ap.parse_args()
+if a.reps is None:
+    a.reps = 5 if a.refresh else 3
 
 
 def csr_bytes(nnz, n):
@@ -136,8 +151,60 @@ def schur_full_rows(grid, A, f):
     c.close()
 
 
+def refresh_rows(grid, A, f):
+    node = np.arange(A.nrows) // 2
+    s = 1.0 + 0.5 * np.sin(2.0 * np.pi * (node % grid) / grid) * np.cos(3.0 * np.pi * (node // grid) / grid)
+    rows = np.repeat(np.arange(A.nrows), np.diff(A.rowptr))
+    Anew = S.CSR(A.rowptr, A.colidx, A.val * s[rows] * s[A.colidx], A.nrows)
+    routes = ("host", "device") if a.setup_only in (None, "both") else (a.setup_only,)
+    for route in routes:
+        c = S.Context(0)
+        t = dict(build=[], refresh=[], build_pc_setup=[], refresh_pc_setup=[], build_solve=[], refresh_solve=[])
+        its = dict(build=[], refresh=[])
+
+        def setup(M, reuse, key=None):
+            c.set_block(S.BLOCK_A00, M)
+            t0 = time.perf_counter()
+            c.pc_setup(S.PC_JACOBI, 0, amg=dict(setup=route), amg_reuse=reuse)
+            wall = time.perf_counter() - t0
+            r = c.amg_reuse_info()
+            if key:
+                assert r["refreshed"] == (key == "refresh"), (key, r)
+                t[key].append(r["seconds"])
+                t[key + "_pc_setup"].append(wall)
+                if not a.setup_only:
+                    conv = solve(c, f, "fgmres")
+                    assert conv["reason"] == 2, conv
+                    its[key].append(conv["its"])
+                    t[key + "_solve"].append(conv["seconds"])
+
+        setup(A, False)                       # warm-up build
+        for _ in range(a.reps):
+            setup(Anew, False, "build")       # the full build on the new values
+            setup(A, True)                    # a hierarchy to refresh
+            setup(Anew, True, "refresh")      # the refresh to the new values
+        info = c.amg_info()
+        c.close()
+        row = dict(mode="refresh", system="A", grid=grid, route=route, reps=a.reps, levels=info["levels"])
+        for key, v in t.items():
+            if v:
+                row[key + "_seconds"] = dict(median=round(float(np.median(v)), 5), min=round(min(v), 5), max=round(max(v), 5))
+        row["build_over_refresh"] = round(float(np.median(t["build"]) / np.median(t["refresh"])), 2)
+        for key, v in its.items():
+            if v:
+                row[key + "_its"] = sorted(set(v))
+        line = json.dumps(row)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as fh:
+                fh.write(line + "\n")
+
+
 for grid in a.grids:
     A, f = S.AssembleOperator_Laplace(grid)
+    if a.refresh:
+        refresh_rows(grid, A, f)
+        continue
     if a.schur_full:
         schur_full_rows(grid, A, f)
         continue
