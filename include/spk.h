@@ -244,6 +244,26 @@ int spk_set_block(spk_ctx *ctx, int which, int64_t row_begin, int32_t nrows_loca
                   int64_t ncols_global, const int32_t *rowptr, const int32_t *colidx,
                   const double *val);
 
+/* KSPSetOperators for A00 of the reference's own discretisation, assembled on the device: what
+ * SpkAssembleOperator_Laplace[Kappa] (spk_assembly.h) + spk_set_block(SPK_BLOCK_A00) do, without the host arrays.
+ * A kernel writes the rank's slab -- the rows spk_partition_slab(my, 2*mx, rank, nranks) deals it -- bit for bit as
+ * the host assembler would, into device memory, and the chain of spk_set_block runs from there.  kappa: one
+ * coefficient per element, (mx-1)*(my-1) values of the WHOLE grid, element e = ej*(mx-1) + ei, in host or device
+ * memory (kappa_mem: SPK_MEM_HOST / SPK_MEM_DEVICE), or NULL for ones.  f_dev: n_local values of spk_vec_create
+ * memory that receive the right-hand side (zero on Dirichlet rows with apply_bc), or NULL.
+ * Refused with the previous operator left in place and usable, before anything large is allocated: mx or my < 2
+ * and an entry of kappa that is not finite and > 0 (SPK_ERR_ARG); 2*mx*my or the slab's non-zeros beyond INT32_MAX
+ * (SPK_ERR_UNSUPPORTED).  Collective like spk_set_block. */
+int spk_set_block_laplace(spk_ctx *ctx, int mx, int my, const double *kappa, int kappa_mem,
+                          int apply_bc, double *f_dev /* n_local values, spk_vec_create memory, or NULL */);
+/* Test hook: the same kernels on rows [row_begin,row_end), the result copied to host arrays sized as for
+ * SpkAssembleOperator_Laplace.  Touches nothing of the context's operator. */
+int spk_assemble_laplace_csr(spk_ctx *ctx, int mx, int my, int64_t row_begin, int64_t row_end,
+                             const double *kappa, int kappa_mem, int apply_bc,
+                             int32_t *rowptr, int32_t *colidx, double *val, double *f);
+/* Wall seconds of the last device assembly's kernels up to a device synchronise (0 before one). */
+int spk_get_assembly_seconds(const spk_ctx *ctx, double *seconds);
+
 /* ---- preconditioner (KSPSetUp, SaddlePointProblem.c:68) ------------------ */
 /* Builds diag(A)^-1 and, for SPK_PC_SCHUR, S^ = diag(B diag(A)^-1 B^T). */
 int spk_pc_setup(spk_ctx *ctx, int pc_type, int schur_fact);

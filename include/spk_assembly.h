@@ -32,6 +32,19 @@ int64_t SpkAssemblySlabNnz(int mx, int my, int64_t row_begin, int64_t row_end);
  * nthreads <= 0: all hardware threads. */
 int SpkAssembleOperator_Laplace(int mx, int my, int64_t row_begin, int64_t row_end, int32_t *rowptr,
                                 int32_t *colidx, double *val, double *f, int apply_bc, int nthreads);
+/* The same with a coefficient: kappa holds one value per ELEMENT of the whole grid, (mx-1)(my-1) of them,
+ * element e = ej*(mx-1) + ei, and enters where the reference's coeff[p] does (tD = 2 * 1 * det J * kappa[e], the
+ * same at the four Gauss points; Discretization.c:318-320); f does not depend on it.  kappa == NULL: ones, and
+ * then bit for bit SpkAssembleOperator_Laplace, which forwards here.  SPK_ERR_ARG for an entry that is not
+ * finite and > 0, decided before any output is written.  The CPU oracle of spk_set_block_laplace (spk.h). */
+int SpkAssembleOperator_LaplaceKappa(int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa,
+                                     int32_t *rowptr, int32_t *colidx, double *val, double *f, int apply_bc,
+                                     int nthreads);
+/* The row pointers of rows [row_begin,row_end) alone (closed form per node; (row_end-row_begin)+1 entries from 0):
+ * what both assemblers above and the device route write.  SPK_ERR_UNSUPPORTED beyond 32-bit indices. */
+int SpkAssemblyRowPointers(int mx, int my, int64_t row_begin, int64_t row_end, int32_t *rowptr);
+/* SPK_ERR_ARG when an entry of kappa ((mx-1)(my-1) values; NULL passes) is not finite and > 0. */
+int SpkAssemblyCheckKappa(int mx, int my, const double *kappa);
 
 /* Build-defined constraint block B (4 rows) restricted to the columns
  * [row_begin,row_end), and g (4 values).  Rows: Ux mean, Uy mean, x-moment of

@@ -37,6 +37,11 @@ int SpkKSPSetCommRCCL(SpkKSP ksp, int rank, int nranks, const void *id128);
 /* A = (0,0) block (operator and preconditioning matrix, as KSPSetOperators(ksp,A,A));
  * B = (1,0) block of the nest sketched at :45-60, or NULL for the as-written A-only solve */
 int SpkKSPSetOperators(SpkKSP ksp, const SpkMatCSR *A, const SpkMatCSR *B); /* KSPSetOperators :66 */
+/* The same with A of the reference's own discretisation assembled on the device (spk_set_block_laplace, boundary
+ * conditions applied): mx x my nodes; kappa: one host value per element, (mx-1)*(my-1) of them, or NULL for ones;
+ * B as above; f_host: receives the rank's n_local right-hand side values, or NULL.  Leaves the KSP in the state
+ * SpkKSPSetOperators would; -ksp_view names the route. */
+int SpkKSPSetOperatorsLaplace(SpkKSP ksp, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host);
 /* argv-style option list, e.g. {"-ksp_type","fgmres","-ksp_rtol","1e-8",
  * "-pc_type","fieldsplit","-pc_fieldsplit_type","schur",
  * "-pc_fieldsplit_schur_fact_type","full"}.  Unknown -ksp_/-pc_/-fieldsplit_

@@ -8,7 +8,7 @@ from ._lib import lib, SpkError, LIB_PATH  # noqa: F401
 from .csr import CSR  # noqa: F401
 from .assembly import (  # noqa: F401
     AssembleOperator_Laplace, AssembleOperator_Constraints, FormStressOperatorQ12D,
-    FormLaplaceRHSQ12D, grid_sizes, partition_slab, WriteVTK,
+    FormLaplaceRHSQ12D, grid_sizes, partition_slab, WriteVTK, slab_row_pointers, element_kappa,
     AssembleOperator_Laplace3D, AssembleOperator_Constraints3D, AssembleOperator_Divergence3D, partition_slab3d,
 )
 from .solver import (  # noqa: F401

@@ -189,6 +189,9 @@ def _load():
     L.spk_debug_time_products.argtypes = [vp, C.c_int32]
     L.spk_get_product_timing.argtypes = [vp, C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.spk_set_block.argtypes = [vp, C.c_int, i64, i32, i64, i32p, i32p, f64p]
+    L.spk_set_block_laplace.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.spk_assemble_laplace_csr.argtypes = [vp, C.c_int, C.c_int, i64, i64, vp, C.c_int, C.c_int, i32p, i32p, f64p, vp]
+    L.spk_get_assembly_seconds.argtypes = [vp, C.POINTER(dbl)]
     L.spk_pc_setup.argtypes = [vp, C.c_int, C.c_int]
     L.spk_pc_set_inner.argtypes = [vp, C.c_int, C.c_double]
     L.spk_default_amg_opts.argtypes = [C.POINTER(AmgOpts)]
@@ -237,6 +240,9 @@ def _load():
     L.SpkAssemblySlabNnz.restype = i64
     L.SpkAssemblySlabNnz.argtypes = [C.c_int, C.c_int, i64, i64]
     L.SpkAssembleOperator_Laplace.argtypes = [C.c_int, C.c_int, i64, i64, i32p, i32p, f64p, vp, C.c_int, C.c_int]
+    L.SpkAssembleOperator_LaplaceKappa.argtypes = [C.c_int, C.c_int, i64, i64, vp, i32p, i32p, f64p, vp, C.c_int, C.c_int]
+    L.SpkAssemblyRowPointers.argtypes = [C.c_int, C.c_int, i64, i64, i32p]
+    L.SpkAssemblyCheckKappa.argtypes = [C.c_int, C.c_int, vp]
     L.SpkConstraintsSlabNnz.restype = i64
     L.SpkConstraintsSlabNnz.argtypes = [C.c_int, C.c_int, i64, i64]
     L.SpkAssembleOperator_Constraints.argtypes = [C.c_int, C.c_int, i64, i64, i32p, i32p, f64p]
@@ -259,6 +265,7 @@ def _load():
     L.SpkKSPCreate.argtypes = [C.c_int, C.POINTER(vp)]
     L.SpkKSPSetCommRCCL.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.SpkKSPSetOperators.argtypes = [vp, C.POINTER(MatCSR), C.POINTER(MatCSR)]
+    L.SpkKSPSetOperatorsLaplace.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
     L.SpkKSPSetFromOptions.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
     L.SpkKSPSetUp.argtypes = [vp]
     L.SpkKSPSolve.argtypes = [vp, f64p, f64p]

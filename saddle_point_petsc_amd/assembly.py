@@ -21,10 +21,35 @@ def grid_sizes(mx, my=None):
     return n.value, nnz.value
 
 
-def AssembleOperator_Laplace(mx, my=None, row_begin=0, row_end=None, apply_bc=True, with_rhs=True, nthreads=0):
+def element_kappa(mx, my, kappa):
+    """kappa as the C ABI takes it: None, or a contiguous float64 array of (mx-1)*(my-1) values, element
+    e = ej*(mx-1) + ei (a 2-D array is indexed [ej, ei])."""
+    if kappa is None:
+        return None
+    k = np.ascontiguousarray(kappa, np.float64).reshape(-1)
+    if k.size != (mx - 1) * (my - 1):
+        raise ValueError(f"kappa must hold one value per element: {(mx - 1) * (my - 1)}, not {k.size}")
+    return k
+
+
+def slab_row_pointers(mx, my=None, row_begin=0, row_end=None):
+    """The closed-form row pointers of rows [row_begin,row_end): what the host assembler and the device route write."""
+    my = mx if my is None else my
+    n, _ = grid_sizes(mx, my)
+    row_end = n if row_end is None else row_end
+    if lib.SpkAssemblySlabNnz(mx, my, row_begin, row_end) < 0:
+        raise SpkError(-1, "row range must consist of whole node lines")
+    rowptr = np.zeros(row_end - row_begin + 1, np.int32)
+    _chk(lib.SpkAssemblyRowPointers(mx, my, row_begin, row_end, rowptr), "SpkAssemblyRowPointers")
+    return rowptr
+
+
+def AssembleOperator_Laplace(mx, my=None, row_begin=0, row_end=None, apply_bc=True, with_rhs=True, nthreads=0, kappa=None):
     """A (CSR slab, global columns) and f for rows [row_begin,row_end) of an
     mx x my NODE grid.  Restates AssembleOperator_Laplace + AssembleRHS_Laplace
-    + ApplyBC_Laplace (Discretization.c:130-274)."""
+    + ApplyBC_Laplace (Discretization.c:130-274).  kappa: one coefficient per element of the whole grid
+    ((mx-1)*(my-1) values, element ej*(mx-1) + ei), entering where the reference's coeff[p] does; None: ones
+    (SpkAssembleOperator_LaplaceKappa, the CPU oracle of Context.set_block_laplace)."""
     my = mx if my is None else my
     n, _ = grid_sizes(mx, my)
     row_end = n if row_end is None else row_end
@@ -36,9 +61,15 @@ def AssembleOperator_Laplace(mx, my=None, row_begin=0, row_end=None, apply_bc=Tr
     colidx = np.zeros(nnz, np.int32)
     val = np.zeros(nnz)
     f = np.zeros(nl) if with_rhs else None
-    _chk(lib.SpkAssembleOperator_Laplace(mx, my, row_begin, row_end, rowptr, colidx, val,
-                                         f.ctypes.data if with_rhs else None, int(apply_bc), nthreads),
-         "SpkAssembleOperator_Laplace")
+    if kappa is None:
+        _chk(lib.SpkAssembleOperator_Laplace(mx, my, row_begin, row_end, rowptr, colidx, val,
+                                             f.ctypes.data if with_rhs else None, int(apply_bc), nthreads),
+             "SpkAssembleOperator_Laplace")
+    else:
+        k = element_kappa(mx, my, kappa)
+        _chk(lib.SpkAssembleOperator_LaplaceKappa(mx, my, row_begin, row_end, k.ctypes.data, rowptr, colidx, val,
+                                                  f.ctypes.data if with_rhs else None, int(apply_bc), nthreads),
+             "SpkAssembleOperator_LaplaceKappa: an entry of kappa is not finite and > 0")
     return CSR(rowptr, colidx, val, n, row_begin), f
 
 

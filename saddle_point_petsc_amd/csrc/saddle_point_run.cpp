@@ -7,11 +7,12 @@
 //
 //   saddle_point_run -da_grid_x 257 -da_grid_y 257 -ksp_type fgmres -ksp_rtol 1e-8 \
 //       -pc_type fieldsplit -pc_fieldsplit_type schur -pc_fieldsplit_schur_fact_type full \
-//       -ksp_converged_reason [-saddle 0] [-solution_view] [-no_vtk]
+//       -ksp_converged_reason [-saddle 0] [-solution_view] [-no_vtk] [-spk_assembly host|device]
 //
 // The reference hard-codes Nx = Ny = 3 elements (main.c:14), i.e. a 4 x 4 node
 // grid; that is the default here too.  -saddle 0 solves A u = f alone, as the
-// reference does at HEAD (KSPSetOperators(ksp, A, A), :66).
+// reference does at HEAD (KSPSetOperators(ksp, A, A), :66).  -spk_assembly device assembles A and f on
+// the GPU (SpkKSPSetOperatorsLaplace) instead of on host threads; the default, host, is the flow above.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,12 @@ static int opt_int(int argc, char **argv, const char *name, int dflt)
 {
     for (int i = 1; i + 1 < argc; ++i)
         if (!std::strcmp(argv[i], name)) return std::atoi(argv[i + 1]);
+    return dflt;
+}
+static const char *opt_str(int argc, char **argv, const char *name, const char *dflt)
+{
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], name)) return argv[i + 1];
     return dflt;
 }
 static bool opt_flag(int argc, char **argv, const char *name)
@@ -47,13 +54,22 @@ int main(int argc, char **argv)
     SpkKSP ksp = nullptr;
     const int mx = opt_int(argc, argv, "-da_grid_x", 4), my = opt_int(argc, argv, "-da_grid_y", 4);
     const bool saddle = opt_int(argc, argv, "-saddle", 1) != 0;
+    const char *route = opt_str(argc, argv, "-spk_assembly", "host");
+    const bool on_device = !std::strcmp(route, "device");
+    if (!on_device && std::strcmp(route, "host")) { std::fprintf(stderr, "-spk_assembly %s is not supported (host | device)\n", route); return 1; }
     int64_t n = 0, nnz = 0;
     CHK(SpkAssemblySizes(mx, my, &n, &nnz));
 
-    // SetupDMDA + AssembleOperator_Laplace + AssembleRHS_Laplace + ApplyBC_Laplace
-    std::vector<int32_t> rowptr((size_t)n + 1), colidx((size_t)nnz);
-    std::vector<double> val((size_t)nnz), rhs((size_t)n + 4, 0.0), sol((size_t)n + 4, 0.0);
-    CHK(SpkAssembleOperator_Laplace(mx, my, 0, n, rowptr.data(), colidx.data(), val.data(), rhs.data(), 1, 0));
+    // SetupDMDA + AssembleOperator_Laplace + AssembleRHS_Laplace + ApplyBC_Laplace (host route; the device route
+    // does the same inside KSPSetOperators below)
+    std::vector<int32_t> rowptr, colidx;
+    std::vector<double> val, rhs((size_t)n + 4, 0.0), sol((size_t)n + 4, 0.0);
+    if (!on_device) {
+        rowptr.resize((size_t)n + 1);
+        colidx.resize((size_t)nnz);
+        val.resize((size_t)nnz);
+        CHK(SpkAssembleOperator_Laplace(mx, my, 0, n, rowptr.data(), colidx.data(), val.data(), rhs.data(), 1, 0));
+    }
     SpkMatCSR A = {0, (int32_t)n, 0, n, rowptr.data(), colidx.data(), val.data()};
 
     // AssembleOperator_Constraints + AssembleRHS_Constraints (stubs in the reference)
@@ -72,7 +88,8 @@ int main(int argc, char **argv)
 
     // the call site SaddlePointProblem.c:65-72
     CHK(SpkKSPCreate(opt_int(argc, argv, "-spk_device", 0), &ksp));
-    CHK(SpkKSPSetOperators(ksp, &A, saddle ? &B : nullptr));
+    if (on_device) CHK(SpkKSPSetOperatorsLaplace(ksp, mx, my, nullptr, saddle ? &B : nullptr, rhs.data()));
+    else CHK(SpkKSPSetOperators(ksp, &A, saddle ? &B : nullptr));
     CHK(SpkKSPSetFromOptions(ksp, argc - 1, argv + 1));
     CHK(SpkKSPSetUp(ksp));
     CHK(SpkKSPSolve(ksp, rhs.data(), sol.data()));

@@ -292,6 +292,28 @@ int spk_set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local,
     SPK_CATCH(c)
 }
 
+int spk_set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+{
+    SPK_TRY(c)
+    spk::set_block_laplace(c, mx, my, kappa, kappa_mem, apply_bc, f_dev);
+    SPK_CATCH(c)
+}
+
+int spk_assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                             int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
+{
+    SPK_TRY(c)
+    spk::assemble_laplace_csr(c, mx, my, row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
+    SPK_CATCH(c)
+}
+
+int spk_get_assembly_seconds(const spk_ctx *c, double *seconds)
+{
+    if (!c || !seconds) return SPK_ERR_ARG;
+    *seconds = c->assembly_seconds;
+    return SPK_OK;
+}
+
 int spk_pc_setup(spk_ctx *c, int pc_type, int schur_fact)
 {
     SPK_TRY(c)

@@ -8,6 +8,7 @@
 // so every stored value is bit-identical to a sequential ADD_VALUES assembly
 // while no two threads ever touch the same entry.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <thread>
@@ -222,28 +223,46 @@ int64_t SpkAssemblySlabNnz(int mx, int my, int64_t row_begin, int64_t row_end)
     return nnz;
 }
 
-int SpkAssembleOperator_Laplace(int mx, int my, int64_t row_begin, int64_t row_end, int32_t *rowptr,
-                                int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
+int SpkAssemblyRowPointers(int mx, int my, int64_t row_begin, int64_t row_end, int32_t *rowptr)
+{
+    const int64_t line = (int64_t)2 * mx;
+    if (!rowptr || SpkAssemblySlabNnz(mx, my, row_begin, row_end) < 0) return SPK_ERR_ARG;
+    if ((int64_t)2 * mx * my > INT32_MAX) return SPK_ERR_UNSUPPORTED;
+    const int j0 = (int)(row_begin / line), j1 = (int)(row_end / line);
+    int64_t k = 0;
+    int64_t r = 0;
+    for (int j = j0; j < j1; ++j)
+        for (int i = 0; i < mx; ++i) {
+            const int w = node_row_nnz(mx, my, i, j);
+            rowptr[r++] = (int32_t)k; k += w;
+            rowptr[r++] = (int32_t)k; k += w;
+        }
+    rowptr[r] = (int32_t)k;
+    return k > INT32_MAX ? SPK_ERR_UNSUPPORTED : SPK_OK;
+}
+
+int SpkAssemblyCheckKappa(int mx, int my, const double *kappa)
+{
+    if (mx < 2 || my < 2) return SPK_ERR_ARG;
+    if (!kappa) return SPK_OK;
+    const int64_t ne = (int64_t)(mx - 1) * (my - 1);
+    for (int64_t e = 0; e < ne; ++e)
+        if (!(kappa[e] > 0.0) || !std::isfinite(kappa[e])) return SPK_ERR_ARG;
+    return SPK_OK;
+}
+
+int SpkAssembleOperator_LaplaceKappa(int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int32_t *rowptr,
+                                     int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
 {
     const int64_t line = (int64_t)2 * mx;
     if (!rowptr || !colidx || !val) return SPK_ERR_ARG;
     if (SpkAssemblySlabNnz(mx, my, row_begin, row_end) < 0) return SPK_ERR_ARG;
     if ((int64_t)2 * mx * my > INT32_MAX) return SPK_ERR_UNSUPPORTED;
+    if (const int rc = SpkAssemblyCheckKappa(mx, my, kappa)) return rc;   // (before anything is written)
     const int j0 = (int)(row_begin / line), j1 = (int)(row_end / line);
 
     // row pointers (closed form per node)
-    {
-        int64_t k = 0;
-        int64_t r = 0;
-        for (int j = j0; j < j1; ++j)
-            for (int i = 0; i < mx; ++i) {
-                const int w = node_row_nnz(mx, my, i, j);
-                rowptr[r++] = (int32_t)k; k += w;
-                rowptr[r++] = (int32_t)k; k += w;
-            }
-        rowptr[r] = (int32_t)k;
-        if (k > INT32_MAX) return SPK_ERR_UNSUPPORTED;
-    }
+    if (const int rc = SpkAssemblyRowPointers(mx, my, row_begin, row_end, rowptr)) return rc;
 
     const int nt = std::max(1, std::min(threads_or_default(nthreads), j1 - j0));
     auto work = [&](int t) {
@@ -251,12 +270,13 @@ int SpkAssembleOperator_Laplace(int mx, int my, int64_t row_begin, int64_t row_e
         const int ne = mx - 1;
         // element matrices / loads of element lines below (ej = j-1) and above (ej = j)
         std::vector<double> KeLo((size_t)ne * 64), KeHi((size_t)ne * 64), FeLo((size_t)ne * 8), FeHi((size_t)ne * 8);
-        const double coeff[4] = {1.0, 1.0, 1.0, 1.0};
         auto fill_line = [&](int ej, std::vector<double> &Ke, std::vector<double> &Fe) {
             if (ej < 0 || ej > my - 2) return;
             for (int ei = 0; ei < ne; ++ei) {
                 double xe[8];
                 element_coords(mx, my, ei, ej, xe);
+                const double kp = kappa ? kappa[(size_t)ej * ne + ei] : 1.0;   // one value per element, at its four Gauss points
+                const double coeff[4] = {kp, kp, kp, kp};
                 stiffness(xe, coeff, &Ke[(size_t)ei * 64]);
                 load(xe, &Fe[(size_t)ei * 8]);
             }
@@ -321,6 +341,12 @@ int SpkAssembleOperator_Laplace(int mx, int my, int64_t row_begin, int64_t row_e
     work(0);
     for (auto &th : pool) th.join();
     return SPK_OK;
+}
+
+int SpkAssembleOperator_Laplace(int mx, int my, int64_t row_begin, int64_t row_end, int32_t *rowptr,
+                                int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
+{
+    return SpkAssembleOperator_LaplaceKappa(mx, my, row_begin, row_end, nullptr, rowptr, colidx, val, f, apply_bc, nthreads);
 }
 
 int64_t SpkConstraintsSlabNnz(int mx, int my, int64_t row_begin, int64_t row_end)

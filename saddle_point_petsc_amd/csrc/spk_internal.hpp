@@ -486,6 +486,11 @@ void csr_split(const int32_t *rowptr, const int32_t *colidx, const double *val, 
                const int32_t *orp, int32_t *d_rowptr, int32_t *d_col, double *d_val, int32_t *o_col, double *o_val, hipStream_t s);
 void bcsr_fill(const int32_t *rp, const int32_t *ci, const double *va, int nbr, int32_t *browptr, int32_t *bcol, double *vtop,
                double *vbot, int32_t *fail, hipStream_t s);
+// spk_k_assembly.hip: the CSR slab and f (may be null) of node lines [j0, j1) of the mx x my grid, bit for bit the host
+// assembler's; kappa: one value per element of the whole grid on the device, or null for ones.  rowptr: 2 mx (j1 - j0) + 1.
+void assemble_laplace(int mx, int my, int j0, int j1, const double *kappa, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val,
+                      double *f, hipStream_t s);
+void kappa_check(const double *kappa, int64_t ne, int32_t *flag, hipStream_t s);   // flag[0] := 1 for an entry not finite and > 0
 // f.out[r] = B_r . x, r < m
 void wide_dot(const WideDev &B, const double *x, const Finish &f, const int32_t *done, hipStream_t s,
               const int32_t *rowmap = nullptr);
@@ -919,6 +924,7 @@ struct spk_ctx {
     spk::DevBuf<double> sw, sfac;          // m planes of stride ld; the Cholesky factor of S (m x m, lower)
     std::vector<double> schur_S;           // S as factored (host, m x m)
     double schur_setup_seconds = 0.0;      // what W, S and the factor added to the last set-up
+    double assembly_seconds = 0.0;         // the kernels of the last device assembly, up to a device synchronise
     spk::k::SchurW schur_w() const { return spk::k::SchurW{amg_d ? sw.p : bd.p, ld, m, sfac.p}; }
     // FP32 inner solve (0 sweeps = plain diag(A)^-1)
     int inner_sweeps = 0;
@@ -1029,6 +1035,10 @@ void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono
                   const double *hist, int32_t hist_cap, spk_result *res, double *history, int32_t history_cap);
 void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
                const int32_t *rowptr, const int32_t *colidx, const double *val);
+// A00 of the reference's own discretisation assembled on the device (spk_k_assembly.hip), then set_block's chain
+void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
+void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                          int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
 
 // The host side of the frame MINRES and pipelined CG share (spk_minres.cpp, spk_pipecg.cpp).  The host only ENQUEUES
 // iterations, each gated by the state's `done` word; the scalar steps run on the device.  The state is copied into a

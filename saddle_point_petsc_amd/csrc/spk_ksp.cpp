@@ -32,6 +32,7 @@ struct SpkKSP_s {
     spk_amg_opts amg[2];
     bool amg_reuse[2] = {false, false};             // -pc_gamg_reuse_interpolation, plain and with -fieldsplit_0_
     bool have_ops = false, is_setup = false, has_B = false;
+    bool ops_device = false;   // the last KSPSetOperators assembled A00 on the device (-ksp_view)
     int32_t n_rows_B = 0;   // m (-ksp_view)
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
@@ -204,14 +205,11 @@ int SpkKSPSetCommRCCL(SpkKSP k, int rank, int nranks, const void *id128)
     return from_ctx(k, spk_comm_enable_peer(k->ctx, nullptr));
 }
 
-int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
+// what follows A00 in KSPSetOperators on either route: the constraint block, then the facade's state
+static int set_operators_tail(SpkKSP k, const SpkMatCSR *B, bool device)
 {
-    if (!k) return SPK_ERR_ARG;
-    if (!A) return set_err(k, SPK_ERR_ARG, "KSPSetOperators: null operator");
-    int rc = ensure_ctx(k);
-    if (rc != SPK_OK) return rc;
-    rc = spk_set_block(k->ctx, SPK_BLOCK_A00, A->row_begin, A->nrows_local, A->ncols_global, A->rowptr, A->colidx, A->val);
-    if (rc != SPK_OK) return from_ctx(k, rc);
+    int rc = SPK_OK;
+    k->ops_device = device;
     k->has_B = false;
     k->n_rows_B = 0;
     if (B) {
@@ -223,6 +221,40 @@ int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
     k->have_ops = true;
     k->is_setup = false;
     return SPK_OK;
+}
+
+int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
+{
+    if (!k) return SPK_ERR_ARG;
+    if (!A) return set_err(k, SPK_ERR_ARG, "KSPSetOperators: null operator");
+    int rc = ensure_ctx(k);
+    if (rc != SPK_OK) return rc;
+    rc = spk_set_block(k->ctx, SPK_BLOCK_A00, A->row_begin, A->nrows_local, A->ncols_global, A->rowptr, A->colidx, A->val);
+    if (rc != SPK_OK) return from_ctx(k, rc);
+    return set_operators_tail(k, B, false);
+}
+
+int SpkKSPSetOperatorsLaplace(SpkKSP k, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host)
+{
+    if (!k) return SPK_ERR_ARG;
+    int rc = ensure_ctx(k);
+    if (rc != SPK_OK) return rc;
+    double *fd = nullptr;
+    const int64_t cap = (mx >= 2 && my >= 2) ? (int64_t)2 * mx * my : 0;   // (the rank's rows are at most all of them)
+    if (f_host && cap > 0 && cap <= INT32_MAX) {
+        rc = spk_vec_create(k->ctx, cap, &fd);
+        if (rc != SPK_OK) return from_ctx(k, rc);
+    }
+    rc = spk_set_block_laplace(k->ctx, mx, my, kappa, SPK_MEM_HOST, 1, fd);
+    if (rc == SPK_OK && fd) {
+        int32_t nl = 0;
+        spk_get_sizes(k->ctx, nullptr, &nl, nullptr, nullptr, nullptr);
+        rc = spk_vec_get(k->ctx, fd, f_host, nl);
+    }
+    if (rc != SPK_OK) from_ctx(k, rc);   // (the message, before the clean-up can replace it)
+    if (fd) spk_vec_destroy(k->ctx, fd);
+    if (rc != SPK_OK) return rc;
+    return set_operators_tail(k, B, true);
 }
 
 int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
@@ -516,6 +548,12 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
             std::printf("left preconditioning, pc=%s, residual replacement tau=%g, replacements=%d\n", pc, k->rr_tau,
                         k->replacements);
         }
+    }
+    if (k->view) {
+        double secs = 0.0;
+        spk_get_assembly_seconds(k->ctx, &secs);
+        if (k->ops_device) std::printf("  A00: assembled on the device (-spk_assembly device), kernels %.6f s\n", secs);
+        else std::printf("  A00: the caller's host arrays (-spk_assembly host)\n");
     }
     if (k->view && k->pc_type == SPK_PC_SCHUR) {
         double secs = 0.0;

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "spk_internal.hpp"
+#include "../../include/spk_assembly.h"
 
 namespace spk {
 
@@ -278,9 +279,8 @@ struct SlabIn {
     int32_t noff = 0;
 };
 
-// Validation: host checks, then the column range on the device.  Nothing of the context changes here.
-static void a_validate(spk_ctx *c, int64_t row_begin, int32_t n, int64_t ncols_global, const int32_t *rowptr, const int32_t *colidx,
-                       const double *val, SlabIn &in)
+// Validation, host part: nothing of the context changes here.
+static void a_check_host(int64_t row_begin, int32_t n, int64_t ncols_global, const int32_t *rowptr)
 {
     if (rowptr[0] != 0) fail(SPK_ERR_ARG, "A00: rowptr[0] must be 0");
     if (row_begin < 0 || row_begin + n > ncols_global)
@@ -288,12 +288,37 @@ static void a_validate(spk_ctx *c, int64_t row_begin, int32_t n, int64_t ncols_g
              (long long)(row_begin + n), (long long)ncols_global, (long long)ncols_global);
     for (int32_t r = 0; r < n; ++r)
         if (rowptr[r + 1] < rowptr[r]) fail(SPK_ERR_ARG, "A00: rowptr not monotone at row %d", r);
-    hipStream_t s = c->stream;
+}
+
+// One source of the slab: the caller's host arrays through the staging pipeline ...
+static void a_bring_upload(spk_ctx *c, int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, SlabIn &in)
+{
     const int64_t nnz = rowptr[n];
     up(c, in.rowptr, rowptr, (size_t)n + 1, 8);
     up(c, in.colidx, colidx, (size_t)nnz, 16);
     up(c, in.val, val, (size_t)nnz, 16);
-    // off-rank entries per row (and the column range check), exclusive scan
+}
+
+// ... the other: the assembly kernel writes it where the chain reads it (kappa_d: on the device, or null)
+static void a_bring_laplace(spk_ctx *c, int mx, int my, int64_t row_begin, int32_t n, int64_t nnz, const double *kappa_d, int apply_bc,
+                            double *f_dev, SlabIn &in)
+{
+    hipStream_t s = c->stream;
+    in.rowptr.alloc_raw((size_t)n + 1, 8);
+    in.colidx.alloc_raw((size_t)nnz, 16);
+    in.val.alloc_raw((size_t)nnz, 16);
+    const int j0 = (int)(row_begin / (2 * (int64_t)mx));
+    SPK_HIP(hipStreamSynchronize(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    k::assemble_laplace(mx, my, j0, j0 + n / (2 * mx), kappa_d, apply_bc, in.rowptr.p, in.colidx.p, in.val.p, f_dev, s);
+    SPK_HIP(hipStreamSynchronize(s));
+    c->assembly_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Validation, device part: off-rank entries per row (and the column range check), exclusive scan
+static void a_check_device(spk_ctx *c, int64_t row_begin, int32_t n, int64_t ncols_global, SlabIn &in)
+{
+    hipStream_t s = c->stream;
     DevBuf<int32_t> cnt, scratch;
     cnt.alloc_raw((size_t)n, 8);
     in.orp.alloc_raw((size_t)n + 1, 8);
@@ -475,16 +500,21 @@ static void a_install_halo(spk_ctx *c, HaloPlan &h)
     c->xghost.alloc((size_t)c->n_ghost, 8);
 }
 
-static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
-                        const int32_t *rowptr, const int32_t *colidx, const double *val)
+// One chain for both sources of the slab.  prepare(): the source's own refusals and the host row pointers (returned),
+// before anything is allocated; bring(in): the slab into device memory.
+template <class Prepare, class Bring>
+static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int64_t ncols_global, Prepare prepare, Bring bring)
 {
     std::vector<int32_t> garray;   // sorted global numbers of the off-rank columns (MatMPIAIJ's garray)
-    // ---- local part: validation, upload, split and blocking on the device (no collective inside)
+    // ---- local part: validation, upload or assembly, split and blocking on the device (no collective inside)
     agree_or_fail(c, locally([&] {
         SlabIn in;
         HostBuf<int32_t> drp;
         std::vector<int32_t> orp_h, ocol_h;
-        a_validate(c, row_begin, nrows_local, ncols_global, rowptr, colidx, val, in);
+        const int32_t *rowptr = prepare();
+        a_check_host(row_begin, nrows_local, ncols_global, rowptr);
+        bring(in);
+        a_check_device(c, row_begin, nrows_local, ncols_global, in);
         a_replace_state(c, row_begin, nrows_local, ncols_global);
         a_split(c, in, rowptr, drp, orp_h, ocol_h);
         a_offrank(c, in, orp_h, ocol_h, garray);
@@ -598,12 +628,91 @@ void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, in
         fail(SPK_ERR_ARG, "set_block: null array");
     if (nrows_local < 0) fail(SPK_ERR_ARG, "set_block: negative row count");
     c->ensure_scratch();
-    if (which == SPK_BLOCK_A00) set_block_A(c, row_begin, nrows_local, ncols_global, rowptr, colidx, val);
+    if (which == SPK_BLOCK_A00)
+        set_block_A(c, row_begin, nrows_local, ncols_global, [&] { return rowptr; },
+                    [&](SlabIn &in) { a_bring_upload(c, nrows_local, rowptr, colidx, val, in); });
     else if (which == SPK_BLOCK_A10)
         // no collective inside, but every rank sets its column slice: agree on the outcome so that a rank
         // whose slice was refused does not leave the others to run into the next collective alone
         agree_or_fail(c, locally([&] { set_block_B(c, nrows_local, ncols_global, rowptr, colidx, val); }), "A10");
     else fail(SPK_ERR_ARG, "set_block: unknown block %d", which);
+}
+
+// ---------------------------------------------------------------------------
+// KSPSetOperators, A00 of the reference's own discretisation: the slab assembled on the device
+// ---------------------------------------------------------------------------
+// kappa on the device, checked: a host array is checked on the host and uploaded, a device array by one kernel.  Null stays null.
+static const double *kappa_on_device(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, DevBuf<double> &own)
+{
+    if (!kappa) return nullptr;
+    if (kappa_mem != SPK_MEM_HOST && kappa_mem != SPK_MEM_DEVICE) fail(SPK_ERR_ARG, "device assembly: kappa_mem %d", kappa_mem);
+    const int64_t ne = (int64_t)(mx - 1) * (my - 1);
+    const char *bad = "device assembly: an entry of kappa is not finite and > 0";
+    if (kappa_mem == SPK_MEM_HOST) {
+        if (SpkAssemblyCheckKappa(mx, my, kappa) != SPK_OK) fail(SPK_ERR_ARG, "%s", bad);
+        own.upload(kappa, (size_t)ne);
+        return own.p;
+    }
+    DevBuf<int32_t> flag;
+    flag.alloc(4);
+    int32_t h = 1;
+    k::kappa_check(kappa, ne, flag.p, c->stream);
+    SPK_HIP(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    if (h) fail(SPK_ERR_ARG, "%s", bad);
+    return kappa;
+}
+
+// the refusals that need no GPU; returns the slab's stored non-zeros
+static int64_t laplace_slab_limits(int mx, int my, int64_t row_begin, int64_t row_end)
+{
+    if (mx < 2 || my < 2) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d nodes (at least 2 x 2)", mx, my);
+    if ((int64_t)2 * mx * my > INT32_MAX)
+        fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld rows exceed 32-bit indices", (long long)2 * mx * my);
+    const int64_t nnz = SpkAssemblySlabNnz(mx, my, row_begin, row_end);
+    if (nnz < 0) fail(SPK_ERR_ARG, "device assembly: rows [%lld,%lld) are not whole node lines of the grid", (long long)row_begin, (long long)row_end);
+    if (nnz > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld stored non-zeros of the slab exceed 32-bit indices", (long long)nnz);
+    return nnz;
+}
+
+void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+{
+    c->ensure_scratch();
+    int64_t rb = 0, re = 0, nnz = 0;
+    // sizes first, and only where they make sense (the chain's own refusal path reports the rest)
+    const bool sane = mx >= 2 && my >= 2 && (int64_t)2 * mx * my <= INT32_MAX;
+    if (sane && spk_partition_slab(my, 2 * (int64_t)mx, c->comm->rank(), c->comm->size(), &rb, &re) != SPK_OK)
+        fail(SPK_ERR_ARG, "device assembly: spk_partition_slab failed");
+    const int32_t n = (int32_t)(re - rb);
+    HostBuf<int32_t> rowptr;
+    DevBuf<double> kappa_own;
+    const double *kappa_d = nullptr;
+    set_block_A(c, rb, n, (int64_t)2 * mx * my, [&] {
+        nnz = laplace_slab_limits(mx, my, rb, re);
+        kappa_d = kappa_on_device(c, mx, my, kappa, kappa_mem, kappa_own);
+        rowptr.alloc((size_t)n + 1);
+        if (SpkAssemblyRowPointers(mx, my, rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
+        return (const int32_t *)rowptr.data();
+    }, [&](SlabIn &in) { a_bring_laplace(c, mx, my, rb, n, nnz, kappa_d, apply_bc, f_dev, in); });
+}
+
+void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                          int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
+{
+    if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace_csr: null array");
+    const int64_t nnz = laplace_slab_limits(mx, my, row_begin, row_end);
+    DevBuf<double> kappa_own, fd;
+    const double *kappa_d = kappa_on_device(c, mx, my, kappa, kappa_mem, kappa_own);
+    const int32_t n = (int32_t)(row_end - row_begin);
+    SlabIn in;
+    if (f) fd.alloc_raw((size_t)n, 8);
+    const double keep = c->assembly_seconds;
+    a_bring_laplace(c, mx, my, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
+    c->assembly_seconds = keep;   // (a test hook: the context's last assembly is the operator's)
+    SPK_HIP(hipMemcpy(rowptr, in.rowptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(val, in.val.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
+    if (f) SPK_HIP(hipMemcpy(f, fd.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
 }
 
 // ---------------------------------------------------------------------------

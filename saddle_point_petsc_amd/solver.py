@@ -428,6 +428,58 @@ class Context:
         self._chk(lib.spk_set_block(self.h, which, A.row_begin if which == BLOCK_A00 else 0, nrows,
                                     A.ncols, A.rowptr, A.colidx, A.val))
 
+    @staticmethod
+    def _kappa(mx, my, kappa):
+        """(pointer, mem, keep-alive) of a coefficient: None, a device vector of vec_create, or a host array."""
+        from .assembly import element_kappa
+        if kappa is None:
+            return None, MEM_HOST, None
+        if isinstance(kappa, C.c_void_p):
+            return kappa, MEM_DEVICE, kappa
+        k = element_kappa(mx, my, kappa)
+        return k.ctypes.data, MEM_HOST, k
+
+    def set_block_laplace(self, mx, my=None, kappa=None, apply_bc=True, rhs=None):
+        """KSPSetOperators for A00 of the reference's own discretisation, assembled on the device (spk_set_block_laplace):
+        what AssembleOperator_Laplace(..., kappa=kappa) + set_block(BLOCK_A00, A) do for this rank's slab, without the host
+        arrays.  kappa: None, one host value per element ((mx-1)*(my-1)), or a device vector of vec_create holding them.
+        rhs: a device vector of vec_create (n_local values) that receives f, or True to get f back as a numpy array."""
+        my = mx if my is None else my
+        kp, mem, _keep = self._kappa(mx, my, kappa)
+        if rhs is True:
+            fd = self.vec_create(n=2 * mx * my if 2 <= mx and 2 <= my and 2 * mx * my < 2 ** 31 else 1)
+            try:
+                self._chk(lib.spk_set_block_laplace(self.h, mx, my, kp, mem, int(apply_bc), fd))
+                return self.vec_get(fd, self.sizes()["n_local"])
+            finally:
+                self.vec_destroy(fd)
+        self._chk(lib.spk_set_block_laplace(self.h, mx, my, kp, mem, int(apply_bc), rhs))
+        return None
+
+    def assemble_laplace_csr(self, mx, my=None, row_begin=0, row_end=None, kappa=None, apply_bc=True):
+        """Test hook: (CSR, f) of rows [row_begin,row_end) from the device assembly kernels (spk_assemble_laplace_csr);
+        touches nothing of the context's operator."""
+        from .assembly import grid_sizes
+        from .csr import CSR
+        my = mx if my is None else my
+        n, _ = grid_sizes(mx, my)
+        row_end = n if row_end is None else row_end
+        nnz = lib.SpkAssemblySlabNnz(mx, my, row_begin, row_end)
+        if nnz < 0:
+            raise SpkError(-1, "row range must consist of whole node lines")
+        kp, mem, _keep = self._kappa(mx, my, kappa)
+        nl = row_end - row_begin
+        rowptr, colidx, val, f = np.zeros(nl + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz), np.zeros(nl)
+        self._chk(lib.spk_assemble_laplace_csr(self.h, mx, my, row_begin, row_end, kp, mem, int(apply_bc), rowptr, colidx, val,
+                                               f.ctypes.data))
+        return CSR(rowptr, colidx, val, n, row_begin), f
+
+    def assembly_seconds(self):
+        """Wall seconds of the kernels of the last set_block_laplace, up to a device synchronise (0 before one)."""
+        v = C.c_double()
+        self._chk(lib.spk_get_assembly_seconds(self.h, C.byref(v)))
+        return v.value
+
     def pc_setup(self, pc_type, schur_fact=SCHUR_FULL, inner_sweeps=0, inner_omega=1.0, amg=None, schur_pre="selfp",
                  amg_reuse=False):
         """inner_sweeps > 0: FP32 damped-Jacobi Richardson sweeps stand for diag(A)^-1.
@@ -723,6 +775,22 @@ class KSP:
         b = _mat(B) if B is not None else None
         self._chk(lib.SpkKSPSetOperators(self.h, C.byref(a), C.byref(b) if b is not None else None))
         self._n = A.nrows + (B.nrows if B is not None else 0)
+
+    def setOperatorsLaplace(self, mx, my=None, kappa=None, B=None, with_rhs=True):
+        """setOperators with A of the reference's own discretisation assembled on the device (SpkKSPSetOperatorsLaplace);
+        kappa: None or one host value per element.  Returns f (numpy) when with_rhs."""
+        from .assembly import element_kappa
+        my = mx if my is None else my
+        k = element_kappa(mx, my, kappa)
+        b = _mat(B) if B is not None else None
+        f = np.zeros(2 * mx * my if 2 <= mx and 2 <= my and 2 * mx * my < 2 ** 31 else 1) if with_rhs else None
+        self._chk(lib.SpkKSPSetOperatorsLaplace(self.h, mx, my, k.ctypes.data if k is not None else None,
+                                                C.byref(b) if b is not None else None, f.ctypes.data if with_rhs else None))
+        ctx, nl = C.c_void_p(), C.c_int32()
+        lib.SpkKSPGetContext(self.h, C.byref(ctx))
+        lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
+        self._n = nl.value + (B.nrows if B is not None else 0)
+        return f[:nl.value] if with_rhs else None
 
     def setFromOptions(self, options):
         """options: PETSc-style string or list, e.g. '-ksp_type fgmres -ksp_rtol 1e-8'."""

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""KSPSetOperators for A00, two routes in one process: (a) the host assembler (16 threads) followed by set_block of
+its arrays, (b) set_block_laplace, which assembles the slab on the device.  One warm-up of each route per grid, then
+`--reps` alternating repetitions; every time is a host clock around work that ends in a device synchronise (both calls
+are synchronous at return).  Prints one JSON line per grid and a table.
+
+  python tools/assembly_bench.py [--grids 256 512 1024] [--reps 5] [--out profiles/assembly_256_512_1024.jsonl]
+
+The kernel's share of 8 TB/s is a byte-model figure -- 12 B per stored non-zero plus row pointers and f written, kappa
+read -- of a kernel that is compute-heavy (an 8 x 8 element matrix per element and workgroup): it says how far the
+assembly is from the cost of merely writing its output, not how well it uses the memory system."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import saddle_point_petsc_amd as S  # noqa: E402
+
+HBM_BYTES_PER_SECOND = 8e12
+
+
+def stat(v):
+    return dict(median=round(statistics.median(v), 6), min=round(min(v), 6), max=round(max(v), 6))
+
+
+def host_route(c, m, threads):
+    t0 = time.perf_counter()
+    A, f = S.AssembleOperator_Laplace(m, nthreads=threads)
+    t1 = time.perf_counter()
+    c.set_block(S.BLOCK_A00, A)
+    t2 = time.perf_counter()
+    return t1 - t0, t2 - t1, t2 - t0
+
+
+def device_route(c, m, kappa, fdev):
+    t0 = time.perf_counter()
+    c.set_block_laplace(m, kappa=kappa, rhs=fdev)
+    t1 = time.perf_counter()
+    return t1 - t0, c.assembly_seconds()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grids", type=int, nargs="+", default=[256, 512, 1024])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--kappa", action="store_true", help="the device route with a coefficient array resident on the device")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+    for m in a.grids:
+        n, nnz = S.grid_sizes(m)
+        with S.Context(0) as ch, S.Context(0) as cd:
+            fdev = cd.vec_create(n=n)
+            kappa = cd.vec_create(np.full((m - 1) * (m - 1), 1.5)) if a.kappa else None
+            host_route(ch, m, a.threads)
+            device_route(cd, m, kappa, fdev)
+            asm, setb, both, dev, kern = [], [], [], [], []
+            for _ in range(a.reps):
+                t = host_route(ch, m, a.threads)
+                asm.append(t[0]), setb.append(t[1]), both.append(t[2])
+                t = device_route(cd, m, kappa, fdev)
+                dev.append(t[0]), kern.append(t[1])
+            same = cd.spmv_info() == ch.spmv_info() and cd.sizes() == ch.sizes()
+            cd.vec_destroy(fdev)
+            if kappa is not None:
+                cd.vec_destroy(kappa)
+        model = 12 * nnz + 4 * (n + 1) + 8 * n + (8 * (m - 1) ** 2 if a.kappa else 0)
+        d, sb = stat(dev), stat(setb)
+        line = dict(mode="assembly", grid=m, rows=n, nnz=nnz, reps=a.reps, threads=a.threads, kappa=bool(a.kappa),
+                    host_assemble_seconds=stat(asm), host_set_block_seconds=sb, host_total_seconds=stat(both),
+                    device_set_block_laplace_seconds=d, device_kernel_seconds=stat(kern), model_bytes=model,
+                    kernel_byte_model_share_of_8TBs=round(model / statistics.median(kern) / HBM_BYTES_PER_SECOND, 4),
+                    device_median_plus_spread_below_host_set_block_median=bool(d["median"] + (d["max"] - d["min"]) < sb["median"]),
+                    same_layout=bool(same))
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    print("\n| grid | host assembly (s) | host set_block (s) | host both (s) | device set_block_laplace (s) | kernels (ms) | byte model / 8 TB/s |")
+    print("|---|---|---|---|---|---|---|")
+    fmt = lambda s: f"{s['median']:.4f} ({s['min']:.4f}..{s['max']:.4f})"  # noqa: E731
+    for ln in lines:
+        k = ln["device_kernel_seconds"]
+        print(f"| {ln['grid']}² | {fmt(ln['host_assemble_seconds'])} | {fmt(ln['host_set_block_seconds'])} | {fmt(ln['host_total_seconds'])} | "
+              f"{fmt(ln['device_set_block_laplace_seconds'])} | {k['median'] * 1e3:.3f} ({k['min'] * 1e3:.3f}..{k['max'] * 1e3:.3f}) | "
+              f"{ln['kernel_byte_model_share_of_8TBs']:.3f} |")
+    if a.out:
+        with open(a.out, "w") as fh:
+            for ln in lines:
+                fh.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
