@@ -84,6 +84,44 @@ __device__ __forceinline__ void dict_prepare_types(const DictArgs &d, const Dict
 }
 // ... and this thread's block row of chunk ch, the last one beyond the end (re-read, not computed)
 __device__ __forceinline__ int dict_rowof(const DictArgs &d, int ch) { return min(ch * kDictChunk + (int)threadIdx.x, d.nbrows - 1); }
+// ... the same for a workgroup whose chunks end at c1: the stage it requests beyond them is never computed, so every lane
+// asks for the workgroup's own last block row (one address per load) instead of streaming the neighbour's first chunk
+__device__ __forceinline__ int dict_rowof(const DictArgs &d, int ch, int c1)
+{
+    return min(ch < c1 ? ch * kDictChunk + (int)threadIdx.x : c1 * kDictChunk - 1, d.nbrows - 1);
+}
+
+// The same tables for the pipelined 2x2 product when every one of them fits one pass of the workgroup (1024^2: 17 row
+// types, 7 classes): request() asks for this thread's words -- one row-type entry with its type's length, one class
+// entry, one field -- with clamped indices and no branch, commit() writes them to LDS: the entries already as
+// dict_prepare_types leaves them (its pass over LDS and its barrier are not needed), the lengths not at all (nothing
+// reads them afterwards).  Loads return in order: whatever the caller requests BETWEEN the two is in flight while commit()
+// waits for the table words alone.
+template <int KM, bool UNI>
+struct Dict2TableWords {
+    int2 ent;
+    int len, fl;
+    double2 cv;
+    __device__ __forceinline__ static bool fits(const DictArgs &d) { return d.ntype * KM <= kThreads && (d.nclass + 1) * 4 <= kThreads; }
+    __device__ __forceinline__ void request(const DictArgs &d)
+    {
+        const int e = min((int)threadIdx.x, d.ntype * KM - 1), c = min((int)threadIdx.x, (d.nclass + 1) * 4 - 1);
+        ent = reinterpret_cast<const int2 *>(d.tab + ((d.ntype + 1) & ~1))[e];
+        len = d.tab[e / KM];
+        cv = reinterpret_cast<const double2 *>(d.cls)[c];
+        fl = UNI ? 0 : d.fld[c];
+    }
+    __device__ __forceinline__ void commit(const DictArgs &d, const DictTables &T, int stride) const
+    {
+        const int i = threadIdx.x;
+        if (i < d.ntype * KM) T.tent[i] = i % KM < len ? make_int2(ent.x * stride, ent.y) : make_int2((int)0x80000000u, d.nclass);
+        if (i < (d.nclass + 1) * 4) {
+            const_cast<double2 *>(T.cv)[i] = cv;
+            if (!UNI) const_cast<int32_t *>(T.fl)[i] = fl;
+        }
+        __syncthreads();
+    }
+};
 
 // The stored form of a block: its bs*bs integer deviations k (value = base + k 2^g), each as a two's-complement BIT FIELD
 // of the width its class entry needs (1 .. 31 bits; the widths of a class fit 64 bits for 2x2 blocks, twice 64 for 3x3

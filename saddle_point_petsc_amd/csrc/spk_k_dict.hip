@@ -155,12 +155,13 @@ struct Dict2Stage {
     int cls[KM];
     double2 yv;
 };
+typedef decltype(__builtin_amdgcn_raw_buffer_load_b128(__amdgpu_buffer_rsrc_t(), 0, 0, 0)) b128_t;
 
-// (xr: x as a raw buffer of 16 * nbrows bytes -- a position beyond a row's length carries the offset 2^31 in the LDS copy
-// of its row type and the null class: the range check of the buffer load returns zeros, no select, no branch)
+// The loads of a stage in two parts.  What needs no table -- the code planes and y -- can be requested before the tables
+// are in LDS (the kernel's first requests to HBM) ...
+// (xr, yr: x and y as raw buffers of 16 * nbrows bytes)
 template <int KM, bool ACC>
-__device__ __forceinline__ void dict2_issue(const DictArgs &d, __amdgpu_buffer_rsrc_t xr, const double *__restrict__ y,
-                                            const int2 *tent, int tc, int brr, Dict2Stage<KM, ACC> &S)
+__device__ __forceinline__ void dict2_issue_stream(const DictArgs &d, __amdgpu_buffer_rsrc_t yr, int brr, Dict2Stage<KM, ACC> &S)
 {
     static_assert(KM % 2 == 1, "an odd last position: its plane holds single words");
 #pragma unroll
@@ -173,7 +174,17 @@ __device__ __forceinline__ void dict2_issue(const DictArgs &d, __amdgpu_buffer_r
         const int2v r = __builtin_nontemporal_load(reinterpret_cast<const int2v *>(d.codes + d.plane_off[KM / 2]) + brr);
         S.w[KM - 1] = (u64)(uint32_t)r.x | ((u64)(uint32_t)r.y << 32);
     }
-    if (ACC) S.yv = reinterpret_cast<const double2 *>(y)[brr];
+    if (ACC) {
+        const int4v r = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(yr, (int)((uint32_t)brr * 16u), 0, 0));
+        S.yv.x = __hiloint2double(r.y, r.x);
+        S.yv.y = __hiloint2double(r.w, r.z);
+    }
+}
+// ... and the gathers of x, which need the row type's entries in LDS (a position beyond a row's length carries the offset
+// 2^31 there and the null class: the range check of the buffer load returns zeros, no select, no branch)
+template <int KM, bool ACC>
+__device__ __forceinline__ void dict2_issue_gather(__amdgpu_buffer_rsrc_t xr, const int2 *tent, int tc, int brr, Dict2Stage<KM, ACC> &S)
+{
     const int2 *te = tent + (size_t)tc * KM;
     const uint32_t b16 = (uint32_t)brr * 16u;
 #pragma unroll
@@ -195,15 +206,41 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
     const int bx = product_prologue<RIDE>(done, gr, reinterpret_cast<double *>(smem));
     int c0, c1;
     if (bx < 0 || !dict_chunk_range(d, bx, c0, c1)) return;
-    // row types of the first two chunks: requested before the tables are copied
-    int tA = (int)d.tid[dict_rowof(d, c0)];
-    int tB = (int)d.tid[dict_rowof(d, c0 + 1)];
-    dict_load_lds(d, (d.nclass + 1) * 4, smem);
+    // decided once per workgroup: on one rank, without B^T rows, a row adds nothing to its sum of A x
+    const bool has_tail = BT || tail.od.rowptr != nullptr;
+    // Every workgroup of the launch is resident and starts here at once: HBM idles until the first of them asks for codes.
+    // So, in this order: the row types of the first two chunks; this thread's table words (out of L2); the code planes and
+    // y of the first chunk (HBM) -- and only then the wait for the table words, which were requested first and so arrive
+    // first.  The second chunk's planes are NOT requested here: the loop's header is reached from here and from its own
+    // back edge, and where the two differ in what is pending, every trip waits by the more cautious picture.  From the
+    // tables on, the requests stand in the loop's own order.
+    int tA = (int)d.tid[dict_rowof(d, c0, c1)];
+    int tB = (int)d.tid[dict_rowof(d, c0 + 1, c1)];
     const DictTables T = dict_tables(d, smem);
-    dict_prepare_types<KM>(d, T, 16);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x), 0, 16 * d.nbrows, 0x00020000);
-
+    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(y, 0, 16 * d.nbrows, 0x00020000);
+    Dict2TableWords<KM, UNI> tw;
+    tw.request(d);
+    __builtin_amdgcn_sched_barrier(0);   // (this order, not the scheduler's: a row type requested late is waited for late)
     Dict2Stage<KM, ACC> SA, SB;
+    dict2_issue_stream<KM, ACC>(d, yr, dict_rowof(d, c0, c1), SA);
+    if (Dict2TableWords<KM, UNI>::fits(d)) {
+        tw.commit(d, T, 16);
+    } else {   // tables beyond one pass of the workgroup: the copy loops (each drains the loads above)
+        dict_load_lds(d, (d.nclass + 1) * 4, smem);
+        dict_prepare_types<KM>(d, T, 16);
+    }
+    dict2_issue_gather<KM, ACC>(xr, T.tent, tA, dict_rowof(d, c0, c1), SA);
+    tA = (int)d.tid[dict_rowof(d, c0 + 2, c1)];
+
+    // The decode of a stage is unconditional and ends in an unconditional store: y is written through a raw buffer of
+    // 16 * nbrows bytes, whose range check drops the rows of a partial last chunk (their sums come from the clamped row's
+    // loads and are never seen).  (It used to end in `if (brc >= nbrows) return;`: the compiler sank the decode and its
+    // waits under that exec-mask branch, and the loop header waited for everything.)
+    // Off-rank columns and B^T entries of the row, where there are any, are the one guarded part (the row must exist): one
+    // branch per chunk, and the sums are needed on both sides of it, so the decode cannot sink under it.  Their loops wait
+    // for their own loads, which is why the header still waits for the stage it is about to decode before it requests the
+    // next one (profiles/product_pipeline_waits.txt).
     auto compute = [&](int ch, const Dict2Stage<KM, ACC> &S) {
         const int brc = ch * kDictChunk + (int)threadIdx.x;
         double s[2] = {0.0, 0.0};
@@ -226,28 +263,33 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
                 s[1] += dict_decode(dict_field2(S.w[g], fb[3]), cb[3]) * S.xv[g].y;
             }
         }
-        if (brc >= d.nbrows) return;
+        if (has_tail && brc < d.nbrows) {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            row_tail_add(tail, 2 * (int64_t)brc + r, s[r], BT);
-            if (ACC) s[r] += r == 0 ? S.yv.x : S.yv.y;
+            for (int r = 0; r < 2; ++r) row_tail_add(tail, 2 * (int64_t)brc + r, s[r], BT);
+        }
+        if (ACC) {
+            s[0] += S.yv.x;
+            s[1] += S.yv.y;
         }
         double2 o;
         o.x = s[0];
         o.y = s[1];
-        reinterpret_cast<double2 *>(y)[brc] = o;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(b128_t, o), yr, (int)((uint32_t)brc * 16u), 0, 0);
     };
-
-    dict2_issue<KM, ACC>(d, xr, y, T.tent, tA, dict_rowof(d, c0), SA);
-    tA = (int)d.tid[dict_rowof(d, c0 + 2)];
+    // One stage's loads (and the row type of the chunk after it) are requested, then the other stage is decoded.
+    auto issue = [&](int ch, int &t, Dict2Stage<KM, ACC> &S) {
+        dict2_issue_stream<KM, ACC>(d, yr, dict_rowof(d, ch, c1), S);
+        dict2_issue_gather<KM, ACC>(xr, T.tent, t, dict_rowof(d, ch, c1), S);
+        t = (int)d.tid[dict_rowof(d, ch + 2, c1)];
+        // (the scheduler must not trade the pipeline for registers: left free, it decodes the other stage first and requests
+        // this one behind it -- 104 VGPRs, and nothing in flight during the arithmetic)
+        __builtin_amdgcn_sched_barrier(0);
+    };
     for (int ch = c0;; ch += 2) {
-        // loads of the next chunk (and the row type of the one after it), then this chunk's arithmetic
-        dict2_issue<KM, ACC>(d, xr, y, T.tent, tB, dict_rowof(d, ch + 1), SB);
-        tB = (int)d.tid[dict_rowof(d, ch + 3)];
+        issue(ch + 1, tB, SB);
         compute(ch, SA);
         if (ch + 1 >= c1) break;
-        dict2_issue<KM, ACC>(d, xr, y, T.tent, tA, dict_rowof(d, ch + 2), SA);
-        tA = (int)d.tid[dict_rowof(d, ch + 4)];
+        issue(ch + 2, tA, SA);
         compute(ch + 1, SB);
         if (ch + 2 >= c1) break;
     }
