@@ -261,6 +261,20 @@ int spk_set_block_laplace(spk_ctx *ctx, int mx, int my, const double *kappa, int
 int spk_assemble_laplace_csr(spk_ctx *ctx, int mx, int my, int64_t row_begin, int64_t row_end,
                              const double *kappa, int kappa_mem, int apply_bc,
                              int32_t *rowptr, int32_t *colidx, double *val, double *f);
+/* The same for the 3-D generator of spk_assembly.h (Q1 hexahedra, dof 3, mx x my x mz nodes): what
+ * SpkAssembleOperator_Laplace3D[Kappa] + spk_set_block(SPK_BLOCK_A00) do, without the host arrays.  The rank's slab is
+ * the node planes spk_partition_slab(mz, 3*mx*my, rank, nranks) deals it.  kappa: one coefficient per hexahedron,
+ * (mx-1)*(my-1)*(mz-1) values of the WHOLE grid, element e = (ek*(my-1) + ej)*(mx-1) + ei, host or device memory, or
+ * NULL for ones.  f_dev as above.  Refused with the previous operator left in place and usable, before anything large
+ * is allocated: a grid side < 2 and an entry of kappa that is not finite and > 0 (SPK_ERR_ARG); 3*mx*my*mz, the slab's
+ * non-zeros or the launch grid beyond INT32_MAX (SPK_ERR_UNSUPPORTED).  Collective like spk_set_block. */
+int spk_set_block_laplace3d(spk_ctx *ctx, int mx, int my, int mz, const double *kappa, int kappa_mem,
+                            int apply_bc, double *f_dev /* n_local values, spk_vec_create memory, or NULL */);
+/* Test hook: the same kernel on any range of whole node planes, the result copied to host arrays sized as for
+ * SpkAssembleOperator_Laplace3D.  Touches nothing of the context's operator. */
+int spk_assemble_laplace3d_csr(spk_ctx *ctx, int mx, int my, int mz, int64_t row_begin, int64_t row_end,
+                               const double *kappa, int kappa_mem, int apply_bc,
+                               int32_t *rowptr, int32_t *colidx, double *val, double *f);
 /* Wall seconds of the last device assembly's kernels up to a device synchronise (0 before one). */
 int spk_get_assembly_seconds(const spk_ctx *ctx, double *seconds);
 

@@ -68,6 +68,20 @@ int SpkAssemblySizes3D(int mx, int my, int mz, int64_t *nrows, int64_t *nnz);
 int64_t SpkAssemblySlabNnz3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end);
 int SpkAssembleOperator_Laplace3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr,
                                   int32_t *colidx, double *val, double *f, int apply_bc, int nthreads);
+/* The same with a coefficient: kappa holds one value per HEXAHEDRON of the whole grid, (mx-1)(my-1)(mz-1) of them,
+ * element e = (ek*(my-1) + ej)*(mx-1) + ei, and enters the element's D: tD[k] = (k < 3 ? 2 : 1) * 1 * det J * kappa[e],
+ * the same at the eight Gauss points; f does not depend on it.  kappa == NULL: ones, and then bit for bit
+ * SpkAssembleOperator_Laplace3D, which forwards here.  SPK_ERR_ARG for an entry that is not finite and > 0, decided
+ * before any output is written.  The CPU oracle of spk_set_block_laplace3d (spk.h). */
+int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa,
+                                       int32_t *rowptr, int32_t *colidx, double *val, double *f, int apply_bc,
+                                       int nthreads);
+/* The row pointers of whole node planes [row_begin,row_end) alone ((row_end-row_begin)+1 entries from 0; a row of node
+ * (i,j,k) holds 3 w(i) w(j) w(k) entries, w = 2 at a face and 3 inside): what the assemblers above and the device
+ * route write.  SPK_ERR_UNSUPPORTED beyond 32-bit indices. */
+int SpkAssemblyRowPointers3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr);
+/* SPK_ERR_ARG when an entry of kappa ((mx-1)(my-1)(mz-1) values; NULL passes) is not finite and > 0. */
+int SpkAssemblyCheckKappa3D(int mx, int my, int mz, const double *kappa);
 int64_t SpkConstraintsSlabNnz3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end);
 int SpkAssembleOperator_Constraints3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr,
                                       int32_t *colidx, double *val);
@@ -96,6 +110,10 @@ int SpkWriteVTK(int mx, int my, const double *u, const char *filename);
  * order (i,j) (i,j+1) (i+1,j+1) (i+1,j). */
 int SpkFormStressOperatorQ12D(const double *xe, const double *coeff4, double *Ke64);
 int SpkFormLaplaceRHSQ12D(const double *xe, double *Fe8);
+/* The hexahedron of the 3-D generator: 24x24 stiffness Ke[a*24+b] and load Fe[24] for corner coordinates
+ * xe[24] = {x0,y0,z0, ...} in the order (i,j,k) (i,j+1,k) (i+1,j+1,k) (i+1,j,k), then the same four at k+1;
+ * coeff: the element's one coefficient (1.0 for the plain operator). */
+int SpkFormStressOperatorQ13D(const double *xe24, double coeff, double *Ke576, double *Fe24);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,9 @@ int SpkKSPSetOperators(SpkKSP ksp, const SpkMatCSR *A, const SpkMatCSR *B); /* K
  * B as above; f_host: receives the rank's n_local right-hand side values, or NULL.  Leaves the KSP in the state
  * SpkKSPSetOperators would; -ksp_view names the route. */
 int SpkKSPSetOperatorsLaplace(SpkKSP ksp, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host);
+/* The same for the 3-D generator of spk_assembly.h (spk_set_block_laplace3d): mx x my x mz nodes, dof 3; kappa: one host
+ * value per hexahedron, (mx-1)*(my-1)*(mz-1) of them, or NULL for ones. */
+int SpkKSPSetOperatorsLaplace3D(SpkKSP ksp, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host);
 /* argv-style option list, e.g. {"-ksp_type","fgmres","-ksp_rtol","1e-8",
  * "-pc_type","fieldsplit","-pc_fieldsplit_type","schur",
  * "-pc_fieldsplit_schur_fact_type","full"}.  Unknown -ksp_/-pc_/-fieldsplit_

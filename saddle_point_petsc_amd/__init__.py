@@ -10,6 +10,7 @@ from .assembly import (  # noqa: F401
     AssembleOperator_Laplace, AssembleOperator_Constraints, FormStressOperatorQ12D,
     FormLaplaceRHSQ12D, grid_sizes, partition_slab, WriteVTK, slab_row_pointers, element_kappa,
     AssembleOperator_Laplace3D, AssembleOperator_Constraints3D, AssembleOperator_Divergence3D, partition_slab3d,
+    FormStressOperatorQ13D, slab_row_pointers3d, element_kappa3d,
 )
 from .solver import (  # noqa: F401
     Context, KSP, LocalGroup, default_opts, unique_id,

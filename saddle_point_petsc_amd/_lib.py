@@ -191,6 +191,8 @@ def _load():
     L.spk_set_block.argtypes = [vp, C.c_int, i64, i32, i64, i32p, i32p, f64p]
     L.spk_set_block_laplace.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.spk_assemble_laplace_csr.argtypes = [vp, C.c_int, C.c_int, i64, i64, vp, C.c_int, C.c_int, i32p, i32p, f64p, vp]
+    L.spk_set_block_laplace3d.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.spk_assemble_laplace3d_csr.argtypes = [vp, C.c_int, C.c_int, C.c_int, i64, i64, vp, C.c_int, C.c_int, i32p, i32p, f64p, vp]
     L.spk_get_assembly_seconds.argtypes = [vp, C.POINTER(dbl)]
     L.spk_pc_setup.argtypes = [vp, C.c_int, C.c_int]
     L.spk_pc_set_inner.argtypes = [vp, C.c_int, C.c_double]
@@ -251,6 +253,9 @@ def _load():
     L.SpkAssemblySlabNnz3D.restype = i64
     L.SpkAssemblySlabNnz3D.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64]
     L.SpkAssembleOperator_Laplace3D.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i32p, i32p, f64p, vp, C.c_int, C.c_int]
+    L.SpkAssembleOperator_Laplace3DKappa.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, vp, i32p, i32p, f64p, vp, C.c_int, C.c_int]
+    L.SpkAssemblyRowPointers3D.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i32p]
+    L.SpkAssemblyCheckKappa3D.argtypes = [C.c_int, C.c_int, C.c_int, vp]
     L.SpkConstraintsSlabNnz3D.restype = i64
     L.SpkConstraintsSlabNnz3D.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64]
     L.SpkAssembleOperator_Constraints3D.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i32p, i32p, f64p]
@@ -261,11 +266,13 @@ def _load():
     L.SpkWriteVTK.argtypes = [C.c_int, C.c_int, f64p, C.c_char_p]
     L.SpkFormStressOperatorQ12D.argtypes = [f64p, f64p, f64p]
     L.SpkFormLaplaceRHSQ12D.argtypes = [f64p, f64p]
+    L.SpkFormStressOperatorQ13D.argtypes = [f64p, C.c_double, f64p, f64p]
     # KSP facade
     L.SpkKSPCreate.argtypes = [C.c_int, C.POINTER(vp)]
     L.SpkKSPSetCommRCCL.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.SpkKSPSetOperators.argtypes = [vp, C.POINTER(MatCSR), C.POINTER(MatCSR)]
     L.SpkKSPSetOperatorsLaplace.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
+    L.SpkKSPSetOperatorsLaplace3D.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
     L.SpkKSPSetFromOptions.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
     L.SpkKSPSetUp.argtypes = [vp]
     L.SpkKSPSolve.argtypes = [vp, f64p, f64p]

@@ -105,9 +105,45 @@ def FormLaplaceRHSQ12D(xe):
     return Fe
 
 
-def AssembleOperator_Laplace3D(mx, my=None, mz=None, row_begin=0, row_end=None, apply_bc=True, nthreads=0):
+def element_kappa3d(mx, my, mz, kappa):
+    """kappa as the C ABI takes it: None, or a contiguous float64 array of (mx-1)*(my-1)*(mz-1) values, element
+    e = (ek*(my-1) + ej)*(mx-1) + ei (a 3-D array is indexed [ek, ej, ei])."""
+    if kappa is None:
+        return None
+    k = np.ascontiguousarray(kappa, np.float64).reshape(-1)
+    ne = (mx - 1) * (my - 1) * (mz - 1)
+    if k.size != ne:
+        raise ValueError(f"kappa must hold one value per element: {ne}, not {k.size}")
+    return k
+
+
+def slab_row_pointers3d(mx, my=None, mz=None, row_begin=0, row_end=None):
+    """The closed-form row pointers of whole node planes [row_begin,row_end) of the 3-D grid: what the host assembler
+    and the device route write."""
+    my = mx if my is None else my
+    mz = mx if mz is None else mz
+    row_end = 3 * mx * my * mz if row_end is None else row_end
+    if lib.SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end) < 0:
+        raise SpkError(-1, "row range must consist of whole node planes")
+    rowptr = np.zeros(row_end - row_begin + 1, np.int32)
+    _chk(lib.SpkAssemblyRowPointers3D(mx, my, mz, row_begin, row_end, rowptr), "SpkAssemblyRowPointers3D")
+    return rowptr
+
+
+def FormStressOperatorQ13D(xe, coeff=1.0):
+    """(Ke 24x24, Fe 24) of one hexahedron of the 3-D generator; xe: 24 corner coordinates in the generator's
+    corner order, coeff: the element's coefficient."""
+    Ke, Fe = np.zeros(576), np.zeros(24)
+    _chk(lib.SpkFormStressOperatorQ13D(np.ascontiguousarray(xe, np.float64).reshape(-1), float(coeff), Ke, Fe),
+         "SpkFormStressOperatorQ13D")
+    return Ke.reshape(24, 24), Fe
+
+
+def AssembleOperator_Laplace3D(mx, my=None, mz=None, row_begin=0, row_end=None, apply_bc=True, nthreads=0, kappa=None):
     """BUILD-DEFINED 3-D input generator (the reference is 2-D only; see include/spk_assembly.h):
-    A (CSR slab of whole node planes, global columns) and f on an mx x my x mz node grid, dof 3."""
+    A (CSR slab of whole node planes, global columns) and f on an mx x my x mz node grid, dof 3.  kappa: one
+    coefficient per hexahedron of the whole grid ((mx-1)*(my-1)*(mz-1) values, element (ek*(my-1) + ej)*(mx-1) + ei);
+    None: ones (SpkAssembleOperator_Laplace3DKappa, the CPU oracle of Context.set_block_laplace3d)."""
     my = mx if my is None else my
     mz = mx if mz is None else mz
     n, nnz = C.c_int64(), C.c_int64()
@@ -121,8 +157,14 @@ def AssembleOperator_Laplace3D(mx, my=None, mz=None, row_begin=0, row_end=None, 
     colidx = np.zeros(nz, np.int32)
     val = np.zeros(nz)
     f = np.zeros(nl)
-    _chk(lib.SpkAssembleOperator_Laplace3D(mx, my, mz, row_begin, row_end, rowptr, colidx, val, f.ctypes.data,
-                                           int(apply_bc), nthreads), "SpkAssembleOperator_Laplace3D")
+    if kappa is None:
+        _chk(lib.SpkAssembleOperator_Laplace3D(mx, my, mz, row_begin, row_end, rowptr, colidx, val, f.ctypes.data,
+                                               int(apply_bc), nthreads), "SpkAssembleOperator_Laplace3D")
+    else:
+        k = element_kappa3d(mx, my, mz, kappa)
+        _chk(lib.SpkAssembleOperator_Laplace3DKappa(mx, my, mz, row_begin, row_end, k.ctypes.data, rowptr, colidx, val,
+                                                    f.ctypes.data, int(apply_bc), nthreads),
+             "SpkAssembleOperator_Laplace3DKappa: an entry of kappa is not finite and > 0")
     return CSR(rowptr, colidx, val, n.value, row_begin), f
 
 

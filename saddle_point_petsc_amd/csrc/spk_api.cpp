@@ -307,6 +307,21 @@ int spk_assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int6
     SPK_CATCH(c)
 }
 
+int spk_set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+{
+    SPK_TRY(c)
+    spk::set_block_laplace3d(c, mx, my, mz, kappa, kappa_mem, apply_bc, f_dev);
+    SPK_CATCH(c)
+}
+
+int spk_assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa,
+                               int kappa_mem, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
+{
+    SPK_TRY(c)
+    spk::assemble_laplace3d_csr(c, mx, my, mz, row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
+    SPK_CATCH(c)
+}
+
 int spk_get_assembly_seconds(const spk_ctx *c, double *seconds)
 {
     if (!c || !seconds) return SPK_ERR_ARG;

@@ -130,8 +130,9 @@ inline int node_row_nnz(int mx, int my, int i, int j)
 // ---- 3-D (build-defined; see include/spk_assembly.h) ----
 const int kSgn3[8][3] = {{-1, -1, -1}, {-1, 1, -1}, {1, 1, -1}, {1, -1, -1}, {-1, -1, 1}, {-1, 1, 1}, {1, 1, 1}, {1, -1, 1}};
 
-// Ke[a*24+b] and Fe[24] of one hexahedron (same operation order as the oracle's restatement)
-void element3d(const double *xe, double *Ke, double *Fe)
+// Ke[a*24+b] and Fe[24] of one hexahedron (same operation order as the oracle's restatement); kp: the element's
+// coefficient, 1.0 for the plain operator
+void element3d(const double *xe, double kp, double *Ke, double *Fe)
 {
     double acc[576];
     std::memset(acc, 0, sizeof acc);
@@ -174,7 +175,7 @@ void element3d(const double *xe, double *Ke, double *Fe)
             Bm[4][3 * a + 1] = Gx[2][a]; Bm[4][3 * a + 2] = Gx[1][a];
             Bm[5][3 * a] = Gx[2][a];     Bm[5][3 * a + 2] = Gx[0][a];
         }
-        for (int k = 0; k < 6; ++k) tD[k] = (k < 3 ? 2.0 : 1.0) * 1.0 * det * 1.0;
+        for (int k = 0; k < 6; ++k) tD[k] = (k < 3 ? 2.0 : 1.0) * 1.0 * det * kp;
         for (int i = 0; i < 24; ++i)
             for (int j = 0; j < 24; ++j)
                 for (int k = 0; k < 6; ++k) acc[i + 24 * j] += Bm[k][i] * tD[k] * Bm[k][j];
@@ -407,25 +408,46 @@ int64_t SpkAssemblySlabNnz3D(int mx, int my, int mz, int64_t row_begin, int64_t 
     return nnz;
 }
 
-int SpkAssembleOperator_Laplace3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr,
-                                  int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
+int SpkAssemblyRowPointers3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr)
+{
+    const int64_t plane = (int64_t)3 * mx * my;
+    if (!rowptr) return SPK_ERR_ARG;
+    const int64_t total = SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end);
+    if (total < 0) return SPK_ERR_ARG;
+    if ((int64_t)3 * mx * my * mz > INT32_MAX || total > INT32_MAX) return SPK_ERR_UNSUPPORTED;
+    const int k0 = (int)(row_begin / plane), k1 = (int)(row_end / plane);
+    int64_t q = 0, r = 0;
+    for (int k = k0; k < k1; ++k)
+        for (int j = 0; j < my; ++j)
+            for (int i = 0; i < mx; ++i) {
+                const int w = width(i, mx) * width(j, my) * width(k, mz) * 3;
+                for (int c = 0; c < 3; ++c) { rowptr[r++] = (int32_t)q; q += w; }
+            }
+    rowptr[r] = (int32_t)q;
+    return SPK_OK;
+}
+
+int SpkAssemblyCheckKappa3D(int mx, int my, int mz, const double *kappa)
+{
+    if (mx < 2 || my < 2 || mz < 2) return SPK_ERR_ARG;
+    if (!kappa) return SPK_OK;
+    const int64_t ne = (int64_t)(mx - 1) * (my - 1) * (mz - 1);
+    for (int64_t e = 0; e < ne; ++e)
+        if (!(kappa[e] > 0.0) || !std::isfinite(kappa[e])) return SPK_ERR_ARG;
+    return SPK_OK;
+}
+
+int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa,
+                                       int32_t *rowptr, int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
 {
     const int64_t plane = (int64_t)3 * mx * my;
     if (!rowptr || !colidx || !val) return SPK_ERR_ARG;
     const int64_t total = SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end);
     if (total < 0) return SPK_ERR_ARG;
     if ((int64_t)3 * mx * my * mz > INT32_MAX || total > INT32_MAX) return SPK_ERR_UNSUPPORTED;
+    if (const int rc = SpkAssemblyCheckKappa3D(mx, my, mz, kappa)) return rc;   // (before anything is written)
     const int k0 = (int)(row_begin / plane), k1 = (int)(row_end / plane);
-    {
-        int64_t q = 0, r = 0;
-        for (int k = k0; k < k1; ++k)
-            for (int j = 0; j < my; ++j)
-                for (int i = 0; i < mx; ++i) {
-                    const int w = width(i, mx) * width(j, my) * width(k, mz) * 3;
-                    for (int c = 0; c < 3; ++c) { rowptr[r++] = (int32_t)q; q += w; }
-                }
-        rowptr[r] = (int32_t)q;
-    }
+    if (const int rc = SpkAssemblyRowPointers3D(mx, my, mz, row_begin, row_end, rowptr)) return rc;
     const int nlines = (k1 - k0) * my;  // node lines (j, k) of the slab
     const int nt = std::max(1, std::min(threads_or_default(nthreads), nlines));
     const int ne = mx - 1;
@@ -458,7 +480,8 @@ int SpkAssembleOperator_Laplace3D(int mx, int my, int mz, int64_t row_begin, int
                     xe[3 * a + 1] = coord(ej + (kSgn3[a][1] > 0), my);
                     xe[3 * a + 2] = coord(ek + (kSgn3[a][2] > 0), mz);
                 }
-                element3d(xe, &Ke[dj][dk][(size_t)ei * 576], &Fe[dj][dk][(size_t)ei * 24]);
+                const double kp = kappa ? kappa[((size_t)ek * (my - 1) + ej) * ne + ei] : 1.0;
+                element3d(xe, kp, &Ke[dj][dk][(size_t)ei * 576], &Fe[dj][dk][(size_t)ei * 24]);
             }
             tag_j[dj][dk] = ej;
             tag_k[dj][dk] = ek;
@@ -532,6 +555,12 @@ int SpkAssembleOperator_Laplace3D(int mx, int my, int mz, int64_t row_begin, int
     work(0);
     for (auto &th : pool) th.join();
     return SPK_OK;
+}
+
+int SpkAssembleOperator_Laplace3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *rowptr,
+                                  int32_t *colidx, double *val, double *f, int apply_bc, int nthreads)
+{
+    return SpkAssembleOperator_Laplace3DKappa(mx, my, mz, row_begin, row_end, nullptr, rowptr, colidx, val, f, apply_bc, nthreads);
 }
 
 int64_t SpkConstraintsSlabNnz3D(int mx, int my, int mz, int64_t row_begin, int64_t row_end)
@@ -649,6 +678,13 @@ int SpkFormLaplaceRHSQ12D(const double *xe, double *Fe8)
 {
     if (!xe || !Fe8) return SPK_ERR_ARG;
     load(xe, Fe8);
+    return SPK_OK;
+}
+
+int SpkFormStressOperatorQ13D(const double *xe, double coeff, double *Ke576, double *Fe24)
+{
+    if (!xe || !Ke576 || !Fe24) return SPK_ERR_ARG;
+    element3d(xe, coeff, Ke576, Fe24);
     return SPK_OK;
 }
 

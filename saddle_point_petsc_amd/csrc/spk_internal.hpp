@@ -490,6 +490,11 @@ void bcsr_fill(const int32_t *rp, const int32_t *ci, const double *va, int nbr, 
 // assembler's; kappa: one value per element of the whole grid on the device, or null for ones.  rowptr: 2 mx (j1 - j0) + 1.
 void assemble_laplace(int mx, int my, int j0, int j1, const double *kappa, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val,
                       double *f, hipStream_t s);
+// spk_k_assembly3d.hip: the same for the node planes [k0, k1) of the mx x my x mz grid of the 3-D generator (dof 3); kappa: one
+// value per hexahedron of the whole grid.  rowptr: 3 mx my (k1 - k0) + 1.  _grid: the workgroups it launches.
+void assemble_laplace3d(int mx, int my, int mz, int k0, int k1, const double *kappa, int apply_bc, int32_t *rowptr, int32_t *colidx,
+                        double *val, double *f, hipStream_t s);
+int64_t assemble_laplace3d_grid(int mx, int my, int k0, int k1);
 void kappa_check(const double *kappa, int64_t ne, int32_t *flag, hipStream_t s);   // flag[0] := 1 for an entry not finite and > 0
 // f.out[r] = B_r . x, r < m
 void wide_dot(const WideDev &B, const double *x, const Finish &f, const int32_t *done, hipStream_t s,
@@ -1039,6 +1044,10 @@ void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, in
 void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
 void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
                           int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
+// the same for the 3-D generator (spk_k_assembly3d.hip): whole node planes
+void set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
+void assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                            int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
 
 // The host side of the frame MINRES and pipelined CG share (spk_minres.cpp, spk_pipecg.cpp).  The host only ENQUEUES
 // iterations, each gated by the state's `done` word; the scalar steps run on the device.  The state is copied into a

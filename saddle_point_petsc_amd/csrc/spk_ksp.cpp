@@ -33,6 +33,7 @@ struct SpkKSP_s {
     bool amg_reuse[2] = {false, false};             // -pc_gamg_reuse_interpolation, plain and with -fieldsplit_0_
     bool have_ops = false, is_setup = false, has_B = false;
     bool ops_device = false;   // the last KSPSetOperators assembled A00 on the device (-ksp_view)
+    bool ops_device_3d = false;   // ... with the 3-D generator's kernel
     int32_t n_rows_B = 0;   // m (-ksp_view)
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
@@ -234,18 +235,21 @@ int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
     return set_operators_tail(k, B, false);
 }
 
-int SpkKSPSetOperatorsLaplace(SpkKSP k, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host)
+// A00 assembled on the device, mz == 0: the 2-D grid (spk_set_block_laplace), else the 3-D generator's
+static int set_operators_device(SpkKSP k, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host)
 {
     if (!k) return SPK_ERR_ARG;
     int rc = ensure_ctx(k);
     if (rc != SPK_OK) return rc;
     double *fd = nullptr;
-    const int64_t cap = (mx >= 2 && my >= 2) ? (int64_t)2 * mx * my : 0;   // (the rank's rows are at most all of them)
+    const bool sane = mx >= 2 && my >= 2 && (mz == 0 || mz >= 2);
+    const int64_t cap = sane ? (mz ? (int64_t)3 * mx * my * mz : (int64_t)2 * mx * my) : 0;   // (the rank's rows are at most all of them)
     if (f_host && cap > 0 && cap <= INT32_MAX) {
         rc = spk_vec_create(k->ctx, cap, &fd);
         if (rc != SPK_OK) return from_ctx(k, rc);
     }
-    rc = spk_set_block_laplace(k->ctx, mx, my, kappa, SPK_MEM_HOST, 1, fd);
+    rc = mz ? spk_set_block_laplace3d(k->ctx, mx, my, mz, kappa, SPK_MEM_HOST, 1, fd)
+            : spk_set_block_laplace(k->ctx, mx, my, kappa, SPK_MEM_HOST, 1, fd);
     if (rc == SPK_OK && fd) {
         int32_t nl = 0;
         spk_get_sizes(k->ctx, nullptr, &nl, nullptr, nullptr, nullptr);
@@ -254,7 +258,20 @@ int SpkKSPSetOperatorsLaplace(SpkKSP k, int mx, int my, const double *kappa, con
     if (rc != SPK_OK) from_ctx(k, rc);   // (the message, before the clean-up can replace it)
     if (fd) spk_vec_destroy(k->ctx, fd);
     if (rc != SPK_OK) return rc;
-    return set_operators_tail(k, B, true);
+    rc = set_operators_tail(k, B, true);
+    if (rc == SPK_OK) k->ops_device_3d = mz != 0;
+    return rc;
+}
+
+int SpkKSPSetOperatorsLaplace(SpkKSP k, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host)
+{
+    return set_operators_device(k, mx, my, 0, kappa, B, f_host);
+}
+
+int SpkKSPSetOperatorsLaplace3D(SpkKSP k, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host)
+{
+    if (k && mz == 0) return set_err(k, SPK_ERR_ARG, "KSPSetOperatorsLaplace3D: mz = 0 (at least 2 x 2 x 2 nodes)");
+    return set_operators_device(k, mx, my, mz, kappa, B, f_host);
 }
 
 int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
@@ -552,7 +569,8 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->view) {
         double secs = 0.0;
         spk_get_assembly_seconds(k->ctx, &secs);
-        if (k->ops_device) std::printf("  A00: assembled on the device (-spk_assembly device), kernels %.6f s\n", secs);
+        if (k->ops_device && k->ops_device_3d) std::printf("  A00: assembled on the device (SpkKSPSetOperatorsLaplace3D), kernels %.6f s\n", secs);
+        else if (k->ops_device) std::printf("  A00: assembled on the device (-spk_assembly device), kernels %.6f s\n", secs);
         else std::printf("  A00: the caller's host arrays (-spk_assembly host)\n");
     }
     if (k->view && k->pc_type == SPK_PC_SCHUR) {

@@ -642,14 +642,15 @@ void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, in
 // KSPSetOperators, A00 of the reference's own discretisation: the slab assembled on the device
 // ---------------------------------------------------------------------------
 // kappa on the device, checked: a host array is checked on the host and uploaded, a device array by one kernel.  Null stays null.
-static const double *kappa_on_device(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, DevBuf<double> &own)
+// mz == 0: the 2-D grid.
+static const double *kappa_on_device(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, DevBuf<double> &own)
 {
     if (!kappa) return nullptr;
     if (kappa_mem != SPK_MEM_HOST && kappa_mem != SPK_MEM_DEVICE) fail(SPK_ERR_ARG, "device assembly: kappa_mem %d", kappa_mem);
-    const int64_t ne = (int64_t)(mx - 1) * (my - 1);
+    const int64_t ne = (int64_t)(mx - 1) * (my - 1) * (mz ? mz - 1 : 1);
     const char *bad = "device assembly: an entry of kappa is not finite and > 0";
     if (kappa_mem == SPK_MEM_HOST) {
-        if (SpkAssemblyCheckKappa(mx, my, kappa) != SPK_OK) fail(SPK_ERR_ARG, "%s", bad);
+        if ((mz ? SpkAssemblyCheckKappa3D(mx, my, mz, kappa) : SpkAssemblyCheckKappa(mx, my, kappa)) != SPK_OK) fail(SPK_ERR_ARG, "%s", bad);
         own.upload(kappa, (size_t)ne);
         return own.p;
     }
@@ -689,7 +690,7 @@ void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kapp
     const double *kappa_d = nullptr;
     set_block_A(c, rb, n, (int64_t)2 * mx * my, [&] {
         nnz = laplace_slab_limits(mx, my, rb, re);
-        kappa_d = kappa_on_device(c, mx, my, kappa, kappa_mem, kappa_own);
+        kappa_d = kappa_on_device(c, mx, my, 0, kappa, kappa_mem, kappa_own);
         rowptr.alloc((size_t)n + 1);
         if (SpkAssemblyRowPointers(mx, my, rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
         return (const int32_t *)rowptr.data();
@@ -702,12 +703,84 @@ void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t
     if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace_csr: null array");
     const int64_t nnz = laplace_slab_limits(mx, my, row_begin, row_end);
     DevBuf<double> kappa_own, fd;
-    const double *kappa_d = kappa_on_device(c, mx, my, kappa, kappa_mem, kappa_own);
+    const double *kappa_d = kappa_on_device(c, mx, my, 0, kappa, kappa_mem, kappa_own);
     const int32_t n = (int32_t)(row_end - row_begin);
     SlabIn in;
     if (f) fd.alloc_raw((size_t)n, 8);
     const double keep = c->assembly_seconds;
     a_bring_laplace(c, mx, my, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
+    c->assembly_seconds = keep;   // (a test hook: the context's last assembly is the operator's)
+    SPK_HIP(hipMemcpy(rowptr, in.rowptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(val, in.val.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
+    if (f) SPK_HIP(hipMemcpy(f, fd.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+}
+
+// ---- the 3-D generator (spk_k_assembly3d.hip): the same chain, whole node planes
+static void a_bring_laplace3d(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int32_t n, int64_t nnz, const double *kappa_d,
+                              int apply_bc, double *f_dev, SlabIn &in)
+{
+    hipStream_t s = c->stream;
+    in.rowptr.alloc_raw((size_t)n + 1, 8);
+    in.colidx.alloc_raw((size_t)nnz, 16);
+    in.val.alloc_raw((size_t)nnz, 16);
+    const int64_t plane = 3 * (int64_t)mx * my;
+    const int k0 = (int)(row_begin / plane);
+    SPK_HIP(hipStreamSynchronize(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    k::assemble_laplace3d(mx, my, mz, k0, k0 + (int)(n / plane), kappa_d, apply_bc, in.rowptr.p, in.colidx.p, in.val.p, f_dev, s);
+    SPK_HIP(hipStreamSynchronize(s));
+    c->assembly_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the refusals that need no GPU; returns the slab's stored non-zeros
+static int64_t laplace3d_slab_limits(int mx, int my, int mz, int64_t row_begin, int64_t row_end)
+{
+    if (mx < 2 || my < 2 || mz < 2) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d x %d nodes (at least 2 x 2 x 2)", mx, my, mz);
+    const int64_t rows = (int64_t)3 * mx * my * mz;
+    if (rows > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld rows exceed 32-bit indices", (long long)rows);
+    const int64_t nnz = SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end);
+    if (nnz < 0) fail(SPK_ERR_ARG, "device assembly: rows [%lld,%lld) are not whole node planes of the grid", (long long)row_begin, (long long)row_end);
+    if (nnz > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld stored non-zeros of the slab exceed 32-bit indices", (long long)nnz);
+    const int64_t plane = 3 * (int64_t)mx * my;
+    const int64_t grid = k::assemble_laplace3d_grid(mx, my, (int)(row_begin / plane), (int)(row_end / plane));
+    if (grid > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld workgroups exceed the launch grid", (long long)grid);
+    return nnz;
+}
+
+void set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+{
+    c->ensure_scratch();
+    int64_t rb = 0, re = 0, nnz = 0;
+    // sizes first, and only where they make sense (the chain's own refusal path reports the rest)
+    const bool sane = mx >= 2 && my >= 2 && mz >= 2 && (int64_t)3 * mx * my * mz <= INT32_MAX;
+    if (sane && spk_partition_slab(mz, 3 * (int64_t)mx * my, c->comm->rank(), c->comm->size(), &rb, &re) != SPK_OK)
+        fail(SPK_ERR_ARG, "device assembly: spk_partition_slab failed");
+    const int32_t n = (int32_t)(re - rb);
+    HostBuf<int32_t> rowptr;
+    DevBuf<double> kappa_own;
+    const double *kappa_d = nullptr;
+    set_block_A(c, rb, n, (int64_t)3 * mx * my * mz, [&] {
+        nnz = laplace3d_slab_limits(mx, my, mz, rb, re);
+        kappa_d = kappa_on_device(c, mx, my, mz, kappa, kappa_mem, kappa_own);
+        rowptr.alloc((size_t)n + 1);
+        if (SpkAssemblyRowPointers3D(mx, my, mz, rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
+        return (const int32_t *)rowptr.data();
+    }, [&](SlabIn &in) { a_bring_laplace3d(c, mx, my, mz, rb, n, nnz, kappa_d, apply_bc, f_dev, in); });
+}
+
+void assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                            int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
+{
+    if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace3d_csr: null array");
+    const int64_t nnz = laplace3d_slab_limits(mx, my, mz, row_begin, row_end);
+    DevBuf<double> kappa_own, fd;
+    const double *kappa_d = kappa_on_device(c, mx, my, mz, kappa, kappa_mem, kappa_own);
+    const int32_t n = (int32_t)(row_end - row_begin);
+    SlabIn in;
+    if (f) fd.alloc_raw((size_t)n, 8);
+    const double keep = c->assembly_seconds;
+    a_bring_laplace3d(c, mx, my, mz, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
     c->assembly_seconds = keep;   // (a test hook: the context's last assembly is the operator's)
     SPK_HIP(hipMemcpy(rowptr, in.rowptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
     SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));

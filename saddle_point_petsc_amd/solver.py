@@ -474,6 +474,53 @@ class Context:
                                                f.ctypes.data))
         return CSR(rowptr, colidx, val, n, row_begin), f
 
+    @staticmethod
+    def _kappa3d(mx, my, mz, kappa):
+        from .assembly import element_kappa3d
+        if kappa is None:
+            return None, MEM_HOST, None
+        if isinstance(kappa, C.c_void_p):
+            return kappa, MEM_DEVICE, kappa
+        k = element_kappa3d(mx, my, mz, kappa)
+        return k.ctypes.data, MEM_HOST, k
+
+    def set_block_laplace3d(self, mx, my=None, mz=None, kappa=None, apply_bc=True, rhs=None):
+        """set_block_laplace for the 3-D generator (spk_set_block_laplace3d): what AssembleOperator_Laplace3D(...,
+        kappa=kappa) + set_block(BLOCK_A00, A) do for this rank's z-slab, without the host arrays.  kappa: None, one host
+        value per hexahedron ((mx-1)*(my-1)*(mz-1)), or a device vector of vec_create holding them.  rhs: a device vector
+        of vec_create (n_local values) that receives f, or True to get f back as a numpy array."""
+        my = mx if my is None else my
+        mz = mx if mz is None else mz
+        kp, mem, _keep = self._kappa3d(mx, my, mz, kappa)
+        if rhs is True:
+            n = 3 * mx * my * mz
+            fd = self.vec_create(n=n if min(mx, my, mz) >= 2 and n < 2 ** 31 else 1)
+            try:
+                self._chk(lib.spk_set_block_laplace3d(self.h, mx, my, mz, kp, mem, int(apply_bc), fd))
+                return self.vec_get(fd, self.sizes()["n_local"])
+            finally:
+                self.vec_destroy(fd)
+        self._chk(lib.spk_set_block_laplace3d(self.h, mx, my, mz, kp, mem, int(apply_bc), rhs))
+        return None
+
+    def assemble_laplace3d_csr(self, mx, my=None, mz=None, row_begin=0, row_end=None, kappa=None, apply_bc=True):
+        """Test hook: (CSR, f) of the whole node planes [row_begin,row_end) from the 3-D device assembly kernel
+        (spk_assemble_laplace3d_csr); touches nothing of the context's operator."""
+        from .csr import CSR
+        my = mx if my is None else my
+        mz = mx if mz is None else mz
+        n = 3 * mx * my * mz
+        row_end = n if row_end is None else row_end
+        nnz = lib.SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end)
+        if nnz < 0:
+            raise SpkError(-1, "row range must consist of whole node planes")
+        kp, mem, _keep = self._kappa3d(mx, my, mz, kappa)
+        nl = row_end - row_begin
+        rowptr, colidx, val, f = np.zeros(nl + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz), np.zeros(nl)
+        self._chk(lib.spk_assemble_laplace3d_csr(self.h, mx, my, mz, row_begin, row_end, kp, mem, int(apply_bc), rowptr, colidx,
+                                                 val, f.ctypes.data))
+        return CSR(rowptr, colidx, val, n, row_begin), f
+
     def assembly_seconds(self):
         """Wall seconds of the kernels of the last set_block_laplace, up to a device synchronise (0 before one)."""
         v = C.c_double()
@@ -786,6 +833,24 @@ class KSP:
         f = np.zeros(2 * mx * my if 2 <= mx and 2 <= my and 2 * mx * my < 2 ** 31 else 1) if with_rhs else None
         self._chk(lib.SpkKSPSetOperatorsLaplace(self.h, mx, my, k.ctypes.data if k is not None else None,
                                                 C.byref(b) if b is not None else None, f.ctypes.data if with_rhs else None))
+        ctx, nl = C.c_void_p(), C.c_int32()
+        lib.SpkKSPGetContext(self.h, C.byref(ctx))
+        lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
+        self._n = nl.value + (B.nrows if B is not None else 0)
+        return f[:nl.value] if with_rhs else None
+
+    def setOperatorsLaplace3D(self, mx, my=None, mz=None, kappa=None, B=None, with_rhs=True):
+        """setOperatorsLaplace for the 3-D generator (SpkKSPSetOperatorsLaplace3D); kappa: None or one host value per
+        hexahedron.  Returns f (numpy) when with_rhs."""
+        from .assembly import element_kappa3d
+        my = mx if my is None else my
+        mz = mx if mz is None else mz
+        k = element_kappa3d(mx, my, mz, kappa)
+        b = _mat(B) if B is not None else None
+        n = 3 * mx * my * mz
+        f = np.zeros(n if min(mx, my, mz) >= 2 and n < 2 ** 31 else 1) if with_rhs else None
+        self._chk(lib.SpkKSPSetOperatorsLaplace3D(self.h, mx, my, mz, k.ctypes.data if k is not None else None,
+                                                  C.byref(b) if b is not None else None, f.ctypes.data if with_rhs else None))
         ctx, nl = C.c_void_p(), C.c_int32()
         lib.SpkKSPGetContext(self.h, C.byref(ctx))
         lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
