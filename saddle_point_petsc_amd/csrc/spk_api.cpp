@@ -295,7 +295,7 @@ int spk_set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local,
 int spk_set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
 {
     SPK_TRY(c)
-    spk::set_block_laplace(c, mx, my, kappa, kappa_mem, apply_bc, f_dev);
+    spk::set_block_laplace(c, mx, my, 0, kappa, kappa_mem, apply_bc, f_dev);
     SPK_CATCH(c)
 }
 
@@ -303,14 +303,14 @@ int spk_assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int6
                              int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
 {
     SPK_TRY(c)
-    spk::assemble_laplace_csr(c, mx, my, row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
+    spk::assemble_laplace_csr(c, mx, my, 0, row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
     SPK_CATCH(c)
 }
 
 int spk_set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
 {
     SPK_TRY(c)
-    spk::set_block_laplace3d(c, mx, my, mz, kappa, kappa_mem, apply_bc, f_dev);
+    spk::set_block_laplace(c, mx, my, spk::laplace_mz3(mx, my, mz), kappa, kappa_mem, apply_bc, f_dev);
     SPK_CATCH(c)
 }
 
@@ -318,7 +318,7 @@ int spk_assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_b
                                int kappa_mem, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
 {
     SPK_TRY(c)
-    spk::assemble_laplace3d_csr(c, mx, my, mz, row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
+    spk::assemble_laplace_csr(c, mx, my, spk::laplace_mz3(mx, my, mz), row_begin, row_end, kappa, kappa_mem, apply_bc, rowptr, colidx, val, f);
     SPK_CATCH(c)
 }
 

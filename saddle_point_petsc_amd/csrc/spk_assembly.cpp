@@ -7,6 +7,9 @@
 // reference's element loop (Discretization.c:146-147) would have added them --
 // so every stored value is bit-identical to a sequential ADD_VALUES assembly
 // while no two threads ever touch the same entry.
+//
+// The element routines below are loops over the per-Gauss-point functions of spk_assembly_core.hpp, which the device kernels
+// (spk_k_assembly.hip, spk_k_assembly3d.hip) call too: one source for the arithmetic on both sides.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,182 +19,64 @@
 
 #include "../../include/spk_assembly.h"
 #include "../../include/spk.h"
+#include "spk_assembly_core.hpp"
 
+#ifdef __clang__
 #pragma clang fp contract(off)
+#endif
 
 namespace {
 
-// 2x2 Gauss points; the 11-digit abscissa is the reference's (Discretization.c:52-55)
-const double kGp[4][2] = {{-0.57735026919, -0.57735026919},
-                          {-0.57735026919, 0.57735026919},
-                          {0.57735026919, 0.57735026919},
-                          {0.57735026919, -0.57735026919}};
+using namespace spk::assembly;
 
-struct GaussPoint {
-    double N[4];      // shape functions
-    double dN[2][4];  // reference gradients
-};
-
-GaussPoint make_gp(int p)
-{
-    GaussPoint g;
-    const double xi = kGp[p][0], eta = kGp[p][1];
-    g.N[0] = 0.25 * (1.0 - xi) * (1.0 - eta);
-    g.N[1] = 0.25 * (1.0 - xi) * (1.0 + eta);
-    g.N[2] = 0.25 * (1.0 + xi) * (1.0 + eta);
-    g.N[3] = 0.25 * (1.0 + xi) * (1.0 - eta);
-    g.dN[0][0] = -0.25 * (1.0 - eta);
-    g.dN[0][1] = -0.25 * (1.0 + eta);
-    g.dN[0][2] = 0.25 * (1.0 + eta);
-    g.dN[0][3] = 0.25 * (1.0 - eta);
-    g.dN[1][0] = -0.25 * (1.0 - xi);
-    g.dN[1][1] = 0.25 * (1.0 - xi);
-    g.dN[1][2] = 0.25 * (1.0 + xi);
-    g.dN[1][3] = -0.25 * (1.0 + xi);
-    return g;
-}
-
-// physical gradients at one Gauss point; returns det J
-double phys_grad(const GaussPoint &g, const double *xe, double gx[2][4])
-{
-    double J[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    for (int c = 0; c < 2; ++c)
-        for (int d = 0; d < 2; ++d)
-            for (int i = 0; i < 4; ++i) J[c][d] += g.dN[c][i] * xe[2 * i + d];
-    const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    const double i00 = J[1][1] / det, i01 = -J[0][1] / det, i10 = -J[1][0] / det, i11 = J[0][0] / det;
-    for (int i = 0; i < 4; ++i) {
-        gx[0][i] = i00 * g.dN[0][i] + i01 * g.dN[1][i];
-        gx[1][i] = i10 * g.dN[0][i] + i11 * g.dN[1][i];
-    }
-    return det;
-}
-
-// Ke[a*8+b]; strain-displacement rows (exx, eyy, 2exy), D = diag(2,2,1)
+// Ke[a*8+b] (the reference hands Ae to MatSetValuesStencil row-major; it is acc[i + 8 j], symmetric anyway)
 void stiffness(const double *xe, const double *coeff, double *Ke)
 {
-    double acc[64];  // acc[i + 8 j], the reference's index (symmetric anyway)
+    double acc[64];
     std::memset(acc, 0, sizeof acc);
+    SPK_UNROLL
     for (int p = 0; p < 4; ++p) {
-        const GaussPoint g = make_gp(p);
-        double gx[2][4], Bm[3][8], tD[3];
-        const double det = phys_grad(g, xe, gx);
-        for (int i = 0; i < 4; ++i) {
-            Bm[0][2 * i] = gx[0][i]; Bm[0][2 * i + 1] = 0.0;
-            Bm[1][2 * i] = 0.0;      Bm[1][2 * i + 1] = gx[1][i];
-            Bm[2][2 * i] = gx[1][i]; Bm[2][2 * i + 1] = gx[0][i];
-        }
-        tD[0] = 2.0 * 1.0 * det * coeff[p];
-        tD[1] = 2.0 * 1.0 * det * coeff[p];
-        tD[2] = 1.0 * det * coeff[p];
+        double g[kG2], Bm[3 * 8], tD[3];
+        gauss2(p, xe, g);
+        for (int i = 0; i < 8; ++i) bm2(g, i, Bm + i, 8);
+        td2(g, coeff[p], tD);
         for (int i = 0; i < 8; ++i)
-            for (int j = 0; j < 8; ++j)
-                for (int k = 0; k < 3; ++k) acc[i + 8 * j] += Bm[k][i] * tD[k] * Bm[k][j];
+            for (int j = 0; j < 8; ++j) acc[i + 8 * j] = ke2_terms(acc[i + 8 * j], Bm + i, tD, Bm + j, 8);
     }
-    // the reference hands Ae to MatSetValuesStencil row-major: (row a, col b) = Ae[a*8+b]
     std::memcpy(Ke, acc, sizeof acc);
 }
 
 void load(const double *xe, double *Fe)
 {
-    std::memset(Fe, 0, 8 * sizeof(double));
-    for (int p = 0; p < 4; ++p) {
-        const GaussPoint g = make_gp(p);
-        double gx[2][4];
-        const double fac = 1.0 * phys_grad(g, xe, gx);
-        const double body[2] = {1.0, 2.0};  // FormRHS, Discretization.c:397-402
-        for (int i = 0; i < 4; ++i)
-            for (int c = 0; c < 2; ++c) Fe[2 * i + c] += fac * g.N[i] * body[c];
-    }
+    double G[4 * kG2];
+    for (int p = 0; p < 4; ++p) gauss2(p, xe, G + p * kG2);
+    for (int n = 0; n < 4; ++n)
+        for (int c = 0; c < 2; ++c) Fe[2 * n + c] = fe2_entry(G, n, c);
 }
-
-inline double coord(int i, int m) { return 0.0 + (1.0 / (double)(m - 1)) * (double)i; }
-
-void element_coords(int mx, int my, int ei, int ej, double *xe)
-{
-    xe[0] = coord(ei, mx);     xe[1] = coord(ej, my);
-    xe[2] = coord(ei, mx);     xe[3] = coord(ej + 1, my);
-    xe[4] = coord(ei + 1, mx); xe[5] = coord(ej + 1, my);
-    xe[6] = coord(ei + 1, mx); xe[7] = coord(ej, my);
-}
-
-// local node number of the corner at offset (oi, oj) from the element origin
-inline int corner(int oi, int oj) { return oi == 0 ? (oj == 0 ? 0 : 1) : (oj == 0 ? 3 : 2); }
-
-inline bool on_boundary(int mx, int my, int i, int j) { return i == 0 || i == mx - 1 || j == 0 || j == my - 1; }
 
 // stored non-zeros of the two rows of node (i,j)
-inline int node_row_nnz(int mx, int my, int i, int j)
-{
-    const int wi = (i > 0) + 1 + (i < mx - 1), wj = (j > 0) + 1 + (j < my - 1);
-    return wi * wj * 2;
-}
+inline int node_row_nnz(int mx, int my, int i, int j) { return width(i, mx) * width(j, my) * 2; }
 
 // ---- 3-D (build-defined; see include/spk_assembly.h) ----
-const int kSgn3[8][3] = {{-1, -1, -1}, {-1, 1, -1}, {1, 1, -1}, {1, -1, -1}, {-1, -1, 1}, {-1, 1, 1}, {1, 1, 1}, {1, -1, 1}};
-
-// Ke[a*24+b] and Fe[24] of one hexahedron (same operation order as the oracle's restatement); kp: the element's
-// coefficient, 1.0 for the plain operator
+// Ke[a*24+b] and Fe[24] of one hexahedron; kp: the element's coefficient, 1.0 for the plain operator
 void element3d(const double *xe, double kp, double *Ke, double *Fe)
 {
-    double acc[576];
-    std::memset(acc, 0, sizeof acc);
-    std::memset(Fe, 0, 24 * sizeof(double));
-    const double gp1 = 0.57735026919;
+    double G[8 * kG3];
+    std::memset(Ke, 0, 576 * sizeof(double));
     for (int p = 0; p < 8; ++p) {
-        const double xi[3] = {kSgn3[p][0] * gp1, kSgn3[p][1] * gp1, kSgn3[p][2] * gp1};
-        double N[8], G[3][8], Gx[3][8], Bm[6][24], tD[6], J[3][3], iJ[3][3];
-        for (int a = 0; a < 8; ++a) {
-            const double sx = kSgn3[a][0], sy = kSgn3[a][1], sz = kSgn3[a][2];
-            N[a] = 0.125 * (1.0 + sx * xi[0]) * (1.0 + sy * xi[1]) * (1.0 + sz * xi[2]);
-            G[0][a] = 0.125 * sx * (1.0 + sy * xi[1]) * (1.0 + sz * xi[2]);
-            G[1][a] = 0.125 * sy * (1.0 + sx * xi[0]) * (1.0 + sz * xi[2]);
-            G[2][a] = 0.125 * sz * (1.0 + sx * xi[0]) * (1.0 + sy * xi[1]);
-        }
-        for (int c = 0; c < 3; ++c)
-            for (int d = 0; d < 3; ++d) {
-                J[c][d] = 0.0;
-                for (int a = 0; a < 8; ++a) J[c][d] += G[c][a] * xe[a * 3 + d];
-            }
-        const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                           J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-        iJ[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) / det;
-        iJ[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-        iJ[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
-        iJ[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-        iJ[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
-        iJ[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-        iJ[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) / det;
-        iJ[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-        iJ[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
-        for (int a = 0; a < 8; ++a)
-            for (int c = 0; c < 3; ++c) Gx[c][a] = iJ[c][0] * G[0][a] + iJ[c][1] * G[1][a] + iJ[c][2] * G[2][a];
-        std::memset(Bm, 0, sizeof Bm);
-        for (int a = 0; a < 8; ++a) {
-            Bm[0][3 * a] = Gx[0][a];
-            Bm[1][3 * a + 1] = Gx[1][a];
-            Bm[2][3 * a + 2] = Gx[2][a];
-            Bm[3][3 * a] = Gx[1][a];     Bm[3][3 * a + 1] = Gx[0][a];
-            Bm[4][3 * a + 1] = Gx[2][a]; Bm[4][3 * a + 2] = Gx[1][a];
-            Bm[5][3 * a] = Gx[2][a];     Bm[5][3 * a + 2] = Gx[0][a];
-        }
-        for (int k = 0; k < 6; ++k) tD[k] = (k < 3 ? 2.0 : 1.0) * 1.0 * det * kp;
-        for (int i = 0; i < 24; ++i)
-            for (int j = 0; j < 24; ++j)
-                for (int k = 0; k < 6; ++k) acc[i + 24 * j] += Bm[k][i] * tD[k] * Bm[k][j];
-        const double fac = 1.0 * det, body[3] = {1.0, 2.0, 3.0};
-        for (int a = 0; a < 8; ++a)
-            for (int c = 0; c < 3; ++c) Fe[3 * a + c] += fac * N[a] * body[c];
+        double *g = G + p * kG3;
+        gauss3(p, xe, kp, g);
+        for (int na = 0; na < 8; ++na)
+            for (int nb = 0; nb < 8; ++nb)
+                for (int c = 0; c < 3; ++c)
+                    for (int d = 0; d < 3; ++d) {
+                        double &e = Ke[(3 * na + c) * 24 + 3 * nb + d];
+                        e = ke3_point(e, g, nb, d, na, c);
+                    }
     }
-    std::memcpy(Ke, acc, sizeof acc);
+    for (int a = 0; a < 8; ++a)
+        for (int c = 0; c < 3; ++c) Fe[3 * a + c] = fe3_entry(G, a, c);
 }
-
-inline int corner3(int oi, int oj, int ok) { return corner(oi, oj) + 4 * ok; }
-inline bool on_boundary3(int mx, int my, int mz, int i, int j, int k)
-{
-    return i == 0 || i == mx - 1 || j == 0 || j == my - 1 || k == 0 || k == mz - 1;
-}
-inline int width(int i, int m) { return (i > 0) + 1 + (i < m - 1); }
 
 int threads_or_default(int n)
 {
@@ -218,8 +103,7 @@ int64_t SpkAssemblySlabNnz(int mx, int my, int64_t row_begin, int64_t row_end)
     if (mx < 2 || my < 2 || row_begin % line || row_end % line || row_begin > row_end || row_end > line * my) return -1;
     int64_t nnz = 0;
     for (int64_t j = row_begin / line; j < row_end / line; ++j) {
-        const int64_t wj = (j > 0) + 1 + (j < my - 1);
-        nnz += 4 * wj * (3 * (int64_t)mx - 2);
+        nnz += (int64_t)4 * width((int)j, my) * (3 * (int64_t)mx - 2);
     }
     return nnz;
 }
@@ -275,7 +159,7 @@ int SpkAssembleOperator_LaplaceKappa(int mx, int my, int64_t row_begin, int64_t 
             if (ej < 0 || ej > my - 2) return;
             for (int ei = 0; ei < ne; ++ei) {
                 double xe[8];
-                element_coords(mx, my, ei, ej, xe);
+                quad_coords(mx, my, ei, ej, xe);
                 const double kp = kappa ? kappa[(size_t)ej * ne + ei] : 1.0;   // one value per element, at its four Gauss points
                 const double coeff[4] = {kp, kp, kp, kp};
                 stiffness(xe, coeff, &Ke[(size_t)ei * 64]);
@@ -475,11 +359,7 @@ int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin
             }
             for (int ei = 0; ei < ne; ++ei) {
                 double xe[24];
-                for (int a = 0; a < 8; ++a) {
-                    xe[3 * a] = coord(ei + (kSgn3[a][0] > 0), mx);
-                    xe[3 * a + 1] = coord(ej + (kSgn3[a][1] > 0), my);
-                    xe[3 * a + 2] = coord(ek + (kSgn3[a][2] > 0), mz);
-                }
+                hex_coords(mx, my, mz, ei, ej, ek, xe);
                 const double kp = kappa ? kappa[((size_t)ek * (my - 1) + ej) * ne + ei] : 1.0;
                 element3d(xe, kp, &Ke[dj][dk][(size_t)ei * 576], &Fe[dj][dk][(size_t)ei * 24]);
             }
@@ -493,7 +373,7 @@ int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin
                 ensure(1, dk, j, k - 1 + dk);
             }
             for (int i = 0; i < mx; ++i) {
-                const bool rb = on_boundary3(mx, my, mz, i, j, k);
+                const bool rb = on_boundary(mx, my, mz, i, j, k);
                 for (int c = 0; c < 3; ++c) {
                     const int64_t grow = (((int64_t)k * my + j) * mx + i) * 3 + c;
                     const int64_t lrow = grow - row_begin;
@@ -507,7 +387,7 @@ int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin
                             for (int di = -1; di <= 1; ++di) {
                                 const int ci = i + di;
                                 if (ci < 0 || ci >= mx) continue;
-                                const bool cb = on_boundary3(mx, my, mz, ci, cj, ck);
+                                const bool cb = on_boundary(mx, my, mz, ci, cj, ck);
                                 for (int d = 0; d < 3; ++d) {
                                     const int64_t gcol = (((int64_t)ck * my + cj) * mx + ci) * 3 + d;
                                     double v = 0.0;
@@ -518,8 +398,8 @@ int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin
                                             const std::vector<double> &K = Ke[ej - (j - 1)][ek - (k - 1)];
                                             for (int ei = std::max(i, ci) - 1; ei <= std::min(i, ci); ++ei) {
                                                 if (ei < 0 || ei > mx - 2) continue;
-                                                const int a = corner3(i - ei, j - ej, k - ek) * 3 + c;
-                                                const int b = corner3(ci - ei, cj - ej, ck - ek) * 3 + d;
+                                                const int a = corner(i - ei, j - ej, k - ek) * 3 + c;
+                                                const int b = corner(ci - ei, cj - ej, ck - ek) * 3 + d;
                                                 v += K[(size_t)ei * 576 + a * 24 + b];
                                             }
                                         }
@@ -540,7 +420,7 @@ int SpkAssembleOperator_Laplace3DKappa(int mx, int my, int mz, int64_t row_begin
                                 const std::vector<double> &F = Fe[ej - (j - 1)][ek - (k - 1)];
                                 for (int ei = i - 1; ei <= i; ++ei) {
                                     if (ei < 0 || ei > mx - 2) continue;
-                                    fv += F[(size_t)ei * 24 + corner3(i - ei, j - ej, k - ek) * 3 + c];
+                                    fv += F[(size_t)ei * 24 + corner(i - ei, j - ej, k - ek) * 3 + c];
                                 }
                             }
                         }

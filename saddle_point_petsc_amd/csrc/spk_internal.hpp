@@ -488,10 +488,12 @@ void bcsr_fill(const int32_t *rp, const int32_t *ci, const double *va, int nbr, 
                double *vbot, int32_t *fail, hipStream_t s);
 // spk_k_assembly.hip: the CSR slab and f (may be null) of node lines [j0, j1) of the mx x my grid, bit for bit the host
 // assembler's; kappa: one value per element of the whole grid on the device, or null for ones.  rowptr: 2 mx (j1 - j0) + 1.
+// _grid: the workgroups it launches.
 void assemble_laplace(int mx, int my, int j0, int j1, const double *kappa, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val,
                       double *f, hipStream_t s);
+int64_t assemble_laplace_grid(int mx, int j0, int j1);
 // spk_k_assembly3d.hip: the same for the node planes [k0, k1) of the mx x my x mz grid of the 3-D generator (dof 3); kappa: one
-// value per hexahedron of the whole grid.  rowptr: 3 mx my (k1 - k0) + 1.  _grid: the workgroups it launches.
+// value per hexahedron of the whole grid.  rowptr: 3 mx my (k1 - k0) + 1.
 void assemble_laplace3d(int mx, int my, int mz, int k0, int k1, const double *kappa, int apply_bc, int32_t *rowptr, int32_t *colidx,
                         double *val, double *f, hipStream_t s);
 int64_t assemble_laplace3d_grid(int mx, int my, int k0, int k1);
@@ -1040,14 +1042,13 @@ void finish_solve(spk_ctx *c, const KrylovState &st, int32_t cycles, std::chrono
                   const double *hist, int32_t hist_cap, spk_result *res, double *history, int32_t history_cap);
 void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, int64_t ncols_global,
                const int32_t *rowptr, const int32_t *colidx, const double *val);
-// A00 of the reference's own discretisation assembled on the device (spk_k_assembly.hip), then set_block's chain
-void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
-void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+// A00 of the reference's own discretisation assembled on the device, then set_block's chain.  mz == 0: the 2-D grid
+// (spk_k_assembly.hip, whole node lines), else the 3-D generator's (spk_k_assembly3d.hip, whole node planes);
+// laplace_mz3: the mz of a 3-D entry point, where 0 is no grid.  assemble_laplace_csr: the slab back on the host (a test hook).
+void set_block_laplace(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
+void assemble_laplace_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
                           int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
-// the same for the 3-D generator (spk_k_assembly3d.hip): whole node planes
-void set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev);
-void assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
-                            int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
+int laplace_mz3(int mx, int my, int mz);
 
 // The host side of the frame MINRES and pipelined CG share (spk_minres.cpp, spk_pipecg.cpp).  The host only ENQUEUES
 // iterations, each gated by the state's `done` word; the scalar steps run on the device.  The state is copied into a

@@ -299,18 +299,41 @@ static void a_bring_upload(spk_ctx *c, int32_t n, const int32_t *rowptr, const i
     up(c, in.val, val, (size_t)nnz, 16);
 }
 
+// The node grid of the device assembly.  mz == 0: the reference's 2-D grid (dof 2, the ranks share out node lines,
+// spk_k_assembly.hip), else the 3-D generator's (dof 3, node planes, spk_k_assembly3d.hip).  Everything in which the two
+// routes differ is answered here; the chain over it is one.
+struct LaplaceGrid {
+    int mx, my, mz;
+    bool sides_ok() const { return mx >= 2 && my >= 2 && (mz == 0 || mz >= 2); }
+    int64_t rows() const { return (mz ? 3 * (int64_t)mz : 2) * mx * my; }
+    int64_t unit_rows() const { return mz ? 3 * (int64_t)mx * my : 2 * (int64_t)mx; }   // rows of a node line / plane
+    int units() const { return mz ? mz : my; }                                          // the lines / planes to share out
+    const char *unit_name() const { return mz ? "planes" : "lines"; }
+    int64_t slab_nnz(int64_t rb, int64_t re) const { return mz ? SpkAssemblySlabNnz3D(mx, my, mz, rb, re) : SpkAssemblySlabNnz(mx, my, rb, re); }
+    int row_pointers(int64_t rb, int64_t re, int32_t *rowptr) const
+    {
+        return mz ? SpkAssemblyRowPointers3D(mx, my, mz, rb, re, rowptr) : SpkAssemblyRowPointers(mx, my, rb, re, rowptr);
+    }
+    int64_t launch_grid(int u0, int u1) const { return mz ? k::assemble_laplace3d_grid(mx, my, u0, u1) : k::assemble_laplace_grid(mx, u0, u1); }
+    void launch(int u0, int u1, const double *kappa_d, int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f, hipStream_t s) const
+    {
+        if (mz) k::assemble_laplace3d(mx, my, mz, u0, u1, kappa_d, apply_bc, rowptr, colidx, val, f, s);
+        else k::assemble_laplace(mx, my, u0, u1, kappa_d, apply_bc, rowptr, colidx, val, f, s);
+    }
+};
+
 // ... the other: the assembly kernel writes it where the chain reads it (kappa_d: on the device, or null)
-static void a_bring_laplace(spk_ctx *c, int mx, int my, int64_t row_begin, int32_t n, int64_t nnz, const double *kappa_d, int apply_bc,
+static void a_bring_laplace(spk_ctx *c, const LaplaceGrid &g, int64_t row_begin, int32_t n, int64_t nnz, const double *kappa_d, int apply_bc,
                             double *f_dev, SlabIn &in)
 {
     hipStream_t s = c->stream;
     in.rowptr.alloc_raw((size_t)n + 1, 8);
     in.colidx.alloc_raw((size_t)nnz, 16);
     in.val.alloc_raw((size_t)nnz, 16);
-    const int j0 = (int)(row_begin / (2 * (int64_t)mx));
+    const int u0 = (int)(row_begin / g.unit_rows());
     SPK_HIP(hipStreamSynchronize(s));
     const auto t0 = std::chrono::steady_clock::now();
-    k::assemble_laplace(mx, my, j0, j0 + n / (2 * mx), kappa_d, apply_bc, in.rowptr.p, in.colidx.p, in.val.p, f_dev, s);
+    g.launch(u0, u0 + (int)(n / g.unit_rows()), kappa_d, apply_bc, in.rowptr.p, in.colidx.p, in.val.p, f_dev, s);
     SPK_HIP(hipStreamSynchronize(s));
     c->assembly_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -664,123 +687,65 @@ static const double *kappa_on_device(spk_ctx *c, int mx, int my, int mz, const d
     return kappa;
 }
 
-// the refusals that need no GPU; returns the slab's stored non-zeros
-static int64_t laplace_slab_limits(int mx, int my, int64_t row_begin, int64_t row_end)
+// the refusals that need no GPU; returns the slab's stored non-zeros.  (The launch grid of a 2-D slab is at most half its
+// node count, so that limit can only stop a 3-D grid.)
+static int64_t laplace_slab_limits(const LaplaceGrid &g, int64_t row_begin, int64_t row_end)
 {
-    if (mx < 2 || my < 2) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d nodes (at least 2 x 2)", mx, my);
-    if ((int64_t)2 * mx * my > INT32_MAX)
-        fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld rows exceed 32-bit indices", (long long)2 * mx * my);
-    const int64_t nnz = SpkAssemblySlabNnz(mx, my, row_begin, row_end);
-    if (nnz < 0) fail(SPK_ERR_ARG, "device assembly: rows [%lld,%lld) are not whole node lines of the grid", (long long)row_begin, (long long)row_end);
+    if (!g.sides_ok()) {
+        if (g.mz) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d x %d nodes (at least 2 x 2 x 2)", g.mx, g.my, g.mz);
+        fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d nodes (at least 2 x 2)", g.mx, g.my);
+    }
+    if (g.rows() > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld rows exceed 32-bit indices", (long long)g.rows());
+    const int64_t nnz = g.slab_nnz(row_begin, row_end);
+    if (nnz < 0)
+        fail(SPK_ERR_ARG, "device assembly: rows [%lld,%lld) are not whole node %s of the grid", (long long)row_begin, (long long)row_end, g.unit_name());
     if (nnz > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld stored non-zeros of the slab exceed 32-bit indices", (long long)nnz);
-    return nnz;
-}
-
-void set_block_laplace(spk_ctx *c, int mx, int my, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
-{
-    c->ensure_scratch();
-    int64_t rb = 0, re = 0, nnz = 0;
-    // sizes first, and only where they make sense (the chain's own refusal path reports the rest)
-    const bool sane = mx >= 2 && my >= 2 && (int64_t)2 * mx * my <= INT32_MAX;
-    if (sane && spk_partition_slab(my, 2 * (int64_t)mx, c->comm->rank(), c->comm->size(), &rb, &re) != SPK_OK)
-        fail(SPK_ERR_ARG, "device assembly: spk_partition_slab failed");
-    const int32_t n = (int32_t)(re - rb);
-    HostBuf<int32_t> rowptr;
-    DevBuf<double> kappa_own;
-    const double *kappa_d = nullptr;
-    set_block_A(c, rb, n, (int64_t)2 * mx * my, [&] {
-        nnz = laplace_slab_limits(mx, my, rb, re);
-        kappa_d = kappa_on_device(c, mx, my, 0, kappa, kappa_mem, kappa_own);
-        rowptr.alloc((size_t)n + 1);
-        if (SpkAssemblyRowPointers(mx, my, rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
-        return (const int32_t *)rowptr.data();
-    }, [&](SlabIn &in) { a_bring_laplace(c, mx, my, rb, n, nnz, kappa_d, apply_bc, f_dev, in); });
-}
-
-void assemble_laplace_csr(spk_ctx *c, int mx, int my, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
-                          int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
-{
-    if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace_csr: null array");
-    const int64_t nnz = laplace_slab_limits(mx, my, row_begin, row_end);
-    DevBuf<double> kappa_own, fd;
-    const double *kappa_d = kappa_on_device(c, mx, my, 0, kappa, kappa_mem, kappa_own);
-    const int32_t n = (int32_t)(row_end - row_begin);
-    SlabIn in;
-    if (f) fd.alloc_raw((size_t)n, 8);
-    const double keep = c->assembly_seconds;
-    a_bring_laplace(c, mx, my, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
-    c->assembly_seconds = keep;   // (a test hook: the context's last assembly is the operator's)
-    SPK_HIP(hipMemcpy(rowptr, in.rowptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
-    SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
-    SPK_HIP(hipMemcpy(val, in.val.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
-    if (f) SPK_HIP(hipMemcpy(f, fd.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-}
-
-// ---- the 3-D generator (spk_k_assembly3d.hip): the same chain, whole node planes
-static void a_bring_laplace3d(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int32_t n, int64_t nnz, const double *kappa_d,
-                              int apply_bc, double *f_dev, SlabIn &in)
-{
-    hipStream_t s = c->stream;
-    in.rowptr.alloc_raw((size_t)n + 1, 8);
-    in.colidx.alloc_raw((size_t)nnz, 16);
-    in.val.alloc_raw((size_t)nnz, 16);
-    const int64_t plane = 3 * (int64_t)mx * my;
-    const int k0 = (int)(row_begin / plane);
-    SPK_HIP(hipStreamSynchronize(s));
-    const auto t0 = std::chrono::steady_clock::now();
-    k::assemble_laplace3d(mx, my, mz, k0, k0 + (int)(n / plane), kappa_d, apply_bc, in.rowptr.p, in.colidx.p, in.val.p, f_dev, s);
-    SPK_HIP(hipStreamSynchronize(s));
-    c->assembly_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// the refusals that need no GPU; returns the slab's stored non-zeros
-static int64_t laplace3d_slab_limits(int mx, int my, int mz, int64_t row_begin, int64_t row_end)
-{
-    if (mx < 2 || my < 2 || mz < 2) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d x %d nodes (at least 2 x 2 x 2)", mx, my, mz);
-    const int64_t rows = (int64_t)3 * mx * my * mz;
-    if (rows > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld rows exceed 32-bit indices", (long long)rows);
-    const int64_t nnz = SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end);
-    if (nnz < 0) fail(SPK_ERR_ARG, "device assembly: rows [%lld,%lld) are not whole node planes of the grid", (long long)row_begin, (long long)row_end);
-    if (nnz > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld stored non-zeros of the slab exceed 32-bit indices", (long long)nnz);
-    const int64_t plane = 3 * (int64_t)mx * my;
-    const int64_t grid = k::assemble_laplace3d_grid(mx, my, (int)(row_begin / plane), (int)(row_end / plane));
+    const int64_t grid = g.launch_grid((int)(row_begin / g.unit_rows()), (int)(row_end / g.unit_rows()));
     if (grid > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device assembly: %lld workgroups exceed the launch grid", (long long)grid);
     return nnz;
 }
 
-void set_block_laplace3d(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+int laplace_mz3(int mx, int my, int mz)
 {
+    if (mz == 0) fail(SPK_ERR_ARG, "device assembly: a grid of %d x %d x %d nodes (at least 2 x 2 x 2)", mx, my, mz);
+    return mz;
+}
+
+void set_block_laplace(spk_ctx *c, int mx, int my, int mz, const double *kappa, int kappa_mem, int apply_bc, double *f_dev)
+{
+    const LaplaceGrid g{mx, my, mz};
     c->ensure_scratch();
     int64_t rb = 0, re = 0, nnz = 0;
     // sizes first, and only where they make sense (the chain's own refusal path reports the rest)
-    const bool sane = mx >= 2 && my >= 2 && mz >= 2 && (int64_t)3 * mx * my * mz <= INT32_MAX;
-    if (sane && spk_partition_slab(mz, 3 * (int64_t)mx * my, c->comm->rank(), c->comm->size(), &rb, &re) != SPK_OK)
+    const bool sane = g.sides_ok() && g.rows() <= INT32_MAX;
+    if (sane && spk_partition_slab(g.units(), g.unit_rows(), c->comm->rank(), c->comm->size(), &rb, &re) != SPK_OK)
         fail(SPK_ERR_ARG, "device assembly: spk_partition_slab failed");
     const int32_t n = (int32_t)(re - rb);
     HostBuf<int32_t> rowptr;
     DevBuf<double> kappa_own;
     const double *kappa_d = nullptr;
-    set_block_A(c, rb, n, (int64_t)3 * mx * my * mz, [&] {
-        nnz = laplace3d_slab_limits(mx, my, mz, rb, re);
+    set_block_A(c, rb, n, g.rows(), [&] {
+        nnz = laplace_slab_limits(g, rb, re);
         kappa_d = kappa_on_device(c, mx, my, mz, kappa, kappa_mem, kappa_own);
         rowptr.alloc((size_t)n + 1);
-        if (SpkAssemblyRowPointers3D(mx, my, mz, rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
+        if (g.row_pointers(rb, re, rowptr.data()) != SPK_OK) fail(SPK_ERR_UNSUPPORTED, "device assembly: row pointers beyond 32-bit indices");
         return (const int32_t *)rowptr.data();
-    }, [&](SlabIn &in) { a_bring_laplace3d(c, mx, my, mz, rb, n, nnz, kappa_d, apply_bc, f_dev, in); });
+    }, [&](SlabIn &in) { a_bring_laplace(c, g, rb, n, nnz, kappa_d, apply_bc, f_dev, in); });
 }
 
-void assemble_laplace3d_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
-                            int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
+void assemble_laplace_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
+                          int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f)
 {
-    if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace3d_csr: null array");
-    const int64_t nnz = laplace3d_slab_limits(mx, my, mz, row_begin, row_end);
+    const LaplaceGrid g{mx, my, mz};
+    if (!rowptr || !colidx || !val) fail(SPK_ERR_ARG, "assemble_laplace%s_csr: null array", mz ? "3d" : "");
+    const int64_t nnz = laplace_slab_limits(g, row_begin, row_end);
     DevBuf<double> kappa_own, fd;
     const double *kappa_d = kappa_on_device(c, mx, my, mz, kappa, kappa_mem, kappa_own);
     const int32_t n = (int32_t)(row_end - row_begin);
     SlabIn in;
     if (f) fd.alloc_raw((size_t)n, 8);
     const double keep = c->assembly_seconds;
-    a_bring_laplace3d(c, mx, my, mz, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
+    a_bring_laplace(c, g, row_begin, n, nnz, kappa_d, apply_bc, f ? fd.p : nullptr, in);
     c->assembly_seconds = keep;   // (a test hook: the context's last assembly is the operator's)
     SPK_HIP(hipMemcpy(rowptr, in.rowptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
     SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));

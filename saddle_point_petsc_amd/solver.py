@@ -2,6 +2,7 @@
 (include/spk_ksp.h).  `KSP` mirrors the reference's call site
 /root/reference/src/SaddlePointProblem.c:65-72 (petsc4py-style method names)."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -429,15 +430,44 @@ class Context:
                                     A.ncols, A.rowptr, A.colidx, A.val))
 
     @staticmethod
-    def _kappa(mx, my, kappa):
-        """(pointer, mem, keep-alive) of a coefficient: None, a device vector of vec_create, or a host array."""
-        from .assembly import element_kappa
+    def _kappa(kappa, *grid):
+        """(pointer, mem, keep-alive) of a coefficient on the 2-D or 3-D grid: None, a device vector of vec_create, or a
+        host array."""
+        from .assembly import element_kappa, element_kappa3d
         if kappa is None:
             return None, MEM_HOST, None
         if isinstance(kappa, C.c_void_p):
             return kappa, MEM_DEVICE, kappa
-        k = element_kappa(mx, my, kappa)
+        k = (element_kappa if len(grid) == 2 else element_kappa3d)(*grid, kappa)
         return k.ctypes.data, MEM_HOST, k
+
+    def _set_block_laplace(self, fn, grid, dof, kappa, apply_bc, rhs):
+        """set_block_laplace / set_block_laplace3d: fn is the library's entry point for the grid (2 or 3 sides)"""
+        kp, mem, _keep = self._kappa(kappa, *grid)
+        if rhs is not True:
+            self._chk(fn(self.h, *grid, kp, mem, int(apply_bc), rhs))
+            return None
+        n = dof * math.prod(grid)
+        fd = self.vec_create(n=n if min(grid) >= 2 and n < 2 ** 31 else 1)
+        try:
+            self._chk(fn(self.h, *grid, kp, mem, int(apply_bc), fd))
+            return self.vec_get(fd, self.sizes()["n_local"])
+        finally:
+            self.vec_destroy(fd)
+
+    def _assemble_laplace_csr(self, fn, slab_nnz, grid, dof, units, row_begin, row_end, kappa, apply_bc):
+        """assemble_laplace_csr / assemble_laplace3d_csr: fn and slab_nnz are the library's entry points for the grid"""
+        from .csr import CSR
+        n = dof * math.prod(grid)
+        row_end = n if row_end is None else row_end
+        nnz = slab_nnz(*grid, row_begin, row_end)
+        if nnz < 0:
+            raise SpkError(-1, f"row range must consist of whole node {units}")
+        kp, mem, _keep = self._kappa(kappa, *grid)
+        nl = row_end - row_begin
+        rowptr, colidx, val, f = np.zeros(nl + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz), np.zeros(nl)
+        self._chk(fn(self.h, *grid, row_begin, row_end, kp, mem, int(apply_bc), rowptr, colidx, val, f.ctypes.data))
+        return CSR(rowptr, colidx, val, n, row_begin), f
 
     def set_block_laplace(self, mx, my=None, kappa=None, apply_bc=True, rhs=None):
         """KSPSetOperators for A00 of the reference's own discretisation, assembled on the device (spk_set_block_laplace):
@@ -445,44 +475,14 @@ class Context:
         arrays.  kappa: None, one host value per element ((mx-1)*(my-1)), or a device vector of vec_create holding them.
         rhs: a device vector of vec_create (n_local values) that receives f, or True to get f back as a numpy array."""
         my = mx if my is None else my
-        kp, mem, _keep = self._kappa(mx, my, kappa)
-        if rhs is True:
-            fd = self.vec_create(n=2 * mx * my if 2 <= mx and 2 <= my and 2 * mx * my < 2 ** 31 else 1)
-            try:
-                self._chk(lib.spk_set_block_laplace(self.h, mx, my, kp, mem, int(apply_bc), fd))
-                return self.vec_get(fd, self.sizes()["n_local"])
-            finally:
-                self.vec_destroy(fd)
-        self._chk(lib.spk_set_block_laplace(self.h, mx, my, kp, mem, int(apply_bc), rhs))
-        return None
+        return self._set_block_laplace(lib.spk_set_block_laplace, (mx, my), 2, kappa, apply_bc, rhs)
 
     def assemble_laplace_csr(self, mx, my=None, row_begin=0, row_end=None, kappa=None, apply_bc=True):
         """Test hook: (CSR, f) of rows [row_begin,row_end) from the device assembly kernels (spk_assemble_laplace_csr);
         touches nothing of the context's operator."""
-        from .assembly import grid_sizes
-        from .csr import CSR
         my = mx if my is None else my
-        n, _ = grid_sizes(mx, my)
-        row_end = n if row_end is None else row_end
-        nnz = lib.SpkAssemblySlabNnz(mx, my, row_begin, row_end)
-        if nnz < 0:
-            raise SpkError(-1, "row range must consist of whole node lines")
-        kp, mem, _keep = self._kappa(mx, my, kappa)
-        nl = row_end - row_begin
-        rowptr, colidx, val, f = np.zeros(nl + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz), np.zeros(nl)
-        self._chk(lib.spk_assemble_laplace_csr(self.h, mx, my, row_begin, row_end, kp, mem, int(apply_bc), rowptr, colidx, val,
-                                               f.ctypes.data))
-        return CSR(rowptr, colidx, val, n, row_begin), f
-
-    @staticmethod
-    def _kappa3d(mx, my, mz, kappa):
-        from .assembly import element_kappa3d
-        if kappa is None:
-            return None, MEM_HOST, None
-        if isinstance(kappa, C.c_void_p):
-            return kappa, MEM_DEVICE, kappa
-        k = element_kappa3d(mx, my, mz, kappa)
-        return k.ctypes.data, MEM_HOST, k
+        return self._assemble_laplace_csr(lib.spk_assemble_laplace_csr, lib.SpkAssemblySlabNnz, (mx, my), 2, "lines", row_begin, row_end,
+                                          kappa, apply_bc)
 
     def set_block_laplace3d(self, mx, my=None, mz=None, kappa=None, apply_bc=True, rhs=None):
         """set_block_laplace for the 3-D generator (spk_set_block_laplace3d): what AssembleOperator_Laplace3D(...,
@@ -491,35 +491,15 @@ class Context:
         of vec_create (n_local values) that receives f, or True to get f back as a numpy array."""
         my = mx if my is None else my
         mz = mx if mz is None else mz
-        kp, mem, _keep = self._kappa3d(mx, my, mz, kappa)
-        if rhs is True:
-            n = 3 * mx * my * mz
-            fd = self.vec_create(n=n if min(mx, my, mz) >= 2 and n < 2 ** 31 else 1)
-            try:
-                self._chk(lib.spk_set_block_laplace3d(self.h, mx, my, mz, kp, mem, int(apply_bc), fd))
-                return self.vec_get(fd, self.sizes()["n_local"])
-            finally:
-                self.vec_destroy(fd)
-        self._chk(lib.spk_set_block_laplace3d(self.h, mx, my, mz, kp, mem, int(apply_bc), rhs))
-        return None
+        return self._set_block_laplace(lib.spk_set_block_laplace3d, (mx, my, mz), 3, kappa, apply_bc, rhs)
 
     def assemble_laplace3d_csr(self, mx, my=None, mz=None, row_begin=0, row_end=None, kappa=None, apply_bc=True):
         """Test hook: (CSR, f) of the whole node planes [row_begin,row_end) from the 3-D device assembly kernel
         (spk_assemble_laplace3d_csr); touches nothing of the context's operator."""
-        from .csr import CSR
         my = mx if my is None else my
         mz = mx if mz is None else mz
-        n = 3 * mx * my * mz
-        row_end = n if row_end is None else row_end
-        nnz = lib.SpkAssemblySlabNnz3D(mx, my, mz, row_begin, row_end)
-        if nnz < 0:
-            raise SpkError(-1, "row range must consist of whole node planes")
-        kp, mem, _keep = self._kappa3d(mx, my, mz, kappa)
-        nl = row_end - row_begin
-        rowptr, colidx, val, f = np.zeros(nl + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz), np.zeros(nl)
-        self._chk(lib.spk_assemble_laplace3d_csr(self.h, mx, my, mz, row_begin, row_end, kp, mem, int(apply_bc), rowptr, colidx,
-                                                 val, f.ctypes.data))
-        return CSR(rowptr, colidx, val, n, row_begin), f
+        return self._assemble_laplace_csr(lib.spk_assemble_laplace3d_csr, lib.SpkAssemblySlabNnz3D, (mx, my, mz), 3, "planes", row_begin,
+                                          row_end, kappa, apply_bc)
 
     def assembly_seconds(self):
         """Wall seconds of the kernels of the last set_block_laplace, up to a device synchronise (0 before one)."""
