@@ -306,6 +306,16 @@ int spk_pc_set_inner(spk_ctx *ctx, int sweeps, double omega);
  * spk_minres with it (spk_pipecg takes it on K = A), and FP32 inner sweeps beside it (spk_pc_set_inner > 0 and spk_pc_set_amg are exclusive). */
 enum { SPK_AMG_CHEBYSHEV = 0, SPK_AMG_RICHARDSON = 1 };
 enum { SPK_AMG_SETUP_HOST = 0, SPK_AMG_SETUP_DEVICE = 1 };
+/* How a level is coarsened.  AGGREGATION: the smoothed aggregation above (PETSc: -pc_type gamg).  GRID (PETSc: -pc_type mg
+ * -pc_mg_galerkin on a DMDA): the unknowns sit on an mx x my (x mz) node grid, bs per node, in natural ordering
+ * row = ((k my + j) mx + i) bs + c; a direction of m nodes halves to (m + 1) / 2 while m is odd and >= 5 (the others
+ * keep m: semi-coarsening), P_l = P_z (x) P_y (x) P_x (x) I_bs with linear interpolation (even fine index i -> coarse i / 2,
+ * weight 1; odd i -> (i - 1) / 2 and (i + 1) / 2, weight 1/2 each), boundary nodes included; the coarse operators are the
+ * same Galerkin products.  threshold and nsmooths are not read, there are no aggregates, SPK_AMG_TENTATIVE returns P.
+ * A level built by the grid rule applies P and R in the V-cycle without reading them (SPK_AMG_TRANSFER_MATRIX_FREE:
+ * every weight is a power of two, the sums run in ascending column order) or as stored CSR like gamg's (STORED). */
+enum { SPK_AMG_COARSEN_AGGREGATION = 0, SPK_AMG_COARSEN_GRID = 1 };
+enum { SPK_AMG_TRANSFER_MATRIX_FREE = 0, SPK_AMG_TRANSFER_STORED = 1 };
 #define SPK_AMG_MAX_LEVELS 16
 #define SPK_AMG_MAX_COARSE 1024
 typedef struct spk_amg_opts {
@@ -321,6 +331,9 @@ typedef struct spk_amg_opts {
     double richardson_scale;  /* -mg_levels_ksp_richardson_scale    (1.0) */
     int32_t setup;            /* -spk_gamg_setup host|device: SPK_AMG_SETUP_* (host); spk_amg_build_host takes either
                                  and builds on the host */
+    int32_t coarsening;       /* SPK_AMG_COARSEN_*                  (aggregation; -pc_type mg selects grid) */
+    int32_t grid[3];          /* grid coarsening: nodes per side mx, my, mz (mz = 1 in 2-D); rows = bs mx my mz */
+    int32_t transfer;         /* -spk_mg_transfer matrixfree|stored: SPK_AMG_TRANSFER_* (grid coarsening only) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -332,6 +345,8 @@ typedef struct spk_amg_info {
     double operator_complexity;              /* sum of nnz(A_l) / nnz(A_0) */
     double setup_seconds;                    /* host build + upload; device build: its wall time up to a device synchronise */
     int32_t setup;                           /* where this hierarchy was built: SPK_AMG_SETUP_* */
+    int32_t coarsening;                      /* SPK_AMG_COARSEN_* */
+    int32_t dims[SPK_AMG_MAX_LEVELS][3];     /* grid coarsening: the node grid of every level (else 0) */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -342,8 +357,16 @@ int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
 enum { SPK_AMG_OP = 0, SPK_AMG_PROLONG = 1, SPK_AMG_TENTATIVE = 2, SPK_AMG_COARSE_INV = 3 };
 int spk_get_amg_level(const spk_ctx *ctx, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
                       int32_t *rowptr, int32_t *colidx, double *val);
-/* Test hook: the aggregate of every node of a level of the context's hierarchy (-1: isolated); agg NULL for the size. */
+/* Test hook: the aggregate of every node of a level of the context's hierarchy (-1: isolated); agg NULL for the size.
+ * SPK_ERR_UNSUPPORTED on a grid-coarsened hierarchy (it has none). */
 int spk_get_amg_aggregates(const spk_ctx *ctx, int level, int32_t *nnodes, int32_t *agg);
+/* Test hook: one transfer of level `level` (< levels - 1) of the context's hierarchy alone, on host vectors.
+ * which 0: out = y + P e (e: the rows of level + 1, y and out: fine_len entries);  which 1: out = R (b - t) (b, t: fine_len
+ * entries, out: the rows of level + 1).  stored 0: the matrix-free kernels (SPK_ERR_STATE unless the level was built by
+ * the grid rule), 1: the CSR kernels on the stored P / R.  fine_len >= the rows of the level: the entries behind them
+ * stand for a padded vector and come back untouched (which 0). */
+int spk_debug_amg_transfer(spk_ctx *ctx, int level, int which, int stored, int64_t fine_len, const double *a, const double *b,
+                           double *out);
 /* Reuse of the interpolation (PETSc: -pc_gamg_reuse_interpolation).  Sticky like spk_pc_set_schur_pre, default 0.  With
  * reuse on, a spk_pc_setup that finds a hierarchy an earlier set-up built with reuse on, the same spk_amg_opts (field by
  * field, route and block size included), the same local size and padded vector length, and a diagonal A00 block with the

@@ -45,6 +45,10 @@ int SpkKSPSetOperatorsLaplace(SpkKSP ksp, int mx, int my, const double *kappa, c
 /* The same for the 3-D generator of spk_assembly.h (spk_set_block_laplace3d): mx x my x mz nodes, dof 3; kappa: one host
  * value per hexahedron, (mx-1)*(my-1)*(mz-1) of them, or NULL for ones. */
 int SpkKSPSetOperatorsLaplace3D(SpkKSP ksp, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host);
+/* The node grid behind the operator of SpkKSPSetOperators: mx x my (x mz; 1 or 0 in 2-D) nodes in natural ordering, bs
+ * unknowns per node (the role of KSPSetDM).  -pc_type mg and -fieldsplit_0_pc_type mg coarsen it; without a known grid
+ * they are refused at SpkKSPSetUp.  SpkKSPSetOperatorsLaplace / ...3D set it themselves. */
+int SpkKSPSetGrid(SpkKSP ksp, int mx, int my, int mz);
 /* argv-style option list, e.g. {"-ksp_type","fgmres","-ksp_rtol","1e-8",
  * "-pc_type","fieldsplit","-pc_fieldsplit_type","schur",
  * "-pc_fieldsplit_schur_fact_type","full"}.  Unknown -ksp_/-pc_/-fieldsplit_
@@ -82,7 +86,15 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * -pc_type fieldsplit).  *selected = 1 when that gamg was asked for.  Unknown -mg_ options are refused like unknown
  * -ksp_ ones.  -pc_type gamg with a B block, gamg with -ksp_type minres (pipecg takes it) and gamg beside the FP32 inner sweeps are
  * refused by SpkKSPSetUp with SPK_ERR_UNSUPPORTED.  (SpkKSPGetOptions reports -pc_type gamg as SPK_PC_JACOBI, the
- * slot the V-cycle takes.) */
+ * slot the V-cycle takes.)
+ * -pc_type mg and -fieldsplit_0_pc_type mg select the same slots with grid coarsening (opts->coarsening =
+ * SPK_AMG_COARSEN_GRID; PETSc: -pc_type mg -pc_mg_galerkin on a DMDA) and share the option sets: -pc_mg_levels,
+ * -mg_levels_*, -pc_gamg_coarse_eq_limit, -pc_gamg_reuse_interpolation, -spk_gamg_setup; -pc_gamg_threshold and
+ * -pc_gamg_agg_nsmooths are read and not used.  -pc_mg_galerkin takes no value, both or pmat (every coarse operator is
+ * the Galerkin product; anything else: SPK_ERR_UNSUPPORTED); -spk_mg_transfer matrixfree|stored selects how the V-cycle
+ * applies P and R (opts->transfer).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
+ * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);
 /* -pc_gamg_reuse_interpolation <bool> (fieldsplit0 = 1: -fieldsplit_0_pc_gamg_reuse_interpolation) as read; default
  * false, a name without a value means true.  On: SpkKSPSetUp passes spk_pc_set_amg_reuse(ctx, 1), so a second

@@ -71,6 +71,7 @@ class AmgOpts(C.Structure):
         ("max_levels", C.c_int32), ("coarse_eq_limit", C.c_int32), ("nsmooths", C.c_int32), ("smoother", C.c_int32),
         ("threshold", C.c_double), ("smooth_its", C.c_int32), ("block_size", C.c_int32), ("esteig", C.c_double * 4),
         ("richardson_scale", C.c_double), ("setup", C.c_int32),
+        ("coarsening", C.c_int32), ("grid", C.c_int32 * 3), ("transfer", C.c_int32),
     ]
 
 
@@ -80,6 +81,7 @@ class AmgInfo(C.Structure):
         ("levels", C.c_int32), ("block_size", C.c_int32), ("rows", C.c_int32 * AMG_MAX_LEVELS),
         ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("lambda_max", C.c_double * AMG_MAX_LEVELS),
         ("operator_complexity", C.c_double), ("setup_seconds", C.c_double), ("setup", C.c_int32),
+        ("coarsening", C.c_int32), ("dims", (C.c_int32 * 3) * AMG_MAX_LEVELS),
     ]
 
 
@@ -202,6 +204,7 @@ def _load():
     L.spk_get_amg_info.argtypes = [vp, C.POINTER(AmgInfo)]
     L.spk_get_amg_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
     L.spk_get_amg_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
+    L.spk_debug_amg_transfer.argtypes = [vp, C.c_int, C.c_int, C.c_int, i64, f64p, f64p, f64p]
     L.spk_amg_build_host.argtypes = [i32, i32p, i32p, f64p, C.POINTER(AmgOpts), C.POINTER(vp)]
     L.spk_amg_refresh_host.argtypes = [vp, vp]
     L.spk_amg_destroy_host.argtypes = [vp]
@@ -273,6 +276,7 @@ def _load():
     L.SpkKSPSetOperators.argtypes = [vp, C.POINTER(MatCSR), C.POINTER(MatCSR)]
     L.SpkKSPSetOperatorsLaplace.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
     L.SpkKSPSetOperatorsLaplace3D.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
+    L.SpkKSPSetGrid.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.SpkKSPSetFromOptions.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
     L.SpkKSPSetUp.argtypes = [vp]
     L.SpkKSPSolve.argtypes = [vp, f64p, f64p]

@@ -90,6 +90,7 @@ int main(int argc, char **argv)
     CHK(SpkKSPCreate(opt_int(argc, argv, "-spk_device", 0), &ksp));
     if (on_device) CHK(SpkKSPSetOperatorsLaplace(ksp, mx, my, nullptr, saddle ? &B : nullptr, rhs.data()));
     else CHK(SpkKSPSetOperators(ksp, &A, saddle ? &B : nullptr));
+    CHK(SpkKSPSetGrid(ksp, mx, my, 1));   // the DMDA's grid: what -pc_type mg coarsens
     CHK(SpkKSPSetFromOptions(ksp, argc - 1, argv + 1));
     CHK(SpkKSPSetUp(ksp));
     CHK(SpkKSPSolve(ksp, rhs.data(), sol.data()));

@@ -2,6 +2,9 @@
 // A00 block by one loop (build_levels) over two routes -- HostRoute: on the host, then uploaded (the default); DevRoute:
 // on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the V-cycle's launch sequence (kernels:
 // spk_k_amg.hip).
+// The same loop builds the grid-coarsened hierarchy (-pc_type mg, SPK_AMG_COARSEN_GRID): where the node grid is known a
+// level halves its odd sides and P is the tensor product of linear interpolations -- no graph, no aggregation, no
+// prolongator smoothing; everything else (Ritz values, Galerkin products, coarse inverse, refresh) is shared.
 // With reuse on (spk_pc_set_amg_reuse) a second, shorter loop (refresh_levels) over the same two routes puts new values
 // of A00 through a hierarchy whose aggregates, prolongators and patterns stay.
 //
@@ -332,6 +335,63 @@ HostCsr tentative(const std::vector<int32_t> &agg, int32_t na, int bs)
     return P;
 }
 
+// ---- grid coarsening (SPK_AMG_COARSEN_GRID): the halving rule and the tensor-product prolongator -------------------
+// a direction of m nodes halves iff m is odd and >= 5
+bool grid_halves(int32_t m) { return m >= 5 && (m & 1); }
+// the coarse grid of `fd`; false when no direction halves
+bool grid_coarse_dims(const int32_t fd[3], int32_t cd[3])
+{
+    bool any = false;
+    for (int a = 0; a < 3; ++a) {
+        cd[a] = grid_halves(fd[a]) ? (fd[a] + 1) / 2 : fd[a];
+        any = any || cd[a] != fd[a];
+    }
+    return any;
+}
+// the parents of fine index i in one direction: `first`, and one more behind it when cnt == 2 (weight 1/2 each, else 1)
+struct GridParents { int32_t first, cnt; };
+GridParents grid_parents(int32_t i, bool halved)
+{
+    if (!halved) return {i, 1};
+    return (i & 1) ? GridParents{(i - 1) / 2, 2} : GridParents{i / 2, 1};
+}
+// entries of P = P_z (x) P_y (x) P_x (x) I_bs: per direction i + i/2 parents lie before fine index i
+int64_t grid_prolong_nnz(const int32_t fd[3], const int32_t cd[3], int bs)
+{
+    int64_t t = bs;
+    for (int a = 0; a < 3; ++a) t *= cd[a] != fd[a] ? (int64_t)fd[a] + fd[a] / 2 : (int64_t)fd[a];
+    return t;
+}
+// P as CSR with ascending columns, boundary nodes included: no special case for Dirichlet rows
+HostCsr grid_prolongator(const int32_t fd[3], const int32_t cd[3], int bs)
+{
+    HostCsr P;
+    P.nrows = fd[0] * fd[1] * fd[2] * bs;
+    P.ncols = cd[0] * cd[1] * cd[2] * bs;
+    P.rp.assign(1, 0);
+    P.rp.reserve((size_t)P.nrows + 1);
+    const size_t nz = (size_t)grid_prolong_nnz(fd, cd, bs);
+    P.ci.reserve(nz);
+    P.v.reserve(nz);
+    for (int32_t k = 0; k < fd[2]; ++k)
+        for (int32_t j = 0; j < fd[1]; ++j)
+            for (int32_t i = 0; i < fd[0]; ++i) {
+                const GridParents px = grid_parents(i, cd[0] != fd[0]), py = grid_parents(j, cd[1] != fd[1]),
+                                  pz = grid_parents(k, cd[2] != fd[2]);
+                const double w = 1.0 / (double)(px.cnt * py.cnt * pz.cnt);   // 1, 1/2, 1/4 or 1/8
+                for (int c = 0; c < bs; ++c) {
+                    for (int32_t kk = 0; kk < pz.cnt; ++kk)
+                        for (int32_t jj = 0; jj < py.cnt; ++jj)
+                            for (int32_t ii = 0; ii < px.cnt; ++ii) {
+                                P.ci.push_back((((pz.first + kk) * cd[1] + py.first + jj) * cd[0] + px.first + ii) * bs + c);
+                                P.v.push_back(w);
+                            }
+                    P.rp.push_back((int32_t)P.ci.size());
+                }
+            }
+    return P;
+}
+
 // dense inverse of the SPD coarsest operator through Cholesky (symmetrised); a_scale as in lanczos: the factor is that
 // of a_scale A and the inverse is scaled back, both exactly
 std::vector<double> coarse_inverse(const HostCsr &A, double a_scale = 1.0)
@@ -408,6 +468,8 @@ void smoother_interval(const spk_amg_opts &o, int l, double lmin, double lmax, d
 //   set_interval(l, lo, hi): keeps what the smoother of level l needs
 //   coarsen(l, bs, agg, na, omega, nsmooths): keeps agg; tentative P, nsmooths times P <- (I - omega D^-1 A) P, R = P^T;
 //                                             appends level l+1 with A = (RAP + (RAP)^T) / 2 and its D^-1
+//   coarsen_grid(l, bs, fd, cd): grid coarsening's step -- P of the node grids fd -> cd (no aggregates, no smoothing),
+//                                             then R and level l+1 as coarsen has them
 //   coarsest(): the last operator as a HostCsr;  set_coarse_inverse(x): keeps its dense inverse
 // t0: when the caller began (its own preparation counts into info.setup_seconds).
 template <class Route>
@@ -415,14 +477,32 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
 {
     if (r.rows(0) % bs) fail(SPK_ERR_ARG, "amg: block_size %d does not divide %d rows", bs, (int)r.rows(0));
     std::memset(&info, 0, sizeof info);
+    const bool grid = o.coarsening == SPK_AMG_COARSEN_GRID;
+    int32_t fd[3] = {o.grid[0], o.grid[1], o.grid[2]}, cd[3] = {0, 0, 0};
+    if (grid && (int64_t)bs * fd[0] * fd[1] * fd[2] != (int64_t)r.rows(0))
+        fail(SPK_ERR_ARG, "amg: grid coarsening: the operator has %d rows, the grid %d x %d x %d nodes of %d unknowns has %lld",
+             (int)r.rows(0), (int)fd[0], (int)fd[1], (int)fd[2], bs, (long long)bs * fd[0] * fd[1] * fd[2]);
+    bool stuck = false;   // grid coarsening: no direction halves any more
     double tot = 0.0;
     int l = 0;
     for (;; ++l) {
         const int32_t n = r.rows(l);
         info.rows[l] = n;
         info.nnz[l] = r.nnz(l);
+        if (grid) std::memcpy(info.dims[l], fd, sizeof fd);
         tot += (double)info.nnz[l];
         if (n <= o.coarse_eq_limit || l + 1 == o.max_levels) break;
+        if (grid) {   // the grid is known: no graph, no aggregation, no prolongator smoothing
+            if (!grid_coarse_dims(fd, cd)) { stuck = true; break; }
+            double lmin = 0.0, lmax = 0.0, lo = 0.0, hi = 0.0;
+            r.ritz(l, &lmin, &lmax);
+            info.lambda_max[l] = lmax;
+            smoother_interval(o, l, lmin, lmax, &lo, &hi);
+            r.set_interval(l, lo, hi);
+            r.coarsen_grid(l, bs, fd, cd);
+            std::memcpy(fd, cd, sizeof fd);
+            continue;
+        }
         std::vector<int32_t> gp, gi, agg;
         r.graph(l, bs, o.threshold, gp, gi);
         const int32_t na = aggregate(gp, gi, agg);
@@ -436,6 +516,15 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
         r.coarsen(l, bs, std::move(agg), na, 4.0 / (3.0 * lmax), o.nsmooths);
     }
     info.levels = l + 1;
+    info.coarsening = o.coarsening;
+    if (r.rows(l) > SPK_AMG_MAX_COARSE && stuck) {
+        int a = 0;   // the largest side that does not halve
+        for (int b = 1; b < 3; ++b) if (fd[b] > fd[a]) a = b;
+        fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
+             "most %d -- grid coarsening stops at %d x %d x %d nodes: the side of %d nodes (direction %c) cannot be halved "
+             "(a side halves while it is odd and >= 5; sides of c 2^k + 1 nodes coarsen to the end)", (int)r.rows(l), info.levels,
+             SPK_AMG_MAX_COARSE, (int)fd[0], (int)fd[1], (int)fd[2], (int)fd[a], "xyz"[a]);
+    }
     if (r.rows(l) > SPK_AMG_MAX_COARSE)
         fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
              "most %d -- raise -pc_mg_levels or -pc_gamg_threshold 0", (int)r.rows(l), info.levels, SPK_AMG_MAX_COARSE);
@@ -498,6 +587,19 @@ struct HostRoute {
                 for (int32_t k = AP.rp[(size_t)i]; k < AP.rp[(size_t)i + 1]; ++k) AP.v[(size_t)k] *= L.dinv[(size_t)i];
             L.P = add(1.0, L.P, -omega, AP);
         }
+        galerkin(l);
+    }
+    void coarsen_grid(int l, int bs, const int32_t fd[3], const int32_t cd[3]) const
+    {
+        if (grid_prolong_nnz(fd, cd, bs) > INT32_MAX)
+            fail(SPK_ERR_UNSUPPORTED, "amg: the prolongator of level %d has more entries than 32-bit offsets address", l);
+        lv(l).P = grid_prolongator(fd, cd, bs);
+        galerkin(l);
+    }
+    // R = P^T and level l+1 from the P of level l
+    void galerkin(int l) const
+    {
+        AmgLevel &L = lv(l);
         L.R = transpose(L.P);
         HostCsr Ac = spgemm(L.R, spgemm(L.A, L.P));
         h.lv.emplace_back();   // (L dangles from here)
@@ -548,8 +650,10 @@ void check_level_query(int L, int l, int which)
 }
 
 template <class Levels>   // of AmgLevel or AmgLevelDev: both keep `agg`
-void aggregates_out(const Levels &lv, int l, int32_t *nnodes, int32_t *agg)
+void aggregates_out(const Levels &lv, const spk_amg_info &info, int l, int32_t *nnodes, int32_t *agg)
 {
+    if (info.coarsening == SPK_AMG_COARSEN_GRID)
+        fail(SPK_ERR_UNSUPPORTED, "amg: a grid-coarsened hierarchy has no aggregates (its levels are the node grids of spk_amg_info.dims)");
     if (l < 0 || l + 1 >= (int)lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no aggregates", l);
     const std::vector<int32_t> &a = lv[(size_t)l].agg;
     if (nnodes) *nnodes = (int32_t)a.size();
@@ -573,6 +677,19 @@ void amg_check_opts(const spk_amg_opts &o)
     if (!(o.richardson_scale > 0.0) || !std::isfinite(o.richardson_scale)) fail(SPK_ERR_ARG, "amg: richardson_scale must be > 0");
     if (o.setup != SPK_AMG_SETUP_HOST && o.setup != SPK_AMG_SETUP_DEVICE)
         fail(SPK_ERR_ARG, "amg: setup %d is neither SPK_AMG_SETUP_HOST (0) nor SPK_AMG_SETUP_DEVICE (1)", o.setup);
+    if (o.coarsening != SPK_AMG_COARSEN_AGGREGATION && o.coarsening != SPK_AMG_COARSEN_GRID)
+        fail(SPK_ERR_ARG, "amg: coarsening %d is neither SPK_AMG_COARSEN_AGGREGATION (0) nor SPK_AMG_COARSEN_GRID (1)", o.coarsening);
+    if (o.coarsening == SPK_AMG_COARSEN_GRID) {   // (grid and transfer are read under grid coarsening only)
+        if (o.grid[0] < 2 || o.grid[1] < 2 || o.grid[2] < 1)
+            fail(SPK_ERR_ARG, "amg: grid %d x %d x %d: at least 2 x 2 nodes (x 1 in 2-D)", o.grid[0], o.grid[1], o.grid[2]);
+        if ((int64_t)o.grid[0] * o.grid[1] > INT32_MAX || (int64_t)o.grid[0] * o.grid[1] * o.grid[2] > INT32_MAX)
+            fail(SPK_ERR_ARG, "amg: grid %d x %d x %d has more nodes than 32-bit rows address", o.grid[0], o.grid[1], o.grid[2]);
+        if (o.transfer != SPK_AMG_TRANSFER_MATRIX_FREE && o.transfer != SPK_AMG_TRANSFER_STORED)
+            fail(SPK_ERR_ARG, "amg: transfer %d is neither SPK_AMG_TRANSFER_MATRIX_FREE (0) nor SPK_AMG_TRANSFER_STORED (1)", o.transfer);
+        if (o.transfer == SPK_AMG_TRANSFER_MATRIX_FREE && (o.grid[1] > 65535 || o.grid[2] > 65535))   // they are launch dimensions
+            fail(SPK_ERR_UNSUPPORTED, "amg: the matrix-free transfers take at most 65535 nodes in y and z (grid %d x %d x %d) -- "
+                 "use -spk_mg_transfer stored", o.grid[0], o.grid[1], o.grid[2]);
+    }
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
@@ -616,7 +733,7 @@ void AmgHier::level(int l, int which, const CsrOut &out) const
     check_level_query((int)lv.size(), l, which);
     const AmgLevel &V = lv[(size_t)l];
     if (which == SPK_AMG_COARSE_INV) coarse_inv_out(V.A.nrows, cinv.data(), out);
-    else csr_out(which == SPK_AMG_OP ? V.A : which == SPK_AMG_PROLONG ? V.P : V.Ptent, out);
+    else csr_out(which == SPK_AMG_OP ? V.A : which == SPK_AMG_PROLONG || o.coarsening == SPK_AMG_COARSEN_GRID ? V.P : V.Ptent, out);
 }
 
 }  // namespace spk
@@ -744,6 +861,7 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
         upload_host_csr(D.P, H.P);
         upload_host_csr(D.R, H.R);
         smoother_coeffs(D, h.o, H.lo, H.hi);
+        if (h.info.coarsening == SPK_AMG_COARSEN_GRID) D.grid.set(h.info.dims[l], h.info.dims[l + 1], h.info.block_size, h.o.transfer);
     }
     d->cinv.upload(h.cinv.data(), h.cinv.size());
     alloc_cycle_vectors(*d, c->ld);
@@ -995,6 +1113,27 @@ struct DevRoute {
             dev_add(Pn, 1.0, L.P, -omega, AP, dinv(l), s);
             L.P = std::move(Pn);
         }
+        galerkin(l);
+    }
+    // P from the node grids alone: every row length is known, so one kernel writes row pointers, columns and weights
+    void coarsen_grid(int l, int bs, const int32_t fd[3], const int32_t cd[3])
+    {
+        AmgLevelDev &L = d.lv[(size_t)l];
+        const int64_t nz = grid_prolong_nnz(fd, cd, bs);
+        if (nz > INT32_MAX)
+            fail(SPK_ERR_UNSUPPORTED, "amg: the prolongator of level %d has more entries than 32-bit offsets address", l);
+        L.grid.set(fd, cd, bs, o.transfer);
+        L.P.nrows = rows(l);
+        L.P.ncols = cd[0] * cd[1] * cd[2] * bs;
+        L.P.rowptr.alloc_raw((size_t)L.P.nrows + 1, 8);
+        dev_csr_values(L.P, nz);
+        k::amgs_grid_prolongator(L.grid, L.P.rowptr.p, L.P.colidx.p, L.P.val.p, s);
+        galerkin(l);
+    }
+    // R = P^T and level l+1 from the P of level l
+    void galerkin(int l)
+    {
+        AmgLevelDev &L = d.lv[(size_t)l];
         dev_transpose(L.R, L.P, s);
         CsrDev AP, Ac, AcT;
         dev_spgemm(AP, A(l), L.P, s);
@@ -1076,8 +1215,10 @@ bool amg_can_refresh(spk_ctx *c)
     const spk_amg_opts &a = c->amg_opts, &b = ru.o;
     bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
                 a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
-                a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup;
+                a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup &&
+                a.coarsening == b.coarsening && a.transfer == b.transfer;
     for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
+    for (int i = 0; i < 3; ++i) same = same && a.grid[i] == b.grid[i];
     if (!same || ctx_block_size(c, a) != ru.bs || c->n_local != ru.n || c->Ad.nnz != ru.nnz || c->ld != ru.ld) return false;
     if ((a.setup == SPK_AMG_SETUP_HOST) != (c->amg_h != nullptr)) return false;
     hipStream_t s = c->stream;
@@ -1155,7 +1296,8 @@ void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out)
         if (out.val) SPK_HIP(hipMemcpy(cinv.data(), d.cinv.p, sizeof(double) * cinv.size(), hipMemcpyDeviceToHost));
         return coarse_inv_out(V.n, cinv.data(), out);
     }
-    const CsrDev &M = which == SPK_AMG_OP ? (l == 0 ? c->Ad : V.A) : which == SPK_AMG_PROLONG ? V.P : V.Ptent;
+    const bool grid = d.info.coarsening == SPK_AMG_COARSEN_GRID;   // no tentative prolongator: SPK_AMG_TENTATIVE is P
+    const CsrDev &M = which == SPK_AMG_OP ? (l == 0 ? c->Ad : V.A) : which == SPK_AMG_PROLONG || grid ? V.P : V.Ptent;
     if (!out.rowptr && !out.colidx && !out.val) return out.sizes(M.nrows, M.ncols, M.nnz);   // nothing to download
     HostCsr H = dev_csr_download(M, true, c->stream);
     if (which == SPK_AMG_OP && l == 0) sort_rows(H);   // the context's CSR keeps the caller's order
@@ -1164,8 +1306,36 @@ void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out)
 
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg)
 {
-    if (c->amg_h) aggregates_out(c->amg_h->h.lv, l, nnodes, agg);
-    else aggregates_out(c->amg_d->lv, l, nnodes, agg);
+    if (c->amg_h) aggregates_out(c->amg_h->h.lv, c->amg_d->info, l, nnodes, agg);
+    else aggregates_out(c->amg_d->lv, c->amg_d->info, l, nnodes, agg);
+}
+
+// the test hook of the transfers: one launch on copies of the caller's vectors
+void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out)
+{
+    AmgDev &d = *c->amg_d;
+    if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no transfer", l);
+    if ((which != 0 && which != 1) || (stored != 0 && stored != 1)) fail(SPK_ERR_ARG, "amg: transfer hook: which and stored are 0 or 1");
+    AmgLevelDev &D = d.lv[(size_t)l];
+    const int64_t nf = D.n, nc = d.lv[(size_t)l + 1].n;
+    if (fine_len < nf) fail(SPK_ERR_ARG, "amg: transfer hook: %lld entries for the %lld rows of level %d", (long long)fine_len, (long long)nf, l);
+    if (!stored && !D.grid.on) fail(SPK_ERR_STATE, "amg: level %d was not built by the grid rule: it has no matrix-free transfer", l);
+    hipStream_t s = c->stream;
+    DevBuf<double> da, db, dout;
+    const int64_t na = which == 0 ? nc : fine_len, nb = fine_len, no = which == 0 ? fine_len : nc;
+    da.upload(a, (size_t)na, 16);
+    db.upload(b, (size_t)nb, 16);
+    if (which == 0) {   // out = y + P e, in place on the copy of y
+        if (stored) k::amg_prolong_add(D.P, da.p, db.p, nullptr, s);
+        else k::amg_prolong_add_grid(D.grid, da.p, db.p, nullptr, s);
+        SPK_HIP(hipMemcpyAsync(out, db.p, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, s));
+    } else {
+        dout.alloc((size_t)no, 16);
+        if (stored) k::amg_restrict(D.R, da.p, db.p, dout.p, nullptr, s);
+        else k::amg_restrict_grid(D.grid, da.p, db.p, dout.p, nullptr, s);
+        SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, s));
+    }
+    SPK_HIP(hipStreamSynchronize(s));
 }
 
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
@@ -1213,14 +1383,16 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
         if (l == 0) a_mult(c, cur[l], D.t.p, nullptr, nullptr, done, false, nullptr);
         else k::amg_spmv(D.A, cur[l], D.ya.p == cur[l] ? D.yb.p : D.ya.p, done, s);
         const double *t = l == 0 ? D.t.p : (D.ya.p == cur[l] ? D.yb.p : D.ya.p);
-        k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
+        if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b.p, done, s);
+        else k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
     }
     AmgLevelDev &C = d.lv[L - 1];   // exact coarse solve
     k::amg_dense(d.cinv.p, C.n, rhs(L - 1), C.ya.p, done, s);
     cur[L - 1] = C.ya.p;
     for (size_t l = L - 1; l-- > 0;) {   // up: prolongation + correction, post-smoothing
         AmgLevelDev &D = d.lv[l];
-        k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
+        if (D.grid.matrix_free) k::amg_prolong_add_grid(D.grid, cur[l + 1], cur[l], done, s);
+        else k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
         cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done);
     }
     if (last) *last = cur[0];   // the caller's own pass reads the iterate where it lies
@@ -1313,7 +1485,7 @@ int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, i
 {
     if (!h) return SPK_ERR_ARG;
     SPK_HOST_TRY
-    spk::aggregates_out(h->h.lv, level, nnodes, agg);
+    spk::aggregates_out(h->h.lv, h->h.info, level, nnodes, agg);
     SPK_HOST_CATCH
 }
 

@@ -399,6 +399,16 @@ int spk_get_amg_aggregates(const spk_ctx *cc, int level, int32_t *nnodes, int32_
     SPK_CATCH(c)
 }
 
+int spk_debug_amg_transfer(spk_ctx *c, int level, int which, int stored, int64_t fine_len, const double *a, const double *b,
+                           double *out)
+{
+    SPK_TRY(c)
+    if (!a || !b || !out) spk::fail(SPK_ERR_ARG, "debug_amg_transfer: null pointer");
+    need_amg(c);
+    spk::amg_debug_transfer(c, level, which, stored, fine_len, a, b, out);
+    SPK_CATCH(c)
+}
+
 int spk_pc_set_amg_reuse(spk_ctx *c, int reuse)
 {
     SPK_TRY(c)

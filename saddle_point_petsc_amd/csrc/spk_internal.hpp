@@ -784,6 +784,20 @@ void krylov_refine_decide(const KrylovArrays &ka, int loc, int mode, const doubl
                           double *dots2, hipStream_t s);
 void krylov_refine_merge(const KrylovArrays &ka, int loc, double *dots, const double *dots2, double *nrm,
                          const double *nrm_b, int nn, hipStream_t s);
+// one transfer of a grid-coarsened level (SPK_AMG_COARSEN_GRID): the node grids on both sides and the node size
+struct AmgGrid {
+    int32_t fd[3] = {0, 0, 0}, cd[3] = {0, 0, 0};   // fine and coarse nodes per side; cd[a] != fd[a]: the direction halves
+    int32_t bs = 0;
+    bool on = false;            // the level was built by the grid rule
+    bool matrix_free = false;   // ... and the V-cycle applies P and R without reading them
+    void set(const int32_t *f, const int32_t *c, int b, int transfer)
+    {
+        for (int a = 0; a < 3; ++a) fd[a] = f[a], cd[a] = c[a];
+        bs = b;
+        on = true;
+        matrix_free = transfer == SPK_AMG_TRANSFER_MATRIX_FREE;
+    }
+};
 // smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
 void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
 void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
@@ -791,6 +805,10 @@ void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const do
 void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s);   // out = R (b - t)
 void amg_prolong_add(const CsrDev &P, const double *e, double *y, const int32_t *done, hipStream_t s);          // y += P e
 // y == nullptr: out = alpha dinv b (zero initial guess); else out = y + alpha dinv (b - t) + beta (y - yo) (yo null: 0)
+// the same two on a grid-coarsened level without reading P or R: the weights are powers of two, the sums run in
+// ascending column order from the first product
+void amg_restrict_grid(const AmgGrid &g, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s);
+void amg_prolong_add_grid(const AmgGrid &g, const double *e, double *y, const int32_t *done, hipStream_t s);
 void amg_cheb_vec(int64_t n, const double *dinv, const double *b, const double *t, const double *y, const double *yo,
                   double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
 // the fine level's fused step on the 2x2 row-type layout (false: A is not that layout, nothing launched)
@@ -805,6 +823,7 @@ void amgs_node_norms(const int32_t *rp, const int32_t *ci, const double *v, int3
 // gp null: out[I] = strong neighbours of node I; else the neighbours at out[gp[I]..), ascending
 void amgs_graph(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double theta, const double *dn,
                 const int32_t *gp, int32_t *out, hipStream_t s);
+void amgs_grid_prolongator(const AmgGrid &g, int32_t *rp, int32_t *ci, double *v, hipStream_t s);   // P of g: row pointers, columns, weights
 void amgs_tent_count(const int32_t *agg, int32_t nrows, int bs, int32_t *cnt, hipStream_t s);
 void amgs_tent_fill(const int32_t *agg, const double *inv, int32_t nrows, int bs, const int32_t *rp, int32_t *ci, double *v,
                     hipStream_t s);
@@ -841,6 +860,7 @@ struct AmgLevelDev {
     DevBuf<double> dinv;               // levels >= 1
     DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
+    k::AmgGrid grid;                    // grid coarsening: the transfer to level l+1
 };
 // what a set-up with reuse on (spk_pc_set_amg_reuse) keeps beside the hierarchy, so that the next one can refresh it
 struct AmgReuse {
@@ -1025,6 +1045,7 @@ void amg_drop_reuse(spk_ctx *c);
 // the test hooks on either route: the host hierarchy's copy, or a download from the device-built levels
 void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
+void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out);
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last = nullptr);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

@@ -1,7 +1,8 @@
 // spk_k_amg.hip -- the V-cycle of the smoothed-aggregation multigrid (-pc_type gamg; host side in spk_amg.cpp).
 // gfx950, wave64, FP64.  The levels >= 1 are CSR (sorted columns): eight lanes per row, each lane a fixed stride of
 // the row, the eight partial sums added in a fixed butterfly -- no atomics, the same bits on every run.  Every launch
-// takes the solver's `done` gate.
+// takes the solver's `done` gate.  A level coarsened by the grid rule (-pc_type mg) applies P and R without reading
+// them: amg_prolong_grid_kernel / amg_restrict_grid_kernel below.
 #include "spk_dict.hpp"
 
 namespace spk {
@@ -171,6 +172,121 @@ __global__ __launch_bounds__(kThreads) void amg_out_kernel(int mode, int64_t n, 
     if (done && *done) return;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
         dst[i] = mode ? dst[i] - src[i] : src[i];
+}
+
+// ---- the transfers of a grid-coarsened level, matrix-free (SPK_AMG_TRANSFER_MATRIX_FREE) -------------------------------
+// P = P_z (x) P_y (x) P_x (x) I_bs is never read: a fine index that is even in a halved direction has the one parent
+// i / 2 (weight 1), an odd one the parents (i - 1) / 2 and (i + 1) / 2 (weight 1/2 each); a direction that does not
+// halve is the identity.  Every weight is a power of two, so every product is exact and the order of the additions alone
+// defines the bits: ascending column of P (prolongation) or of R (restriction), from the first product -- z outermost,
+// x innermost.  The grid's x is one row of dofs of a node row, y and z the node row: no integer division but by BS.
+struct GridArgs {
+    int32_t fx, fy, cx, cy, cz;   // fine nodes in x, y; coarse nodes per side
+    int32_t hx, hy, hz;           // 1: the direction halves
+};
+
+// y[f] += sum_parents w e[c]: one thread per fine dof; byte model: y read + y written + e read
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amg_prolong_grid_kernel(GridArgs g, const double *__restrict__ e, double *y,
+                                                                    const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the node row
+    if (xd >= g.fx * BS) return;
+    const int32_t i = xd / BS, c = xd - i * BS, j = (int32_t)blockIdx.y, k = (int32_t)blockIdx.z;
+    const bool ox = g.hx && (i & 1), oy = g.hy && (j & 1), oz = g.hz && (k & 1);   // two parents in the direction
+    const int32_t ic = g.hx ? i >> 1 : i, jc = g.hy ? j >> 1 : j, kc = g.hz ? k >> 1 : k;   // the first parent
+    const double w = (ox ? 0.5 : 1.0) * (oy ? 0.5 : 1.0) * (oz ? 0.5 : 1.0);
+    const int64_t sx = BS, sy = (int64_t)g.cx * BS, sz = sy * g.cy;
+    const double *p = e + ((int64_t)kc * g.cy + jc) * sy + (int64_t)ic * BS + c;
+    // the (up to) eight parents, loaded before the first addition; absent ones read the first parent again and add nothing
+    const double e000 = p[0], e001 = p[ox ? sx : 0], e010 = p[oy ? sy : 0], e011 = p[(oy ? sy : 0) + (ox ? sx : 0)];
+    const int64_t oz_ = oz ? sz : 0;
+    const double e100 = p[oz_], e101 = p[oz_ + (ox ? sx : 0)], e110 = p[oz_ + (oy ? sy : 0)],
+                 e111 = p[oz_ + (oy ? sy : 0) + (ox ? sx : 0)];
+    double s = w * e000;
+    if (ox) s += w * e001;
+    if (oy) { s += w * e010; if (ox) s += w * e011; }
+    if (oz) {
+        s += w * e100;
+        if (ox) s += w * e101;
+        if (oy) { s += w * e110; if (ox) s += w * e111; }
+    }
+    const int64_t f = (((int64_t)k * g.fy + j) * g.fx) * BS + xd;
+    y[f] = y[f] + s;
+}
+
+// out[c] = sum_children w (b[f] - t[f]): one thread per coarse dof, a gather over the <= 3 fine indices of every halved
+// direction (<= 27 terms), no atomics; byte model: b + t read + out written
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g, int32_t fz, const double *__restrict__ b,
+                                                                     const double *__restrict__ t, double *__restrict__ out,
+                                                                     const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the coarse node row
+    if (xd >= g.cx * BS) return;
+    const int32_t ic = xd / BS, c = xd - ic * BS, jc = (int32_t)blockIdx.y, kc = (int32_t)blockIdx.z;
+    // the fine indices [lo, hi] of a direction and its centre (weight 1; the others 1/2)
+    const int32_t mi = g.hx ? 2 * ic : ic, mj = g.hy ? 2 * jc : jc, mk = g.hz ? 2 * kc : kc;
+    const int32_t i0 = g.hx ? max(mi - 1, 0) : mi, i1 = g.hx ? min(mi + 1, g.fx - 1) : mi;
+    const int32_t j0 = g.hy ? max(mj - 1, 0) : mj, j1 = g.hy ? min(mj + 1, g.fy - 1) : mj;
+    const int32_t k0 = g.hz ? max(mk - 1, 0) : mk, k1 = g.hz ? min(mk + 1, fz - 1) : mk;
+    double s = 0.0;
+    bool first = true;
+#pragma unroll
+    for (int dk = 0; dk < 3; ++dk) {
+        const int32_t k = k0 + dk;
+        if (k > k1) break;
+#pragma unroll
+        for (int dj = 0; dj < 3; ++dj) {
+            const int32_t j = j0 + dj;
+            if (j > j1) break;
+            const double wyz = (k == mk ? 1.0 : 0.5) * (j == mj ? 1.0 : 0.5);
+            const int64_t row = (((int64_t)k * g.fy + j) * g.fx) * BS + c;
+            double r[3];
+#pragma unroll
+            for (int di = 0; di < 3; ++di) {   // the row's loads first: they do not wait for the sum
+                const int32_t i = min(i0 + di, i1);
+                r[di] = b[row + (int64_t)i * BS] - t[row + (int64_t)i * BS];
+            }
+#pragma unroll
+            for (int di = 0; di < 3; ++di) {
+                const int32_t i = i0 + di;
+                if (i > i1) break;
+                const double term = (wyz * (i == mi ? 1.0 : 0.5)) * r[di];
+                s = first ? term : s + term;
+                first = false;
+            }
+        }
+    }
+    out[(((int64_t)kc * g.cy + jc) * g.cx) * BS + xd] = s;
+}
+
+namespace {
+inline GridArgs grid_args(const AmgGrid &a)
+{
+    return GridArgs{a.fd[0], a.fd[1], a.cd[0], a.cd[1], a.cd[2], a.cd[0] != a.fd[0], a.cd[1] != a.fd[1], a.cd[2] != a.fd[2]};
+}
+// x: the dofs of one node row in workgroups; y, z: the node rows (amg_check_opts keeps both within 65535)
+inline dim3 transfer_grid(const int32_t d[3], int bs) { return dim3((unsigned)(((int64_t)d[0] * bs + kThreads - 1) / kThreads), (unsigned)d[1], (unsigned)d[2]); }
+}  // namespace
+
+void amg_prolong_add_grid(const AmgGrid &a, const double *e, double *y, const int32_t *done, hipStream_t s)
+{
+    const GridArgs g = grid_args(a);
+    const dim3 grid = transfer_grid(a.fd, a.bs);
+    if (a.bs == 1) hipLaunchKernelGGL(amg_prolong_grid_kernel<1>, grid, dim3(kThreads), 0, s, g, e, y, done);
+    else if (a.bs == 2) hipLaunchKernelGGL(amg_prolong_grid_kernel<2>, grid, dim3(kThreads), 0, s, g, e, y, done);
+    else hipLaunchKernelGGL(amg_prolong_grid_kernel<3>, grid, dim3(kThreads), 0, s, g, e, y, done);
+}
+void amg_restrict_grid(const AmgGrid &a, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s)
+{
+    const GridArgs g = grid_args(a);
+    const dim3 grid = transfer_grid(a.cd, a.bs);
+    if (a.bs == 1) hipLaunchKernelGGL(amg_restrict_grid_kernel<1>, grid, dim3(kThreads), 0, s, g, a.fd[2], b, t, out, done);
+    else if (a.bs == 2) hipLaunchKernelGGL(amg_restrict_grid_kernel<2>, grid, dim3(kThreads), 0, s, g, a.fd[2], b, t, out, done);
+    else hipLaunchKernelGGL(amg_restrict_grid_kernel<3>, grid, dim3(kThreads), 0, s, g, a.fd[2], b, t, out, done);
 }
 
 namespace {

@@ -133,6 +133,38 @@ __global__ __launch_bounds__(kThreads) void amgs_tent_fill_kernel(const int32_t 
 }
 
 // ---------------------------------------------------------------------------
+// grid coarsening: P = P_z (x) P_y (x) P_x (x) I_bs from the node grids alone, one row (fine dof) per thread.  i + i / 2
+// parents lie before fine index i of a halved direction (i of one that keeps its nodes), so the row's offset follows
+// from its indices: no count, no scan.  Columns ascend (z outermost), the weights are 1, 1/2, 1/4 or 1/8.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void amgs_grid_prolongator_kernel(int32_t fx, int32_t fy, int32_t fz, int32_t cx, int32_t cy,
+                                                                         int32_t cz, int bs, int32_t *__restrict__ rp,
+                                                                         int32_t *__restrict__ ci, double *__restrict__ v)
+{
+    const int64_t nrows = (int64_t)fx * fy * fz * bs, f = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (f >= nrows) return;
+    const int32_t node = (int32_t)(f / bs), c = (int32_t)(f - (int64_t)node * bs);
+    const int32_t i = node % fx, j = (node / fx) % fy, k = node / fx / fy;
+    const bool hx = cx != fx, hy = cy != fy, hz = cz != fz;
+    const int32_t nx = hx && (i & 1) ? 2 : 1, ny = hy && (j & 1) ? 2 : 1, nz = hz && (k & 1) ? 2 : 1;
+    const int32_t ic = hx ? i >> 1 : i, jc = hy ? j >> 1 : j, kc = hz ? k >> 1 : k;
+    // parents before this index per direction, and in a whole direction
+    const int64_t bx = hx ? i + (i >> 1) : i, by = hy ? j + (j >> 1) : j, bz = hz ? k + (k >> 1) : k;
+    const int64_t tx = hx ? fx + (fx >> 1) : fx, ty = hy ? fy + (fy >> 1) : fy;
+    const int32_t len = nx * ny * nz;
+    int64_t p = (tx * ty * bz + nz * (tx * by + ny * bx)) * bs + (int64_t)c * len;
+    rp[f] = (int32_t)p;
+    if (f + 1 == nrows) rp[nrows] = (int32_t)(p + len);
+    const double w = 1.0 / (double)len;
+    for (int32_t kk = 0; kk < nz; ++kk)
+        for (int32_t jj = 0; jj < ny; ++jj)
+            for (int32_t ii = 0; ii < nx; ++ii, ++p) {
+                ci[p] = (((kc + kk) * cy + jc + jj) * cx + ic + ii) * bs + c;
+                v[p] = w;
+            }
+}
+
+// ---------------------------------------------------------------------------
 // C = A B, one row per thread.  bound: what a row can hold at most (its number of products, or every column of B);
 // expand: the row's slice of the scratch keeps a sorted list of (column, sum) -- a product finds its column by bisection
 // or opens it by shifting the tail -- so each entry is summed in A's stored order, then B's, from 0, as the host's dense
@@ -478,6 +510,11 @@ void amgs_tent_fill(const int32_t *agg, const double *inv, int32_t nrows, int bs
                     hipStream_t s)
 {
     if (nrows > 0) hipLaunchKernelGGL(amgs_tent_fill_kernel, row_grid(nrows), dim3(kThreads), 0, s, agg, inv, nrows, bs, rp, ci, v);
+}
+void amgs_grid_prolongator(const AmgGrid &g, int32_t *rp, int32_t *ci, double *v, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_grid_prolongator_kernel, row_grid((int64_t)g.fd[0] * g.fd[1] * g.fd[2] * g.bs), dim3(kThreads), 0, s,
+                       g.fd[0], g.fd[1], g.fd[2], g.cd[0], g.cd[1], g.cd[2], (int)g.bs, rp, ci, v);
 }
 void amgs_spgemm_bound(const CsrDev &A, const CsrDev &B, int32_t *bound, unsigned long long *total, hipStream_t s)
 {

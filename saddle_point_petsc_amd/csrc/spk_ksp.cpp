@@ -31,6 +31,9 @@ struct SpkKSP_s {
     int split1_pc = -1;                             // -fieldsplit_1_pc_type: 0 jacobi, 1 cholesky | lu, -1 follows schur_pre
     spk_amg_opts amg[2];
     bool amg_reuse[2] = {false, false};             // -pc_gamg_reuse_interpolation, plain and with -fieldsplit_0_
+    // -pc_type mg / -fieldsplit_0_pc_type mg: the same slots and option sets with amg[].coarsening = SPK_AMG_COARSEN_GRID;
+    // the node grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid (mz = 1 in 2-D; 0: not known)
+    int32_t grid[3] = {0, 0, 0};
     bool have_ops = false, is_setup = false, has_B = false;
     bool ops_device = false;   // the last KSPSetOperators assembled A00 on the device (-ksp_view)
     bool ops_device_3d = false;   // ... with the 3-D generator's kernel
@@ -131,6 +134,16 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "host") o.setup = SPK_AMG_SETUP_HOST;
         else if (v == "device") o.setup = SPK_AMG_SETUP_DEVICE;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (host | device)");
+    } else if (key == "-pc_mg_galerkin") {   // Galerkin is the only coarse operator here
+        if (val && std::string(val) != "both" && std::string(val) != "pmat")
+            return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (no value | both | pmat: every "
+                                                   "coarse operator is the Galerkin product)");
+    } else if (key == "-spk_mg_transfer") {
+        if (!val) return need("matrixfree or stored");
+        const std::string v(val);
+        if (v == "matrixfree") o.transfer = SPK_AMG_TRANSFER_MATRIX_FREE;
+        else if (v == "stored") o.transfer = SPK_AMG_TRANSFER_STORED;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (matrixfree | stored)");
     } else if (key == "-mg_levels_pc_type") {
         if (!val) return need("a type");
         if (std::string(val) != "jacobi") return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (jacobi)");
@@ -260,7 +273,19 @@ static int set_operators_device(SpkKSP k, int mx, int my, int mz, const double *
     if (rc != SPK_OK) return rc;
     rc = set_operators_tail(k, B, true);
     if (rc == SPK_OK) k->ops_device_3d = mz != 0;
+    if (rc == SPK_OK) k->grid[0] = mx, k->grid[1] = my, k->grid[2] = mz ? mz : 1;
     return rc;
+}
+
+int SpkKSPSetGrid(SpkKSP k, int mx, int my, int mz)
+{
+    if (!k) return SPK_ERR_ARG;
+    if (mx < 2 || my < 2 || mz < 0)
+        return set_err(k, SPK_ERR_ARG, "KSPSetGrid: " + std::to_string(mx) + " x " + std::to_string(my) + " x " + std::to_string(mz) +
+                                       " nodes (at least 2 x 2; mz = 1, or 0, in 2-D)");
+    k->grid[0] = mx, k->grid[1] = my, k->grid[2] = mz ? mz : 1;
+    k->is_setup = false;
+    return SPK_OK;
 }
 
 int SpkKSPSetOperatorsLaplace(SpkKSP k, int mx, int my, const double *kappa, const SpkMatCSR *B, double *f_host)
@@ -352,9 +377,10 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (v == "none") k->pc_type = SPK_PC_NONE;
             else if (v == "jacobi") k->pc_type = SPK_PC_JACOBI;
             else if (v == "fieldsplit") k->pc_type = SPK_PC_SCHUR;
-            else if (v == "gamg") k->pc_type = SPK_PC_JACOBI;   // Jacobi's slot, M^-1 = one V-cycle (K = A only)
+            else if (v == "gamg" || v == "mg") k->pc_type = SPK_PC_JACOBI;   // Jacobi's slot, M^-1 = one V-cycle (K = A only)
             else return bad();
-            k->pc_gamg = v == "gamg";
+            k->pc_gamg = v == "gamg" || v == "mg";
+            if (k->pc_gamg) k->amg[0].coarsening = v == "mg" ? SPK_AMG_COARSEN_GRID : SPK_AMG_COARSEN_AGGREGATION;
             k->pc_type_given = true;
         } else if (key == "-pc_fieldsplit_type") {
             if (!val) return need("a type");
@@ -393,8 +419,9 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (!val) return need("a type");
             const std::string v(val);
             if (v == "jacobi") k->split0_gamg = false;
-            else if (v == "gamg") k->split0_gamg = true;
+            else if (v == "gamg" || v == "mg") k->split0_gamg = true;
             else return bad();
+            if (k->split0_gamg) k->amg[1].coarsening = v == "mg" ? SPK_AMG_COARSEN_GRID : SPK_AMG_COARSEN_AGGREGATION;
         } else if (key == "-fieldsplit_1_pc_type") {
             if (!val) return need("a type");
             const std::string v(val);
@@ -437,7 +464,7 @@ int SpkKSPSetUp(SpkKSP k)
                                                "preconditioner)");
     if (!k->pc_type_given)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: no -pc_type given; PETSc's default (ilu, bjacobi+ilu in parallel) is "
-                                               "not implemented -- pass -pc_type jacobi | fieldsplit | gamg | none");
+                                               "not implemented -- pass -pc_type jacobi | fieldsplit | gamg | mg | none");
     // KSP / PC compatibility: option checks only, no GPU needed
     const bool minres = k->ksp_type == kMinres, pipecgrr = k->ksp_type == kPipecgrr;
     const bool pipecg = k->ksp_type == kPipecg || pipecgrr;
@@ -478,12 +505,19 @@ int SpkKSPSetUp(SpkKSP k)
                                                "inner sweeps are not one in FP64 -- drop -fieldsplit_0_ksp_type richardson / "
                                                "-spk_inner_sweeps, or pass -pc_fieldsplit_schur_precondition selfp");
     const int amg_slot = amg_active(k);
+    const bool mg = amg_slot >= 0 && k->amg[amg_slot].coarsening == SPK_AMG_COARSEN_GRID;
+    const std::string mgname = mg ? "mg" : "gamg";
     if (minres && amg_slot >= 0)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (gamg) is not "
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (" + mgname + ") is not "
                                                "implemented -- pass -ksp_type fgmres");
     if (amg_slot >= 0 && k->inner_richardson && k->inner_sweeps > 0)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: gamg and the FP32 inner sweeps both stand for A^-1 -- drop "
-                                               "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the gamg option");
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: " + mgname + " and the FP32 inner sweeps both stand for A^-1 -- drop "
+                                               "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the " + mgname + " option");
+    if (mg && k->grid[0] == 0)
+        return set_err(k, SPK_ERR_STATE, std::string("KSPSetUp: ") + (amg_slot ? "-fieldsplit_0_pc_type mg" : "-pc_type mg") +
+                       " coarsens a node grid and none is known -- call SpkKSPSetGrid(ksp, mx, my, mz) (the role of KSPSetDM), or "
+                       "set the operator with SpkKSPSetOperatorsLaplace / SpkKSPSetOperatorsLaplace3D");
+    if (mg) std::memcpy(k->amg[amg_slot].grid, k->grid, sizeof k->grid);
     for (int slot = 0; slot < 2; ++slot)
         if (k->amg_reuse[slot] && slot != amg_slot)
             return set_err(k, SPK_ERR_UNSUPPORTED, std::string("KSPSetUp: ") + (slot ? "-fieldsplit_0_pc_gamg_reuse_interpolation" :
@@ -497,9 +531,9 @@ int SpkKSPSetUp(SpkKSP k)
     if (k->pc_type == SPK_PC_SCHUR && !k->has_B)
         return set_err(k, SPK_ERR_STATE, "KSPSetUp: -pc_type fieldsplit (schur) needs the constraint block B");
     if (k->pc_type == SPK_PC_JACOBI && k->pc_gamg && k->has_B)
-        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -pc_type gamg is for K = A alone; the saddle matrix [A B^T; B 0] "
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -pc_type " + mgname + " is for K = A alone; the saddle matrix [A B^T; B 0] "
                                                "(indefinite, zero (1,1) block) is not a multigrid target -- pass -pc_type "
-                                               "fieldsplit -fieldsplit_0_pc_type gamg");
+                                               "fieldsplit -fieldsplit_0_pc_type " + mgname);
     int rc = amg_slot >= 0 ? SPK_OK : spk_pc_set_amg(k->ctx, nullptr);
     if (rc != SPK_OK) return from_ctx(k, rc);
     rc = spk_pc_set_inner(k->ctx, k->inner_richardson ? k->inner_sweeps : 0, k->inner_omega);
@@ -556,7 +590,8 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
         else
             std::printf("%s norm, ", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned");
         std::printf("rtol=%g atol=%g divtol=%g max_it=%d, ", k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it);
-        const char *pc = k->pc_gamg ? "gamg" : k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none";
+        const char *pc = k->pc_gamg ? (k->amg[0].coarsening == SPK_AMG_COARSEN_GRID ? "mg" : "gamg") :
+                         k->pc_type == SPK_PC_JACOBI ? "jacobi" : "none";
         switch (k->ksp_type) {
         case kFgmres: std::printf("right preconditioning, pc=%d schur_fact=%d\n", k->pc_type, k->schur_fact); break;
         case kMinres: std::printf("pc=%d schur_fact=%d\n", k->pc_type, k->schur_fact); break;
@@ -589,19 +624,29 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
         spk_amg_info ai;
         if (spk_get_amg_info(k->ctx, &ai) == SPK_OK) {
             const spk_amg_opts &o = k->amg[amg_active(k)];
-            std::printf("  PC gamg (smoothed aggregation, %s): %d levels, block size %d, operator complexity %.4f, set-up %.3f s on the %s\n",
+            const bool grid = ai.coarsening == SPK_AMG_COARSEN_GRID;
+            std::printf("  PC %s, %s): %d levels, block size %d, operator complexity %.4f, set-up %.3f s on the %s\n",
+                        grid ? "mg (grid coarsening, Galerkin" : "gamg (smoothed aggregation",
                         amg_active(k) ? "fieldsplit_0" : "K = A", ai.levels, ai.block_size, ai.operator_complexity, ai.setup_seconds,
                         ai.setup == SPK_AMG_SETUP_DEVICE ? "device" : "host");
-            std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
-                        o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
-                        o.nsmooths, o.coarse_eq_limit);
+            if (grid)
+                std::printf("    smoother %s x %d, transfers %s, coarse_eq_limit %d\n",
+                            o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its,
+                            o.transfer == SPK_AMG_TRANSFER_STORED ? "stored (CSR)" : "matrix-free", o.coarse_eq_limit);
+            else
+                std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
+                            o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
+                            o.nsmooths, o.coarse_eq_limit);
             int32_t refreshed = 0;
             double secs = 0.0;
             if (k->amg_reuse[amg_active(k)] && spk_get_amg_reuse_info(k->ctx, &refreshed, &secs) == SPK_OK)
                 std::printf("    reuse_interpolation: the last set-up %s the hierarchy in %.3f s\n", refreshed ? "refreshed" : "built", secs);
-            for (int l = 0; l < ai.levels; ++l)
-                std::printf("    level %d: rows %d nnz %lld lambda_max %.6g%s\n", l, ai.rows[l], (long long)ai.nnz[l],
+            for (int l = 0; l < ai.levels; ++l) {
+                char dims[64] = "";
+                if (grid) std::snprintf(dims, sizeof dims, " grid %d x %d x %d", ai.dims[l][0], ai.dims[l][1], ai.dims[l][2]);
+                std::printf("    level %d:%s rows %d nnz %lld lambda_max %.6g%s\n", l, dims, ai.rows[l], (long long)ai.nnz[l],
                             ai.lambda_max[l], l + 1 == ai.levels ? " (coarse: dense Cholesky inverse)" : "");
+            }
         }
     }
     return SPK_OK;

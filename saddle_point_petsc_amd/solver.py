@@ -34,14 +34,19 @@ def default_opts(**kw):
 AMG_CHEBYSHEV, AMG_RICHARDSON = 0, 1
 AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV = 0, 1, 2, 3
 AMG_SETUP_HOST, AMG_SETUP_DEVICE = 0, 1
+AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID = 0, 1
+AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED = 0, 1
 SPK_ERR_ARG = -1   # include/spk.h
 _SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
 _SETUPS = {"host": AMG_SETUP_HOST, "device": AMG_SETUP_DEVICE}
+_COARSENINGS = {"aggregation": AMG_COARSEN_AGGREGATION, "grid": AMG_COARSEN_GRID}
+_TRANSFERS = {"matrixfree": AMG_TRANSFER_MATRIX_FREE, "stored": AMG_TRANSFER_STORED}
 
 
 def amg_opts(**kw):
     """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
-    'host' / 'device')."""
+    'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored'; grid=(mx, my[, mz]) are the
+    nodes per side that grid coarsening halves)."""
     o = AmgOpts()
     lib.spk_default_amg_opts(C.byref(o))
     for k, v in kw.items():
@@ -51,8 +56,17 @@ def amg_opts(**kw):
             v = _SMOOTHERS[v]
         if k == "setup" and isinstance(v, str):
             v = _SETUPS[v]
+        if k == "coarsening" and isinstance(v, str):
+            v = _COARSENINGS[v]
+        if k == "transfer" and isinstance(v, str):
+            v = _TRANSFERS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
+        if k == "grid":
+            v = tuple(int(m) for m in v)
+            if len(v) not in (2, 3):
+                raise TypeError("grid takes (mx, my) or (mx, my, mz)")
+            v = (C.c_int32 * 3)(*(v + (1,) * (3 - len(v))))
         setattr(o, k, v)
     return o
 
@@ -60,6 +74,7 @@ def amg_opts(**kw):
 def amg_opts_dict(o):
     d = {k: getattr(o, k) for k, _ in AmgOpts._fields_}
     d["esteig"] = tuple(o.esteig)
+    d["grid"] = tuple(o.grid)
     return d
 
 
@@ -67,7 +82,8 @@ def _amg_info(ai):
     L = ai.levels
     return dict(levels=L, block_size=ai.block_size, rows=list(ai.rows[:L]), nnz=list(ai.nnz[:L]),
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
-                setup_seconds=ai.setup_seconds, setup=ai.setup)
+                setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
+                dims=[tuple(ai.dims[l]) for l in range(L)])
 
 
 def _amg_matrix(fn, level, which):
@@ -541,6 +557,17 @@ class Context:
         self._chk(lib.spk_get_amg_reuse_info(self.h, C.byref(r), C.byref(t)))
         return dict(refreshed=bool(r.value), seconds=t.value)
 
+    def debug_amg_transfer(self, level, which, a, b, stored=False):
+        """Test hook (spk_debug_amg_transfer): one transfer of a level alone.  which 'prolong': b + P a (a: coarse, b: fine);
+        'restrict': R (a - b) (both fine).  The fine vectors may be longer than the level (a padded vector)."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        info = self.amg_info()
+        pro = which == "prolong"
+        out = np.zeros(b.size if pro else info["rows"][level + 1])
+        self._chk(lib.spk_debug_amg_transfer(self.h, level, 0 if pro else 1, 1 if stored else 0, b.size, a, b, out))
+        return out
+
     def amg_aggregates(self, level):
         """The aggregate of every node of a level of the context's hierarchy (-1: isolated)."""
         n = C.c_int32()
@@ -836,6 +863,11 @@ class KSP:
         lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
         self._n = nl.value + (B.nrows if B is not None else 0)
         return f[:nl.value] if with_rhs else None
+
+    def setGrid(self, mx, my, mz=1):
+        """The node grid behind the operator of setOperators (SpkKSPSetGrid; the role of KSPSetDM): what -pc_type mg
+        coarsens.  setOperatorsLaplace / setOperatorsLaplace3D set it themselves."""
+        self._chk(lib.SpkKSPSetGrid(self.h, mx, my, mz))
 
     def setFromOptions(self, options):
         """options: PETSc-style string or list, e.g. '-ksp_type fgmres -ksp_rtol 1e-8'."""

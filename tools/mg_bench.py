@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""Grid-coarsening multigrid (-pc_type mg) against the smoothed aggregation it leaves untouched (-pc_type gamg) on one
+GPU, in one process:
+    python tools/mg_bench.py [--grids 257 513 1025] [--reps 5] [--out profiles/FILE.jsonl]
+K = A, FGMRES(30) to rtol 1e-8, both hierarchies built on the device.  Per grid one context per preconditioner; after one
+warm-up round, --reps alternating rounds of set-up -> solve -> V-cycle timing (spk_pc_apply back to back on device
+vectors).  Per row: levels, operator complexity, and median (min..max) of the V-cycle, the solve, the set-up and set-up +
+solve, with the iterations.  The bar, checked at the largest grid: mg's solve median plus its spread (max - min) at or
+below gamg's solve median; the exit status is 1 when it is missed.  Then the saddle system with Schur FULL and the exact
+Schur complement (schur_pre="full"), the same comparison, reported only.
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mg_bench.py --transfers [--grid 1025]
+    python tools/mg_bench.py --transfers-report DIR [--grid 1025] [--out profiles/FILE.jsonl]
+The two transfers of level 0 alone, through the test hook (one launch per call, on fresh copies of the same vectors):
+after one warm-up round, --reps alternating rounds of the matrix-free prolongation, the stored one (amg_csr_kernel<3> on
+P), the matrix-free restriction and the stored one (amg_csr_kernel<2> on R), all on the hierarchy of one context.  The
+report reads the kernel trace of that run: median (min..max) per kernel, the fraction of the byte model
+(prolongation: y read + y written + e read; restriction: b + t read + b_c written) at the HBM peak, and the bar --
+matrix-free median plus its spread below the stored median -- with exit status 1 when it is missed."""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+PEAK = 8.0e12   # HBM bytes per second
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--grids", type=int, nargs="+", default=[257, 513, 1025])
+ap.add_argument("--grid", type=int, default=1025, help="--transfers / --transfers-report: nodes per side")
+ap.add_argument("--rtol", type=float, default=1e-8)
+ap.add_argument("--reps", type=int, default=5, help="alternating rounds after the warm-up round")
+ap.add_argument("--no-saddle", action="store_true", help="leave out the saddle rows")
+ap.add_argument("--transfers", action="store_true", help="only launch the level-0 transfers (for a kernel trace)")
+ap.add_argument("--transfers-report", metavar="DIR", help="read the kernel trace a --transfers run left under DIR")
+ap.add_argument("--out", help="append the JSON lines to this file too")
+a = ap.parse_args()
+
+
+def emit(row):
+    line = json.dumps(row)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(line + "\n")
+
+
+def mmm(v, scale=1.0, digits=6):
+    return dict(median=round(float(np.median(v)) * scale, digits), min=round(min(v) * scale, digits), max=round(max(v) * scale, digits))
+
+
+def transfer_models(grid):
+    n, nc = 2 * grid * grid, 2 * ((grid + 1) // 2) ** 2
+    return dict(prolong=8 * (2 * n + nc), restrict=8 * (2 * n + nc))
+
+
+if a.transfers_report:
+    names = dict(prolong_matrixfree="amg_prolong_grid_kernel", restrict_matrixfree="amg_restrict_grid_kernel",
+                 prolong_stored="amg_csr_kernel<3>", restrict_stored="amg_csr_kernel<2>")
+    files = glob.glob(os.path.join(a.transfers_report, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        sys.exit(f"no *kernel_trace.csv under {a.transfers_report}")
+    rows = []
+    for fn in files:
+        with open(fn, newline="") as fh:
+            rows += list(csv.DictReader(fh))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    model = transfer_models(a.grid)
+    us = {}
+    for key, sub in names.items():
+        d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if sub in r["Kernel_Name"]]
+        if len(d) < 2:
+            sys.exit(f"{len(d)} launches of {sub} in the trace: run --transfers under the profiler first")
+        us[key] = d[1:]   # the first launch of each is the warm-up round
+    ok = True
+    for what in ("prolong", "restrict"):
+        mf, st = us[what + "_matrixfree"], us[what + "_stored"]
+        met = float(np.median(mf)) + (max(mf) - min(mf)) < float(np.median(st))
+        ok = ok and met
+        emit(dict(mode="transfers", grid=a.grid, level=0, kernel=what, launches=len(mf), model_bytes=model[what],
+                  matrixfree_us=mmm(mf, digits=2), stored_us=mmm(st, digits=2),
+                  matrixfree_frac_peak=round(model[what] / (float(np.median(mf)) * 1e-6) / PEAK, 3),
+                  stored_over_matrixfree=round(float(np.median(st) / np.median(mf)), 2),
+                  bar="matrix-free median + spread < stored median", bar_met=bool(met)))
+    sys.exit(0 if ok else 1)
+
+import saddle_point_petsc_amd as S  # noqa: E402
+
+if a.transfers:
+    g = a.grid
+    A, _ = S.AssembleOperator_Laplace(g, g)
+    rng = np.random.default_rng(g)
+    with S.Context(0) as c:
+        c.set_block(S.BLOCK_A00, A)
+        c.pc_setup(S.PC_JACOBI, amg=dict(coarsening="grid", grid=(g, g), setup="device"))
+        info = c.amg_info()
+        nf, nc = info["rows"][0], info["rows"][1]
+        e, y, b, t = rng.standard_normal(nc), rng.standard_normal(nf), rng.standard_normal(nf), rng.standard_normal(nf)
+        for rep in range(-1, a.reps):
+            for stored in (False, True):
+                c.debug_amg_transfer(0, "prolong", e, y, stored=stored)
+            for stored in (False, True):
+                c.debug_amg_transfer(0, "restrict", b, t, stored=stored)
+    print(json.dumps(dict(mode="transfers-launched", grid=g, rows=[nf, nc], rounds=a.reps + 1)), flush=True)
+    sys.exit(0)
+
+KINDS = dict(mg=lambda g: dict(coarsening="grid", grid=(g, g), setup="device"), gamg=lambda g: dict(setup="device"))
+
+
+def compare(system, g, A, B, rhs):
+    """one context per preconditioner, alternating rounds; returns {kind: solve seconds}"""
+    pc, pre = (S.PC_JACOBI, "selfp") if B is None else (S.PC_SCHUR, "full")
+    ctxs, t = {}, {}
+    for kind in KINDS:
+        c = S.Context(0)
+        c.set_block(S.BLOCK_A00, A)
+        if B is not None:
+            c.set_block(S.BLOCK_A10, B)
+        ctxs[kind] = c
+        t[kind] = dict(setup=[], solve=[], vcycle=[], its=[], res=[])
+    for rep in range(-1, a.reps):   # -1: the warm-up round, not counted
+        for kind, c in ctxs.items():
+            c.pc_setup(pc, S.SCHUR_FULL, amg=KINDS[kind](g), schur_pre=pre)
+            x, info = c.fgmres(rhs, rtol=a.rtol, max_it=500, restart=30)
+            assert info["reason"] == 2, (kind, info["reason"])
+            vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            r = t[kind]
+            r["setup"].append(c.amg_info()["setup_seconds"])
+            r["solve"].append(info["solve_seconds"])
+            r["vcycle"].append(vc_ms * 1e-3)
+            r["its"].append(info["its"])
+            r["res"].append(float(np.linalg.norm(rhs - c.mult(x)) / np.linalg.norm(rhs)))
+    for kind, c in ctxs.items():
+        info, r = c.amg_info(), t[kind]
+        emit(dict(mode="solve", system=system, grid=g, pc=kind, solver="fgmres(30)", rtol=a.rtol, reps=a.reps, levels=info["levels"],
+                  rows=info["rows"], operator_complexity=round(info["operator_complexity"], 4), its=sorted(set(r["its"])),
+                  true_rel_res=max(r["res"]), pc_apply_us=mmm(r["vcycle"], 1e6, 1), solve_ms=mmm(r["solve"], 1e3, 3),
+                  setup_ms=mmm(r["setup"], 1e3, 3),
+                  setup_plus_solve_ms=mmm([u + v for u, v in zip(r["setup"], r["solve"])], 1e3, 3)))
+        c.close()
+    return {kind: t[kind]["solve"] for kind in KINDS}
+
+
+met = True
+for g in a.grids:
+    A, f = S.AssembleOperator_Laplace(g, g)
+    s = compare("A", g, A, None, f)
+    if g == max(a.grids):
+        mg, gamg = s["mg"], s["gamg"]
+        met = float(np.median(mg)) + (max(mg) - min(mg)) <= float(np.median(gamg))
+        emit(dict(mode="bar", system="A", grid=g, bar="mg solve median + spread <= gamg solve median",
+                  mg_solve_ms=mmm(mg, 1e3, 3), gamg_solve_ms=mmm(gamg, 1e3, 3), bar_met=bool(met)))
+    if not a.no_saddle:
+        B, gg = S.AssembleOperator_Constraints(g, g)
+        compare("saddle_full_exact_schur", g, A, B, np.concatenate([f, gg]))
+sys.exit(0 if met else 1)
