@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from test_stream_edges_cpu import long_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +46,13 @@ def test_spmv_A_block_bitwise(spk, oracle, mx, my):
 
 def test_spmv_irregular_rows(spk, oracle):
     """Ragged CSR: empty rows, rows longer than one LDS tile (long-row path),
-    unsorted columns, tile boundaries at odd offsets."""
+    unsorted columns, tile boundaries at odd offsets.  Which rows take the long-row path is long_csr's rule (a tile
+    starts at a 4-entry boundary: not the length alone), with rows of 2047, 2048 and 2049 entries at the switch."""
     rng = np.random.default_rng(7)
     n = 3000
     lens = rng.integers(0, 40, n)
     lens[5] = 0; lens[6] = 0; lens[100] = 5000; lens[101] = 4097; lens[2999] = 1
+    lens[700] = 2047; lens[1400] = 2048; lens[2100] = 2049
     rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     colidx = rng.integers(0, n, rowptr[-1]).astype(np.int32)
     val = rng.standard_normal(rowptr[-1])
@@ -59,7 +62,9 @@ def test_spmv_irregular_rows(spk, oracle):
         c.set_block(spk.BLOCK_A00, A)
         y = c.mult(x)
     y_ref = oracle.spmv(A, x)
-    short = lens <= 4096
+    short = ~long_csr(rowptr)
+    assert not short[[100, 101, 2100]].any() and (short | (lens >= 2046)).all()
+    assert np.array_equal(short[[700, 1400]], [rowptr[700] % 4 < 2, rowptr[1400] % 4 < 1])
     assert np.array_equal(y[short], y_ref[short])                      # CSR-order sums: bitwise
     assert np.allclose(y[~short], y_ref[~short], rtol=1e-12, atol=1e-12)  # long rows: tree order
 
