@@ -530,6 +530,9 @@ int spk_get_sizes(const spk_ctx *ctx, int64_t *n_global, int32_t *n_local, int32
  * their pattern and columns pair up, as for a dof-2 DMDA; SPK_SPMV_FORMAT=csr forces CSR).
  * layout_bytes = bytes one SpMV reads and writes in that layout (matrix + x + y). */
 int spk_get_spmv_info(const spk_ctx *ctx, int32_t *format, int64_t *layout_bytes);
+/* Test hook: the row-type layout of the A block as set up. out[0..11] = ok, bs, nbrows, kmax, ntype, nclass, lds_bytes,
+ * uniform, straddle, uniform3, product kernel (0 plain, 1 pipelined 2x2, 2 pipelined 3x3), chunks_per_wg.  ok = 0: the rest is 0. */
+int spk_debug_dict_layout(const spk_ctx *ctx, int32_t out[12]);
 /* Formats 3 / 4: ROW TYPES + DEVIATION CODES over the 2x2 / 3x3 blocks (the default wherever the layout exists).  On the
  * reference's uniform grid (Discretization.c:25; one element matrix for all elements, :293-332) the assembled entries
  * scatter by rounding noise around a handful of ideal values (:96-128: a Jacobian formed from coordinates): A holds a few

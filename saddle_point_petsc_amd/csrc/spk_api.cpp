@@ -506,6 +506,18 @@ int spk_get_spmv_info(const spk_ctx *c, int32_t *format, int64_t *layout_bytes)
     return SPK_OK;
 }
 
+int spk_debug_dict_layout(const spk_ctx *c, int32_t out[12])
+{
+    if (!c || !out) return SPK_ERR_ARG;
+    std::fill(out, out + 12, 0);
+    const spk::DictDev &D = c->Adict;
+    if (c->spmv_format == 0 || !D.ok) return SPK_OK;
+    const int32_t v[12] = {1, D.bs, D.nbrows, D.kmax, D.ntype, D.nclass, D.lds_bytes, D.uniform ? 1 : 0, D.straddle ? 1 : 0, D.uniform3,
+                           spk::k::dict_product_kernel(D), spk::k::dict_chunks_per_wg(D)};
+    std::copy(v, v + 12, out);
+    return SPK_OK;
+}
+
 int spk_get_iteration_form(const spk_ctx *c, int32_t *form, int32_t *single_reduce)
 {
     if (!c) return SPK_ERR_ARG;

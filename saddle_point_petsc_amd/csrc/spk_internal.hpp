@@ -461,6 +461,9 @@ bool spmv_dict3(const DictDev &A, const double *x, double *y, const CsrDev *bt, 
                 bool accumulate, const OffDiag *od, const GivensRider *rider);
 bool jacobi_sweep_f32_dict3(const DictDev &A, const float *d32, float omega, const float *x32, const float *yin, float *yout,
                             const int32_t *done, hipStream_t s);
+bool dict3_pipelined(const DictDev &A);     // the predicate of both
+int dict_product_kernel(const DictDev &A);   // 0 plain, 1 pipelined 2x2, 2 pipelined 3x3 (single rank, no off-rank columns)
+int dict_chunks_per_wg(const DictDev &A);
 void dict_class_stats(int bs, const double *v0, const double *v1, int64_t ldp, int64_t nblocks, const int32_t *rep_of_id, int nid,
                       const int32_t *slot2id, int32_t *slot, double *cls, int32_t *gexp, unsigned long long *dmax, int32_t *bad,
                       hipStream_t s);

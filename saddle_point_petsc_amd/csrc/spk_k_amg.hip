@@ -106,6 +106,7 @@ __global__ __launch_bounds__(kThreads) void amg_cheb_dict2_kernel(DictArgs d, co
         const int2 *te = tent + (size_t)tc * d.kmax;
         constexpr int G = 10;   // a 2-D interior block row whole: five 16-byte code loads + nine gathers of y in flight
         for (int k0 = 0; k0 < len; k0 += G) {
+#pragma clang fp contract(off)  // the sums of spmv_dict_kernel: every product rounded on its own (the update below is amg_cheb_vec's)
             int2 e[G];
             u64 w0[G];
             double2 yv[G];

@@ -295,6 +295,18 @@ __global__ __launch_bounds__(kThreads) void spmv_dict2_kernel(DictArgs d, const 
     }
 }
 
+// row types of the 9-point stencil: the pipelined kernel
+static bool dict2_pipelined(const DictDev &A) { return A.bs == 2 && A.kmax == 9 && A.nbrows < (1 << 27) && !A.straddle; }
+
+// which product kernel a launch on this layout takes (spk_debug_dict_layout): 0 plain, 1 pipelined 2x2, 2 pipelined 3x3 --
+// the launchers' own predicates, in their order -- and the chunks a workgroup of the plain kernels walks
+int dict_product_kernel(const DictDev &A) { return dict3_pipelined(A) ? 2 : dict2_pipelined(A) ? 1 : 0; }
+int dict_chunks_per_wg(const DictDev &A)
+{
+    int grid = 0;
+    return dict_args(A, &grid).chunks_per_wg;
+}
+
 void spmv_dict(const DictDev &A, const double *x, double *y, const CsrDev *bt, const double *lam, const int32_t *done,
                hipStream_t s, bool accumulate, const OffDiag *odp, const GivensRider *rider)
 {
@@ -305,8 +317,7 @@ void spmv_dict(const DictDev &A, const double *x, double *y, const CsrDev *bt, c
     const DictArgs d = dict_args(A, &grid);
     // LDS: the tables; a launch with a rider needs the rider's scratch in block 0
     const size_t lds = std::max((size_t)A.lds_bytes, p.rider_lds);
-    // row types of the 9-point stencil: the pipelined kernel
-    const bool pipelined = A.bs == 2 && A.kmax == 9 && A.nbrows < (1 << 27) && !A.straddle;
+    const bool pipelined = dict2_pipelined(A);
     dispatch_product(p.acc, p.ride, p.bt, [&](auto acc, auto ride, auto btf) {
         constexpr bool ACC = acc.value, RIDE = ride.value, BTF = btf.value;
         auto launch = [&](auto kern) {

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void spmv_dict3_kernel(DictArgs d, const 
     dict3_two_stage<Dict3Stage<ACC>>(d, c0, c1, tA, issue, compute);
 }
 
-static bool dict3_applies(const DictDev &A)
+bool dict3_pipelined(const DictDev &A)
 {
     // SPK_DICT3_PIPELINE=0 / 1: never / at any size (tests run both forms on small grids); read at every call
     const char *env = getenv("SPK_DICT3_PIPELINE");
@@ -162,7 +162,7 @@ static DictArgs dict3_args(const DictDev &A, int *grid)
 bool spmv_dict3(const DictDev &A, const double *x, double *y, const CsrDev *bt, const double *lam, const int32_t *done,
                 hipStream_t s, bool accumulate, const OffDiag *odp, const GivensRider *rider)
 {
-    if (!dict3_applies(A) || A.nbrows == 0) return false;
+    if (!dict3_pipelined(A) || A.nbrows == 0) return false;
     int grid = 0;
     const DictArgs d = dict3_args(A, &grid);
     const ProductLaunch p = make_product_launch(bt, lam, odp, rider, done, accumulate);
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void jacobi_sweep_f32_dict3_kernel(DictAr
 bool jacobi_sweep_f32_dict3(const DictDev &A, const float *d32, float omega, const float *x32, const float *yin, float *yout,
                             const int32_t *done, hipStream_t s)
 {
-    if (!dict3_applies(A) || A.nbrows == 0 || (int64_t)A.nbrows * 12 >= (1ll << 31)) return false;
+    if (!dict3_pipelined(A) || A.nbrows == 0 || (int64_t)A.nbrows * 12 >= (1ll << 31)) return false;
     int grid = 0;
     const DictArgs d = dict3_args(A, &grid);
     if (A.uniform3 == 1)

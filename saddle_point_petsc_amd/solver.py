@@ -590,6 +590,14 @@ class Context:
         lib.spk_get_spmv_info(self.h, C.byref(fmt), C.byref(b))
         return dict(format={0: "csr", 1: "bcsr2x2", 2: "bcsr3x3", 3: "dict2x2", 4: "dict3x3"}[fmt.value], layout_bytes=b.value)
 
+    def dict_layout(self):
+        """The row-type layout of the A block as set up (spk_debug_dict_layout); ok = 0: the blocked / CSR kernels run."""
+        out = (C.c_int32 * 12)()
+        self._chk(lib.spk_debug_dict_layout(self.h, out))
+        names = ("ok", "bs", "nbrows", "kmax", "ntype", "nclass", "lds_bytes", "uniform", "straddle", "uniform3", "product_kernel",
+                 "chunks_per_wg")
+        return dict(zip(names, (int(v) for v in out)))
+
     def iteration_form(self):
         """(form, single_reduce) of the last fgmres on this context: the SPK_ITER_* actually run, -1 = step-by-step path."""
         f, sr = C.c_int32(), C.c_int32()
