@@ -138,8 +138,20 @@ typedef struct spk_opts {
                                5 (same algorithm; spk_get_iteration_form reports what ran).
                                Measured us per iteration, forms 1 / 5: 1/8 slab of 1024^2 47.9 / 43.3,
                                512^2 71.8 / 66.0, 1024^2 219.7 / 209.2. */
-    int32_t reserved;
+    int32_t basis_precision; /* -spk_basis_precision: how the Krylov basis V is STORED (the arithmetic is FP64 either way):
+                               SPK_BASIS_DOUBLE (0, default) | SPK_BASIS_SINGLE (1): a compressed basis -- the un-normalised
+                               vectors V~_j are kept as float(w') with their FP64 scale factor beside them, half the bytes
+                               of the two Gram-Schmidt passes and of the basis itself; w~, z~, c~ and Z~ stay FP64.  Runs
+                               form 5 only (AUTO, 6, 7 resolve to 5) on one rank; everything that is not form 5 (MGS, CGS
+                               refinement, single_reduce, fused = 0, restart + 2 m > 62, an odd local size, V-cycles, FP32
+                               inner sweeps, a dense Schur complement, Schur DIAG / UPPER, no PC, several ranks) is refused with SPK_ERR_UNSUPPORTED
+                               before anything is enqueued.  Two rules keep the answer honest: a convergence or max_it seen
+                               by the recurrence only ends the cycle, the true residual at the restart decides; and a
+                               cycle also ends once the recurrence residual is <= 2^-20 of the cycle's starting residual
+                               (below that the stored vectors carry rounding noise only).  spk_get_basis_info reports
+                               what ran. */
 } spk_opts;
+enum { SPK_BASIS_DOUBLE = 0, SPK_BASIS_SINGLE = 1 };
 enum { SPK_ITER_AUTO = 0, SPK_ITER_FOUR_LAUNCH = 1,
        SPK_ITER_TWO_LAUNCH = 2, SPK_ITER_THREE_LAUNCH = 3, SPK_ITER_BA = 4,   /* retired: run as SPK_ITER_UNNORM */
        SPK_ITER_UNNORM = 5, SPK_ITER_RESIDENT = 6, SPK_ITER_GS_FUSED = 7,
@@ -512,6 +524,10 @@ int spk_pipecgrr_set_tau(spk_ctx *ctx, double tau);
  * beyond 62, MGS or CGS refinement on a fusable preconditioner report SPK_ITER_FOUR_LAUNCH: the head kernel runs);
  * *single_reduce = 1 when the single-reduction mode ran.  For byte models (bench.py). */
 int spk_get_iteration_form(const spk_ctx *ctx, int32_t *form, int32_t *single_reduce);
+/* The basis of the last spk_fgmres on this context: SPK_BASIS_* it ran with and the bytes allocated for V (restart + 2
+ * vectors of ld doubles, or restart + 1 vectors of ld floats; the two FP64 work vectors of a single-precision solve are
+ * not part of it).  -1 and 0 before the first solve.  Either pointer may be NULL. */
+int spk_get_basis_info(const spk_ctx *ctx, int32_t *precision, int64_t *basis_bytes);
 
 /* ---- device vectors for callers that keep b/x resident in HBM --------------- */
 /* (a PCSHELL/MATSHELL glue over device Vecs, bench.py).  Zero-filled, length
@@ -596,6 +612,10 @@ typedef struct spk_debug_mdot_opts {
 } spk_debug_mdot_opts;
 /* out: nv + nv2 + 1 values (the dot products, then w.w) */
 int spk_debug_mdot(spk_ctx *ctx, const spk_debug_mdot_opts *o, const double *V, const double *V2, const double *w, double *out);
+/* The same over an FP32 basis (k::mdot_f32, what a -spk_basis_precision single solve launches): V holds floats (stride ld
+ * floats on the device), V2 and w stay FP64.  nv2 <= 8, nv + 2 nv2 <= 63.  out: nv + 2 nv2 + 1 values -- the dot products
+ * with w, w.w, then the nv2 plane values of the LAST vector of V (B D of the newest basis vector as stored). */
+int spk_debug_mdot_f32(spk_ctx *ctx, const spk_debug_mdot_opts *o, const float *V, const double *V2, const double *w, double *out);
 typedef struct spk_debug_maxpy_opts {
     int64_t n, n_dot, n_bd;
     double sign, pad;

@@ -65,7 +65,10 @@ int SpkKSPSetGrid(SpkKSP ksp, int mx, int my, int mz);
  * PETSc's KSPPIPECG) before it looks at the operators, and with a B block once they are set.  -ksp_type pipecgrr
  * (spk_pipecgrr, pipecg with residual replacement) follows the same rules, with "pipecgrr" in the messages, and takes
  * -spk_pipecgrr_tau <tau >= 0> (SPK_PIPECGRR_TAU_DEFAULT); -ksp_view prints tau and the replacements of the last
- * solve.  -ksp_type cg is not implemented and stays refused. */
+ * solve.  -ksp_type cg is not implemented and stays refused.
+ * -spk_basis_precision double (default) | single: how fgmres stores its Krylov basis (spk_opts.basis_precision; single:
+ * FP32 storage, FP64 arithmetic, iteration form 5 on one rank; any other value: SPK_ERR_ARG; -ksp_view shows it).  What a
+ * single-precision basis cannot run is refused by SpkKSPSolve with SPK_ERR_UNSUPPORTED. */
 int SpkKSPSetFromOptions(SpkKSP ksp, int argc, const char *const *argv);    /* KSPSetFromOptions :67 */
 int SpkKSPSetUp(SpkKSP ksp);                                                /* KSPSetUp       :68 */
 /* b, x: host vectors of n_local + m values ([u ; lambda]) */

@@ -28,7 +28,8 @@ class Opts(C.Structure):
         ("restart", C.c_int32), ("max_it", C.c_int32), ("rtol", C.c_double),
         ("abstol", C.c_double), ("dtol", C.c_double), ("guess_nonzero", C.c_int32),
         ("orthog", C.c_int32), ("check_every", C.c_int32), ("fused", C.c_int32),
-        ("cgs_refine", C.c_int32), ("single_reduce", C.c_int32), ("iteration_form", C.c_int32), ("reserved", C.c_int32),
+        ("cgs_refine", C.c_int32), ("single_reduce", C.c_int32), ("iteration_form", C.c_int32),
+        ("basis_precision", C.c_int32),
     ]
 
 
@@ -182,6 +183,7 @@ def _load():
     L.spk_debug_wave_sums.argtypes = [vp, C.c_int, f64p, f64p]
     L.spk_debug_vec_shape.argtypes = [vp, i64, i32p]
     L.spk_debug_mdot.argtypes = [vp, C.POINTER(DebugMdotOpts), vp, vp, f64p, f64p]
+    L.spk_debug_mdot_f32.argtypes = [vp, C.POINTER(DebugMdotOpts), vp, vp, f64p, f64p]
     L.spk_debug_maxpy.argtypes = [vp, C.POINTER(DebugMaxpyOpts), vp, f64p, f64p, vp, vp, vp, f64p, vp, vp]
     L.spk_debug_cycle_norm.argtypes = [vp, i64, i64, i64, i32, dbl, f64p, vp, vp, vp, f64p, vp]
     L.spk_debug_schur_w.argtypes = [vp, i64, i32, i32, i32, dbl, f64p, f64p, f64p, vp, vp, f64p]
@@ -237,6 +239,7 @@ def _load():
     L.spk_get_spmv_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.spk_debug_dict_layout.argtypes = [vp, C.POINTER(i32)]
     L.spk_get_iteration_form.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.spk_get_basis_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.spk_get_spmv_models.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]
     L.spk_time_kernel.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(dbl)]
     L.spk_partition_slab.argtypes = [i64, i64, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]

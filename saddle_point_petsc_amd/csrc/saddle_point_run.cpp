@@ -8,6 +8,7 @@
 //   saddle_point_run -da_grid_x 257 -da_grid_y 257 -ksp_type fgmres -ksp_rtol 1e-8 \
 //       -pc_type fieldsplit -pc_fieldsplit_type schur -pc_fieldsplit_schur_fact_type full \
 //       -ksp_converged_reason [-saddle 0] [-solution_view] [-no_vtk] [-spk_assembly host|device]
+//       [-spk_basis_precision double|single]
 //
 // The reference hard-codes Nx = Ny = 3 elements (main.c:14), i.e. a 4 x 4 node
 // grid; that is the default here too.  -saddle 0 solves A u = f alone, as the

@@ -526,6 +526,14 @@ int spk_get_iteration_form(const spk_ctx *c, int32_t *form, int32_t *single_redu
     return SPK_OK;
 }
 
+int spk_get_basis_info(const spk_ctx *c, int32_t *precision, int64_t *basis_bytes)
+{
+    if (!c) return SPK_ERR_ARG;
+    if (precision) *precision = c->last_basis;
+    if (basis_bytes) *basis_bytes = c->last_basis_bytes;
+    return SPK_OK;
+}
+
 int spk_get_spmv_models(const spk_ctx *c, int64_t *csr_bytes, int64_t *blocked_bytes, int64_t *dict_bytes, int32_t *npat,
                         int32_t *nblk)
 {
@@ -711,6 +719,37 @@ int spk_debug_mdot(spk_ctx *c, const spk_debug_mdot_opts *o, const double *V, co
     dbg_fill(dout, (size_t)k, SPK_DEBUG_MARKER);
     const int32_t *done = dbg_done(ddone, o->done);
     spk::k::mdot(dV.p, ld, o->nv, dw.p, n, o->n_dot, c->fin(dout.p), done, c->stream, o->nv2 ? dV2.p : nullptr, o->nv2, o->split);
+    SPK_HIP(hipStreamSynchronize(c->stream));
+    c->check_device_error();
+    SPK_HIP(hipMemcpy(out, dout.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost));
+    SPK_CATCH(c)
+}
+
+int spk_debug_mdot_f32(spk_ctx *c, const spk_debug_mdot_opts *o, const float *V, const double *V2, const double *w, double *out)
+{
+    SPK_TRY(c)
+    if (!o || !w || !out || o->n <= 0 || o->n_dot < 0 || o->n_dot > o->n || o->nv < 0 || o->nv2 < 0 || o->nv2 > 8 ||
+        o->nv + 2 * o->nv2 > spk::k::kMaxNv - 1 || (o->nv && !V) || (o->nv2 && !V2) || (o->split && (o->nv2 & 1)) || o->done > 1)
+        spk::fail(SPK_ERR_ARG, "spk_debug_mdot_f32: bad arguments");
+    c->ensure_scratch();
+    const int64_t n = o->n, ld = dbg_ld(n);
+    const int rows2 = o->split ? o->nv2 / 2 : o->nv2, k = o->nv + 2 * o->nv2 + 1;
+    spk::DevBuf<float> dV;
+    spk::DevBuf<double> dV2, dw, dout;
+    spk::DevBuf<int32_t> ddone;
+    {   // rows of n floats -> device rows of stride ld floats, entries [n, ld) = pad
+        dV.alloc_raw((size_t)ld * (size_t)std::max(o->nv, 1), 256);
+        std::vector<float> row((size_t)ld, (float)o->pad);
+        for (int i = 0; i < std::max(o->nv, 1); ++i) {
+            if (i < o->nv) std::memcpy(row.data(), V + (size_t)i * (size_t)n, sizeof(float) * (size_t)n);
+            SPK_HIP(hipMemcpy(dV.p + (size_t)ld * i, row.data(), sizeof(float) * (size_t)ld, hipMemcpyHostToDevice));
+        }
+    }
+    dbg_upload(dV2, V2, rows2, n, ld, o->pad);
+    dbg_upload(dw, w, 1, n, ld, o->pad);
+    dbg_fill(dout, (size_t)k, SPK_DEBUG_MARKER);
+    const int32_t *done = dbg_done(ddone, o->done);
+    spk::k::mdot_f32(dV.p, ld, o->nv, dw.p, n, o->n_dot, c->fin(dout.p), done, c->stream, o->nv2 ? dV2.p : nullptr, ld, o->nv2, o->split);
     SPK_HIP(hipStreamSynchronize(c->stream));
     c->check_device_error();
     SPK_HIP(hipMemcpy(out, dout.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost));

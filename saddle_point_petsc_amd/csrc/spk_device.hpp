@@ -119,6 +119,42 @@ __device__ __forceinline__ void st2nt(double *p, int64_t i2, double2 v)   // non
     t.y = v.y;
     __builtin_nontemporal_store(t, reinterpret_cast<dbl2v *>(p) + i2);
 }
+// an FP32 Krylov basis (-spk_basis_precision single): two floats where the FP64 kernels read a double2
+typedef float flt2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float2 ldf2s(const float *p, int64_t i2)   // streamed once: non-temporal 8-byte load
+{
+    const flt2v v = __builtin_nontemporal_load(reinterpret_cast<const flt2v *>(p) + i2);
+    float2 r;
+    r.x = v.x;
+    r.y = v.y;
+    return r;
+}
+__device__ __forceinline__ void stf2nt(float *p, int64_t i2, float2 v)   // non-temporal 8-byte store
+{
+    flt2v t;
+    t.x = v.x;
+    t.y = v.y;
+    __builtin_nontemporal_store(t, reinterpret_cast<flt2v *>(p) + i2);
+}
+// How kernel B reads the basis it is instantiated for: pair i2 and entry i of vector `vec` (V as IterB carries it)
+template <class BT>
+struct BasisElem {
+    using E2 = double2;
+    static __device__ __forceinline__ E2 ld(const double *V, size_t vec, int64_t ldv, int64_t i2) { return ld2s<true>(V + vec * ldv, i2); }
+    static __device__ __forceinline__ double at(const double *V, size_t vec, int64_t ldv, int64_t i) { return V[vec * ldv + i]; }
+};
+template <>
+struct BasisElem<float> {
+    using E2 = float2;
+    static __device__ __forceinline__ E2 ld(const double *V, size_t vec, int64_t ldv, int64_t i2)
+    {
+        return ldf2s(reinterpret_cast<const float *>(V) + vec * ldv, i2);
+    }
+    static __device__ __forceinline__ double at(const double *V, size_t vec, int64_t ldv, int64_t i)
+    {
+        return (double)reinterpret_cast<const float *>(V)[vec * ldv + i];
+    }
+};
 template <bool NT>
 __device__ __forceinline__ int4 ld4i(const int32_t *p)
 {
@@ -605,6 +641,13 @@ __device__ inline void givens_block_lds(const KrylovArrays &ka, int loc, const d
     if (reason > 0 && ka.tentative) {
         // single-reduction mode: ||w'|| came out of a difference that can sit in rounding noise, so the
         // recurrence is trusted to END THE CYCLE only; the restart's true residual decides (krylov_cycle_begin)
+        st->skip_iter = 1;
+        return;
+    }
+    if (ka.theta > 0.0 && (reason == SPK_DIVERGED_ITS || (!reason && rnorm <= ka.theta * st->beta))) {
+        // an FP32 basis: -ksp_max_it is confirmed on the true residual as well (the reported norm is then the true one),
+        // and a cycle whose recurrence residual has fallen to theta of its starting residual ends here -- the stored
+        // vectors carry rounding noise from there on (kBasisTheta)
         st->skip_iter = 1;
         return;
     }

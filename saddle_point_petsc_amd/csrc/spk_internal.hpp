@@ -315,6 +315,7 @@ struct KrylovState {
     double cnorm0;  // the norm the relative and the divergence tests refer to (||b|| or the initial residual)
     double inv_tt;  // 1/||w|| of the last orthogonalised vector (or 1/||r||)
     double tt;
+    double beta;    // the residual norm this restart cycle started from (the early-restart test of an FP32 basis)
 };
 
 // What the states of MINRES and pipelined CG share: the convergence words of KrylovState (converged_default) and the
@@ -514,6 +515,12 @@ void scatter_row(const int32_t *colidx, const double *val, int k0, int k1, const
                  double *dense, hipStream_t s);
 // out[i] = sum_r slots[r*ld + i] in rank order (local-group all-reduce)
 void sum_slots(const double *slots, int nslots, int ld, int count, double *out, hipStream_t s);
+// VecMDot over an FP32 basis (one rank, nv2 <= 8; basis vectors beyond 40 in a launch of their own): V holds floats of stride ldv floats, the
+// planes V2 (stride ld2 doubles) and w stay FP64; results as mdot's.  Always the streaming form.
+void mdot_f32(const float *V, int64_t ldv, int nv, const double *w, int64_t n, int64_t n_dot, const Finish &f,
+              const int32_t *done, hipStream_t s, const double *V2, int64_t ld2, int nv2, int split);
+// dst = float(src), n entries (V~_0 of a cycle on an FP32 basis)
+void cvt_basis_f32(const double *src, float *dst, int64_t n, const int32_t *done, hipStream_t s);
 // f.out[i] = V_i . w for i < nv, then V2_i . w for i < nv2 (second slab, same stride), then w.w
 void mdot(const double *V, int64_t ldv, int nv, const double *w, int64_t n, int64_t n_dot,
           const Finish &f, const int32_t *done, hipStream_t s, const double *V2 = nullptr, int nv2 = 0,
@@ -610,7 +617,14 @@ struct KrylovArrays {
     double *H, *cc, *ss, *rs, *nrs, *hcol, *hist, *tb;
     int32_t hist_cap, ldh;
     int32_t tentative;  // 1: the recurrence may end a cycle, only a true residual may end the solve
+    // > 0 (an FP32 basis, with tentative): -ksp_max_it seen by the recurrence is tentative too, and a cycle also ends once
+    // the recurrence residual is <= theta times the residual the cycle started from (kBasisTheta)
+    double theta;
 };
+// Early restart of a solve on an FP32 basis: FP32's unit round-off 2^-24 with 16x head-room.  Below theta * beta the stored
+// vectors carry rounding noise only (a strong preconditioner stalls near 1e-7 beta): the cycle ends, the true residual
+// of the restart takes over.  A named constant, not an option.
+constexpr double kBasisTheta = 1.0 / 1048576.0;   // 2^-20
 // where a reducer reports a partial that never arrived (execution failure, not a numerical one): the
 // context's sticky error word; the bound of the wait in 100 MHz ticks
 struct FinErr {
@@ -667,6 +681,9 @@ struct IterB {
     double *sc, *hbuf, *wl_out;
     KrylovArrays ka;
     int loc;
+    // an FP32 basis (iter_maxpy_uhead with b.w32): V points at floats (stride ldv floats), w~ stays FP64 in w and
+    // float(w') goes to w32 -- ||w'||^2 is taken from the ROUNDED values, z~ and c~ from the unrounded ones
+    float *w32;
     int defer_fin;       // publish the partials of ||w'||^2 and leave: the rider of the next product launch reduces them
     int dead_out;        // the cycle's last iteration: nobody reads w', z~, c~ (x += Z y takes Z_0 .. Z_{mk-1}, r comes from x): not stored
 };
@@ -993,7 +1010,11 @@ struct spk_ctx {
     int last_form = -1, last_single = 0;
 
     // Krylov workspace (sized by restart)
-    int ws_restart = -1;
+    int ws_restart = -1, ws_basis = -1;   // what V (or Vf and Vw) and Z are sized for
+    spk::DevBuf<float> Vf;       // the FP32 basis of a -spk_basis_precision single solve: restart + 1 vectors of ld floats
+    spk::DevBuf<double> Vw;      // its two FP64 work vectors: w~ and c~ in turn (and r at the restart)
+    int last_basis = -1;         // spk_get_basis_info
+    int64_t last_basis_bytes = 0;
     spk::DevBuf<double> V, Z, xsol, rhs, tmp;
     spk::DevBuf<double> basis_sc;    // scale factors of the un-normalised basis (forms 5, 6, 7)
     spk::DevBuf<double> res_P;       // resident cycle kernel: all-to-all buffer of the inner products

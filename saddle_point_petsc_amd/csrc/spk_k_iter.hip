@@ -29,9 +29,16 @@ namespace k {
 // keep (form 7 only, see KeepSet): the first tile takes w~, the parity planes and V_0 .. V_{KV-1} from the keep set; its
 // loads ahead of the scalar prologue are D^-1 and the first group behind the kept vectors.  Groups, slots past nv and
 // the order of every addition are those of the other tiles.
-template <int T, int G, int U, int MP, class Dots, class Keep = NoKeep>
+// BT = float (-spk_basis_precision single, b.w32): V~_0 .. V~_{nv-1} are read as floats (converted exactly), w' is formed in
+// FP64 as ever and stored as float(w') into w32, ||w'||^2 is the norm of the ROUNDED vector -- so that the scale factor
+// belongs to what the basis holds -- and z~, c~ come from the unrounded w' in registers (the method is flexible).
+template <int T, int G, int U, int MP, class Dots, class Keep = NoKeep, class BT = double>
 __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg, Dots dots, Keep *keep = nullptr)
 {
+    constexpr bool F32 = std::is_same<BT, float>::value;
+    static_assert(!F32 || !Keep::any, "the keep set holds FP64 operands");
+    using Basis = BasisElem<BT>;
+    using E2 = typename Basis::E2;
     constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
     static_assert(KV % G == 0, "whole groups of basis vectors are kept");
     const int32_t dn = __builtin_nontemporal_load(b.done);  // looked at behind the first loads (see mdot_ws16_kernel)
@@ -52,7 +59,8 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     constexpr bool PRE = U * (MP > 0 ? MP : 1) <= 16;  // planes of B D fetched ahead too, where the registers allow (not 512 x 4 x 8 rows)
     static_assert(KP == 0 || (PRE && KP <= NP / 2), "kept planes are parity planes fetched ahead");
     const bool kpl = KP > 0 && b.packed && m > 0;   // (as in mdot_tiles: the first tile's planes are in the keep set)
-    double2 wv[U], dv[U], pe[PRE ? NP : 1][U], t0[G][U], tdead;
+    double2 wv[U], dv[U], pe[PRE ? NP : 1][U], tdead;
+    E2 t0[G][U];
     int64_t idx[U];
     bool ok[U];
     int64_t tile = bx;
@@ -92,9 +100,8 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
 #pragma unroll
         for (int v = 0; v < G; ++v) {
             const bool live = v0 + v < nv;
-            const double *Vi = b.V + (size_t)(live ? v0 + v : 0) * b.ldv;
 #pragma unroll
-            for (int u = 0; u < U; ++u) t0[v][u] = ld2s<true>(Vi, live ? idx[u] : 0);
+            for (int u = 0; u < U; ++u) t0[v][u] = Basis::ld(b.V, (size_t)(live ? v0 + v : 0), b.ldv, live ? idx[u] : 0);
         }
     };
     bool have = is_main && tile * (T * U) < n2;
@@ -103,7 +110,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     // ---- scalars, derived by every workgroup from the reduced [h, q]; all their loads first
     double lamv = 0.0;
     const bool lam_mine = (int)threadIdx.x < nv * m;
-    if (lam_mine) lamv = b.V[(size_t)(threadIdx.x / m) * b.ldv + b.nl + (threadIdx.x % m)];
+    if (lam_mine) lamv = Basis::at(b.V, (size_t)(threadIdx.x / m), b.ldv, b.nl + (threadIdx.x % m));
     double wl = 0.0, sh = 1.0;
     if ((int)threadIdx.x < m) {
         wl = b.wl_in[threadIdx.x];
@@ -115,7 +122,12 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         const int i = threadIdx.x;
         sci = i < nv ? b.sc[i] : 0.0;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) tbv_pre[r] = (r < m && i < nv) ? b.tb[i * 8 + r] : 0.0;
+        for (int r = 0; r < 8; ++r) {
+            // an FP32 basis: B D of the newest vector AS STORED comes from MDot (behind w.w), not from the recurrence value
+            // the previous kernel B left for the unrounded w'
+            if (F32 && i == nv - 1) tbv_pre[r] = r < m ? b.dots[nv + m + 1 + r] : 0.0;
+            else tbv_pre[r] = (r < m && i < nv) ? b.tb[i * 8 + r] : 0.0;
+        }
         dots(i < nv ? i : -1, i < m ? nv + i : -1, hi_pre, qv_pre);
     }
     if (dn) return;
@@ -131,6 +143,11 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         const double qv = qv_pre * s_w;
         if (i < nv) hs[i] = ci;
         if ((int)blockIdx.x == scalar_wg && i < nv) b.hbuf[i] = hi;  // the Hessenberg column (reducer only)
+        if (F32 && (int)blockIdx.x == scalar_wg && i == nv - 1) {   // ... and kept for the iterations to come
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < m) b.tb[(size_t)i * 8 + r] = tbv_pre[r];
+        }
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             if (r < m) {  // uniform
@@ -141,7 +158,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         }
     }
     if (lam_mine) lam[threadIdx.x] = lamv;
-    for (int t = threadIdx.x + T; t < nv * m; t += T) lam[t] = b.V[(size_t)(t / m) * b.ldv + b.nl + (t % m)];
+    for (int t = threadIdx.x + T; t < nv * m; t += T) lam[t] = Basis::at(b.V, (size_t)(t / m), b.ldv, b.nl + (t % m));
     __syncthreads();
     if ((int)threadIdx.x < NP && MP > 0) {
         const int r = threadIdx.x;
@@ -175,7 +192,8 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             if (b.fact == SPK_SCHUR_FULL)
                 for (int q = 0; q < m; ++q) w1 -= b.gram[r * m + q] * ys[q];
             if (!b.dead_out) {
-                b.w[b.nl + r] = wraws[r];
+                if (F32) b.w32[b.nl + r] = (float)wraws[r];
+                else b.w[b.nl + r] = wraws[r];
                 b.zun[b.nl + r] = ys[r];
                 b.c[b.nl + r] = w1;
             }
@@ -185,7 +203,10 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         __syncthreads();
         double lam2 = 0.0;  // the multiplier entries' share of ||w'||^2 (rank 0 only)
         if (threadIdx.x == 0)
-            for (int r = 0; r < m; ++r) lam2 += b.lam_in_dot ? wraws[r] * wraws[r] : 0.0;
+            for (int r = 0; r < m; ++r) {
+                const double wr = F32 ? (double)(float)wraws[r] : wraws[r];   // (the norm of what the basis holds)
+                lam2 += b.lam_in_dot ? wr * wr : 0.0;
+            }
         if (b.defer_fin) {
             // un-normalised basis: nothing in the product launch that follows needs ||w'||^2 except its rider workgroup
             // (scale factor, Givens step), so the rider also REDUCES the partials (and all-reduces the sum) beside the
@@ -289,29 +310,28 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                 const double ai = v0 + v < nv ? -hs[v0 + v] : 0.0;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    wv[u].x += ai * t0[v][u].x;
-                    wv[u].y += ai * t0[v][u].y;
+                    wv[u].x += ai * (double)t0[v][u].x;
+                    wv[u].y += ai * (double)t0[v][u].y;
                 }
             }
         }
         for (int g0 = v0 + G; g0 < nv; g0 += G) {
-            double2 t[G][U];
+            E2 t[G][U];
             double ai[G];
 #pragma unroll
             for (int v = 0; v < G; ++v) {
                 const bool live = g0 + v < nv;
                 const int ic = live ? g0 + v : 0;
                 ai[v] = live ? -hs[ic] : 0.0;
-                const double *Vi = b.V + (size_t)ic * b.ldv;
 #pragma unroll
-                for (int u = 0; u < U; ++u) t[v][u] = ld2s<true>(Vi, live ? idx[u] : 0);
+                for (int u = 0; u < U; ++u) t[v][u] = Basis::ld(b.V, (size_t)ic, b.ldv, live ? idx[u] : 0);
             }
 #pragma unroll
             for (int v = 0; v < G; ++v) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    wv[u].x += ai[v] * t[v][u].x;
-                    wv[u].y += ai[v] * t[v][u].y;
+                    wv[u].x += ai[v] * (double)t[v][u].x;
+                    wv[u].y += ai[v] * (double)t[v][u].y;
                 }
             }
         }
@@ -320,8 +340,16 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             if (ok[u]) {
                 const int64_t i = idx[u];
                 double2 zz, cc;
-                nrm += wv[u].x * wv[u].x;
-                nrm += wv[u].y * wv[u].y;
+                float2 wf;
+                if (F32) {
+                    wf.x = (float)wv[u].x;   // round to nearest
+                    wf.y = (float)wv[u].y;
+                    nrm += (double)wf.x * (double)wf.x;
+                    nrm += (double)wf.y * (double)wf.y;
+                } else {
+                    nrm += wv[u].x * wv[u].x;
+                    nrm += wv[u].y * wv[u].y;
+                }
                 zz.x = wv[u].x * dv[u].x;
                 zz.y = wv[u].y * dv[u].y;
                 if (MP > 0 && b.fact == SPK_SCHUR_FULL) {
@@ -331,7 +359,8 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                 // streamed out past the L2 (non-temporal stores): nobody on this XCD reads them again before the kernel
                 // boundary writes them back anyway (same box, alternating: 512^2 60.6 -> 59.1 us per iteration, 1024^2 203.3 -> 202.1, 1/8 slab 39.3 -> 39.0)
                 if (!b.dead_out) {
-                    st2nt(b.w, i, wv[u]);
+                    if (F32) stf2nt(b.w32, i, wf);
+                    else st2nt(b.w, i, wv[u]);
                     st2nt(b.zun, i, zz);
                     if (MP > 0) {
                         cc.x = sv[u].x / dv[u].x;
@@ -394,14 +423,15 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         if (threadIdx.x == 0) b.out[0] = red[0] + lam[0];
     }
 }
-template <int T, int G, int U, int MP>
+template <int T, int G, int U, int MP, class BT = double>
 __global__ __launch_bounds__(T) void iter_maxpy_uhead_kernel(IterB b)
 {
     const int nhalo = b.sr.peer ? (2 * b.sr.nrecv + T - 1) / T : 0;
-    maxpy_uhead_tiles<T, G, U, MP>(b, b.gmain + nhalo, [&](int i, int j, double &a, double &c) {
+    auto dots = [&](int i, int j, double &a, double &c) {
         if (i >= 0) a = b.dots[i];
         if (j >= 0) c = b.dots[j];
-    });
+    };
+    maxpy_uhead_tiles<T, G, U, MP, decltype(dots), NoKeep, BT>(b, b.gmain + nhalo, dots);
 }
 
 int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial rows its norm is spread over (defer_fin)
@@ -422,6 +452,24 @@ int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial 
     if (b.nv + b.m > kMaxNv - 1) fail(SPK_ERR_ARG, "iter_maxpy_uhead: %d values exceed one reduction", b.nv + b.m);
 #define SPK_IB(TT, GG, UU, MPP) hipLaunchKernelGGL((iter_maxpy_uhead_kernel<TT, GG, UU, MPP>), dim3(grid), dim3(TT), 0, s, b)
     const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+    if (b.w32) {
+        // an FP32 basis: the same thread positions, so a basis load is 8 bytes per lane -- twice the vectors are loaded
+        // together instead (the same bytes in flight, the same registers as the FP64 groups)
+        if (b.sr.n || b.sr.peer || b.ar.P) fail(SPK_ERR_STATE, "iter_maxpy_uhead: an FP32 basis runs on one rank");
+#define SPK_IBF(TT, GG, UU, MPP) hipLaunchKernelGGL((iter_maxpy_uhead_kernel<TT, GG, UU, MPP, float>), dim3(grid), dim3(TT), 0, s, b)
+#define SPK_IBF_MP(MPP)                                     \
+    do {                                                    \
+        if (!thin) SPK_IBF(512, 8, 4, MPP);                 \
+        else if (U == 2) SPK_IBF(256, 16, 2, MPP);          \
+        else SPK_IBF(256, 16, 1, MPP);                      \
+    } while (0)
+        if (mp == 0) SPK_IBF_MP(0);
+        else if (mp == 4) SPK_IBF_MP(4);
+        else SPK_IBF_MP(8);
+#undef SPK_IBF_MP
+#undef SPK_IBF
+        return b.gmain;
+    }
     static const int deep = [] { const char *e = getenv("SPK_VEC_DEEP"); return e ? atoi(e) : 0; }();
     // thin forms: the whole basis in one group of loads where registers allow (see maxpy)
     const int g1 = !deep || b.nv <= 8 ? 8 : (b.nv <= 16 ? 16 : 32), g2 = !deep || b.nv <= 8 ? 8 : 16;

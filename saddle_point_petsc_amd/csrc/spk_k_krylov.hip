@@ -34,6 +34,7 @@ __global__ void krylov_init_kernel(KrylovArrays ka, spk_opts o, const double *bn
     st->rnorm0 = 0.0;
     st->inv_tt = 1.0;
     st->tt = 0.0;
+    st->beta = 0.0;
 }
 void krylov_init(const KrylovArrays &ka, const spk_opts &o, const double *bnorm2, hipStream_t s)
 {
@@ -49,6 +50,7 @@ __device__ __forceinline__ void cycle_begin_body(const KrylovArrays &ka, const d
     if (st->done) return;
     const double rnorm = sqrt(*nrm2);
     st->rnorm = rnorm;
+    st->beta = rnorm;
     if (st->its == 0) {
         // KSPConvergedDefault at iteration 0 (PETSc iterativ.c, as published): zero initial guess -> the
         // reference norm is the initial residual; -ksp_initial_guess_nonzero -> ||b||, or the initial

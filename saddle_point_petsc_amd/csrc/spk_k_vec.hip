@@ -475,6 +475,217 @@ void mdot(const double *V, int64_t ldv, int nv, const double *w, int64_t n, int6
 }
 
 // ---------------------------------------------------------------------------
+// VecMDot over an FP32 basis (-spk_basis_precision single): the nv basis vectors are floats, w~ and the planes of B D
+// stay FP64.  float -> double is exact, every product and every sum is FP64, the orders are fixed: the sums of a thread
+// tile by tile, the wave tree, the waves of a workgroup in order, final_reduce over the workgroups.
+// A thread keeps mdot_kernel's positions (one double2 of w~ per unroll step), so a basis load is 8 bytes per lane; the
+// bytes in flight are kept by loading EIGHT basis vectors together where mdot_kernel loads four (the same 32 x U
+// dwords per thread).  Always this streaming form, whatever the length (the wave-split forms are not built for it).
+// Accumulators: NG * 8 for the basis, 8 for the plane values (m <= 8), one for w.w, 8 for vnew.
+// vnew (the newest basis vector V~_{nv-1}, with planes): its products with the planes, B D V~_{nv-1} of the vector AS STORED,
+// come out behind w.w.  Kernel B's identity B D w' = q - sum_i c_i (B D V~_i) needs B D of exactly the vectors it
+// subtracts; the value kernel B itself left in tb[] belongs to the unrounded w'.  The planes are in registers here
+// anyway: the price is one more basis load per tile.
+// ---------------------------------------------------------------------------
+template <int NG, int T, int U>
+__global__ __launch_bounds__(T) void mdot_f32_kernel(const float *__restrict__ V, int64_t ldv, int nv,
+                                                     const double *__restrict__ V2, int64_t ldp, int nv2, int split,
+                                                     const float *__restrict__ vnew, const double *__restrict__ w, int64_t n2, int64_t n_dot,
+                                                     double *__restrict__ partials, int with_ww, double *__restrict__ out,
+                                                     FinErr fe, const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    constexpr int NB = NG * 8, NA = NB + 17, NW = NB + 8, W = T / kWave, TILE2 = T * U, G = 8;
+    __shared__ double lds[(W * NA > T) ? W * NA : T];
+    double acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) acc[i] = 0.0;
+    const int rows2 = split ? (nv2 + 1) / 2 : nv2;   // planes to stream
+
+    for (int64_t tile = blockIdx.x; tile * TILE2 < n2; tile += gridDim.x) {
+        double2 wv[U];
+        int64_t idx[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            idx[u] = tile * TILE2 + u * T + threadIdx.x;
+            ok[u] = idx[u] < n2;
+            if (ok[u]) {
+                wv[u] = ld2(w, idx[u]);
+                if (2 * idx[u] >= n_dot) wv[u].x = 0.0;
+                if (2 * idx[u] + 1 >= n_dot) wv[u].y = 0.0;
+            } else {
+                wv[u].x = wv[u].y = 0.0;
+                idx[u] = 0;  // safe address, zero weight
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[NW] += wv[u].x * wv[u].x + wv[u].y * wv[u].y;
+#pragma unroll
+        for (int g0 = 0; g0 < NB; g0 += G) {
+            if (g0 < nv) {  // wave-uniform
+                float2 a[G][U];
+#pragma unroll
+                for (int v = 0; v < G; ++v) {
+                    // a slot past nv loads ONE broadcast address of vector 0 (weight 0): branch-free, no bandwidth
+                    const bool live = g0 + v < nv;
+                    const float *Vi = V + (size_t)(live ? g0 + v : 0) * ldv;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) a[v][u] = ldf2s(Vi, live ? idx[u] : 0);
+                }
+#pragma unroll
+                for (int v = 0; v < G; ++v) {
+                    double d = 0.0;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) d += (double)a[v][u].x * wv[u].x + (double)a[v][u].y * wv[u].y;
+                    // (a dead slot read finite or not: it is never added)
+                    if (g0 + v < nv) acc[g0 + v] += d;
+                }
+            }
+        }
+        // the planes of B D (FP64), four together: dense row r -> value r; parity plane q -> values 2q (even entries)
+        // and 2q + 1 (odd entries)
+#pragma unroll
+        for (int r0 = 0; r0 < 8; r0 += 4) {
+            if (r0 < rows2) {  // wave-uniform
+                double2 e[4][U], vn[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    vn[u].x = vn[u].y = 0.0;
+                    if (vnew) {   // (uniform) masked like w~: entries behind n_dot do not count
+                        const float2 f = ldf2s(vnew, idx[u]);
+                        if (ok[u] && 2 * idx[u] < n_dot) vn[u].x = (double)f.x;
+                        if (ok[u] && 2 * idx[u] + 1 < n_dot) vn[u].y = (double)f.y;
+                    }
+                }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const bool live = r0 + v < rows2;
+                    const double *Pi = live ? V2 + (size_t)(r0 + v) * ldp : w;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) e[v][u] = ld2s<true>(Pi, live ? idx[u] : 0);
+                }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    if (r0 + v < rows2) {
+                        if (split) {
+                            double dx = 0.0, dy = 0.0;
+#pragma unroll
+                            for (int u = 0; u < U; ++u) {
+                                dx += e[v][u].x * wv[u].x;
+                                dy += e[v][u].y * wv[u].y;
+                            }
+                            double tx = 0.0, ty = 0.0;
+#pragma unroll
+                            for (int u = 0; u < U; ++u) {
+                                tx += e[v][u].x * vn[u].x;
+                                ty += e[v][u].y * vn[u].y;
+                            }
+                            if (r0 + v < 4) {   // (nv2 <= 8: at most four parity planes)
+                                acc[NB + 2 * ((r0 + v) & 3)] += dx;
+                                acc[NB + 2 * ((r0 + v) & 3) + 1] += dy;
+                                acc[NW + 1 + 2 * ((r0 + v) & 3)] += tx;
+                                acc[NW + 1 + 2 * ((r0 + v) & 3) + 1] += ty;
+                            }
+                        } else {
+                            double d = 0.0;
+#pragma unroll
+                            for (int u = 0; u < U; ++u) d += e[v][u].x * wv[u].x + e[v][u].y * wv[u].y;
+                            acc[NB + r0 + v] += d;
+                            double t = 0.0;
+#pragma unroll
+                            for (int u = 0; u < U; ++u) t += e[v][u].x * vn[u].x + e[v][u].y * vn[u].y;
+                            acc[NW + 1 + r0 + v] += t;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // workgroup sums -> partials[block][.]: the basis values, the plane values behind them, then w.w
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const double s = wave_sum(acc[i]);
+        if (lane == 0) lds[wave * NA + i] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NA) {
+        const int i = threadIdx.x;
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < W; ++j) s += lds[j * NA + i];
+        double *row = partials + (size_t)blockIdx.x * kPartialLd;
+        if (i < NB) { if (i < nv) publish(row + i, s); }
+        else if (i < NW) { if (i - NB < nv2) publish(row + nv + (i - NB), s); }
+        else if (i == NW) { if (with_ww) publish(row + nv + nv2, s); }
+        else if (vnew && i - NW - 1 < nv2) publish(row + nv + nv2 + 1 + (i - NW - 1), s);
+    }
+    if (!arrive_last(gridDim.x)) return;
+    const int k = nv + nv2 + (with_ww ? 1 : 0) + (vnew ? nv2 : 0);
+    final_reduce(partials, gridDim.x, kPartialLd, k, lds, fe);
+    if ((int)threadIdx.x < k) out[threadIdx.x] = lds[threadIdx.x];
+}
+
+static void mdot_f32_launch(const float *V, int64_t ldv, int nv, const double *V2, int64_t ld2, int nv2, int split, const float *vnew,
+                            const double *w,
+                            int64_t n2, int64_t n_dot, double *partials, int with_ww, double *out, FinErr fe, const int32_t *done,
+                            const VecShape &vs, hipStream_t s)
+{
+    const int ng = (nv + 7) / 8 > 0 ? (nv + 7) / 8 : 1;
+#define SPK_MDOT_F32(NGG, TT, UU) hipLaunchKernelGGL((mdot_f32_kernel<NGG, TT, UU>), dim3(vs.grid), dim3(TT), 0, s, V, ldv, nv, V2, ld2, \
+                                                     nv2, split, vnew, w, n2, n_dot, partials, with_ww, out, fe, done)
+#define SPK_MDOT_F32_NG(TT, UU)                                                \
+    switch (ng) {                                                              \
+    case 1: SPK_MDOT_F32(1, TT, UU); break;                                    \
+    case 2: SPK_MDOT_F32(2, TT, UU); break;                                    \
+    case 3: SPK_MDOT_F32(3, TT, UU); break;                                    \
+    case 4: SPK_MDOT_F32(4, TT, UU); break;                                    \
+    default: SPK_MDOT_F32(5, TT, UU); break;                                   \
+    }
+    if (vs.T == 512) { SPK_MDOT_F32_NG(512, 4) }
+    else if (vs.U == 4) { SPK_MDOT_F32_NG(256, 4) }
+    else if (vs.U == 2) { SPK_MDOT_F32_NG(256, 2) }
+    else { SPK_MDOT_F32_NG(256, 1) }
+#undef SPK_MDOT_F32_NG
+#undef SPK_MDOT_F32
+}
+
+void mdot_f32(const float *V, int64_t ldv, int nv, const double *w, int64_t n, int64_t n_dot, const Finish &f,
+              const int32_t *done, hipStream_t s, const double *V2, int64_t ld2, int nv2, int split)
+{
+    if (nv < 0 || nv2 < 0 || nv2 > 8 || nv + 2 * nv2 > kMaxNv - 1 || (split && (nv2 & 1)))
+        fail(SPK_ERR_ARG, "mdot_f32: %d vectors + 2 x %d plane values (<= %d, <= 8 plane values)", nv, nv2, kMaxNv - 1);
+    const float *vnew = nv > 0 && nv2 > 0 ? V + (size_t)(nv - 1) * ldv : nullptr;
+    if (f.ar.P) fail(SPK_ERR_STATE, "mdot_f32: one rank only");
+    const int64_t n2 = (n + 1) / 2;
+    const VecShape vs = vec_shape(n2);
+    const FinErr fe{f.err, f.fin_ticks};
+    // up to 40 basis vectors per launch; the plane values and w.w come out of the last one, where they still fit it
+    for (int v0 = 0;;) {
+        const int cnt = std::min(nv - v0, 40);
+        const int last = v0 + cnt == nv && cnt + nv2 <= 40;
+        mdot_f32_launch(V + (size_t)v0 * ldv, ldv, cnt, last ? V2 : nullptr, ld2, last ? nv2 : 0, split, last ? vnew : nullptr, w, n2, n_dot, f.partials + v0,
+                        last, f.out + v0, fe, done, vs, s);
+        if (last) break;
+        v0 += cnt;
+    }
+}
+
+// V~_0 of a cycle on an FP32 basis: the head kernel has normalised r in FP64; its rounded copy is what the basis holds
+__global__ __launch_bounds__(kThreads) void cvt_basis_f32_kernel(const double *__restrict__ src, float *__restrict__ dst, int64_t n,
+                                                                 const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) dst[i] = (float)src[i];
+}
+void cvt_basis_f32(const double *src, float *dst, int64_t n, const int32_t *done, hipStream_t s)
+{
+    const int grid = (int)std::min<int64_t>((n + kThreads - 1) / kThreads, kMaxBlocks);
+    hipLaunchKernelGGL(cvt_basis_f32_kernel, dim3(grid > 0 ? grid : 1), dim3(kThreads), 0, s, src, dst, n, done);
+}
+
+// ---------------------------------------------------------------------------
 // VecMAXPY:  w += sign * sum_i a[i] V_i, coefficients read from device memory;
 // the squared norm of the updated w (first n_dot entries) is produced in the
 // same pass -> VecNorm costs no extra sweep.

@@ -434,6 +434,12 @@ int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
             if (!val || !parse_int(val, &k->opts.iteration_form) || k->opts.iteration_form < 0 || k->opts.iteration_form > SPK_ITER_LAST)
                 return need("an integer 0..7 (0 automatic, 1 four launches per iteration, 5 three launches on an un-normalised basis, "
                             "6 one launch per restart cycle, 7 as 5 with MDot and MAXPY in one launch; 2..4 are accepted and run as 5)");
+        } else if (key == "-spk_basis_precision") {
+            // how fgmres stores its Krylov basis (spk_opts.basis_precision); the solve refuses what single cannot run
+            const std::string v(val ? val : "");
+            if (v == "double") k->opts.basis_precision = SPK_BASIS_DOUBLE;
+            else if (v == "single") k->opts.basis_precision = SPK_BASIS_SINGLE;
+            else return need("double | single");
         } else if (key == "-spk_check_every") {
             if (!val || !parse_int(val, &k->opts.check_every)) return need("an integer");
         } else if (key.rfind("-ksp_", 0) == 0 || key.rfind("-pc_", 0) == 0 || key.rfind("-fieldsplit_", 0) == 0) {
@@ -586,7 +592,8 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
     if (k->view) {
         std::printf("KSP Object: type %s (MI355X device-resident), ", kKspTypes[k->ksp_type]);
         if (k->ksp_type == kFgmres)
-            std::printf("restart=%d, classical Gram-Schmidt, ", k->opts.restart);
+            std::printf("restart=%d, classical Gram-Schmidt, basis stored in %s precision (-spk_basis_precision), ", k->opts.restart,
+                        k->opts.basis_precision == SPK_BASIS_SINGLE ? "single" : "double");
         else
             std::printf("%s norm, ", k->norm_type == SPK_NORM_NATURAL ? "natural" : "unpreconditioned");
         std::printf("rtol=%g atol=%g divtol=%g max_it=%d, ", k->opts.rtol, k->opts.abstol, k->opts.dtol, k->opts.max_it);

@@ -383,14 +383,24 @@ static void ensure_krylov(spk_ctx *c, const spk_opts &o)
     c->ensure_scratch();
     c->ensure_vectors();
     const int mk = o.restart;
-    if (mk < 1 || mk > k::kBigNv - 2) fail(SPK_ERR_ARG, "fgmres: restart %d outside [1,%d]", mk, k::kBigNv - 2);
     const int32_t hist_cap = (int32_t)std::min<int64_t>((int64_t)std::max(o.max_it, 0) + 2, 1 << 22);
-    if (c->ws_restart != mk) {
-        // one more of each than the cycle uses: the un-normalised three-launch form lets the last iteration of a cycle
-        // write its (unused) next vectors too
-        c->V.alloc((size_t)c->ld * (mk + 2));
-        c->Z.alloc((size_t)c->ld * (mk + 1));
+    if (c->ws_restart != mk || c->ws_basis != o.basis_precision) {
+        if (o.basis_precision == SPK_BASIS_SINGLE) {
+            // the basis as floats, restart + 1 vectors (the cycle's last iteration stores no w'), and two FP64 work vectors
+            // that take turns as w~ and as the c~ the next product accumulates onto; the FP64 basis goes
+            c->V.release();
+            c->Vf.alloc((size_t)c->ld * (mk + 1));
+            c->Vw.alloc((size_t)c->ld * 2);
+        } else {
+            c->Vf.release();
+            c->Vw.release();
+            // one more of each than the cycle uses: the un-normalised three-launch form lets the last iteration of a cycle
+            // write its (unused) next vectors too
+            c->V.alloc((size_t)c->ld * (mk + 2));
+        }
+        if (c->ws_restart != mk) c->Z.alloc((size_t)c->ld * (mk + 1));
         c->ws_restart = mk;
+        c->ws_basis = o.basis_precision;
     }
     const int ldh = mk + 2;
     const size_t nd = (size_t)ldh * (mk + 1) + 4 * (size_t)(mk + 2) + 8 * (size_t)(mk + 2) + (size_t)hist_cap + 64;
@@ -418,6 +428,7 @@ struct FgmresPlan {
     enum Orth { kOrthUn3, kOrthMgs, kOrthSingle, kOrthCgs } orth;
     bool schur, head;     // a head kernel scales v_j, runs the Givens step of j-1; Schur: B D w' out of the last MAXPY
     bool big;             // restart > kMaxNv - 2: the Givens step is a launch of its own
+    bool f32;             // the basis is stored as floats (opts.basis_precision; form 5 only)
     bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
     int gs_keep;          // form 7: the first tile's operands stay on chip between its two passes (SPK_GS_KEEP=0: not, for tests)
     int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
@@ -494,6 +505,25 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
     p.orth = un3 ? FgmresPlan::kOrthUn3 : o.orthog == SPK_ORTHOG_MGS ? FgmresPlan::kOrthMgs
            : single ? FgmresPlan::kOrthSingle : FgmresPlan::kOrthCgs;
+    if (o.basis_precision == SPK_BASIS_SINGLE) {
+        // an FP32 basis: form 5 only (AUTO, 6 and 7 resolve to it).  Whatever does not run there is refused here, before
+        // anything is allocated or enqueued -- the first reason that applies is named
+        const char *why = c->comm->size() > 1 ? "it runs on one rank (the path agreed across ranks does not carry the precision)"
+            : o.orthog != SPK_ORTHOG_CGS ? "modified Gram-Schmidt"
+            : o.cgs_refine != SPK_REFINE_NEVER ? "CGS refinement"
+            : o.single_reduce == 1 ? "single_reduce"
+            : !o.fused ? "fused = 0"
+            : c->amg_d ? "a multigrid V-cycle runs on the step-by-step path"
+            : c->inner_sweeps > 0 ? "the FP32 inner sweeps run on the step-by-step path"
+            : c->schur_dense && c->pc_type == SPK_PC_SCHUR ? "a dense Schur complement runs on the step-by-step path"
+            : !c->even_all ? "an odd local size"
+            : mk + 2 * m > k::kMaxNv - 2 ? "restart + 2 m beyond the fused limit of 62 (VecMDot carries B D of the newest vector too)"
+            : !p.head ? "this preconditioner runs on the step-by-step path"
+            : !un3 ? "this iteration_form is not the un-normalised one" : nullptr;
+        if (why || !un3) fail(SPK_ERR_UNSUPPORTED, "fgmres: basis_precision single needs iteration form 5: %s", why ? why : "refused");
+        p.resident = p.gsf = false;
+    }
+    p.f32 = o.basis_precision == SPK_BASIS_SINGLE;
     p.form = p.resident ? SPK_ITER_RESIDENT : p.gsf ? SPK_ITER_GS_FUSED : un3 ? SPK_ITER_UNNORM : p.head ? SPK_ITER_FOUR_LAUNCH : -1;
     return p;
 }
@@ -519,7 +549,12 @@ struct FgmresRun {
     int mk, m, lam_in_dot, nl;
     int64_t N, ld, n_dot;
     double *V, *Z, *sm, *sm2, *nrm2b, *w1side;
+    float *Vf;    // an FP32 basis (else nullptr): V~_j as floats, w~ / c~ in the two work vectors W
+    double *W;
     double *Vj(int j) const { return V + (size_t)ld * j; }
+    // forms 5-7: the residual of a restart (normalised into v_0 by the first head) and w~ of iteration loc (c~ of loc - 1)
+    double *r0() const { return Vf ? W : V; }
+    double *wun(int loc) const { return Vf ? W + (size_t)ld * ((loc + 1) & 1) : Vj(loc + 1); }
     double *Zj(int j) const { return Z + (size_t)ld * j; }
     // small[]: two parity sets so that a deferred Givens step (head paths) can still read iteration j-1's scalars while
     // iteration j produces its own: dots at q*128, norm (+ B D w') at q*128+64; lambda entries of w, side copies at 400
@@ -554,11 +589,12 @@ void product(const FgmresRun &r, const double *z, double *w, bool halo_done, boo
 void launch_head(const FgmresRun &r, int j, double *w, int givens, const k::SendRanges *sr, const int32_t *done, double *wl)
 {
     spk_ctx *c = r.c;
+    double *vj = j == 0 ? r.r0() : r.Vj(j);
     if (r.p.schur)
-        k::fused_head(r.Vj(j), r.nrmbuf(j + 1), r.w1side, c->dinv.p, r.p.bdp, r.ld, c->shat.p, c->gram.p, c->schur_fact, r.nl,
+        k::fused_head(vj, r.nrmbuf(j + 1), r.w1side, c->dinv.p, r.p.bdp, r.ld, c->shat.p, c->gram.p, c->schur_fact, r.nl,
                       r.m, r.Zj(j), w, c->ka, givens, r.dotsbuf(j + 1), done, r.s, sr, r.p.bpk, wl);
     else
-        k::fused_head(r.Vj(j), r.nrmbuf(j + 1), nullptr, c->dinv.p, nullptr, r.ld, nullptr, nullptr, SPK_SCHUR_LOWER, r.nl, 0,
+        k::fused_head(vj, r.nrmbuf(j + 1), nullptr, c->dinv.p, nullptr, r.ld, nullptr, nullptr, SPK_SCHUR_LOWER, r.nl, 0,
                       r.Zj(j), nullptr, c->ka, givens, r.dotsbuf(j + 1), done, r.s, sr);
 }
 
@@ -567,12 +603,13 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
 {
     spk_ctx *c = r.c;
     const bool schur = r.p.schur;
-    double *w = r.Vj(loc + 1), *db = r.dotsbuf(loc), *nb = r.nrmbuf(loc);
+    double *w = r.wun(loc), *db = r.dotsbuf(loc), *nb = r.nrmbuf(loc);
     if (loc == 0) {
         // first iteration of a cycle: the classic head on the normalised r, then the plain product
         k::SendRanges sr = c->send_ranges;
         const bool inhead = sr.n > 0 && c->comm->fused_halo(sr, c->xghost.p);
         launch_head(r, 0, w, -1, sr.n > 0 ? &sr : nullptr, done, r.wl(0));
+        if (r.Vf) k::cvt_basis_f32(r.r0(), r.Vf, r.N, done, r.s);   // V~_0 = float(v_0)
         product(r, r.Zj(0), w, inhead, schur, done);
     }
     if (r.p.resident) {
@@ -598,7 +635,11 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     // (form 7: inside the launch of kernel B, below)
     // (the cycle's last iteration too, where its loc + 1 + m values fit MDot's 40 accumulators)
     const bool gs = r.p.gsf && (loc + 1 < r.mk || loc + 1 + (schur ? r.m : 0) <= 40);
-    if (!gs) {
+    if (r.Vf) {
+        const bool spl = r.p.bpk != 0;
+        k::mdot_f32(r.Vf, r.ld, loc + 1, w, r.N, r.n_dot, c->fin(db), done, r.s, schur ? (spl ? c->bdpk.p : c->bd.p) : nullptr, r.ld,
+                    schur ? r.m : 0, spl ? 1 : 0);
+    } else if (!gs) {
         const bool one = loc + 1 + r.m <= 40, spl = r.p.bpk && one;
         const k::PeerAR ar = one ? c->comm->fused_allreduce(loc + 2 + (schur ? r.m : 0), k::kStatArDots) : k::PeerAR{};
         k::mdot(r.V, r.ld, loc + 1, w, r.N, r.n_dot, c->fin(db, ar), done, r.s, schur ? (spl ? c->bdpk.p : c->bd.p) : nullptr,
@@ -607,11 +648,12 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     }
     const k::PeerAR ar2 = c->comm->fused_allreduce(1, k::kStatArNorm);
     k::IterB b{};
-    b.V = r.V; b.ldv = r.ld; b.nv = loc + 1; b.dots = db; b.tb = c->ka.tb;
+    b.V = r.Vf ? reinterpret_cast<const double *>(r.Vf) : r.V; b.ldv = r.ld; b.nv = loc + 1;
+    b.w32 = r.Vf ? r.Vf + (size_t)r.ld * (loc + 1) : nullptr; b.dots = db; b.tb = c->ka.tb;
     b.w = w; b.dinv = c->dinv.p; b.bd = r.p.bdp; b.ldb = r.ld; b.shat = c->shat.p; b.gram = c->gram.p;
     b.fact = schur ? c->schur_fact : SPK_SCHUR_LOWER;
     b.nl = r.nl; b.m = r.m; b.packed = r.p.bpk;
-    b.zun = r.Zj(loc + 1); b.c = schur ? r.Vj(loc + 2) : nullptr; b.wl_in = r.wl(loc); b.wl_out = r.wl(loc + 1);
+    b.zun = r.Zj(loc + 1); b.c = schur ? r.wun(loc + 1) : nullptr; b.wl_in = r.wl(loc); b.wl_out = r.wl(loc + 1);
     b.lam_in_dot = r.lam_in_dot;
     b.partials = c->partials.p; b.out = nb; b.ar = ar2; b.err = c->errw.p; b.fin_ticks = c->fin_ticks;
     b.sc = c->basis_sc.p; b.hbuf = r.sm2; b.ka = c->ka; b.loc = loc;
@@ -644,7 +686,7 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     // the Givens step of this iteration (and the new vector's scale factor) ride in the next product launch
     k::GivensRider gr{c->ka, loc, r.sm2, nb, c->basis_sc.p, defer ? c->partials.p : nullptr, defer ? fin_n : 0,
                       k::FinErr{c->errw.p, c->fin_ticks}, defer ? ar2 : k::PeerAR{}};
-    if (loc + 1 < r.mk) product(r, r.Zj(loc + 1), r.Vj(loc + 2), inb, schur, done, &gr);
+    if (loc + 1 < r.mk) product(r, r.Zj(loc + 1), r.wun(loc + 1), inb, schur, done, &gr);
     else cs.pend_h = r.sm2, cs.pend_n = nb, cs.pend_loc = loc;   // no product behind it: the step runs in the cycle-end launch
     return false;
 }
@@ -747,9 +789,14 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     require_setup(c, "fgmres");
     if (o.orthog != SPK_ORTHOG_CGS && o.orthog != SPK_ORTHOG_MGS) fail(SPK_ERR_ARG, "fgmres: unknown orthogonalisation %d", o.orthog);
     if (o.cgs_refine < SPK_REFINE_NEVER || o.cgs_refine > SPK_REFINE_ALWAYS) fail(SPK_ERR_ARG, "fgmres: unknown cgs_refine %d", o.cgs_refine);
+    if (o.basis_precision != SPK_BASIS_DOUBLE && o.basis_precision != SPK_BASIS_SINGLE)
+        fail(SPK_ERR_ARG, "fgmres: unknown basis_precision %d", o.basis_precision);
+    if (o.restart < 1 || o.restart > k::kBigNv - 2) fail(SPK_ERR_ARG, "fgmres: restart %d outside [1,%d]", o.restart, k::kBigNv - 2);
+    const FgmresPlan p = plan_fgmres(c, o);   // (refuses before anything is allocated or enqueued)
     ensure_krylov(c, o);
-    const FgmresPlan p = plan_fgmres(c, o);
     c->last_form = p.form;
+    c->last_basis = o.basis_precision;
+    c->last_basis_bytes = p.f32 ? (int64_t)(c->Vf.n * sizeof(float)) : (int64_t)(c->V.n * sizeof(double));
     c->last_single = p.orth == FgmresPlan::kOrthSingle ? 1 : 0;
     hipStream_t s = c->stream;
     const int mk = o.restart;
@@ -759,7 +806,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     const double *inv_tt = &c->kst.p->inv_tt;
     double *sm = c->small.p, *bn2 = sm + 384;   // small[]: FgmresRun's parity sets at 0..255, ||b||^2 at 384
     const FgmresRun r{c, p, s, mk, c->m, c->comm->rank() == 0 ? 1 : 0, c->n_local, N, ld, n_dot,
-                      c->V.p, c->Z.p, sm, sm + 256, sm + 320, c->y1tmp.p + 48};
+                      c->V.p, c->Z.p, sm, sm + 256, sm + 320, c->y1tmp.p + 48, p.f32 ? c->Vf.p : nullptr, c->Vw.p};
     const bool un3 = p.product == FgmresPlan::kUn3;
 
     SPK_HIP(hipStreamSynchronize(s));
@@ -773,11 +820,12 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     // initial residual into V0
     if (o.guess_nonzero) op_mult(c, x, c->tmp.p, nullptr);
     else SPK_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, s));
-    SPK_HIP(hipMemcpyAsync(r.Vj(0), b, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
-    if (o.guess_nonzero) k::axpby(-1.0, c->tmp.p, 1.0, r.Vj(0), N, nullptr, s);
+    SPK_HIP(hipMemcpyAsync(r.r0(), b, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));
+    if (o.guess_nonzero) k::axpby(-1.0, c->tmp.p, 1.0, r.r0(), N, nullptr, s);
     ensure_plan_buffers(c, p, mk);
 
-    c->ka.tentative = p.orth == FgmresPlan::kOrthSingle ? 1 : 0;
+    c->ka.tentative = p.orth == FgmresPlan::kOrthSingle || p.f32 ? 1 : 0;
+    c->ka.theta = p.f32 ? k::kBasisTheta : 0.0;
     KrylovState st{};
     int cycles = 0;
     // The solve's state reaches the host through pinned memory written by krylov_cycle_begin (no copy on the stream); the
@@ -804,8 +852,8 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         // ---- cycle start: ||r|| (parity slot 1 = "iteration -1"), convergence test, v0 = r/||r|| ----
         // (from the second cycle on the previous cycle's end has formed r = b - K x and these sums in one pass)
         if (cycles == 0) {
-            if (p.schur) k::sqnorm_bd(r.Vj(0), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s);
-            else k::sqnorm(r.Vj(0), n_dot, c->fin(r.nrmbuf(1)), done, s);
+            if (p.schur) k::sqnorm_bd(r.r0(), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s);
+            else k::sqnorm(r.r0(), n_dot, c->fin(r.nrmbuf(1)), done, s);
         }
         c->comm->allreduce_sum(r.nrmbuf(1), p.nn, s);
         // (the kernel also reports the state it finds / leaves into pinned memory: the verdict on the PREVIOUS cycle and,
@@ -831,7 +879,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
             // (gated) launches beyond it
             if (loc >= its_cap) break;
             const int32_t *done = &c->kst.p->skip_iter;  // the gate of everything inside an iteration
-            double *w = r.Vj(loc + 1);
+            double *w = un3 ? nullptr : r.Vj(loc + 1);   // (forms 5-7 take theirs from the run: an FP32 basis has no such slot)
             double *db = p.big ? c->bigdots.p : r.dotsbuf(loc), *nb = r.nrmbuf(loc);
             if (un3) {
                 if (un3_iteration(r, cs, loc, done)) break;   // (form 6: the whole cycle was one launch)
@@ -868,8 +916,8 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
         // ---- true residual for the next cycle (KSPFGMRESResidual); skipped once done ----
         op_mult(c, x, c->tmp.p, done);
         // r = b - K x into V0 together with ||r||^2 (and B D r) for the start of the next cycle
-        if (p.schur) k::sqnorm_bd(r.Vj(0), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s, b, c->tmp.p);
-        else k::sqnorm_sub(b, c->tmp.p, r.Vj(0), N, n_dot, c->fin(r.nrmbuf(1)), done, s);
+        if (p.schur) k::sqnorm_bd(r.r0(), N, n_dot, c->bd.p, ld, r.nl, r.m, r.w1side, c->fin(r.nrmbuf(1)), done, s, b, c->tmp.p);
+        else k::sqnorm_sub(b, c->tmp.p, r.r0(), N, n_dot, c->fin(r.nrmbuf(1)), done, s);
         ++cycles;
         SPK_HIP(hipGetLastError());  // a rejected launch inside the cycle surfaces here, not as a wrong answer
     }

@@ -21,10 +21,20 @@ SCHUR_PRE_SELFP_DIAG, SCHUR_PRE_FULL = 0, 1
 _SCHUR_PRES = {"selfp": SCHUR_PRE_SELFP_DIAG, "full": SCHUR_PRE_FULL}
 
 
+BASIS_DOUBLE, BASIS_SINGLE = 0, 1   # SPK_BASIS_* (include/spk.h)
+_BASES = {"double": BASIS_DOUBLE, "single": BASIS_SINGLE}
+
+
 def default_opts(**kw):
+    """spk_opts with PETSc's defaults, overridden by keyword.  basis="double" | "single" sets basis_precision: how the
+    Krylov basis of fgmres is stored (single: FP32 storage, FP64 arithmetic, iteration form 5 on one rank)."""
     o = Opts()
     lib.spk_default_opts(C.byref(o))
     for k, v in kw.items():
+        if k == "basis":
+            if v not in _BASES:
+                raise ValueError(f"basis must be one of {sorted(_BASES)}")
+            k, v = "basis_precision", _BASES[v]
         if not hasattr(o, k):
             raise TypeError(f"unknown solver option {k}")
         setattr(o, k, v)
@@ -331,6 +341,23 @@ class Context:
         self._chk(lib.spk_debug_mdot(self.h, C.byref(o), self._ptr(V), self._ptr(V2), w, out))
         return out
 
+    def debug_mdot_f32(self, V, w, n_dot=None, V2=None, split=0, done=-1, pad=0.0):
+        """k::mdot_f32, VecMDot over an FP32 basis: as debug_mdot with V (nv, n) float32; w and V2 stay float64.  Behind
+        the nv + nv2 + 1 values of debug_mdot come the nv2 plane values of V[-1] (the first n_dot entries)."""
+        from ._lib import DebugMdotOpts
+        w = self._f64(w)
+        n = w.shape[0]
+        V = np.ascontiguousarray(V, np.float32)
+        if V.shape != (np.shape(V)[0], n):
+            raise ValueError(f"expected an array of shape {(np.shape(V)[0], n)}, got {V.shape}")
+        rows2 = 0 if V2 is None else np.shape(V2)[0]
+        V2 = None if V2 is None else self._f64(V2, (rows2, n))
+        nv, nv2 = V.shape[0], (2 * rows2 if split else rows2)
+        o = DebugMdotOpts(n, n if n_dot is None else n_dot, nv, nv2, int(split), int(done), float(pad))
+        out = np.zeros(nv + 2 * nv2 + 1)
+        self._chk(lib.spk_debug_mdot_f32(self.h, C.byref(o), self._ptr(V), self._ptr(V2), w, out))
+        return out
+
     def debug_maxpy(self, V, a, w, sign=1.0, n_dot=None, nv_live=-1, want_norm=1, bd=None, packed=0, n_bd=0, m=0,
                     w1side=0, pyth=None, done=-1, pad=0.0):
         """k::maxpy: V (nv, n), a (nv,), w (n,); bd: (m, n) dense rows or, packed, (m / 2, n) parity planes;
@@ -603,6 +630,13 @@ class Context:
         f, sr = C.c_int32(), C.c_int32()
         self._chk(lib.spk_get_iteration_form(self.h, C.byref(f), C.byref(sr)))
         return f.value, sr.value
+
+    def basis_info(self):
+        """(precision, basis_bytes) of the last fgmres on this context: "double" / "single" (None before the first solve)
+        and the bytes allocated for the basis V."""
+        p, nb = C.c_int32(), C.c_int64()
+        self._chk(lib.spk_get_basis_info(self.h, C.byref(p), C.byref(nb)))
+        return {BASIS_DOUBLE: "double", BASIS_SINGLE: "single"}.get(p.value), nb.value
 
     def spmv_models(self):
         """Bytes of one product y = A x in the CSR, blocked and row-pattern-dictionary layouts (0: layout absent)."""
