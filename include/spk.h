@@ -325,9 +325,15 @@ enum { SPK_AMG_SETUP_HOST = 0, SPK_AMG_SETUP_DEVICE = 1 };
  * weight 1; odd i -> (i - 1) / 2 and (i + 1) / 2, weight 1/2 each), boundary nodes included; the coarse operators are the
  * same Galerkin products.  threshold and nsmooths are not read, there are no aggregates, SPK_AMG_TENTATIVE returns P.
  * A level built by the grid rule applies P and R in the V-cycle without reading them (SPK_AMG_TRANSFER_MATRIX_FREE:
- * every weight is a power of two, the sums run in ascending column order) or as stored CSR like gamg's (STORED). */
+ * every weight is a power of two, the sums run in ascending column order) or as stored CSR like gamg's (STORED).
+ * Which sides halve (grid coarsening only).  ODD: the rule above -- a grid with an even side that is too large for the
+ * dense coarse solve is refused.  ANY: an even side of m >= 4 nodes halves too, to m / 2 + 1: its coarse nodes are the
+ * fine indices 0, 2, ..., m - 2 and m - 1 (the last fine element is itself a coarse element, so the coarse Q1 space stays
+ * nested); fine index i < m - 1 has the parents of the odd rule, fine index m - 1 the one parent m / 2 with weight 1.
+ * Odd sides halve as under ODD, sides of 2 and 3 nodes never do: 1024 -> 513 -> 257 -> ... -> 5. */
 enum { SPK_AMG_COARSEN_AGGREGATION = 0, SPK_AMG_COARSEN_GRID = 1 };
 enum { SPK_AMG_TRANSFER_MATRIX_FREE = 0, SPK_AMG_TRANSFER_STORED = 1 };
+enum { SPK_AMG_SIDES_ODD = 0, SPK_AMG_SIDES_ANY = 1 };
 #define SPK_AMG_MAX_LEVELS 16
 #define SPK_AMG_MAX_COARSE 1024
 typedef struct spk_amg_opts {
@@ -346,6 +352,7 @@ typedef struct spk_amg_opts {
     int32_t coarsening;       /* SPK_AMG_COARSEN_*                  (aggregation; -pc_type mg selects grid) */
     int32_t grid[3];          /* grid coarsening: nodes per side mx, my, mz (mz = 1 in 2-D); rows = bs mx my mz */
     int32_t transfer;         /* -spk_mg_transfer matrixfree|stored: SPK_AMG_TRANSFER_* (grid coarsening only) */
+    int32_t sides;            /* -spk_mg_sides odd|any: SPK_AMG_SIDES_* (odd; grid coarsening only) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -359,6 +366,7 @@ typedef struct spk_amg_info {
     int32_t setup;                           /* where this hierarchy was built: SPK_AMG_SETUP_* */
     int32_t coarsening;                      /* SPK_AMG_COARSEN_* */
     int32_t dims[SPK_AMG_MAX_LEVELS][3];     /* grid coarsening: the node grid of every level (else 0) */
+    int32_t sides;                           /* grid coarsening: SPK_AMG_SIDES_* of the rule that built it (else 0) */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);

@@ -95,7 +95,9 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * -mg_levels_*, -pc_gamg_coarse_eq_limit, -pc_gamg_reuse_interpolation, -spk_gamg_setup; -pc_gamg_threshold and
  * -pc_gamg_agg_nsmooths are read and not used.  -pc_mg_galerkin takes no value, both or pmat (every coarse operator is
  * the Galerkin product; anything else: SPK_ERR_UNSUPPORTED); -spk_mg_transfer matrixfree|stored selects how the V-cycle
- * applies P and R (opts->transfer).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * applies P and R (opts->transfer); -spk_mg_sides odd|any selects which sides halve (opts->sides: odd, the default, refuses
+ * a grid whose even side keeps the coarsest level too large; any halves an even side of m >= 4 nodes to m / 2 + 1, so
+ * 1024 -> 513 -> ... -> 5; another value: SPK_ERR_UNSUPPORTED; given without mg it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
  * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
  * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);

@@ -18,5 +18,5 @@ from .solver import (  # noqa: F401
     BLOCK_A00, BLOCK_A10, MEM_HOST, MEM_DEVICE, NORM_UNPRECONDITIONED, NORM_NATURAL, DIVERGED_INDEFINITE_PC,
     DIVERGED_INDEFINITE_MAT, PIPECGRR_TAU_DEFAULT, SCHUR_PRE_SELFP_DIAG, SCHUR_PRE_FULL,
     AmgHierarchy, amg_opts, AMG_CHEBYSHEV, AMG_RICHARDSON, AMG_SETUP_HOST, AMG_SETUP_DEVICE, AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID,
-    AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED, AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV,
+    AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED, AMG_SIDES_ODD, AMG_SIDES_ANY, AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV,
 )

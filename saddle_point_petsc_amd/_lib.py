@@ -72,7 +72,7 @@ class AmgOpts(C.Structure):
         ("max_levels", C.c_int32), ("coarse_eq_limit", C.c_int32), ("nsmooths", C.c_int32), ("smoother", C.c_int32),
         ("threshold", C.c_double), ("smooth_its", C.c_int32), ("block_size", C.c_int32), ("esteig", C.c_double * 4),
         ("richardson_scale", C.c_double), ("setup", C.c_int32),
-        ("coarsening", C.c_int32), ("grid", C.c_int32 * 3), ("transfer", C.c_int32),
+        ("coarsening", C.c_int32), ("grid", C.c_int32 * 3), ("transfer", C.c_int32), ("sides", C.c_int32),
     ]
 
 
@@ -82,7 +82,7 @@ class AmgInfo(C.Structure):
         ("levels", C.c_int32), ("block_size", C.c_int32), ("rows", C.c_int32 * AMG_MAX_LEVELS),
         ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("lambda_max", C.c_double * AMG_MAX_LEVELS),
         ("operator_complexity", C.c_double), ("setup_seconds", C.c_double), ("setup", C.c_int32),
-        ("coarsening", C.c_int32), ("dims", (C.c_int32 * 3) * AMG_MAX_LEVELS),
+        ("coarsening", C.c_int32), ("dims", (C.c_int32 * 3) * AMG_MAX_LEVELS), ("sides", C.c_int32),
     ]
 
 

@@ -3,7 +3,7 @@
 // on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the V-cycle's launch sequence (kernels:
 // spk_k_amg.hip).
 // The same loop builds the grid-coarsened hierarchy (-pc_type mg, SPK_AMG_COARSEN_GRID): where the node grid is known a
-// level halves its odd sides and P is the tensor product of linear interpolations -- no graph, no aggregation, no
+// level halves its odd sides (-spk_mg_sides any: the even ones too) and P is the tensor product of linear interpolations -- no graph, no aggregation, no
 // prolongator smoothing; everything else (Ritz values, Galerkin products, coarse inverse, refresh) is shared.
 // With reuse on (spk_pc_set_amg_reuse) a second, shorter loop (refresh_levels) over the same two routes puts new values
 // of A00 through a hierarchy whose aggregates, prolongators and patterns stay.
@@ -336,30 +336,34 @@ HostCsr tentative(const std::vector<int32_t> &agg, int32_t na, int bs)
 }
 
 // ---- grid coarsening (SPK_AMG_COARSEN_GRID): the halving rule and the tensor-product prolongator -------------------
-// a direction of m nodes halves iff m is odd and >= 5
-bool grid_halves(int32_t m) { return m >= 5 && (m & 1); }
-// the coarse grid of `fd`; false when no direction halves
-bool grid_coarse_dims(const int32_t fd[3], int32_t cd[3])
+// a direction of m nodes halves iff m is odd and >= 5 (SPK_AMG_SIDES_ODD), or m >= 4 (SPK_AMG_SIDES_ANY)
+bool grid_halves(int32_t m, int sides) { return sides == SPK_AMG_SIDES_ANY ? m >= 4 : m >= 5 && (m & 1); }
+// the coarse grid of `fd`; false when no direction halves.  A halved side of m nodes keeps m / 2 + 1: (m + 1) / 2 of an odd
+// m; of an even m the fine indices 0, 2, ..., m - 2 and m - 1
+bool grid_coarse_dims(const int32_t fd[3], int32_t cd[3], int sides)
 {
     bool any = false;
     for (int a = 0; a < 3; ++a) {
-        cd[a] = grid_halves(fd[a]) ? (fd[a] + 1) / 2 : fd[a];
+        cd[a] = grid_halves(fd[a], sides) ? fd[a] / 2 + 1 : fd[a];
         any = any || cd[a] != fd[a];
     }
     return any;
 }
-// the parents of fine index i in one direction: `first`, and one more behind it when cnt == 2 (weight 1/2 each, else 1)
+// the parents of fine index i in one direction of m nodes: `first`, and one more behind it when cnt == 2 (weight 1/2 each,
+// else 1).  An odd i that is the last index (m even) is a coarse node itself: the one parent m / 2
 struct GridParents { int32_t first, cnt; };
-GridParents grid_parents(int32_t i, bool halved)
+GridParents grid_parents(int32_t i, int32_t m, bool halved)
 {
     if (!halved) return {i, 1};
+    if ((i & 1) && i == m - 1) return {(i + 1) / 2, 1};
     return (i & 1) ? GridParents{(i - 1) / 2, 2} : GridParents{i / 2, 1};
 }
-// entries of P = P_z (x) P_y (x) P_x (x) I_bs: per direction i + i/2 parents lie before fine index i
+// entries of P = P_z (x) P_y (x) P_x (x) I_bs: per direction i + i/2 parents lie before fine index i; the last index of an
+// even side has one parent, not two
 int64_t grid_prolong_nnz(const int32_t fd[3], const int32_t cd[3], int bs)
 {
     int64_t t = bs;
-    for (int a = 0; a < 3; ++a) t *= cd[a] != fd[a] ? (int64_t)fd[a] + fd[a] / 2 : (int64_t)fd[a];
+    for (int a = 0; a < 3; ++a) t *= cd[a] != fd[a] ? (int64_t)fd[a] + fd[a] / 2 - !(fd[a] & 1) : (int64_t)fd[a];
     return t;
 }
 // P as CSR with ascending columns, boundary nodes included: no special case for Dirichlet rows
@@ -376,8 +380,8 @@ HostCsr grid_prolongator(const int32_t fd[3], const int32_t cd[3], int bs)
     for (int32_t k = 0; k < fd[2]; ++k)
         for (int32_t j = 0; j < fd[1]; ++j)
             for (int32_t i = 0; i < fd[0]; ++i) {
-                const GridParents px = grid_parents(i, cd[0] != fd[0]), py = grid_parents(j, cd[1] != fd[1]),
-                                  pz = grid_parents(k, cd[2] != fd[2]);
+                const GridParents px = grid_parents(i, fd[0], cd[0] != fd[0]), py = grid_parents(j, fd[1], cd[1] != fd[1]),
+                                  pz = grid_parents(k, fd[2], cd[2] != fd[2]);
                 const double w = 1.0 / (double)(px.cnt * py.cnt * pz.cnt);   // 1, 1/2, 1/4 or 1/8
                 for (int c = 0; c < bs; ++c) {
                     for (int32_t kk = 0; kk < pz.cnt; ++kk)
@@ -493,7 +497,7 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
         tot += (double)info.nnz[l];
         if (n <= o.coarse_eq_limit || l + 1 == o.max_levels) break;
         if (grid) {   // the grid is known: no graph, no aggregation, no prolongator smoothing
-            if (!grid_coarse_dims(fd, cd)) { stuck = true; break; }
+            if (!grid_coarse_dims(fd, cd, o.sides)) { stuck = true; break; }
             double lmin = 0.0, lmax = 0.0, lo = 0.0, hi = 0.0;
             r.ritz(l, &lmin, &lmax);
             info.lambda_max[l] = lmax;
@@ -517,12 +521,14 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
     }
     info.levels = l + 1;
     info.coarsening = o.coarsening;
-    if (r.rows(l) > SPK_AMG_MAX_COARSE && stuck) {
+    info.sides = grid ? o.sides : 0;
+    if (r.rows(l) > SPK_AMG_MAX_COARSE && stuck) {   // (SPK_AMG_SIDES_ODD only: under ANY no side above 3 nodes is stuck)
         int a = 0;   // the largest side that does not halve
         for (int b = 1; b < 3; ++b) if (fd[b] > fd[a]) a = b;
         fail(SPK_ERR_UNSUPPORTED, "amg: the coarsest level keeps %d equations after %d levels; the dense coarse solve takes at "
              "most %d -- grid coarsening stops at %d x %d x %d nodes: the side of %d nodes (direction %c) cannot be halved "
-             "(a side halves while it is odd and >= 5; sides of c 2^k + 1 nodes coarsen to the end)", (int)r.rows(l), info.levels,
+             "(a side halves while it is odd and >= 5; sides of c 2^k + 1 nodes coarsen to the end) "
+             "(`-spk_mg_sides any` coarsens even sides)", (int)r.rows(l), info.levels,
              SPK_AMG_MAX_COARSE, (int)fd[0], (int)fd[1], (int)fd[2], (int)fd[a], "xyz"[a]);
     }
     if (r.rows(l) > SPK_AMG_MAX_COARSE)
@@ -679,13 +685,15 @@ void amg_check_opts(const spk_amg_opts &o)
         fail(SPK_ERR_ARG, "amg: setup %d is neither SPK_AMG_SETUP_HOST (0) nor SPK_AMG_SETUP_DEVICE (1)", o.setup);
     if (o.coarsening != SPK_AMG_COARSEN_AGGREGATION && o.coarsening != SPK_AMG_COARSEN_GRID)
         fail(SPK_ERR_ARG, "amg: coarsening %d is neither SPK_AMG_COARSEN_AGGREGATION (0) nor SPK_AMG_COARSEN_GRID (1)", o.coarsening);
-    if (o.coarsening == SPK_AMG_COARSEN_GRID) {   // (grid and transfer are read under grid coarsening only)
+    if (o.coarsening == SPK_AMG_COARSEN_GRID) {   // (grid, transfer and sides are read under grid coarsening only)
         if (o.grid[0] < 2 || o.grid[1] < 2 || o.grid[2] < 1)
             fail(SPK_ERR_ARG, "amg: grid %d x %d x %d: at least 2 x 2 nodes (x 1 in 2-D)", o.grid[0], o.grid[1], o.grid[2]);
         if ((int64_t)o.grid[0] * o.grid[1] > INT32_MAX || (int64_t)o.grid[0] * o.grid[1] * o.grid[2] > INT32_MAX)
             fail(SPK_ERR_ARG, "amg: grid %d x %d x %d has more nodes than 32-bit rows address", o.grid[0], o.grid[1], o.grid[2]);
         if (o.transfer != SPK_AMG_TRANSFER_MATRIX_FREE && o.transfer != SPK_AMG_TRANSFER_STORED)
             fail(SPK_ERR_ARG, "amg: transfer %d is neither SPK_AMG_TRANSFER_MATRIX_FREE (0) nor SPK_AMG_TRANSFER_STORED (1)", o.transfer);
+        if (o.sides != SPK_AMG_SIDES_ODD && o.sides != SPK_AMG_SIDES_ANY)
+            fail(SPK_ERR_ARG, "amg: sides %d is neither SPK_AMG_SIDES_ODD (0) nor SPK_AMG_SIDES_ANY (1)", o.sides);
         if (o.transfer == SPK_AMG_TRANSFER_MATRIX_FREE && (o.grid[1] > 65535 || o.grid[2] > 65535))   // they are launch dimensions
             fail(SPK_ERR_UNSUPPORTED, "amg: the matrix-free transfers take at most 65535 nodes in y and z (grid %d x %d x %d) -- "
                  "use -spk_mg_transfer stored", o.grid[0], o.grid[1], o.grid[2]);
@@ -1216,7 +1224,7 @@ bool amg_can_refresh(spk_ctx *c)
     bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
                 a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
                 a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup &&
-                a.coarsening == b.coarsening && a.transfer == b.transfer;
+                a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides;
     for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
     for (int i = 0; i < 3; ++i) same = same && a.grid[i] == b.grid[i];
     if (!same || ctx_block_size(c, a) != ru.bs || c->n_local != ru.n || c->Ad.nnz != ru.nnz || c->ld != ru.ld) return false;

@@ -178,12 +178,16 @@ __global__ __launch_bounds__(kThreads) void amg_out_kernel(int mode, int64_t n, 
 // ---- the transfers of a grid-coarsened level, matrix-free (SPK_AMG_TRANSFER_MATRIX_FREE) -------------------------------
 // P = P_z (x) P_y (x) P_x (x) I_bs is never read: a fine index that is even in a halved direction has the one parent
 // i / 2 (weight 1), an odd one the parents (i - 1) / 2 and (i + 1) / 2 (weight 1/2 each); a direction that does not
-// halve is the identity.  Every weight is a power of two, so every product is exact and the order of the additions alone
-// defines the bits: ascending column of P (prolongation) or of R (restriction), from the first product -- z outermost,
-// x innermost.  The grid's x is one row of dofs of a node row, y and z the node row: no integer division but by BS.
+// halve is the identity.  A halved side of an even number m of nodes (SPK_AMG_SIDES_ANY) keeps fine m - 1 as its last
+// coarse node m / 2: that fine index has this one parent (weight 1), and that coarse index gathers it alone -- coarse
+// m / 2 - 1 (fine m - 2) does not reach it.  Every weight is a power of two, so every product is exact and the order of
+// the additions alone defines the bits: ascending column of P (prolongation) or of R (restriction), from the first
+// product -- z outermost, x innermost.  The grid's x is one row of dofs of a node row, y and z the node row: no integer
+// division but by BS.
 struct GridArgs {
     int32_t fx, fy, cx, cy, cz;   // fine nodes in x, y; coarse nodes per side
     int32_t hx, hy, hz;           // 1: the direction halves
+    int32_t ex, ey, ez;           // 1: ... and its fine side is even
 };
 
 // y[f] += sum_parents w e[c]: one thread per fine dof; byte model: y read + y written + e read
@@ -195,8 +199,10 @@ __global__ __launch_bounds__(kThreads) void amg_prolong_grid_kernel(GridArgs g, 
     const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the node row
     if (xd >= g.fx * BS) return;
     const int32_t i = xd / BS, c = xd - i * BS, j = (int32_t)blockIdx.y, k = (int32_t)blockIdx.z;
-    const bool ox = g.hx && (i & 1), oy = g.hy && (j & 1), oz = g.hz && (k & 1);   // two parents in the direction
-    const int32_t ic = g.hx ? i >> 1 : i, jc = g.hy ? j >> 1 : j, kc = g.hz ? k >> 1 : k;   // the first parent
+    // the last index of an even halved side (the launch's z is the fine nodes in z): a coarse node itself
+    const int32_t lx = g.ex && i == g.fx - 1, ly = g.ey && j == g.fy - 1, lz = g.ez && k == (int32_t)gridDim.z - 1;
+    const bool ox = g.hx && (i & 1) && !lx, oy = g.hy && (j & 1) && !ly, oz = g.hz && (k & 1) && !lz;   // two parents in the direction
+    const int32_t ic = g.hx ? (i + lx) >> 1 : i, jc = g.hy ? (j + ly) >> 1 : j, kc = g.hz ? (k + lz) >> 1 : k;   // the first parent
     const double w = (ox ? 0.5 : 1.0) * (oy ? 0.5 : 1.0) * (oz ? 0.5 : 1.0);
     const int64_t sx = BS, sy = (int64_t)g.cx * BS, sz = sy * g.cy;
     const double *p = e + ((int64_t)kc * g.cy + jc) * sy + (int64_t)ic * BS + c;
@@ -228,11 +234,14 @@ __global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g,
     const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the coarse node row
     if (xd >= g.cx * BS) return;
     const int32_t ic = xd / BS, c = xd - ic * BS, jc = (int32_t)blockIdx.y, kc = (int32_t)blockIdx.z;
-    // the fine indices [lo, hi] of a direction and its centre (weight 1; the others 1/2)
-    const int32_t mi = g.hx ? 2 * ic : ic, mj = g.hy ? 2 * jc : jc, mk = g.hz ? 2 * kc : kc;
-    const int32_t i0 = g.hx ? max(mi - 1, 0) : mi, i1 = g.hx ? min(mi + 1, g.fx - 1) : mi;
-    const int32_t j0 = g.hy ? max(mj - 1, 0) : mj, j1 = g.hy ? min(mj + 1, g.fy - 1) : mj;
-    const int32_t k0 = g.hz ? max(mk - 1, 0) : mk, k1 = g.hz ? min(mk + 1, fz - 1) : mk;
+    // the last coarse index of an even halved side (the launch's z is the coarse nodes in z): the last fine index alone
+    const int32_t tx = g.ex && ic == g.cx - 1, ty = g.ey && jc == g.cy - 1, tz = g.ez && kc == g.cz - 1;
+    // the fine indices [lo, hi] of a direction and its centre (weight 1; the others 1/2); on an even side the last fine
+    // index belongs to the last coarse one only
+    const int32_t mi = g.hx ? 2 * ic - tx : ic, mj = g.hy ? 2 * jc - ty : jc, mk = g.hz ? 2 * kc - tz : kc;
+    const int32_t i0 = g.hx && !tx ? max(mi - 1, 0) : mi, i1 = g.hx && !tx ? min(mi + 1, g.fx - 1 - g.ex) : mi;
+    const int32_t j0 = g.hy && !ty ? max(mj - 1, 0) : mj, j1 = g.hy && !ty ? min(mj + 1, g.fy - 1 - g.ey) : mj;
+    const int32_t k0 = g.hz && !tz ? max(mk - 1, 0) : mk, k1 = g.hz && !tz ? min(mk + 1, fz - 1 - g.ez) : mk;
     double s = 0.0;
     bool first = true;
 #pragma unroll
@@ -267,7 +276,8 @@ __global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g,
 namespace {
 inline GridArgs grid_args(const AmgGrid &a)
 {
-    return GridArgs{a.fd[0], a.fd[1], a.cd[0], a.cd[1], a.cd[2], a.cd[0] != a.fd[0], a.cd[1] != a.fd[1], a.cd[2] != a.fd[2]};
+    const int32_t hx = a.cd[0] != a.fd[0], hy = a.cd[1] != a.fd[1], hz = a.cd[2] != a.fd[2];
+    return GridArgs{a.fd[0], a.fd[1], a.cd[0], a.cd[1], a.cd[2], hx, hy, hz, hx && !(a.fd[0] & 1), hy && !(a.fd[1] & 1), hz && !(a.fd[2] & 1)};
 }
 // x: the dofs of one node row in workgroups; y, z: the node rows (amg_check_opts keeps both within 65535)
 inline dim3 transfer_grid(const int32_t d[3], int bs) { return dim3((unsigned)(((int64_t)d[0] * bs + kThreads - 1) / kThreads), (unsigned)d[1], (unsigned)d[2]); }

@@ -135,7 +135,9 @@ __global__ __launch_bounds__(kThreads) void amgs_tent_fill_kernel(const int32_t 
 // ---------------------------------------------------------------------------
 // grid coarsening: P = P_z (x) P_y (x) P_x (x) I_bs from the node grids alone, one row (fine dof) per thread.  i + i / 2
 // parents lie before fine index i of a halved direction (i of one that keeps its nodes), so the row's offset follows
-// from its indices: no count, no scan.  Columns ascend (z outermost), the weights are 1, 1/2, 1/4 or 1/8.
+// from its indices: no count, no scan.  The last index of an even halved side (an odd index that is the last one) is a
+// coarse node itself: one parent, (i + 1) / 2, so such a side has fx + fx / 2 - 1 parents.  Columns ascend (z
+// outermost), the weights are 1, 1/2, 1/4 or 1/8.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void amgs_grid_prolongator_kernel(int32_t fx, int32_t fy, int32_t fz, int32_t cx, int32_t cy,
                                                                          int32_t cz, int bs, int32_t *__restrict__ rp,
@@ -146,11 +148,12 @@ __global__ __launch_bounds__(kThreads) void amgs_grid_prolongator_kernel(int32_t
     const int32_t node = (int32_t)(f / bs), c = (int32_t)(f - (int64_t)node * bs);
     const int32_t i = node % fx, j = (node / fx) % fy, k = node / fx / fy;
     const bool hx = cx != fx, hy = cy != fy, hz = cz != fz;
-    const int32_t nx = hx && (i & 1) ? 2 : 1, ny = hy && (j & 1) ? 2 : 1, nz = hz && (k & 1) ? 2 : 1;
-    const int32_t ic = hx ? i >> 1 : i, jc = hy ? j >> 1 : j, kc = hz ? k >> 1 : k;
+    const int32_t lx = hx && (i & 1) && i == fx - 1, ly = hy && (j & 1) && j == fy - 1, lz = hz && (k & 1) && k == fz - 1;
+    const int32_t nx = hx && (i & 1) && !lx ? 2 : 1, ny = hy && (j & 1) && !ly ? 2 : 1, nz = hz && (k & 1) && !lz ? 2 : 1;
+    const int32_t ic = hx ? (i + lx) >> 1 : i, jc = hy ? (j + ly) >> 1 : j, kc = hz ? (k + lz) >> 1 : k;
     // parents before this index per direction, and in a whole direction
     const int64_t bx = hx ? i + (i >> 1) : i, by = hy ? j + (j >> 1) : j, bz = hz ? k + (k >> 1) : k;
-    const int64_t tx = hx ? fx + (fx >> 1) : fx, ty = hy ? fy + (fy >> 1) : fy;
+    const int64_t tx = hx ? fx + (fx >> 1) - !(fx & 1) : fx, ty = hy ? fy + (fy >> 1) - !(fy & 1) : fy;
     const int32_t len = nx * ny * nz;
     int64_t p = (tx * ty * bz + nz * (tx * by + ny * bx)) * bs + (int64_t)c * len;
     rp[f] = (int32_t)p;

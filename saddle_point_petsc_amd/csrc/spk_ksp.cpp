@@ -144,6 +144,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "matrixfree") o.transfer = SPK_AMG_TRANSFER_MATRIX_FREE;
         else if (v == "stored") o.transfer = SPK_AMG_TRANSFER_STORED;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (matrixfree | stored)");
+    } else if (key == "-spk_mg_sides") {
+        if (!val) return need("odd or any");
+        const std::string v(val);
+        if (v == "odd") o.sides = SPK_AMG_SIDES_ODD;
+        else if (v == "any") o.sides = SPK_AMG_SIDES_ANY;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (odd | any)");
     } else if (key == "-mg_levels_pc_type") {
         if (!val) return need("a type");
         if (std::string(val) != "jacobi") return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (jacobi)");
@@ -637,9 +643,10 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                         amg_active(k) ? "fieldsplit_0" : "K = A", ai.levels, ai.block_size, ai.operator_complexity, ai.setup_seconds,
                         ai.setup == SPK_AMG_SETUP_DEVICE ? "device" : "host");
             if (grid)
-                std::printf("    smoother %s x %d, transfers %s, coarse_eq_limit %d\n",
+                std::printf("    smoother %s x %d, transfers %s, sides %s, coarse_eq_limit %d\n",
                             o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its,
-                            o.transfer == SPK_AMG_TRANSFER_STORED ? "stored (CSR)" : "matrix-free", o.coarse_eq_limit);
+                            o.transfer == SPK_AMG_TRANSFER_STORED ? "stored (CSR)" : "matrix-free",
+                            ai.sides == SPK_AMG_SIDES_ANY ? "any (even sides halve too)" : "odd", o.coarse_eq_limit);
             else
                 std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
                             o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,

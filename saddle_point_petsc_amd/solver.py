@@ -46,17 +46,20 @@ AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV = 0, 1, 2, 3
 AMG_SETUP_HOST, AMG_SETUP_DEVICE = 0, 1
 AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID = 0, 1
 AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED = 0, 1
+AMG_SIDES_ODD, AMG_SIDES_ANY = 0, 1
 SPK_ERR_ARG = -1   # include/spk.h
 _SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
 _SETUPS = {"host": AMG_SETUP_HOST, "device": AMG_SETUP_DEVICE}
 _COARSENINGS = {"aggregation": AMG_COARSEN_AGGREGATION, "grid": AMG_COARSEN_GRID}
 _TRANSFERS = {"matrixfree": AMG_TRANSFER_MATRIX_FREE, "stored": AMG_TRANSFER_STORED}
+_SIDES = {"odd": AMG_SIDES_ODD, "any": AMG_SIDES_ANY}
 
 
 def amg_opts(**kw):
     """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
-    'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored'; grid=(mx, my[, mz]) are the
-    nodes per side that grid coarsening halves)."""
+    'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored', sides 'odd' / 'any';
+    grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
+    ones too)."""
     o = AmgOpts()
     lib.spk_default_amg_opts(C.byref(o))
     for k, v in kw.items():
@@ -70,6 +73,8 @@ def amg_opts(**kw):
             v = _COARSENINGS[v]
         if k == "transfer" and isinstance(v, str):
             v = _TRANSFERS[v]
+        if k == "sides" and isinstance(v, str):
+            v = _SIDES[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         if k == "grid":
@@ -93,7 +98,7 @@ def _amg_info(ai):
     return dict(levels=L, block_size=ai.block_size, rows=list(ai.rows[:L]), nnz=list(ai.nnz[:L]),
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
-                dims=[tuple(ai.dims[l]) for l in range(L)])
+                dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides)
 
 
 def _amg_matrix(fn, level, which):

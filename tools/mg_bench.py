@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Grid-coarsening multigrid (-pc_type mg) against the smoothed aggregation it leaves untouched (-pc_type gamg) on one
 GPU, in one process:
-    python tools/mg_bench.py [--grids 257 513 1025] [--reps 5] [--out profiles/FILE.jsonl]
+    python tools/mg_bench.py [--grids 257 513 1025] [--sides odd|any] [--reps 5] [--out profiles/FILE.jsonl]
+--sides any (-spk_mg_sides any) lets mg coarsen even sides, so --grids 256 512 1024 run; every emitted line records it.
 K = A, FGMRES(30) to rtol 1e-8, both hierarchies built on the device.  Per grid one context per preconditioner; after one
 warm-up round, --reps alternating rounds of set-up -> solve -> V-cycle timing (spk_pc_apply back to back on device
 vectors).  Per row: levels, operator complexity, and median (min..max) of the V-cycle, the solve, the set-up and set-up +
@@ -31,6 +32,7 @@ PEAK = 8.0e12   # HBM bytes per second
 ap = argparse.ArgumentParser()
 ap.add_argument("--grids", type=int, nargs="+", default=[257, 513, 1025])
 ap.add_argument("--grid", type=int, default=1025, help="--transfers / --transfers-report: nodes per side")
+ap.add_argument("--sides", choices=["odd", "any"], default="odd", help="mg's side rule (-spk_mg_sides)")
 ap.add_argument("--rtol", type=float, default=1e-8)
 ap.add_argument("--reps", type=int, default=5, help="alternating rounds after the warm-up round")
 ap.add_argument("--no-saddle", action="store_true", help="leave out the saddle rows")
@@ -41,7 +43,7 @@ a = ap.parse_args()
 
 
 def emit(row):
-    line = json.dumps(row)
+    line = json.dumps(dict(row, sides=a.sides))
     print(line, flush=True)
     if a.out:
         with open(a.out, "a") as fh:
@@ -52,8 +54,13 @@ def mmm(v, scale=1.0, digits=6):
     return dict(median=round(float(np.median(v)) * scale, digits), min=round(min(v) * scale, digits), max=round(max(v) * scale, digits))
 
 
+def coarse_side(m):
+    """the side rule: an odd side >= 5 halves, under `any` an even side >= 4 too, to m // 2 + 1"""
+    return m // 2 + 1 if (m >= 4 if a.sides == "any" else m >= 5 and m % 2 == 1) else m
+
+
 def transfer_models(grid):
-    n, nc = 2 * grid * grid, 2 * ((grid + 1) // 2) ** 2
+    n, nc = 2 * grid * grid, 2 * coarse_side(grid) ** 2
     return dict(prolong=8 * (2 * n + nc), restrict=8 * (2 * n + nc))
 
 
@@ -95,7 +102,7 @@ if a.transfers:
     rng = np.random.default_rng(g)
     with S.Context(0) as c:
         c.set_block(S.BLOCK_A00, A)
-        c.pc_setup(S.PC_JACOBI, amg=dict(coarsening="grid", grid=(g, g), setup="device"))
+        c.pc_setup(S.PC_JACOBI, amg=dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides))
         info = c.amg_info()
         nf, nc = info["rows"][0], info["rows"][1]
         e, y, b, t = rng.standard_normal(nc), rng.standard_normal(nf), rng.standard_normal(nf), rng.standard_normal(nf)
@@ -104,10 +111,10 @@ if a.transfers:
                 c.debug_amg_transfer(0, "prolong", e, y, stored=stored)
             for stored in (False, True):
                 c.debug_amg_transfer(0, "restrict", b, t, stored=stored)
-    print(json.dumps(dict(mode="transfers-launched", grid=g, rows=[nf, nc], rounds=a.reps + 1)), flush=True)
+    print(json.dumps(dict(mode="transfers-launched", grid=g, sides=a.sides, rows=[nf, nc], rounds=a.reps + 1)), flush=True)
     sys.exit(0)
 
-KINDS = dict(mg=lambda g: dict(coarsening="grid", grid=(g, g), setup="device"), gamg=lambda g: dict(setup="device"))
+KINDS = dict(mg=lambda g: dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides), gamg=lambda g: dict(setup="device"))
 
 
 def compare(system, g, A, B, rhs):
