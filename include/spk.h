@@ -334,8 +334,25 @@ enum { SPK_AMG_SETUP_HOST = 0, SPK_AMG_SETUP_DEVICE = 1 };
 enum { SPK_AMG_COARSEN_AGGREGATION = 0, SPK_AMG_COARSEN_GRID = 1 };
 enum { SPK_AMG_TRANSFER_MATRIX_FREE = 0, SPK_AMG_TRANSFER_STORED = 1 };
 enum { SPK_AMG_SIDES_ODD = 0, SPK_AMG_SIDES_ANY = 1 };
+/* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail and
+ * tail_rows alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
+ *     cycle(l, fresh): l == L-1: COARSE; return
+ *                      fresh ? PRE0 : PRE;  DOWN;  cycle(l+1, true);  if W and l+1 < L-1: cycle(l+1, false);  UP;  POST
+ * (PETSc's PCMGMCycle): level l < L-1 is entered 2^l times, the coarsest 2^(L-2) times (a repeated exact solve changes
+ * nothing).  PRE0: nu smoothing steps from the zero guess, PRE: nu steps from the level's own iterate (the second visit),
+ * DOWN: b_{l+1} = R_l (b_l - A_l y_l), COARSE: y = A_L^-1 b, UP: y_l += P_l y_{l+1}, POST: nu steps from y_l.  Same smoother
+ * before and after, R = P^T and an exact coarse solve keep the W-cycle symmetric, like the V-cycle.
+ * The tail: the coarse levels l >= tail_first >= 1 -- those whose every level has at most tail_rows rows -- run as one
+ * workgroup in one launch per tail run (a maximal stretch of consecutive steps on those levels), with a workgroup barrier
+ * where the launches have a kernel boundary; the bits are those of the launches.  LAUNCHES: every step a launch of its own
+ * (no tail).  AUTO: LAUNCHES under V, FUSED under W.  tail_rows 0: the library's default (SPK_AMG_TAIL_ROWS_DEFAULT). */
+enum { SPK_AMG_CYCLE_V = 0, SPK_AMG_CYCLE_W = 1 };
+enum { SPK_AMG_TAIL_AUTO = 0, SPK_AMG_TAIL_LAUNCHES = 1, SPK_AMG_TAIL_FUSED = 2 };
+enum { SPK_AMG_STEP_PRE0 = 0, SPK_AMG_STEP_PRE = 1, SPK_AMG_STEP_DOWN = 2, SPK_AMG_STEP_COARSE = 3, SPK_AMG_STEP_UP = 4,
+       SPK_AMG_STEP_POST = 5 };
 #define SPK_AMG_MAX_LEVELS 16
 #define SPK_AMG_MAX_COARSE 1024
+#define SPK_AMG_TAIL_ROWS_DEFAULT 1024   /* tail_rows = 0 (DESIGN.md "The cycle and the fused tail" has the sweep behind it) */
 typedef struct spk_amg_opts {
     int32_t max_levels;       /* -pc_mg_levels                      (10; 1..SPK_AMG_MAX_LEVELS) */
     int32_t coarse_eq_limit;  /* -pc_gamg_coarse_eq_limit           (50)  */
@@ -353,6 +370,9 @@ typedef struct spk_amg_opts {
     int32_t grid[3];          /* grid coarsening: nodes per side mx, my, mz (mz = 1 in 2-D); rows = bs mx my mz */
     int32_t transfer;         /* -spk_mg_transfer matrixfree|stored: SPK_AMG_TRANSFER_* (grid coarsening only) */
     int32_t sides;            /* -spk_mg_sides odd|any: SPK_AMG_SIDES_* (odd; grid coarsening only) */
+    int32_t cycle;            /* -spk_mg_cycle v|w: SPK_AMG_CYCLE_*  (v) */
+    int32_t tail;             /* -spk_mg_tail auto|launches|fused: SPK_AMG_TAIL_* (auto: launches under v, fused under w) */
+    int32_t tail_rows;        /* -spk_mg_tail_rows n: the largest level the fused tail takes (0: SPK_AMG_TAIL_ROWS_DEFAULT; else >= 1) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -367,6 +387,9 @@ typedef struct spk_amg_info {
     int32_t coarsening;                      /* SPK_AMG_COARSEN_* */
     int32_t dims[SPK_AMG_MAX_LEVELS][3];     /* grid coarsening: the node grid of every level (else 0) */
     int32_t sides;                           /* grid coarsening: SPK_AMG_SIDES_* of the rule that built it (else 0) */
+    int32_t cycle;                           /* SPK_AMG_CYCLE_* of the application */
+    int32_t tail_first;                      /* the first level inside the fused tail launch (>= 1), -1: no tail */
+    int32_t tail_launches;                   /* launches of the tail kernel per application (0 without a tail) */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -426,6 +449,9 @@ int spk_amg_host_info(const spk_amg_hier *h, spk_amg_info *info);
 int spk_amg_host_level(const spk_amg_hier *h, int level, int which, int32_t *nrows, int32_t *ncols, int64_t *nnz,
                        int32_t *rowptr, int32_t *colidx, double *val);
 int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, int32_t *agg);
+/* Test hook (host only): the steps of one cycle over `levels` levels (1..SPK_AMG_MAX_LEVELS) in the order both routes
+ * run them, as pairs of int32 (SPK_AMG_STEP_*, level).  steps NULL: *nsteps alone. */
+int spk_amg_cycle_steps(int32_t levels, int32_t cycle, int64_t *nsteps, int32_t *steps);
 
 /* What stands for the Schur complement in SPK_PC_SCHUR (PETSc: -pc_fieldsplit_schur_precondition):
  *   SPK_SCHUR_PRE_SELFP_DIAG (default): S^ = diag(B diag(A)^-1 B^T), divided by entry by entry;

@@ -19,4 +19,6 @@ from .solver import (  # noqa: F401
     DIVERGED_INDEFINITE_MAT, PIPECGRR_TAU_DEFAULT, SCHUR_PRE_SELFP_DIAG, SCHUR_PRE_FULL,
     AmgHierarchy, amg_opts, AMG_CHEBYSHEV, AMG_RICHARDSON, AMG_SETUP_HOST, AMG_SETUP_DEVICE, AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID,
     AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED, AMG_SIDES_ODD, AMG_SIDES_ANY, AMG_OP, AMG_PROLONG, AMG_TENTATIVE, AMG_COARSE_INV,
+    AMG_CYCLE_V, AMG_CYCLE_W, AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED, amg_cycle_steps,
+    AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST,
 )

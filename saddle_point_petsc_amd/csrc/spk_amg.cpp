@@ -1,7 +1,8 @@
 // spk_amg.cpp -- smoothed-aggregation algebraic multigrid (-pc_type gamg): the hierarchy, built at KSPSetUp from the
 // A00 block by one loop (build_levels) over two routes -- HostRoute: on the host, then uploaded (the default); DevRoute:
-// on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the V-cycle's launch sequence (kernels:
-// spk_k_amg.hip).
+// on the device (-spk_gamg_setup device, kernels: spk_k_amg_setup.hip) -- and the cycle's launch sequence (kernels:
+// spk_k_amg.hip): amg_apply walks the step list of spk_host.cpp's amg_cycle_steps (V or W), a tail run of coarse levels
+// as one launch where the options ask for it (amg_plan_cycle).
 // The same loop builds the grid-coarsened hierarchy (-pc_type mg, SPK_AMG_COARSEN_GRID): where the node grid is known a
 // level halves its odd sides (-spk_mg_sides any: the even ones too) and P is the tensor product of linear interpolations -- no graph, no aggregation, no
 // prolongator smoothing; everything else (Ritz values, Galerkin products, coarse inverse, refresh) is shared.
@@ -465,6 +466,15 @@ void smoother_interval(const spk_amg_opts &o, int l, double lmin, double lmax, d
         fail(SPK_ERR_ARG, "amg: Chebyshev interval [%g, %g] on level %d is empty or not positive (esteig)", *lo, *hi, l);
 }
 
+// what the application's options make of the levels `info` lists: after every build and every refresh, on both routes
+// (build_levels clears the info and the host-route refresh copies the host's over it)
+void fill_cycle_info(const spk_amg_opts &o, spk_amg_info &info)
+{
+    info.cycle = o.cycle;
+    info.tail_first = amg_tail_first(info.levels, info.rows, o.cycle, o.tail, o.tail_rows);
+    info.tail_launches = info.tail_first < 0 ? 0 : (int32_t)amg_tail_runs(amg_cycle_steps(info.levels, o.cycle), info.tail_first).size();
+}
+
 // The set-up, stated once: the level loop with every rule of the algorithm and the whole of `info`.  A route supplies
 // what differs between the host and the device -- where the matrices live and what computes them:
 //   rows(l), nnz(l) of A_l;  graph(l, bs, theta, gp, gi): the strong-connection graph of its nodes, in host vectors
@@ -698,6 +708,11 @@ void amg_check_opts(const spk_amg_opts &o)
             fail(SPK_ERR_UNSUPPORTED, "amg: the matrix-free transfers take at most 65535 nodes in y and z (grid %d x %d x %d) -- "
                  "use -spk_mg_transfer stored", o.grid[0], o.grid[1], o.grid[2]);
     }
+    if (o.cycle != SPK_AMG_CYCLE_V && o.cycle != SPK_AMG_CYCLE_W)
+        fail(SPK_ERR_ARG, "amg: cycle %d is neither SPK_AMG_CYCLE_V (0) nor SPK_AMG_CYCLE_W (1)", o.cycle);
+    if (o.tail != SPK_AMG_TAIL_AUTO && o.tail != SPK_AMG_TAIL_LAUNCHES && o.tail != SPK_AMG_TAIL_FUSED)
+        fail(SPK_ERR_ARG, "amg: tail %d is none of SPK_AMG_TAIL_AUTO (0), SPK_AMG_TAIL_LAUNCHES (1), SPK_AMG_TAIL_FUSED (2)", o.tail);
+    if (o.tail_rows < 0) fail(SPK_ERR_ARG, "amg: tail_rows %d < 0 (0: the default of %d)", o.tail_rows, SPK_AMG_TAIL_ROWS_DEFAULT);
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
@@ -716,6 +731,7 @@ void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
     h.dinv_sum = abs_sum(h.lv[0].dinv);
     HostRoute r{h};
     build_levels(r, o.block_size > 0 ? o.block_size : detect_bs(h.lv[0].A), o, SPK_AMG_SETUP_HOST, t0, h.info);
+    fill_cycle_info(o, h.info);
 }
 
 void amg_refresh(AmgHier &h, const double *val)
@@ -728,6 +744,7 @@ void amg_refresh(AmgHier &h, const double *val)
     HostRoute r{h, binade_scale(h.dinv_sum, abs_sum(F.dinv))};
     try {
         refresh_levels(r, h.o, t0, h.info);
+        fill_cycle_info(h.o, h.info);
     } catch (...) {   // half-refreshed: never to be read or applied
         h.lv.clear();
         h.cinv.clear();
@@ -831,6 +848,61 @@ static void alloc_cycle_vectors(AmgDev &d, int64_t ld)
     }
 }
 
+// The application's plan, rebuilt at every set-up (build or refresh) from the options and the levels as they are now:
+// the steps of the cycle, the tail runs, and -- where there is a tail -- the kernel's descriptor and step list on the
+// device: the pointers, the smoothing coefficients and, per step, the buffer that holds the iterate (smooth()'s rule:
+// every smoothing step writes the buffer its input is not in; PRE0 starts into ya; the coarse solve writes ya).
+static void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o)
+{
+    fill_cycle_info(o, d.info);
+    const int L = (int)d.lv.size(), t = d.info.tail_first, nu = o.smooth_its;
+    d.steps = amg_cycle_steps(L, o.cycle);
+    d.runs = amg_tail_runs(d.steps, t);
+    d.run_sel.assign(d.runs.size(), 0);
+    d.tsteps.clear();
+    if (t < 0) {
+        d.tail_desc.release();
+        d.tail_steps.release();
+        return;
+    }
+    if (d.steps.size() > (size_t)INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "amg: the cycle has more steps than 32 bits count");
+    d.tsteps.resize(d.steps.size());
+    int32_t sel[SPK_AMG_MAX_LEVELS] = {};
+    size_t run = 0;
+    for (size_t i = 0; i < d.steps.size(); ++i) {
+        const AmgStep st = d.steps[i];
+        d.tsteps[i] = k::AmgTailStep{st.kind, st.level, sel[st.level], st.level + 1 < L ? sel[st.level + 1] : 0};
+        if (st.kind == SPK_AMG_STEP_PRE0) sel[st.level] = (nu & 1) ? 0 : 1;
+        else if (st.kind == SPK_AMG_STEP_PRE || st.kind == SPK_AMG_STEP_POST) sel[st.level] ^= nu & 1;
+        else if (st.kind == SPK_AMG_STEP_COARSE) sel[st.level] = 0;
+        if (run < d.runs.size() && (size_t)d.runs[run].second == i + 1) d.run_sel[run++] = sel[t];   // where the run leaves level t's iterate
+    }
+    auto desc = std::make_unique<k::AmgTailDesc>();
+    std::memset(desc.get(), 0, sizeof *desc);
+    d.tail_steps.upload(d.tsteps.data(), d.tsteps.size());
+    desc->cinv = d.cinv.p;
+    desc->steps = d.tail_steps.p;
+    desc->first = t;
+    desc->levels = L;
+    for (int l = t; l < L; ++l) {
+        AmgLevelDev &D = d.lv[(size_t)l];
+        k::AmgTailLevel &V = desc->lv[l];
+        V.arp = D.A.rowptr.p, V.aci = D.A.colidx.p, V.av = D.A.val.p;
+        V.dinv = D.dinv.p;
+        V.b = D.b.p, V.ya = D.ya.p, V.yb = D.yb.p;
+        V.n = D.n;
+        V.nu = nu;
+        if (l + 1 == L) continue;
+        V.nc = d.lv[(size_t)l + 1].n;
+        V.prp = D.P.rowptr.p, V.pci = D.P.colidx.p, V.pv = D.P.val.p;
+        V.rrp = D.R.rowptr.p, V.rci = D.R.colidx.p, V.rv = D.R.val.p;
+        V.matrix_free = D.grid.matrix_free ? 1 : 0;
+        if (D.grid.on) V.g = k::grid_args(D.grid), V.bs = D.grid.bs, V.fz = D.grid.fd[2];
+        for (int q = 0; q < nu; ++q) V.alpha[q] = D.alpha[(size_t)q], V.beta[q] = D.beta[(size_t)q];
+    }
+    d.tail_desc.upload(desc.get(), 1);
+}
+
 // reuse on: what the next set-up compares before it refreshes -- the options, the sizes and a device copy of the
 // diagonal block's pattern as the context stores it
 static void keep_pattern(spk_ctx *c, AmgDev &d)
@@ -876,6 +948,7 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
     if (c->amg_reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info = h.info;
+    amg_plan_cycle(*d, h.o);
     d->info.setup_seconds += seconds_since(t0);
     c->amg_d = std::move(d);
     c->amg_h = std::move(hp);
@@ -1210,6 +1283,7 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
     DevRoute r{c, *d, o, A0, dinv0.p, c->stream, d->reuse != nullptr, nullptr};
     build_levels(r, bs, o, SPK_AMG_SETUP_DEVICE, t0, d->info);
     alloc_cycle_vectors(*d, c->ld);
+    amg_plan_cycle(*d, o);
     if (d->reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info.setup_seconds = seconds_since(t0);   // the vectors count too, up to the synchronise
@@ -1246,8 +1320,12 @@ void amg_refresh_ctx(spk_ctx *c)
     AmgDev &d = *c->amg_d;
     AmgReuse &ru = *d.reuse;
     const size_t L = d.lv.size();
+    // cycle, tail and tail_rows steer the application, not the hierarchy (amg_can_refresh does not compare them): the
+    // refresh takes the ones this set-up was given
+    ru.o.cycle = c->amg_opts.cycle, ru.o.tail = c->amg_opts.tail, ru.o.tail_rows = c->amg_opts.tail_rows;
     if (c->amg_h) {   // the host route: the values down, the host refresh, the values of the levels up
         AmgHier &h = c->amg_h->h;
+        h.o.cycle = ru.o.cycle, h.o.tail = ru.o.tail, h.o.tail_rows = ru.o.tail_rows;
         std::vector<double> val((size_t)c->Ad.nnz);
         if (!val.empty()) SPK_HIP(hipMemcpyAsync(val.data(), c->Ad.val.p, sizeof(double) * val.size(), hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
@@ -1279,6 +1357,7 @@ void amg_refresh_ctx(spk_ctx *c)
         refresh_levels(r, ru.o, t0, d.info);
         SPK_HIP(hipDeviceSynchronize());
     }
+    amg_plan_cycle(d, ru.o);   // the coefficients are new, and the device route's coarse inverse lies elsewhere
     d.info.setup_seconds = seconds_since(t0);
 }
 
@@ -1385,23 +1464,37 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
     const size_t L = d.lv.size();
     std::vector<double *> cur(L, nullptr);
     auto rhs = [&](size_t l) -> const double * { return l == 0 ? x : d.lv[l].b.p; };
-    for (size_t l = 0; l + 1 < L; ++l) {   // down: pre-smoothing, residual, restriction
+    size_t run = 0;
+    for (size_t i = 0; i < d.steps.size(); ++i) {   // the cycle's steps in order (amg_cycle_steps); under V: down, coarse, up
+        if (run < d.runs.size() && (size_t)d.runs[run].first == i) {   // a tail run: one launch of one workgroup
+            const size_t t = (size_t)d.info.tail_first;
+            k::amg_tail(d.tail_desc.p, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, s);
+            cur[t] = d.run_sel[run] ? d.lv[t].yb.p : d.lv[t].ya.p;
+            i = (size_t)d.runs[run++].second - 1;
+            continue;
+        }
+        const size_t l = (size_t)d.steps[i].level;
         AmgLevelDev &D = d.lv[l];
-        cur[l] = smooth(c, D, (int)l, rhs(l), nullptr, done);
-        if (l == 0) a_mult(c, cur[l], D.t.p, nullptr, nullptr, done, false, nullptr);
-        else k::amg_spmv(D.A, cur[l], D.ya.p == cur[l] ? D.yb.p : D.ya.p, done, s);
-        const double *t = l == 0 ? D.t.p : (D.ya.p == cur[l] ? D.yb.p : D.ya.p);
-        if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b.p, done, s);
-        else k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
-    }
-    AmgLevelDev &C = d.lv[L - 1];   // exact coarse solve
-    k::amg_dense(d.cinv.p, C.n, rhs(L - 1), C.ya.p, done, s);
-    cur[L - 1] = C.ya.p;
-    for (size_t l = L - 1; l-- > 0;) {   // up: prolongation + correction, post-smoothing
-        AmgLevelDev &D = d.lv[l];
-        if (D.grid.matrix_free) k::amg_prolong_add_grid(D.grid, cur[l + 1], cur[l], done, s);
-        else k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
-        cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done);
+        switch (d.steps[i].kind) {
+        case SPK_AMG_STEP_PRE0: cur[l] = smooth(c, D, (int)l, rhs(l), nullptr, done); break;
+        case SPK_AMG_STEP_PRE:
+        case SPK_AMG_STEP_POST: cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done); break;
+        case SPK_AMG_STEP_DOWN: {   // residual, restriction
+            if (l == 0) a_mult(c, cur[l], D.t.p, nullptr, nullptr, done, false, nullptr);
+            else k::amg_spmv(D.A, cur[l], D.ya.p == cur[l] ? D.yb.p : D.ya.p, done, s);
+            const double *t = l == 0 ? D.t.p : (D.ya.p == cur[l] ? D.yb.p : D.ya.p);
+            if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b.p, done, s);
+            else k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
+            break;
+        }
+        case SPK_AMG_STEP_COARSE:   // exact coarse solve
+            k::amg_dense(d.cinv.p, D.n, rhs(l), D.ya.p, done, s);
+            cur[l] = D.ya.p;
+            break;
+        default:   // SPK_AMG_STEP_UP: prolongation + correction
+            if (D.grid.matrix_free) k::amg_prolong_add_grid(D.grid, cur[l + 1], cur[l], done, s);
+            else k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
+        }
     }
     if (last) *last = cur[0];   // the caller's own pass reads the iterate where it lies
     else k::amg_out(mode, c->n_local, cur[0], y, done, s);
@@ -1494,6 +1587,16 @@ int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, i
     if (!h) return SPK_ERR_ARG;
     SPK_HOST_TRY
     spk::aggregates_out(h->h.lv, h->h.info, level, nnodes, agg);
+    SPK_HOST_CATCH
+}
+
+int spk_amg_cycle_steps(int32_t levels, int32_t cycle, int64_t *nsteps, int32_t *steps)
+{
+    if (!nsteps) return SPK_ERR_ARG;
+    SPK_HOST_TRY
+    const std::vector<spk::AmgStep> st = spk::amg_cycle_steps(levels, cycle);
+    *nsteps = (int64_t)st.size();
+    for (size_t i = 0; steps && i < st.size(); ++i) steps[2 * i] = st[i].kind, steps[2 * i + 1] = st[i].level;
     SPK_HOST_CATCH
 }
 

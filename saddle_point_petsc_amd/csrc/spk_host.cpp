@@ -439,6 +439,59 @@ void transpose_rows(int32_t m, int32_t nl, const int32_t *rowptr, const int32_t 
     }, max_threads);
 }
 
+// ---------------------------------------------------------------------------
+// the multigrid cycle: its steps in order, and which of them the fused tail takes
+// ---------------------------------------------------------------------------
+static void cycle_steps(std::vector<AmgStep> &out, int l, int L, bool w, bool fresh)
+{
+    if (l == L - 1) { out.push_back({SPK_AMG_STEP_COARSE, l}); return; }
+    out.push_back({fresh ? SPK_AMG_STEP_PRE0 : SPK_AMG_STEP_PRE, l});
+    out.push_back({SPK_AMG_STEP_DOWN, l});
+    cycle_steps(out, l + 1, L, w, true);
+    if (w && l + 1 < L - 1) cycle_steps(out, l + 1, L, w, false);
+    out.push_back({SPK_AMG_STEP_UP, l});
+    out.push_back({SPK_AMG_STEP_POST, l});
+}
+
+std::vector<AmgStep> amg_cycle_steps(int levels, int cycle)
+{
+    if (levels < 1 || levels > SPK_AMG_MAX_LEVELS) fail(SPK_ERR_ARG, "amg: %d levels outside [1,%d]", levels, SPK_AMG_MAX_LEVELS);
+    if (cycle != SPK_AMG_CYCLE_V && cycle != SPK_AMG_CYCLE_W)
+        fail(SPK_ERR_ARG, "amg: cycle %d is neither SPK_AMG_CYCLE_V (0) nor SPK_AMG_CYCLE_W (1)", cycle);
+    std::vector<AmgStep> out;
+    cycle_steps(out, 0, levels, cycle == SPK_AMG_CYCLE_W, true);
+    return out;
+}
+
+int amg_resolve_tail(int cycle, int tail)
+{
+    if (tail != SPK_AMG_TAIL_AUTO) return tail;
+    return cycle == SPK_AMG_CYCLE_W ? SPK_AMG_TAIL_FUSED : SPK_AMG_TAIL_LAUNCHES;
+}
+
+int amg_tail_first(int levels, const int32_t *rows, int cycle, int tail, int tail_rows)
+{
+    if (levels < 2 || amg_resolve_tail(cycle, tail) != SPK_AMG_TAIL_FUSED) return -1;
+    const int32_t limit = tail_rows > 0 ? tail_rows : SPK_AMG_TAIL_ROWS_DEFAULT;
+    int t = levels;
+    while (t > 1 && rows[t - 1] <= limit) --t;
+    return t < levels ? t : -1;
+}
+
+std::vector<std::pair<int64_t, int64_t>> amg_tail_runs(const std::vector<AmgStep> &steps, int tail_first)
+{
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    if (tail_first < 1) return runs;
+    for (int64_t s = 0, n = (int64_t)steps.size(); s < n;) {
+        if (steps[(size_t)s].level < tail_first) { ++s; continue; }
+        int64_t e = s;
+        while (e < n && steps[(size_t)e].level >= tail_first) ++e;
+        runs.push_back({s, e});
+        s = e;
+    }
+    return runs;
+}
+
 // (G + G^T) / 2 into S, its Cholesky factor (lower, row-major, zeros above) into L.  A pivot at or below the rounding of
 // its own subtraction (64 eps S_jj) counts as zero: the rows of B are then linearly dependent to working precision.
 int schur_dense_factor(int m, const double *G, double *S, double *L)

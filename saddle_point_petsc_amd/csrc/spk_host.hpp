@@ -112,6 +112,19 @@ void gather_rows(int32_t m, const int32_t *rowptr, const int32_t *col, const dou
 void transpose_rows(int32_t m, int32_t nl, const int32_t *rowptr, const int32_t *col, const double *v, int32_t *trp, int32_t *tci,
                     double *tv, int max_threads = 0);
 
+// ---- the order of one multigrid cycle and the fused tail (spk_amg_opts.cycle / tail / tail_rows) ----
+// One source for both routes: the launches walk this list and the tail kernel interprets its share of it.
+struct AmgStep { int32_t kind, level; };   // kind: SPK_AMG_STEP_*
+// cycle(0, fresh) of include/spk.h over L levels (L >= 1; L == 1: the coarse solve alone)
+std::vector<AmgStep> amg_cycle_steps(int levels, int cycle);
+// SPK_AMG_TAIL_AUTO resolved: LAUNCHES under V, FUSED under W
+int amg_resolve_tail(int cycle, int tail);
+// the smallest t >= 1 such that every level l >= t has rows[l] <= tail_rows (0: SPK_AMG_TAIL_ROWS_DEFAULT); -1 when the
+// coarsest level exceeds it, with one level, or when `tail` resolves to LAUNCHES.  Level 0 is never in the tail.
+int amg_tail_first(int levels, const int32_t *rows, int cycle, int tail, int tail_rows);
+// the tail runs of a step list: maximal stretches [begin, end) of consecutive steps on levels >= tail_first (none for -1)
+std::vector<std::pair<int64_t, int64_t>> amg_tail_runs(const std::vector<AmgStep> &steps, int tail_first);
+
 // ---- the dense Schur complement of a few constraint rows (spk_pc_set_schur_pre) ----
 // G: m x m as computed; S = (G + G^T) / 2; L: its Cholesky factor (lower, row-major).  Returns -1, or the first pivot that
 // is not positive beyond rounding (S is not positive definite: linearly dependent rows of B)

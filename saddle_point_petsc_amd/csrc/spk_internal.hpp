@@ -818,6 +818,42 @@ struct AmgGrid {
         matrix_free = transfer == SPK_AMG_TRANSFER_MATRIX_FREE;
     }
 };
+// what the matrix-free transfer kernels take of an AmgGrid
+struct GridArgs {
+    int32_t fx, fy, cx, cy, cz;   // fine nodes in x, y; coarse nodes per side
+    int32_t hx, hy, hz;           // 1: the direction halves
+    int32_t ex, ey, ez;           // 1: ... and its fine side is even
+};
+inline GridArgs grid_args(const AmgGrid &a)
+{
+    const int32_t hx = a.cd[0] != a.fd[0], hy = a.cd[1] != a.fd[1], hz = a.cd[2] != a.fd[2];
+    return GridArgs{a.fd[0], a.fd[1], a.cd[0], a.cd[1], a.cd[2], hx, hy, hz, hx && !(a.fd[0] & 1), hy && !(a.fd[1] & 1), hz && !(a.fd[2] & 1)};
+}
+// The fused tail (amg_tail_kernel): what one workgroup needs of the levels >= first, device-resident, written at every
+// set-up.  The matrices, D^-1 and the coarse inverse are read-only in the launch; b, ya and yb are written and read by
+// other waves behind a workgroup barrier -- plain pointers.
+constexpr int kAmgMaxSmooth = 64;   // amg_check_opts: smooth_its <= 64
+struct AmgTailLevel {
+    const int32_t *arp, *aci, *prp, *pci, *rrp, *rci;   // CSR of A_l, and of P_l, R_l to level l + 1 (stored transfers)
+    const double *av, *pv, *rv, *dinv;
+    double *b, *ya, *yb;
+    int32_t n, nc;                  // rows of the level and of level l + 1
+    int32_t nu, bs, matrix_free, fz;   // smoothing steps; node size; the transfers are the grid rule's; fine nodes in z
+    GridArgs g;
+    double alpha[kAmgMaxSmooth], beta[kAmgMaxSmooth];
+};
+// one step as the kernel reads it: sel / sel_next = which buffer (0: ya, 1: yb) holds the iterate of the step's level /
+// of the level below it when the step begins, resolved on the host (smooth()'s rule) so that no thread chooses
+struct AmgTailStep { int32_t kind, level, sel, sel_next; };
+struct AmgTailDesc {
+    const double *cinv;         // the coarse inverse (level `levels` - 1), dense row-major
+    const AmgTailStep *steps;   // the whole cycle's list (a launch takes a range of it)
+    int32_t first, levels;
+    AmgTailLevel lv[SPK_AMG_MAX_LEVELS];   // by level; those below `first` are not filled
+};
+constexpr int kAmgTailThreads = 1024;   // one workgroup, 16 waves: 128 CSR rows or 16 dense rows per sweep
+// steps [s0, s1) of d->steps -- one tail run -- in one launch of one workgroup
+void amg_tail(const AmgTailDesc *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);
 // smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
 void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
 void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
@@ -902,6 +938,14 @@ struct AmgDev {
     DevBuf<double> cinv;
     spk_amg_info info{};         // what spk_get_amg_info returns, on both routes
     std::unique_ptr<AmgReuse> reuse;   // null unless built with reuse on
+    // the application's plan (amg_plan_cycle, at every set-up): the steps in order, the buffer each one finds its
+    // iterate in, the tail runs as ranges of steps, and the tail kernel's descriptor and step list on the device
+    std::vector<AmgStep> steps;
+    std::vector<k::AmgTailStep> tsteps;
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    std::vector<int32_t> run_sel;   // per run: the buffer (0: ya, 1: yb) it leaves the iterate of level tail_first in
+    DevBuf<k::AmgTailDesc> tail_desc;
+    DevBuf<k::AmgTailStep> tail_steps;
 };
 
 }  // namespace spk

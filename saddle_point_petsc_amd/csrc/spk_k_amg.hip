@@ -2,7 +2,9 @@
 // gfx950, wave64, FP64.  The levels >= 1 are CSR (sorted columns): eight lanes per row, each lane a fixed stride of
 // the row, the eight partial sums added in a fixed butterfly -- no atomics, the same bits on every run.  Every launch
 // takes the solver's `done` gate.  A level coarsened by the grid rule (-pc_type mg) applies P and R without reading
-// them: amg_prolong_grid_kernel / amg_restrict_grid_kernel below.
+// them: amg_prolong_grid_kernel / amg_restrict_grid_kernel below.  The per-row work of every kernel of a coarse level is a
+// __device__ function of the row index, shared with amg_tail_kernel, which runs the coarse levels' steps as one workgroup
+// in one launch (-spk_mg_tail fused) and gives the launches' bits.
 #include "spk_dict.hpp"
 
 namespace spk {
@@ -28,6 +30,34 @@ __device__ __forceinline__ double row_dot(const int32_t *__restrict__ rp, const 
     acc += __shfl_xor(acc, 1);
     return acc;
 }
+
+// one CSR row in its eight lanes (all eight call it together), MODE as amg_csr_kernel states them; lane 0 writes
+template <int MODE>
+__device__ __forceinline__ void csr_row(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                        const double *__restrict__ v, const double *x, const double *sub, const double *dinv,
+                                        const double *b, const double *yo, double *out, double alpha, double beta, int32_t i,
+                                        int lane)
+{
+    const double d = row_dot(rp, ci, v, x, MODE == 2 ? sub : nullptr, i, lane);
+    if (lane != 0) return;
+    if (MODE == 0 || MODE == 2) out[i] = d;
+    else if (MODE == 3) out[i] += d;
+    else {
+        const double y = x[i];
+        double r = y + alpha * (dinv[i] * (b[i] - d));
+        if (beta != 0.0) r += beta * (y - (yo ? yo[i] : 0.0));   // yo null: the zero initial guess
+        out[i] = r;
+    }
+}
+
+// row i of y = C b, C dense row-major n x n: the lanes of one wave, lane-strided sums, fixed butterfly; lane 0 writes
+__device__ __forceinline__ void dense_row(const double *__restrict__ C, int32_t n, const double *b, double *y, int32_t i, int lane)
+{
+    double acc = 0.0;
+    for (int32_t j = lane; j < n; j += kWave) acc += C[(size_t)i * n + j] * b[j];
+    for (int off = kWave / 2; off > 0; off /= 2) acc += __shfl_xor(acc, off);
+    if (lane == 0) y[i] = acc;
+}
 }  // namespace
 
 // MODE 0: out = A x
@@ -46,16 +76,7 @@ __global__ __launch_bounds__(kThreads) void amg_csr_kernel(const int32_t *__rest
     const int lane = threadIdx.x % kAmgLanes;
     const int32_t i = (int32_t)blockIdx.x * kAmgRows + (int32_t)(threadIdx.x / kAmgLanes);
     if (i >= n) return;   // whole groups of eight leave together: the butterfly stays inside live lanes
-    const double d = row_dot(rp, ci, v, x, MODE == 2 ? sub : nullptr, i, lane);
-    if (lane != 0) return;
-    if (MODE == 0 || MODE == 2) out[i] = d;
-    else if (MODE == 3) out[i] += d;
-    else {
-        const double y = x[i];
-        double r = y + alpha * (dinv[i] * (b[i] - d));
-        if (beta != 0.0) r += beta * (y - (yo ? yo[i] : 0.0));   // yo null: the zero initial guess
-        out[i] = r;
-    }
+    csr_row<MODE>(rp, ci, v, x, sub, dinv, b, yo, out, alpha, beta, i, lane);
 }
 
 // the fine level's vector pass behind the layout's own product t = A y:
@@ -160,10 +181,7 @@ __global__ __launch_bounds__(kThreads) void amg_dense_kernel(const double *__res
     const int lane = threadIdx.x % kWave;
     const int32_t i = (int32_t)blockIdx.x * (kThreads / kWave) + (int32_t)(threadIdx.x / kWave);
     if (i >= n) return;
-    double acc = 0.0;
-    for (int32_t j = lane; j < n; j += kWave) acc += C[(size_t)i * n + j] * b[j];
-    for (int off = kWave / 2; off > 0; off /= 2) acc += __shfl_xor(acc, off);
-    if (lane == 0) y[i] = acc;
+    dense_row(C, n, b, y, i, lane);
 }
 
 // mode 0: dst = src; mode 1: dst -= src
@@ -184,23 +202,16 @@ __global__ __launch_bounds__(kThreads) void amg_out_kernel(int mode, int64_t n, 
 // the additions alone defines the bits: ascending column of P (prolongation) or of R (restriction), from the first
 // product -- z outermost, x innermost.  The grid's x is one row of dofs of a node row, y and z the node row: no integer
 // division but by BS.
-struct GridArgs {
-    int32_t fx, fy, cx, cy, cz;   // fine nodes in x, y; coarse nodes per side
-    int32_t hx, hy, hz;           // 1: the direction halves
-    int32_t ex, ey, ez;           // 1: ... and its fine side is even
-};
-
-// y[f] += sum_parents w e[c]: one thread per fine dof; byte model: y read + y written + e read
+// (GridArgs: spk_internal.hpp)
+namespace {
+// fine dof xd of node row (j, k) of a grid with fz fine nodes in z: y[f] += sum_parents w e[c]
 template <int BS>
-__global__ __launch_bounds__(kThreads) void amg_prolong_grid_kernel(GridArgs g, const double *__restrict__ e, double *y,
-                                                                    const int32_t *__restrict__ done)
+__device__ __forceinline__ void prolong_grid_dof(const GridArgs g, int32_t fz, const double *e, double *y, int32_t xd, int32_t j,
+                                                 int32_t k)
 {
-    if (done && *done) return;
-    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the node row
-    if (xd >= g.fx * BS) return;
-    const int32_t i = xd / BS, c = xd - i * BS, j = (int32_t)blockIdx.y, k = (int32_t)blockIdx.z;
-    // the last index of an even halved side (the launch's z is the fine nodes in z): a coarse node itself
-    const int32_t lx = g.ex && i == g.fx - 1, ly = g.ey && j == g.fy - 1, lz = g.ez && k == (int32_t)gridDim.z - 1;
+    const int32_t i = xd / BS, c = xd - i * BS;
+    // the last index of an even halved side: a coarse node itself
+    const int32_t lx = g.ex && i == g.fx - 1, ly = g.ey && j == g.fy - 1, lz = g.ez && k == fz - 1;
     const bool ox = g.hx && (i & 1) && !lx, oy = g.hy && (j & 1) && !ly, oz = g.hz && (k & 1) && !lz;   // two parents in the direction
     const int32_t ic = g.hx ? (i + lx) >> 1 : i, jc = g.hy ? (j + ly) >> 1 : j, kc = g.hz ? (k + lz) >> 1 : k;   // the first parent
     const double w = (ox ? 0.5 : 1.0) * (oy ? 0.5 : 1.0) * (oz ? 0.5 : 1.0);
@@ -223,18 +234,14 @@ __global__ __launch_bounds__(kThreads) void amg_prolong_grid_kernel(GridArgs g, 
     y[f] = y[f] + s;
 }
 
-// out[c] = sum_children w (b[f] - t[f]): one thread per coarse dof, a gather over the <= 3 fine indices of every halved
-// direction (<= 27 terms), no atomics; byte model: b + t read + out written
+// coarse dof xd of coarse node row (jc, kc): out[c] = sum_children w (b[f] - t[f]), a gather over the <= 3 fine indices of
+// every halved direction (<= 27 terms), no atomics
 template <int BS>
-__global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g, int32_t fz, const double *__restrict__ b,
-                                                                     const double *__restrict__ t, double *__restrict__ out,
-                                                                     const int32_t *__restrict__ done)
+__device__ __forceinline__ void restrict_grid_dof(const GridArgs g, int32_t fz, const double *b, const double *t, double *out,
+                                                  int32_t xd, int32_t jc, int32_t kc)
 {
-    if (done && *done) return;
-    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the coarse node row
-    if (xd >= g.cx * BS) return;
-    const int32_t ic = xd / BS, c = xd - ic * BS, jc = (int32_t)blockIdx.y, kc = (int32_t)blockIdx.z;
-    // the last coarse index of an even halved side (the launch's z is the coarse nodes in z): the last fine index alone
+    const int32_t ic = xd / BS, c = xd - ic * BS;
+    // the last coarse index of an even halved side: the last fine index alone
     const int32_t tx = g.ex && ic == g.cx - 1, ty = g.ey && jc == g.cy - 1, tz = g.ez && kc == g.cz - 1;
     // the fine indices [lo, hi] of a direction and its centre (weight 1; the others 1/2); on an even side the last fine
     // index belongs to the last coarse one only
@@ -272,13 +279,146 @@ __global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g,
     }
     out[(((int64_t)kc * g.cy + jc) * g.cx) * BS + xd] = s;
 }
+}  // namespace
+
+// y[f] += sum_parents w e[c]: one thread per fine dof (the launch's y, z: the fine node rows); byte model: y read + y
+// written + e read
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amg_prolong_grid_kernel(GridArgs g, const double *__restrict__ e, double *y,
+                                                                    const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the node row
+    if (xd >= g.fx * BS) return;
+    prolong_grid_dof<BS>(g, (int32_t)gridDim.z, e, y, xd, (int32_t)blockIdx.y, (int32_t)blockIdx.z);
+}
+
+// out[c] = sum_children w (b[f] - t[f]): one thread per coarse dof (the launch's y, z: the coarse node rows); byte model:
+// b + t read + out written
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amg_restrict_grid_kernel(GridArgs g, int32_t fz, const double *__restrict__ b,
+                                                                     const double *__restrict__ t, double *__restrict__ out,
+                                                                     const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    const int32_t xd = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;   // dof within the coarse node row
+    if (xd >= g.cx * BS) return;
+    restrict_grid_dof<BS>(g, fz, b, t, out, xd, (int32_t)blockIdx.y, (int32_t)blockIdx.z);
+}
+
+// ---- the fused tail: the levels >= d->first as one workgroup in one launch ----------------------------------------
+// Steps [s0, s1) of the cycle's list (one tail run), interpreted in order by 1024 threads; where the launches have a kernel
+// boundary there is a workgroup barrier.  The per-row work is the functions above, called in loops: the bits are the
+// launches'.  Every thread reaches every barrier: the trip counts and every choice of buffer depend on the descriptor and
+// the step alone (workgroup-uniform); the row predicates depend on threadIdx.x / 8 (CSR rows) or / 64 (dense rows), so
+// the lanes of a butterfly enter it together; nothing returns before the last step.  The vectors b, ya, yb are written here
+// and read by other waves behind a barrier: one CU, workgroup scope, plain pointers.
+namespace {
+constexpr int kTailRows = kAmgTailThreads / kAmgLanes;   // CSR rows per sweep
+constexpr int kTailWaves = kAmgTailThreads / kWave;      // dense rows per sweep
+
+template <int MODE>
+__device__ __forceinline__ void tail_csr(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                         const double *__restrict__ v, int32_t n, const double *x, const double *sub,
+                                         const double *dinv, const double *b, const double *yo, double *out, double alpha,
+                                         double beta)
+{
+    const int lane = threadIdx.x % kAmgLanes;
+    const int32_t r = (int32_t)(threadIdx.x / kAmgLanes);
+    for (int32_t i0 = 0; i0 < n; i0 += kTailRows)
+        if (i0 + r < n) csr_row<MODE>(rp, ci, v, x, sub, dinv, b, yo, out, alpha, beta, i0 + r, lane);
+    __syncthreads();
+}
+
+// nu smoothing steps on level V from y (null: the zero guess), as smooth() orders them; ends in sel ^ (nu & 1) (from null: in ya for odd nu)
+__device__ __forceinline__ void tail_smooth(const AmgTailLevel &V, double *y)
+{
+    const double *prev = nullptr;
+    for (int32_t k = 0; k < V.nu; ++k) {
+        double *dst = y == V.ya ? V.yb : V.ya;
+        if (y) tail_csr<1>(V.arp, V.aci, V.av, V.n, y, nullptr, V.dinv, V.b, prev, dst, V.alpha[k], V.beta[k]);
+        else {   // amg_cheb_vec_kernel from the zero guess
+            const double alpha = V.alpha[k];
+            for (int32_t i = (int32_t)threadIdx.x; i < V.n; i += kAmgTailThreads) dst[i] = alpha * (V.dinv[i] * V.b[i]);
+            __syncthreads();
+        }
+        prev = y;
+        y = dst;
+    }
+}
+
+template <int BS>
+__device__ __forceinline__ void tail_restrict_grid(const AmgTailLevel &V, const double *t, double *out)
+{
+    const GridArgs g = V.g;
+    const int32_t w = g.cx * BS, wy = w * g.cy, tot = wy * g.cz;   // (tot = the rows of the next level <= tail_rows)
+    for (int32_t q = (int32_t)threadIdx.x; q < tot; q += kAmgTailThreads) {
+        const int32_t kc = q / wy, r = q - kc * wy, jc = r / w;
+        restrict_grid_dof<BS>(g, V.fz, V.b, t, out, r - jc * w, jc, kc);
+    }
+}
+template <int BS>
+__device__ __forceinline__ void tail_prolong_grid(const AmgTailLevel &V, const double *e, double *y)
+{
+    const GridArgs g = V.g;
+    const int32_t w = g.fx * BS, wy = w * g.fy, tot = wy * V.fz;
+    for (int32_t q = (int32_t)threadIdx.x; q < tot; q += kAmgTailThreads) {
+        const int32_t k = q / wy, r = q - k * wy, j = r / w;
+        prolong_grid_dof<BS>(g, V.fz, e, y, r - j * w, j, k);
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(kAmgTailThreads) void amg_tail_kernel(const AmgTailDesc *__restrict__ d, int32_t s0, int32_t s1,
+                                                                   const int32_t *__restrict__ done)
+{
+    if (done && *done) return;   // written by launches before this one only: the whole workgroup reads one value
+    for (int32_t s = s0; s < s1; ++s) {
+        const AmgTailStep st = d->steps[s];
+        const AmgTailLevel &V = d->lv[st.level];
+        double *y = st.sel ? V.yb : V.ya, *o = st.sel ? V.ya : V.yb;   // the level's iterate and the other buffer
+        switch (st.kind) {
+        case SPK_AMG_STEP_PRE0: tail_smooth(V, nullptr); break;
+        case SPK_AMG_STEP_PRE:
+        case SPK_AMG_STEP_POST: tail_smooth(V, y); break;
+        case SPK_AMG_STEP_DOWN: {   // o = A y, then b of the next level = R (b - o)
+            double *bn = d->lv[st.level + 1].b;
+            tail_csr<0>(V.arp, V.aci, V.av, V.n, y, nullptr, nullptr, nullptr, nullptr, o, 0.0, 0.0);
+            if (V.matrix_free) {
+                if (V.bs == 1) tail_restrict_grid<1>(V, o, bn);
+                else if (V.bs == 2) tail_restrict_grid<2>(V, o, bn);
+                else tail_restrict_grid<3>(V, o, bn);
+                __syncthreads();
+            } else {
+                tail_csr<2>(V.rrp, V.rci, V.rv, V.nc, V.b, o, nullptr, nullptr, nullptr, bn, 0.0, 0.0);
+            }
+            break;
+        }
+        case SPK_AMG_STEP_COARSE: {   // always into ya
+            const int lane = threadIdx.x % kWave;
+            const int32_t r = (int32_t)(threadIdx.x / kWave);
+            for (int32_t i0 = 0; i0 < V.n; i0 += kTailWaves)
+                if (i0 + r < V.n) dense_row(d->cinv, V.n, V.b, V.ya, i0 + r, lane);
+            __syncthreads();
+            break;
+        }
+        default: {   // SPK_AMG_STEP_UP: y += P e, e the iterate of the next level
+            const AmgTailLevel &N = d->lv[st.level + 1];
+            const double *e = st.sel_next ? N.yb : N.ya;
+            if (V.matrix_free) {
+                if (V.bs == 1) tail_prolong_grid<1>(V, e, y);
+                else if (V.bs == 2) tail_prolong_grid<2>(V, e, y);
+                else tail_prolong_grid<3>(V, e, y);
+                __syncthreads();
+            } else {
+                tail_csr<3>(V.prp, V.pci, V.pv, V.n, e, nullptr, nullptr, nullptr, nullptr, y, 0.0, 0.0);
+            }
+        }
+        }
+    }
+}
 
 namespace {
-inline GridArgs grid_args(const AmgGrid &a)
-{
-    const int32_t hx = a.cd[0] != a.fd[0], hy = a.cd[1] != a.fd[1], hz = a.cd[2] != a.fd[2];
-    return GridArgs{a.fd[0], a.fd[1], a.cd[0], a.cd[1], a.cd[2], hx, hy, hz, hx && !(a.fd[0] & 1), hy && !(a.fd[1] & 1), hz && !(a.fd[2] & 1)};
-}
 // x: the dofs of one node row in workgroups; y, z: the node rows (amg_check_opts keeps both within 65535)
 inline dim3 transfer_grid(const int32_t d[3], int bs) { return dim3((unsigned)(((int64_t)d[0] * bs + kThreads - 1) / kThreads), (unsigned)d[1], (unsigned)d[2]); }
 }  // namespace
@@ -359,6 +499,11 @@ void amg_dense(const double *C, int32_t n, const double *b, double *y, const int
     if (n == 0) return;
     const int rows = kThreads / kWave;
     hipLaunchKernelGGL(amg_dense_kernel, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, s, C, n, b, y, done);
+}
+void amg_tail(const AmgTailDesc *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s)
+{
+    if (s0 >= s1) return;
+    hipLaunchKernelGGL(amg_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
 }
 void amg_out(int mode, int64_t n, const double *src, double *dst, const int32_t *done, hipStream_t s)
 {

@@ -150,6 +150,27 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "odd") o.sides = SPK_AMG_SIDES_ODD;
         else if (v == "any") o.sides = SPK_AMG_SIDES_ANY;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (odd | any)");
+    } else if (key == "-spk_mg_cycle") {
+        if (!val) return need("v or w");
+        const std::string v(val);
+        if (v == "v") o.cycle = SPK_AMG_CYCLE_V;
+        else if (v == "w") o.cycle = SPK_AMG_CYCLE_W;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (v | w)");
+    } else if (key == "-spk_mg_tail") {
+        if (!val) return need("auto, launches or fused");
+        const std::string v(val);
+        if (v == "auto") o.tail = SPK_AMG_TAIL_AUTO;
+        else if (v == "launches") o.tail = SPK_AMG_TAIL_LAUNCHES;
+        else if (v == "fused") o.tail = SPK_AMG_TAIL_FUSED;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (auto | launches | fused)");
+    } else if (key == "-spk_mg_tail_rows") {
+        if (!val || !parse_int(val, &iv) || iv < 0) return need("an integer >= 0 (0: the default)");
+        o.tail_rows = iv;
+    } else if (key == "-pc_mg_cycle_type") {   // PETSc's name: v is what runs anyway; the W-cycle is -spk_mg_cycle w
+        if (!val) return need("v (the W-cycle is -spk_mg_cycle w)");
+        if (std::string(val) != "v")
+            return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (v) -- the W-cycle is " +
+                                                   (full.rfind("-fieldsplit_0_", 0) == 0 ? "-fieldsplit_0_spk_mg_cycle w" : "-spk_mg_cycle w"));
     } else if (key == "-mg_levels_pc_type") {
         if (!val) return need("a type");
         if (std::string(val) != "jacobi") return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + val + " is not supported (jacobi)");
@@ -651,6 +672,11 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                 std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
                             o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
                             o.nsmooths, o.coarse_eq_limit);
+            const int tail = ai.tail_first >= 0 ? SPK_AMG_TAIL_FUSED : SPK_AMG_TAIL_LAUNCHES;   // as it resolved on these levels
+            std::printf("    cycle %s (-spk_mg_cycle), tail %s (-spk_mg_tail %s), tail_first %d, tail_rows %d%s, tail launches per application %d\n",
+                        ai.cycle == SPK_AMG_CYCLE_W ? "w" : "v", tail == SPK_AMG_TAIL_FUSED ? "fused" : "launches",
+                        o.tail == SPK_AMG_TAIL_AUTO ? "auto" : o.tail == SPK_AMG_TAIL_FUSED ? "fused" : "launches", ai.tail_first,
+                        o.tail_rows > 0 ? o.tail_rows : SPK_AMG_TAIL_ROWS_DEFAULT, o.tail_rows > 0 ? "" : " (default)", ai.tail_launches);
             int32_t refreshed = 0;
             double secs = 0.0;
             if (k->amg_reuse[amg_active(k)] && spk_get_amg_reuse_info(k->ctx, &refreshed, &secs) == SPK_OK)

@@ -47,17 +47,23 @@ AMG_SETUP_HOST, AMG_SETUP_DEVICE = 0, 1
 AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID = 0, 1
 AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED = 0, 1
 AMG_SIDES_ODD, AMG_SIDES_ANY = 0, 1
+AMG_CYCLE_V, AMG_CYCLE_W = 0, 1
+AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED = 0, 1, 2
+AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST = range(6)
 SPK_ERR_ARG = -1   # include/spk.h
 _SMOOTHERS = {"chebyshev": AMG_CHEBYSHEV, "richardson": AMG_RICHARDSON}
 _SETUPS = {"host": AMG_SETUP_HOST, "device": AMG_SETUP_DEVICE}
 _COARSENINGS = {"aggregation": AMG_COARSEN_AGGREGATION, "grid": AMG_COARSEN_GRID}
 _TRANSFERS = {"matrixfree": AMG_TRANSFER_MATRIX_FREE, "stored": AMG_TRANSFER_STORED}
 _SIDES = {"odd": AMG_SIDES_ODD, "any": AMG_SIDES_ANY}
+_CYCLES = {"v": AMG_CYCLE_V, "w": AMG_CYCLE_W}
+_TAILS = {"auto": AMG_TAIL_AUTO, "launches": AMG_TAIL_LAUNCHES, "fused": AMG_TAIL_FUSED}
 
 
 def amg_opts(**kw):
     """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
-    'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored', sides 'odd' / 'any';
+    'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored', sides 'odd' / 'any', cycle
+    'v' / 'w', tail 'auto' / 'launches' / 'fused';
     grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
     ones too)."""
     o = AmgOpts()
@@ -75,6 +81,10 @@ def amg_opts(**kw):
             v = _TRANSFERS[v]
         if k == "sides" and isinstance(v, str):
             v = _SIDES[v]
+        if k == "cycle" and isinstance(v, str):
+            v = _CYCLES[v]
+        if k == "tail" and isinstance(v, str):
+            v = _TAILS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         if k == "grid":
@@ -98,7 +108,23 @@ def _amg_info(ai):
     return dict(levels=L, block_size=ai.block_size, rows=list(ai.rows[:L]), nnz=list(ai.nnz[:L]),
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
-                dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides)
+                dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides, cycle=ai.cycle, tail_first=ai.tail_first,
+                tail_launches=ai.tail_launches)
+
+
+def amg_cycle_steps(levels, cycle="v"):
+    """The steps of one multigrid cycle over `levels` levels in the order the library runs them (spk_amg_cycle_steps,
+    host only): a list of (kind, level), kind one of AMG_STEP_*."""
+    cyc = _CYCLES[cycle] if isinstance(cycle, str) else int(cycle)
+    n = C.c_int64()
+    rc = lib.spk_amg_cycle_steps(levels, cyc, C.byref(n), None)
+    if rc != 0:
+        raise SpkError(rc, (lib.spk_last_error(None) or b"").decode())
+    st = np.zeros((n.value, 2), np.int32)
+    rc = lib.spk_amg_cycle_steps(levels, cyc, C.byref(n), st.ctypes.data)
+    if rc != 0:
+        raise SpkError(rc, (lib.spk_last_error(None) or b"").decode())
+    return [tuple(int(x) for x in r) for r in st]
 
 
 def _amg_matrix(fn, level, which):
