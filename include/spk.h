@@ -334,6 +334,27 @@ enum { SPK_AMG_SETUP_HOST = 0, SPK_AMG_SETUP_DEVICE = 1 };
 enum { SPK_AMG_COARSEN_AGGREGATION = 0, SPK_AMG_COARSEN_GRID = 1 };
 enum { SPK_AMG_TRANSFER_MATRIX_FREE = 0, SPK_AMG_TRANSFER_STORED = 1 };
 enum { SPK_AMG_SIDES_ODD = 0, SPK_AMG_SIDES_ANY = 1 };
+/* What forms the coarse operators of a grid-coarsened hierarchy (grid coarsening only; both give A_{l+1} =
+ * (P^T A_l P + (P^T A_l P)^T) / 2 up to the rounding of their sums).  PRODUCTS (the default): the generic sparse products
+ * and transposes gamg uses, on any level-0 pattern.  STENCIL: a gather on the node grid, with every pattern in closed form.
+ *   Children.  In a halved direction of m fine nodes coarse index c sits at fine index 2c; under SPK_AMG_SIDES_ANY with m
+ *   even the last coarse index m / 2 sits at fine m - 1.  Its children are fine 2c - 1 (weight 1/2), 2c (1) and 2c + 1
+ *   (1/2), clipped to the line; fine m - 1 of an even halved side is the child of m / 2 alone, with weight 1.  A direction
+ *   that keeps its nodes is the identity.  ch(C) is the tensor product, w(f, C) the product of the weights (1 .. 1/8):
+ *   exactly the non-zeros of column C of P.
+ *   The sum.  For coarse row r = C bs + a and column c = C' bs + b, C' within one node of C in every direction,
+ *     S[r, c] = sum (w(f, C) w(f', C')) A_l[f bs + a, f' bs + b]
+ *   over f in ch(C) in ascending node index and, within a fine row, over its stored entries in ascending position whose
+ *   column node f' lies in ch(C'); plain additions from +0.0, entries A_l does not store count as zero.  Every product is
+ *   exact, so host and device agree byte for byte.  A_{l+1}[r, c] = 0.5 S[r, c] + 0.5 S[c, r]: bitwise symmetric.
+ *   The pattern.  Every coarse node row stores the full bs x bs blocks of its clipped 3^d-node neighbourhood in ascending
+ *   column order, zeros included; nnz of a level is bs^2 prod (3 n_a - 2) over its sides n_a.
+ *   Level 0 is the only level with a foreign pattern: every stored entry's column node must lie within one node of its
+ *   row's node in every direction (a 5-point operator qualifies).  Otherwise spk_pc_setup / spk_amg_build_host fail with
+ *   SPK_ERR_UNSUPPORTED, the message naming the row and column and `-spk_mg_galerkin products`; the context stays usable.
+ *   Host and device levels being the same bytes, the device set-up takes the Ritz values of a level >= 1 of at most
+ *   SPK_AMG_MAX_COARSE rows from the host's Lanczos on a download of it: lambda_max there is the host's to the bit. */
+enum { SPK_AMG_GALERKIN_PRODUCTS = 0, SPK_AMG_GALERKIN_STENCIL = 1 };
 /* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail and
  * tail_rows alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
  *     cycle(l, fresh): l == L-1: COARSE; return
@@ -373,6 +394,7 @@ typedef struct spk_amg_opts {
     int32_t cycle;            /* -spk_mg_cycle v|w: SPK_AMG_CYCLE_*  (v) */
     int32_t tail;             /* -spk_mg_tail auto|launches|fused: SPK_AMG_TAIL_* (auto: launches under v, fused under w) */
     int32_t tail_rows;        /* -spk_mg_tail_rows n: the largest level the fused tail takes (0: SPK_AMG_TAIL_ROWS_DEFAULT; else >= 1) */
+    int32_t galerkin;         /* -spk_mg_galerkin products|stencil: SPK_AMG_GALERKIN_* (products; grid coarsening only) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -390,6 +412,7 @@ typedef struct spk_amg_info {
     int32_t cycle;                           /* SPK_AMG_CYCLE_* of the application */
     int32_t tail_first;                      /* the first level inside the fused tail launch (>= 1), -1: no tail */
     int32_t tail_launches;                   /* launches of the tail kernel per application (0 without a tail) */
+    int32_t galerkin;                        /* grid coarsening: SPK_AMG_GALERKIN_* of what built the coarse operators (else 0) */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -423,7 +446,8 @@ int spk_debug_amg_transfer(spk_ctx *ctx, int level, int which, int stored, int64
  * operator scaled back to the binade it was built in).  The case is a time step, a Newton step or a coefficient
  * sweep on a fixed mesh.  Anything else is a full build, silently.  To compare patterns the set-up keeps a device copy of
  * rowptr / colidx as the context stores them (about 150 MB at 1024 x 1024, bs 2; the same pattern in another column order
- * counts as different), and the device route the patterns and values of A_l P_l and R_l A_l P_l; reuse = 0 releases
+ * counts as different), and the device route the patterns and values of A_l P_l and R_l A_l P_l (not under
+ * SPK_AMG_GALERKIN_STENCIL, whose refresh is the build's kernel on the new values); reuse = 0 releases
  * both and leaves the hierarchy.  A refresh fails where a build would (an empty Chebyshev interval, a coarse operator that
  * is not positive definite: SPK_ERR_ARG); the half-refreshed hierarchy is then dropped and the context is without a
  * preconditioner until the next spk_pc_setup, which builds.  Everything behind the hierarchy (diag(A)^-1, S^, the B D
@@ -452,6 +476,10 @@ int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, i
 /* Test hook (host only): the steps of one cycle over `levels` levels (1..SPK_AMG_MAX_LEVELS) in the order both routes
  * run them, as pairs of int32 (SPK_AMG_STEP_*, level).  steps NULL: *nsteps alone. */
 int spk_amg_cycle_steps(int32_t levels, int32_t cycle, int64_t *nsteps, int32_t *steps);
+/* Test hook (host only): the children of coarse node `node` under SPK_AMG_GALERKIN_STENCIL between the node grids
+ * fine[3] and coarse[3] -- the fine nodes in ascending order and their weights (at most 27 each; either may be NULL);
+ * *n: how many.  They are the non-zeros of the node's column of P. */
+int spk_amg_stencil_children(const int32_t *fine, const int32_t *coarse, int32_t node, int32_t *n, int32_t *nodes, double *weights);
 
 /* What stands for the Schur complement in SPK_PC_SCHUR (PETSc: -pc_fieldsplit_schur_precondition):
  *   SPK_SCHUR_PRE_SELFP_DIAG (default): S^ = diag(B diag(A)^-1 B^T), divided by entry by entry;

@@ -97,7 +97,10 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * the Galerkin product; anything else: SPK_ERR_UNSUPPORTED); -spk_mg_transfer matrixfree|stored selects how the V-cycle
  * applies P and R (opts->transfer); -spk_mg_sides odd|any selects which sides halve (opts->sides: odd, the default, refuses
  * a grid whose even side keeps the coarsest level too large; any halves an even side of m >= 4 nodes to m / 2 + 1, so
- * 1024 -> 513 -> ... -> 5; another value: SPK_ERR_UNSUPPORTED; given without mg it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * 1024 -> 513 -> ... -> 5; another value: SPK_ERR_UNSUPPORTED; given without mg it is read and not used);
+ * -spk_mg_galerkin products|stencil selects what forms the coarse operators (opts->galerkin: the generic sparse products,
+ * the default, or the gather on the node grid of SPK_AMG_GALERKIN_STENCIL; another value: SPK_ERR_UNSUPPORTED naming the
+ * two, no value: SPK_ERR_ARG; given without mg it is read and not used; -pc_mg_galerkin keeps its meaning).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
  * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
  * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);

@@ -73,7 +73,7 @@ class AmgOpts(C.Structure):
         ("threshold", C.c_double), ("smooth_its", C.c_int32), ("block_size", C.c_int32), ("esteig", C.c_double * 4),
         ("richardson_scale", C.c_double), ("setup", C.c_int32),
         ("coarsening", C.c_int32), ("grid", C.c_int32 * 3), ("transfer", C.c_int32), ("sides", C.c_int32),
-        ("cycle", C.c_int32), ("tail", C.c_int32), ("tail_rows", C.c_int32),
+        ("cycle", C.c_int32), ("tail", C.c_int32), ("tail_rows", C.c_int32), ("galerkin", C.c_int32),
     ]
 
 
@@ -84,7 +84,7 @@ class AmgInfo(C.Structure):
         ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("lambda_max", C.c_double * AMG_MAX_LEVELS),
         ("operator_complexity", C.c_double), ("setup_seconds", C.c_double), ("setup", C.c_int32),
         ("coarsening", C.c_int32), ("dims", (C.c_int32 * 3) * AMG_MAX_LEVELS), ("sides", C.c_int32),
-        ("cycle", C.c_int32), ("tail_first", C.c_int32), ("tail_launches", C.c_int32),
+        ("cycle", C.c_int32), ("tail_first", C.c_int32), ("tail_launches", C.c_int32), ("galerkin", C.c_int32),
     ]
 
 
@@ -218,6 +218,7 @@ def _load():
     L.spk_amg_host_level.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, vp]
     L.spk_amg_host_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
     L.spk_amg_cycle_steps.argtypes = [i32, i32, C.POINTER(i64), vp]
+    L.spk_amg_stencil_children.argtypes = [vp, vp, i32, C.POINTER(i32), vp, vp]
     L.spk_pc_set_schur_pre.argtypes = [vp, C.c_int]
     L.spk_get_schur_matrix.argtypes = [vp, f64p]
     L.spk_get_schur_setup_seconds.argtypes = [vp, C.POINTER(dbl)]

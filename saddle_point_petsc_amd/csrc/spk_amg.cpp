@@ -6,6 +6,8 @@
 // The same loop builds the grid-coarsened hierarchy (-pc_type mg, SPK_AMG_COARSEN_GRID): where the node grid is known a
 // level halves its odd sides (-spk_mg_sides any: the even ones too) and P is the tensor product of linear interpolations -- no graph, no aggregation, no
 // prolongator smoothing; everything else (Ritz values, Galerkin products, coarse inverse, refresh) is shared.
+// -spk_mg_galerkin stencil (SPK_AMG_GALERKIN_STENCIL) forms the coarse operators of such a hierarchy by a gather on the
+// node grid instead (spk_galerkin_core.hpp): both routes call it in coarsen_grid and, on new values, in regalerkin.
 // With reuse on (spk_pc_set_amg_reuse) a second, shorter loop (refresh_levels) over the same two routes puts new values
 // of A00 through a hierarchy whose aggregates, prolongators and patterns stay.
 //
@@ -18,6 +20,7 @@
 #include <cstring>
 
 #include "spk_amg.hpp"
+#include "spk_galerkin_core.hpp"
 #include "spk_internal.hpp"
 
 namespace spk {
@@ -532,6 +535,7 @@ void build_levels(Route &r, int bs, const spk_amg_opts &o, int setup, Clock::tim
     info.levels = l + 1;
     info.coarsening = o.coarsening;
     info.sides = grid ? o.sides : 0;
+    info.galerkin = grid ? o.galerkin : 0;
     if (r.rows(l) > SPK_AMG_MAX_COARSE && stuck) {   // (SPK_AMG_SIDES_ODD only: under ANY no side above 3 nodes is stuck)
         int a = 0;   // the largest side that does not halve
         for (int b = 1; b < 3; ++b) if (fd[b] > fd[a]) a = b;
@@ -610,7 +614,26 @@ struct HostRoute {
         if (grid_prolong_nnz(fd, cd, bs) > INT32_MAX)
             fail(SPK_ERR_UNSUPPORTED, "amg: the prolongator of level %d has more entries than 32-bit offsets address", l);
         lv(l).P = grid_prolongator(fd, cd, bs);
-        galerkin(l);
+        if (h.o.galerkin != SPK_AMG_GALERKIN_STENCIL) return galerkin(l);
+        if (galerkin::gs_nnz(cd, bs) > INT32_MAX)
+            fail(SPK_ERR_UNSUPPORTED, "amg: the operator of level %d has more entries than 32-bit offsets address", l + 1);
+        if (l == 0) galerkin_stencil_check_host(fd, bs, lv(0).A.rp.data(), lv(0).A.ci.data());
+        lv(l).R = transpose(lv(l).P);
+        h.lv.emplace_back();
+        HostCsr &N = h.lv.back().A;
+        N.nrows = N.ncols = cd[0] * cd[1] * cd[2] * bs;
+        N.rp.assign((size_t)N.nrows + 1, 0);
+        N.ci.assign((size_t)galerkin::gs_nnz(cd, bs), 0);
+        N.v.assign(N.ci.size(), 0.0);
+        stencil(l, fd, cd, bs);
+    }
+    // level l+1 by the grid-stencil gather (SPK_AMG_GALERKIN_STENCIL), the build's and the refresh's: pattern, values, D^-1
+    void stencil(int l, const int32_t fd[3], const int32_t cd[3], int bs) const
+    {
+        const HostCsr &F = lv(l).A;
+        HostCsr &N = lv(l + 1).A;
+        galerkin_stencil_host(fd, cd, bs, F.rp.data(), F.ci.data(), F.v.data(), N.rp.data(), N.ci.data(), N.v.data());
+        lv(l + 1).dinv = diag_inv(N);
     }
     // R = P^T and level l+1 from the P of level l
     void galerkin(int l) const
@@ -625,6 +648,7 @@ struct HostRoute {
     int levels() const { return (int)h.lv.size(); }
     void regalerkin(int l) const
     {
+        if (h.info.galerkin == SPK_AMG_GALERKIN_STENCIL) return stencil(l, h.info.dims[l], h.info.dims[l + 1], h.info.block_size);
         AmgLevel &L = lv(l), &N = lv(l + 1);
         const HostCsr Ac = spgemm(L.R, spgemm(L.A, L.P));
         HostCsr An = add(0.5, Ac, 0.5, transpose(Ac));
@@ -695,7 +719,7 @@ void amg_check_opts(const spk_amg_opts &o)
         fail(SPK_ERR_ARG, "amg: setup %d is neither SPK_AMG_SETUP_HOST (0) nor SPK_AMG_SETUP_DEVICE (1)", o.setup);
     if (o.coarsening != SPK_AMG_COARSEN_AGGREGATION && o.coarsening != SPK_AMG_COARSEN_GRID)
         fail(SPK_ERR_ARG, "amg: coarsening %d is neither SPK_AMG_COARSEN_AGGREGATION (0) nor SPK_AMG_COARSEN_GRID (1)", o.coarsening);
-    if (o.coarsening == SPK_AMG_COARSEN_GRID) {   // (grid, transfer and sides are read under grid coarsening only)
+    if (o.coarsening == SPK_AMG_COARSEN_GRID) {   // (grid, transfer, sides and galerkin are read under grid coarsening only)
         if (o.grid[0] < 2 || o.grid[1] < 2 || o.grid[2] < 1)
             fail(SPK_ERR_ARG, "amg: grid %d x %d x %d: at least 2 x 2 nodes (x 1 in 2-D)", o.grid[0], o.grid[1], o.grid[2]);
         if ((int64_t)o.grid[0] * o.grid[1] > INT32_MAX || (int64_t)o.grid[0] * o.grid[1] * o.grid[2] > INT32_MAX)
@@ -704,6 +728,8 @@ void amg_check_opts(const spk_amg_opts &o)
             fail(SPK_ERR_ARG, "amg: transfer %d is neither SPK_AMG_TRANSFER_MATRIX_FREE (0) nor SPK_AMG_TRANSFER_STORED (1)", o.transfer);
         if (o.sides != SPK_AMG_SIDES_ODD && o.sides != SPK_AMG_SIDES_ANY)
             fail(SPK_ERR_ARG, "amg: sides %d is neither SPK_AMG_SIDES_ODD (0) nor SPK_AMG_SIDES_ANY (1)", o.sides);
+        if (o.galerkin != SPK_AMG_GALERKIN_PRODUCTS && o.galerkin != SPK_AMG_GALERKIN_STENCIL)
+            fail(SPK_ERR_ARG, "amg: galerkin %d is neither SPK_AMG_GALERKIN_PRODUCTS (0) nor SPK_AMG_GALERKIN_STENCIL (1)", o.galerkin);
         if (o.transfer == SPK_AMG_TRANSFER_MATRIX_FREE && (o.grid[1] > 65535 || o.grid[2] > 65535))   // they are launch dimensions
             fail(SPK_ERR_UNSUPPORTED, "amg: the matrix-free transfers take at most 65535 nodes in y and z (grid %d x %d x %d) -- "
                  "use -spk_mg_transfer stored", o.grid[0], o.grid[1], o.grid[2]);
@@ -1161,7 +1187,23 @@ struct DevRoute {
         if (ne) SPK_HIP(hipMemcpyAsync(gi.data(), gid.p, sizeof(int32_t) * gi.size(), hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
     }
-    void ritz(int l, double *lmin, double *lmax) const { dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax, a_scale); }
+    // Under SPK_AMG_GALERKIN_STENCIL a level >= 1 holds the host route's bytes, so where it is small enough to cross the bus
+    // as the coarsest operator does (at most SPK_AMG_MAX_COARSE rows) the host's own Lanczos runs on a download of it: the
+    // host's Ritz values to the bit, and one download where the device steps read two sums back 30 times.  It is on such
+    // levels that the bits matter: 30 steps without reorthogonalisation on a few dozen rows lose orthogonality altogether
+    // before the largest Ritz value has converged, and its value then follows the rounding of every sum
+    bool ritz_on_host(int l) const
+    {
+        return o.coarsening == SPK_AMG_COARSEN_GRID && o.galerkin == SPK_AMG_GALERKIN_STENCIL && l > 0 && rows(l) <= SPK_AMG_MAX_COARSE;
+    }
+    void ritz(int l, double *lmin, double *lmax) const
+    {
+        if (ritz_on_host(l)) {
+            const HostCsr H = dev_csr_download(A(l), true, s);
+            return lanczos(H, diag_inv(H), lmin, lmax, a_scale);
+        }
+        dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax, a_scale);
+    }
     void set_interval(int l, double lo, double hi) { smoother_coeffs(d.lv[(size_t)l], o, lo, hi); }
     void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths)
     {
@@ -1209,7 +1251,41 @@ struct DevRoute {
         L.P.rowptr.alloc_raw((size_t)L.P.nrows + 1, 8);
         dev_csr_values(L.P, nz);
         k::amgs_grid_prolongator(L.grid, L.P.rowptr.p, L.P.colidx.p, L.P.val.p, s);
-        galerkin(l);
+        if (o.galerkin != SPK_AMG_GALERKIN_STENCIL) return galerkin(l);
+        const int64_t nc = galerkin::gs_nnz(cd, bs);
+        if (nc > INT32_MAX)
+            fail(SPK_ERR_UNSUPPORTED, "amg: the operator of level %d has more entries than 32-bit offsets address", l + 1);
+        dev_transpose(L.R, L.P, s);
+        d.lv.emplace_back();   // (reserved)
+        AmgLevelDev &N = d.lv.back();
+        N.n = N.A.nrows = N.A.ncols = L.P.ncols;
+        N.A.rowptr.alloc_raw((size_t)N.n + 1, 8);
+        dev_csr_values(N.A, nc);
+        N.dinv.alloc((size_t)N.n, 8);
+        DevBuf<unsigned long long> bad;   // (row << 32 | column) of the first entry outside the stencil, else all ones
+        if (l == 0) {   // level 0 alone has a foreign pattern: its one check, read back behind the level's launches
+            bad.alloc_raw(1);
+            SPK_HIP(hipMemsetAsync(bad.p, 0xff, sizeof(unsigned long long), s));
+            k::amgs_galerkin_stencil_check(L.grid, A(0), bad.p, s);
+        }
+        stencil(l);
+        if (l == 0) {
+            unsigned long long key = 0;
+            SPK_HIP(hipMemcpyAsync(&key, bad.p, sizeof key, hipMemcpyDeviceToHost, s));
+            SPK_HIP(hipStreamSynchronize(s));
+            if (key != ~0ull)
+                fail(SPK_ERR_UNSUPPORTED, "amg: the entry in row %d, column %d of the operator couples nodes that are not neighbours "
+                     "on the %d x %d x %d grid; the stencil products take couplings between neighbouring nodes only -- use "
+                     "-spk_mg_galerkin products", (int)(key >> 32), (int)(key & 0xffffffffull), (int)fd[0], (int)fd[1], (int)fd[2]);
+        }
+    }
+    // level l+1 by the grid-stencil gather, the build's and the refresh's: three launches into buffers whose sizes follow
+    // from the node grids -- no count, no scan, no scratch, no read-back
+    void stencil(int l)
+    {
+        AmgLevelDev &L = d.lv[(size_t)l], &N = d.lv[(size_t)l + 1];
+        k::amgs_galerkin_stencil(L.grid, A(l), N.A, s);
+        k::extract_diag_inv(N.A, N.dinv.p, s);
     }
     // R = P^T and level l+1 from the P of level l
     void galerkin(int l)
@@ -1236,6 +1312,7 @@ struct DevRoute {
     // three launches into buffers the build left: nothing is allocated, counted or scanned
     void regalerkin(int l)
     {
+        if (o.galerkin == SPK_AMG_GALERKIN_STENCIL) return stencil(l);
         AmgLevelDev &L = d.lv[(size_t)l], &N = d.lv[(size_t)l + 1];
         k::amgs_spgemm_numeric(A(l), L.P, L.AP, err, s);
         k::amgs_spgemm_numeric(L.R, L.AP, L.Ac, err, s);
@@ -1298,7 +1375,7 @@ bool amg_can_refresh(spk_ctx *c)
     bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
                 a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
                 a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup &&
-                a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides;
+                a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides && a.galerkin == b.galerkin;
     for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
     for (int i = 0; i < 3; ++i) same = same && a.grid[i] == b.grid[i];
     if (!same || ctx_block_size(c, a) != ru.bs || c->n_local != ru.n || c->Ad.nnz != ru.nnz || c->ld != ru.ld) return false;
@@ -1587,6 +1664,18 @@ int spk_amg_host_aggregates(const spk_amg_hier *h, int level, int32_t *nnodes, i
     if (!h) return SPK_ERR_ARG;
     SPK_HOST_TRY
     spk::aggregates_out(h->h.lv, h->h.info, level, nnodes, agg);
+    SPK_HOST_CATCH
+}
+
+int spk_amg_stencil_children(const int32_t *fine, const int32_t *coarse, int32_t node, int32_t *n, int32_t *nodes, double *weights)
+{
+    if (!fine || !coarse || !n) return SPK_ERR_ARG;
+    SPK_HOST_TRY
+    for (int a = 0; a < 3; ++a)
+        if (fine[a] < 1 || (coarse[a] != fine[a] && coarse[a] != fine[a] / 2 + 1))
+            spk::fail(SPK_ERR_ARG, "amg: %d coarse nodes are not a coarsening of %d fine ones", (int)coarse[a], (int)fine[a]);
+    if (node < 0 || (int64_t)node >= (int64_t)coarse[0] * coarse[1] * coarse[2]) spk::fail(SPK_ERR_ARG, "amg: coarse node %d outside the grid", (int)node);
+    *n = spk::galerkin_stencil_children(fine, coarse, node, nodes, weights);
     SPK_HOST_CATCH
 }
 

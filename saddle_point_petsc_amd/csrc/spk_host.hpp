@@ -125,6 +125,17 @@ int amg_tail_first(int levels, const int32_t *rows, int cycle, int tail, int tai
 // the tail runs of a step list: maximal stretches [begin, end) of consecutive steps on levels >= tail_first (none for -1)
 std::vector<std::pair<int64_t, int64_t>> amg_tail_runs(const std::vector<AmgStep> &steps, int tail_first);
 
+// ---- the grid-stencil Galerkin product (SPK_AMG_GALERKIN_STENCIL; spk_galerkin_host.cpp over spk_galerkin_core.hpp) ----
+// fd -> cd: the node grids of level l and l + 1 (grid_coarse_dims), bs the node size (1, 2 or 3).
+// level 0's condition: throws SPK_ERR_UNSUPPORTED naming the first stored entry whose nodes are not neighbours
+void galerkin_stencil_check_host(const int32_t fd[3], int bs, const int32_t *arp, const int32_t *aci);
+// A_{l+1} from the sorted CSR of A_l: rp (rows + 1), ci and v (gs_nnz(cd, bs) entries each) are all written
+void galerkin_stencil_host(const int32_t fd[3], const int32_t cd[3], int bs, const int32_t *arp, const int32_t *aci, const double *av,
+                           int32_t *rp, int32_t *ci, double *v);
+// the fine nodes of coarse node `node` in ascending order and their weights (at most 27; either pointer may be null);
+// returns how many
+int galerkin_stencil_children(const int32_t fd[3], const int32_t cd[3], int32_t node, int32_t *nodes, double *w);
+
 // ---- the dense Schur complement of a few constraint rows (spk_pc_set_schur_pre) ----
 // G: m x m as computed; S = (G + G^T) / 2; L: its Cholesky factor (lower, row-major).  Returns -1, or the first pivot that
 // is not positive beyond rounding (S is not positive definite: linearly dependent rows of B)

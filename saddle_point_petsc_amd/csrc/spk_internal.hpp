@@ -880,6 +880,11 @@ void amgs_node_norms(const int32_t *rp, const int32_t *ci, const double *v, int3
 void amgs_graph(const int32_t *rp, const int32_t *ci, const double *v, int32_t nn, int bs, double theta, const double *dn,
                 const int32_t *gp, int32_t *out, hipStream_t s);
 void amgs_grid_prolongator(const AmgGrid &g, int32_t *rp, int32_t *ci, double *v, hipStream_t s);   // P of g: row pointers, columns, weights
+// the grid-stencil Galerkin product (SPK_AMG_GALERKIN_STENCIL; spk_galerkin_core.hpp): row pointers, columns and values
+// of N = A_{l+1} from the sorted CSR of A = A_l over the node grids of g, in two launches (gather, symmetrise in place); N's
+// buffers hold gs_nnz(g.cd, g.bs) entries.  check: *bad = min(*bad, row << 32 | column) over A's entries outside the stencil
+void amgs_galerkin_stencil(const AmgGrid &g, const CsrDev &A, CsrDev &N, hipStream_t s);
+void amgs_galerkin_stencil_check(const AmgGrid &g, const CsrDev &A, unsigned long long *bad, hipStream_t s);
 void amgs_tent_count(const int32_t *agg, int32_t nrows, int bs, int32_t *cnt, hipStream_t s);
 void amgs_tent_fill(const int32_t *agg, const double *inv, int32_t nrows, int bs, const int32_t *rp, int32_t *ci, double *v,
                     hipStream_t s);
@@ -911,7 +916,7 @@ struct AmgLevelDev {
     int32_t n = 0;
     CsrDev A, P, R;                    // A: levels >= 1; P, R: all but the coarsest
     CsrDev Ptent;                      // device-built hierarchies only (test hook)
-    CsrDev AP, Ac;                     // device-built with reuse on: A_l P_l and R_l A_l P_l, patterns and the refresh's value buffers
+    CsrDev AP, Ac;                     // device-built with reuse on: A_l P_l and R_l A_l P_l, patterns and the refresh's value buffers (empty under SPK_AMG_GALERKIN_STENCIL)
     std::vector<int32_t> agg;          // device-built hierarchies only: the aggregates the host step returned
     DevBuf<double> dinv;               // levels >= 1
     DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product

@@ -1,7 +1,8 @@
 // spk_k_amg_setup.hip -- the multigrid set-up on the device (-spk_gamg_setup device; host sequencing: amg_build_device
 // in spk_amg.cpp).  gfx950, wave64, FP64.  Node graph, tentative prolongator, Lanczos vector passes, CSR x CSR, union
 // add and transpose; for the refresh of a kept hierarchy (amg_refresh_ctx) the pattern comparison and the numeric
-// product and symmetrisation on known patterns.  Set-up runs before any solve: no launch here takes the solver's `done` gate.
+// product and symmetrisation on known patterns; for grid coarsening the prolongator and the grid-stencil Galerkin product
+// (amgs_galerkin_stencil...) in closed form.  Set-up runs before any solve: no launch here takes the solver's `done` gate.
 //
 // Every kernel is deterministic.  The sparse kernels work one row (or node) per thread in the host builder's traversal
 // order, and where the host's result depends on the order and rounding of a sum (the strong-connection test, the
@@ -9,6 +10,7 @@
 // no FMA, the device contracts by default.  Integer atomics allocate slots only where a sort follows; there are no
 // floating-point atomics.
 #include "spk_device.hpp"
+#include "spk_galerkin_core.hpp"
 
 namespace spk {
 namespace k {
@@ -484,8 +486,78 @@ __global__ __launch_bounds__(kVT) void amgs_lz_update_kernel(int64_t n, double a
 }
 
 // ---------------------------------------------------------------------------
+// the grid-stencil Galerkin product (SPK_AMG_GALERKIN_STENCIL; the arithmetic: spk_galerkin_core.hpp).  One thread per
+// (coarse row, neighbour node): it walks the <= 3^d fine rows of the row's node once, keeps the bs sums of its block row
+// in registers and writes bs consecutive columns and values, so the lanes of a wave fill consecutive entries of a few
+// coarse rows while they read the same few fine rows out of cache.  (One thread per coarse row would carry 3^d bs
+// accumulators -- 81 doubles in 3-D -- and write with a stride of a row.)  The thread of the node itself writes the row
+// pointer.  A second launch symmetrises in place: the owner of a pair (row <= column) reads both raw sums and writes
+// both entries, so nothing is scattered and nothing is atomic.  No scratch, no count, no scan.
+// ---------------------------------------------------------------------------
+namespace gs = galerkin;
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amgs_galerkin_stencil_kernel(gs::GsGrid g, const int32_t *__restrict__ arp,
+                                                                         const int32_t *__restrict__ aci, const double *__restrict__ av,
+                                                                         int32_t *__restrict__ rp, int32_t *__restrict__ ci,
+                                                                         double *__restrict__ v)
+{
+    const int32_t cd[3] = {g.d[0].n, g.d[1].n, g.d[2].n};
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    gs::GsItem it;
+    if (t >= gs::gs_items(cd, BS) || !gs::gs_item(cd, BS, t, &it)) return;
+    gs::gs_gather<BS>(g, arp, aci, av, it, rp, ci, v);
+}
+template <int BS>
+__global__ __launch_bounds__(kThreads) void amgs_galerkin_stencil_sym_kernel(int32_t cx, int32_t cy, int32_t cz, double *v)
+{
+    const int32_t cd[3] = {cx, cy, cz};
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    gs::GsItem it;
+    if (t >= gs::gs_items(cd, BS) || !gs::gs_item(cd, BS, t, &it)) return;
+    gs::gs_symmetrise<BS>(cd, it, v);
+}
+// level 0's condition, one row per thread: *bad = min(*bad, row << 32 | column) over the entries whose nodes are not
+// neighbours (the caller sets all ones)
+__global__ __launch_bounds__(kThreads) void amgs_galerkin_stencil_check_kernel(int32_t fx, int32_t fy, int32_t fz, int bs,
+                                                                               const int32_t *__restrict__ arp,
+                                                                               const int32_t *__restrict__ aci, unsigned long long *bad)
+{
+    const int32_t fd[3] = {fx, fy, fz};
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= (int64_t)fx * fy * fz * bs) return;
+    const int32_t c = gs::gs_check_row(fd, bs, arp, aci, r);
+    if (c >= 0) atomicMin(bad, ((unsigned long long)r << 32) | (unsigned long long)(uint32_t)c);
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+template <int BS>
+static void galerkin_stencil_launch(const gs::GsGrid &g, const CsrDev &A, CsrDev &N, hipStream_t s)
+{
+    const int32_t cd[3] = {g.d[0].n, g.d[1].n, g.d[2].n};
+    const dim3 grid = row_grid(gs::gs_items(cd, BS));
+    hipLaunchKernelGGL(amgs_galerkin_stencil_kernel<BS>, grid, dim3(kThreads), 0, s, g, A.rowptr.p, A.colidx.p, A.val.p, N.rowptr.p,
+                       N.colidx.p, N.val.p);
+    hipLaunchKernelGGL(amgs_galerkin_stencil_sym_kernel<BS>, grid, dim3(kThreads), 0, s, cd[0], cd[1], cd[2], N.val.p);
+}
+void amgs_galerkin_stencil(const AmgGrid &a, const CsrDev &A, CsrDev &N, hipStream_t s)
+{
+    const gs::GsGrid g = gs::gs_grid(a.fd, a.cd);
+    if ((gs::gs_items(a.cd, a.bs) + kThreads - 1) / kThreads > INT32_MAX)
+        fail(SPK_ERR_UNSUPPORTED, "amg: the stencil products of a %d x %d x %d grid need more workgroups than a launch takes", (int)a.cd[0],
+             (int)a.cd[1], (int)a.cd[2]);
+    if (a.bs == 1) galerkin_stencil_launch<1>(g, A, N, s);
+    else if (a.bs == 2) galerkin_stencil_launch<2>(g, A, N, s);
+    else if (a.bs == 3) galerkin_stencil_launch<3>(g, A, N, s);
+    else fail(SPK_ERR_ARG, "amg: the stencil products take node sizes 1, 2 and 3, not %d", (int)a.bs);
+    SPK_HIP(hipGetLastError());
+}
+void amgs_galerkin_stencil_check(const AmgGrid &a, const CsrDev &A, unsigned long long *bad, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_galerkin_stencil_check_kernel, row_grid(A.nrows), dim3(kThreads), 0, s, a.fd[0], a.fd[1], a.fd[2], (int)a.bs,
+                       A.rowptr.p, A.colidx.p, bad);
+}
 void amgs_rows_sorted(const int32_t *rp, const int32_t *ci, int32_t n, int32_t *flag, hipStream_t s)
 {
     if (n > 0) hipLaunchKernelGGL(amgs_rows_sorted_kernel, row_grid(n), dim3(kThreads), 0, s, rp, ci, n, flag);

@@ -150,6 +150,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "odd") o.sides = SPK_AMG_SIDES_ODD;
         else if (v == "any") o.sides = SPK_AMG_SIDES_ANY;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (odd | any)");
+    } else if (key == "-spk_mg_galerkin") {
+        if (!val) return need("products or stencil");
+        const std::string v(val);
+        if (v == "products") o.galerkin = SPK_AMG_GALERKIN_PRODUCTS;
+        else if (v == "stencil") o.galerkin = SPK_AMG_GALERKIN_STENCIL;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (products | stencil)");
     } else if (key == "-spk_mg_cycle") {
         if (!val) return need("v or w");
         const std::string v(val);
@@ -672,6 +678,11 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                 std::printf("    smoother %s x %d, threshold %g, nsmooths %d, coarse_eq_limit %d\n",
                             o.smoother == SPK_AMG_CHEBYSHEV ? "chebyshev/jacobi" : "richardson/jacobi", o.smooth_its, o.threshold,
                             o.nsmooths, o.coarse_eq_limit);
+            if (grid)
+                std::printf("    coarse operators: %s (-spk_mg_galerkin %s)\n",
+                            ai.galerkin == SPK_AMG_GALERKIN_STENCIL ? "the gather on the grid stencil, closed-form patterns"
+                                                                    : "the generic sparse products",
+                            ai.galerkin == SPK_AMG_GALERKIN_STENCIL ? "stencil" : "products");
             const int tail = ai.tail_first >= 0 ? SPK_AMG_TAIL_FUSED : SPK_AMG_TAIL_LAUNCHES;   // as it resolved on these levels
             std::printf("    cycle %s (-spk_mg_cycle), tail %s (-spk_mg_tail %s), tail_first %d, tail_rows %d%s, tail launches per application %d\n",
                         ai.cycle == SPK_AMG_CYCLE_W ? "w" : "v", tail == SPK_AMG_TAIL_FUSED ? "fused" : "launches",

@@ -48,6 +48,7 @@ AMG_COARSEN_AGGREGATION, AMG_COARSEN_GRID = 0, 1
 AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED = 0, 1
 AMG_SIDES_ODD, AMG_SIDES_ANY = 0, 1
 AMG_CYCLE_V, AMG_CYCLE_W = 0, 1
+AMG_GALERKIN_PRODUCTS, AMG_GALERKIN_STENCIL = 0, 1
 AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED = 0, 1, 2
 AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST = range(6)
 SPK_ERR_ARG = -1   # include/spk.h
@@ -57,13 +58,15 @@ _COARSENINGS = {"aggregation": AMG_COARSEN_AGGREGATION, "grid": AMG_COARSEN_GRID
 _TRANSFERS = {"matrixfree": AMG_TRANSFER_MATRIX_FREE, "stored": AMG_TRANSFER_STORED}
 _SIDES = {"odd": AMG_SIDES_ODD, "any": AMG_SIDES_ANY}
 _CYCLES = {"v": AMG_CYCLE_V, "w": AMG_CYCLE_W}
+_GALERKINS = {"products": AMG_GALERKIN_PRODUCTS, "stencil": AMG_GALERKIN_STENCIL}
 _TAILS = {"auto": AMG_TAIL_AUTO, "launches": AMG_TAIL_LAUNCHES, "fused": AMG_TAIL_FUSED}
 
 
 def amg_opts(**kw):
     """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
     'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored', sides 'odd' / 'any', cycle
-    'v' / 'w', tail 'auto' / 'launches' / 'fused';
+    'v' / 'w', tail 'auto' / 'launches' / 'fused', galerkin 'products' / 'stencil' (what forms the coarse operators of a
+    grid-coarsened hierarchy: the generic sparse products, or the gather on the node grid);
     grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
     ones too)."""
     o = AmgOpts()
@@ -85,6 +88,8 @@ def amg_opts(**kw):
             v = _CYCLES[v]
         if k == "tail" and isinstance(v, str):
             v = _TAILS[v]
+        if k == "galerkin" and isinstance(v, str):
+            v = _GALERKINS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         if k == "grid":
@@ -109,7 +114,19 @@ def _amg_info(ai):
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
                 dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides, cycle=ai.cycle, tail_first=ai.tail_first,
-                tail_launches=ai.tail_launches)
+                tail_launches=ai.tail_launches, galerkin=ai.galerkin)
+
+
+def amg_stencil_children(fine, coarse, node):
+    """The fine nodes of coarse node `node` between the node grids fine -> coarse (three sides each) under
+    galerkin='stencil', ascending, and their weights (spk_amg_stencil_children, host only)."""
+    f, c = (C.c_int32 * 3)(*fine), (C.c_int32 * 3)(*coarse)
+    n = C.c_int32()
+    nodes, w = np.zeros(27, np.int32), np.zeros(27, np.float64)
+    rc = lib.spk_amg_stencil_children(f, c, int(node), C.byref(n), nodes.ctypes.data, w.ctypes.data)
+    if rc != 0:
+        raise SpkError(rc, (lib.spk_last_error(None) or b"").decode())
+    return nodes[:n.value].copy(), w[:n.value].copy()
 
 
 def amg_cycle_steps(levels, cycle="v"):

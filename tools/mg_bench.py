@@ -16,7 +16,17 @@ after one warm-up round, --reps alternating rounds of the matrix-free prolongati
 P), the matrix-free restriction and the stored one (amg_csr_kernel<2> on R), all on the hierarchy of one context.  The
 report reads the kernel trace of that run: median (min..max) per kernel, the fraction of the byte model
 (prolongation: y read + y written + e read; restriction: b + t read + b_c written) at the HBM peak, and the bar --
-matrix-free median plus its spread below the stored median -- with exit status 1 when it is missed."""
+matrix-free median plus its spread below the stored median -- with exit status 1 when it is missed.
+    python tools/mg_bench.py --galerkin both [--grids 1025] [--sides odd|any] [--out profiles/FILE.jsonl]
+--galerkin products|stencil (-spk_mg_galerkin; default products) selects what forms mg's coarse operators in the runs
+above; every emitted line records it.  --galerkin both compares the two instead of mg and gamg: K = A, per grid two
+contexts in one process, reuse off so that every set-up is a build, after one warm-up round --reps alternating rounds of
+set-up -> solve -> V-cycle timing; then, per context, a reuse-on refresh on the values of a kappa-scaled operator.  Per
+route: set-up, solve, iterations, V-cycle, refresh and nnz per level.  The bar, checked at 1025 and 1024 nodes per side:
+the stencil route's set-up median plus its spread (max - min) at or below the products route's set-up median (exit
+status 1 when missed); the iterations of the two must agree within 1.
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mg_bench.py --setup-only stencil [--grid 1025]
+--setup-only products|stencil launches builds alone (a warm-up and --reps more), for a kernel trace."""
 import argparse
 import csv
 import glob
@@ -38,12 +48,14 @@ ap.add_argument("--reps", type=int, default=5, help="alternating rounds after th
 ap.add_argument("--no-saddle", action="store_true", help="leave out the saddle rows")
 ap.add_argument("--transfers", action="store_true", help="only launch the level-0 transfers (for a kernel trace)")
 ap.add_argument("--transfers-report", metavar="DIR", help="read the kernel trace a --transfers run left under DIR")
+ap.add_argument("--galerkin", choices=["products", "stencil", "both"], default="products", help="mg's coarse operators (-spk_mg_galerkin)")
+ap.add_argument("--setup-only", choices=["products", "stencil"], help="only launch device builds of --grid (for a kernel trace)")
 ap.add_argument("--out", help="append the JSON lines to this file too")
 a = ap.parse_args()
 
 
 def emit(row):
-    line = json.dumps(dict(row, sides=a.sides))
+    line = json.dumps(dict(dict(galerkin=a.galerkin), **dict(row, sides=a.sides)))
     print(line, flush=True)
     if a.out:
         with open(a.out, "a") as fh:
@@ -114,7 +126,85 @@ if a.transfers:
     print(json.dumps(dict(mode="transfers-launched", grid=g, sides=a.sides, rows=[nf, nc], rounds=a.reps + 1)), flush=True)
     sys.exit(0)
 
-KINDS = dict(mg=lambda g: dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides), gamg=lambda g: dict(setup="device"))
+if a.setup_only:
+    g = a.grid
+    A, _ = S.AssembleOperator_Laplace(g, g)
+    with S.Context(0) as c:
+        c.set_block(S.BLOCK_A00, A)
+        for rep in range(-1, a.reps):
+            c.pc_setup(S.PC_JACOBI, amg=dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=a.setup_only))
+        info = c.amg_info()
+    print(json.dumps(dict(mode="setup-only-launched", grid=g, sides=a.sides, galerkin=a.setup_only, builds=a.reps + 1, rows=info["rows"],
+                          nnz=info["nnz"])), flush=True)
+    sys.exit(0)
+
+
+def mg_opts(g, galerkin):
+    return dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=galerkin)
+
+
+def compare_galerkin(g):
+    """the two routes of mg's coarse operators on K = A; returns {route: (set-up seconds, iterations)}"""
+    A, f = S.AssembleOperator_Laplace(g, g)
+    A1, _ = S.AssembleOperator_Laplace(g, g, kappa=1.0 + np.random.default_rng(g).random((g - 1) * (g - 1)))
+    routes = ("products", "stencil")
+    ctxs, t = {}, {}
+    for route in routes:
+        c = S.Context(0)
+        c.set_block(S.BLOCK_A00, A)
+        ctxs[route] = c
+        t[route] = dict(setup=[], solve=[], vcycle=[], its=[], res=[], refresh=[])
+    for rep in range(-1, a.reps):   # -1: the warm-up round, not counted; reuse off: every set-up builds
+        for route, c in ctxs.items():
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, route))
+            x, info = c.fgmres(f, rtol=a.rtol, max_it=500, restart=30)
+            assert info["reason"] == 2, (route, info["reason"])
+            vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            r = t[route]
+            r["setup"].append(c.amg_info()["setup_seconds"])
+            r["solve"].append(info["solve_seconds"])
+            r["vcycle"].append(vc_ms * 1e-3)
+            r["its"].append(info["its"])
+            r["res"].append(float(np.linalg.norm(f - c.mult(x)) / np.linalg.norm(f)))
+    infos = {route: c.amg_info() for route, c in ctxs.items()}
+    for route, c in ctxs.items():   # reuse on: one build, then refreshes on alternating values of the same pattern
+        c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, route), amg_reuse=True)
+        for rep in range(-1, a.reps):
+            c.set_block(S.BLOCK_A00, A1 if rep % 2 else A)
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, route), amg_reuse=True)
+            ri = c.amg_reuse_info()
+            assert ri["refreshed"], route
+            if rep >= 0:
+                t[route]["refresh"].append(ri["seconds"])
+    for route, c in ctxs.items():
+        info, r = infos[route], t[route]
+        emit(dict(mode="galerkin", system="A", grid=g, pc="mg", route=route, solver="fgmres(30)", rtol=a.rtol, reps=a.reps,
+                  levels=info["levels"], rows=info["rows"], nnz=info["nnz"], operator_complexity=round(info["operator_complexity"], 4),
+                  its=sorted(set(r["its"])), true_rel_res=max(r["res"]), pc_apply_us=mmm(r["vcycle"], 1e6, 1),
+                  solve_ms=mmm(r["solve"], 1e3, 3), setup_ms=mmm(r["setup"], 1e3, 3), refresh_ms=mmm(r["refresh"], 1e3, 3)))
+        c.close()
+    return {route: (t[route]["setup"], t[route]["its"]) for route in routes}
+
+
+if a.galerkin == "both":
+    met = True
+    for g in a.grids:
+        s = compare_galerkin(g)
+        (ps, pi), (ss, si) = s["products"], s["stencil"]
+        same_its = max(abs(u - v) for u in pi for v in si) <= 1
+        row = dict(mode="bar", system="A", grid=g, iterations_within_one=bool(same_its), products_setup_ms=mmm(ps, 1e3, 3),
+                   stencil_setup_ms=mmm(ss, 1e3, 3), products_over_stencil=round(float(np.median(ps) / np.median(ss)), 2))
+        met = met and same_its
+        if g in (1024, 1025):
+            ok = float(np.median(ss)) + (max(ss) - min(ss)) <= float(np.median(ps))
+            met = met and ok
+            row.update(bar="stencil set-up median + spread <= products set-up median", bar_met=bool(ok))
+        emit(row)
+    sys.exit(0 if met else 1)
+
+KINDS = dict(mg=lambda g: mg_opts(g, a.galerkin), gamg=lambda g: dict(setup="device"))
 
 
 def compare(system, g, A, B, rhs):
