@@ -355,8 +355,22 @@ enum { SPK_AMG_SIDES_ODD = 0, SPK_AMG_SIDES_ANY = 1 };
  *   Host and device levels being the same bytes, the device set-up takes the Ritz values of a level >= 1 of at most
  *   SPK_AMG_MAX_COARSE rows from the host's Lanczos on a download of it: lambda_max there is the host's to the bit. */
 enum { SPK_AMG_GALERKIN_PRODUCTS = 0, SPK_AMG_GALERKIN_STENCIL = 1 };
-/* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail and
- * tail_rows alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
+/* How the cycle applies the operators of the levels between level 0 and the coarsest one (it steers the application, not
+ * the hierarchy: a set-up that differs in it alone may refresh, and the hierarchy's bytes are those of CSR).  CSR (the
+ * default): as sparse matrices -- row pointers, column indices, eight lanes per row and a butterfly.  STENCIL: every level
+ * l with 1 <= l < levels - 1 applies A_l from its value array alone, in the residual product of the DOWN step and in the
+ * fused smoothing step out = y + alpha D^-1 (b - A_l y) + beta (y - y-): the pattern of such a level is the closed form of
+ * SPK_AMG_GALERKIN_STENCIL, so the row pointers and column indices carry no information and are not read (they stay
+ * allocated -- the device Lanczos, the hooks and the stored transfers use them -- so device memory is unchanged; the value
+ * array is the one the CSR level owns, no copy, no repack).  A row's sum runs over its stored entries in ascending position
+ * from the first product, every product rounded on its own, one row per thread: not the bits of the CSR route (eight
+ * strided partial sums), the same on every run, and the same in the fused tail as in the launches.  Level 0 keeps the
+ * context's layout, the coarsest level its dense inverse.  Needs coarsening = GRID and galerkin = STENCIL -- only that
+ * route guarantees the pattern on both set-up routes; otherwise spk_pc_set_amg / spk_amg_build_host fail with
+ * SPK_ERR_UNSUPPORTED naming `-spk_mg_galerkin stencil` (or `-pc_type mg` under aggregation) and nothing changes. */
+enum { SPK_AMG_OPERATOR_CSR = 0, SPK_AMG_OPERATOR_STENCIL = 1 };
+/* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail,
+ * tail_rows and op alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
  *     cycle(l, fresh): l == L-1: COARSE; return
  *                      fresh ? PRE0 : PRE;  DOWN;  cycle(l+1, true);  if W and l+1 < L-1: cycle(l+1, false);  UP;  POST
  * (PETSc's PCMGMCycle): level l < L-1 is entered 2^l times, the coarsest 2^(L-2) times (a repeated exact solve changes
@@ -395,6 +409,7 @@ typedef struct spk_amg_opts {
     int32_t tail;             /* -spk_mg_tail auto|launches|fused: SPK_AMG_TAIL_* (auto: launches under v, fused under w) */
     int32_t tail_rows;        /* -spk_mg_tail_rows n: the largest level the fused tail takes (0: SPK_AMG_TAIL_ROWS_DEFAULT; else >= 1) */
     int32_t galerkin;         /* -spk_mg_galerkin products|stencil: SPK_AMG_GALERKIN_* (products; grid coarsening only) */
+    int32_t op;               /* -spk_mg_operator csr|stencil: SPK_AMG_OPERATOR_* (csr; stencil needs grid coarsening and galerkin stencil) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -413,6 +428,7 @@ typedef struct spk_amg_info {
     int32_t tail_first;                      /* the first level inside the fused tail launch (>= 1), -1: no tail */
     int32_t tail_launches;                   /* launches of the tail kernel per application (0 without a tail) */
     int32_t galerkin;                        /* grid coarsening: SPK_AMG_GALERKIN_* of what built the coarse operators (else 0) */
+    int32_t op;                              /* SPK_AMG_OPERATOR_* of the application: how the levels 1 .. levels - 2 apply A_l */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -433,6 +449,14 @@ int spk_get_amg_aggregates(const spk_ctx *ctx, int level, int32_t *nnodes, int32
  * stand for a padded vector and come back untouched (which 0). */
 int spk_debug_amg_transfer(spk_ctx *ctx, int level, int which, int stored, int64_t fine_len, const double *a, const double *b,
                            double *out);
+/* Test hook: the operator of level `level` (1 <= level < levels - 1, else SPK_ERR_ARG) of the context's hierarchy alone, on
+ * host vectors of the level's rows, one launch.  which 0: out = A x (b and xo are not read);  which 1: the smoothing step
+ * out = x + alpha D^-1 (b - A x) + beta (x - xo) with the level's own D^-1 (xo NULL: the zero vector).  which 2 and 3: the
+ * same two launches behind a set `done` gate: out comes back as it was passed in.  stencil 0: the CSR kernels, 1: the
+ * value-array kernels of SPK_AMG_OPERATOR_STENCIL, whatever the context's option is (SPK_ERR_STATE unless the hierarchy
+ * was built with grid coarsening and SPK_AMG_GALERKIN_STENCIL: the level has no closed-form pattern). */
+int spk_debug_amg_operator(spk_ctx *ctx, int level, int which, int stencil, double alpha, double beta, const double *x,
+                           const double *xo, const double *b, double *out);
 /* Reuse of the interpolation (PETSc: -pc_gamg_reuse_interpolation).  Sticky like spk_pc_set_schur_pre, default 0.  With
  * reuse on, a spk_pc_setup that finds a hierarchy an earlier set-up built with reuse on, the same spk_amg_opts (field by
  * field, route and block size included), the same local size and padded vector length, and a diagonal A00 block with the

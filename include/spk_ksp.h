@@ -100,7 +100,11 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * 1024 -> 513 -> ... -> 5; another value: SPK_ERR_UNSUPPORTED; given without mg it is read and not used);
  * -spk_mg_galerkin products|stencil selects what forms the coarse operators (opts->galerkin: the generic sparse products,
  * the default, or the gather on the node grid of SPK_AMG_GALERKIN_STENCIL; another value: SPK_ERR_UNSUPPORTED naming the
- * two, no value: SPK_ERR_ARG; given without mg it is read and not used; -pc_mg_galerkin keeps its meaning).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * two, no value: SPK_ERR_ARG; given without mg it is read and not used; -pc_mg_galerkin keeps its meaning);
+ * -spk_mg_operator csr|stencil selects how the cycle applies the levels between level 0 and the coarsest (opts->op: as
+ * sparse matrices, the default, or from their value arrays alone, SPK_AMG_OPERATOR_STENCIL, which needs mg with
+ * -spk_mg_galerkin stencil: otherwise SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED naming what is missing; another value:
+ * SPK_ERR_UNSUPPORTED naming the two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
  * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
  * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);

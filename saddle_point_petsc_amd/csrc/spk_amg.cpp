@@ -8,6 +8,9 @@
 // prolongator smoothing; everything else (Ritz values, Galerkin products, coarse inverse, refresh) is shared.
 // -spk_mg_galerkin stencil (SPK_AMG_GALERKIN_STENCIL) forms the coarse operators of such a hierarchy by a gather on the
 // node grid instead (spk_galerkin_core.hpp): both routes call it in coarsen_grid and, on new values, in regalerkin.
+// -spk_mg_operator stencil (SPK_AMG_OPERATOR_STENCIL) has the cycle apply the levels between level 0 and the coarsest from
+// their value arrays alone (spk_stencil_op_core.hpp): smooth(), the DOWN step and the tail descriptor dispatch on the
+// level's flag, which amg_plan_cycle sets; the hierarchy is untouched.
 // With reuse on (spk_pc_set_amg_reuse) a second, shorter loop (refresh_levels) over the same two routes puts new values
 // of A00 through a hierarchy whose aggregates, prolongators and patterns stay.
 //
@@ -474,6 +477,7 @@ void smoother_interval(const spk_amg_opts &o, int l, double lmin, double lmax, d
 void fill_cycle_info(const spk_amg_opts &o, spk_amg_info &info)
 {
     info.cycle = o.cycle;
+    info.op = o.op;
     info.tail_first = amg_tail_first(info.levels, info.rows, o.cycle, o.tail, o.tail_rows);
     info.tail_launches = info.tail_first < 0 ? 0 : (int32_t)amg_tail_runs(amg_cycle_steps(info.levels, o.cycle), info.tail_first).size();
 }
@@ -739,6 +743,15 @@ void amg_check_opts(const spk_amg_opts &o)
     if (o.tail != SPK_AMG_TAIL_AUTO && o.tail != SPK_AMG_TAIL_LAUNCHES && o.tail != SPK_AMG_TAIL_FUSED)
         fail(SPK_ERR_ARG, "amg: tail %d is none of SPK_AMG_TAIL_AUTO (0), SPK_AMG_TAIL_LAUNCHES (1), SPK_AMG_TAIL_FUSED (2)", o.tail);
     if (o.tail_rows < 0) fail(SPK_ERR_ARG, "amg: tail_rows %d < 0 (0: the default of %d)", o.tail_rows, SPK_AMG_TAIL_ROWS_DEFAULT);
+    if (o.op != SPK_AMG_OPERATOR_CSR && o.op != SPK_AMG_OPERATOR_STENCIL)
+        fail(SPK_ERR_ARG, "amg: op %d is neither SPK_AMG_OPERATOR_CSR (0) nor SPK_AMG_OPERATOR_STENCIL (1)", o.op);
+    if (o.op == SPK_AMG_OPERATOR_STENCIL && o.coarsening != SPK_AMG_COARSEN_GRID)
+        fail(SPK_ERR_UNSUPPORTED, "amg: -spk_mg_operator stencil applies levels whose pattern is the grid stencil's closed form; "
+             "smoothed aggregation (gamg) has none -- use -pc_type mg with -spk_mg_galerkin stencil, or -spk_mg_operator csr");
+    if (o.op == SPK_AMG_OPERATOR_STENCIL && o.galerkin != SPK_AMG_GALERKIN_STENCIL)
+        fail(SPK_ERR_UNSUPPORTED, "amg: -spk_mg_operator stencil applies levels whose pattern is the grid stencil's closed form; "
+             "only -spk_mg_galerkin stencil guarantees it (the generic products keep whatever pattern they meet) -- pass "
+             "-spk_mg_galerkin stencil, or -spk_mg_operator csr");
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
@@ -882,10 +895,13 @@ static void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o)
 {
     fill_cycle_info(o, d.info);
     const int L = (int)d.lv.size(), t = d.info.tail_first, nu = o.smooth_its;
+    // (amg_check_opts: the option comes with grid coarsening and the stencil products, so these levels have the closed form)
+    for (int l = 0; l < L; ++l) d.lv[(size_t)l].stencil_op = o.op == SPK_AMG_OPERATOR_STENCIL && l >= 1 && l + 1 < L;
     d.steps = amg_cycle_steps(L, o.cycle);
     d.runs = amg_tail_runs(d.steps, t);
     d.run_sel.assign(d.runs.size(), 0);
     d.tsteps.clear();
+    d.tail_stencil = false;
     if (t < 0) {
         d.tail_desc.release();
         d.tail_steps.release();
@@ -923,6 +939,9 @@ static void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o)
         V.prp = D.P.rowptr.p, V.pci = D.P.colidx.p, V.pv = D.P.val.p;
         V.rrp = D.R.rowptr.p, V.rci = D.R.colidx.p, V.rv = D.R.val.p;
         V.matrix_free = D.grid.matrix_free ? 1 : 0;
+        V.stencil = D.stencil_op ? 1 : 0;
+        d.tail_stencil = d.tail_stencil || D.stencil_op;
+        if (D.grid.on) std::memcpy(V.nd, D.grid.fd, sizeof V.nd);
         if (D.grid.on) V.g = k::grid_args(D.grid), V.bs = D.grid.bs, V.fz = D.grid.fd[2];
         for (int q = 0; q < nu; ++q) V.alpha[q] = D.alpha[(size_t)q], V.beta[q] = D.beta[(size_t)q];
     }
@@ -1376,6 +1395,7 @@ bool amg_can_refresh(spk_ctx *c)
                 a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
                 a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup &&
                 a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides && a.galerkin == b.galerkin;
+    // (cycle, tail, tail_rows and op steer the application, not the hierarchy: not compared)
     for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
     for (int i = 0; i < 3; ++i) same = same && a.grid[i] == b.grid[i];
     if (!same || ctx_block_size(c, a) != ru.bs || c->n_local != ru.n || c->Ad.nnz != ru.nnz || c->ld != ru.ld) return false;
@@ -1397,12 +1417,12 @@ void amg_refresh_ctx(spk_ctx *c)
     AmgDev &d = *c->amg_d;
     AmgReuse &ru = *d.reuse;
     const size_t L = d.lv.size();
-    // cycle, tail and tail_rows steer the application, not the hierarchy (amg_can_refresh does not compare them): the
+    // cycle, tail, tail_rows and op steer the application, not the hierarchy (amg_can_refresh does not compare them): the
     // refresh takes the ones this set-up was given
-    ru.o.cycle = c->amg_opts.cycle, ru.o.tail = c->amg_opts.tail, ru.o.tail_rows = c->amg_opts.tail_rows;
+    ru.o.cycle = c->amg_opts.cycle, ru.o.tail = c->amg_opts.tail, ru.o.tail_rows = c->amg_opts.tail_rows, ru.o.op = c->amg_opts.op;
     if (c->amg_h) {   // the host route: the values down, the host refresh, the values of the levels up
         AmgHier &h = c->amg_h->h;
-        h.o.cycle = ru.o.cycle, h.o.tail = ru.o.tail, h.o.tail_rows = ru.o.tail_rows;
+        h.o.cycle = ru.o.cycle, h.o.tail = ru.o.tail, h.o.tail_rows = ru.o.tail_rows, h.o.op = ru.o.op;
         std::vector<double> val((size_t)c->Ad.nnz);
         if (!val.empty()) SPK_HIP(hipMemcpyAsync(val.data(), c->Ad.val.p, sizeof(double) * val.size(), hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
@@ -1502,6 +1522,42 @@ void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_l
     SPK_HIP(hipStreamSynchronize(s));
 }
 
+// the test hook of the level operators: one launch of either route on copies of the caller's vectors
+void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
+                        const double *b, double *out)
+{
+    AmgDev &d = *c->amg_d;
+    if (l < 1 || l + 1 >= (int)d.lv.size())
+        fail(SPK_ERR_ARG, "amg: operator hook: level %d is not between level 0 and the coarsest level %d", l, (int)d.lv.size() - 1);
+    if (which < 0 || which > 3 || (stencil != 0 && stencil != 1)) fail(SPK_ERR_ARG, "amg: operator hook: which is 0..3, stencil 0 or 1");
+    AmgLevelDev &D = d.lv[(size_t)l];
+    if (stencil && !(d.info.coarsening == SPK_AMG_COARSEN_GRID && d.info.galerkin == SPK_AMG_GALERKIN_STENCIL && D.grid.on))
+        fail(SPK_ERR_STATE, "amg: level %d was not built by -spk_mg_galerkin stencil: its pattern is no closed form", l);
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)D.n;
+    const bool step = which & 1, gated = which >= 2;
+    DevBuf<double> dx, dxo, db, dout;
+    DevBuf<int32_t> gate;
+    dx.upload(x, n, 16);
+    if (step) db.upload(b, n, 16);
+    if (step && xo) dxo.upload(xo, n, 16);
+    if (gated) {
+        const int32_t one = 1;
+        gate.upload(&one, 1);
+        dout.upload(out, n, 16);
+    } else {
+        dout.alloc(n, 16);
+    }
+    const int32_t *done = gated ? gate.p : nullptr;
+    const double *yo = step && xo ? dxo.p : nullptr;
+    if (stencil) k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, step ? 1 : 0, dx.p, D.dinv.p, db.p, yo, dout.p, alpha, beta, done, s);
+    else if (step) k::amg_cheb_csr(D.A, D.dinv.p, db.p, dx.p, yo, dout.p, alpha, beta, done, s);
+    else k::amg_spmv(D.A, dx.p, dout.p, done, s);
+    SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    c->check_device_error();
+}
+
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
 // (n_local % 2: never false here -- the 2x2 blocked copy the row types are built over exists only for an even n_local;
 // the condition states what amg_cheb_dict2 needs rather than guarding a case that occurs)
@@ -1523,6 +1579,8 @@ static double *smooth(spk_ctx *c, AmgLevelDev &D, int l, const double *b, double
         } else if (l == 0) {                   // other layouts: the layout's own product, then a vector pass
             if (y) a_mult(c, y, D.t.p, nullptr, nullptr, done, false, nullptr);
             k::amg_cheb_vec(D.n, dinv, b, D.t.p, y, prev, dst, D.alpha[k], D.beta[k], done, s);
+        } else if (y && D.stencil_op) {
+            k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, 1, y, dinv, b, prev, dst, D.alpha[k], D.beta[k], done, s);
         } else if (y) {
             k::amg_cheb_csr(D.A, dinv, b, y, prev, dst, D.alpha[k], D.beta[k], done, s);
         } else {
@@ -1545,7 +1603,7 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
     for (size_t i = 0; i < d.steps.size(); ++i) {   // the cycle's steps in order (amg_cycle_steps); under V: down, coarse, up
         if (run < d.runs.size() && (size_t)d.runs[run].first == i) {   // a tail run: one launch of one workgroup
             const size_t t = (size_t)d.info.tail_first;
-            k::amg_tail(d.tail_desc.p, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, s);
+            k::amg_tail(d.tail_desc.p, d.tail_stencil, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, s);
             cur[t] = d.run_sel[run] ? d.lv[t].yb.p : d.lv[t].ya.p;
             i = (size_t)d.runs[run++].second - 1;
             continue;
@@ -1558,8 +1616,10 @@ void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *
         case SPK_AMG_STEP_POST: cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done); break;
         case SPK_AMG_STEP_DOWN: {   // residual, restriction
             if (l == 0) a_mult(c, cur[l], D.t.p, nullptr, nullptr, done, false, nullptr);
-            else k::amg_spmv(D.A, cur[l], D.ya.p == cur[l] ? D.yb.p : D.ya.p, done, s);
-            const double *t = l == 0 ? D.t.p : (D.ya.p == cur[l] ? D.yb.p : D.ya.p);
+            double *o = D.ya.p == cur[l] ? D.yb.p : D.ya.p;
+            if (l > 0 && D.stencil_op) k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, 0, cur[l], nullptr, nullptr, nullptr, o, 0.0, 0.0, done, s);
+            else if (l > 0) k::amg_spmv(D.A, cur[l], o, done, s);
+            const double *t = l == 0 ? D.t.p : o;
             if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b.p, done, s);
             else k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
             break;

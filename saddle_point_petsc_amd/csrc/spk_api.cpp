@@ -409,6 +409,16 @@ int spk_debug_amg_transfer(spk_ctx *c, int level, int which, int stored, int64_t
     SPK_CATCH(c)
 }
 
+int spk_debug_amg_operator(spk_ctx *c, int level, int which, int stencil, double alpha, double beta, const double *x,
+                           const double *xo, const double *b, double *out)
+{
+    SPK_TRY(c)
+    if (!x || !out || (!b && (which & 1))) spk::fail(SPK_ERR_ARG, "debug_amg_operator: null pointer");
+    need_amg(c);
+    spk::amg_debug_operator(c, level, which, stencil, alpha, beta, x, xo, b, out);
+    SPK_CATCH(c)
+}
+
 int spk_pc_set_amg_reuse(spk_ctx *c, int reuse)
 {
     SPK_TRY(c)

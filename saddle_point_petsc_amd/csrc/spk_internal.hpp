@@ -839,6 +839,7 @@ struct AmgTailLevel {
     double *b, *ya, *yb;
     int32_t n, nc;                  // rows of the level and of level l + 1
     int32_t nu, bs, matrix_free, fz;   // smoothing steps; node size; the transfers are the grid rule's; fine nodes in z
+    int32_t stencil, nd[3];         // A_l is applied from av alone (SPK_AMG_OPERATOR_STENCIL); the level's node grid
     GridArgs g;
     double alpha[kAmgMaxSmooth], beta[kAmgMaxSmooth];
 };
@@ -852,12 +853,20 @@ struct AmgTailDesc {
     AmgTailLevel lv[SPK_AMG_MAX_LEVELS];   // by level; those below `first` are not filled
 };
 constexpr int kAmgTailThreads = 1024;   // one workgroup, 16 waves: 128 CSR rows or 16 dense rows per sweep
-// steps [s0, s1) of d->steps -- one tail run -- in one launch of one workgroup
-void amg_tail(const AmgTailDesc *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);
+// steps [s0, s1) of d->steps -- one tail run -- in one launch of one workgroup; stencil: a level of the tail has its
+// `stencil` flag set (the kernel that knows the value-array route; without, the kernel is the one of the CSR route alone)
+void amg_tail(const AmgTailDesc *d, bool stencil, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);
 // smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
 void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
 void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
                   double alpha, double beta, const int32_t *done, hipStream_t s);   // out = y + a D^-1 (b - A y) + b (y - yo)
+// the same two on a level with the grid stencil's closed-form pattern (nd: its node grid, bs its node size), from A.val
+// alone -- rowptr and colidx are not read (SPK_AMG_OPERATOR_STENCIL; spk_stencil_op_core.hpp states the sums).  mode 0:
+// out = A x; mode 1: out = x + alpha dinv (b - A x) + beta (x - yo).  stencil_op_rows: the rows of one workgroup
+struct StencilOpArgs { int32_t nx, ny, nz, n; };   // the level's node grid and its rows
+int stencil_op_rows(const int32_t nd[3], int bs);
+void amg_stencil_op(const CsrDev &A, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv, const double *b,
+                    const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
 void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s);   // out = R (b - t)
 void amg_prolong_add(const CsrDev &P, const double *e, double *y, const int32_t *done, hipStream_t s);          // y += P e
 // y == nullptr: out = alpha dinv b (zero initial guess); else out = y + alpha dinv (b - t) + beta (y - yo) (yo null: 0)
@@ -922,6 +931,7 @@ struct AmgLevelDev {
     DevBuf<double> b, ya, yb, t;       // right-hand side, two iterates, the fine level's product
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
     k::AmgGrid grid;                    // grid coarsening: the transfer to level l+1
+    bool stencil_op = false;           // the cycle applies A from A.val alone (SPK_AMG_OPERATOR_STENCIL; amg_plan_cycle sets it)
 };
 // what a set-up with reuse on (spk_pc_set_amg_reuse) keeps beside the hierarchy, so that the next one can refresh it
 struct AmgReuse {
@@ -949,6 +959,7 @@ struct AmgDev {
     std::vector<k::AmgTailStep> tsteps;
     std::vector<std::pair<int64_t, int64_t>> runs;
     std::vector<int32_t> run_sel;   // per run: the buffer (0: ya, 1: yb) it leaves the iterate of level tail_first in
+    bool tail_stencil = false;      // a level inside the tail applies A from its value array alone
     DevBuf<k::AmgTailDesc> tail_desc;
     DevBuf<k::AmgTailStep> tail_steps;
 };
@@ -1119,6 +1130,8 @@ void amg_drop_reuse(spk_ctx *c);
 void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
 void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out);
+void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
+                        const double *b, double *out);
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last = nullptr);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

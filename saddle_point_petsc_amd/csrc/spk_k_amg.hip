@@ -4,8 +4,10 @@
 // takes the solver's `done` gate.  A level coarsened by the grid rule (-pc_type mg) applies P and R without reading
 // them: amg_prolong_grid_kernel / amg_restrict_grid_kernel below.  The per-row work of every kernel of a coarse level is a
 // __device__ function of the row index, shared with amg_tail_kernel, which runs the coarse levels' steps as one workgroup
-// in one launch (-spk_mg_tail fused) and gives the launches' bits.
+// in one launch (-spk_mg_tail fused) and gives the launches' bits.  A level whose pattern is the grid stencil's closed form
+// applies A from its value array alone where the options ask for it (-spk_mg_operator stencil): amg_stencil_kernel.
 #include "spk_dict.hpp"
+#include "spk_stencil_op_core.hpp"
 
 namespace spk {
 namespace k {
@@ -77,6 +79,50 @@ __global__ __launch_bounds__(kThreads) void amg_csr_kernel(const int32_t *__rest
     const int32_t i = (int32_t)blockIdx.x * kAmgRows + (int32_t)(threadIdx.x / kAmgLanes);
     if (i >= n) return;   // whole groups of eight leave together: the butterfly stays inside live lanes
     csr_row<MODE>(rp, ci, v, x, sub, dinv, b, yo, out, alpha, beta, i, lane);
+}
+
+// ---- a level >= 1 with the grid stencil's closed-form pattern, from its value array alone (SPK_AMG_OPERATOR_STENCIL) ----
+// MODE 0: out = A x;  MODE 1: out = y + alpha dinv (b - A y) + beta (y - yo) (amg_csr_kernel<1>'s formula; out may be yo,
+// never y).  One row per thread, `rows` = blockDim.x consecutive rows per workgroup: their values are one contiguous range
+// of `v` (so_row_begin of the first row to that of the row behind the last), streamed into LDS by consecutive lanes in
+// 16-byte pieces; then every thread runs so_row (spk_stencil_op_core.hpp) on its own row from there -- the gather of x is
+// contiguous across lanes, neighbouring rows being neighbouring nodes of a grid line.  The range begins at a multiple of
+// BS, not of two: it is staged from the even position at or below its begin, so that 16-byte pieces of global memory
+// are 16-byte pieces of LDS, with the odd first and last values peeled.  No row pointer or column index is read.
+// Byte model: 8 B per stored entry + x (gathered, cached) + out; MODE 1: + dinv, b, yo.
+template <int BS, int MODE>
+__global__ __launch_bounds__(kThreads) void amg_stencil_kernel(StencilOpArgs g, const double *__restrict__ v, const double *x,
+                                                               const double *__restrict__ dinv, const double *__restrict__ b,
+                                                               const double *yo, double *out, double alpha, double beta,
+                                                               const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *sv = reinterpret_cast<double *>(smem);
+    const int32_t nd[3] = {g.nx, g.ny, g.nz};
+    const int32_t rows = (int32_t)blockDim.x, r0 = (int32_t)blockIdx.x * rows, r1 = min(r0 + rows, g.n);
+    if (r0 >= g.n) return;   // (workgroup-uniform)
+    const int64_t p0 = stencil_op::so_row_begin<BS>(nd, r0), p1 = stencil_op::so_row_begin<BS>(nd, r1);
+    const int64_t base = p0 & ~(int64_t)1;   // sv[e] = v[base + e]
+    const int64_t q0 = (p0 + 1) >> 1, q1 = p1 >> 1;   // the whole pairs [2 q0, 2 q1) of the range
+    const double2 *v2 = reinterpret_cast<const double2 *>(v);
+    double2 *s2 = reinterpret_cast<double2 *>(sv);
+    for (int64_t q = q0 + threadIdx.x; q < q1; q += 4 * rows) {   // four pieces per thread in flight
+        double2 t[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = v2[min(q + u * rows, q1 - 1)];   // (past the range: its last piece again, not stored)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (q + u * rows < q1) s2[q + u * rows - (base >> 1)] = t[u];
+    }
+    if (threadIdx.x == 0 && (p0 & 1)) sv[p0 - base] = v[p0];
+    if (threadIdx.x == 1 && (p1 & 1) && p1 - 1 >= 2 * q0) sv[p1 - 1 - base] = v[p1 - 1];
+    __syncthreads();
+    const int32_t r = r0 + (int32_t)threadIdx.x;
+    if (r >= r1) return;
+    const stencil_op::SoRow w = stencil_op::so_row_of<BS>(nd, r);
+    const int64_t off = galerkin::gs_row_offset(nd, BS, w.i, w.j, w.k, w.a);
+    out[r] = stencil_op::so_row<BS, MODE>(nd, w, sv + (off - base), x, dinv, b, yo, alpha, beta);
 }
 
 // the fine level's vector pass behind the layout's own product t = A y:
@@ -330,13 +376,38 @@ __device__ __forceinline__ void tail_csr(const int32_t *__restrict__ rp, const i
     __syncthreads();
 }
 
+// the same steps on a level applied from its value array alone (V.stencil): so_row over the level's rows, the values
+// read from global memory; the bits are amg_stencil_kernel's
+template <int BS, int MODE>
+__device__ __forceinline__ void tail_stencil_bs(const AmgTailLevel &V, const double *x, const double *yo, double *out, double alpha,
+                                                double beta)
+{
+    const int32_t nd[3] = {V.nd[0], V.nd[1], V.nd[2]};
+    for (int32_t r = (int32_t)threadIdx.x; r < V.n; r += kAmgTailThreads) {
+        const stencil_op::SoRow w = stencil_op::so_row_of<BS>(nd, r);
+        const double *v = V.av + galerkin::gs_row_offset(nd, BS, w.i, w.j, w.k, w.a);
+        out[r] = stencil_op::so_row<BS, MODE, 1>(nd, w, v, x, V.dinv, V.b, yo, alpha, beta);   // (one line at a time: 1024 threads leave 128 registers each)
+    }
+    __syncthreads();
+}
+template <int MODE>
+__device__ __forceinline__ void tail_stencil(const AmgTailLevel &V, const double *x, const double *yo, double *out, double alpha,
+                                             double beta)
+{
+    if (V.bs == 1) tail_stencil_bs<1, MODE>(V, x, yo, out, alpha, beta);
+    else if (V.bs == 2) tail_stencil_bs<2, MODE>(V, x, yo, out, alpha, beta);
+    else tail_stencil_bs<3, MODE>(V, x, yo, out, alpha, beta);
+}
+
 // nu smoothing steps on level V from y (null: the zero guess), as smooth() orders them; ends in sel ^ (nu & 1) (from null: in ya for odd nu)
+template <bool STENCIL>
 __device__ __forceinline__ void tail_smooth(const AmgTailLevel &V, double *y)
 {
     const double *prev = nullptr;
     for (int32_t k = 0; k < V.nu; ++k) {
         double *dst = y == V.ya ? V.yb : V.ya;
-        if (y) tail_csr<1>(V.arp, V.aci, V.av, V.n, y, nullptr, V.dinv, V.b, prev, dst, V.alpha[k], V.beta[k]);
+        if (STENCIL && y && V.stencil) tail_stencil<1>(V, y, prev, dst, V.alpha[k], V.beta[k]);
+        else if (y) tail_csr<1>(V.arp, V.aci, V.av, V.n, y, nullptr, V.dinv, V.b, prev, dst, V.alpha[k], V.beta[k]);
         else {   // amg_cheb_vec_kernel from the zero guess
             const double alpha = V.alpha[k];
             for (int32_t i = (int32_t)threadIdx.x; i < V.n; i += kAmgTailThreads) dst[i] = alpha * (V.dinv[i] * V.b[i]);
@@ -369,21 +440,24 @@ __device__ __forceinline__ void tail_prolong_grid(const AmgTailLevel &V, const d
 }
 }  // namespace
 
-__global__ __launch_bounds__(kAmgTailThreads) void amg_tail_kernel(const AmgTailDesc *__restrict__ d, int32_t s0, int32_t s1,
-                                                                   const int32_t *__restrict__ done)
+// STENCIL: a level of the tail may apply A from its value array alone (AmgTailLevel.stencil): amg_stencil_tail_kernel;
+// without, the body is amg_tail_kernel as it was before that option existed
+namespace {
+template <bool STENCIL>
+__device__ __forceinline__ void tail_run(const AmgTailDesc *__restrict__ d, int32_t s0, int32_t s1)
 {
-    if (done && *done) return;   // written by launches before this one only: the whole workgroup reads one value
     for (int32_t s = s0; s < s1; ++s) {
         const AmgTailStep st = d->steps[s];
         const AmgTailLevel &V = d->lv[st.level];
         double *y = st.sel ? V.yb : V.ya, *o = st.sel ? V.ya : V.yb;   // the level's iterate and the other buffer
         switch (st.kind) {
-        case SPK_AMG_STEP_PRE0: tail_smooth(V, nullptr); break;
+        case SPK_AMG_STEP_PRE0: tail_smooth<STENCIL>(V, nullptr); break;
         case SPK_AMG_STEP_PRE:
-        case SPK_AMG_STEP_POST: tail_smooth(V, y); break;
+        case SPK_AMG_STEP_POST: tail_smooth<STENCIL>(V, y); break;
         case SPK_AMG_STEP_DOWN: {   // o = A y, then b of the next level = R (b - o)
             double *bn = d->lv[st.level + 1].b;
-            tail_csr<0>(V.arp, V.aci, V.av, V.n, y, nullptr, nullptr, nullptr, nullptr, o, 0.0, 0.0);
+            if (STENCIL && V.stencil) tail_stencil<0>(V, y, nullptr, o, 0.0, 0.0);
+            else tail_csr<0>(V.arp, V.aci, V.av, V.n, y, nullptr, nullptr, nullptr, nullptr, o, 0.0, 0.0);
             if (V.matrix_free) {
                 if (V.bs == 1) tail_restrict_grid<1>(V, o, bn);
                 else if (V.bs == 2) tail_restrict_grid<2>(V, o, bn);
@@ -416,6 +490,20 @@ __global__ __launch_bounds__(kAmgTailThreads) void amg_tail_kernel(const AmgTail
         }
         }
     }
+}
+}  // namespace
+
+__global__ __launch_bounds__(kAmgTailThreads) void amg_tail_kernel(const AmgTailDesc *__restrict__ d, int32_t s0, int32_t s1,
+                                                                   const int32_t *__restrict__ done)
+{
+    if (done && *done) return;   // written by launches before this one only: the whole workgroup reads one value
+    tail_run<false>(d, s0, s1);
+}
+__global__ __launch_bounds__(kAmgTailThreads) void amg_stencil_tail_kernel(const AmgTailDesc *__restrict__ d, int32_t s0, int32_t s1,
+                                                                           const int32_t *__restrict__ done)
+{
+    if (done && *done) return;
+    tail_run<true>(d, s0, s1);
 }
 
 namespace {
@@ -459,6 +547,34 @@ void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const do
     hipLaunchKernelGGL(amg_csr_kernel<1>, csr_grid(A.nrows), dim3(kThreads), 0, s, A.rowptr.p, A.colidx.p, A.val.p, A.nrows,
                        y, (const double *)nullptr, dinv, b, yo, out, alpha, beta, done);
 }
+// rows per workgroup of amg_stencil_kernel: whole waves whose longest rows fill at most 32 KiB of LDS (several
+// workgroups per CU), at most kThreads.  2-D: 256 (bs 1), 192 (bs 2), 128 (bs 3); 3-D: 128, 64, 64 (bs 3: 41 KiB)
+int stencil_op_rows(const int32_t nd[3], int bs)
+{
+    const int per = 32768 / (stencil_op::so_max_row(nd, bs) * (int)sizeof(double));
+    return std::min(std::max(per / kWave * kWave, kWave), kThreads);
+}
+template <int BS>
+static void stencil_op_launch(const StencilOpArgs &g, int rows, size_t lds, int mode, const double *v, const double *x,
+                              const double *dinv, const double *b, const double *yo, double *out, double alpha, double beta,
+                              const int32_t *done, hipStream_t s)
+{
+    const dim3 grid((unsigned)((g.n + rows - 1) / rows));
+    if (mode == 0) hipLaunchKernelGGL((amg_stencil_kernel<BS, 0>), grid, dim3(rows), lds, s, g, v, x, dinv, b, yo, out, alpha, beta, done);
+    else hipLaunchKernelGGL((amg_stencil_kernel<BS, 1>), grid, dim3(rows), lds, s, g, v, x, dinv, b, yo, out, alpha, beta, done);
+}
+void amg_stencil_op(const CsrDev &A, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv, const double *b,
+                    const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s)
+{
+    if (A.nrows == 0) return;
+    const StencilOpArgs g{nd[0], nd[1], nd[2], A.nrows};
+    const int rows = stencil_op_rows(nd, bs);
+    // the workgroup's range and the one value in front of an odd begin, rounded up to whole pairs
+    const size_t lds = ((size_t)rows * (size_t)stencil_op::so_max_row(nd, bs) + 2) * sizeof(double);
+    if (bs == 1) stencil_op_launch<1>(g, rows, lds, mode, A.val.p, x, dinv, b, yo, out, alpha, beta, done, s);
+    else if (bs == 2) stencil_op_launch<2>(g, rows, lds, mode, A.val.p, x, dinv, b, yo, out, alpha, beta, done, s);
+    else stencil_op_launch<3>(g, rows, lds, mode, A.val.p, x, dinv, b, yo, out, alpha, beta, done, s);
+}
 void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s)
 {
     if (R.nrows == 0) return;
@@ -500,10 +616,11 @@ void amg_dense(const double *C, int32_t n, const double *b, double *y, const int
     const int rows = kThreads / kWave;
     hipLaunchKernelGGL(amg_dense_kernel, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, s, C, n, b, y, done);
 }
-void amg_tail(const AmgTailDesc *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s)
+void amg_tail(const AmgTailDesc *d, bool stencil, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s)
 {
     if (s0 >= s1) return;
-    hipLaunchKernelGGL(amg_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
+    if (stencil) hipLaunchKernelGGL(amg_stencil_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
+    else hipLaunchKernelGGL(amg_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
 }
 void amg_out(int mode, int64_t n, const double *src, double *dst, const int32_t *done, hipStream_t s)
 {

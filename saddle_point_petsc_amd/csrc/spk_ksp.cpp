@@ -156,6 +156,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "products") o.galerkin = SPK_AMG_GALERKIN_PRODUCTS;
         else if (v == "stencil") o.galerkin = SPK_AMG_GALERKIN_STENCIL;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (products | stencil)");
+    } else if (key == "-spk_mg_operator") {
+        if (!val) return need("csr or stencil");
+        const std::string v(val);
+        if (v == "csr") o.op = SPK_AMG_OPERATOR_CSR;
+        else if (v == "stencil") o.op = SPK_AMG_OPERATOR_STENCIL;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (csr | stencil)");
     } else if (key == "-spk_mg_cycle") {
         if (!val) return need("v or w");
         const std::string v(val);
@@ -683,6 +689,13 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                             ai.galerkin == SPK_AMG_GALERKIN_STENCIL ? "the gather on the grid stencil, closed-form patterns"
                                                                     : "the generic sparse products",
                             ai.galerkin == SPK_AMG_GALERKIN_STENCIL ? "stencil" : "products");
+            if (grid && ai.op == SPK_AMG_OPERATOR_STENCIL && ai.levels > 2)
+                std::printf("    level operators: stencil (-spk_mg_operator stencil): levels 1..%d apply A from their value arrays "
+                            "alone, no row pointers or column indices read\n", ai.levels - 2);
+            else if (grid && ai.op == SPK_AMG_OPERATOR_STENCIL)
+                std::printf("    level operators: stencil (-spk_mg_operator stencil): no level between level 0 and the coarsest\n");
+            else if (grid)
+                std::printf("    level operators: csr (-spk_mg_operator csr): levels >= 1 as sparse matrices\n");
             const int tail = ai.tail_first >= 0 ? SPK_AMG_TAIL_FUSED : SPK_AMG_TAIL_LAUNCHES;   // as it resolved on these levels
             std::printf("    cycle %s (-spk_mg_cycle), tail %s (-spk_mg_tail %s), tail_first %d, tail_rows %d%s, tail launches per application %d\n",
                         ai.cycle == SPK_AMG_CYCLE_W ? "w" : "v", tail == SPK_AMG_TAIL_FUSED ? "fused" : "launches",

@@ -49,6 +49,7 @@ AMG_TRANSFER_MATRIX_FREE, AMG_TRANSFER_STORED = 0, 1
 AMG_SIDES_ODD, AMG_SIDES_ANY = 0, 1
 AMG_CYCLE_V, AMG_CYCLE_W = 0, 1
 AMG_GALERKIN_PRODUCTS, AMG_GALERKIN_STENCIL = 0, 1
+AMG_OPERATOR_CSR, AMG_OPERATOR_STENCIL = 0, 1
 AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED = 0, 1, 2
 AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST = range(6)
 SPK_ERR_ARG = -1   # include/spk.h
@@ -59,6 +60,7 @@ _TRANSFERS = {"matrixfree": AMG_TRANSFER_MATRIX_FREE, "stored": AMG_TRANSFER_STO
 _SIDES = {"odd": AMG_SIDES_ODD, "any": AMG_SIDES_ANY}
 _CYCLES = {"v": AMG_CYCLE_V, "w": AMG_CYCLE_W}
 _GALERKINS = {"products": AMG_GALERKIN_PRODUCTS, "stencil": AMG_GALERKIN_STENCIL}
+_OPERATORS = {"csr": AMG_OPERATOR_CSR, "stencil": AMG_OPERATOR_STENCIL}
 _TAILS = {"auto": AMG_TAIL_AUTO, "launches": AMG_TAIL_LAUNCHES, "fused": AMG_TAIL_FUSED}
 
 
@@ -66,12 +68,18 @@ def amg_opts(**kw):
     """spk_amg_opts with PETSc's defaults, overridden by keyword (smoother may be 'chebyshev' / 'richardson', setup
     'host' / 'device', coarsening 'aggregation' / 'grid', transfer 'matrixfree' / 'stored', sides 'odd' / 'any', cycle
     'v' / 'w', tail 'auto' / 'launches' / 'fused', galerkin 'products' / 'stencil' (what forms the coarse operators of a
-    grid-coarsened hierarchy: the generic sparse products, or the gather on the node grid);
+    grid-coarsened hierarchy: the generic sparse products, or the gather on the node grid), operator 'csr' / 'stencil'
+    (how the cycle applies the levels between level 0 and the coarsest: as sparse matrices, or from their value arrays
+    alone -- the struct's field is `op`; 'stencil' needs coarsening='grid' and galerkin='stencil');
     grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
     ones too)."""
     o = AmgOpts()
     lib.spk_default_amg_opts(C.byref(o))
     for k, v in kw.items():
+        if k == "operator":
+            k = "op"
+            if isinstance(v, str):
+                v = _OPERATORS[v]
         if not hasattr(o, k):
             raise TypeError(f"unknown multigrid option {k}")
         if k == "smoother" and isinstance(v, str):
@@ -105,6 +113,7 @@ def amg_opts_dict(o):
     d = {k: getattr(o, k) for k, _ in AmgOpts._fields_}
     d["esteig"] = tuple(o.esteig)
     d["grid"] = tuple(o.grid)
+    d["operator"] = o.op
     return d
 
 
@@ -114,7 +123,7 @@ def _amg_info(ai):
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
                 dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides, cycle=ai.cycle, tail_first=ai.tail_first,
-                tail_launches=ai.tail_launches, galerkin=ai.galerkin)
+                tail_launches=ai.tail_launches, galerkin=ai.galerkin, operator=ai.op)
 
 
 def amg_stencil_children(fine, coarse, node):
@@ -641,6 +650,27 @@ class Context:
         pro = which == "prolong"
         out = np.zeros(b.size if pro else info["rows"][level + 1])
         self._chk(lib.spk_debug_amg_transfer(self.h, level, 0 if pro else 1, 1 if stored else 0, b.size, a, b, out))
+        return out
+
+    def debug_amg_operator(self, level, which, x, b=None, xo=None, alpha=0.0, beta=0.0, stencil=True, done=False, out=None):
+        """Test hook (spk_debug_amg_operator): the operator of a level between level 0 and the coarsest alone, one launch.
+        which 'product': A x; 'step': x + alpha D^-1 (b - A x) + beta (x - xo) (xo None: the zero vector).  stencil: the
+        value-array kernels, else the CSR kernels.  done: the launch finds the `done` gate set, and `out` (given, or
+        zeros) comes back as it went in."""
+        rows = self.amg_info()["rows"]
+        if not 0 <= level < len(rows):
+            raise SpkError(SPK_ERR_ARG, f"level {level} outside the hierarchy")
+        n = rows[level]
+        step = which == "step"
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, np.float64)
+        x, b, xo = vec(x), vec(b), vec(xo)
+        for v in (x, b, xo):
+            if v is not None and v.size != n:
+                raise SpkError(SPK_ERR_ARG, f"a vector of {v.size} entries for the {n} rows of level {level}")
+        out = np.zeros(n) if out is None else np.array(out, np.float64)
+        ptr = lambda v: None if v is None else v.ctypes.data
+        self._chk(lib.spk_debug_amg_operator(self.h, level, (1 if step else 0) + (2 if done else 0), 1 if stencil else 0,
+                                             float(alpha), float(beta), x, ptr(xo), ptr(b), out))
         return out
 
     def amg_aggregates(self, level):

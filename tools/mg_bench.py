@@ -26,7 +26,20 @@ route: set-up, solve, iterations, V-cycle, refresh and nnz per level.  The bar, 
 the stencil route's set-up median plus its spread (max - min) at or below the products route's set-up median (exit
 status 1 when missed); the iterations of the two must agree within 1.
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mg_bench.py --setup-only stencil [--grid 1025]
---setup-only products|stencil launches builds alone (a warm-up and --reps more), for a kernel trace."""
+--setup-only products|stencil launches builds alone (a warm-up and --reps more), for a kernel trace.
+    python tools/mg_bench.py --operator both --galerkin stencil [--grids 1025] [--sides odd|any] [--out profiles/FILE.jsonl]
+--operator csr|stencil (-spk_mg_operator; default csr) selects how mg's cycle applies the levels between level 0 and the
+coarsest in the runs above (stencil needs --galerkin stencil); every emitted line records it.  --operator both compares
+the two: K = A, per grid two contexts on the same hierarchy bytes in one process, after one warm-up round --reps
+alternating rounds of set-up -> solve -> V-cycle timing.  Per route: V-cycle, solve, iterations and set-up.  The bar,
+checked at 1025 and 1024 nodes per side: the stencil route's V-cycle median plus its spread (max - min) at or below the csr
+route's V-cycle median (exit status 1 when missed); the iterations of the two must agree within 1.
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mg_bench.py --operator-kernels [--grid 1025]
+    python tools/rocpd_by_grid.py DIR/<host>/<pid>_results.db out.csv amg_stencil_kernel amg_csr_kernel
+--operator-kernels launches the product and the smoothing step of levels 1 and 2 alone through the test hook, on both
+routes alternating (a warm-up round and --reps more), for a kernel trace; tools/rocpd_by_grid.py tells the levels apart by
+their launch grids.  The line it prints has the byte models: 8 B per stored entry (csr: 12 B and the row pointers) plus
+the vectors."""
 import argparse
 import csv
 import glob
@@ -50,12 +63,14 @@ ap.add_argument("--transfers", action="store_true", help="only launch the level-
 ap.add_argument("--transfers-report", metavar="DIR", help="read the kernel trace a --transfers run left under DIR")
 ap.add_argument("--galerkin", choices=["products", "stencil", "both"], default="products", help="mg's coarse operators (-spk_mg_galerkin)")
 ap.add_argument("--setup-only", choices=["products", "stencil"], help="only launch device builds of --grid (for a kernel trace)")
+ap.add_argument("--operator", choices=["csr", "stencil", "both"], default="csr", help="how mg's cycle applies the levels >= 1 (-spk_mg_operator)")
+ap.add_argument("--operator-kernels", action="store_true", help="only launch the level operators of levels 1 and 2 of --grid (for a kernel trace)")
 ap.add_argument("--out", help="append the JSON lines to this file too")
 a = ap.parse_args()
 
 
 def emit(row):
-    line = json.dumps(dict(dict(galerkin=a.galerkin), **dict(row, sides=a.sides)))
+    line = json.dumps(dict(dict(galerkin=a.galerkin, operator=a.operator), **dict(row, sides=a.sides)))
     print(line, flush=True)
     if a.out:
         with open(a.out, "a") as fh:
@@ -139,8 +154,33 @@ if a.setup_only:
     sys.exit(0)
 
 
-def mg_opts(g, galerkin):
-    return dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=galerkin)
+def mg_opts(g, galerkin, operator=None):
+    return dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=galerkin,
+                operator=operator or (a.operator if a.operator != "both" else "csr"))
+
+
+if a.operator_kernels:
+    g = a.grid
+    A, _ = S.AssembleOperator_Laplace(g, g)
+    rng = np.random.default_rng(g)
+    with S.Context(0) as c:
+        c.set_block(S.BLOCK_A00, A)
+        c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, "stencil", "stencil"))
+        info = c.amg_info()
+        models = []
+        for l in (1, 2):
+            n, nnz = info["rows"][l], info["nnz"][l]
+            x, xo, b = rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(n)
+            for rep in range(-1, a.reps):
+                for stencil in (False, True):
+                    c.debug_amg_operator(l, "product", x, stencil=stencil)
+                    c.debug_amg_operator(l, "step", x, b=b, xo=xo, alpha=0.7, beta=0.3, stencil=stencil)
+            # x read + out written; the step: + D^-1, b, y-
+            models.append(dict(level=l, rows=n, nnz=nnz, dims=info["dims"][l],
+                               stencil_product_bytes=8 * nnz + 16 * n, stencil_step_bytes=8 * nnz + 40 * n,
+                               csr_product_bytes=12 * nnz + 4 * (n + 1) + 16 * n, csr_step_bytes=12 * nnz + 4 * (n + 1) + 40 * n))
+    print(json.dumps(dict(mode="operator-kernels-launched", grid=g, sides=a.sides, rounds=a.reps + 1, levels=models)), flush=True)
+    sys.exit(0)
 
 
 def compare_galerkin(g):
@@ -187,6 +227,59 @@ def compare_galerkin(g):
         c.close()
     return {route: (t[route]["setup"], t[route]["its"]) for route in routes}
 
+
+def compare_operator(g):
+    """the two routes of the level operators on K = A over the same hierarchy; returns {route: (V-cycle seconds, iterations)}"""
+    A, f = S.AssembleOperator_Laplace(g, g)
+    routes = ("csr", "stencil")
+    ctxs, t = {}, {}
+    for route in routes:
+        c = S.Context(0)
+        c.set_block(S.BLOCK_A00, A)
+        ctxs[route] = c
+        t[route] = dict(setup=[], solve=[], vcycle=[], its=[], res=[])
+    for rep in range(-1, a.reps):   # -1: the warm-up round, not counted
+        for route, c in ctxs.items():
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, "stencil", route))
+            x, info = c.fgmres(f, rtol=a.rtol, max_it=500, restart=30)
+            assert info["reason"] == 2, (route, info["reason"])
+            vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            r = t[route]
+            r["setup"].append(c.amg_info()["setup_seconds"])
+            r["solve"].append(info["solve_seconds"])
+            r["vcycle"].append(vc_ms * 1e-3)
+            r["its"].append(info["its"])
+            r["res"].append(float(np.linalg.norm(f - c.mult(x)) / np.linalg.norm(f)))
+    for route, c in ctxs.items():
+        info, r = c.amg_info(), t[route]
+        assert info["operator"] == (route == "stencil")
+        emit(dict(mode="operator", system="A", grid=g, pc="mg", route=route, solver="fgmres(30)", rtol=a.rtol, reps=a.reps,
+                  levels=info["levels"], rows=info["rows"], nnz=info["nnz"], operator_complexity=round(info["operator_complexity"], 4),
+                  its=sorted(set(r["its"])), true_rel_res=max(r["res"]), pc_apply_us=mmm(r["vcycle"], 1e6, 1),
+                  solve_ms=mmm(r["solve"], 1e3, 3), setup_ms=mmm(r["setup"], 1e3, 3)))
+        c.close()
+    return {route: (t[route]["vcycle"], t[route]["its"]) for route in routes}
+
+
+if a.operator == "both":
+    if a.galerkin != "stencil":
+        sys.exit("--operator both compares two applications of stencil-built levels: pass --galerkin stencil")
+    met = True
+    for g in a.grids:
+        s = compare_operator(g)
+        (cv, ci), (sv, si) = s["csr"], s["stencil"]
+        same_its = max(abs(u - v) for u in ci for v in si) <= 1
+        row = dict(mode="bar", system="A", grid=g, iterations_within_one=bool(same_its), csr_pc_apply_us=mmm(cv, 1e6, 1),
+                   stencil_pc_apply_us=mmm(sv, 1e6, 1), csr_over_stencil=round(float(np.median(cv) / np.median(sv)), 3))
+        met = met and same_its
+        if g in (1024, 1025):
+            ok = float(np.median(sv)) + (max(sv) - min(sv)) <= float(np.median(cv))
+            met = met and ok
+            row.update(bar="stencil V-cycle median + spread <= csr V-cycle median", bar_met=bool(ok))
+        emit(row)
+    sys.exit(0 if met else 1)
 
 if a.galerkin == "both":
     met = True
