@@ -369,6 +369,16 @@ enum { SPK_AMG_GALERKIN_PRODUCTS = 0, SPK_AMG_GALERKIN_STENCIL = 1 };
  * route guarantees the pattern on both set-up routes; otherwise spk_pc_set_amg / spk_amg_build_host fail with
  * SPK_ERR_UNSUPPORTED naming `-spk_mg_galerkin stencil` (or `-pc_type mg` under aggregation) and nothing changes. */
 enum { SPK_AMG_OPERATOR_CSR = 0, SPK_AMG_OPERATOR_STENCIL = 1 };
+/* Who holds the scalars of the device set-up's Lanczos (SPK_AMG_SETUP_DEVICE only; the tridiagonal, lambda_max and with
+ * them every byte of the hierarchy are the same under both).  STEPWISE (the default): the host reads the two sums of every
+ * step back -- it passes them to the next launch and keeps the break rule: 1 + 2 steps drained read-backs per level.
+ * RESIDENT: the sums stay in a small block on the device; the workgroup that finishes a sum applies the host loop's rule
+ * to it (the square root correctly rounded, the same break test), the next launch loads what it needs from the block, and a
+ * launch after the break returns at once.  All 30 steps of a level are enqueued without a synchronise and the host reads
+ * the block back once per level.  The sums are reduced by the same finish in the same launch geometry, so their bits are
+ * the stepwise route's.  RESIDENT with setup = SPK_AMG_SETUP_HOST: spk_pc_set_amg fails with SPK_ERR_UNSUPPORTED naming
+ * `-spk_gamg_setup device` and nothing changes; spk_amg_build_host range-checks the field and does not read it. */
+enum { SPK_AMG_LANCZOS_STEPWISE = 0, SPK_AMG_LANCZOS_RESIDENT = 1 };
 /* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail,
  * tail_rows and op alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
  *     cycle(l, fresh): l == L-1: COARSE; return
@@ -410,6 +420,7 @@ typedef struct spk_amg_opts {
     int32_t tail_rows;        /* -spk_mg_tail_rows n: the largest level the fused tail takes (0: SPK_AMG_TAIL_ROWS_DEFAULT; else >= 1) */
     int32_t galerkin;         /* -spk_mg_galerkin products|stencil: SPK_AMG_GALERKIN_* (products; grid coarsening only) */
     int32_t op;               /* -spk_mg_operator csr|stencil: SPK_AMG_OPERATOR_* (csr; stencil needs grid coarsening and galerkin stencil) */
+    int32_t lanczos;          /* -spk_amg_lanczos stepwise|resident: SPK_AMG_LANCZOS_* (stepwise; resident needs setup device) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -429,6 +440,10 @@ typedef struct spk_amg_info {
     int32_t tail_launches;                   /* launches of the tail kernel per application (0 without a tail) */
     int32_t galerkin;                        /* grid coarsening: SPK_AMG_GALERKIN_* of what built the coarse operators (else 0) */
     int32_t op;                              /* SPK_AMG_OPERATOR_* of the application: how the levels 1 .. levels - 2 apply A_l */
+    int32_t lanczos;                         /* SPK_AMG_LANCZOS_* of the route the last build or refresh took (a host-built hierarchy: 0) */
+    int32_t ritz_readbacks;                  /* device -> host reads the Ritz estimates of the last build or refresh made: a stepwise level
+                                                1 + 2 steps, a resident level 1, a level whose Lanczos ran on a download of it 1; a
+                                                host-built hierarchy 0 */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -457,6 +472,11 @@ int spk_debug_amg_transfer(spk_ctx *ctx, int level, int which, int stored, int64
  * was built with grid coarsening and SPK_AMG_GALERKIN_STENCIL: the level has no closed-form pattern). */
 int spk_debug_amg_operator(spk_ctx *ctx, int level, int which, int stencil, double alpha, double beta, const double *x,
                            const double *xo, const double *b, double *out);
+/* Test hook: the Lanczos of the device set-up alone on level `level` (0 <= level < levels - 1, else SPK_ERR_ARG) of the
+ * context's device-built hierarchy (SPK_ERR_STATE without one), on the unscaled operator.  resident 0: the stepwise route,
+ * 1: the resident route, whatever the context's option is.  *steps: the steps taken (<= 30); al: 30 doubles, be: 31 doubles
+ * (be[0] = 0), both filled up to *steps -- the tridiagonal whose extreme eigenvalues are the level's Ritz values. */
+int spk_debug_amg_lanczos(spk_ctx *ctx, int level, int resident, int32_t *steps, double *al, double *be);
 /* Reuse of the interpolation (PETSc: -pc_gamg_reuse_interpolation).  Sticky like spk_pc_set_schur_pre, default 0.  With
  * reuse on, a spk_pc_setup that finds a hierarchy an earlier set-up built with reuse on, the same spk_amg_opts (field by
  * field, route and block size included), the same local size and padded vector length, and a diagonal A00 block with the

@@ -104,7 +104,12 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * -spk_mg_operator csr|stencil selects how the cycle applies the levels between level 0 and the coarsest (opts->op: as
  * sparse matrices, the default, or from their value arrays alone, SPK_AMG_OPERATOR_STENCIL, which needs mg with
  * -spk_mg_galerkin stencil: otherwise SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED naming what is missing; another value:
- * SPK_ERR_UNSUPPORTED naming the two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * SPK_ERR_UNSUPPORTED naming the two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).
+ * -spk_amg_lanczos stepwise|resident (both multigrids, also as -fieldsplit_0_spk_amg_lanczos) selects who holds the scalars
+ * of the device set-up's Lanczos (opts->lanczos: the host, reading two sums back per step, the default, or a block on the
+ * device read once per level, SPK_AMG_LANCZOS_RESIDENT -- the same hierarchy byte for byte; it needs -spk_gamg_setup device:
+ * otherwise SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED naming that option; another value: SPK_ERR_UNSUPPORTED naming the
+ * two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
  * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
  * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);

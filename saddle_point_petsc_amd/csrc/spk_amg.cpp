@@ -202,6 +202,7 @@ void ritz_extremes(const std::vector<double> &al, const std::vector<double> &be,
 }
 
 constexpr int kLanczosSteps = 30;
+static_assert(kLanczosSteps == lanczos_core::kSteps, "the state block of the resident route holds kLanczosSteps steps");
 
 // extreme Ritz values of D^-1 A after kLanczosSteps Lanczos steps on the similar D^-1/2 A D^-1/2, from a fixed start vector.
 // Ritz values lie inside the spectrum: both estimates approach from within (lmax from below).
@@ -706,7 +707,7 @@ void aggregates_out(const Levels &lv, const spk_amg_info &info, int l, int32_t *
 
 }  // namespace
 
-void amg_check_opts(const spk_amg_opts &o)
+void amg_check_opts(const spk_amg_opts &o, bool host_builder)
 {
     if (o.max_levels < 1 || o.max_levels > SPK_AMG_MAX_LEVELS)
         fail(SPK_ERR_ARG, "amg: max_levels %d outside [1,%d]", o.max_levels, SPK_AMG_MAX_LEVELS);
@@ -752,12 +753,17 @@ void amg_check_opts(const spk_amg_opts &o)
         fail(SPK_ERR_UNSUPPORTED, "amg: -spk_mg_operator stencil applies levels whose pattern is the grid stencil's closed form; "
              "only -spk_mg_galerkin stencil guarantees it (the generic products keep whatever pattern they meet) -- pass "
              "-spk_mg_galerkin stencil, or -spk_mg_operator csr");
+    if (o.lanczos != SPK_AMG_LANCZOS_STEPWISE && o.lanczos != SPK_AMG_LANCZOS_RESIDENT)
+        fail(SPK_ERR_ARG, "amg: lanczos %d is neither SPK_AMG_LANCZOS_STEPWISE (0) nor SPK_AMG_LANCZOS_RESIDENT (1)", o.lanczos);
+    if (!host_builder && o.lanczos == SPK_AMG_LANCZOS_RESIDENT && o.setup == SPK_AMG_SETUP_HOST)
+        fail(SPK_ERR_UNSUPPORTED, "amg: -spk_amg_lanczos resident keeps the scalars of the device set-up's Lanczos on the device; the "
+             "host set-up has no device Lanczos -- pass -spk_gamg_setup device, or -spk_amg_lanczos stepwise");
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
 {
     const auto t0 = Clock::now();
-    amg_check_opts(o);
+    amg_check_opts(o, true);   // (the host builder reads neither setup nor lanczos: it range-checks both)
     if (A.nrows != A.ncols || A.nrows <= 0) fail(SPK_ERR_ARG, "amg: the operator must be square and non-empty");
     std::vector<int32_t> perm;
     sort_rows(A, &perm);
@@ -1102,8 +1108,10 @@ void dev_transpose(CsrDev &T, const CsrDev &A, hipStream_t s)
 
 // the 30 Lanczos steps of `lanczos` with the level's own product (level 0: the context's layout, else the CSR kernel);
 // the two sums of a step come back to the host, which keeps the tridiagonal and the break rule
+// tri (the test hook's): the tridiagonal itself;  *reads += the read-backs made
+struct LzTri { std::vector<double> al, be; };
 void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, double *lmin, double *lmax,
-                 double a_scale = 1.0)
+                 double a_scale = 1.0, int32_t *reads = nullptr, LzTri *tri = nullptr)
 {
     hipStream_t s = c->stream;
     DevBuf<double> sv, q, qp, w, t, aw, res;
@@ -1114,6 +1122,7 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
         double h = 0.0;
         SPK_HIP(hipMemcpyAsync(&h, res.p, sizeof h, hipMemcpyDeviceToHost, s));
         SPK_HIP(hipStreamSynchronize(s));
+        if (reads) ++*reads;
         return h;
     };
     k::amgs_lz_init(n, dinv, 1.0 / a_scale, sv.p, q.p, f, s);
@@ -1136,6 +1145,62 @@ void dev_lanczos(spk_ctx *c, const CsrDev *A, int32_t n, int64_t nv, const doubl
         k::amgs_lz_scale(n, nb, w.p, sv.p, qc, t.p, s);
     }
     c->check_device_error();
+    if (tri) tri->al = al, tri->be = be;
+    ritz_extremes(al, be, lmin, lmax);
+}
+
+// What the resident route (SPK_AMG_LANCZOS_RESIDENT) owns for a whole build or refresh: the six vectors, sized once for
+// level 0's padded length, and the state block.  No level allocates; a level clears what it uses (dev_lanczos gets its
+// vectors zeroed too: the first update reads qp, and level 0's product reads t over the padded length).
+struct LzWork {
+    DevBuf<double> v;
+    DevBuf<lanczos_core::LzState> st;
+    size_t cap = 0;   // doubles per vector
+    static size_t stride(int64_t nv) { return ((size_t)nv + 16 + 31) / 32 * 32; }   // 256-byte aligned, like an allocation of its own
+    void ensure(int64_t nv)
+    {
+        if (v.p && stride(nv) <= cap) return;
+        cap = stride(nv);
+        v.alloc_raw(6 * cap);
+        st.alloc_raw(1);
+    }
+};
+
+// dev_lanczos without the host in the loop: all kk steps enqueued blind, the scalars in the state block (the rule:
+// spk_lanczos_core.hpp), the kernels behind the break returning at their entry (the product still runs, on a stale t into
+// aw, which nothing reads); one read of the block per call.  The sums are dev_lanczos's to the bit, so is the tridiagonal.
+void dev_lanczos_resident(spk_ctx *c, LzWork &wk, const CsrDev *A, int32_t n, int64_t nv, const double *dinv, double *lmin,
+                          double *lmax, double a_scale = 1.0, int32_t *reads = nullptr, LzTri *tri = nullptr)
+{
+    hipStream_t s = c->stream;
+    wk.ensure(nv);
+    const size_t ld = LzWork::stride(nv);
+    double *sv = wk.v.p, *q = sv + ld, *qp = q + ld, *w = qp + ld, *t = w + ld, *aw = t + ld;
+    lanczos_core::LzState *st = wk.st.p;
+    SPK_HIP(hipMemsetAsync(wk.v.p, 0, sizeof(double) * 6 * ld, s));
+    SPK_HIP(hipMemsetAsync(st, 0, sizeof *st, s));
+    const k::Finish f = c->fin(nullptr);
+    k::amgs_lz_init_resident(n, dinv, 1.0 / a_scale, sv, q, f, st, s);
+    k::amgs_lz_scale_resident(n, -1, q, sv, q, t, st, s);
+    const int kk = (int)std::min<int64_t>(kLanczosSteps, n);
+    double *qc = q, *qo = qp;
+    for (int j = 0; j < kk; ++j) {
+        if (A) k::amg_spmv(*A, t, aw, nullptr, s);
+        else a_mult(c, t, aw, nullptr, nullptr, nullptr, false, nullptr);
+        k::amgs_lz_dot_resident(n, j, sv, aw, a_scale, w, qc, f, st, s);
+        k::amgs_lz_update_resident(n, j, kk, qc, qo, w, f, st, s);
+        if (j + 1 == kk) break;
+        std::swap(qc, qo);
+        k::amgs_lz_scale_resident(n, j + 1, w, sv, qc, t, st, s);
+    }
+    lanczos_core::LzState h;
+    SPK_HIP(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+    SPK_HIP(hipStreamSynchronize(s));
+    if (reads) ++*reads;
+    c->check_device_error();
+    if (h.steps < 1 || h.steps > kk) fail(SPK_ERR_HIP, "amg: the resident Lanczos reports %d steps of %d", (int)h.steps, kk);
+    const std::vector<double> al(h.al, h.al + h.steps), be(h.be, h.be + h.steps);
+    if (tri) tri->al = al, tri->be = be;
     ritz_extremes(al, be, lmin, lmax);
 }
 
@@ -1180,6 +1245,10 @@ struct DevRoute {
     bool keep = false;        // reuse on: coarsen keeps A_l P_l and R_l A_l P_l for regalerkin
     int32_t *err = nullptr;   // regalerkin's error word
     double a_scale = 1.0;     // the refresh's (see lanczos)
+    mutable LzWork work;             // SPK_AMG_LANCZOS_RESIDENT: the vectors and the state block of every level's Lanczos
+    mutable int32_t readbacks = 0;   // device -> host reads of the Ritz estimates (spk_amg_info.ritz_readbacks)
+    // the route's part of the info, behind build_levels / refresh_levels
+    void ritz_info(spk_amg_info &info) const { info.lanczos = o.lanczos, info.ritz_readbacks = readbacks; }
     const CsrDev &A(int l) const { return l == 0 ? A0 : d.lv[(size_t)l].A; }
     const double *dinv(int l) const { return l == 0 ? dinv0 : d.lv[(size_t)l].dinv.p; }
     int32_t rows(int l) const { return A(l).nrows; }
@@ -1219,9 +1288,13 @@ struct DevRoute {
     {
         if (ritz_on_host(l)) {
             const HostCsr H = dev_csr_download(A(l), true, s);
+            ++readbacks;
             return lanczos(H, diag_inv(H), lmin, lmax, a_scale);
         }
-        dev_lanczos(c, l ? &A(l) : nullptr, rows(l), l ? rows(l) : c->ld, dinv(l), lmin, lmax, a_scale);
+        const CsrDev *M = l ? &A(l) : nullptr;
+        const int64_t nv = l ? rows(l) : c->ld;
+        if (o.lanczos == SPK_AMG_LANCZOS_RESIDENT) dev_lanczos_resident(c, work, M, rows(l), nv, dinv(l), lmin, lmax, a_scale, &readbacks);
+        else dev_lanczos(c, M, rows(l), nv, dinv(l), lmin, lmax, a_scale, &readbacks);
     }
     void set_interval(int l, double lo, double hi) { smoother_coeffs(d.lv[(size_t)l], o, lo, hi); }
     void coarsen(int l, int bs, std::vector<int32_t> agg, int32_t na, double omega, int nsmooths)
@@ -1376,8 +1449,9 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
         d->reuse->sum.alloc(8);
         d->reuse->dinv_sum = dev_abs_sum(c, dinv0.p, c->n_local, d->reuse->sum);
     }
-    DevRoute r{c, *d, o, A0, dinv0.p, c->stream, d->reuse != nullptr, nullptr};
+    DevRoute r{c, *d, o, A0, dinv0.p, c->stream, d->reuse != nullptr, nullptr, 1.0, {}, 0};
     build_levels(r, bs, o, SPK_AMG_SETUP_DEVICE, t0, d->info);
+    r.ritz_info(d->info);
     alloc_cycle_vectors(*d, c->ld);
     amg_plan_cycle(*d, o);
     if (d->reuse) keep_pattern(c, *d);
@@ -1394,7 +1468,8 @@ bool amg_can_refresh(spk_ctx *c)
     bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
                 a.smoother == b.smoother && a.threshold == b.threshold && a.smooth_its == b.smooth_its &&
                 a.block_size == b.block_size && a.richardson_scale == b.richardson_scale && a.setup == b.setup &&
-                a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides && a.galerkin == b.galerkin;
+                a.coarsening == b.coarsening && a.transfer == b.transfer && a.sides == b.sides && a.galerkin == b.galerkin &&
+                a.lanczos == b.lanczos;
     // (cycle, tail, tail_rows and op steer the application, not the hierarchy: not compared)
     for (int i = 0; i < 4; ++i) same = same && a.esteig[i] == b.esteig[i];
     for (int i = 0; i < 3; ++i) same = same && a.grid[i] == b.grid[i];
@@ -1450,8 +1525,9 @@ void amg_refresh_ctx(spk_ctx *c)
         }
         k::extract_diag_inv(c->Ad, ru.dinv0.p, s);
         const double a_scale = binade_scale(ru.dinv_sum, dev_abs_sum(c, ru.dinv0.p, ru.n, ru.sum));
-        DevRoute r{c, d, ru.o, ru.use_sorted ? ru.sorted : c->Ad, ru.dinv0.p, s, true, ru.flag.p + 1, a_scale};
+        DevRoute r{c, d, ru.o, ru.use_sorted ? ru.sorted : c->Ad, ru.dinv0.p, s, true, ru.flag.p + 1, a_scale, {}, 0};
         refresh_levels(r, ru.o, t0, d.info);
+        r.ritz_info(d.info);
         SPK_HIP(hipDeviceSynchronize());
     }
     amg_plan_cycle(d, ru.o);   // the coefficients are new, and the device route's coarse inverse lies elsewhere
@@ -1558,6 +1634,35 @@ void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha,
     c->check_device_error();
 }
 
+// the test hook of the set-up's Lanczos: either route on one level of the device-built hierarchy as it stands (level 0:
+// the context's layout and the D^-1 of its CSR copy, as at the build; no binade scale)
+void amg_debug_lanczos(spk_ctx *c, int l, int resident, int32_t *steps, double *al, double *be)
+{
+    if (c->amg_h) fail(SPK_ERR_STATE, "amg: Lanczos hook: the hierarchy was built on the host -- pass -spk_gamg_setup device");
+    AmgDev &d = *c->amg_d;
+    if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: Lanczos hook: level %d has no Ritz estimate (levels: %d)", l, (int)d.lv.size());
+    if (resident != 0 && resident != 1) fail(SPK_ERR_ARG, "amg: Lanczos hook: resident is 0 or 1");
+    c->ensure_scratch();
+    AmgLevelDev &D = d.lv[(size_t)l];
+    DevBuf<double> dinv0;
+    if (l == 0) {
+        dinv0.alloc((size_t)c->n_local, 8);
+        k::extract_diag_inv(c->Ad, dinv0.p, c->stream);
+    }
+    const CsrDev *M = l ? &D.A : nullptr;
+    const int32_t n = l ? D.A.nrows : c->n_local;
+    const int64_t nv = l ? n : c->ld;
+    const double *dinv = l ? D.dinv.p : dinv0.p;
+    double lmin = 0.0, lmax = 0.0;
+    LzTri tri;
+    LzWork work;
+    if (resident) dev_lanczos_resident(c, work, M, n, nv, dinv, &lmin, &lmax, 1.0, nullptr, &tri);
+    else dev_lanczos(c, M, n, nv, dinv, &lmin, &lmax, 1.0, nullptr, &tri);
+    *steps = (int32_t)tri.al.size();
+    std::copy(tri.al.begin(), tri.al.end(), al);
+    std::copy(tri.be.begin(), tri.be.end(), be);
+}
+
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
 // (n_local % 2: never false here -- the 2x2 blocked copy the row types are built over exists only for an even n_local;
 // the condition states what amg_cheb_dict2 needs rather than guarding a case that occurs)
@@ -1661,6 +1766,7 @@ void spk_default_amg_opts(spk_amg_opts *o)
     o->esteig[3] = 1.1;
     o->richardson_scale = 1.0;
     o->setup = SPK_AMG_SETUP_HOST;
+    o->lanczos = SPK_AMG_LANCZOS_STEPWISE;
 }
 
 #define SPK_HOST_TRY try {

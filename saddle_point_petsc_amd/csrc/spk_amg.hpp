@@ -43,7 +43,8 @@ struct AmgHier {
 };
 
 // throws spk::Error
-void amg_check_opts(const spk_amg_opts &o);
+// host_builder: spk_amg_build_host's check -- it takes a set-up route and a Lanczos route it does not read
+void amg_check_opts(const spk_amg_opts &o, bool host_builder = false);
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o);
 // new values (in the order of the arrays amg_build was given) on the kept aggregates, prolongators and patterns: every
 // A_l, D_l^-1, interval and the coarse inverse again.  A throw leaves h empty.

@@ -419,6 +419,15 @@ int spk_debug_amg_operator(spk_ctx *c, int level, int which, int stencil, double
     SPK_CATCH(c)
 }
 
+int spk_debug_amg_lanczos(spk_ctx *c, int level, int resident, int32_t *steps, double *al, double *be)
+{
+    SPK_TRY(c)
+    if (!steps || !al || !be) spk::fail(SPK_ERR_ARG, "debug_amg_lanczos: null pointer");
+    need_amg(c);
+    spk::amg_debug_lanczos(c, level, resident, steps, al, be);
+    SPK_CATCH(c)
+}
+
 int spk_pc_set_amg_reuse(spk_ctx *c, int reuse)
 {
     SPK_TRY(c)

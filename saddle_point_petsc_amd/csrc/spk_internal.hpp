@@ -30,6 +30,7 @@
 
 #include "spk_host.hpp"
 #include "spk_amg.hpp"
+#include "spk_lanczos_core.hpp"
 
 namespace spk {
 
@@ -918,6 +919,17 @@ void amgs_abs_sum(int64_t n, const double *x, const Finish &f, hipStream_t s);  
 void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, double *q, double *t, hipStream_t s);
 void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double ascale, double *w, const double *q, const Finish &f, hipStream_t s);
 void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s);
+// the same four passes under SPK_AMG_LANCZOS_RESIDENT: the scalars come from and go to the state block st on the device
+// (spk_lanczos_core.hpp; f.out is not written), and a pass behind the stop returns at its entry.  scale: jb < 0 divides by
+// st->nq, else by st->be[jb];  dot of step j: st->al[j];  update of step j of kk: reads al[j], be[j], keeps the break rule
+void amgs_lz_init_resident(int64_t n, const double *dinv, double dscale, double *sv, double *q, const Finish &f,
+                           lanczos_core::LzState *st, hipStream_t s);
+void amgs_lz_scale_resident(int64_t n, int jb, const double *w, const double *sv, double *q, double *t, const lanczos_core::LzState *st,
+                            hipStream_t s);
+void amgs_lz_dot_resident(int64_t n, int j, const double *sv, const double *aw, double ascale, double *w, const double *q,
+                          const Finish &f, lanczos_core::LzState *st, hipStream_t s);
+void amgs_lz_update_resident(int64_t n, int j, int kk, const double *q, const double *qp, double *w, const Finish &f,
+                             lanczos_core::LzState *st, hipStream_t s);
 }  // namespace k
 
 // the device copy of the hierarchy (spk_amg.cpp): level 0 keeps the context's A layout and diag(A)^-1
@@ -1132,6 +1144,7 @@ void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
 void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out);
 void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
                         const double *b, double *out);
+void amg_debug_lanczos(spk_ctx *c, int l, int resident, int32_t *steps, double *al, double *be);
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last = nullptr);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

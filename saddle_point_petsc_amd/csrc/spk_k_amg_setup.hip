@@ -402,7 +402,8 @@ __global__ __launch_bounds__(kThreads) void amgs_symmetrise_numeric_kernel(const
 // reduced in a fixed order by the sentinel finish (spk_device.hpp)
 // ---------------------------------------------------------------------------
 namespace {
-__device__ __forceinline__ void lz_finish(double acc, double *red, double *partials, double *out, FinErr fe)
+// true in thread 0 of the reducing workgroup, with the sum in red[0]
+__device__ __forceinline__ bool lz_reduce(double acc, double *red, double *partials, FinErr fe)
 {
     const double s = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -413,9 +414,62 @@ __device__ __forceinline__ void lz_finish(double acc, double *red, double *parti
         for (int j = 0; j < kVWaves; ++j) t += red[j];
         publish(partials + (size_t)blockIdx.x * kPartialLd, t);
     }
-    if (!arrive_last(gridDim.x)) return;
+    if (!arrive_last(gridDim.x)) return false;
     final_reduce(partials, gridDim.x, kPartialLd, 1, red, fe);
-    if (threadIdx.x == 0) out[0] = red[0];
+    return threadIdx.x == 0;
+}
+__device__ __forceinline__ void lz_finish(double acc, double *red, double *partials, double *out, FinErr fe)
+{
+    if (lz_reduce(acc, red, partials, fe)) out[0] = red[0];
+}
+
+// The element passes of the four Lanczos kernels, each written once: the stepwise kernels take their scalars as
+// arguments, the resident ones (SPK_AMG_LANCZOS_RESIDENT) load them from the state block, and both run these bodies --
+// device code contracts a * b + c, so an expression written twice could round differently in its two copies.
+__device__ __forceinline__ double lz_init_pass(int64_t n, const double *__restrict__ dinv, double dscale, double *__restrict__ sv,
+                                               double *__restrict__ q)
+{
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        sv[i] = sqrt(fabs(dinv[i] * dscale));
+        uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
+        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+        const double x = 0.5 + (double)(h & 0xffffu) / 65536.0;
+        q[i] = x;
+        acc += x * x;
+    }
+    return acc;
+}
+__device__ __forceinline__ void lz_scale_pass(int64_t n, double nb, const double *w, const double *__restrict__ sv, double *q,
+                                              double *__restrict__ t)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = w[i] / nb;
+        q[i] = x;
+        t[i] = sv[i] * x;
+    }
+}
+__device__ __forceinline__ double lz_dot_pass(int64_t n, const double *__restrict__ sv, const double *__restrict__ aw, double ascale,
+                                              double *__restrict__ w, const double *__restrict__ q)
+{
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = sv[i] * (aw[i] * ascale);
+        w[i] = x;
+        acc += x * q[i];
+    }
+    return acc;
+}
+__device__ __forceinline__ double lz_update_pass(int64_t n, double a, double be, const double *__restrict__ q,
+                                                 const double *__restrict__ qp, double *__restrict__ w)
+{
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
+        const double x = w[i] - (a * q[i] + be * qp[i]);
+        w[i] = x;
+        acc += x * x;
+    }
+    return acc;
 }
 }  // namespace
 
@@ -435,26 +489,13 @@ __global__ __launch_bounds__(kVT) void amgs_lz_init_kernel(int64_t n, const doub
                                                            double *out, FinErr fe)
 {
     __shared__ double red[kVT];
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        sv[i] = sqrt(fabs(dinv[i] * dscale));
-        uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
-        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-        const double x = 0.5 + (double)(h & 0xffffu) / 65536.0;
-        q[i] = x;
-        acc += x * x;
-    }
-    lz_finish(acc, red, partials, out, fe);
+    lz_finish(lz_init_pass(n, dinv, dscale, sv, q), red, partials, out, fe);
 }
 // q = w / nb, t = sv q   (w may be q)
 __global__ __launch_bounds__(kVT) void amgs_lz_scale_kernel(int64_t n, double nb, const double *w, const double *__restrict__ sv,
                                                             double *q, double *__restrict__ t)
 {
-    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        const double x = w[i] / nb;
-        q[i] = x;
-        t[i] = sv[i] * x;
-    }
+    lz_scale_pass(n, nb, w, sv, q, t);
 }
 // w = sv (aw ascale) (ascale: a power of two, 1 on a build: the product with it is exact), out[0] = w.q
 __global__ __launch_bounds__(kVT) void amgs_lz_dot_kernel(int64_t n, const double *__restrict__ sv, const double *__restrict__ aw,
@@ -462,13 +503,7 @@ __global__ __launch_bounds__(kVT) void amgs_lz_dot_kernel(int64_t n, const doubl
                                                           double *out, FinErr fe)
 {
     __shared__ double red[kVT];
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        const double x = sv[i] * (aw[i] * ascale);
-        w[i] = x;
-        acc += x * q[i];
-    }
-    lz_finish(acc, red, partials, out, fe);
+    lz_finish(lz_dot_pass(n, sv, aw, ascale, w, q), red, partials, out, fe);
 }
 // w -= a q + be qp, out[0] = w.w
 __global__ __launch_bounds__(kVT) void amgs_lz_update_kernel(int64_t n, double a, double be, const double *__restrict__ q,
@@ -476,13 +511,48 @@ __global__ __launch_bounds__(kVT) void amgs_lz_update_kernel(int64_t n, double a
                                                              double *out, FinErr fe)
 {
     __shared__ double red[kVT];
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVT) {
-        const double x = w[i] - (a * q[i] + be * qp[i]);
-        w[i] = x;
-        acc += x * x;
-    }
-    lz_finish(acc, red, partials, out, fe);
+    lz_finish(lz_update_pass(n, a, be, q, qp, w), red, partials, out, fe);
+}
+
+// The resident variants (SPK_AMG_LANCZOS_RESIDENT): the same passes and the same finish in the same launch geometry, so
+// every sum is the stepwise route's to the bit; the scalars are plain loads from the state block at entry (the kernel
+// boundary on the one stream has made the previous finisher's stores visible), and thread 0 of the reducing workgroup
+// applies the host loop's rule to the sum (spk_lanczos_core.hpp) with ordinary stores.  `stopped` is the same in every
+// workgroup of a launch -- only an earlier launch's finisher writes it -- so behind the break a whole launch returns
+// before it touches a vector or the partials, and the sentinels stay armed.
+__global__ __launch_bounds__(kVT) void amgs_lz_init_resident_kernel(int64_t n, const double *__restrict__ dinv, double dscale,
+                                                                    double *__restrict__ sv, double *__restrict__ q, double *partials,
+                                                                    lanczos_core::LzState *st, FinErr fe)
+{
+    __shared__ double red[kVT];
+    if (st->stopped) return;   // (never set here: the block is zeroed in front of this launch)
+    if (lz_reduce(lz_init_pass(n, dinv, dscale, sv, q), red, partials, fe)) lanczos_core::lz_after_init(st, red[0]);
+}
+// jb < 0: the start vector's norm, else be[jb]
+__global__ __launch_bounds__(kVT) void amgs_lz_scale_resident_kernel(int64_t n, int jb, const double *w, const double *__restrict__ sv,
+                                                                     double *q, double *__restrict__ t, const lanczos_core::LzState *st)
+{
+    if (st->stopped) return;
+    const double nb = jb < 0 ? st->nq : st->be[jb];
+    lz_scale_pass(n, nb, w, sv, q, t);
+}
+__global__ __launch_bounds__(kVT) void amgs_lz_dot_resident_kernel(int64_t n, int j, const double *__restrict__ sv,
+                                                                   const double *__restrict__ aw, double ascale, double *__restrict__ w,
+                                                                   const double *__restrict__ q, double *partials,
+                                                                   lanczos_core::LzState *st, FinErr fe)
+{
+    __shared__ double red[kVT];
+    if (st->stopped) return;
+    if (lz_reduce(lz_dot_pass(n, sv, aw, ascale, w, q), red, partials, fe)) lanczos_core::lz_after_dot(st, j, red[0]);
+}
+__global__ __launch_bounds__(kVT) void amgs_lz_update_resident_kernel(int64_t n, int j, int kk, const double *__restrict__ q,
+                                                                      const double *__restrict__ qp, double *__restrict__ w,
+                                                                      double *partials, lanczos_core::LzState *st, FinErr fe)
+{
+    __shared__ double red[kVT];
+    if (st->stopped) return;
+    const double a = st->al[j], be = st->be[j];
+    if (lz_reduce(lz_update_pass(n, a, be, q, qp, w), red, partials, fe)) lanczos_core::lz_after_update(st, j, kk, red[0]);
 }
 
 // ---------------------------------------------------------------------------
@@ -662,6 +732,29 @@ void amgs_lz_scale(int64_t n, double nb, const double *w, const double *sv, doub
 void amgs_lz_dot(int64_t n, const double *sv, const double *aw, double ascale, double *w, const double *q, const Finish &f, hipStream_t s)
 {
     hipLaunchKernelGGL(amgs_lz_dot_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, sv, aw, ascale, w, q, f.partials, f.out,
+                       FinErr{f.err, f.fin_ticks});
+}
+void amgs_lz_init_resident(int64_t n, const double *dinv, double dscale, double *sv, double *q, const Finish &f,
+                           lanczos_core::LzState *st, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_init_resident_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, dinv, dscale, sv, q, f.partials, st,
+                       FinErr{f.err, f.fin_ticks});
+}
+void amgs_lz_scale_resident(int64_t n, int jb, const double *w, const double *sv, double *q, double *t, const lanczos_core::LzState *st,
+                            hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_scale_resident_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, jb, w, sv, q, t, st);
+}
+void amgs_lz_dot_resident(int64_t n, int j, const double *sv, const double *aw, double ascale, double *w, const double *q,
+                          const Finish &f, lanczos_core::LzState *st, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_dot_resident_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, j, sv, aw, ascale, w, q, f.partials, st,
+                       FinErr{f.err, f.fin_ticks});
+}
+void amgs_lz_update_resident(int64_t n, int j, int kk, const double *q, const double *qp, double *w, const Finish &f,
+                             lanczos_core::LzState *st, hipStream_t s)
+{
+    hipLaunchKernelGGL(amgs_lz_update_resident_kernel, dim3(lz_grid(n)), dim3(kVT), 0, s, n, j, kk, q, qp, w, f.partials, st,
                        FinErr{f.err, f.fin_ticks});
 }
 void amgs_lz_update(int64_t n, double a, double be, const double *q, const double *qp, double *w, const Finish &f, hipStream_t s)

@@ -162,6 +162,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "csr") o.op = SPK_AMG_OPERATOR_CSR;
         else if (v == "stencil") o.op = SPK_AMG_OPERATOR_STENCIL;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (csr | stencil)");
+    } else if (key == "-spk_amg_lanczos") {
+        if (!val) return need("stepwise or resident");
+        const std::string v(val);
+        if (v == "stepwise") o.lanczos = SPK_AMG_LANCZOS_STEPWISE;
+        else if (v == "resident") o.lanczos = SPK_AMG_LANCZOS_RESIDENT;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (stepwise | resident)");
     } else if (key == "-spk_mg_cycle") {
         if (!val) return need("v or w");
         const std::string v(val);
@@ -696,6 +702,12 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                 std::printf("    level operators: stencil (-spk_mg_operator stencil): no level between level 0 and the coarsest\n");
             else if (grid)
                 std::printf("    level operators: csr (-spk_mg_operator csr): levels >= 1 as sparse matrices\n");
+            if (ai.setup == SPK_AMG_SETUP_DEVICE)
+                std::printf("    set-up Lanczos: %s (-spk_amg_lanczos %s): %s, %d read-backs in the last set-up\n",
+                            ai.lanczos == SPK_AMG_LANCZOS_RESIDENT ? "resident" : "stepwise",
+                            ai.lanczos == SPK_AMG_LANCZOS_RESIDENT ? "resident" : "stepwise",
+                            ai.lanczos == SPK_AMG_LANCZOS_RESIDENT ? "the scalars stay on the device, one read per level"
+                                                                   : "the host reads two sums per step", (int)ai.ritz_readbacks);
             const int tail = ai.tail_first >= 0 ? SPK_AMG_TAIL_FUSED : SPK_AMG_TAIL_LAUNCHES;   // as it resolved on these levels
             std::printf("    cycle %s (-spk_mg_cycle), tail %s (-spk_mg_tail %s), tail_first %d, tail_rows %d%s, tail launches per application %d\n",
                         ai.cycle == SPK_AMG_CYCLE_W ? "w" : "v", tail == SPK_AMG_TAIL_FUSED ? "fused" : "launches",

@@ -50,6 +50,7 @@ AMG_SIDES_ODD, AMG_SIDES_ANY = 0, 1
 AMG_CYCLE_V, AMG_CYCLE_W = 0, 1
 AMG_GALERKIN_PRODUCTS, AMG_GALERKIN_STENCIL = 0, 1
 AMG_OPERATOR_CSR, AMG_OPERATOR_STENCIL = 0, 1
+AMG_LANCZOS_STEPWISE, AMG_LANCZOS_RESIDENT = 0, 1
 AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED = 0, 1, 2
 AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST = range(6)
 SPK_ERR_ARG = -1   # include/spk.h
@@ -61,6 +62,7 @@ _SIDES = {"odd": AMG_SIDES_ODD, "any": AMG_SIDES_ANY}
 _CYCLES = {"v": AMG_CYCLE_V, "w": AMG_CYCLE_W}
 _GALERKINS = {"products": AMG_GALERKIN_PRODUCTS, "stencil": AMG_GALERKIN_STENCIL}
 _OPERATORS = {"csr": AMG_OPERATOR_CSR, "stencil": AMG_OPERATOR_STENCIL}
+_LANCZOS = {"stepwise": AMG_LANCZOS_STEPWISE, "resident": AMG_LANCZOS_RESIDENT}
 _TAILS = {"auto": AMG_TAIL_AUTO, "launches": AMG_TAIL_LAUNCHES, "fused": AMG_TAIL_FUSED}
 
 
@@ -70,7 +72,9 @@ def amg_opts(**kw):
     'v' / 'w', tail 'auto' / 'launches' / 'fused', galerkin 'products' / 'stencil' (what forms the coarse operators of a
     grid-coarsened hierarchy: the generic sparse products, or the gather on the node grid), operator 'csr' / 'stencil'
     (how the cycle applies the levels between level 0 and the coarsest: as sparse matrices, or from their value arrays
-    alone -- the struct's field is `op`; 'stencil' needs coarsening='grid' and galerkin='stencil');
+    alone -- the struct's field is `op`; 'stencil' needs coarsening='grid' and galerkin='stencil'), lanczos 'stepwise' /
+    'resident' (who holds the scalars of the device set-up's Lanczos: the host, reading two sums back per step, or a block
+    on the device read once per level -- the same hierarchy to the bit; 'resident' needs setup='device');
     grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
     ones too)."""
     o = AmgOpts()
@@ -98,6 +102,8 @@ def amg_opts(**kw):
             v = _TAILS[v]
         if k == "galerkin" and isinstance(v, str):
             v = _GALERKINS[v]
+        if k == "lanczos" and isinstance(v, str):
+            v = _LANCZOS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         if k == "grid":
@@ -123,7 +129,8 @@ def _amg_info(ai):
                 lambda_max=list(ai.lambda_max[:L]), operator_complexity=ai.operator_complexity,
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
                 dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides, cycle=ai.cycle, tail_first=ai.tail_first,
-                tail_launches=ai.tail_launches, galerkin=ai.galerkin, operator=ai.op)
+                tail_launches=ai.tail_launches, galerkin=ai.galerkin, operator=ai.op, lanczos=ai.lanczos,
+                ritz_readbacks=ai.ritz_readbacks)
 
 
 def amg_stencil_children(fine, coarse, node):
@@ -672,6 +679,15 @@ class Context:
         self._chk(lib.spk_debug_amg_operator(self.h, level, (1 if step else 0) + (2 if done else 0), 1 if stencil else 0,
                                              float(alpha), float(beta), x, ptr(xo), ptr(b), out))
         return out
+
+    def debug_amg_lanczos(self, level, resident=False):
+        """Test hook (spk_debug_amg_lanczos): the device set-up's Lanczos alone on a level below the coarsest of the
+        device-built hierarchy, by the stepwise or the resident route.  Returns (steps, al[:steps], be[:steps]): the
+        tridiagonal whose extreme eigenvalues are the level's Ritz values (be[0] = 0)."""
+        steps = C.c_int32()
+        al, be = np.zeros(30), np.zeros(31)
+        self._chk(lib.spk_debug_amg_lanczos(self.h, int(level), 1 if resident else 0, C.byref(steps), al, be))
+        return steps.value, al[:steps.value].copy(), be[:steps.value].copy()
 
     def amg_aggregates(self, level):
         """The aggregate of every node of a level of the context's hierarchy (-1: isolated)."""

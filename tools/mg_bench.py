@@ -39,7 +39,15 @@ route's V-cycle median (exit status 1 when missed); the iterations of the two mu
 --operator-kernels launches the product and the smoothing step of levels 1 and 2 alone through the test hook, on both
 routes alternating (a warm-up round and --reps more), for a kernel trace; tools/rocpd_by_grid.py tells the levels apart by
 their launch grids.  The line it prints has the byte models: 8 B per stored entry (csr: 12 B and the row pointers) plus
-the vectors."""
+the vectors.
+    python tools/mg_bench.py --lanczos both --galerkin stencil [--grids 1025] [--sides odd|any] [--out profiles/FILE.jsonl]
+--lanczos stepwise|resident (-spk_amg_lanczos; default stepwise) selects who holds the scalars of the device set-up's
+Lanczos in the runs above; every emitted line records it.  --lanczos both compares the two: K = A, per grid two contexts in
+one process, reuse off so that every set-up is a build, after one warm-up round --reps alternating rounds of set-up -> solve
+-> V-cycle timing; then, per context, reuse-on refreshes on alternating values.  Per route: set-up and refresh as median
+(min..max) with the read-backs of the Ritz estimates, solve, iterations and V-cycle.  The bar, checked at 1025 and 1024
+nodes per side, for the build and for the refresh: the resident route's median plus its spread (max - min) at or below the
+stepwise route's median (exit status 1 when missed); iterations and lambda_max of the two must be equal."""
 import argparse
 import csv
 import glob
@@ -65,12 +73,14 @@ ap.add_argument("--galerkin", choices=["products", "stencil", "both"], default="
 ap.add_argument("--setup-only", choices=["products", "stencil"], help="only launch device builds of --grid (for a kernel trace)")
 ap.add_argument("--operator", choices=["csr", "stencil", "both"], default="csr", help="how mg's cycle applies the levels >= 1 (-spk_mg_operator)")
 ap.add_argument("--operator-kernels", action="store_true", help="only launch the level operators of levels 1 and 2 of --grid (for a kernel trace)")
+ap.add_argument("--lanczos", choices=["stepwise", "resident", "both"], default="stepwise",
+                help="who holds the scalars of the device set-up's Lanczos (-spk_amg_lanczos)")
 ap.add_argument("--out", help="append the JSON lines to this file too")
 a = ap.parse_args()
 
 
 def emit(row):
-    line = json.dumps(dict(dict(galerkin=a.galerkin, operator=a.operator), **dict(row, sides=a.sides)))
+    line = json.dumps(dict(dict(galerkin=a.galerkin, operator=a.operator, lanczos=a.lanczos), **dict(row, sides=a.sides)))
     print(line, flush=True)
     if a.out:
         with open(a.out, "a") as fh:
@@ -154,9 +164,10 @@ if a.setup_only:
     sys.exit(0)
 
 
-def mg_opts(g, galerkin, operator=None):
+def mg_opts(g, galerkin, operator=None, lanczos=None):
     return dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=galerkin,
-                operator=operator or (a.operator if a.operator != "both" else "csr"))
+                operator=operator or (a.operator if a.operator != "both" else "csr"),
+                lanczos=lanczos or (a.lanczos if a.lanczos != "both" else "stepwise"))
 
 
 if a.operator_kernels:
@@ -262,6 +273,77 @@ def compare_operator(g):
         c.close()
     return {route: (t[route]["vcycle"], t[route]["its"]) for route in routes}
 
+
+def compare_lanczos(g):
+    """the two routes of the set-up's Lanczos on K = A: the same hierarchy; returns {route: (set-up seconds, refresh seconds, its)}"""
+    A, f = S.AssembleOperator_Laplace(g, g)
+    A1, _ = S.AssembleOperator_Laplace(g, g, kappa=1.0 + np.random.default_rng(g).random((g - 1) * (g - 1)))
+    routes = ("stepwise", "resident")
+    galerkin = a.galerkin if a.galerkin != "both" else "stencil"
+    ctxs, t = {}, {}
+    for route in routes:
+        c = S.Context(0)
+        c.set_block(S.BLOCK_A00, A)
+        ctxs[route] = c
+        t[route] = dict(setup=[], solve=[], vcycle=[], its=[], res=[], refresh=[])
+    for rep in range(-1, a.reps):   # -1: the warm-up round, not counted; reuse off: every set-up builds
+        for route, c in ctxs.items():
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, galerkin, lanczos=route))
+            x, info = c.fgmres(f, rtol=a.rtol, max_it=500, restart=30)
+            assert info["reason"] == 2, (route, info["reason"])
+            vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            r = t[route]
+            r["setup"].append(c.amg_info()["setup_seconds"])
+            r["solve"].append(info["solve_seconds"])
+            r["vcycle"].append(vc_ms * 1e-3)
+            r["its"].append(info["its"])
+            r["res"].append(float(np.linalg.norm(f - c.mult(x)) / np.linalg.norm(f)))
+    infos = {route: c.amg_info() for route, c in ctxs.items()}
+    assert infos["stepwise"]["lambda_max"] == infos["resident"]["lambda_max"], "the two routes estimate different Ritz values"
+    refresh_reads = {}
+    for route, c in ctxs.items():   # reuse on: one build, then refreshes on alternating values of the same pattern
+        c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, galerkin, lanczos=route), amg_reuse=True)
+        for rep in range(-1, a.reps):
+            c.set_block(S.BLOCK_A00, A1 if rep % 2 else A)
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, galerkin, lanczos=route), amg_reuse=True)
+            ri = c.amg_reuse_info()
+            assert ri["refreshed"], route
+            if rep >= 0:
+                t[route]["refresh"].append(ri["seconds"])
+        refresh_reads[route] = c.amg_info()["ritz_readbacks"]
+    for route, c in ctxs.items():
+        info, r = infos[route], t[route]
+        assert info["lanczos"] == (route == "resident")
+        emit(dict(mode="lanczos", system="A", grid=g, pc="mg", route=route, galerkin=galerkin, solver="fgmres(30)", rtol=a.rtol,
+                  reps=a.reps, levels=info["levels"], rows=info["rows"], ritz_readbacks=info["ritz_readbacks"],
+                  refresh_ritz_readbacks=refresh_reads[route], its=sorted(set(r["its"])), true_rel_res=max(r["res"]),
+                  pc_apply_us=mmm(r["vcycle"], 1e6, 1), solve_ms=mmm(r["solve"], 1e3, 3), setup_ms=mmm(r["setup"], 1e3, 3),
+                  refresh_ms=mmm(r["refresh"], 1e3, 3)))
+        c.close()
+    return {route: (t[route]["setup"], t[route]["refresh"], t[route]["its"]) for route in routes}
+
+
+if a.lanczos == "both":
+    met = True
+    for g in a.grids:
+        s = compare_lanczos(g)
+        (ss, sr, si), (rs, rr, ri) = s["stepwise"], s["resident"]
+        same_its = set(si) == set(ri)
+        row = dict(mode="bar", system="A", grid=g, iterations_equal=bool(same_its), stepwise_setup_ms=mmm(ss, 1e3, 3),
+                   resident_setup_ms=mmm(rs, 1e3, 3), stepwise_refresh_ms=mmm(sr, 1e3, 3), resident_refresh_ms=mmm(rr, 1e3, 3),
+                   setup_stepwise_over_resident=round(float(np.median(ss) / np.median(rs)), 3),
+                   refresh_stepwise_over_resident=round(float(np.median(sr) / np.median(rr)), 3))
+        met = met and same_its
+        if g in (1024, 1025):
+            ok_b = float(np.median(rs)) + (max(rs) - min(rs)) <= float(np.median(ss))
+            ok_r = float(np.median(rr)) + (max(rr) - min(rr)) <= float(np.median(sr))
+            met = met and ok_b and ok_r
+            row.update(bar="resident median + spread <= stepwise median, build and refresh", bar_met_build=bool(ok_b),
+                       bar_met_refresh=bool(ok_r))
+        emit(row)
+    sys.exit(0 if met else 1)
 
 if a.operator == "both":
     if a.galerkin != "stencil":
