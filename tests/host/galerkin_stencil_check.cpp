@@ -1,7 +1,7 @@
 // galerkin_stencil_check.cpp -- the grid-stencil Galerkin product on the host (csrc/spk_galerkin_core.hpp through
 // csrc/spk_galerkin_host.cpp: galerkin_stencil_host, galerkin_stencil_check_host, galerkin_stencil_children) without a GPU: the
-// closed-form pattern, bitwise symmetry, the values against a dense P^T A P, the buffers' exact sizes (the sanitizers watch
-// every index) and the level-0 refusal.  Compiled with g++ and the sanitizers by tests/test_mg_galerkin_cpu.py.
+// closed-form pattern, bitwise symmetry, the values against a dense P^T A P under a symmetric and a non-symmetric value rule,
+// the buffers' exact sizes (the sanitizers watch every index) and the level-0 refusal.  Compiled with g++ and the sanitizers by tests/test_mg_galerkin_cpu.py.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -27,12 +27,13 @@ struct Csr {
     std::vector<double> v;
 };
 
-// a symmetric operator with full bs x bs blocks on the 3^d stencil (corners = false: on the 2 d + 1 point stencil), values
-// from a fixed recurrence
-static Csr stencil_operator(const int32_t d[3], int bs, bool corners)
+// an operator with full bs x bs blocks on the 3^d stencil (corners = false: on the 2 d + 1 point stencil), values from a
+// fixed recurrence.  symmetric = false: val(r, c) != val(c, r), so that the symmetrisation averages two different numbers
+// and a gather that reads the transposed slot or the transposed block gives other values
+static Csr stencil_operator(const int32_t d[3], int bs, bool corners, bool symmetric = true)
 {
-    auto val = [](int64_t r, int64_t c) {
-        const int64_t lo = r < c ? r : c, hi = r < c ? c : r;
+    auto val = [symmetric](int64_t r, int64_t c) {
+        const int64_t lo = !symmetric || r < c ? r : c, hi = !symmetric || r < c ? c : r;
         const double x = (double)((lo * 7919 + hi * 104729) % 1009) / 1009.0;
         return r == c ? 30.0 + x : -(0.25 + x);
     };
@@ -58,9 +59,18 @@ static Csr stencil_operator(const int32_t d[3], int bs, bool corners)
     return A;
 }
 
-static void run(const int32_t fd[3], const int32_t cd[3], int bs, bool corners)
+static void run(const int32_t fd[3], const int32_t cd[3], int bs, bool corners, bool symmetric)
 {
-    const Csr A = stencil_operator(fd, bs, corners);
+    const Csr A = stencil_operator(fd, bs, corners, symmetric);
+    if (!symmetric) {   // the rule does what it is for: some pair of the first node's entries differs
+        bool differs = false;
+        for (int32_t q = A.rp[0]; q < A.rp[1]; ++q) {
+            const int32_t c = A.ci[(size_t)q];
+            for (int32_t t = A.rp[(size_t)c]; t < A.rp[(size_t)c + 1]; ++t)
+                if (A.ci[(size_t)t] == 0 && A.v[(size_t)t] != A.v[(size_t)q]) differs = true;
+        }
+        CHECK(differs);
+    }
     const int64_t nf = (int64_t)fd[0] * fd[1] * fd[2] * bs, nc = (int64_t)cd[0] * cd[1] * cd[2] * bs, nz = gs::gs_nnz(cd, bs);
     spk::galerkin_stencil_check_host(fd, bs, A.rp.data(), A.ci.data());
     std::vector<int32_t> rp((size_t)nc + 1, -1), ci((size_t)nz, -1);   // exactly as long as the closed form says
@@ -130,18 +140,20 @@ static void run(const int32_t fd[3], const int32_t cd[3], int bs, bool corners)
 
 int main()
 {
-    const int32_t a5[3] = {5, 5, 1}, a3[3] = {3, 3, 1};
-    run(a5, a3, 2, true);     // one interior coarse node
-    const int32_t b0[3] = {12, 10, 1}, b1[3] = {7, 6, 1}, b2[3] = {4, 4, 1}, b3[3] = {3, 3, 1};
-    run(b0, b1, 2, true);     // both sides even: the single-child last node
-    run(b1, b2, 2, true);     // odd x, even y
-    run(b2, b3, 1, false);    // 4 -> 3, a 5-point operator
-    const int32_t c0[3] = {12, 9, 1}, c1[3] = {12, 5, 1};
-    run(c0, c1, 1, false);    // x does not halve
-    const int32_t d0[3] = {6, 4, 3}, d1[3] = {4, 3, 3};
-    run(d0, d1, 3, true);     // 3-D, z does not halve
-    const int32_t e0[3] = {5, 5, 5}, e1[3] = {3, 3, 3};
-    run(e0, e1, 3, true);
+    for (const bool symmetric : {true, false}) {   // every grid under both value rules
+        const int32_t a5[3] = {5, 5, 1}, a3[3] = {3, 3, 1};
+        run(a5, a3, 2, true, symmetric);     // one interior coarse node
+        const int32_t b0[3] = {12, 10, 1}, b1[3] = {7, 6, 1}, b2[3] = {4, 4, 1}, b3[3] = {3, 3, 1};
+        run(b0, b1, 2, true, symmetric);     // both sides even: the single-child last node
+        run(b1, b2, 2, true, symmetric);     // odd x, even y
+        run(b2, b3, 1, false, symmetric);    // 4 -> 3, a 5-point operator
+        const int32_t c0[3] = {12, 9, 1}, c1[3] = {12, 5, 1};
+        run(c0, c1, 1, false, symmetric);    // x does not halve
+        const int32_t d0[3] = {6, 4, 3}, d1[3] = {4, 3, 3};
+        run(d0, d1, 3, true, symmetric);     // 3-D, z does not halve
+        const int32_t e0[3] = {5, 5, 5}, e1[3] = {3, 3, 3};
+        run(e0, e1, 3, true, symmetric);
+    }
     // the refusal: an entry two nodes away in x
     {
         const int32_t fd[3] = {6, 4, 1};
