@@ -1,4 +1,5 @@
-// spk_amg.hpp -- smoothed-aggregation multigrid: the host hierarchy (spk_amg.cpp) and its device copy.
+// spk_amg.hpp -- multigrid: the data of the host hierarchy and what spk_amg_host.cpp builds and refreshes it with.
+// Host-pure: the standard library and include/spk.h only (the device copy is AmgDev, spk_internal.hpp).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -45,6 +46,10 @@ struct AmgHier {
 // throws spk::Error
 // host_builder: spk_amg_build_host's check -- it takes a set-up route and a Lanczos route it does not read
 void amg_check_opts(const spk_amg_opts &o, bool host_builder = false);
+// every field that decides the hierarchy agrees (all but cycle, tail, tail_rows and op, which steer the application);
+// and those four taken from src
+bool amg_same_hierarchy_opts(const spk_amg_opts &a, const spk_amg_opts &b);
+void amg_take_application_opts(spk_amg_opts &dst, const spk_amg_opts &src);
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o);
 // new values (in the order of the arrays amg_build was given) on the kept aggregates, prolongators and patterns: every
 // A_l, D_l^-1, interval and the coarse inverse again.  A throw leaves h empty.

@@ -13,11 +13,6 @@ namespace spk {
 void rccl_unique_id(void *id128);
 }
 
-static thread_local std::string g_create_error;
-namespace spk {
-void set_create_error(const std::string &m) { g_create_error = m; }
-}
-
 #define SPK_TRY(ctx)                                                     \
     if (!(ctx)) return SPK_ERR_ARG;                                      \
     try {                                                                \
@@ -92,12 +87,12 @@ int spk_create(spk_ctx **out, int device)
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
-        g_create_error = std::string("spk_create: no HIP device available (") + hipGetErrorString(e) +
-                         "); libspk has no CPU fallback";
+        spk::set_create_error(std::string("spk_create: no HIP device available (") + hipGetErrorString(e) +
+                              "); libspk has no CPU fallback");
         return SPK_ERR_HIP;
     }
     if (device < 0 || device >= ndev) {
-        g_create_error = "spk_create: device index out of range";
+        spk::set_create_error("spk_create: device index out of range");
         return SPK_ERR_ARG;
     }
     spk_ctx *c = nullptr;
@@ -113,11 +108,11 @@ int spk_create(spk_ctx **out, int device)
         c->comm.reset(spk::make_self_comm());
         c->ensure_scratch();
     } catch (const spk::Error &er) {
-        g_create_error = er.msg;
+        spk::set_create_error(er.msg);
         delete c;
         return er.code;
     } catch (const std::exception &er) {
-        g_create_error = er.what();
+        spk::set_create_error(er.what());
         delete c;
         return SPK_ERR_NOMEM;
     }
@@ -146,7 +141,7 @@ int spk_destroy(spk_ctx *c)
     return SPK_OK;
 }
 
-const char *spk_last_error(const spk_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
+const char *spk_last_error(const spk_ctx *c) { return c ? c->err.c_str() : spk::create_error(); }
 
 int spk_comm_unique_id(void *id128)
 {
@@ -154,7 +149,7 @@ int spk_comm_unique_id(void *id128)
     try {
         spk::rccl_unique_id(id128);
     } catch (const spk::Error &e) {
-        g_create_error = e.msg;
+        spk::set_create_error(e.msg);
         return e.code;
     }
     return SPK_OK;

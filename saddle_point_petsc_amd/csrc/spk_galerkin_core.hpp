@@ -9,7 +9,7 @@
 //   coarse index c sits at fine index 2c (under e the last one, n - 1 = m / 2, at m - 1); its children are the fine
 //   indices 2c - 1 (weight 1/2), 2c (1), 2c + 1 (1/2), clipped to the line; under e fine m - 1 is the child of n - 1
 //   alone, with weight 1; a direction that does not halve is the identity.  A node's weight is the product over the
-//   directions.  This is grid_parents (spk_amg.cpp) read from the coarse side.
+//   directions.  This is grid_parents (spk_amg_host.cpp) read from the coarse side.
 //   S[C bs + a, C' bs + b] = sum over f in ch(C), ascending node index, over the stored entries of row f bs + a in
 //   ascending position whose column is f' bs + b with f' in ch(C'), of (w(f, C) w(f', C')) A_l[f bs + a, f' bs + b],
 //   added from +0.0.  Every product is exact (the weights are powers of two), so contraction cannot change a bit; it

@@ -1,5 +1,5 @@
 // spk_galerkin_host.cpp -- the grid-stencil Galerkin product (SPK_AMG_GALERKIN_STENCIL) in plain loops over the functions
-// of spk_galerkin_core.hpp: the host route's step (spk_amg.cpp: HostRoute::stencil) and the oracle of the kernels
+// of spk_galerkin_core.hpp: the host route's step (spk_amg_host.cpp: HostRoute::stencil) and the oracle of the kernels
 // (spk_k_amg_setup.hip: amgs_galerkin_stencil...).  Host-pure like spk_host.cpp, whose header declares these: the standard
 // library, include/spk.h and the core header only; exercised without a GPU by tests/host/galerkin_stencil_check.cpp.
 #include "spk_host.hpp"

@@ -24,6 +24,10 @@ void fail(int code, const char *fmt, ...)
     throw Error{code, std::string(buf)};
 }
 
+static thread_local std::string g_create_error;
+void set_create_error(const std::string &m) { g_create_error = m; }
+const char *create_error() { return g_create_error.c_str(); }
+
 void parallel_for(int64_t n, const std::function<void(int64_t, int64_t, int)> &fn, int max_threads)
 {
     int nt = max_threads > 0 ? max_threads : (int)std::thread::hardware_concurrency();
@@ -490,6 +494,27 @@ std::vector<std::pair<int64_t, int64_t>> amg_tail_runs(const std::vector<AmgStep
         s = e;
     }
     return runs;
+}
+
+AmgBuffers amg_cycle_buffers(const std::vector<AmgStep> &steps, const std::vector<std::pair<int64_t, int64_t>> &runs, int levels,
+                             int nu, int tail_first)
+{
+    AmgBuffers b;
+    b.sel.resize(steps.size());
+    b.sel_next.resize(steps.size());
+    b.run_sel.assign(runs.size(), 0);
+    int32_t sel[SPK_AMG_MAX_LEVELS] = {};
+    size_t run = 0;
+    for (size_t i = 0; i < steps.size(); ++i) {
+        const AmgStep st = steps[i];
+        b.sel[i] = sel[st.level];
+        b.sel_next[i] = st.level + 1 < levels ? sel[st.level + 1] : 0;
+        if (st.kind == SPK_AMG_STEP_PRE0) sel[st.level] = (nu & 1) ? 0 : 1;
+        else if (st.kind == SPK_AMG_STEP_PRE || st.kind == SPK_AMG_STEP_POST) sel[st.level] ^= nu & 1;
+        else if (st.kind == SPK_AMG_STEP_COARSE) sel[st.level] = 0;
+        if (run < runs.size() && (size_t)runs[run].second == i + 1) b.run_sel[run++] = sel[tail_first];   // (a run: tail_first >= 1)
+    }
+    return b;
 }
 
 // (G + G^T) / 2 into S, its Cholesky factor (lower, row-major, zeros above) into L.  A pivot at or below the rounding of

@@ -20,6 +20,10 @@ struct Error {
     std::string msg;
 };
 [[noreturn]] void fail(int code, const char *fmt, ...);
+// the words of a failure that has no context to keep them (spk_create, the host-only entry points), per thread: what
+// spk_last_error(NULL) returns
+void set_create_error(const std::string &m);
+const char *create_error();
 
 // uninitialised host array (std::vector would zero hundreds of MB on one thread first)
 template <class T>
@@ -124,6 +128,14 @@ int amg_resolve_tail(int cycle, int tail);
 int amg_tail_first(int levels, const int32_t *rows, int cycle, int tail, int tail_rows);
 // the tail runs of a step list: maximal stretches [begin, end) of consecutive steps on levels >= tail_first (none for -1)
 std::vector<std::pair<int64_t, int64_t>> amg_tail_runs(const std::vector<AmgStep> &steps, int tail_first);
+// Where the iterate lies: of a level's two buffers (0: ya, 1: yb), the one that holds its iterate when a step begins --
+// sel[i] for the level of step i, sel_next[i] for the level below it (0 on the coarsest) -- and run_sel[r], where tail run
+// r leaves the iterate of level tail_first.  The rule is that of the launches (smooth(), spk_amg_cycle.cpp): each of
+// the nu smoothing steps writes the buffer its input is not in, a fresh start (PRE0) writes ya first, the coarse solve
+// writes ya, DOWN and UP leave the iterate where it is.  The fused tail kernel reads this; the launches follow the rule.
+struct AmgBuffers { std::vector<int32_t> sel, sel_next, run_sel; };
+AmgBuffers amg_cycle_buffers(const std::vector<AmgStep> &steps, const std::vector<std::pair<int64_t, int64_t>> &runs, int levels,
+                             int nu, int tail_first);
 
 // ---- the grid-stencil Galerkin product (SPK_AMG_GALERKIN_STENCIL; spk_galerkin_host.cpp over spk_galerkin_core.hpp) ----
 // fd -> cd: the node grids of level l and l + 1 (grid_coarse_dims), bs the node size (1, 2 or 3).

@@ -932,7 +932,7 @@ void amgs_lz_update_resident(int64_t n, int j, int kk, const double *q, const do
                              lanczos_core::LzState *st, hipStream_t s);
 }  // namespace k
 
-// the device copy of the hierarchy (spk_amg.cpp): level 0 keeps the context's A layout and diag(A)^-1
+// the device copy of the hierarchy (spk_amg_setup.cpp): level 0 keeps the context's A layout and diag(A)^-1
 struct AmgLevelDev {
     int32_t n = 0;
     CsrDev A, P, R;                    // A: levels >= 1; P, R: all but the coarsest
@@ -1124,8 +1124,7 @@ void op_pc_apply(spk_ctx *c, const double *x, double *y, const int32_t *done);
 // out[r] = B_r . (x .* scale) over this rank's columns (scale == nullptr: B_r . x); no all-reduce
 void apply_B(spk_ctx *c, const double *x, const double *scale, double *out, const int32_t *done);
 void pc_setup(spk_ctx *c, int pc_type, int schur_fact);   // (spk_operator.cpp, like set_block below)
-// multigrid (spk_amg.cpp): the host hierarchy from the context's A00 (single rank) and its upload; one V-cycle,
-// mode 0: y = V x, mode 1: y -= V x; last != nullptr: y is not written, *last = the buffer of the hierarchy that holds V x
+// multigrid set-up (spk_amg_setup.cpp): the host hierarchy from the context's A00 (single rank) and its upload
 std::unique_ptr<spk_amg_hier> amg_build_ctx(spk_ctx *c);
 void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> h);
 // the same hierarchy built on the device from c->Ad (-spk_gamg_setup device); touches nothing of the context but its
@@ -1141,10 +1140,15 @@ void amg_drop_reuse(spk_ctx *c);
 // the test hooks on either route: the host hierarchy's copy, or a download from the device-built levels
 void amg_ctx_level(spk_ctx *c, int l, int which, const CsrOut &out);
 void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
+void amg_debug_lanczos(spk_ctx *c, int l, int resident, int32_t *steps, double *al, double *be);
+// the multigrid cycle (spk_amg_cycle.cpp).  What every set-up ends in: the cycle's vectors (ld: the context's padded
+// length) and the application's plan from the options and the levels as they are
+void alloc_cycle_vectors(AmgDev &d, int64_t ld);
+void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o);
 void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out);
 void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
                         const double *b, double *out);
-void amg_debug_lanczos(spk_ctx *c, int l, int resident, int32_t *steps, double *al, double *be);
+// one cycle, mode 0: y = V x, mode 1: y -= V x; last != nullptr: y is not written, *last = the buffer of the hierarchy that holds V x
 void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last = nullptr);
 void fgmres(spk_ctx *c, const double *b_dev, double *x_dev, const spk_opts &o, spk_result *res,
             double *history, int32_t history_cap);

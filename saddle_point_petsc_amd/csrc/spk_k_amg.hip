@@ -1,4 +1,4 @@
-// spk_k_amg.hip -- the V-cycle of the smoothed-aggregation multigrid (-pc_type gamg; host side in spk_amg.cpp).
+// spk_k_amg.hip -- the V-cycle of the smoothed-aggregation multigrid (-pc_type gamg; host side in spk_amg_cycle.cpp).
 // gfx950, wave64, FP64.  The levels >= 1 are CSR (sorted columns): eight lanes per row, each lane a fixed stride of
 // the row, the eight partial sums added in a fixed butterfly -- no atomics, the same bits on every run.  Every launch
 // takes the solver's `done` gate.  A level coarsened by the grid rule (-pc_type mg) applies P and R without reading

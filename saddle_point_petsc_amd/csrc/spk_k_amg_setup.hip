@@ -1,5 +1,5 @@
 // spk_k_amg_setup.hip -- the multigrid set-up on the device (-spk_gamg_setup device; host sequencing: amg_build_device
-// in spk_amg.cpp).  gfx950, wave64, FP64.  Node graph, tentative prolongator, Lanczos vector passes, CSR x CSR, union
+// in spk_amg_setup.cpp).  gfx950, wave64, FP64.  Node graph, tentative prolongator, Lanczos vector passes, CSR x CSR, union
 // add and transpose; for the refresh of a kept hierarchy (amg_refresh_ctx) the pattern comparison and the numeric
 // product and symmetrisation on known patterns; for grid coarsening the prolongator and the grid-stencil Galerkin product
 // (amgs_galerkin_stencil...) in closed form.  Set-up runs before any solve: no launch here takes the solver's `done` gate.

@@ -1,7 +1,7 @@
 // spk_lanczos_core.hpp -- the one source of the scalar rule of the device set-up's Lanczos under -spk_amg_lanczos resident
 // (SPK_AMG_LANCZOS_RESIDENT): the state block that stays on the device and the transitions its sums take.  The kernels
 // (spk_k_amg_setup.hip: thread 0 of the workgroup that finishes a sum) and the CPU run (tests/host/lanczos_core_check.cpp)
-// call the same functions, so the block holds what the host loop of dev_lanczos (spk_amg.cpp) would have kept because the
+// call the same functions, so the block holds what the host loop of dev_lanczos (spk_amg_setup.cpp) would have kept because the
 // same expressions ran on the same sums.  Standard library only; no ROCm.
 //
 // The host loop, for kk = min(kSteps, n) steps:
@@ -29,7 +29,7 @@
 namespace spk {
 namespace lanczos_core {
 
-constexpr int kSteps = 30;   // kLanczosSteps of spk_amg.cpp
+constexpr int kSteps = 30;   // kLanczosSteps of spk_amg_levels.hpp
 
 struct LzState {
     double al[kSteps];       // the diagonal: al[j] = the dot of step j

@@ -1,6 +1,7 @@
 // amg_cycle_check.cpp -- the host-pure order of a multigrid cycle and the rule of the fused tail (csrc/spk_host.cpp:
-// amg_cycle_steps, amg_tail_first, amg_tail_runs) at L = 1, 2 and 16, without a GPU: compiled with g++ and the sanitizers
-// by tests/test_mg_cycle_cpu.py.
+// amg_cycle_steps, amg_tail_first, amg_tail_runs) at L = 1, 2 and 16, and where the iterate of each level lies after each
+// step (amg_cycle_buffers) at L = 2, 3 and 5, without a GPU: compiled with g++ and the sanitizers by
+// tests/test_mg_cycle_cpu.py.
 #include <cstdio>
 #include <vector>
 
@@ -52,8 +53,50 @@ static bool same(const std::vector<AmgStep> &a, const std::vector<AmgStep> &b)
     return true;
 }
 
+// amg_cycle_buffers against the launches' rule, walked step by step as smooth() and amg_apply (spk_amg_cycle.cpp) walk
+// it: cur[l] is the buffer (0: ya, 1: yb) that holds the iterate of level l, -1 while it has none.  Each single smoothing
+// step writes the buffer its input is not in, a fresh start writes ya, the coarse solve writes ya, UP works in place.
+// The fields are compared where the tail kernel reads them: sel at PRE, POST, DOWN and UP, sel_next at UP.
+static void check_buffers(int L, int cycle, int nu, int t)
+{
+    const std::vector<AmgStep> st = spk::amg_cycle_steps(L, cycle);
+    const auto runs = spk::amg_tail_runs(st, t);
+    const spk::AmgBuffers b = spk::amg_cycle_buffers(st, runs, L, nu, t);
+    CHECK(b.sel.size() == st.size() && b.sel_next.size() == st.size() && b.run_sel.size() == runs.size());
+    CHECK(!runs.empty());
+    std::vector<int> cur((size_t)L, -1);
+    size_t run = 0;
+    for (size_t i = 0; i < st.size(); ++i) {
+        const size_t l = (size_t)st[i].level;
+        switch (st[i].kind) {
+        case SPK_AMG_STEP_PRE0: cur[l] = -1;   // the zero guess: no input buffer
+            [[fallthrough]];
+        case SPK_AMG_STEP_PRE:
+        case SPK_AMG_STEP_POST:
+            if (st[i].kind != SPK_AMG_STEP_PRE0) CHECK(cur[l] >= 0 && b.sel[i] == cur[l]);
+            for (int k = 0; k < nu; ++k) cur[l] = cur[l] == 0 ? 1 : 0;   // dst = y == ya ? yb : ya
+            break;
+        case SPK_AMG_STEP_DOWN: CHECK(cur[l] >= 0 && b.sel[i] == cur[l]); break;
+        case SPK_AMG_STEP_COARSE: cur[l] = 0; break;
+        default:   // SPK_AMG_STEP_UP
+            CHECK(cur[l] >= 0 && b.sel[i] == cur[l]);
+            CHECK(cur[l + 1] >= 0 && b.sel_next[i] == cur[l + 1]);
+        }
+        if (run < runs.size() && (size_t)runs[run].second == i + 1) {
+            CHECK(cur[(size_t)t] >= 0 && b.run_sel[run] == cur[(size_t)t]);
+            ++run;
+        }
+    }
+    CHECK(run == runs.size());
+}
+
 int main()
 {
+    for (int L : {2, 3, 5})
+        for (int cycle : {SPK_AMG_CYCLE_V, SPK_AMG_CYCLE_W})
+            for (int nu : {1, 2, 3})
+                for (int t : {1, 2, L - 1})
+                    if (t >= 1 && t <= L - 1) check_buffers(L, cycle, nu, t);
     for (int L : {1, 2, 16})
         for (int cycle : {SPK_AMG_CYCLE_V, SPK_AMG_CYCLE_W}) {
             const bool w = cycle == SPK_AMG_CYCLE_W;

@@ -1,6 +1,6 @@
 // lanczos_core_check.cpp -- the scalar rule of -spk_amg_lanczos resident on the host (csrc/spk_lanczos_core.hpp: the state
 // block and the transitions the kernels' finishing workgroup applies) without a GPU.  A plain Lanczos on D^-1/2 A D^-1/2 of
-// small dense SPD matrices keeps its tridiagonal with push_back and break exactly as dev_lanczos (spk_amg.cpp) does and
+// small dense SPD matrices keeps its tridiagonal with push_back and break exactly as dev_lanczos (spk_amg_setup.cpp) does and
 // records the two sums of every step; the same sums then go through the state machine for ALL kk steps -- behind the break
 // with poison values, as the device enqueues every step blind -- and steps, al and be must agree byte for byte, the state
 // behind the break untouched.  Compiled with g++ and the sanitizers by tests/test_amg_lanczos_cpu.py.

@@ -33,7 +33,7 @@ def hierarchy_mats(get, info):
 
 
 def vcycle_ref(A, P, Ci, lam, b, smoother="chebyshev", smooth_its=2, esteig=(0, 0.1, 0, 1.1), richardson_scale=1.0):
-    """One V-cycle as spk_amg.cpp / spk_k_amg.hip run it: nu steps y+ = y + alpha D^-1 (b - A y) + beta (y - y-) from
+    """One V-cycle as spk_amg_cycle.cpp / spk_k_amg.hip run it: nu steps y+ = y + alpha D^-1 (b - A y) + beta (y - y-) from
     zero, residual restricted by P^T, recursion, y += P e, nu steps from y; the coarsest level y = C b.  Chebyshev
     coefficients of Saad Alg. 12.1 over [b lmax, d lmax] (a and c multiply the smallest Ritz value, 0 by default)."""
     L = len(A)
