@@ -379,8 +379,35 @@ enum { SPK_AMG_OPERATOR_CSR = 0, SPK_AMG_OPERATOR_STENCIL = 1 };
  * the stepwise route's.  RESIDENT with setup = SPK_AMG_SETUP_HOST: spk_pc_set_amg fails with SPK_ERR_UNSUPPORTED naming
  * `-spk_gamg_setup device` and nothing changes; spk_amg_build_host range-checks the field and does not read it. */
 enum { SPK_AMG_LANCZOS_STEPWISE = 0, SPK_AMG_LANCZOS_RESIDENT = 1 };
+/* The precision of the levels >= 1 in the cycle (it steers the application, not the hierarchy: a set-up that differs in it
+ * alone may refresh).  DOUBLE (the default): everything FP64.  SINGLE: the cycle runs every level l >= 1 in FP32.
+ *   What stays FP64.  The hierarchy, byte for byte: the set-up, the Galerkin gather, the Lanczos, lambda_max, what
+ *   spk_get_amg_level returns and the refresh are untouched.  Level 0 keeps the context's layout and its FP64 vectors.
+ *   FP32 copies, made behind every build and every refresh: the value array of every level >= 1, its D^-1 (the FP64 D^-1
+ *   rounded, not recomputed), its Chebyshev / Richardson coefficients and the coarsest level's dense inverse -- every
+ *   conversion one round-to-nearest.  The cycle vectors of the levels >= 1 are float.  The FP64 value arrays stay (the
+ *   refresh and the hooks read them): device memory grows by 4 B per stored entry of the levels >= 1 and shrinks by 4 B per
+ *   entry of their vectors.
+ *   Arithmetic.  On the levels >= 1 all of it is FP32: the expressions of the FP64 route in its order (the row sums of
+ *   SPK_AMG_OPERATOR_STENCIL, the step, the transfers, the lane-strided sums and the butterfly of the dense product),
+ *   every product and every addition rounded on its own -- the same bits on every run, and in the fused tail (which
+ *   never holds level 0) the bits of the launches.
+ *   The boundary.  DOWN on level 0 computes R (b - A y) in FP64 as under DOUBLE and rounds each result once to float
+ *   on the store; UP on level 0 widens each entry of the correction to double, which is exact, and adds in FP64 as
+ *   under DOUBLE.  The transfer weights are powers of two: between FP32 levels the transfers keep their stated order of
+ *   additions and nothing else.
+ *   No scaling.  Nothing rescales the restricted residual: an input whose restricted residual leaves FP32's normal range
+ *   (below 1.2e-38 or above 3.4e38 in magnitude) loses accuracy or overflows; scale such a system first.
+ *   The rounded cycle is not an exactly symmetric linear operator: spk_pipecg / spk_pipecgrr refuse a context whose
+ *   hierarchy was built with SINGLE (SPK_ERR_UNSUPPORTED, the message pointing to -ksp_type fgmres), as they and
+ *   spk_minres refuse the FP32 inner sweeps; FGMRES is flexible and takes it.
+ *   Needs coarsening = GRID, galerkin = STENCIL, op = STENCIL and transfer = MATRIX_FREE -- on that route no kernel of
+ *   a level >= 1 reads an index array; otherwise spk_pc_set_amg fails with SPK_ERR_UNSUPPORTED naming the missing one
+ *   (`-pc_type mg`, `-spk_mg_galerkin stencil`, `-spk_mg_operator stencil`, `-spk_mg_transfer matrixfree`) and nothing
+ *   changes.  spk_amg_build_host range-checks the field and does not read it. */
+enum { SPK_AMG_PRECISION_DOUBLE = 0, SPK_AMG_PRECISION_SINGLE = 1 };
 /* The cycle of one application (it steers the application, not the hierarchy: a set-up that differs in cycle, tail,
- * tail_rows and op alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
+ * tail_rows, op and precision alone may refresh).  V: every level once.  W: the textbook recursion with two visits of the next level,
  *     cycle(l, fresh): l == L-1: COARSE; return
  *                      fresh ? PRE0 : PRE;  DOWN;  cycle(l+1, true);  if W and l+1 < L-1: cycle(l+1, false);  UP;  POST
  * (PETSc's PCMGMCycle): level l < L-1 is entered 2^l times, the coarsest 2^(L-2) times (a repeated exact solve changes
@@ -421,6 +448,8 @@ typedef struct spk_amg_opts {
     int32_t galerkin;         /* -spk_mg_galerkin products|stencil: SPK_AMG_GALERKIN_* (products; grid coarsening only) */
     int32_t op;               /* -spk_mg_operator csr|stencil: SPK_AMG_OPERATOR_* (csr; stencil needs grid coarsening and galerkin stencil) */
     int32_t lanczos;          /* -spk_amg_lanczos stepwise|resident: SPK_AMG_LANCZOS_* (stepwise; resident needs setup device) */
+    int32_t precision;        /* -spk_mg_precision double|single: SPK_AMG_PRECISION_* (double; single needs grid coarsening,
+                                 galerkin stencil, op stencil and matrix-free transfers) */
 } spk_amg_opts;
 void spk_default_amg_opts(spk_amg_opts *opts);
 int spk_pc_set_amg(spk_ctx *ctx, const spk_amg_opts *opts);
@@ -444,6 +473,7 @@ typedef struct spk_amg_info {
     int32_t ritz_readbacks;                  /* device -> host reads the Ritz estimates of the last build or refresh made: a stepwise level
                                                 1 + 2 steps, a resident level 1, a level whose Lanczos ran on a download of it 1; a
                                                 host-built hierarchy 0 */
+    int32_t precision;                       /* SPK_AMG_PRECISION_* of the application: what the levels >= 1 run in */
 } spk_amg_info;
 /* SPK_ERR_STATE unless spk_pc_setup built a hierarchy. */
 int spk_get_amg_info(const spk_ctx *ctx, spk_amg_info *info);
@@ -472,6 +502,14 @@ int spk_debug_amg_transfer(spk_ctx *ctx, int level, int which, int stored, int64
  * was built with grid coarsening and SPK_AMG_GALERKIN_STENCIL: the level has no closed-form pattern). */
 int spk_debug_amg_operator(spk_ctx *ctx, int level, int which, int stencil, double alpha, double beta, const double *x,
                            const double *xo, const double *b, double *out);
+/* The two hooks above on the FP32 kernels of SPK_AMG_PRECISION_SINGLE (SPK_ERR_STATE unless the hierarchy was built with
+ * it), on float host vectors.  Operator: the value-array kernel on the level's FP32 copies, levels 1 .. levels - 2, `which`
+ * as above.  Transfer: the matrix-free kernels; on a level >= 1 every vector is float (a, b: const float *, out: float *);
+ * on level 0 the boundary forms: which 1 takes double a and b (fine_len entries) and gives a float out, which 0 takes a
+ * float a (the correction e) and a double b and out (y, fine_len entries). */
+int spk_debug_amg_operator_f32(spk_ctx *ctx, int level, int which, float alpha, float beta, const float *x, const float *xo,
+                               const float *b, float *out);
+int spk_debug_amg_transfer_f32(spk_ctx *ctx, int level, int which, int64_t fine_len, const void *a, const void *b, void *out);
 /* Test hook: the Lanczos of the device set-up alone on level `level` (0 <= level < levels - 1, else SPK_ERR_ARG) of the
  * context's device-built hierarchy (SPK_ERR_STATE without one), on the unscaled operator.  resident 0: the stepwise route,
  * 1: the resident route, whatever the context's option is.  *steps: the steps taken (<= 30); al: 30 doubles, be: 31 doubles
@@ -590,7 +628,8 @@ int spk_minres(spk_ctx *ctx, const double *b, double *x, int mem, const spk_opts
 /* KSP type pipecg: preconditioned pipelined CG (Ghysels-Vanroose 2014, Alg. 3; PETSc KSPPIPECG) on the device, for a
  * symmetric positive definite K = A (no constraint block: a context with one is refused with SPK_ERR_UNSUPPORTED, the
  * saddle matrix is indefinite -- use spk_minres) and PC none, Jacobi or the V-cycle (spk_pc_set_amg).  The Schur
- * preconditioners and FP32 inner sweeps are refused with SPK_ERR_UNSUPPORTED.  A short recurrence with ONE reduction per
+ * preconditioners, FP32 inner sweeps and a V-cycle with FP32 levels (SPK_AMG_PRECISION_SINGLE: not exactly symmetric) are
+ * refused with SPK_ERR_UNSUPPORTED.  A short recurrence with ONE reduction per
  * iteration whose scalars are ready a pass before they are needed: with none / Jacobi an iteration is the product n = K m
  * plus one pass that applies the eight updates (u = D r and q = D s formed in the pass, not stored), writes m = D w for
  * the next product and reduces [<r, u>, <w, u>, r.r]; the scalar step runs in the finishing workgroup of that pass (one

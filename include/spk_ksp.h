@@ -109,7 +109,13 @@ int SpkKSPGetOptions(SpkKSP ksp, spk_opts *opts, int32_t *pc_type, int32_t *schu
  * of the device set-up's Lanczos (opts->lanczos: the host, reading two sums back per step, the default, or a block on the
  * device read once per level, SPK_AMG_LANCZOS_RESIDENT -- the same hierarchy byte for byte; it needs -spk_gamg_setup device:
  * otherwise SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED naming that option; another value: SPK_ERR_UNSUPPORTED naming the
- * two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
+ * two, no value: SPK_ERR_ARG; given without multigrid it is read and not used).
+ * -spk_mg_precision double|single (also as -fieldsplit_0_spk_mg_precision) selects what the levels >= 1 of the cycle run in
+ * (opts->precision: FP64, the default, or FP32, SPK_AMG_PRECISION_SINGLE, which needs mg with -spk_mg_galerkin stencil,
+ * -spk_mg_operator stencil and matrix-free transfers: otherwise SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED naming what is
+ * missing; with -ksp_type pipecg | pipecgrr SpkKSPSetUp fails with SPK_ERR_UNSUPPORTED pointing to -ksp_type fgmres: the
+ * rounded cycle is not an exactly symmetric operator; another value: SPK_ERR_UNSUPPORTED naming the two, no value:
+ * SPK_ERR_ARG; given without multigrid it is read and not used).  The grid comes from SpkKSPSetOperatorsLaplace / ...3D or SpkKSPSetGrid and is
  * copied into opts->grid at SpkKSPSetUp, which refuses mg without one (SPK_ERR_STATE) before any GPU work; mg is refused
  * where gamg is. */
 int SpkKSPGetAMGOptions(SpkKSP ksp, int fieldsplit0, spk_amg_opts *opts, int32_t *selected);

@@ -22,5 +22,5 @@ from .solver import (  # noqa: F401
     AMG_CYCLE_V, AMG_CYCLE_W, AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED, amg_cycle_steps,
     AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST,
     AMG_GALERKIN_PRODUCTS, AMG_GALERKIN_STENCIL, AMG_OPERATOR_CSR, AMG_OPERATOR_STENCIL, amg_stencil_children,
-    AMG_LANCZOS_STEPWISE, AMG_LANCZOS_RESIDENT,
+    AMG_LANCZOS_STEPWISE, AMG_LANCZOS_RESIDENT, AMG_PRECISION_DOUBLE, AMG_PRECISION_SINGLE,
 )

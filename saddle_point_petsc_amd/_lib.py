@@ -74,7 +74,7 @@ class AmgOpts(C.Structure):
         ("richardson_scale", C.c_double), ("setup", C.c_int32),
         ("coarsening", C.c_int32), ("grid", C.c_int32 * 3), ("transfer", C.c_int32), ("sides", C.c_int32),
         ("cycle", C.c_int32), ("tail", C.c_int32), ("tail_rows", C.c_int32), ("galerkin", C.c_int32),
-        ("op", C.c_int32), ("lanczos", C.c_int32),
+        ("op", C.c_int32), ("lanczos", C.c_int32), ("precision", C.c_int32),
     ]
 
 
@@ -87,6 +87,7 @@ class AmgInfo(C.Structure):
         ("coarsening", C.c_int32), ("dims", (C.c_int32 * 3) * AMG_MAX_LEVELS), ("sides", C.c_int32),
         ("cycle", C.c_int32), ("tail_first", C.c_int32), ("tail_launches", C.c_int32), ("galerkin", C.c_int32),
         ("op", C.c_int32), ("lanczos", C.c_int32), ("ritz_readbacks", C.c_int32),
+        ("precision", C.c_int32),
     ]
 
 
@@ -212,6 +213,8 @@ def _load():
     L.spk_get_amg_aggregates.argtypes = [vp, C.c_int, C.POINTER(i32), vp]
     L.spk_debug_amg_transfer.argtypes = [vp, C.c_int, C.c_int, C.c_int, i64, f64p, f64p, f64p]
     L.spk_debug_amg_operator.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, f64p, C.c_void_p, C.c_void_p, f64p]
+    L.spk_debug_amg_operator_f32.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.spk_debug_amg_transfer_f32.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.spk_debug_amg_lanczos.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), f64p, f64p]
     L.spk_amg_build_host.argtypes = [i32, i32p, i32p, f64p, C.POINTER(AmgOpts), C.POINTER(vp)]
     L.spk_amg_refresh_host.argtypes = [vp, vp]

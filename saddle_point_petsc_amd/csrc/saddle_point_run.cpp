@@ -9,6 +9,8 @@
 //       -pc_type fieldsplit -pc_fieldsplit_type schur -pc_fieldsplit_schur_fact_type full \
 //       -ksp_converged_reason [-saddle 0] [-solution_view] [-no_vtk] [-spk_assembly host|device]
 //       [-spk_basis_precision double|single]
+// (every option of SpkKSPSetFromOptions, include/spk_ksp.h: e.g. -pc_type mg -spk_mg_galerkin stencil -spk_mg_operator
+// stencil -spk_mg_precision single)
 //
 // The reference hard-codes Nx = Ny = 3 elements (main.c:14), i.e. a 4 x 4 node
 // grid; that is the default here too.  -saddle 0 solves A u = f alone, as the

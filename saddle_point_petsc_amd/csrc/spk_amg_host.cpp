@@ -13,6 +13,7 @@
 // DESIGN.md "Algebraic multigrid" has the algorithm and where it departs from PETSc's GAMG.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "spk_amg.hpp"
@@ -480,11 +481,12 @@ void smoother_coeffs(const spk_amg_opts &o, double lo, double hi, std::vector<do
     }
 }
 
-// Which options make the hierarchy, stated once: cycle, tail, tail_rows and op steer the application (amg_plan_cycle reads
-// them at every set-up) and are the second function's; every other field decides the hierarchy and is compared by the
+// Which options make the hierarchy, stated once: cycle, tail, tail_rows, op and precision steer the application
+// (amg_plan_cycle reads them at every set-up) and are the second function's; every other field decides the hierarchy and is compared by the
 // first -- a refresh keeps a hierarchy only where they all agree.  A new field of spk_amg_opts goes on one side or the
 // other: a hierarchy option missing from the comparison would make a stale hierarchy pass for a fresh one.
-static_assert(sizeof(spk_amg_opts) == 128, "spk_amg_opts has changed: put the new field into amg_same_hierarchy_opts or amg_take_application_opts");
+// (precision took the four bytes of padding behind lanczos: the size is the same)
+static_assert(sizeof(spk_amg_opts) == 128 && offsetof(spk_amg_opts, precision) == 124, "spk_amg_opts has changed: put the new field into amg_same_hierarchy_opts or amg_take_application_opts");
 bool amg_same_hierarchy_opts(const spk_amg_opts &a, const spk_amg_opts &b)
 {
     bool same = a.max_levels == b.max_levels && a.coarse_eq_limit == b.coarse_eq_limit && a.nsmooths == b.nsmooths &&
@@ -498,7 +500,7 @@ bool amg_same_hierarchy_opts(const spk_amg_opts &a, const spk_amg_opts &b)
 }
 void amg_take_application_opts(spk_amg_opts &dst, const spk_amg_opts &src)
 {
-    dst.cycle = src.cycle, dst.tail = src.tail, dst.tail_rows = src.tail_rows, dst.op = src.op;
+    dst.cycle = src.cycle, dst.tail = src.tail, dst.tail_rows = src.tail_rows, dst.op = src.op, dst.precision = src.precision;
 }
 
 // what the application's options make of the levels `info` lists: after every build and every refresh, on both routes
@@ -674,6 +676,22 @@ void amg_check_opts(const spk_amg_opts &o, bool host_builder)
     if (!host_builder && o.lanczos == SPK_AMG_LANCZOS_RESIDENT && o.setup == SPK_AMG_SETUP_HOST)
         fail(SPK_ERR_UNSUPPORTED, "amg: -spk_amg_lanczos resident keeps the scalars of the device set-up's Lanczos on the device; the "
              "host set-up has no device Lanczos -- pass -spk_gamg_setup device, or -spk_amg_lanczos stepwise");
+    if (o.precision != SPK_AMG_PRECISION_DOUBLE && o.precision != SPK_AMG_PRECISION_SINGLE)
+        fail(SPK_ERR_ARG, "amg: precision %d is neither SPK_AMG_PRECISION_DOUBLE (0) nor SPK_AMG_PRECISION_SINGLE (1)", o.precision);
+    if (host_builder || o.precision != SPK_AMG_PRECISION_SINGLE) return;   // (the host builder has no cycle: it does not read the field)
+    const char *const what = "amg: -spk_mg_precision single runs the levels >= 1 in FP32 from their value arrays alone, with "
+                             "matrix-free transfers";
+    if (o.coarsening != SPK_AMG_COARSEN_GRID)
+        fail(SPK_ERR_UNSUPPORTED, "%s; smoothed aggregation (gamg) has neither -- use grid coarsening (-pc_type mg) with -spk_mg_galerkin "
+             "stencil -spk_mg_operator stencil, or -spk_mg_precision double", what);
+    if (o.galerkin != SPK_AMG_GALERKIN_STENCIL)
+        fail(SPK_ERR_UNSUPPORTED, "%s; the generic products keep whatever pattern they meet -- pass -spk_mg_galerkin stencil, or "
+             "-spk_mg_precision double", what);
+    if (o.op != SPK_AMG_OPERATOR_STENCIL)
+        fail(SPK_ERR_UNSUPPORTED, "%s; the CSR kernels are FP64 only -- pass -spk_mg_operator stencil, or -spk_mg_precision double", what);
+    if (o.transfer != SPK_AMG_TRANSFER_MATRIX_FREE)
+        fail(SPK_ERR_UNSUPPORTED, "%s; the stored transfers are FP64 CSR matrices -- pass -spk_mg_transfer matrixfree, or "
+             "-spk_mg_precision double", what);
 }
 
 void amg_build(AmgHier &h, HostCsr A, const spk_amg_opts &o)
@@ -747,6 +765,7 @@ void spk_default_amg_opts(spk_amg_opts *o)
     o->richardson_scale = 1.0;
     o->setup = SPK_AMG_SETUP_HOST;
     o->lanczos = SPK_AMG_LANCZOS_STEPWISE;
+    o->precision = SPK_AMG_PRECISION_DOUBLE;
 }
 
 #define SPK_HOST_TRY try {

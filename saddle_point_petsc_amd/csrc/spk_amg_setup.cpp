@@ -103,11 +103,11 @@ void amg_upload(spk_ctx *c, std::unique_ptr<spk_amg_hier> hp)
         if (h.info.coarsening == SPK_AMG_COARSEN_GRID) D.grid.set(h.info.dims[l], h.info.dims[l + 1], h.info.block_size, h.o.transfer);
     }
     d->cinv.upload(h.cinv.data(), h.cinv.size());
-    alloc_cycle_vectors(*d, c->ld);
+    alloc_cycle_vectors(*d, c->ld, h.o.precision == SPK_AMG_PRECISION_SINGLE);
     if (c->amg_reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info = h.info;
-    amg_plan_cycle(*d, h.o);
+    amg_plan_cycle(*d, h.o, c->ld, c->stream);
     d->info.setup_seconds += seconds_since(t0);
     c->amg_d = std::move(d);
     c->amg_h = std::move(hp);
@@ -560,8 +560,8 @@ std::unique_ptr<AmgDev> amg_build_device(spk_ctx *c)
     DevRoute r{c, *d, o, A0, dinv0.p, c->stream, d->reuse != nullptr, nullptr, 1.0, {}, 0};
     build_levels(r, bs, o, SPK_AMG_SETUP_DEVICE, t0, d->info);
     r.ritz_info(d->info);
-    alloc_cycle_vectors(*d, c->ld);
-    amg_plan_cycle(*d, o);
+    alloc_cycle_vectors(*d, c->ld, o.precision == SPK_AMG_PRECISION_SINGLE);
+    amg_plan_cycle(*d, o, c->ld, c->stream);
     if (d->reuse) keep_pattern(c, *d);
     SPK_HIP(hipDeviceSynchronize());
     d->info.setup_seconds = seconds_since(t0);   // the vectors count too, up to the synchronise
@@ -631,7 +631,7 @@ void amg_refresh_ctx(spk_ctx *c)
         r.ritz_info(d.info);
         SPK_HIP(hipDeviceSynchronize());
     }
-    amg_plan_cycle(d, ru.o);   // the coefficients are new, and the device route's coarse inverse lies elsewhere
+    amg_plan_cycle(d, ru.o, c->ld, s);   // the coefficients are new, and the device route's coarse inverse lies elsewhere
     d.info.setup_seconds = seconds_since(t0);
 }
 

@@ -414,6 +414,25 @@ int spk_debug_amg_operator(spk_ctx *c, int level, int which, int stencil, double
     SPK_CATCH(c)
 }
 
+int spk_debug_amg_operator_f32(spk_ctx *c, int level, int which, float alpha, float beta, const float *x, const float *xo,
+                               const float *b, float *out)
+{
+    SPK_TRY(c)
+    if (!x || !out || (!b && (which & 1))) spk::fail(SPK_ERR_ARG, "debug_amg_operator_f32: null pointer");
+    need_amg(c);
+    spk::amg_debug_operator_f32(c, level, which, alpha, beta, x, xo, b, out);
+    SPK_CATCH(c)
+}
+
+int spk_debug_amg_transfer_f32(spk_ctx *c, int level, int which, int64_t fine_len, const void *a, const void *b, void *out)
+{
+    SPK_TRY(c)
+    if (!a || !b || !out) spk::fail(SPK_ERR_ARG, "debug_amg_transfer_f32: null pointer");
+    need_amg(c);
+    spk::amg_debug_transfer_f32(c, level, which, fine_len, a, b, out);
+    SPK_CATCH(c)
+}
+
 int spk_debug_amg_lanczos(spk_ctx *c, int level, int resident, int32_t *steps, double *al, double *be)
 {
     SPK_TRY(c)

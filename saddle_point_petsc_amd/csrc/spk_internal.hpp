@@ -833,30 +833,38 @@ inline GridArgs grid_args(const AmgGrid &a)
 // The fused tail (amg_tail_kernel): what one workgroup needs of the levels >= first, device-resident, written at every
 // set-up.  The matrices, D^-1 and the coarse inverse are read-only in the launch; b, ya and yb are written and read by
 // other waves behind a workgroup barrier -- plain pointers.
+// T: the scalar type of the tail's levels -- double, or float under SPK_AMG_PRECISION_SINGLE (the tail never contains
+// level 0, so it is FP32 throughout: av is the level's FP32 value array, the index arrays and pv, rv are not read)
 constexpr int kAmgMaxSmooth = 64;   // amg_check_opts: smooth_its <= 64
-struct AmgTailLevel {
+template <typename T>
+struct AmgTailLevelT {
     const int32_t *arp, *aci, *prp, *pci, *rrp, *rci;   // CSR of A_l, and of P_l, R_l to level l + 1 (stored transfers)
-    const double *av, *pv, *rv, *dinv;
-    double *b, *ya, *yb;
+    const T *av, *pv, *rv, *dinv;
+    T *b, *ya, *yb;
     int32_t n, nc;                  // rows of the level and of level l + 1
     int32_t nu, bs, matrix_free, fz;   // smoothing steps; node size; the transfers are the grid rule's; fine nodes in z
     int32_t stencil, nd[3];         // A_l is applied from av alone (SPK_AMG_OPERATOR_STENCIL); the level's node grid
     GridArgs g;
-    double alpha[kAmgMaxSmooth], beta[kAmgMaxSmooth];
+    T alpha[kAmgMaxSmooth], beta[kAmgMaxSmooth];
 };
+using AmgTailLevel = AmgTailLevelT<double>;
 // one step as the kernel reads it: sel / sel_next = which buffer (0: ya, 1: yb) holds the iterate of the step's level /
 // of the level below it when the step begins, resolved on the host (smooth()'s rule) so that no thread chooses
 struct AmgTailStep { int32_t kind, level, sel, sel_next; };
-struct AmgTailDesc {
-    const double *cinv;         // the coarse inverse (level `levels` - 1), dense row-major
+template <typename T>
+struct AmgTailDescT {
+    const T *cinv;              // the coarse inverse (level `levels` - 1), dense row-major
     const AmgTailStep *steps;   // the whole cycle's list (a launch takes a range of it)
     int32_t first, levels;
-    AmgTailLevel lv[SPK_AMG_MAX_LEVELS];   // by level; those below `first` are not filled
+    AmgTailLevelT<T> lv[SPK_AMG_MAX_LEVELS];   // by level; those below `first` are not filled
 };
+using AmgTailDesc = AmgTailDescT<double>;
+using AmgTailDescF32 = AmgTailDescT<float>;
 constexpr int kAmgTailThreads = 1024;   // one workgroup, 16 waves: 128 CSR rows or 16 dense rows per sweep
 // steps [s0, s1) of d->steps -- one tail run -- in one launch of one workgroup; stencil: a level of the tail has its
 // `stencil` flag set (the kernel that knows the value-array route; without, the kernel is the one of the CSR route alone)
 void amg_tail(const AmgTailDesc *d, bool stencil, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);
+void amg_tail(const AmgTailDescF32 *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);   // (every level below the coarsest has `stencil` set)
 // smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
 void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
 void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
@@ -865,9 +873,24 @@ void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const do
 // alone -- rowptr and colidx are not read (SPK_AMG_OPERATOR_STENCIL; spk_stencil_op_core.hpp states the sums).  mode 0:
 // out = A x; mode 1: out = x + alpha dinv (b - A x) + beta (x - yo).  stencil_op_rows: the rows of one workgroup
 struct StencilOpArgs { int32_t nx, ny, nz, n; };   // the level's node grid and its rows
-int stencil_op_rows(const int32_t nd[3], int bs);
+int stencil_op_rows(const int32_t nd[3], int bs, size_t elem = sizeof(double));   // elem: sizeof of the scalar type
 void amg_stencil_op(const CsrDev &A, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv, const double *b,
                     const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
+// The FP32 forms of SPK_AMG_PRECISION_SINGLE, overloads on the vectors' types.  The level operator from the FP32 copy `val`
+// of the n-row level's value array (the rows of a workgroup keep the byte budget of stencil_op_rows, so a float workgroup
+// takes up to twice the rows);  the zero-guess step out = alpha dinv b;  the dense product;
+// the transfers float -> float between FP32 levels, and at the level 0 / level 1 boundary R (b - t) summed in FP64 and
+// rounded once on the store, y += P e with every e widened and the sums in FP64
+void amg_stencil_op(int32_t n, const float *val, const int32_t nd[3], int bs, int mode, const float *x, const float *dinv,
+                    const float *b, const float *yo, float *out, float alpha, float beta, const int32_t *done, hipStream_t s);
+void amg_cheb_vec0(int64_t n, const float *dinv, const float *b, float *out, float alpha, const int32_t *done, hipStream_t s);
+void amg_dense(const float *C, int32_t n, const float *b, float *y, const int32_t *done, hipStream_t s);
+void amg_restrict_grid(const AmgGrid &g, const float *b, const float *t, float *out, const int32_t *done, hipStream_t s);
+void amg_restrict_grid(const AmgGrid &g, const double *b, const double *t, float *out, const int32_t *done, hipStream_t s);
+void amg_prolong_add_grid(const AmgGrid &g, const float *e, float *y, const int32_t *done, hipStream_t s);
+void amg_prolong_add_grid(const AmgGrid &g, const float *e, double *y, const int32_t *done, hipStream_t s);
+// dst[i] = (float)src[i], one rounding to nearest (the FP32 copies of a set-up; no `done` gate)
+void amg_round_f32(int64_t n, const double *src, float *dst, hipStream_t s);
 void amg_restrict(const CsrDev &R, const double *b, const double *t, double *out, const int32_t *done, hipStream_t s);   // out = R (b - t)
 void amg_prolong_add(const CsrDev &P, const double *e, double *y, const int32_t *done, hipStream_t s);          // y += P e
 // y == nullptr: out = alpha dinv b (zero initial guess); else out = y + alpha dinv (b - t) + beta (y - yo) (yo null: 0)
@@ -944,6 +967,10 @@ struct AmgLevelDev {
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
     k::AmgGrid grid;                    // grid coarsening: the transfer to level l+1
     bool stencil_op = false;           // the cycle applies A from A.val alone (SPK_AMG_OPERATOR_STENCIL; amg_plan_cycle sets it)
+    // SPK_AMG_PRECISION_SINGLE, levels >= 1: the FP32 copies of A.val and dinv (amg_round_levels, behind every build and
+    // refresh), the cycle vectors in float (b, ya, yb above stay empty there) and the smoothing coefficients rounded
+    DevBuf<float> val32, dinv32, b32, ya32, yb32;
+    std::vector<float> alpha32, beta32;
 };
 // what a set-up with reuse on (spk_pc_set_amg_reuse) keeps beside the hierarchy, so that the next one can refresh it
 struct AmgReuse {
@@ -974,6 +1001,11 @@ struct AmgDev {
     bool tail_stencil = false;      // a level inside the tail applies A from its value array alone
     DevBuf<k::AmgTailDesc> tail_desc;
     DevBuf<k::AmgTailStep> tail_steps;
+    // SPK_AMG_PRECISION_SINGLE: the levels >= 1 run in FP32 (the vectors were allocated so); the coarse inverse rounded, and
+    // the tail's descriptor over the float buffers (tail_desc stays empty)
+    bool single = false;
+    DevBuf<float> cinv32;
+    DevBuf<k::AmgTailDescF32> tail_desc32;
 };
 
 }  // namespace spk
@@ -1143,9 +1175,12 @@ void amg_ctx_aggregates(spk_ctx *c, int l, int32_t *nnodes, int32_t *agg);
 void amg_debug_lanczos(spk_ctx *c, int l, int resident, int32_t *steps, double *al, double *be);
 // the multigrid cycle (spk_amg_cycle.cpp).  What every set-up ends in: the cycle's vectors (ld: the context's padded
 // length) and the application's plan from the options and the levels as they are
-void alloc_cycle_vectors(AmgDev &d, int64_t ld);
-void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o);
+void alloc_cycle_vectors(AmgDev &d, int64_t ld, bool single);
+void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o, int64_t ld, hipStream_t s);
 void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out);
+void amg_debug_operator_f32(spk_ctx *c, int l, int which, float alpha, float beta, const float *x, const float *xo, const float *b,
+                            float *out);
+void amg_debug_transfer_f32(spk_ctx *c, int l, int which, int64_t fine_len, const void *a, const void *b, void *out);
 void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
                         const double *b, double *out);
 // one cycle, mode 0: y = V x, mode 1: y -= V x; last != nullptr: y is not written, *last = the buffer of the hierarchy that holds V x

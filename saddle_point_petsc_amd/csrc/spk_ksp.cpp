@@ -168,6 +168,12 @@ int parse_amg(SpkKSP k, spk_amg_opts &o, bool &reuse, const std::string &full, c
         if (v == "stepwise") o.lanczos = SPK_AMG_LANCZOS_STEPWISE;
         else if (v == "resident") o.lanczos = SPK_AMG_LANCZOS_RESIDENT;
         else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (stepwise | resident)");
+    } else if (key == "-spk_mg_precision") {
+        if (!val) return need("double or single");
+        const std::string v(val);
+        if (v == "double") o.precision = SPK_AMG_PRECISION_DOUBLE;
+        else if (v == "single") o.precision = SPK_AMG_PRECISION_SINGLE;
+        else return set_err(k, SPK_ERR_UNSUPPORTED, "option " + full + " " + v + " is not supported (double | single)");
     } else if (key == "-spk_mg_cycle") {
         if (!val) return need("v or w");
         const std::string v(val);
@@ -561,6 +567,10 @@ int SpkKSPSetUp(SpkKSP k)
     if (minres && amg_slot >= 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type minres with the multigrid preconditioner (" + mgname + ") is not "
                                                "implemented -- pass -ksp_type fgmres");
+    if (pipecg && amg_slot >= 0 && k->amg[amg_slot].precision == SPK_AMG_PRECISION_SINGLE)
+        return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: -ksp_type " + pt + " needs a symmetric preconditioner and the cycle of "
+                                               "-spk_mg_precision single, rounded to FP32 on its levels >= 1, is not exactly one "
+                                               "-- pass -ksp_type fgmres, or -spk_mg_precision double");
     if (amg_slot >= 0 && k->inner_richardson && k->inner_sweeps > 0)
         return set_err(k, SPK_ERR_UNSUPPORTED, "KSPSetUp: " + mgname + " and the FP32 inner sweeps both stand for A^-1 -- drop "
                                                "-fieldsplit_0_ksp_type richardson / -spk_inner_sweeps, or the " + mgname + " option");
@@ -702,6 +712,9 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
                 std::printf("    level operators: stencil (-spk_mg_operator stencil): no level between level 0 and the coarsest\n");
             else if (grid)
                 std::printf("    level operators: csr (-spk_mg_operator csr): levels >= 1 as sparse matrices\n");
+            if (ai.precision == SPK_AMG_PRECISION_SINGLE)
+                std::printf("    precision: single (-spk_mg_precision single): levels 1..%d run in FP32 on rounded copies of their "
+                            "values, level 0 and the hierarchy stay FP64\n", ai.levels - 1);
             if (ai.setup == SPK_AMG_SETUP_DEVICE)
                 std::printf("    set-up Lanczos: %s (-spk_amg_lanczos %s): %s, %d read-backs in the last set-up\n",
                             ai.lanczos == SPK_AMG_LANCZOS_RESIDENT ? "resident" : "stepwise",

@@ -29,6 +29,9 @@ void run(spk_ctx *c, const double *b, double *x, const spk_opts &o, int norm, sp
     if (c->inner_sweeps > 0 && c->pc_type != SPK_PC_NONE)
         fail(SPK_ERR_UNSUPPORTED, "%s needs a symmetric preconditioner: the FP32 inner sweeps are not -- call "
              "spk_pc_set_inner(ctx, 0, omega) before spk_pc_setup, or use -ksp_type fgmres", who);
+    if (c->amg_d && c->amg_d->single && c->pc_type == SPK_PC_JACOBI)
+        fail(SPK_ERR_UNSUPPORTED, "%s needs a symmetric preconditioner: the multigrid cycle of -spk_mg_precision single, rounded to "
+             "FP32 on its levels >= 1, is not exactly one -- use -ksp_type fgmres (spk_fgmres), or -spk_mg_precision double", who);
     SolverFrame<PipecgState> F(c, c->pipecg_work, kPcVecs, 3, o, kPcChunk);   // vectors zero-filled: the pad entries stay zero
     hipStream_t s = c->stream;
     const int64_t ld = c->ld, N = c->n_local, n_dot = N;   // m = 0: no multiplier rows

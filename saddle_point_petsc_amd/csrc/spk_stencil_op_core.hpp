@@ -12,6 +12,8 @@
 //   MODE 0: d.   MODE 1: y + alpha (dinv (b - d)) [+ beta (y - yo) when beta != 0; yo null: y - 0], y = x of the row itself:
 //   amg_csr_kernel<1>'s expressions in its order.
 // These are not the CSR route's bits (eight strided partial sums and a butterfly); they are held to this statement.
+// The scalar type T of the values and the vectors is double, or float under SPK_AMG_PRECISION_SINGLE: the same expressions in
+// the same order, every operation rounded to T.
 #pragma once
 #include "spk_galerkin_core.hpp"
 
@@ -53,12 +55,25 @@ SPK_HD inline int32_t so_max_row(const int32_t nd[3], int bs)
     return wx * wy * wz * bs;
 }
 
+// The rows of one workgroup of the launch (amg_stencil_kernel: one row per thread, the workgroup's values in LDS): whole
+// waves of 64 whose longest rows fill at most 32 KiB, at most 256 rows.  elem: sizeof of the scalar type -- the byte budget
+// is the same for float, so its workgroups take up to twice the rows.
+// 2-D: 256, 192, 128 rows for bs 1, 2, 3 in double, 256 each in float; 3-D: 128, 64, 64 (bs 3: 41 KiB) and 256, 128, 64
+SPK_HD inline int32_t so_wg_rows(const int32_t nd[3], int bs, int32_t elem)
+{
+    const int32_t per = 32768 / (so_max_row(nd, bs) * elem), whole = per / 64 * 64;
+    return whole < 64 ? 64 : whole > 256 ? 256 : whole;
+}
+
 // one row: v points at the row's first value; x is the level's vector (MODE 1: the iterate y).  Returns out[row].
 // G: the grid lines whose loads are issued together, 3 (a plane) or 1 -- registers against loads in flight; it changes
-// no bit (the additions keep their order)
-template <int BS, int MODE, int G = (BS <= 2 ? 3 : 1)>
-SPK_HD inline double so_row(const int32_t nd[3], const SoRow &w, const double *v, const double *x, const double *dinv,
-                            const double *b, const double *yo, double alpha, double beta)
+// no bit (the additions keep their order).  T is deduced from v and x; the other operands are of it (a null pointer or a
+// double constant may stand there)
+template <typename T> struct SoSame { using type = T; };
+template <int BS, int MODE, int G = (BS <= 2 ? 3 : 1), typename T>
+SPK_HD inline T so_row(const int32_t nd[3], const SoRow &w, const T *v, const T *x, const typename SoSame<T>::type *dinv,
+                       const typename SoSame<T>::type *b, const typename SoSame<T>::type *yo, typename SoSame<T>::type alpha,
+                       typename SoSame<T>::type beta)
 {
     SPK_GS_EXACT
     const int32_t i0 = galerkin::gs_first(w.i), j0 = galerkin::gs_first(w.j), k0 = galerkin::gs_first(w.k);
@@ -70,20 +85,20 @@ SPK_HD inline double so_row(const int32_t nd[3], const SoRow &w, const double *v
     // b innermost, wi values
     static_assert(G == 1 || G == 3, "lines per group");
     constexpr int W = 3 * BS;
-    double d = 0.0;
-    const double *vp = v;
+    T d = T(0);
+    const T *vp = v;
     SPK_SO_UNROLL
     for (int kk = 0; kk < 3; ++kk) {
         if (kk >= wk) break;
         SPK_SO_UNROLL
         for (int jg = 0; jg < 3; jg += G) {
             if (jg >= wj) break;
-            double vv[G][W], xv[G][W];
+            T vv[G][W], xv[G][W];
             SPK_SO_UNROLL
             for (int u = 0; u < G; ++u) {
                 const int32_t jc = jg + u < wj ? jg + u : wj - 1;
-                const double *xr = x + ((int64_t)((k0 + kk) * nd[1] + (j0 + jc)) * nd[0] + i0) * BS;
-                const double *vr = vp + jc * wi;
+                const T *xr = x + ((int64_t)((k0 + kk) * nd[1] + (j0 + jc)) * nd[0] + i0) * BS;
+                const T *vr = vp + jc * wi;
                 SPK_SO_UNROLL
                 for (int n = 0; n < 3; ++n) {   // the line's neighbour nodes: one address each, b at constant offsets
                     const int32_t nc = (n < ni ? n : ni - 1) * BS;
@@ -99,7 +114,7 @@ SPK_HD inline double so_row(const int32_t nd[3], const SoRow &w, const double *v
                 SPK_SO_UNROLL
                 for (int t = 0; t < W; ++t) {
                     if (jg + u >= wj || t >= wi) continue;
-                    const double term = vv[u][t] * xv[u][t];
+                    const T term = vv[u][t] * xv[u][t];
                     d = (kk == 0 && jg + u == 0 && t == 0) ? term : d + term;
                 }
         }
@@ -107,9 +122,9 @@ SPK_HD inline double so_row(const int32_t nd[3], const SoRow &w, const double *v
     }
     if (MODE == 0) return d;
     const int64_t row = ((int64_t)(w.k * nd[1] + w.j) * nd[0] + w.i) * BS + w.a;
-    const double y = x[row];
-    double r = y + alpha * (dinv[row] * (b[row] - d));
-    if (beta != 0.0) r += beta * (y - (yo ? yo[row] : 0.0));   // yo null: the zero initial guess
+    const T y = x[row];
+    T r = y + alpha * (dinv[row] * (b[row] - d));
+    if (beta != T(0)) r += beta * (y - (yo ? yo[row] : T(0)));   // yo null: the zero initial guess
     return r;
 }
 

@@ -51,6 +51,7 @@ AMG_CYCLE_V, AMG_CYCLE_W = 0, 1
 AMG_GALERKIN_PRODUCTS, AMG_GALERKIN_STENCIL = 0, 1
 AMG_OPERATOR_CSR, AMG_OPERATOR_STENCIL = 0, 1
 AMG_LANCZOS_STEPWISE, AMG_LANCZOS_RESIDENT = 0, 1
+AMG_PRECISION_DOUBLE, AMG_PRECISION_SINGLE = 0, 1
 AMG_TAIL_AUTO, AMG_TAIL_LAUNCHES, AMG_TAIL_FUSED = 0, 1, 2
 AMG_STEP_PRE0, AMG_STEP_PRE, AMG_STEP_DOWN, AMG_STEP_COARSE, AMG_STEP_UP, AMG_STEP_POST = range(6)
 SPK_ERR_ARG = -1   # include/spk.h
@@ -63,6 +64,7 @@ _CYCLES = {"v": AMG_CYCLE_V, "w": AMG_CYCLE_W}
 _GALERKINS = {"products": AMG_GALERKIN_PRODUCTS, "stencil": AMG_GALERKIN_STENCIL}
 _OPERATORS = {"csr": AMG_OPERATOR_CSR, "stencil": AMG_OPERATOR_STENCIL}
 _LANCZOS = {"stepwise": AMG_LANCZOS_STEPWISE, "resident": AMG_LANCZOS_RESIDENT}
+_PRECISIONS = {"double": AMG_PRECISION_DOUBLE, "single": AMG_PRECISION_SINGLE}
 _TAILS = {"auto": AMG_TAIL_AUTO, "launches": AMG_TAIL_LAUNCHES, "fused": AMG_TAIL_FUSED}
 
 
@@ -74,7 +76,10 @@ def amg_opts(**kw):
     (how the cycle applies the levels between level 0 and the coarsest: as sparse matrices, or from their value arrays
     alone -- the struct's field is `op`; 'stencil' needs coarsening='grid' and galerkin='stencil'), lanczos 'stepwise' /
     'resident' (who holds the scalars of the device set-up's Lanczos: the host, reading two sums back per step, or a block
-    on the device read once per level -- the same hierarchy to the bit; 'resident' needs setup='device');
+    on the device read once per level -- the same hierarchy to the bit; 'resident' needs setup='device'), precision
+    'double' / 'single' (what the levels >= 1 of the cycle run in: 'single' keeps the FP64 hierarchy and level 0 and runs
+    the other levels in FP32 on rounded copies; it needs coarsening='grid', galerkin='stencil', operator='stencil' and
+    transfer='matrixfree');
     grid=(mx, my[, mz]) are the nodes per side that grid coarsening halves: the odd ones, or under sides='any' the even
     ones too)."""
     o = AmgOpts()
@@ -104,6 +109,8 @@ def amg_opts(**kw):
             v = _GALERKINS[v]
         if k == "lanczos" and isinstance(v, str):
             v = _LANCZOS[v]
+        if k == "precision" and isinstance(v, str):
+            v = _PRECISIONS[v]
         if k == "esteig":
             v = (C.c_double * 4)(*v)
         if k == "grid":
@@ -130,7 +137,7 @@ def _amg_info(ai):
                 setup_seconds=ai.setup_seconds, setup=ai.setup, coarsening=ai.coarsening,
                 dims=[tuple(ai.dims[l]) for l in range(L)], sides=ai.sides, cycle=ai.cycle, tail_first=ai.tail_first,
                 tail_launches=ai.tail_launches, galerkin=ai.galerkin, operator=ai.op, lanczos=ai.lanczos,
-                ritz_readbacks=ai.ritz_readbacks)
+                ritz_readbacks=ai.ritz_readbacks, precision=ai.precision)
 
 
 def amg_stencil_children(fine, coarse, node):
@@ -648,9 +655,22 @@ class Context:
         self._chk(lib.spk_get_amg_reuse_info(self.h, C.byref(r), C.byref(t)))
         return dict(refreshed=bool(r.value), seconds=t.value)
 
-    def debug_amg_transfer(self, level, which, a, b, stored=False):
+    def debug_amg_transfer(self, level, which, a, b, stored=False, precision="double"):
         """Test hook (spk_debug_amg_transfer): one transfer of a level alone.  which 'prolong': b + P a (a: coarse, b: fine);
-        'restrict': R (a - b) (both fine).  The fine vectors may be longer than the level (a padded vector)."""
+        'restrict': R (a - b) (both fine).  The fine vectors may be longer than the level (a padded vector).
+        precision 'single' (spk_debug_amg_transfer_f32, a hierarchy built with it): the matrix-free FP32 kernels -- float32
+        vectors on a level >= 1; on level 0 'restrict' takes float64 and gives float32, 'prolong' takes a float32 a and a
+        float64 b and gives float64."""
+        if precision == "single":
+            pro = which == "prolong"
+            ta = np.float32 if level > 0 or pro else np.float64
+            tb = np.float32 if level > 0 else np.float64
+            to = np.float32 if level > 0 or not pro else np.float64
+            a, b = np.ascontiguousarray(a, ta), np.ascontiguousarray(b, tb)
+            out = np.zeros(b.size if pro else self.amg_info()["rows"][level + 1], to)
+            self._chk(lib.spk_debug_amg_transfer_f32(self.h, level, 0 if pro else 1, b.size, a.ctypes.data, b.ctypes.data,
+                                                     out.ctypes.data))
+            return out
         a = np.ascontiguousarray(a, np.float64)
         b = np.ascontiguousarray(b, np.float64)
         info = self.amg_info()
@@ -659,23 +679,30 @@ class Context:
         self._chk(lib.spk_debug_amg_transfer(self.h, level, 0 if pro else 1, 1 if stored else 0, b.size, a, b, out))
         return out
 
-    def debug_amg_operator(self, level, which, x, b=None, xo=None, alpha=0.0, beta=0.0, stencil=True, done=False, out=None):
+    def debug_amg_operator(self, level, which, x, b=None, xo=None, alpha=0.0, beta=0.0, stencil=True, done=False, out=None,
+                           precision="double"):
         """Test hook (spk_debug_amg_operator): the operator of a level between level 0 and the coarsest alone, one launch.
         which 'product': A x; 'step': x + alpha D^-1 (b - A x) + beta (x - xo) (xo None: the zero vector).  stencil: the
         value-array kernels, else the CSR kernels.  done: the launch finds the `done` gate set, and `out` (given, or
-        zeros) comes back as it went in."""
+        zeros) comes back as it went in.  precision 'single' (spk_debug_amg_operator_f32, a hierarchy built with it): the
+        FP32 value-array kernel on float32 vectors; alpha and beta are rounded to float32."""
         rows = self.amg_info()["rows"]
         if not 0 <= level < len(rows):
             raise SpkError(SPK_ERR_ARG, f"level {level} outside the hierarchy")
         n = rows[level]
         step = which == "step"
-        vec = lambda v: None if v is None else np.ascontiguousarray(v, np.float64)
+        dt = np.float32 if precision == "single" else np.float64
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, dt)
         x, b, xo = vec(x), vec(b), vec(xo)
         for v in (x, b, xo):
             if v is not None and v.size != n:
                 raise SpkError(SPK_ERR_ARG, f"a vector of {v.size} entries for the {n} rows of level {level}")
-        out = np.zeros(n) if out is None else np.array(out, np.float64)
+        out = np.zeros(n, dt) if out is None else np.array(out, dt)
         ptr = lambda v: None if v is None else v.ctypes.data
+        if precision == "single":
+            self._chk(lib.spk_debug_amg_operator_f32(self.h, level, (1 if step else 0) + (2 if done else 0), float(alpha), float(beta),
+                                                     ptr(x), ptr(xo), ptr(b), ptr(out)))
+            return out
         self._chk(lib.spk_debug_amg_operator(self.h, level, (1 if step else 0) + (2 if done else 0), 1 if stencil else 0,
                                              float(alpha), float(beta), x, ptr(xo), ptr(b), out))
         return out

@@ -47,7 +47,20 @@ one process, reuse off so that every set-up is a build, after one warm-up round 
 -> V-cycle timing; then, per context, reuse-on refreshes on alternating values.  Per route: set-up and refresh as median
 (min..max) with the read-backs of the Ritz estimates, solve, iterations and V-cycle.  The bar, checked at 1025 and 1024
 nodes per side, for the build and for the refresh: the resident route's median plus its spread (max - min) at or below the
-stepwise route's median (exit status 1 when missed); iterations and lambda_max of the two must be equal."""
+stepwise route's median (exit status 1 when missed); iterations and lambda_max of the two must be equal.
+    python tools/mg_bench.py --precision both --galerkin stencil --operator stencil [--grids 1025] [--sides odd|any] [--dim 2|3]
+--precision double|single (-spk_mg_precision; default double) selects what the levels >= 1 of mg's cycle run in in the runs
+above (single needs --galerkin stencil --operator stencil); every emitted line records it.  --precision both compares the
+two: K = A, per grid two contexts on the same hierarchy bytes in one process, after one warm-up round --reps alternating
+rounds of set-up -> solve -> V-cycle timing.  Per route: V-cycle, solve, iterations and set-up.  --dim 3: the 3-D generator
+on a cube of --grids nodes per side (bs 3).  The bar, checked at 1025 and 1024 nodes per side: single's V-cycle median plus
+its spread (max - min) at or below double's V-cycle median (exit status 1 when missed); the iterations of the two must
+agree within 1.
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mg_bench.py --precision-kernels [--grid 1025]
+    python tools/rocpd_by_grid.py DIR/<host>/<pid>_results.db out.csv amg_stencil_kernel amg_stencil_f32_kernel
+--precision-kernels launches the product and the smoothing step of levels 1 and 2 alone through the two test hooks, FP64
+and FP32 alternating (a warm-up round and --reps more), for a kernel trace; the line it prints has the byte models: 8 B
+or 4 B per stored entry plus the vectors."""
 import argparse
 import csv
 import glob
@@ -75,12 +88,15 @@ ap.add_argument("--operator", choices=["csr", "stencil", "both"], default="csr",
 ap.add_argument("--operator-kernels", action="store_true", help="only launch the level operators of levels 1 and 2 of --grid (for a kernel trace)")
 ap.add_argument("--lanczos", choices=["stepwise", "resident", "both"], default="stepwise",
                 help="who holds the scalars of the device set-up's Lanczos (-spk_amg_lanczos)")
+ap.add_argument("--precision", choices=["double", "single", "both"], default="double", help="what mg's levels >= 1 run in (-spk_mg_precision)")
+ap.add_argument("--precision-kernels", action="store_true", help="only launch the FP64 and FP32 level operators of levels 1 and 2 of --grid (for a kernel trace)")
+ap.add_argument("--dim", type=int, choices=[2, 3], default=2, help="--precision both: the 2-D generator, or the 3-D one on a cube")
 ap.add_argument("--out", help="append the JSON lines to this file too")
 a = ap.parse_args()
 
 
 def emit(row):
-    line = json.dumps(dict(dict(galerkin=a.galerkin, operator=a.operator, lanczos=a.lanczos), **dict(row, sides=a.sides)))
+    line = json.dumps(dict(dict(galerkin=a.galerkin, operator=a.operator, lanczos=a.lanczos, precision=a.precision), **dict(row, sides=a.sides)))
     print(line, flush=True)
     if a.out:
         with open(a.out, "a") as fh:
@@ -164,10 +180,35 @@ if a.setup_only:
     sys.exit(0)
 
 
-def mg_opts(g, galerkin, operator=None, lanczos=None):
-    return dict(coarsening="grid", grid=(g, g), setup="device", sides=a.sides, galerkin=galerkin,
+def mg_opts(g, galerkin, operator=None, lanczos=None, precision=None, dim=2):
+    return dict(coarsening="grid", grid=(g, g) if dim == 2 else (g, g, g), setup="device", sides=a.sides, galerkin=galerkin,
                 operator=operator or (a.operator if a.operator != "both" else "csr"),
-                lanczos=lanczos or (a.lanczos if a.lanczos != "both" else "stepwise"))
+                lanczos=lanczos or (a.lanczos if a.lanczos != "both" else "stepwise"),
+                precision=precision or (a.precision if a.precision != "both" else "double"))
+
+
+if a.precision_kernels:
+    g = a.grid
+    A, _ = S.AssembleOperator_Laplace(g, g)
+    rng = np.random.default_rng(g)
+    with S.Context(0) as c:
+        c.set_block(S.BLOCK_A00, A)
+        c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, "stencil", "stencil", precision="single"))
+        info = c.amg_info()
+        models = []
+        for l in (1, 2):
+            n, nnz = info["rows"][l], info["nnz"][l]
+            x, xo, b = rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(n)
+            for rep in range(-1, a.reps):
+                for prec in ("double", "single"):
+                    c.debug_amg_operator(l, "product", x, precision=prec)
+                    c.debug_amg_operator(l, "step", x, b=b, xo=xo, alpha=0.7, beta=0.3, precision=prec)
+            # x read + out written; the step: + D^-1, b, y-
+            models.append(dict(level=l, rows=n, nnz=nnz, dims=info["dims"][l],
+                               double_product_bytes=8 * nnz + 16 * n, double_step_bytes=8 * nnz + 40 * n,
+                               single_product_bytes=4 * nnz + 8 * n, single_step_bytes=4 * nnz + 20 * n))
+    print(json.dumps(dict(mode="precision-kernels-launched", grid=g, sides=a.sides, rounds=a.reps + 1, levels=models)), flush=True)
+    sys.exit(0)
 
 
 if a.operator_kernels:
@@ -274,6 +315,41 @@ def compare_operator(g):
     return {route: (t[route]["vcycle"], t[route]["its"]) for route in routes}
 
 
+def compare_precision(g):
+    """FP64 and FP32 levels >= 1 on K = A over the same hierarchy; returns {route: (V-cycle seconds, iterations)}"""
+    A, f = S.AssembleOperator_Laplace(g, g) if a.dim == 2 else S.AssembleOperator_Laplace3D(g, g, g)
+    routes = ("double", "single")
+    ctxs, t = {}, {}
+    for route in routes:
+        c = S.Context(0)
+        c.set_block(S.BLOCK_A00, A)
+        ctxs[route] = c
+        t[route] = dict(setup=[], solve=[], vcycle=[], its=[], res=[])
+    for rep in range(-1, a.reps):   # -1: the warm-up round, not counted
+        for route, c in ctxs.items():
+            c.pc_setup(S.PC_JACOBI, amg=mg_opts(g, "stencil", "stencil", precision=route, dim=a.dim))
+            x, info = c.fgmres(f, rtol=a.rtol, max_it=500, restart=30)
+            assert info["reason"] == 2, (route, info["reason"])
+            vc_ms = c.time_kernel("pc", warmup=5, reps=50)
+            if rep < 0:
+                continue
+            r = t[route]
+            r["setup"].append(c.amg_info()["setup_seconds"])
+            r["solve"].append(info["solve_seconds"])
+            r["vcycle"].append(vc_ms * 1e-3)
+            r["its"].append(info["its"])
+            r["res"].append(float(np.linalg.norm(f - c.mult(x)) / np.linalg.norm(f)))
+    for route, c in ctxs.items():
+        info, r = c.amg_info(), t[route]
+        assert info["precision"] == (route == "single")
+        emit(dict(mode="precision", system="A", dim=a.dim, grid=g, pc="mg", route=route, solver="fgmres(30)", rtol=a.rtol, reps=a.reps,
+                  levels=info["levels"], rows=info["rows"], nnz=info["nnz"], operator_complexity=round(info["operator_complexity"], 4),
+                  its=sorted(set(r["its"])), true_rel_res=max(r["res"]), pc_apply_us=mmm(r["vcycle"], 1e6, 1),
+                  solve_ms=mmm(r["solve"], 1e3, 3), setup_ms=mmm(r["setup"], 1e3, 3)))
+        c.close()
+    return {route: (t[route]["vcycle"], t[route]["its"]) for route in routes}
+
+
 def compare_lanczos(g):
     """the two routes of the set-up's Lanczos on K = A: the same hierarchy; returns {route: (set-up seconds, refresh seconds, its)}"""
     A, f = S.AssembleOperator_Laplace(g, g)
@@ -324,6 +400,24 @@ def compare_lanczos(g):
         c.close()
     return {route: (t[route]["setup"], t[route]["refresh"], t[route]["its"]) for route in routes}
 
+
+if a.precision == "both":
+    if a.galerkin != "stencil" or a.operator != "stencil":
+        sys.exit("--precision both compares two applications of the all-stencil route: pass --galerkin stencil --operator stencil")
+    met = True
+    for g in a.grids:
+        s = compare_precision(g)
+        (dv, di), (sv, si) = s["double"], s["single"]
+        same_its = max(abs(u - v) for u in di for v in si) <= 1
+        row = dict(mode="bar", system="A", dim=a.dim, grid=g, iterations_within_one=bool(same_its), double_pc_apply_us=mmm(dv, 1e6, 1),
+                   single_pc_apply_us=mmm(sv, 1e6, 1), double_over_single=round(float(np.median(dv) / np.median(sv)), 3))
+        met = met and same_its
+        if a.dim == 2 and g in (1024, 1025):
+            ok = float(np.median(sv)) + (max(sv) - min(sv)) <= float(np.median(dv))
+            met = met and ok
+            row.update(bar="single V-cycle median + spread <= double V-cycle median", bar_met=bool(ok))
+        emit(row)
+    sys.exit(0 if met else 1)
 
 if a.lanczos == "both":
     met = True
