@@ -397,7 +397,10 @@ enum { SPK_AMG_LANCZOS_STEPWISE = 0, SPK_AMG_LANCZOS_RESIDENT = 1 };
  *   under DOUBLE.  The transfer weights are powers of two: between FP32 levels the transfers keep their stated order of
  *   additions and nothing else.
  *   No scaling.  Nothing rescales the restricted residual: an input whose restricted residual leaves FP32's normal range
- *   (below 1.2e-38 or above 3.4e38 in magnitude) loses accuracy or overflows; scale such a system first.
+ *   (below 1.2e-38 or above 3.4e38 in magnitude) loses accuracy or overflows; scale such a system first.  Inside the normal
+ *   range a scaling of the input by a power of two scales the output by it, bit for bit.  Below it the FP32 kernels
+ *   underflow gradually (IEEE subnormals, nothing is flushed to zero: the code objects are built with FP32 denormals on,
+ *   the compiler's default for gfx950), so accuracy is lost bit by bit down to 1.4e-45 and not at once.
  *   The rounded cycle is not an exactly symmetric linear operator: spk_pipecg / spk_pipecgrr refuse a context whose
  *   hierarchy was built with SINGLE (SPK_ERR_UNSUPPORTED, the message pointing to -ksp_type fgmres), as they and
  *   spk_minres refuse the FP32 inner sweeps; FGMRES is flexible and takes it.

@@ -123,6 +123,11 @@ def amg_kw(shape, **kw):
     return dict(dict(coarsening="grid", grid=grid, sides=sides, block_size=bs, coarse_eq_limit=10), **kw)
 
 
+def stencil_kw(shape, **kw):
+    """amg_kw on the all-stencil route: what precision='single' needs"""
+    return amg_kw(shape, **dict(dict(galerkin="stencil", operator="stencil"), **kw))
+
+
 @functools.lru_cache(maxsize=None)
 def host_hierarchy(shape, field, galerkin="stencil"):
     """(info, (A_l, P_l, C^-1)) of the host build, computed once; nobody writes into it"""

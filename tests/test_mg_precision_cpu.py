@@ -48,16 +48,19 @@ def host_hierarchy(name):
 
 
 # ---- the numpy cycle with FP32 levels -----------------------------------------------------------------------------------
-def vcycle_ref_mixed(A, P, Ci, lam, b, smooth_its=2, esteig=(0, 0.1, 0, 1.1), gamma=1):
+def vcycle_ref_mixed(A, P, Ci, lam, b, smooth_its=2, esteig=(0, 0.1, 0, 1.1), gamma=1, dinv=None):
     """vcycle_ref (test_mg_sides_cpu; gamma = 2: the W-cycle of test_mg_cycle_cpu.cycle_ref, a second visit of level l + 1
     from its own iterate unless it is the coarsest) with the levels >= 1 in numpy float32, as SPK_AMG_PRECISION_SINGLE states them: the
     values of A_l, D^-1 (the FP64 D^-1 rounded), the coefficients and the coarse inverse rounded once to float32, the vectors
     of the levels >= 1 float32 and every operation on them a float32 one; level 0 in float64; DOWN on level 0 computes
     R (b - A y) in float64 and rounds the result once, UP on level 0 widens e and adds in float64.  The transfer weights
-    are powers of two, so P as float32 is exact."""
+    are powers of two, so P as float32 is exact.  dinv: a list per level of FP64 vectors in place of 1 / diag(A_l), rounded
+    as that is (test_mg_varcoef_cpu.vcycle_with's argument: the mis-indexed cycles of test_mg_precision_varcoef_cpu.py)."""
     L = len(A)
     dt = lambda l: np.float64 if l == 0 else F32
-    dinv = [(1.0 / np.where(a.diagonal() == 0.0, 1.0, a.diagonal())).astype(dt(l)) for l, a in enumerate(A)]
+    if dinv is None:
+        dinv = [1.0 / np.where(a.diagonal() == 0.0, 1.0, a.diagonal()) for a in A]
+    dinv = [np.asarray(d, np.float64).astype(dt(l)) for l, d in enumerate(dinv)]
     Al = [a.astype(dt(l)) for l, a in enumerate(A)]
     Pl = [p.astype(dt(l)) for l, p in enumerate(P)]
     Cl = Ci.astype(dt(L - 1))
