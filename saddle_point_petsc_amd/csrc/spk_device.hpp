@@ -855,15 +855,21 @@ inline WsShape ws_shape(int64_t n2)
 // items must be dead before kernel B's tile loop (w~ and the planes are: they move into its prefetch arrays ahead of the
 // loop); the kept basis vectors are read inside the loop and live in LDS.  NoKeep (the default of both bodies) keeps
 // nothing and compiles to the code without a keep set.
+// AH (SPK_GS_AHEAD, a launch with a keep set only): what kernel B's pass asks for ahead of the totals wait beyond the
+// first group that is not kept -- the first AH vectors of the group behind it (V_{KV+G} .. V_{KV+G+AH-1}), requested
+// into the tile loop's own buffer, which is empty until the loop's first trip.  No addition moves.
 struct NoKeep {
-    static constexpr int KW = 0, KP = 0, KV = 0;
-    static constexpr bool any = false, fused = false;
+    static constexpr int KW = 0, KP = 0, KV = 0, AH = 0;
+    static constexpr bool any = false, fused = false, PK = false;
     __device__ __forceinline__ void put(int, int, double2) {}
     __device__ __forceinline__ double2 get(int, int) const { return double2{0.0, 0.0}; }
 };
-template <int T, int U, int KW_, int KP_, int KV_, int KR_>
+template <int T, int U, int KW_, int KP_, int KV_, int KR_, int AH_ = 0, bool PK_ = false>
 struct KeepSet {
     static constexpr int KW = KW_, KP = KP_, KV = KV_, KR = KR_, N = KW_ + KP_ + KV_, KL = N > KR_ ? N - KR_ : 0;
+    static constexpr int AH = AH_;
+    static constexpr bool PK = PK_;   // kernel B's pass is only launched on parity planes of B D (IterB::packed)
+    static_assert(AH_ == 0 || KV_ > 0, "the loads ahead of the wait follow the kept vectors");
     static constexpr bool any = N > 0, fused = true;   // fused: a KeepSet (an empty one too) is form 7's launch
     double2 r[KR_ > 0 ? KR_ : 1][U];
     double2 *l;   // KL * U * T double2 of LDS

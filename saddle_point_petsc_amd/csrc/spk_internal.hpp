@@ -694,6 +694,7 @@ struct GsArgs {
     const double *V2;    // planes of B D (parity-interleaved when split)
     int cnt, split;      // cnt = nv + m values (<= 40), w.w after them
     int keep;            // the first tile's operands stay on chip between the two passes (FgmresPlan::gs_keep)
+    int ahead;           // with keep: a second group of basis loads ahead of the totals wait (FgmresPlan::gs_ahead)
     int64_t n2, n_dot;   // MDot's length in double2 (the multiplier entries included), entries that count
     double *partials;    // MDot's partial rows (column offset 1 of the context's partials)
     double *out;         // the reduced [h, q, w.w] (as mdot's Finish::out)

@@ -27,8 +27,9 @@ namespace k {
 // and j into a and c (an index < 0: none, the value stays) -- in form 7 a wait, so both are requested before either is
 // looked at and every load that does not depend on them is requested first.
 // keep (form 7 only, see KeepSet): the first tile takes w~, the parity planes and V_0 .. V_{KV-1} from the keep set; its
-// loads ahead of the scalar prologue are D^-1 and the first group behind the kept vectors.  Groups, slots past nv and
-// the order of every addition are those of the other tiles.
+// loads ahead of the scalar prologue are D^-1, the first group behind the kept vectors and Keep::AH vectors of the group
+// behind that one (held in the tile loop's buffer).  Groups, slots past nv and the order of every addition are those of
+// the other tiles.
 // BT = float (-spk_basis_precision single, b.w32): V~_0 .. V~_{nv-1} are read as floats (converted exactly), w' is formed in
 // FP64 as ever and stored as float(w') into w32, ||w'||^2 is the norm of the ROUNDED vector -- so that the scale factor
 // belongs to what the basis holds -- and z~, c~ come from the unrounded w' in registers (the method is flexible).
@@ -41,6 +42,9 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     using E2 = typename Basis::E2;
     constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
     static_assert(KV % G == 0, "whole groups of basis vectors are kept");
+    // the kept tile: AH more vectors requested ahead of the totals wait, into the tile loop's buffer (see NoKeep)
+    constexpr int AH = Keep::AH;
+    static_assert(AH <= G, "the tile loop's buffer is one group");
     const int32_t dn = __builtin_nontemporal_load(b.done);  // looked at behind the first loads (see mdot_ws16_kernel)
     __shared__ double hs[kMaxNv], lam[kMaxNv * 8], ys[8], wraws[8], tus[8];
     __shared__ double red[T];
@@ -58,16 +62,22 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
     // memory round trips of its own (kernel of 16 us on the 1/8 slab, 8 us of them not bytes)
     constexpr bool PRE = U * (MP > 0 ? MP : 1) <= 16;  // planes of B D fetched ahead too, where the registers allow (not 512 x 4 x 8 rows)
     static_assert(KP == 0 || (PRE && KP <= NP / 2), "kept planes are parity planes fetched ahead");
-    const bool kpl = KP > 0 && b.packed && m > 0;   // (as in mdot_tiles: the first tile's planes are in the keep set)
-    double2 wv[U], dv[U], pe[PRE ? NP : 1][U], tdead;
-    E2 t0[G][U];
+    // Keep::PK: the launcher vouches for parity planes (b.packed), so only NP / 2 planes are fetched ahead -- the registers
+    // of the other half hold the loads requested ahead of the totals wait instead
+    constexpr bool PK = Keep::PK;
+    constexpr int NPE = PK ? NP / 2 : NP;
+    static_assert(!PK || (PRE && MP > 0), "parity planes fetched ahead");
+    const bool packed = PK || b.packed;
+    const bool kpl = KP > 0 && packed && m > 0;   // (as in mdot_tiles: the first tile's planes are in the keep set)
+    double2 wv[U], dv[U], pe[PRE ? NPE : 1][U], tdead;
+    E2 t0[G][U], t[G][U];   // t: the tile loop's buffer (empty until the loop's first trip past t0)
     int64_t idx[U];
     bool ok[U];
     int64_t tile = bx;
     auto load_planes = [&]() {
 #pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const bool live = b.packed ? 2 * q < m : q < m;
+        for (int q = 0; q < NPE; ++q) {
+            const bool live = packed ? 2 * q < m : q < m;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 pe[q][u].x = pe[q][u].y = 0.0;
@@ -87,7 +97,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
         if (MP > 0 && PRE) {
             if (KF && kpl) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) {
+                for (int q = 0; q < NPE; ++q) {
 #pragma unroll
                     for (int u = 0; u < U; ++u) pe[q][u] = q < KP ? keep->get(KW + q, u) : double2{0.0, 0.0};
                 }
@@ -102,6 +112,14 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             const bool live = v0 + v < nv;
 #pragma unroll
             for (int u = 0; u < U; ++u) t0[v][u] = Basis::ld(b.V, (size_t)(live ? v0 + v : 0), b.ldv, live ? idx[u] : 0);
+        }
+        if (KF && AH > 0) {   // ... and of the group behind it: the first trip of the tile loop finds them here
+#pragma unroll
+            for (int v = 0; v < AH; ++v) {
+                const bool live = v0 + G + v < nv;
+#pragma unroll
+                for (int u = 0; u < U; ++u) t[v][u] = Basis::ld(b.V, (size_t)(live ? v0 + G + v : 0), b.ldv, live ? idx[u] : 0);
+            }
         }
     };
     bool have = is_main && tile * (T * U) < n2;
@@ -268,7 +286,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                 }
             }
         } else if (MP > 0) {
-            if (b.packed) {
+            if (packed) {
 #pragma unroll
                 for (int q = 0; q < NP / 2; ++q) {
 #pragma unroll
@@ -277,7 +295,7 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
                         sv[u].y += pe[q][u].y * yv[2 * q + 1];
                     }
                 }
-            } else {
+            } else if constexpr (!PK) {
 #pragma unroll
                 for (int r = 0; r < NP; ++r) {
 #pragma unroll
@@ -316,15 +334,18 @@ __device__ __forceinline__ void maxpy_uhead_tiles(const IterB &b, int scalar_wg,
             }
         }
         for (int g0 = v0 + G; g0 < nv; g0 += G) {
-            E2 t[G][U];
+            const bool first = AH > 0 && KF && g0 == v0 + G;   // its first AH vectors: requested ahead of the totals wait (load_tile)
             double ai[G];
 #pragma unroll
             for (int v = 0; v < G; ++v) {
                 const bool live = g0 + v < nv;
                 const int ic = live ? g0 + v : 0;
+                const bool pre = first && v < AH;
                 ai[v] = live ? -hs[ic] : 0.0;
+                if (!pre) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) t[v][u] = Basis::ld(b.V, (size_t)ic, b.ldv, live ? idx[u] : 0);
+                    for (int u = 0; u < U; ++u) t[v][u] = Basis::ld(b.V, (size_t)ic, b.ldv, live ? idx[u] : 0);
+                }
             }
 #pragma unroll
             for (int v = 0; v < G; ++v) {
@@ -534,17 +555,29 @@ constexpr int kGsT = 512, kGsU = 4, kGsG = 4;   // vec_shape's fat shape (mdot_k
 // fit 160 KiB).  Sized by the compiler's resource remark on gfx950 (tests/test_gs_keep_resources_cpu.py):
 // no scratch, <= 256 registers for every instantiation -- <5, 4> with the planes kept spills 19 VGPRs, so it keeps
 // w~ and the basis vectors only.
-template <int NG, int MP>
+template <int NG, int MP, int AH = 0>
 struct GsKeep {
     static constexpr int KP = MP == 4 && NG <= 4 ? 2 : 0, KV = 4;
-    using type = KeepSet<kGsT, kGsU, 1, KP, KV, 1 + KP>;
+    using type = KeepSet<kGsT, kGsU, 1, KP, KV, 1 + KP, AH, (MP == 4 && AH > 0)>;
 };
 
-template <int NG, int MP, bool KEEP>
+// What a launch with a keep set asks for ahead of the totals wait beyond V_4 .. V_7 (GsArgs::ahead, SPK_GS_AHEAD; NoKeep
+// in spk_device.hpp): kGsAhead[MP / 4][NG - 1] vectors of the group V_8 .. V_11, held across the wait in the registers
+// of the tile loop's buffer, 16 each.  Sized by the compiler's resource remark (tests/test_gs_ahead_resources_cpu.py
+// reads this table and the remark of every instantiation): MP = 4 takes the registers of the two planes that parity
+// planes leave unused (KeepSet::PK) and still spills 4 .. 12 VGPRs with the whole group, so it holds three vectors.
+constexpr int kGsAhead[3][5] = {
+    {4, 4, 4, 4, 4},   // MP = 0
+    {3, 3, 3, 3, 3},   // MP = 4
+    {4, 4, 4, 4, 4},   // MP = 8
+};
+
+template <int NG, int MP, bool KEEP, int AH = 0>
 __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
 {
     constexpr int NA = NG * 8 + 1, W = kGsT / kWave;
-    using Keep = typename std::conditional<KEEP, typename GsKeep<NG, MP>::type, KeepSet<kGsT, kGsU, 0, 0, 0, 0>>::type;
+    static_assert(KEEP || AH == 0, "loads ahead of the wait belong to the launch with a keep set");
+    using Keep = typename std::conditional<KEEP, typename GsKeep<NG, MP, AH>::type, KeepSet<kGsT, kGsU, 0, 0, 0, 0>>::type;
     __shared__ double lds[(W * NA > kGsT) ? W * NA : kGsT];
     __shared__ double2 klds[Keep::KL > 0 ? Keep::KL * kGsU * kGsT : 1];
     Keep keep;
@@ -579,9 +612,14 @@ int gs_fused_occupancy(int ng, int m, bool keep)
 {
     const int mp = m == 0 ? 0 : (m <= 4 ? 4 : 8);
     int nb = 0;
+    // (with a keep set: the fewer of the two instantiations SPK_GS_AHEAD chooses between)
 #define SPK_GS_OCC(NG, MP)                                                                                          \
-    if (keep) SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, true>, kGsT, 0));  \
-    else SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, false>, kGsT, 0));      \
+    if (keep) {                                                                                                     \
+        int n1 = 0;                                                                                                 \
+        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, true>, kGsT, 0));        \
+        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>, kGsT, 0)); \
+        nb = std::min(nb, n1);                                                                                      \
+    } else SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, false>, kGsT, 0));    \
     break
     SPK_GS_SWITCH(ng, mp, SPK_GS_OCC)
 #undef SPK_GS_OCC
@@ -606,8 +644,13 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s)
     const int ng = (g.cnt + 7) / 8 > 0 ? (g.cnt + 7) / 8 : 1;
     const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
     gs_stamps_aim(b.loc, (int)grid, s);   // (GS_STAMPS=1 builds only)
+    // MP = 4: the loads ahead of the wait take the registers of half the planes, which parity planes leave free
+    // (KeepSet::PK); rows of B D that do not pack run the launch without them
+    const bool ahead = g.ahead && !(mp == 4 && !b.packed);
 #define SPK_GS_LAUNCH(NG, MP)                                                                                       \
-    if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);  \
+    if (g.keep && ahead)                                                                                            \
+        hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
+    else if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
     else hipLaunchKernelGGL((gs_fused_kernel<NG, MP, false>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);        \
     break
     SPK_GS_SWITCH(ng, mp, SPK_GS_LAUNCH)

@@ -431,6 +431,7 @@ struct FgmresPlan {
     bool f32;             // the basis is stored as floats (opts.basis_precision; form 5 only)
     bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
     int gs_keep;          // form 7: the first tile's operands stay on chip between its two passes (SPK_GS_KEEP=0: not, for tests)
+    int gs_ahead;         // form 7 with its keep set: a second group of basis loads is requested ahead of the totals wait (SPK_GS_AHEAD=0: not, for tests)
     int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
     int nn, bpk, form;    // norm (+ B D w') out of the last MAXPY; B D as m/2 parity planes; what is reported
     const double *bdp;    // the B D rows the kernels stream (Schur)
@@ -500,6 +501,8 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     // (the knob is read per solve, so that a test can flip it between two solves of one context)
     const char *keep_env = getenv("SPK_GS_KEEP");
     p.gs_keep = keep_env && !strcmp(keep_env, "0") ? 0 : 1;
+    const char *ahead_env = getenv("SPK_GS_AHEAD");
+    p.gs_ahead = ahead_env && !strcmp(ahead_env, "0") ? 0 : 1;   // (2 once added groups left to the L2: taken out; it runs as 1)
     p.gsf = un3 && !p.resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
             c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m, p.gs_keep != 0);
     p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
@@ -670,7 +673,7 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     if (gs) {
         k::GsArgs g{};
         g.V2 = schur ? (r.p.bpk ? c->bdpk.p : c->bd.p) : nullptr;
-        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk; g.keep = r.p.gs_keep;
+        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk; g.keep = r.p.gs_keep; g.ahead = r.p.gs_ahead;
         g.n2 = (r.N + 1) / 2; g.n_dot = r.n_dot;
         g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
         g.out = db;

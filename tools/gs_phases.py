@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase table of form 7's fused Gram-Schmidt launch (gs_fused_kernel) from a library built with `make GS_STAMPS=1`
 (csrc/spk_gs_stamps.hpp):
-    python tools/gs_phases.py [--grid 1024] [--grid-y 0] [--pc schur-full|jacobi] [--cycles 3] [--label TEXT]
+    python tools/gs_phases.py [--grid 1024] [--grid-y 0] [--pc schur-full|jacobi] [--cycles 3] [--label TEXT] [--straggler]
 Runs whole restart cycles of FGMRES(30) (rtol 0), reads the time stamps every workgroup's thread 0 took in the LAST cycle
 and prints, per position loc in the cycle, the median and the longest duration of each phase over the launch's workgroups
 (us), the skew between the first and the last workgroup at "MDot tiles done", and the launch from its first entry to its
@@ -28,6 +28,8 @@ ap.add_argument("--pc", default="schur-full", choices=["schur-full", "jacobi"])
 ap.add_argument("--restart", type=int, default=30)
 ap.add_argument("--cycles", type=int, default=3)
 ap.add_argument("--label", default="")
+ap.add_argument("--straggler", action="store_true",
+                help="per loc also: the workgroup that is last at 'MDot tiles done', its gap to the second-last and to the median")
 a = ap.parse_args()
 
 mx, my = a.grid, a.grid_y or a.grid
@@ -56,6 +58,7 @@ print("# median / max over workgroups of each phase; skew = last - first workgro
 print("loc  nv NG | " + " | ".join(f"{n:>13s}" for n in names) + " |  skew | launch")
 tot = np.zeros(len(names))
 rows = 0
+last = []   # --straggler: (loc, workgroup, XCD = workgroup % 8, gap to the second-last, gap to the median), us
 for loc in range(64):
     t = st[loc].astype(np.int64)
     live = t[:, 6] > 0
@@ -65,7 +68,11 @@ for loc in range(64):
         # a launch enqueued behind the solve's end and gated off by the device stamped its entry over this row
         print(f"{loc:3d}  (entry stamps overwritten by a gated launch behind the end of the solve)")
         continue
+    wgs = np.flatnonzero(live)
     t = t[live] / 100.0
+    if t.shape[0] > 1:
+        order = np.argsort(t[:, 2], kind="stable")
+        last.append((loc, int(wgs[order[-1]]), t[order[-1], 2] - t[order[-2], 2], t[order[-1], 2] - np.median(t[:, 2])))
     ph = np.empty((t.shape[0], 7))
     ph[:, 0] = t[:, 0] - t[:, 0].min()
     ph[:, 1:] = np.diff(t[:, :7], axis=1)
@@ -78,3 +85,11 @@ for loc in range(64):
     rows += 1
 if rows:
     print(f"sum of medians over {rows} launches: " + ", ".join(f"{n} {v:.1f}" for n, v in zip(names, tot)) + " us")
+if a.straggler and last:
+    print("# the workgroup that is last at 'MDot tiles done' (XCD = workgroup mod 8), its gap to the second-last one and to the median workgroup, us")
+    print("loc | last wg xcd | to 2nd-last | to median")
+    for loc, wg, g2, gm in last:
+        print(f"{loc:3d} | {wg:7d} {wg % 8:3d} | {g2:11.2f} | {gm:9.2f}")
+    who = np.bincount([wg for _, wg, _, _ in last], minlength=1)
+    top = np.argsort(-who, kind="stable")[:5]
+    print("most often last: " + ", ".join(f"workgroup {w} ({who[w]} of {len(last)})" for w in top if who[w]))
