@@ -672,6 +672,10 @@ int spk_pipecgrr_set_tau(spk_ctx *ctx, double tau);
  * beyond 62, MGS or CGS refinement on a fusable preconditioner report SPK_ITER_FOUR_LAUNCH: the head kernel runs);
  * *single_reduce = 1 when the single-reduction mode ran.  For byte models (bench.py). */
 int spk_get_iteration_form(const spk_ctx *ctx, int32_t *form, int32_t *single_reduce);
+/* Form 7's launches of the LAST spk_fgmres on ctx (0 where another form ran): *launches = how many were enqueued,
+ * *tail = how many of them staged a short remainder tile of VecMDot's pass in LDS instead of walking it as a tile of its
+ * own (all of them or none: the vector length decides, and SPK_GS_TAIL=0 turns it off).  Either pointer may be NULL. */
+int spk_get_gs_launch(const spk_ctx *ctx, int32_t *launches, int32_t *tail);
 /* The basis of the last spk_fgmres on this context: SPK_BASIS_* it ran with and the bytes allocated for V (restart + 2
  * vectors of ld doubles, or restart + 1 vectors of ld floats; the two FP64 work vectors of a single-precision solve are
  * not part of it).  -1 and 0 before the first solve.  Either pointer may be NULL. */

@@ -250,6 +250,7 @@ def _load():
     L.spk_get_spmv_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.spk_debug_dict_layout.argtypes = [vp, C.POINTER(i32)]
     L.spk_get_iteration_form.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.spk_get_gs_launch.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.spk_get_basis_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.spk_get_spmv_models.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]
     L.spk_time_kernel.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(dbl)]

@@ -559,6 +559,14 @@ int spk_get_iteration_form(const spk_ctx *c, int32_t *form, int32_t *single_redu
     return SPK_OK;
 }
 
+int spk_get_gs_launch(const spk_ctx *c, int32_t *launches, int32_t *tail)
+{
+    if (!c) return SPK_ERR_ARG;
+    if (launches) *launches = c->last_gs_launches;
+    if (tail) *tail = c->last_gs_tail;
+    return SPK_OK;
+}
+
 int spk_get_basis_info(const spk_ctx *c, int32_t *precision, int64_t *basis_bytes)
 {
     if (!c) return SPK_ERR_ARG;

@@ -884,6 +884,30 @@ struct KeepSet {
     }
 };
 
+// One element's step of a VecMDot sum with the contraction WRITTEN OUT: which product is fused into the FMA decides the
+// rounding, and the remainder epilogue of the fused launch (TAIL below) must round as the tile loop does, so neither
+// is left to the compiler's choice.  The forms are the ones the compiler chose for the loop before this helper existed
+// (the loop's v_mul_f64 / v_fma_f64 / v_add_f64 sequence on gfx950 is unchanged).
+__device__ __forceinline__ double mdot_step(double d, double2 a, double2 w)   // d + (a . w)
+{
+#pragma clang fp contract(off)
+    return d + __builtin_fma(w.x, a.x, w.y * a.y);
+}
+__device__ __forceinline__ double mdot_step_x(double d, double2 a, double2 w) { return __builtin_fma(w.x, a.x, d); }   // parity planes:
+__device__ __forceinline__ double mdot_step_y(double d, double2 a, double2 w) { return __builtin_fma(w.y, a.y, d); }   // one half each
+__device__ __forceinline__ double mdot_step_ww(double s, double2 w)           // s + (w . w)
+{
+#pragma clang fp contract(off)
+    return s + __builtin_fma(w.y, w.y, w.x * w.x);
+}
+
+// The short remainder tile of form 7's launch (TAIL; gs_fused_tail_kernel, SPK_GS_TAIL): at most kGsTailMax double2 behind
+// the whole tiles (at 1024^2 with the full Schur preconditioner the four multiplier entries), staged in LDS at entry
+// instead of being a tile-loop trip of their own.  kGsTailSrc sources: w~ and the <= 40 vectors or planes of one
+// reduction (GsArgs::cnt); 41 x 16 double2 = 10 496 B of the 19 776 B that LDS has free beside the keep set
+// (160 KiB - 4 x 32 KiB - 12 992 B).
+constexpr int kGsTailMax = 16, kGsTailSrc = 41;
+
 // VecMDot body (mdot_kernel, gs_fused_kernel): the workgroup's tiles (tile = blockIdx.x + k gridDim.x of T x U double2),
 // all nv dot products V_i . w in ONE pass over w (kept in registers), w.w in slot nv (with_ww); the workgroup's sums
 // are published to partials[blockIdx.x][0..nv] for the reducer.  lds: max(W (NG 8 + 1), T) doubles.
@@ -893,20 +917,51 @@ struct KeepSet {
 // FUSED (gs_fused_kernel): gate is the launch's `done` word, requested by the caller and looked at behind the first
 // tile's first loads (a gated workgroup returns true: nothing added, nothing published); the wave sums are taken by
 // wave_sum_multi (the same trees as wave_sum, which mdot_kernel keeps: forms 5 and 7 agree to the bit).
-template <int NG, int T, int G, bool NT, int U, class Keep = NoKeep, bool FUSED = false>
+// TAIL (the launcher vouches: 0 < n2 mod (T U) <= kGsTailMax, the whole tiles a multiple of the grid): the remainder
+// tile is no loop trip.  Its owner -- the workgroup the loop would give it to -- requests the remainder's entries of w~,
+// the vectors and the second slab at entry (two loads per thread), stores them to tl (kGsTailSrc x kGsTailMax double2 of
+// LDS) where the gate is looked at, and adds their products behind the loop.  That is what the trip would have added:
+// there every thread past n2 has wv = 0, so its d is a sum of +-0 and acc[i] += mk d leaves the accumulator as it is
+// (one that starts at +0.0 and only receives sums is never -0.0); for the same reason the u >= 1 terms of the live
+// threads (u T + t >= T > R) leave d's value, and a zero's sign in d is lost in acc[i] += d.  What remains per live
+// slot, in slot order, is d = 0.0 + one mdot_step and acc[i] += d, with the same n_dot masks on w~.  The kept-plane
+// path (kpl) is the first tile's; the remainder never is the first tile.
+template <int NG, int T, int G, bool NT, int U, class Keep = NoKeep, bool FUSED = false, bool TAIL = false>
 __device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t ldv, int nv,
                                            const double *__restrict__ V2, int nv1,
                                            const double *__restrict__ w, int64_t n2,
                                            int64_t n_dot, double *__restrict__ partials,
-                                           int with_ww, int split, double *lds, Keep *keep = nullptr, int32_t gate = 0)
+                                           int with_ww, int split, double *lds, Keep *keep = nullptr, int32_t gate = 0,
+                                           double2 *tl = nullptr)
 {
     constexpr int NA = NG * 8 + 1, W = T / kWave, TILE2 = T * U;
     constexpr int KW = Keep::KW, KP = Keep::KP, KV = Keep::KV;
+    static_assert(!TAIL || (FUSED && kGsTailMax < T && kGsTailSrc * kGsTailMax <= 2 * T && NG * 8 + 1 <= kGsTailSrc),
+                  "the remainder: fused launch, live in u = 0 only, two loads per thread, one source per slot and w~");
     double acc[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) acc[i] = 0.0;
 
-    for (int64_t tile = blockIdx.x; tile * TILE2 < n2; tile += gridDim.x) {
+    const int64_t ntw = n2 / TILE2;   // whole tiles
+    const int R = TAIL ? (int)(n2 - ntw * TILE2) : 0;
+    const bool own = TAIL && (int64_t)blockIdx.x == ntw % (int64_t)gridDim.x;   // workgroup-uniform
+    double2 st[2];
+    if (TAIL && own) {
+        // sources: w~, V_0 .. V_{nv1-1}, the second slab's planes (split) or rows
+        const int nsrc = 1 + nv1 + (nv > nv1 ? (split ? (nv - nv1 + 1) >> 1 : nv - nv1) : 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int q = (int)threadIdx.x + j * T, s = q / kGsTailMax, e = q % kGsTailMax;
+            st[j].x = st[j].y = 0.0;
+            if (s < nsrc && e < R) {
+                const int64_t i2 = ntw * TILE2 + e;
+                if (s == 0) st[j] = ld2(w, i2);
+                else st[j] = ld2s<NT>(s <= nv1 ? V + (size_t)(s - 1) * ldv : V2 + (size_t)(s - 1 - nv1) * ldv, i2);
+            }
+        }
+    }
+
+    for (int64_t tile = blockIdx.x; TAIL ? tile < ntw : tile * TILE2 < n2; tile += gridDim.x) {
         const bool KF = Keep::any && tile == (int64_t)blockIdx.x;   // the first tile leaves its operands behind
         const bool kpl = KF && KP > 0 && split && nv > nv1;   // this tile's planes go through the keep set
         double2 wv[U];
@@ -937,7 +992,7 @@ __device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t
             }
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc[NA - 1] += wv[u].x * wv[u].x + wv[u].y * wv[u].y;
+        for (int u = 0; u < U; ++u) acc[NA - 1] = mdot_step_ww(acc[NA - 1], wv[u]);
 #pragma unroll
         for (int g0 = 0; g0 < NG * 8; g0 += G) {
             if (g0 < nv) {  // wave-uniform
@@ -962,6 +1017,13 @@ __device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t
                     asm volatile("" : "+v"(gate));
                     if (__builtin_amdgcn_readfirstlane(gate)) return true;
                     GS_STAMP_COPY(kGsEntry, kGsEntryRaw);
+                    if (TAIL && own) {   // the remainder's entries were requested ahead of this tile's: they are back first
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int q = (int)threadIdx.x + j * T;
+                            if (q < kGsTailSrc * kGsTailMax) tl[q] = st[j];
+                        }
+                    }
                 }
 #pragma unroll
                 for (int v = 0; v < G; ++v) {
@@ -971,14 +1033,14 @@ __device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t
                     if (split && g0 + v >= nv1 && live) {  // wave-uniform
                         if ((g0 + v - nv1) & 1) {
 #pragma unroll
-                            for (int u = 0; u < U; ++u) d += a[v][u].y * wv[u].y;
+                            for (int u = 0; u < U; ++u) d = mdot_step_y(d, a[v][u], wv[u]);
                         } else {
 #pragma unroll
-                            for (int u = 0; u < U; ++u) d += a[v][u].x * wv[u].x;
+                            for (int u = 0; u < U; ++u) d = mdot_step_x(d, a[v][u], wv[u]);
                         }
                     } else {
 #pragma unroll
-                        for (int u = 0; u < U; ++u) d += a[v][u].x * wv[u].x + a[v][u].y * wv[u].y;
+                        for (int u = 0; u < U; ++u) d = mdot_step(d, a[v][u], wv[u]);
                     }
                     acc[g0 + v] += mk * d;
                 }
@@ -1004,14 +1066,39 @@ __device__ __forceinline__ bool mdot_tiles(const double *__restrict__ V, int64_t
                         double d = 0.0;
                         if (h) {
 #pragma unroll
-                            for (int u = 0; u < U; ++u) d += keep->get(KW + q, u).y * wv[u].y;
+                            for (int u = 0; u < U; ++u) d = mdot_step_y(d, keep->get(KW + q, u), wv[u]);
                         } else {
 #pragma unroll
-                            for (int u = 0; u < U; ++u) d += keep->get(KW + q, u).x * wv[u].x;
+                            for (int u = 0; u < U; ++u) d = mdot_step_x(d, keep->get(KW + q, u), wv[u]);
                         }
 #pragma unroll
                         for (int i = 0; i < NA - 1; ++i)
                             if (i == slot) acc[i] += d;
+                    }
+                }
+            }
+        }
+    }
+    if (TAIL && own) {
+        __syncthreads();   // the staged entries come from other threads (a branch the whole workgroup takes)
+        if ((int)threadIdx.x < R) {
+            const int e = threadIdx.x;
+            const int64_t i2 = ntw * TILE2 + e;
+            double2 wt = tl[e];
+            if (2 * i2 >= n_dot) wt.x = 0.0;
+            if (2 * i2 + 1 >= n_dot) wt.y = 0.0;
+            acc[NA - 1] = mdot_step_ww(acc[NA - 1], wt);
+#pragma unroll
+            for (int g0 = 0; g0 < NG * 8; g0 += G) {
+#pragma unroll
+                for (int v = 0; v < G; ++v) {
+                    if (g0 + v < nv) {  // wave-uniform: acc[] stays statically indexed
+                        const int j2 = g0 + v - nv1;
+                        const double2 a = tl[(g0 + v < nv1 ? 1 + g0 + v : 1 + nv1 + (split ? j2 >> 1 : j2)) * kGsTailMax + e];
+                        double d = 0.0;
+                        if (split && j2 >= 0) d = (j2 & 1) ? mdot_step_y(d, a, wt) : mdot_step_x(d, a, wt);
+                        else d = mdot_step(d, a, wt);
+                        acc[g0 + v] += d;
                     }
                 }
             }

@@ -701,7 +701,10 @@ struct GsArgs {
     double *tot, *tot_next;   // the armed totals line of this launch, the line it arms for the next one
     FinErr fe;
 };
-int gs_fused(IterB b, GsArgs g, hipStream_t s);
+// tail (FgmresPlan::gs_tail; the launcher's alone, no kernel argument): with keep and ahead, a short remainder tile is
+// staged in LDS where the shape allows -- gs_fused_tail says whether this launch does (gs_fused_tail_kernel)
+int gs_fused(IterB b, GsArgs g, hipStream_t s, int tail = 1);
+bool gs_fused_tail(const IterB &b, const GsArgs &g, int tail = 1);
 int gs_fused_occupancy(int ng, int m, bool keep);   // workgroups of the fused kernel (with / without its keep set) that fit one CU
 int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
 // GS_STAMPS=1 builds: the launches' phase time stamps, 64 iterations x 256 workgroups x 8 (spk_gs_stamps.hpp); false otherwise
@@ -1113,6 +1116,8 @@ struct spk_ctx {
     // how the last spk_fgmres launched its iterations (spk_get_iteration_form): SPK_ITER_* actually run, -1 for the
     // step-by-step path (PCApply and MatMult as launches of their own); single-reduction mode beside it
     int last_form = -1, last_single = 0;
+    // form 7's launches of the last spk_fgmres (spk_get_gs_launch): those that staged their remainder tile in LDS
+    int last_gs_launches = 0, last_gs_tail = 0;
 
     // Krylov workspace (sized by restart)
     int ws_restart = -1, ws_basis = -1;   // what V (or Vf and Vw) and Z are sized for

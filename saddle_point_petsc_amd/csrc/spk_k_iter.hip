@@ -601,6 +601,39 @@ __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
     maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe}, &keep);
 }
 
+// The default launch -- gs_fused_kernel<NG, MP, true, AH> line by line -- with a short remainder tile staged in LDS
+// (SPK_GS_TAIL, gs_fused_tail): the remainder behind the whole tiles, at 1024^2 with the full Schur preconditioner two
+// double2 (the multiplier entries), is requested at entry by the workgroup the tile loop would give it to and added
+// behind that workgroup's loop (mdot_tiles, TAIL), instead of costing it a trip of dependent loads while every other
+// workgroup has finished its tiles and waits for the totals.  A kernel of its own, not one more template argument: the
+// instantiations above keep their names and, to the instruction, their code.
+template <int NG, int MP, int AH>
+__global__ __launch_bounds__(kGsT) void gs_fused_tail_kernel(IterB b, GsArgs g)
+{
+    constexpr int NA = NG * 8 + 1, W = kGsT / kWave;
+    using Keep = typename GsKeep<NG, MP, AH>::type;
+    __shared__ double lds[(W * NA > kGsT) ? W * NA : kGsT];
+    __shared__ double2 klds[Keep::KL * kGsU * kGsT];
+    __shared__ double2 tlds[kGsTailSrc * kGsTailMax];
+    Keep keep;
+    keep.l = klds;
+    GS_STAMP(kGsEntryRaw);
+    if (blockIdx.x == 0 && threadIdx.x < kWave) publish(g.tot_next + threadIdx.x, __longlong_as_double((long long)kSentinelBits));
+    const int32_t dn = __builtin_nontemporal_load(b.done);   // a gated launch returns before anything is staged
+    if (mdot_tiles<NG, kGsT, kGsG, true, kGsU, Keep, true, true>(b.V, b.ldv, g.cnt, g.V2, b.nv, b.w, g.n2, g.n_dot, g.partials, 1,
+                                                                 g.split, lds, &keep, dn, tlds))
+        return;
+    if (arrive_last(gridDim.x)) {
+        const int k = g.cnt + 1;
+        final_reduce(g.partials, gridDim.x, kPartialLd, k, lds, g.fe);
+        if ((int)threadIdx.x < k) {
+            g.out[threadIdx.x] = lds[threadIdx.x];
+            publish(g.tot + threadIdx.x, lds[threadIdx.x]);
+        }
+    }
+    maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe}, &keep);
+}
+
 #define SPK_GS_SWITCH(NGV, MPV, CASE)                                                        \
     switch ((NGV) * 10 + (MPV)) {                                                           \
     case 10: CASE(1, 0); case 20: CASE(2, 0); case 30: CASE(3, 0); case 40: CASE(4, 0); case 50: CASE(5, 0); \
@@ -612,13 +645,14 @@ int gs_fused_occupancy(int ng, int m, bool keep)
 {
     const int mp = m == 0 ? 0 : (m <= 4 ? 4 : 8);
     int nb = 0;
-    // (with a keep set: the fewer of the two instantiations SPK_GS_AHEAD chooses between)
+    // (with a keep set: the fewest of the three instantiations SPK_GS_AHEAD and SPK_GS_TAIL choose between)
 #define SPK_GS_OCC(NG, MP)                                                                                          \
     if (keep) {                                                                                                     \
-        int n1 = 0;                                                                                                 \
+        int n1 = 0, n2 = 0;                                                                                         \
         SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, true>, kGsT, 0));        \
         SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>, kGsT, 0)); \
-        nb = std::min(nb, n1);                                                                                      \
+        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, gs_fused_tail_kernel<NG, MP, kGsAhead[MP / 4][NG - 1]>, kGsT, 0)); \
+        nb = std::min(nb, std::min(n1, n2));                                                                        \
     } else SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, false>, kGsT, 0));    \
     break
     SPK_GS_SWITCH(ng, mp, SPK_GS_OCC)
@@ -633,7 +667,20 @@ int64_t gs_fused_grid(int64_t nl)
     return kVecMaxBlocks;                               // >= 256 tiles of 2048 double2: both kernels' grids
 }
 
-int gs_fused(IterB b, GsArgs g, hipStream_t s)
+// Does the launch stage its remainder tile in LDS (gs_fused_tail_kernel)?  Asked for (tail), the default launch
+// (keep set and loads ahead of the wait: the one instantiation built with it), a remainder of 1 .. kGsTailMax double2,
+// and whole tiles that are a multiple of the grid -- so that the remainder would be a trip of its own beyond every
+// workgroup's whole tiles.  Any other shape keeps the loop trip.
+bool gs_fused_tail(const IterB &b, const GsArgs &g, int tail)
+{
+    const int64_t grid = gs_fused_grid(b.nl), tile2 = (int64_t)kGsT * kGsU;
+    const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+    if (!grid || !tail || !g.keep || !g.ahead || (mp == 4 && !b.packed)) return false;
+    const int64_t whole = g.n2 / tile2, rem = g.n2 % tile2;
+    return rem > 0 && rem <= kGsTailMax && whole >= grid && whole % grid == 0;
+}
+
+int gs_fused(IterB b, GsArgs g, hipStream_t s, int tail)
 {
     const int64_t grid = gs_fused_grid(b.nl);
     const VecShape vs = vec_shape(g.n2);
@@ -647,8 +694,11 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s)
     // MP = 4: the loads ahead of the wait take the registers of half the planes, which parity planes leave free
     // (KeepSet::PK); rows of B D that do not pack run the launch without them
     const bool ahead = g.ahead && !(mp == 4 && !b.packed);
+    const bool staged = gs_fused_tail(b, g, tail);
 #define SPK_GS_LAUNCH(NG, MP)                                                                                       \
-    if (g.keep && ahead)                                                                                            \
+    if (staged)                                                                                                     \
+        hipLaunchKernelGGL((gs_fused_tail_kernel<NG, MP, kGsAhead[MP / 4][NG - 1]>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
+    else if (g.keep && ahead)                                                                                       \
         hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
     else if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
     else hipLaunchKernelGGL((gs_fused_kernel<NG, MP, false>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);        \

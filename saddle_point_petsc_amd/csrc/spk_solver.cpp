@@ -432,6 +432,7 @@ struct FgmresPlan {
     bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
     int gs_keep;          // form 7: the first tile's operands stay on chip between its two passes (SPK_GS_KEEP=0: not, for tests)
     int gs_ahead;         // form 7 with its keep set: a second group of basis loads is requested ahead of the totals wait (SPK_GS_AHEAD=0: not, for tests)
+    int gs_tail;          // form 7's default launch: a short remainder tile is staged in LDS at entry instead of being a tile-loop trip (SPK_GS_TAIL=0: not, for tests)
     int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
     int nn, bpk, form;    // norm (+ B D w') out of the last MAXPY; B D as m/2 parity planes; what is reported
     const double *bdp;    // the B D rows the kernels stream (Schur)
@@ -503,6 +504,8 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     p.gs_keep = keep_env && !strcmp(keep_env, "0") ? 0 : 1;
     const char *ahead_env = getenv("SPK_GS_AHEAD");
     p.gs_ahead = ahead_env && !strcmp(ahead_env, "0") ? 0 : 1;   // (2 once added groups left to the L2: taken out; it runs as 1)
+    const char *tail_env = getenv("SPK_GS_TAIL");
+    p.gs_tail = tail_env && !strcmp(tail_env, "0") ? 0 : 1;
     p.gsf = un3 && !p.resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
             c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m, p.gs_keep != 0);
     p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
@@ -680,7 +683,9 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
         g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
         g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
         g.fe = k::FinErr{c->errw.p, c->fin_ticks};
-        fin_n = k::gs_fused(b, g, r.s);
+        fin_n = k::gs_fused(b, g, r.s, r.p.gs_tail);
+        ++c->last_gs_launches;
+        if (k::gs_fused_tail(b, g, r.p.gs_tail)) ++c->last_gs_tail;
         ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
     } else {
         fin_n = k::iter_maxpy_uhead(b, r.s);
@@ -798,6 +803,7 @@ void fgmres(spk_ctx *c, const double *b, double *x, const spk_opts &o, spk_resul
     const FgmresPlan p = plan_fgmres(c, o);   // (refuses before anything is allocated or enqueued)
     ensure_krylov(c, o);
     c->last_form = p.form;
+    c->last_gs_launches = c->last_gs_tail = 0;
     c->last_basis = o.basis_precision;
     c->last_basis_bytes = p.f32 ? (int64_t)(c->Vf.n * sizeof(float)) : (int64_t)(c->V.n * sizeof(double));
     c->last_single = p.orth == FgmresPlan::kOrthSingle ? 1 : 0;

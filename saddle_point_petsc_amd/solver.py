@@ -752,6 +752,13 @@ class Context:
         self._chk(lib.spk_get_iteration_form(self.h, C.byref(f), C.byref(sr)))
         return f.value, sr.value
 
+    def gs_launch(self):
+        """(launches, tail) of the last fgmres on this context: form 7's launches, and those of them that staged a short
+        remainder tile in LDS (SPK_GS_TAIL; all or none)."""
+        n, t = C.c_int32(), C.c_int32()
+        self._chk(lib.spk_get_gs_launch(self.h, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
     def basis_info(self):
         """(precision, basis_bytes) of the last fgmres on this context: "double" / "single" (None before the first solve)
         and the bytes allocated for the basis V."""

@@ -52,7 +52,7 @@ def cycles(seq):
 def fused(rs, value):
     seq = []
     for r in sorted(rs, key=lambda r: int(r["Dispatch_Id"])):
-        m = re.search(r"gs_fused_kernel<(\d)", r["Kernel_Name"])
+        m = re.search(r"gs_fused(?:_tail)?_kernel<(\d)", r["Kernel_Name"])
         if m:
             seq.append((int(m.group(1)), value(r)))
     return cycles(seq)
