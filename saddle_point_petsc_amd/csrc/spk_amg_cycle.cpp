@@ -6,7 +6,10 @@
 // level's flag, which amg_plan_cycle sets; the hierarchy is untouched.
 // -spk_mg_precision single (SPK_AMG_PRECISION_SINGLE) runs the levels >= 1 of that route in FP32: their vectors are float,
 // their values, D^-1, coefficients and the coarse inverse FP32 copies rounded here behind every set-up (amg_round_levels);
-// level 0 and the hierarchy stay FP64, and the transfers of level 0 cross the boundary.
+// level 0 and the hierarchy stay FP64, and the transfers of level 0 cross the boundary.  The walk, the tail's descriptor
+// and the test hooks are written once over the scalar type T of a level's vectors: AmgLevelDev::view<T>() gives what a
+// level holds in T.  The CSR operators and the stored transfers exist in FP64 alone (amg_check_opts plans no other), so
+// their branches stand under `if constexpr`.
 // Every step is deterministic: two cycles on the same hierarchy and vector give the same bytes.
 #include <cstring>
 
@@ -14,6 +17,9 @@
 #include "spk_internal.hpp"
 
 namespace spk {
+
+template <typename T>
+constexpr bool is_f64 = std::is_same<T, double>::value;
 
 // the V-cycle's vectors; level 0 takes the context's padded length, as the layouts' products want them.  Both callers
 // pass c->ld, the device build even before pc_setup's own ensure_vectors: every set_block ends in ensure_vectors and
@@ -28,12 +34,12 @@ void alloc_cycle_vectors(AmgDev &d, int64_t ld, bool single)
         const size_t nv = l == 0 ? (size_t)ld : (size_t)D.n;
         if (l > 0 && single) {
             D.b.release(), D.ya.release(), D.yb.release();
-            D.b32.alloc(nv, 8);
-            D.ya32.alloc(nv, 16);
-            D.yb32.alloc(nv, 16);
+            D.f32.b.alloc(nv, 8);
+            D.f32.ya.alloc(nv, 16);
+            D.f32.yb.alloc(nv, 16);
             continue;
         }
-        D.b32.release(), D.ya32.release(), D.yb32.release();
+        D.f32.b.release(), D.f32.ya.release(), D.f32.yb.release();
         if (l > 0) D.b.alloc(nv, 8);
         D.ya.alloc(nv, 16);
         D.yb.alloc(nv, 16);
@@ -49,21 +55,60 @@ static void amg_round_levels(AmgDev &d, hipStream_t s)
     const size_t L = d.lv.size();
     for (size_t l = 1; l < L; ++l) {
         AmgLevelDev &D = d.lv[l];
+        AmgLevelDev::F32 &F = D.f32;
         if (!d.single) {
-            D.val32.release(), D.dinv32.release();
+            F.val.release(), F.dinv.release();
             continue;
         }
-        if (D.val32.n != (size_t)D.A.nnz || !D.val32.p) D.val32.alloc_raw((size_t)D.A.nnz, 4);
-        if (D.dinv32.n != (size_t)D.n || !D.dinv32.p) D.dinv32.alloc_raw((size_t)D.n, 4);
-        k::amg_round_f32(D.A.nnz, D.A.val.p, D.val32.p, s);
-        k::amg_round_f32(D.n, D.dinv.p, D.dinv32.p, s);
-        D.alpha32.assign(D.alpha.begin(), D.alpha.end());   // (double -> float: round to nearest)
-        D.beta32.assign(D.beta.begin(), D.beta.end());
+        if (F.val.n != (size_t)D.A.nnz || !F.val.p) F.val.alloc_raw((size_t)D.A.nnz, 4);
+        if (F.dinv.n != (size_t)D.n || !F.dinv.p) F.dinv.alloc_raw((size_t)D.n, 4);
+        k::amg_round_f32(D.A.nnz, D.A.val.p, F.val.p, s);
+        k::amg_round_f32(D.n, D.dinv.p, F.dinv.p, s);
+        F.alpha.assign(D.alpha.begin(), D.alpha.end());   // (double -> float: round to nearest)
+        F.beta.assign(D.beta.begin(), D.beta.end());
     }
-    if (!d.single) return d.cinv32.release();
-    if (d.cinv32.n != d.cinv.n || !d.cinv32.p) d.cinv32.alloc_raw(d.cinv.n, 4);
-    k::amg_round_f32((int64_t)d.cinv.n, d.cinv.p, d.cinv32.p, s);
+    if (!d.single) return d.f32.cinv.release();
+    if (d.f32.cinv.n != d.cinv.n || !d.f32.cinv.p) d.f32.cinv.alloc_raw(d.cinv.n, 4);
+    k::amg_round_f32((int64_t)d.cinv.n, d.cinv.p, d.f32.cinv.p, s);
     SPK_HIP(hipStreamSynchronize(s));
+}
+
+// the tail kernel's descriptor over the levels >= t in T.  float: the tail over the float buffers -- stencil levels and
+// matrix-free transfers only (amg_check_opts), the index arrays are not read
+template <typename T>
+static void fill_tail_desc(AmgDev &d, int t, int nu)
+{
+    const int L = (int)d.lv.size();
+    auto desc = std::make_unique<k::AmgTailDescT<T>>();
+    std::memset(desc.get(), 0, sizeof *desc);
+    desc->cinv = d.coarse_inv<T>().p;
+    desc->steps = d.tail_steps.p;
+    desc->first = t;
+    desc->levels = L;
+    for (int l = t; l < L; ++l) {
+        AmgLevelDev &D = d.lv[(size_t)l];
+        const AmgLevelView<T> W = D.view<T>();
+        k::AmgTailLevelT<T> &V = desc->lv[l];
+        if constexpr (is_f64<T>) V.arp = D.A.rowptr.p, V.aci = D.A.colidx.p;
+        V.av = W.val, V.dinv = W.dinv;
+        V.b = W.b, V.ya = W.ya, V.yb = W.yb;
+        V.n = D.n;
+        V.nu = nu;
+        if (l + 1 == L) continue;
+        V.nc = d.lv[(size_t)l + 1].n;
+        V.matrix_free = V.stencil = 1;
+        if constexpr (is_f64<T>) {
+            V.prp = D.P.rowptr.p, V.pci = D.P.colidx.p, V.pv = D.P.val.p;
+            V.rrp = D.R.rowptr.p, V.rci = D.R.colidx.p, V.rv = D.R.val.p;
+            V.matrix_free = D.grid.matrix_free ? 1 : 0;
+            V.stencil = D.stencil_op ? 1 : 0;
+        }
+        d.tail_stencil = d.tail_stencil || V.stencil;
+        if (D.grid.on) std::memcpy(V.nd, D.grid.fd, sizeof V.nd);
+        if (D.grid.on) V.g = k::grid_args(D.grid), V.bs = D.grid.bs, V.fz = D.grid.fd[2];
+        for (int q = 0; q < nu; ++q) V.alpha[q] = W.alpha[(size_t)q], V.beta[q] = W.beta[(size_t)q];
+    }
+    d.tail<T>().upload(desc.get(), 1);
 }
 
 // The application's plan, rebuilt at every set-up (build or refresh) from the options and the levels as they are now:
@@ -84,7 +129,7 @@ void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o, int64_t ld, hipStream_t s)
     d.tsteps.clear();
     d.tail_stencil = false;
     if (t < 0 || d.single) d.tail_desc.release();
-    if (t < 0 || !d.single) d.tail_desc32.release();
+    if (t < 0 || !d.single) d.f32.tail_desc.release();
     if (t < 0) {
         d.tail_steps.release();
         return;
@@ -95,61 +140,21 @@ void amg_plan_cycle(AmgDev &d, const spk_amg_opts &o, int64_t ld, hipStream_t s)
     for (size_t i = 0; i < d.steps.size(); ++i) d.tsteps[i] = k::AmgTailStep{d.steps[i].kind, d.steps[i].level, buf.sel[i], buf.sel_next[i]};
     d.run_sel = std::move(buf.run_sel);
     d.tail_steps.upload(d.tsteps.data(), d.tsteps.size());
-    if (d.single) {   // the tail over the float buffers: stencil levels and matrix-free transfers only (amg_check_opts)
-        auto desc = std::make_unique<k::AmgTailDescF32>();
-        std::memset(desc.get(), 0, sizeof *desc);
-        desc->cinv = d.cinv32.p;
-        desc->steps = d.tail_steps.p;
-        desc->first = t;
-        desc->levels = L;
-        for (int l = t; l < L; ++l) {
-            AmgLevelDev &D = d.lv[(size_t)l];
-            k::AmgTailLevelT<float> &V = desc->lv[l];
-            V.av = D.val32.p, V.dinv = D.dinv32.p;
-            V.b = D.b32.p, V.ya = D.ya32.p, V.yb = D.yb32.p;
-            V.n = D.n;
-            V.nu = nu;
-            if (l + 1 == L) continue;
-            V.nc = d.lv[(size_t)l + 1].n;
-            V.matrix_free = 1, V.stencil = 1;
-            d.tail_stencil = true;
-            std::memcpy(V.nd, D.grid.fd, sizeof V.nd);
-            V.g = k::grid_args(D.grid), V.bs = D.grid.bs, V.fz = D.grid.fd[2];
-            for (int q = 0; q < nu; ++q) V.alpha[q] = D.alpha32[(size_t)q], V.beta[q] = D.beta32[(size_t)q];
-        }
-        d.tail_desc32.upload(desc.get(), 1);
-        return;
-    }
-    auto desc = std::make_unique<k::AmgTailDesc>();
-    std::memset(desc.get(), 0, sizeof *desc);
-    desc->cinv = d.cinv.p;
-    desc->steps = d.tail_steps.p;
-    desc->first = t;
-    desc->levels = L;
-    for (int l = t; l < L; ++l) {
-        AmgLevelDev &D = d.lv[(size_t)l];
-        k::AmgTailLevel &V = desc->lv[l];
-        V.arp = D.A.rowptr.p, V.aci = D.A.colidx.p, V.av = D.A.val.p;
-        V.dinv = D.dinv.p;
-        V.b = D.b.p, V.ya = D.ya.p, V.yb = D.yb.p;
-        V.n = D.n;
-        V.nu = nu;
-        if (l + 1 == L) continue;
-        V.nc = d.lv[(size_t)l + 1].n;
-        V.prp = D.P.rowptr.p, V.pci = D.P.colidx.p, V.pv = D.P.val.p;
-        V.rrp = D.R.rowptr.p, V.rci = D.R.colidx.p, V.rv = D.R.val.p;
-        V.matrix_free = D.grid.matrix_free ? 1 : 0;
-        V.stencil = D.stencil_op ? 1 : 0;
-        d.tail_stencil = d.tail_stencil || D.stencil_op;
-        if (D.grid.on) std::memcpy(V.nd, D.grid.fd, sizeof V.nd);
-        if (D.grid.on) V.g = k::grid_args(D.grid), V.bs = D.grid.bs, V.fz = D.grid.fd[2];
-        for (int q = 0; q < nu; ++q) V.alpha[q] = D.alpha[(size_t)q], V.beta[q] = D.beta[(size_t)q];
-    }
-    d.tail_desc.upload(desc.get(), 1);
+    if (d.single) fill_tail_desc<float>(d, t, nu);
+    else fill_tail_desc<double>(d, t, nu);
 }
 
-// the test hook of the transfers: one launch on copies of the caller's vectors
-void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out)
+// the FP32 hooks run the kernels of SPK_AMG_PRECISION_SINGLE on the copies it made
+static void need_single(const AmgDev &d, const char *hook)
+{
+    if (!d.single) fail(SPK_ERR_STATE, "amg: %s: the hierarchy was not built with -spk_mg_precision single", hook);
+}
+
+// the test hook of the transfers: one launch on copies of the caller's vectors, TF the scalar type on the fine side of the
+// transfer and TC on the coarse side.  which 0: out = y + P e on copies of e (nc entries) and y (fine_len), in place on
+// the copy of y;  which 1: out = R (b - t)
+template <typename TF, typename TC>
+static void debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const void *a, const void *b, void *out)
 {
     AmgDev &d = *c->amg_d;
     if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no transfer", l);
@@ -159,26 +164,38 @@ void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_l
     if (fine_len < nf) fail(SPK_ERR_ARG, "amg: transfer hook: %lld entries for the %lld rows of level %d", (long long)fine_len, (long long)nf, l);
     if (!stored && !D.grid.on) fail(SPK_ERR_STATE, "amg: level %d was not built by the grid rule: it has no matrix-free transfer", l);
     hipStream_t s = c->stream;
-    DevBuf<double> da, db, dout;
-    const int64_t na = which == 0 ? nc : fine_len, nb = fine_len, no = which == 0 ? fine_len : nc;
-    da.upload(a, (size_t)na, 16);
-    db.upload(b, (size_t)nb, 16);
-    if (which == 0) {   // out = y + P e, in place on the copy of y
-        if (stored) k::amg_prolong_add(D.P, da.p, db.p, nullptr, s);
-        else k::amg_prolong_add_grid(D.grid, da.p, db.p, nullptr, s);
-        SPK_HIP(hipMemcpyAsync(out, db.p, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, s));
-    } else {
-        dout.alloc((size_t)no, 16);
-        if (stored) k::amg_restrict(D.R, da.p, db.p, dout.p, nullptr, s);
-        else k::amg_restrict_grid(D.grid, da.p, db.p, dout.p, nullptr, s);
-        SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, s));
+    DevBuf<TF> fa, fb;   // the copies of a and b where they are fine vectors
+    DevBuf<TC> co;       // the coarse vector: the copy of a (e), or the restriction's result
+    fb.upload(static_cast<const TF *>(b), (size_t)fine_len, 16);
+    if (which == 0) {    // a: e, b: y
+        co.upload(static_cast<const TC *>(a), (size_t)nc, 16);
+        if (!stored) k::amg_prolong_add_grid(D.grid, co.p, fb.p, nullptr, s);
+        else if constexpr (is_f64<TC>) k::amg_prolong_add(D.P, co.p, fb.p, nullptr, s);
+        SPK_HIP(hipMemcpyAsync(out, fb.p, sizeof(TF) * (size_t)fine_len, hipMemcpyDeviceToHost, s));
+    } else {             // a: b, b: t
+        fa.upload(static_cast<const TF *>(a), (size_t)fine_len, 16);
+        co.alloc((size_t)nc, 16);
+        if (!stored) k::amg_restrict_grid(D.grid, fa.p, fb.p, co.p, nullptr, s);
+        else if constexpr (is_f64<TC>) k::amg_restrict(D.R, fa.p, fb.p, co.p, nullptr, s);
+        SPK_HIP(hipMemcpyAsync(out, co.p, sizeof(TC) * (size_t)nc, hipMemcpyDeviceToHost, s));
     }
     SPK_HIP(hipStreamSynchronize(s));
 }
+void amg_debug_transfer(spk_ctx *c, int l, int which, int stored, int64_t fine_len, const double *a, const double *b, double *out)
+{
+    debug_transfer<double, double>(c, l, which, stored, fine_len, a, b, out);
+}
+void amg_debug_transfer_f32(spk_ctx *c, int l, int which, int64_t fine_len, const void *a, const void *b, void *out)
+{
+    need_single(*c->amg_d, "transfer hook");
+    if (l > 0) debug_transfer<float, float>(c, l, which, 0, fine_len, a, b, out);
+    else debug_transfer<double, float>(c, l, which, 0, fine_len, a, b, out);   // the boundary: level 0 is FP64
+    c->check_device_error();
+}
 
 // the test hook of the level operators: one launch of either route on copies of the caller's vectors
-void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
-                        const double *b, double *out)
+template <typename T>
+static void debug_operator(spk_ctx *c, int l, int which, int stencil, T alpha, T beta, const T *x, const T *xo, const T *b, T *out)
 {
     AmgDev &d = *c->amg_d;
     if (l < 1 || l + 1 >= (int)d.lv.size())
@@ -190,7 +207,7 @@ void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha,
     hipStream_t s = c->stream;
     const size_t n = (size_t)D.n;
     const bool step = which & 1, gated = which >= 2;
-    DevBuf<double> dx, dxo, db, dout;
+    DevBuf<T> dx, dxo, db, dout;
     DevBuf<int32_t> gate;
     dx.upload(x, n, 16);
     if (step) db.upload(b, n, 16);
@@ -203,88 +220,27 @@ void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha,
         dout.alloc(n, 16);
     }
     const int32_t *done = gated ? gate.p : nullptr;
-    const double *yo = step && xo ? dxo.p : nullptr;
-    if (stencil) k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, step ? 1 : 0, dx.p, D.dinv.p, db.p, yo, dout.p, alpha, beta, done, s);
-    else if (step) k::amg_cheb_csr(D.A, D.dinv.p, db.p, dx.p, yo, dout.p, alpha, beta, done, s);
-    else k::amg_spmv(D.A, dx.p, dout.p, done, s);
-    SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    const T *yo = step && xo ? dxo.p : nullptr;
+    const AmgLevelView<T> V = D.view<T>();
+    if (stencil) k::amg_stencil_op(D.n, V.val, D.grid.fd, D.grid.bs, step ? 1 : 0, dx.p, V.dinv, db.p, yo, dout.p, alpha, beta, done, s);
+    else if constexpr (is_f64<T>) {
+        if (step) k::amg_cheb_csr(D.A, V.dinv, db.p, dx.p, yo, dout.p, alpha, beta, done, s);
+        else k::amg_spmv(D.A, dx.p, dout.p, done, s);
+    }
+    SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost, s));
     SPK_HIP(hipStreamSynchronize(s));
     c->check_device_error();
 }
-
-// the two hooks on the FP32 kernels of SPK_AMG_PRECISION_SINGLE
-static void need_single(const AmgDev &d, const char *hook)
+void amg_debug_operator(spk_ctx *c, int l, int which, int stencil, double alpha, double beta, const double *x, const double *xo,
+                        const double *b, double *out)
 {
-    if (!d.single) fail(SPK_ERR_STATE, "amg: %s: the hierarchy was not built with -spk_mg_precision single", hook);
-}
-// out = y + P e on copies of e (nc entries) and y (fine_len), in place on the copy of y;  out = R (b - t)
-template <typename TE, typename TY>
-static void prolong32(spk_ctx *c, const AmgLevelDev &D, int64_t nc, int64_t fine_len, const void *e, const void *y, void *out)
-{
-    DevBuf<TE> de;
-    DevBuf<TY> dy;
-    de.upload(static_cast<const TE *>(e), (size_t)nc, 16);
-    dy.upload(static_cast<const TY *>(y), (size_t)fine_len, 16);
-    k::amg_prolong_add_grid(D.grid, de.p, dy.p, nullptr, c->stream);
-    SPK_HIP(hipMemcpyAsync(out, dy.p, sizeof(TY) * (size_t)fine_len, hipMemcpyDeviceToHost, c->stream));
-    SPK_HIP(hipStreamSynchronize(c->stream));
-}
-template <typename TI>
-static void restrict32(spk_ctx *c, const AmgLevelDev &D, int64_t nc, int64_t fine_len, const void *b, const void *t, void *out)
-{
-    DevBuf<TI> db, dt;
-    DevBuf<float> dout;
-    db.upload(static_cast<const TI *>(b), (size_t)fine_len, 16);
-    dt.upload(static_cast<const TI *>(t), (size_t)fine_len, 16);
-    dout.alloc((size_t)nc, 16);
-    k::amg_restrict_grid(D.grid, db.p, dt.p, dout.p, nullptr, c->stream);
-    SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
-    SPK_HIP(hipStreamSynchronize(c->stream));
-}
-void amg_debug_transfer_f32(spk_ctx *c, int l, int which, int64_t fine_len, const void *a, const void *b, void *out)
-{
-    AmgDev &d = *c->amg_d;
-    need_single(d, "transfer hook");
-    if (l < 0 || l + 1 >= (int)d.lv.size()) fail(SPK_ERR_ARG, "amg: level %d has no transfer", l);
-    if (which != 0 && which != 1) fail(SPK_ERR_ARG, "amg: transfer hook: which is 0 or 1");
-    AmgLevelDev &D = d.lv[(size_t)l];
-    const int64_t nf = D.n, nc = d.lv[(size_t)l + 1].n;
-    if (fine_len < nf) fail(SPK_ERR_ARG, "amg: transfer hook: %lld entries for the %lld rows of level %d", (long long)fine_len, (long long)nf, l);
-    if (which == 0 && l > 0) prolong32<float, float>(c, D, nc, fine_len, a, b, out);
-    else if (which == 0) prolong32<float, double>(c, D, nc, fine_len, a, b, out);
-    else if (l > 0) restrict32<float>(c, D, nc, fine_len, a, b, out);
-    else restrict32<double>(c, D, nc, fine_len, a, b, out);
-    c->check_device_error();
+    debug_operator<double>(c, l, which, stencil, alpha, beta, x, xo, b, out);
 }
 void amg_debug_operator_f32(spk_ctx *c, int l, int which, float alpha, float beta, const float *x, const float *xo, const float *b,
                             float *out)
 {
-    AmgDev &d = *c->amg_d;
-    need_single(d, "operator hook");
-    if (l < 1 || l + 1 >= (int)d.lv.size())
-        fail(SPK_ERR_ARG, "amg: operator hook: level %d is not between level 0 and the coarsest level %d", l, (int)d.lv.size() - 1);
-    if (which < 0 || which > 3) fail(SPK_ERR_ARG, "amg: operator hook: which is 0..3");
-    AmgLevelDev &D = d.lv[(size_t)l];
-    hipStream_t s = c->stream;
-    const size_t n = (size_t)D.n;
-    const bool step = which & 1, gated = which >= 2;
-    DevBuf<float> dx, dxo, db, dout;
-    DevBuf<int32_t> gate;
-    dx.upload(x, n, 16);
-    if (step) db.upload(b, n, 16);
-    if (step && xo) dxo.upload(xo, n, 16);
-    if (gated) {
-        const int32_t one = 1;
-        gate.upload(&one, 1);
-        dout.upload(out, n, 16);
-    } else {
-        dout.alloc(n, 16);
-    }
-    k::amg_stencil_op(D.n, D.val32.p, D.grid.fd, D.grid.bs, step ? 1 : 0, dx.p, D.dinv32.p, db.p, step && xo ? dxo.p : nullptr, dout.p,
-                      alpha, beta, gated ? gate.p : nullptr, s);
-    SPK_HIP(hipMemcpyAsync(out, dout.p, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-    SPK_HIP(hipStreamSynchronize(s));
-    c->check_device_error();
+    need_single(*c->amg_d, "operator hook");
+    debug_operator<float>(c, l, which, 1, alpha, beta, x, xo, b, out);   // (the FP32 levels are stencil levels)
 }
 
 // the fine level's product runs in the row-type 2x2 layout (what a_mult takes for it) on one rank
@@ -295,27 +251,37 @@ static bool fused_fine(const spk_ctx *c)
     return c->spmv_format != 0 && c->Adict.ok && c->Adict.bs == 2 && c->n_ghost == 0 && c->n_local % 2 == 0;
 }
 
-// nu smoothing steps on level l from *y (nullptr: the zero guess); returns the buffer holding the result.  Which buffer
-// that is follows the rule amg_cycle_buffers (spk_host.cpp) states for the tail kernel: each step writes the buffer its
-// input is not in, the zero guess writes ya
-static double *smooth(spk_ctx *c, AmgLevelDev &D, int l, const double *b, double *y, const int32_t *done)
+// one smoothing step on level 0, FP64 on every route: from y (nullptr: the zero guess) and the iterate before it into dst
+static void smooth_fine(spk_ctx *c, AmgLevelDev &D, const double *b, const double *y, const double *prev, double *dst, double alpha,
+                        double beta, const int32_t *done)
+{
+    if (y && fused_fine(c)) {   // the 2x2 row-type layout: product and step in one pass
+        k::amg_cheb_dict2(c->Adict, c->dinv.p, b, y, prev, dst, alpha, beta, done, c->stream);
+    } else {                    // other layouts: the layout's own product, then a vector pass
+        if (y) a_mult(c, y, D.t.p, nullptr, nullptr, done, false, nullptr);
+        k::amg_cheb_vec(D.n, c->dinv.p, b, D.t.p, y, prev, dst, alpha, beta, done, c->stream);
+    }
+}
+
+// nu smoothing steps on level l, whose vectors are T, from *y (nullptr: the zero guess); returns the buffer holding the
+// result.  Which buffer that is follows the rule amg_cycle_buffers (spk_host.cpp) states for the tail kernel: each step
+// writes the buffer its input is not in, the zero guess writes ya
+template <typename T>
+static T *smooth(spk_ctx *c, AmgLevelDev &D, size_t l, const T *b, T *y, const int32_t *done)
 {
     hipStream_t s = c->stream;
-    const double *dinv = l == 0 ? c->dinv.p : D.dinv.p;
-    const double *prev = nullptr;   // the iterate before y (nullptr: zero)
-    for (size_t k = 0; k < D.alpha.size(); ++k) {
-        double *dst = y == D.ya.p ? D.yb.p : D.ya.p;   // may be `prev`: each entry is read before it is written
-        if (l == 0 && y && fused_fine(c)) {   // the 2x2 row-type layout: product and step in one pass
-            k::amg_cheb_dict2(c->Adict, dinv, b, y, prev, dst, D.alpha[k], D.beta[k], done, s);
-        } else if (l == 0) {                   // other layouts: the layout's own product, then a vector pass
-            if (y) a_mult(c, y, D.t.p, nullptr, nullptr, done, false, nullptr);
-            k::amg_cheb_vec(D.n, dinv, b, D.t.p, y, prev, dst, D.alpha[k], D.beta[k], done, s);
+    const AmgLevelView<T> V = D.view<T>();
+    const T *prev = nullptr;   // the iterate before y (nullptr: zero)
+    for (size_t k = 0; k < V.alpha.size(); ++k) {
+        T *dst = y == V.ya ? V.yb : V.ya;   // may be `prev`: each entry is read before it is written
+        if (l == 0) {
+            if constexpr (is_f64<T>) smooth_fine(c, D, b, y, prev, dst, V.alpha[k], V.beta[k], done);
         } else if (y && D.stencil_op) {
-            k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, 1, y, dinv, b, prev, dst, D.alpha[k], D.beta[k], done, s);
+            k::amg_stencil_op(D.n, V.val, D.grid.fd, D.grid.bs, 1, y, V.dinv, b, prev, dst, V.alpha[k], V.beta[k], done, s);
         } else if (y) {
-            k::amg_cheb_csr(D.A, dinv, b, y, prev, dst, D.alpha[k], D.beta[k], done, s);
+            if constexpr (is_f64<T>) k::amg_cheb_csr(D.A, V.dinv, b, y, prev, dst, V.alpha[k], V.beta[k], done, s);
         } else {
-            k::amg_cheb_vec(D.n, dinv, b, nullptr, nullptr, nullptr, dst, D.alpha[k], 0.0, done, s);
+            k::amg_cheb_vec(D.n, V.dinv, b, nullptr, nullptr, nullptr, dst, V.alpha[k], T(0), done, s);
         }
         prev = y;
         y = dst;
@@ -323,99 +289,76 @@ static double *smooth(spk_ctx *c, AmgLevelDev &D, int l, const double *b, double
     return y;
 }
 
-// smooth() on a level >= 1 under SPK_AMG_PRECISION_SINGLE: every such level below the coarsest is a stencil level
-static float *smooth32(spk_ctx *c, AmgLevelDev &D, float *y, const int32_t *done)
+// One step of the cycle on level st.level, whose vectors are T and those of the level below it TN (level 0 under
+// SPK_AMG_PRECISION_SINGLE: double and float, so that its DOWN rounds once on the store -- FP64 sums -- and its UP widens
+// e and adds in FP64; the overloads of the grid transfers resolve it).  b: the level's right-hand side, y: its iterate,
+// yn: the iterate of the level below
+template <typename T, typename TN>
+static void step(spk_ctx *c, AmgDev &d, const AmgStep &st, const T *b, T *&y, const TN *yn, const int32_t *done)
 {
     hipStream_t s = c->stream;
-    const float *prev = nullptr;
-    for (size_t k = 0; k < D.alpha32.size(); ++k) {
-        float *dst = y == D.ya32.p ? D.yb32.p : D.ya32.p;
-        if (y) k::amg_stencil_op(D.n, D.val32.p, D.grid.fd, D.grid.bs, 1, y, D.dinv32.p, D.b32.p, prev, dst, D.alpha32[k], D.beta32[k], done, s);
-        else k::amg_cheb_vec0(D.n, D.dinv32.p, D.b32.p, dst, D.alpha32[k], done, s);
-        prev = y;
-        y = dst;
-    }
-    return y;
-}
-
-// one step of the cycle on level l >= 1 in FP32 (amg_apply's switch on float buffers; cur: the levels' iterates)
-static void step32(spk_ctx *c, AmgDev &d, int kind, size_t l, std::vector<float *> &cur, const int32_t *done)
-{
-    hipStream_t s = c->stream;
+    const size_t l = (size_t)st.level;
     AmgLevelDev &D = d.lv[l];
-    switch (kind) {
-    case SPK_AMG_STEP_PRE0: cur[l] = smooth32(c, D, nullptr, done); break;
+    const AmgLevelView<T> V = D.view<T>();
+    switch (st.kind) {
+    case SPK_AMG_STEP_PRE0: y = smooth<T>(c, D, l, b, nullptr, done); break;
     case SPK_AMG_STEP_PRE:
-    case SPK_AMG_STEP_POST: cur[l] = smooth32(c, D, cur[l], done); break;
-    case SPK_AMG_STEP_DOWN: {
-        float *o = D.ya32.p == cur[l] ? D.yb32.p : D.ya32.p;
-        k::amg_stencil_op(D.n, D.val32.p, D.grid.fd, D.grid.bs, 0, cur[l], nullptr, nullptr, nullptr, o, 0.0f, 0.0f, done, s);
-        k::amg_restrict_grid(D.grid, D.b32.p, o, d.lv[l + 1].b32.p, done, s);
+    case SPK_AMG_STEP_POST: y = smooth<T>(c, D, l, b, y, done); break;
+    case SPK_AMG_STEP_DOWN: {   // residual, restriction
+        T *t = V.ya == y ? V.yb : V.ya;   // A y: in the buffer y is not in; level 0 has one of its own
+        if (l == 0) {
+            if constexpr (is_f64<T>) a_mult(c, y, t = D.t.p, nullptr, nullptr, done, false, nullptr);
+        } else if (D.stencil_op) {
+            k::amg_stencil_op(D.n, V.val, D.grid.fd, D.grid.bs, 0, y, nullptr, nullptr, nullptr, t, T(0), T(0), done, s);
+        } else if constexpr (is_f64<T>) {
+            k::amg_spmv(D.A, y, t, done, s);
+        }
+        TN *bn = d.lv[l + 1].view<TN>().b;
+        if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, b, t, bn, done, s);
+        else if constexpr (is_f64<TN>) k::amg_restrict(D.R, b, t, bn, done, s);
         break;
     }
-    case SPK_AMG_STEP_COARSE:
-        k::amg_dense(d.cinv32.p, D.n, D.b32.p, D.ya32.p, done, s);
-        cur[l] = D.ya32.p;
+    case SPK_AMG_STEP_COARSE:   // exact coarse solve
+        k::amg_dense(d.coarse_inv<T>().p, D.n, b, V.ya, done, s);
+        y = V.ya;
         break;
-    default: k::amg_prolong_add_grid(D.grid, cur[l + 1], cur[l], done, s);
+    default:   // SPK_AMG_STEP_UP: prolongation + correction
+        if (D.grid.matrix_free) k::amg_prolong_add_grid(D.grid, yn, y, done, s);
+        else if constexpr (is_f64<TN>) k::amg_prolong_add(D.P, yn, y, done, s);
     }
 }
 
-void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last)
+// the cycle's steps in order (amg_cycle_steps; under V: down, coarse, up) with the levels >= 1 in T; returns the buffer of
+// level 0 that holds the result
+template <typename T>
+static const double *walk(spk_ctx *c, AmgDev &d, const double *x, const int32_t *done)
 {
-    hipStream_t s = c->stream;
-    AmgDev &d = *c->amg_d;
     const size_t L = d.lv.size();
-    std::vector<double *> cur(L, nullptr);
-    std::vector<float *> cur32(d.single ? L : 0, nullptr);   // SPK_AMG_PRECISION_SINGLE: the iterates of the levels >= 1
-    auto rhs = [&](size_t l) -> const double * { return l == 0 ? x : d.lv[l].b.p; };
+    double *y0 = nullptr;
+    std::vector<T *> cur(L + 1, nullptr);   // the iterates of the levels >= 1 ([L]: below the coarsest, none)
     size_t run = 0;
-    for (size_t i = 0; i < d.steps.size(); ++i) {   // the cycle's steps in order (amg_cycle_steps); under V: down, coarse, up
+    for (size_t i = 0; i < d.steps.size(); ++i) {
         if (run < d.runs.size() && (size_t)d.runs[run].first == i) {   // a tail run: one launch of one workgroup
             const size_t t = (size_t)d.info.tail_first;
-            if (d.single) {
-                k::amg_tail(d.tail_desc32.p, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, s);
-                cur32[t] = d.run_sel[run] ? d.lv[t].yb32.p : d.lv[t].ya32.p;
-            } else {
-                k::amg_tail(d.tail_desc.p, d.tail_stencil, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, s);
-                cur[t] = d.run_sel[run] ? d.lv[t].yb.p : d.lv[t].ya.p;
-            }
+            const AmgLevelView<T> V = d.lv[t].view<T>();
+            k::amg_tail(d.tail<T>().p, d.tail_stencil, (int32_t)d.runs[run].first, (int32_t)d.runs[run].second, done, c->stream);
+            cur[t] = d.run_sel[run] ? V.yb : V.ya;
             i = (size_t)d.runs[run++].second - 1;
             continue;
         }
         const size_t l = (size_t)d.steps[i].level;
-        AmgLevelDev &D = d.lv[l];
-        if (d.single && l > 0) {
-            step32(c, d, d.steps[i].kind, l, cur32, done);
-            continue;
-        }
-        switch (d.steps[i].kind) {
-        case SPK_AMG_STEP_PRE0: cur[l] = smooth(c, D, (int)l, rhs(l), nullptr, done); break;
-        case SPK_AMG_STEP_PRE:
-        case SPK_AMG_STEP_POST: cur[l] = smooth(c, D, (int)l, rhs(l), cur[l], done); break;
-        case SPK_AMG_STEP_DOWN: {   // residual, restriction
-            if (l == 0) a_mult(c, cur[l], D.t.p, nullptr, nullptr, done, false, nullptr);
-            double *o = D.ya.p == cur[l] ? D.yb.p : D.ya.p;
-            if (l > 0 && D.stencil_op) k::amg_stencil_op(D.A, D.grid.fd, D.grid.bs, 0, cur[l], nullptr, nullptr, nullptr, o, 0.0, 0.0, done, s);
-            else if (l > 0) k::amg_spmv(D.A, cur[l], o, done, s);
-            const double *t = l == 0 ? D.t.p : o;
-            if (d.single) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b32.p, done, s);   // (level 0: FP64 sums, one rounding on the store)
-            else if (D.grid.matrix_free) k::amg_restrict_grid(D.grid, rhs(l), t, d.lv[l + 1].b.p, done, s);
-            else k::amg_restrict(D.R, rhs(l), t, d.lv[l + 1].b.p, done, s);
-            break;
-        }
-        case SPK_AMG_STEP_COARSE:   // exact coarse solve
-            k::amg_dense(d.cinv.p, D.n, rhs(l), D.ya.p, done, s);
-            cur[l] = D.ya.p;
-            break;
-        default:   // SPK_AMG_STEP_UP: prolongation + correction
-            if (d.single) k::amg_prolong_add_grid(D.grid, cur32[l + 1], cur[l], done, s);   // (level 0: e widened, FP64 sums)
-            else if (D.grid.matrix_free) k::amg_prolong_add_grid(D.grid, cur[l + 1], cur[l], done, s);
-            else k::amg_prolong_add(D.P, cur[l + 1], cur[l], done, s);
-        }
+        if (l == 0) step<double, T>(c, d, d.steps[i], x, y0, cur[1], done);
+        else step<T, T>(c, d, d.steps[i], d.lv[l].view<T>().b, cur[l], cur[l + 1], done);
     }
-    if (last) *last = cur[0];   // the caller's own pass reads the iterate where it lies
-    else k::amg_out(mode, c->n_local, cur[0], y, done, s);
+    return y0;
+}
+
+void amg_apply(spk_ctx *c, const double *x, double *y, int mode, const int32_t *done, const double **last)
+{
+    AmgDev &d = *c->amg_d;
+    const double *v = d.single ? walk<float>(c, d, x, done) : walk<double>(c, d, x, done);
+    if (last) *last = v;   // the caller's own pass reads the iterate where it lies
+    else k::amg_out(mode, c->n_local, v, y, done, c->stream);
 }
 
 }  // namespace spk

@@ -24,6 +24,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_ext.h>
@@ -868,26 +869,27 @@ constexpr int kAmgTailThreads = 1024;   // one workgroup, 16 waves: 128 CSR rows
 // steps [s0, s1) of d->steps -- one tail run -- in one launch of one workgroup; stencil: a level of the tail has its
 // `stencil` flag set (the kernel that knows the value-array route; without, the kernel is the one of the CSR route alone)
 void amg_tail(const AmgTailDesc *d, bool stencil, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);
-void amg_tail(const AmgTailDescF32 *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);   // (every level below the coarsest has `stencil` set)
+void amg_tail(const AmgTailDescF32 *d, bool stencil, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s);   // (one kernel: it knows both routes)
 // smoothed-aggregation multigrid (spk_k_amg.hip): CSR levels, eight lanes per row
 void amg_spmv(const CsrDev &A, const double *x, double *out, const int32_t *done, hipStream_t s);              // out = A x
 void amg_cheb_csr(const CsrDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
                   double alpha, double beta, const int32_t *done, hipStream_t s);   // out = y + a D^-1 (b - A y) + b (y - yo)
-// the same two on a level with the grid stencil's closed-form pattern (nd: its node grid, bs its node size), from A.val
-// alone -- rowptr and colidx are not read (SPK_AMG_OPERATOR_STENCIL; spk_stencil_op_core.hpp states the sums).  mode 0:
-// out = A x; mode 1: out = x + alpha dinv (b - A x) + beta (x - yo).  stencil_op_rows: the rows of one workgroup
+// the same two on an n-row level with the grid stencil's closed-form pattern (nd: its node grid, bs its node size), from its
+// value array `val` alone -- rowptr and colidx are not read (SPK_AMG_OPERATOR_STENCIL; spk_stencil_op_core.hpp states the
+// sums).  mode 0: out = A x; mode 1: out = x + alpha dinv (b - A x) + beta (x - yo).  stencil_op_rows: the rows of one workgroup
 struct StencilOpArgs { int32_t nx, ny, nz, n; };   // the level's node grid and its rows
 int stencil_op_rows(const int32_t nd[3], int bs, size_t elem = sizeof(double));   // elem: sizeof of the scalar type
-void amg_stencil_op(const CsrDev &A, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv, const double *b,
-                    const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
+void amg_stencil_op(int32_t n, const double *val, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv,
+                    const double *b, const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s);
 // The FP32 forms of SPK_AMG_PRECISION_SINGLE, overloads on the vectors' types.  The level operator from the FP32 copy `val`
-// of the n-row level's value array (the rows of a workgroup keep the byte budget of stencil_op_rows, so a float workgroup
-// takes up to twice the rows);  the zero-guess step out = alpha dinv b;  the dense product;
+// of the level's value array (the rows of a workgroup keep the byte budget of stencil_op_rows, so a float workgroup
+// takes up to twice the rows);  the vector step (amg_cheb_vec below);  the dense product;
 // the transfers float -> float between FP32 levels, and at the level 0 / level 1 boundary R (b - t) summed in FP64 and
 // rounded once on the store, y += P e with every e widened and the sums in FP64
 void amg_stencil_op(int32_t n, const float *val, const int32_t nd[3], int bs, int mode, const float *x, const float *dinv,
                     const float *b, const float *yo, float *out, float alpha, float beta, const int32_t *done, hipStream_t s);
-void amg_cheb_vec0(int64_t n, const float *dinv, const float *b, float *out, float alpha, const int32_t *done, hipStream_t s);
+void amg_cheb_vec(int64_t n, const float *dinv, const float *b, const float *t, const float *y, const float *yo, float *out,
+                  float alpha, float beta, const int32_t *done, hipStream_t s);
 void amg_dense(const float *C, int32_t n, const float *b, float *y, const int32_t *done, hipStream_t s);
 void amg_restrict_grid(const AmgGrid &g, const float *b, const float *t, float *out, const int32_t *done, hipStream_t s);
 void amg_restrict_grid(const AmgGrid &g, const double *b, const double *t, float *out, const int32_t *done, hipStream_t s);
@@ -959,6 +961,13 @@ void amgs_lz_update_resident(int64_t n, int j, int kk, const double *q, const do
                              lanczos_core::LzState *st, hipStream_t s);
 }  // namespace k
 
+// what the cycle reads and writes of one level in the scalar type T of its vectors (AmgLevelDev::view)
+template <typename T>
+struct AmgLevelView {
+    const T *val, *dinv;                  // the operator's value array and D^-1 (levels >= 1)
+    T *b, *ya, *yb;
+    const std::vector<T> &alpha, &beta;
+};
 // the device copy of the hierarchy (spk_amg_setup.cpp): level 0 keeps the context's A layout and diag(A)^-1
 struct AmgLevelDev {
     int32_t n = 0;
@@ -971,10 +980,20 @@ struct AmgLevelDev {
     std::vector<double> alpha, beta;   // smoothing steps: y+ = y + alpha D^-1 (b - A y) + beta (y - y-)
     k::AmgGrid grid;                    // grid coarsening: the transfer to level l+1
     bool stencil_op = false;           // the cycle applies A from A.val alone (SPK_AMG_OPERATOR_STENCIL; amg_plan_cycle sets it)
-    // SPK_AMG_PRECISION_SINGLE, levels >= 1: the FP32 copies of A.val and dinv (amg_round_levels, behind every build and
-    // refresh), the cycle vectors in float (b, ya, yb above stay empty there) and the smoothing coefficients rounded
-    DevBuf<float> val32, dinv32, b32, ya32, yb32;
-    std::vector<float> alpha32, beta32;
+    // SPK_AMG_PRECISION_SINGLE, levels >= 1: the same in FP32 -- val and dinv the copies of A.val and dinv (amg_round_levels,
+    // behind every build and refresh), the cycle vectors in float (b, ya, yb above stay empty there) and the smoothing
+    // coefficients rounded
+    struct F32 {
+        DevBuf<float> val, dinv, b, ya, yb;
+        std::vector<float> alpha, beta;
+    } f32;
+    // double: what the set-up owns above; float: the copies
+    template <typename T>
+    AmgLevelView<T> view()
+    {
+        if constexpr (std::is_same<T, double>::value) return {A.val.p, dinv.p, b.p, ya.p, yb.p, alpha, beta};
+        else return {f32.val.p, f32.dinv.p, f32.b.p, f32.ya.p, f32.yb.p, f32.alpha, f32.beta};
+    }
 };
 // what a set-up with reuse on (spk_pc_set_amg_reuse) keeps beside the hierarchy, so that the next one can refresh it
 struct AmgReuse {
@@ -1008,8 +1027,15 @@ struct AmgDev {
     // SPK_AMG_PRECISION_SINGLE: the levels >= 1 run in FP32 (the vectors were allocated so); the coarse inverse rounded, and
     // the tail's descriptor over the float buffers (tail_desc stays empty)
     bool single = false;
-    DevBuf<float> cinv32;
-    DevBuf<k::AmgTailDescF32> tail_desc32;
+    struct F32 {
+        DevBuf<float> cinv;
+        DevBuf<k::AmgTailDescF32> tail_desc;
+    } f32;
+    // the coarse inverse and the tail's descriptor of the cycle whose levels >= 1 are T
+    template <typename T>
+    auto &coarse_inv() { if constexpr (std::is_same<T, double>::value) return cinv; else return f32.cinv; }
+    template <typename T>
+    auto &tail() { if constexpr (std::is_same<T, double>::value) return tail_desc; else return f32.tail_desc; }
 };
 
 }  // namespace spk

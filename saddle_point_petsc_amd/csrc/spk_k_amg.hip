@@ -650,10 +650,10 @@ static void stencil_op_run(int32_t n, const T *val, const int32_t nd[3], int bs,
     else if (bs == 2) stencil_op_launch<2>(g, rows, lds, mode, val, x, dinv, b, yo, out, alpha, beta, done, s);
     else stencil_op_launch<3>(g, rows, lds, mode, val, x, dinv, b, yo, out, alpha, beta, done, s);
 }
-void amg_stencil_op(const CsrDev &A, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv, const double *b,
-                    const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s)
+void amg_stencil_op(int32_t n, const double *val, const int32_t nd[3], int bs, int mode, const double *x, const double *dinv,
+                    const double *b, const double *yo, double *out, double alpha, double beta, const int32_t *done, hipStream_t s)
 {
-    stencil_op_run(A.nrows, A.val.p, nd, bs, mode, x, dinv, b, yo, out, alpha, beta, done, s);
+    stencil_op_run(n, val, nd, bs, mode, x, dinv, b, yo, out, alpha, beta, done, s);
 }
 void amg_stencil_op(int32_t n, const float *val, const int32_t nd[3], int bs, int mode, const float *x, const float *dinv,
                     const float *b, const float *yo, float *out, float alpha, float beta, const int32_t *done, hipStream_t s)
@@ -679,11 +679,11 @@ void amg_cheb_vec(int64_t n, const double *dinv, const double *b, const double *
     if (n == 0) return;
     hipLaunchKernelGGL(amg_cheb_vec_kernel<double>, vec_grid1(n), dim3(kThreads), 0, s, n, dinv, b, t, y, yo, out, alpha, beta, done);
 }
-void amg_cheb_vec0(int64_t n, const float *dinv, const float *b, float *out, float alpha, const int32_t *done, hipStream_t s)
+void amg_cheb_vec(int64_t n, const float *dinv, const float *b, const float *t, const float *y, const float *yo, float *out,
+                  float alpha, float beta, const int32_t *done, hipStream_t s)
 {
     if (n == 0) return;
-    hipLaunchKernelGGL(amg_cheb_vec_kernel<float>, vec_grid1(n), dim3(kThreads), 0, s, n, dinv, b, (const float *)nullptr,
-                       (const float *)nullptr, (const float *)nullptr, out, alpha, 0.0f, done);
+    hipLaunchKernelGGL(amg_cheb_vec_kernel<float>, vec_grid1(n), dim3(kThreads), 0, s, n, dinv, b, t, y, yo, out, alpha, beta, done);
 }
 bool amg_cheb_dict2(const DictDev &A, const double *dinv, const double *b, const double *y, const double *yo, double *out,
                     double alpha, double beta, const int32_t *done, hipStream_t s)
@@ -716,7 +716,7 @@ void amg_tail(const AmgTailDesc *d, bool stencil, int32_t s0, int32_t s1, const 
     if (stencil) hipLaunchKernelGGL(amg_stencil_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
     else hipLaunchKernelGGL(amg_tail_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
 }
-void amg_tail(const AmgTailDescF32 *d, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s)
+void amg_tail(const AmgTailDescF32 *d, bool, int32_t s0, int32_t s1, const int32_t *done, hipStream_t s)
 {
     if (s0 >= s1) return;
     hipLaunchKernelGGL(amg_stencil_tail_f32_kernel, dim3(1), dim3(kAmgTailThreads), 0, s, d, s0, s1, done);
