@@ -14,12 +14,11 @@ namespace k {
 
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
-// Reducing vector kernels on big vectors run fat workgroups on a grid of <= 256 (one per
-// CU): the reducer reads one partial row per workgroup, so few fat workgroups beat many thin ones.
+// Reducing vector kernels on big vectors run fat workgroups on a grid of <= 256 (kVecMaxBlocks in spk_gs_launch.hpp,
+// one per CU): the reducer reads one partial row per workgroup, so few fat workgroups beat many thin ones.
 constexpr int kVT = 1024;
 constexpr int kVWaves = kVT / kWave;
 constexpr int kVecUnroll = 4;    // double2 per thread per vector tile
-constexpr int kVecMaxBlocks = 256;
 
 // ---------------------------------------------------------------------------
 // reductions inside a workgroup
@@ -900,13 +899,6 @@ __device__ __forceinline__ double mdot_step_ww(double s, double2 w)           //
 #pragma clang fp contract(off)
     return s + __builtin_fma(w.y, w.y, w.x * w.x);
 }
-
-// The short remainder tile of form 7's launch (TAIL; gs_fused_tail_kernel, SPK_GS_TAIL): at most kGsTailMax double2 behind
-// the whole tiles (at 1024^2 with the full Schur preconditioner the four multiplier entries), staged in LDS at entry
-// instead of being a tile-loop trip of their own.  kGsTailSrc sources: w~ and the <= 40 vectors or planes of one
-// reduction (GsArgs::cnt); 41 x 16 double2 = 10 496 B of the 19 776 B that LDS has free beside the keep set
-// (160 KiB - 4 x 32 KiB - 12 992 B).
-constexpr int kGsTailMax = 16, kGsTailSrc = 41;
 
 // VecMDot body (mdot_kernel, gs_fused_kernel): the workgroup's tiles (tile = blockIdx.x + k gridDim.x of T x U double2),
 // all nv dot products V_i . w in ONE pass over w (kept in registers), w.w in slot nv (with_ww); the workgroup's sums

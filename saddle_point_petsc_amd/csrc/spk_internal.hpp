@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -32,6 +33,7 @@
 #include "spk_host.hpp"
 #include "spk_amg.hpp"
 #include "spk_lanczos_core.hpp"
+#include "spk_gs_launch.hpp"
 
 namespace spk {
 
@@ -694,20 +696,20 @@ struct IterB {
 struct GsArgs {
     const double *V2;    // planes of B D (parity-interleaved when split)
     int cnt, split;      // cnt = nv + m values (<= 40), w.w after them
-    int keep;            // the first tile's operands stay on chip between the two passes (FgmresPlan::gs_keep)
-    int ahead;           // with keep: a second group of basis loads ahead of the totals wait (FgmresPlan::gs_ahead)
+    int variant, pad;    // the GsVariant launched (set by the launcher; no kernel reads it: the fields behind it stay where they are)
     int64_t n2, n_dot;   // MDot's length in double2 (the multiplier entries included), entries that count
     double *partials;    // MDot's partial rows (column offset 1 of the context's partials)
     double *out;         // the reduced [h, q, w.w] (as mdot's Finish::out)
     double *tot, *tot_next;   // the armed totals line of this launch, the line it arms for the next one
     FinErr fe;
 };
-// tail (FgmresPlan::gs_tail; the launcher's alone, no kernel argument): with keep and ahead, a short remainder tile is
-// staged in LDS where the shape allows -- gs_fused_tail says whether this launch does (gs_fused_tail_kernel)
-int gs_fused(IterB b, GsArgs g, hipStream_t s, int tail = 1);
-bool gs_fused_tail(const IterB &b, const GsArgs &g, int tail = 1);
+static_assert(sizeof(GsArgs) == 88 && offsetof(GsArgs, V2) == 0 && offsetof(GsArgs, cnt) == 8 && offsetof(GsArgs, split) == 12 &&
+              offsetof(GsArgs, n2) == 24 && offsetof(GsArgs, n_dot) == 32 && offsetof(GsArgs, partials) == 40 &&
+              offsetof(GsArgs, out) == 48 && offsetof(GsArgs, tot) == 56 && offsetof(GsArgs, tot_next) == 64 &&
+              offsetof(GsArgs, fe) == 72, "GsArgs is a kernel argument: the kernels read these fields at these offsets");
+// launches the instantiation v names (gs_fused_variant in spk_gs_launch.hpp resolves it from the knobs and the shape)
+int gs_fused(IterB b, GsArgs g, GsVariant v, hipStream_t s);
 int gs_fused_occupancy(int ng, int m, bool keep);   // workgroups of the fused kernel (with / without its keep set) that fit one CU
-int64_t gs_fused_grid(int64_t nl);       // its grid for nl local rows; 0: not the fat vector shape
 // GS_STAMPS=1 builds: the launches' phase time stamps, 64 iterations x 256 workgroups x 8 (spk_gs_stamps.hpp); false otherwise
 bool gs_stamps(unsigned long long *out);
 // Resident restart cycle (spk_k_resident.hip): ONE launch runs iterations 0 .. mk-1 of a cycle with the basis in registers

@@ -472,7 +472,7 @@ int iter_maxpy_uhead(IterB b, hipStream_t s)   // returns the number of partial 
     if (b.sr.peer) grid += (2 * b.sr.nrecv + T - 1) / T;
     if (b.nv + b.m > kMaxNv - 1) fail(SPK_ERR_ARG, "iter_maxpy_uhead: %d values exceed one reduction", b.nv + b.m);
 #define SPK_IB(TT, GG, UU, MPP) hipLaunchKernelGGL((iter_maxpy_uhead_kernel<TT, GG, UU, MPP>), dim3(grid), dim3(TT), 0, s, b)
-    const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+    const int mp = plane_class(b.m);
     if (b.w32) {
         // an FP32 basis: the same thread positions, so a basis load is 8 bytes per lane -- twice the vectors are loaded
         // together instead (the same bytes in flight, the same registers as the FP64 groups)
@@ -548,28 +548,15 @@ struct TotalsWait {   // kernel B's dots: spins (bounded) while a value it needs
     }
 };
 
-constexpr int kGsT = 512, kGsU = 4, kGsG = 4;   // vec_shape's fat shape (mdot_kernel<NG, 512, 4, true, 4>, kernel B <512, 4, 4, MP>)
-
-// The keep set of instantiation <NG, MP> (GsArgs::keep; without it an empty one): w~ and, where kernel B fetches them
+// The keep set of instantiation <NG, MP> (GsKnobs::keep; without it an empty one): w~ and, where kernel B fetches them
 // ahead (MP = 4), the two parity planes in registers, V_0 .. V_3 in LDS (4 x 32 KiB beside 12 992 B; a fifth does not
-// fit 160 KiB).  Sized by the compiler's resource remark on gfx950 (tests/test_gs_keep_resources_cpu.py):
+// fit 160 KiB).  Sized by the compiler's resource remark on gfx950 (tests/test_gs_resources_cpu.py):
 // no scratch, <= 256 registers for every instantiation -- <5, 4> with the planes kept spills 19 VGPRs, so it keeps
 // w~ and the basis vectors only.
 template <int NG, int MP, int AH = 0>
 struct GsKeep {
     static constexpr int KP = MP == 4 && NG <= 4 ? 2 : 0, KV = 4;
     using type = KeepSet<kGsT, kGsU, 1, KP, KV, 1 + KP, AH, (MP == 4 && AH > 0)>;
-};
-
-// What a launch with a keep set asks for ahead of the totals wait beyond V_4 .. V_7 (GsArgs::ahead, SPK_GS_AHEAD; NoKeep
-// in spk_device.hpp): kGsAhead[MP / 4][NG - 1] vectors of the group V_8 .. V_11, held across the wait in the registers
-// of the tile loop's buffer, 16 each.  Sized by the compiler's resource remark (tests/test_gs_ahead_resources_cpu.py
-// reads this table and the remark of every instantiation): MP = 4 takes the registers of the two planes that parity
-// planes leave unused (KeepSet::PK) and still spills 4 .. 12 VGPRs with the whole group, so it holds three vectors.
-constexpr int kGsAhead[3][5] = {
-    {4, 4, 4, 4, 4},   // MP = 0
-    {3, 3, 3, 3, 3},   // MP = 4
-    {4, 4, 4, 4, 4},   // MP = 8
 };
 
 template <int NG, int MP, bool KEEP, int AH = 0>
@@ -602,7 +589,7 @@ __global__ __launch_bounds__(kGsT) void gs_fused_kernel(IterB b, GsArgs g)
 }
 
 // The default launch -- gs_fused_kernel<NG, MP, true, AH> line by line -- with a short remainder tile staged in LDS
-// (SPK_GS_TAIL, gs_fused_tail): the remainder behind the whole tiles, at 1024^2 with the full Schur preconditioner two
+// (SPK_GS_TAIL, kGsKeepAheadTail): the remainder behind the whole tiles, at 1024^2 with the full Schur preconditioner two
 // double2 (the multiplier entries), is requested at entry by the workgroup the tile loop would give it to and added
 // behind that workgroup's loop (mdot_tiles, TAIL), instead of costing it a trip of dependent loads while every other
 // workgroup has finished its tiles and waits for the totals.  A kernel of its own, not one more template argument: the
@@ -634,53 +621,48 @@ __global__ __launch_bounds__(kGsT) void gs_fused_tail_kernel(IterB b, GsArgs g)
     maxpy_uhead_tiles<kGsT, kGsG, kGsU, MP>(b, (int)gridDim.x - 2, TotalsWait{g.tot, g.fe}, &keep);
 }
 
-#define SPK_GS_SWITCH(NGV, MPV, CASE)                                                        \
-    switch ((NGV) * 10 + (MPV)) {                                                           \
-    case 10: CASE(1, 0); case 20: CASE(2, 0); case 30: CASE(3, 0); case 40: CASE(4, 0); case 50: CASE(5, 0); \
-    case 14: CASE(1, 4); case 24: CASE(2, 4); case 34: CASE(3, 4); case 44: CASE(4, 4); case 54: CASE(5, 4); \
-    case 18: CASE(1, 8); case 28: CASE(2, 8); case 38: CASE(3, 8); case 48: CASE(4, 8); default: CASE(5, 8); \
+// f(NG, MP) as std::integral_constant values, for the fifteen <NG, MP> the fused kernels are built for
+template <int N> using GsInt = std::integral_constant<int, N>;
+template <class F>
+inline void gs_dispatch(int ng, int mp, F &&f)
+{
+    if (ng < 1 || ng > 5 || (mp != 0 && mp != 4 && mp != 8))
+        fail(SPK_ERR_ARG, "gs_fused: no kernel for %d groups of dot products and plane class %d", ng, mp);
+    const auto groups = [&](auto mpc) {
+        ng == 1 ? f(GsInt<1>{}, mpc) : ng == 2 ? f(GsInt<2>{}, mpc) : ng == 3 ? f(GsInt<3>{}, mpc)
+                                     : ng == 4 ? f(GsInt<4>{}, mpc) : f(GsInt<5>{}, mpc);
+    };
+    mp == 0 ? groups(GsInt<0>{}) : mp == 4 ? groups(GsInt<4>{}) : groups(GsInt<8>{});
+}
+// the kernel of variant v at <NG, MP>
+template <int NG, int MP>
+inline auto gs_kernel(GsVariant v) -> void (*)(IterB, GsArgs)
+{
+    constexpr int AH = kGsAhead[MP / 4][NG - 1];
+    switch (v) {
+    case kGsKeep: return gs_fused_kernel<NG, MP, true>;
+    case kGsKeepAhead: return gs_fused_kernel<NG, MP, true, AH>;
+    case kGsKeepAheadTail: return gs_fused_tail_kernel<NG, MP, AH>;
+    case kGsPlain: return gs_fused_kernel<NG, MP, false>;
     }
+    fail(SPK_ERR_ARG, "gs_fused: unknown variant %d", (int)v);
+}
 
 int gs_fused_occupancy(int ng, int m, bool keep)
 {
-    const int mp = m == 0 ? 0 : (m <= 4 ? 4 : 8);
-    int nb = 0;
-    // (with a keep set: the fewest of the three instantiations SPK_GS_AHEAD and SPK_GS_TAIL choose between)
-#define SPK_GS_OCC(NG, MP)                                                                                          \
-    if (keep) {                                                                                                     \
-        int n1 = 0, n2 = 0;                                                                                         \
-        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, true>, kGsT, 0));        \
-        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>, kGsT, 0)); \
-        SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, gs_fused_tail_kernel<NG, MP, kGsAhead[MP / 4][NG - 1]>, kGsT, 0)); \
-        nb = std::min(nb, std::min(n1, n2));                                                                        \
-    } else SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gs_fused_kernel<NG, MP, false>, kGsT, 0));    \
-    break
-    SPK_GS_SWITCH(ng, mp, SPK_GS_OCC)
-#undef SPK_GS_OCC
+    // with a keep set: the fewest of the three variants SPK_GS_AHEAD and SPK_GS_TAIL choose between
+    int nb = 1 << 30;
+    gs_dispatch(ng, plane_class(m), [&](auto ngc, auto mpc) {
+        for (int v = keep ? kGsKeep : kGsPlain; v <= (keep ? kGsKeepAheadTail : kGsPlain); ++v) {
+            int n = 0;
+            SPK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gs_kernel<ngc.value, mpc.value>((GsVariant)v), kGsT, 0));
+            nb = std::min(nb, n);
+        }
+    });
     return nb;
 }
 
-int64_t gs_fused_grid(int64_t nl)
-{
-    const int64_t n2 = nl / 2;
-    if (n2 < (int64_t)kVecMaxBlocks * 2048) return 0;   // not the fat vector shape
-    return kVecMaxBlocks;                               // >= 256 tiles of 2048 double2: both kernels' grids
-}
-
-// Does the launch stage its remainder tile in LDS (gs_fused_tail_kernel)?  Asked for (tail), the default launch
-// (keep set and loads ahead of the wait: the one instantiation built with it), a remainder of 1 .. kGsTailMax double2,
-// and whole tiles that are a multiple of the grid -- so that the remainder would be a trip of its own beyond every
-// workgroup's whole tiles.  Any other shape keeps the loop trip.
-bool gs_fused_tail(const IterB &b, const GsArgs &g, int tail)
-{
-    const int64_t grid = gs_fused_grid(b.nl), tile2 = (int64_t)kGsT * kGsU;
-    const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
-    if (!grid || !tail || !g.keep || !g.ahead || (mp == 4 && !b.packed)) return false;
-    const int64_t whole = g.n2 / tile2, rem = g.n2 % tile2;
-    return rem > 0 && rem <= kGsTailMax && whole >= grid && whole % grid == 0;
-}
-
-int gs_fused(IterB b, GsArgs g, hipStream_t s, int tail)
+int gs_fused(IterB b, GsArgs g, GsVariant v, hipStream_t s)
 {
     const int64_t grid = gs_fused_grid(b.nl);
     const VecShape vs = vec_shape(g.n2);
@@ -688,26 +670,13 @@ int gs_fused(IterB b, GsArgs g, hipStream_t s, int tail)
     if (b.ar.P || b.sr.n || b.sr.peer) fail(SPK_ERR_STATE, "gs_fused: one rank only");
     if (g.cnt > 40 || b.nv + b.m > kMaxNv - 1) fail(SPK_ERR_ARG, "gs_fused: %d values exceed one reduction", g.cnt);
     b.gmain = (int)grid;
-    const int ng = (g.cnt + 7) / 8 > 0 ? (g.cnt + 7) / 8 : 1;
-    const int mp = b.m == 0 ? 0 : (b.m <= 4 ? 4 : 8);
+    g.variant = v;
     gs_stamps_aim(b.loc, (int)grid, s);   // (GS_STAMPS=1 builds only)
-    // MP = 4: the loads ahead of the wait take the registers of half the planes, which parity planes leave free
-    // (KeepSet::PK); rows of B D that do not pack run the launch without them
-    const bool ahead = g.ahead && !(mp == 4 && !b.packed);
-    const bool staged = gs_fused_tail(b, g, tail);
-#define SPK_GS_LAUNCH(NG, MP)                                                                                       \
-    if (staged)                                                                                                     \
-        hipLaunchKernelGGL((gs_fused_tail_kernel<NG, MP, kGsAhead[MP / 4][NG - 1]>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
-    else if (g.keep && ahead)                                                                                       \
-        hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true, kGsAhead[MP / 4][NG - 1]>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
-    else if (g.keep) hipLaunchKernelGGL((gs_fused_kernel<NG, MP, true>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g); \
-    else hipLaunchKernelGGL((gs_fused_kernel<NG, MP, false>), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);        \
-    break
-    SPK_GS_SWITCH(ng, mp, SPK_GS_LAUNCH)
-#undef SPK_GS_LAUNCH
+    gs_dispatch(dot_groups(g.cnt), plane_class(b.m), [&](auto ngc, auto mpc) {
+        hipLaunchKernelGGL((gs_kernel<ngc.value, mpc.value>(v)), dim3((unsigned)grid), dim3(kGsT), 0, s, b, g);
+    });
     return b.gmain;
 }
-#undef SPK_GS_SWITCH
 
 bool gs_stamps(unsigned long long *out) { return gs_stamps_fetch(out); }
 

@@ -435,7 +435,7 @@ void mdot(const double *V, int64_t ldv, int nv, const double *w, int64_t n, int6
         const double *V2p = nv1 > 0 ? V2 : V2 + (size_t)(v0 - nv) * ldv;
         double *pp = f.partials + v0;
         double *oo = f.out + v0;
-        const int ng = (cnt + 7) / 8 > 0 ? (cnt + 7) / 8 : 1;
+        const int ng = dot_groups(cnt);
         const WsShape ws = ws_shape(n2);
         static const int ws16 = [] { const char *e = getenv("SPK_VEC_WS16"); return e ? atoi(e) : 1; }();
         if (ws.on && ws16) {
@@ -632,7 +632,7 @@ static void mdot_f32_launch(const float *V, int64_t ldv, int nv, const double *V
                             int64_t n2, int64_t n_dot, double *partials, int with_ww, double *out, FinErr fe, const int32_t *done,
                             const VecShape &vs, hipStream_t s)
 {
-    const int ng = (nv + 7) / 8 > 0 ? (nv + 7) / 8 : 1;
+    const int ng = dot_groups(nv);
 #define SPK_MDOT_F32(NGG, TT, UU) hipLaunchKernelGGL((mdot_f32_kernel<NGG, TT, UU>), dim3(vs.grid), dim3(TT), 0, s, V, ldv, nv, V2, ld2, \
                                                      nv2, split, vnew, w, n2, n_dot, partials, with_ww, out, fe, done)
 #define SPK_MDOT_F32_NG(TT, UU)                                                \

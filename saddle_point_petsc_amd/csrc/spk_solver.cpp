@@ -58,7 +58,7 @@ bool spk_ctx::gs_fused_fits(int64_t nl, int m, bool keep)
 {
     const int64_t grid = k::gs_fused_grid(nl);
     if (!grid) return false;
-    const int mi = (m == 0 ? 0 : (m <= 4 ? 1 : 2)) + (keep ? 3 : 0);
+    const int mi = k::plane_class(m) / 4 + (keep ? 3 : 0);
     if (gs_occ[mi] < 0) {   // blocks per CU of the fused kernel at its real block size and LDS: the fewest over its instantiations
         int occ = 1 << 30;
         for (int ng = 1; ng <= 5; ++ng) occ = std::min(occ, k::gs_fused_occupancy(ng, m, keep));
@@ -430,9 +430,7 @@ struct FgmresPlan {
     bool big;             // restart > kMaxNv - 2: the Givens step is a launch of its own
     bool f32;             // the basis is stored as floats (opts.basis_precision; form 5 only)
     bool resident, gsf;   // form 6: one launch per restart cycle; form 7: MDot inside kernel B's launch
-    int gs_keep;          // form 7: the first tile's operands stay on chip between its two passes (SPK_GS_KEEP=0: not, for tests)
-    int gs_ahead;         // form 7 with its keep set: a second group of basis loads is requested ahead of the totals wait (SPK_GS_AHEAD=0: not, for tests)
-    int gs_tail;          // form 7's default launch: a short remainder tile is staged in LDS at entry instead of being a tile-loop trip (SPK_GS_TAIL=0: not, for tests)
+    k::GsKnobs gs;        // form 7: the test knobs that choose between its launch variants (spk_gs_launch.hpp)
     int chunk, refine;    // CGS: vectors per MDot / MAXPY launch; -ksp_gmres_cgs_refinement_type
     int nn, bpk, form;    // norm (+ B D w') out of the last MAXPY; B D as m/2 parity planes; what is reported
     const double *bdp;    // the B D rows the kernels stream (Schur)
@@ -500,14 +498,9 @@ FgmresPlan plan_fgmres(spk_ctx *c, const spk_opts &o)
     // GS_FUSED (form 7): MDot and kernel B in one launch -- one rank, fat vectors,
     // every workgroup of the launch resident at once; what AUTO takes there
     // (the knob is read per solve, so that a test can flip it between two solves of one context)
-    const char *keep_env = getenv("SPK_GS_KEEP");
-    p.gs_keep = keep_env && !strcmp(keep_env, "0") ? 0 : 1;
-    const char *ahead_env = getenv("SPK_GS_AHEAD");
-    p.gs_ahead = ahead_env && !strcmp(ahead_env, "0") ? 0 : 1;   // (2 once added groups left to the L2: taken out; it runs as 1)
-    const char *tail_env = getenv("SPK_GS_TAIL");
-    p.gs_tail = tail_env && !strcmp(tail_env, "0") ? 0 : 1;
+    p.gs = k::gs_knobs_env();
     p.gsf = un3 && !p.resident && (form == SPK_ITER_GS_FUSED || form == SPK_ITER_AUTO) && c->comm->size() == 1 &&
-            c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m, p.gs_keep != 0);
+            c->peers.empty() && c->n_ghost == 0 && mk + m <= 41 && c->gs_fused_fits(nl, m, p.gs.keep);
     p.product = un3 ? FgmresPlan::kUn3 : p.schur ? FgmresPlan::kSchurHead : jac ? FgmresPlan::kJacobiHead : FgmresPlan::kStep;
     p.orth = un3 ? FgmresPlan::kOrthUn3 : o.orthog == SPK_ORTHOG_MGS ? FgmresPlan::kOrthMgs
            : single ? FgmresPlan::kOrthSingle : FgmresPlan::kOrthCgs;
@@ -676,16 +669,17 @@ bool un3_iteration(const FgmresRun &r, CycleState &cs, int loc, const int32_t *d
     if (gs) {
         k::GsArgs g{};
         g.V2 = schur ? (r.p.bpk ? c->bdpk.p : c->bd.p) : nullptr;
-        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk; g.keep = r.p.gs_keep; g.ahead = r.p.gs_ahead;
+        g.cnt = loc + 1 + (schur ? r.m : 0); g.split = r.p.bpk;
         g.n2 = (r.N + 1) / 2; g.n_dot = r.n_dot;
         g.partials = c->partials.p + 1;   // column 0 of the rows carries the ||w'||^2 partials
         g.out = db;
         g.tot = c->gs_tot.p + (c->gs_seq & 1) * k::kPartialLd;
         g.tot_next = c->gs_tot.p + ((c->gs_seq + 1) & 1) * k::kPartialLd;
         g.fe = k::FinErr{c->errw.p, c->fin_ticks};
-        fin_n = k::gs_fused(b, g, r.s, r.p.gs_tail);
+        const k::GsVariant v = k::gs_fused_variant(r.p.gs, b.nl, g.n2, b.m, b.packed);
+        fin_n = k::gs_fused(b, g, v, r.s);
         ++c->last_gs_launches;
-        if (k::gs_fused_tail(b, g, r.p.gs_tail)) ++c->last_gs_tail;
+        if (v == k::kGsKeepAheadTail) ++c->last_gs_tail;
         ++c->gs_seq;   // (launched: it arms tot_next even when the solve is over)
     } else {
         fin_n = k::iter_maxpy_uhead(b, r.s);

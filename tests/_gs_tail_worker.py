@@ -2,19 +2,16 @@
 
     SPK_GS_TAIL=0|1 python _gs_tail_worker.py OUT_DIR      (a fresh process per variant: clean contexts)
 
-Per case the child solves with AUTO (form 7 asserted by the test) and with forced form 5 on one context, compares the
-two in place and writes the AUTO solve's x as OUT_DIR/<case>.npy and everything else to OUT_DIR/results.json (the
-residual histories as hex floats: bit-exact; Context.gs_launch() of either solve: how many of form 7's launches staged
-their remainder tile in LDS).  Nothing here is imported by the CPU suite."""
+The case loop, the pair of solves per case and the gated sequence behind "full" are tests/_gs_rig.py's; this child adds
+Context.gs_launch() to the record of every solve: how many of form 7's launches staged their remainder tile in LDS.
+Nothing here is imported by the CPU suite."""
 import contextlib
-import json
 import os
 import sys
 
-import numpy as np
+import _gs_rig as R
+from _gs_rig import FULL, LOWER
 
-UN3, GSF = 5, 7
-LOWER, FULL = 1, 3
 TILE2, GRID, R_MAX = 2048, 256, 16   # the fused launch's tile (512 threads x 4 double2), its grid, kGsTailMax
 
 # name: (grid, saddle, fact, restart, max_it).  1024 x 512 is the smallest fat vector: one whole tile per workgroup and
@@ -40,80 +37,24 @@ CASES = {
 
 
 def tail_expected(n, m):
-    """The launcher's condition (spk_k_iter.hip gs_fused_tail) for n rows and m multipliers on the default launch."""
+    """The launcher's condition (gs_fused_variant in csrc/spk_gs_launch.hpp, stated again here) for n rows and m multipliers
+    on the default launch."""
     n2 = (n + m + 1) // 2
     whole, rem = divmod(n2, TILE2)
     return 0 < rem <= R_MAX and whole >= GRID and whole % GRID == 0
 
 
-def _system(S, grid, saddle):
-    if len(grid) == 3:
-        A, f = S.AssembleOperator_Laplace3D(*grid, nthreads=16)
-        B, g = S.AssembleOperator_Constraints3D(*grid)
-        return A, B, np.concatenate([f, g])
-    A, f = S.AssembleOperator_Laplace(*grid)
-    if not saddle:
-        return A, None, f
-    B, g = S.AssembleOperator_Constraints(*grid)
-    return A, B, np.concatenate([f, g])
-
-
-def _ctx(S, A, B, fact):
-    c = S.Context(0)
-    c.set_block(S.BLOCK_A00, A)
-    if B is not None:
-        c.set_block(S.BLOCK_A10, B)
-    c.pc_setup(S.PC_SCHUR if B is not None else S.PC_JACOBI, fact)
-    return c
-
-
-def _hex(h):
-    return [float(v).hex() for v in np.asarray(h, float)]
-
-
 def _record(c, info):
     launches, tail = c.gs_launch()
-    return {"its": int(info["its"]), "reason": int(info["reason"]), "form": int(c.iteration_form()[0]),
-            "launches": int(launches), "tail": int(tail), "history": _hex(info["history"])}
+    return dict(R._record(None, info, c.iteration_form()[0]), launches=int(launches), tail=int(tail))
 
 
 def main(out_dir):
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import saddle_point_petsc_amd as S
-
-    res = {"tail": os.environ.get("SPK_GS_TAIL")}
-    sys_key = ctx_key = None
+    S = R.package()
+    res = {"knob": os.environ.get("SPK_GS_TAIL")}
     with contextlib.ExitStack() as stack:
-        for name, (grid, saddle, fact, restart, max_it) in CASES.items():   # consecutive cases share system and context
-            if (grid, saddle) != sys_key:
-                stack.close()
-                ctx_key = None
-                sys_key = (grid, saddle)
-                A, B, rhs = _system(S, grid, saddle)
-            if (sys_key, fact) != ctx_key:
-                stack.close()
-                ctx_key = (sys_key, fact)
-                c = stack.enter_context(_ctx(S, A, B, fact))
-            x7, i7 = c.fgmres(rhs, rtol=0.0, abstol=0.0, max_it=max_it, restart=restart)
-            r = _record(c, i7)
-            r["rows"], r["m"] = int(A.nrows), 0 if B is None else int(B.nrows)
-            x5, i5 = c.fgmres(rhs, rtol=0.0, abstol=0.0, max_it=max_it, restart=restart, iteration_form=UN3)
-            r["form5"] = _record(c, i5)
-            r["x_equals_form5"] = bool(np.array_equal(x7, x5))
-            np.save(os.path.join(out_dir, name + ".npy"), x7)
-            res[name] = r
-            if name != "full":
-                continue
-            # -ksp_max_it in the middle of the second cycle, the convergence test live: the launches enqueued behind the end
-            # of the solve are gated off with the remainder's loads in flight; the next solve must not notice
-            _, ig = c.fgmres(rhs, rtol=1e-30, max_it=47, restart=restart)
-            g = _record(c, ig)
-            xa, ia = c.fgmres(rhs, rtol=0.0, abstol=0.0, max_it=max_it, restart=restart)
-            g["after"] = _record(c, ia)
-            g["after_x_equal"] = bool(np.array_equal(xa, x7))
-            res["gated"] = g
-    with open(os.path.join(out_dir, "results.json"), "w") as fh:
-        json.dump(res, fh)
+        for _ in R.solved_cases(S, CASES, stack, out_dir, res, _record):
+            pass
 
 
 if __name__ == "__main__":

@@ -7,72 +7,32 @@ every value read is the one a later load would return: the variants and forced f
 
 Each variant runs all cases in ONE fresh child process (tests/_gs_ahead_worker.py): the knob is read per solve, but the
 variants are compared across clean contexts.  Needs a real MI355X: run with -m gpu."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import _gs_ahead_worker as W
+import _gs_rig as R
+from _gs_rig import _hist
 
 pytestmark = pytest.mark.gpu
 
 VARIANTS = ("0", "1", "2")
 
-
-@pytest.fixture(scope="module")
-def runs(tmp_path_factory):
-    """{variant: (results, directory of the x arrays)}; the children run one after the other (the launch needs every one
-    of its workgroups resident)."""
-    out = {}
-    for a in VARIANTS:
-        d = tmp_path_factory.mktemp("gs_ahead_" + a)
-        env = dict(os.environ, SPK_GS_AHEAD=a)
-        env.pop("SPK_GS_KEEP", None)
-        env.pop("SPK_ITER_FORM", None)
-        p = subprocess.run([sys.executable, W.__file__, str(d)], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, f"SPK_GS_AHEAD={a}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}"
-        with open(d / "results.json") as fh:
-            out[a] = (json.load(fh), d)
-        assert out[a][0]["ahead"] == a
-    return out
-
-
-def _hist(r):
-    return np.array([float.fromhex(v) for v in r["history"]])
+runs = R.child_runs("SPK_GS_AHEAD", VARIANTS, W.__file__)
 
 
 @pytest.mark.parametrize("name", list(W.CASES))
 def test_every_variant_is_form_5_bit_for_bit(runs, name):
     """AUTO takes form 7 under every SPK_GS_AHEAD; its residual history and x equal forced form 5 on the same context and
     the other variants' (np.array_equal)."""
-    max_it = W.CASES[name][4]
-    ref, dref = runs[VARIANTS[0]]
-    x0 = np.load(dref / (name + ".npy"))
-    for a in VARIANTS:
-        r, d = runs[a]
-        r = r[name]
-        assert r["form"] == W.GSF and r["form5"]["form"] == W.UN3, (a, r["form"], r["form5"]["form"])
-        assert r["its"] == r["form5"]["its"] == max_it and r["reason"] == r["form5"]["reason"], a
-        assert np.array_equal(_hist(r), _hist(r["form5"])) and r["x_equals_form5"], a
-        assert len(r["history"]) >= max_it
-        if a != VARIANTS[0]:
-            assert np.array_equal(_hist(r), _hist(ref[name])), a
-            assert np.array_equal(np.load(d / (name + ".npy")), x0), a
-    assert np.isfinite(x0).all() and np.isfinite(_hist(ref[name])).all()
+    R.assert_form_5_bit_for_bit(runs, VARIANTS, name, W.CASES[name][4])
 
 
 @pytest.mark.parametrize("a", VARIANTS)
 def test_launches_gated_off_behind_the_end_of_the_solve(runs, a):
     """-ksp_max_it 47 at restart 30: the launches enqueued behind iteration 47 return at the gate with their loads ahead of
     the wait in flight.  The count and the reason are max_it's, and the next solve is the undisturbed one bit for bit."""
-    r = runs[a][0]
-    g = r["gated"]
-    assert g["form"] == W.GSF and g["its"] == 47 and g["reason"] == -3
-    assert g["after"]["its"] == 45 and g["after"]["reason"] == r["full"]["reason"]
-    assert np.array_equal(_hist(g["after"]), _hist(r["full"])) and g["after_x_equal"]
+    R.assert_gated(runs[a][0])
 
 
 @pytest.mark.parametrize("a", VARIANTS)

@@ -6,28 +6,15 @@ Needs a real MI355X: run with -m gpu."""
 import numpy as np
 import pytest
 
+import _gs_rig as R
+from _gs_rig import GSF, UN3, _ctx
 from conftest import relerr
 
 pytestmark = pytest.mark.gpu
 
-UN3, GSF = 5, 7
-
 
 def _system(spk, mx, my, saddle):
-    A, f = spk.AssembleOperator_Laplace(mx, my)
-    if not saddle:
-        return A, None, f
-    B, g = spk.AssembleOperator_Constraints(mx, my)
-    return A, B, np.concatenate([f, g])
-
-
-def _ctx(spk, A, B, fact=3):
-    c = spk.Context(0)
-    c.set_block(spk.BLOCK_A00, A)
-    if B is not None:
-        c.set_block(spk.BLOCK_A10, B)
-    c.pc_setup(spk.PC_SCHUR if B is not None else spk.PC_JACOBI, fact)
-    return c
+    return R._system(spk, (mx, my), saddle)
 
 
 def _three_solves(c, rhs, monkeypatch, restart, max_it=45):
@@ -75,9 +62,7 @@ def test_keep_set_3d_six_constraint_rows(spk, monkeypatch):
     the tile loop, none of them kept; w~ and V_0..V_3 are).  AUTO takes form 7 for it (observed on an MI355X; asserted,
     not forced), with and without the keep set, and the three solves are the same bits."""
     grid = (128, 128, 32)   # 1.57 M rows: fat vectors
-    A, f = spk.AssembleOperator_Laplace3D(*grid, nthreads=16)
-    B, g = spk.AssembleOperator_Constraints3D(*grid)
-    rhs = np.concatenate([f, g])
+    A, B, rhs = R._system(spk, grid, True)
     with _ctx(spk, A, B) as c:
         k, n, u = _three_solves(c, rhs, monkeypatch, 30)
     print(f"3-D {grid}, m = {B.nrows}: AUTO resolved to form {k[2]} (SPK_GS_KEEP=0: {n[2]})")

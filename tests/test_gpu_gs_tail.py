@@ -12,14 +12,9 @@ are the check of the kernel.
 
 Each variant runs all cases in ONE fresh child process (tests/_gs_tail_worker.py): the knob is read per solve, but the
 variants are compared across clean contexts.  Needs a real MI355X: run with -m gpu."""
-import json
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 
+import _gs_rig as R
 import _gs_tail_worker as W
 
 pytestmark = pytest.mark.gpu
@@ -29,26 +24,7 @@ VARIANTS = ("0", "1")
 TAKEN = {"full", "restart4", "restart8", "restart9", "restart12", "restart13", "lower", "real_nodes"}
 
 
-@pytest.fixture(scope="module")
-def runs(tmp_path_factory):
-    """{variant: (results, directory of the x arrays)}; the children run one after the other (the launch needs every one
-    of its workgroups resident)."""
-    out = {}
-    for a in VARIANTS:
-        d = tmp_path_factory.mktemp("gs_tail_" + a)
-        env = dict(os.environ, SPK_GS_TAIL=a)
-        for k in ("SPK_GS_KEEP", "SPK_GS_AHEAD", "SPK_ITER_FORM"):
-            env.pop(k, None)
-        p = subprocess.run([sys.executable, W.__file__, str(d)], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, f"SPK_GS_TAIL={a}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}"
-        with open(d / "results.json") as fh:
-            out[a] = (json.load(fh), d)
-        assert out[a][0]["tail"] == a
-    return out
-
-
-def _hist(r):
-    return np.array([float.fromhex(v) for v in r["history"]])
+runs = R.child_runs("SPK_GS_TAIL", VARIANTS, W.__file__)
 
 
 @pytest.mark.parametrize("name", list(W.CASES))
@@ -56,24 +32,13 @@ def test_every_variant_is_form_5_bit_for_bit(runs, name):
     """AUTO takes form 7 under either SPK_GS_TAIL; its residual history and x equal forced form 5 on the same context and
     the other variant's (np.array_equal).  The remainder is staged exactly where the launcher's condition holds and the
     knob allows it: in every launch of the solve or in none."""
-    max_it = W.CASES[name][4]
-    ref, dref = runs[VARIANTS[0]]
-    x0 = np.load(dref / (name + ".npy"))
+    R.assert_form_5_bit_for_bit(runs, VARIANTS, name, W.CASES[name][4])
     for a in VARIANTS:
-        r, d = runs[a]
-        r = r[name]
-        assert r["form"] == W.GSF and r["form5"]["form"] == W.UN3, (a, r["form"], r["form5"]["form"])
-        assert r["its"] == r["form5"]["its"] == max_it and r["reason"] == r["form5"]["reason"], a
+        r = runs[a][0][name]
         assert W.tail_expected(r["rows"], r["m"]) == (name in TAKEN), (name, r["rows"], r["m"])
         print(f"{name} SPK_GS_TAIL={a}: {r['launches']} launches of form 7, {r['tail']} with the remainder staged")
         assert r["launches"] > 0 and r["form5"]["launches"] == r["form5"]["tail"] == 0, (a, r["launches"])
         assert r["tail"] == (r["launches"] if a == "1" and name in TAKEN else 0), (a, r["tail"], r["launches"])
-        assert np.array_equal(_hist(r), _hist(r["form5"])) and r["x_equals_form5"], a
-        assert len(r["history"]) >= max_it
-        if a != VARIANTS[0]:
-            assert np.array_equal(_hist(r), _hist(ref[name])), a
-            assert np.array_equal(np.load(d / (name + ".npy")), x0), a
-    assert np.isfinite(x0).all() and np.isfinite(_hist(ref[name])).all()
 
 
 @pytest.mark.parametrize("a", VARIANTS)
@@ -81,9 +46,6 @@ def test_launches_gated_off_behind_the_end_of_the_solve(runs, a):
     """-ksp_max_it 47 at restart 30: the launches enqueued behind iteration 47 return at the gate with the remainder's
     loads in flight and nothing staged.  The count and the reason are max_it's, and the next solve is the undisturbed one
     bit for bit."""
-    r = runs[a][0]
-    g = r["gated"]
-    assert g["form"] == W.GSF and g["its"] == 47 and g["reason"] == -3
+    R.assert_gated(runs[a][0])
+    g = runs[a][0]["gated"]
     assert g["tail"] == (g["launches"] if a == "1" else 0) and g["launches"] > 0
-    assert g["after"]["its"] == 45 and g["after"]["reason"] == r["full"]["reason"]
-    assert np.array_equal(_hist(g["after"]), _hist(r["full"])) and g["after_x_equal"]
