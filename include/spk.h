@@ -290,6 +290,32 @@ int spk_assemble_laplace3d_csr(spk_ctx *ctx, int mx, int my, int mz, int64_t row
 /* Wall seconds of the last device assembly's kernels up to a device synchronise (0 before one). */
 int spk_get_assembly_seconds(const spk_ctx *ctx, double *seconds);
 
+/* KSPSetOperators for A10 of the reference's own discretisation, written on the device: what
+ * SpkAssembleOperator_Constraints[3D] (spk_assembly.h) + spk_set_block(SPK_BLOCK_A10) do, without the host arrays.
+ * Kernels write the rank's column slice -- the columns of the rows A00 gave it -- as B by rows, B^T by rows and the
+ * column-window pointers, bit for bit what the host chain uploads, and the rest of spk_set_block's chain runs from
+ * there.  mz == 0: the 2-D block of 4 rows over the mx x my grid, else the 3-D block of 6 rows.  g_dev: m values of
+ * spk_vec_create memory that receive SpkAssembleRHS_Constraints[3D], or NULL.
+ * Refused with the previous B left in place and usable: no A00 yet (SPK_ERR_STATE); a grid side < 3, dof*mx*my[*mz]
+ * that is not A00's n_global, rows of the rank that are not whole node lines (2-D) or planes (3-D) (SPK_ERR_ARG).
+ * Collective like spk_set_block.  A caller's own B still goes through spk_set_block. */
+int spk_set_block_constraints(spk_ctx *ctx, int mx, int my, int mz /* 0: the 2-D block */,
+                              double *g_dev /* m values of spk_vec_create memory, or NULL */);
+/* Test hook: the same kernels on the columns [row_begin,row_end) of any slab of whole node lines / planes, copied to host
+ * arrays.  nnz = SpkConstraintsSlabNnz[3D]: b_colidx, b_val (B by rows, m rows of nnz / m entries each, localised
+ * columns), bt_colidx, bt_val; bt_rowptr: row_end - row_begin + 1; win, nwin: the window width and count; winptr:
+ * (nwin + 1) * m values, refused (SPK_ERR_ARG) beyond winptr_cap.  Touches nothing of the context's operator. */
+int spk_assemble_constraints_csr(spk_ctx *ctx, int mx, int my, int mz, int64_t row_begin, int64_t row_end,
+                                 int32_t *b_colidx, double *b_val, int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val,
+                                 int32_t *win, int32_t *nwin, int32_t *winptr, int64_t winptr_cap);
+/* The same arrays by the host chain of spk_set_block(SPK_BLOCK_A10) over the generator's block: the reference of the
+ * hook above.  Needs neither a context nor a GPU. */
+int spk_host_constraints_csr(int mx, int my, int mz, int64_t row_begin, int64_t row_end,
+                             int32_t *b_colidx, double *b_val, int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val,
+                             int32_t *win, int32_t *nwin, int32_t *winptr, int64_t winptr_cap);
+/* Wall seconds of the last spk_set_block_constraints' kernels up to a device synchronise (0 before one). */
+int spk_get_constraints_seconds(const spk_ctx *ctx, double *seconds);
+
 /* ---- preconditioner (KSPSetUp, SaddlePointProblem.c:68) ------------------ */
 /* Builds diag(A)^-1 and, for SPK_PC_SCHUR, S^ = diag(B diag(A)^-1 B^T). */
 int spk_pc_setup(spk_ctx *ctx, int pc_type, int schur_fact);

@@ -45,6 +45,13 @@ int SpkKSPSetOperatorsLaplace(SpkKSP ksp, int mx, int my, const double *kappa, c
 /* The same for the 3-D generator of spk_assembly.h (spk_set_block_laplace3d): mx x my x mz nodes, dof 3; kappa: one host
  * value per hexahedron, (mx-1)*(my-1)*(mz-1) of them, or NULL for ones. */
 int SpkKSPSetOperatorsLaplace3D(SpkKSP ksp, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host);
+/* The saddle system of the reference's own discretisation without a host matrix: A as SpkKSPSetOperatorsLaplace[3D]
+ * assembles it, and the generator's constraint block (SpkAssembleOperator_Constraints[3D]: 4 rows in 2-D, 6 in 3-D)
+ * written on the device by spk_set_block_constraints.  rhs_host: receives the rank's n_local values of f and, behind
+ * them, the multipliers' right-hand side g (n_local + 4 values, + 6 in 3-D), or NULL.  Grid sides of at least 3.
+ * Leaves the KSP in the state SpkKSPSetOperators(A, B) would; -ksp_view names the route. */
+int SpkKSPSetOperatorsLaplaceConstrained(SpkKSP ksp, int mx, int my, const double *kappa, double *rhs_host);
+int SpkKSPSetOperatorsLaplaceConstrained3D(SpkKSP ksp, int mx, int my, int mz, const double *kappa, double *rhs_host);
 /* The node grid behind the operator of SpkKSPSetOperators: mx x my (x mz; 1 or 0 in 2-D) nodes in natural ordering, bs
  * unknowns per node (the role of KSPSetDM).  -pc_type mg and -fieldsplit_0_pc_type mg coarsen it; without a known grid
  * they are refused at SpkKSPSetUp.  SpkKSPSetOperatorsLaplace / ...3D set it themselves. */

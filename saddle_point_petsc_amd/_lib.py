@@ -203,6 +203,12 @@ def _load():
     L.spk_set_block_laplace3d.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.spk_assemble_laplace3d_csr.argtypes = [vp, C.c_int, C.c_int, C.c_int, i64, i64, vp, C.c_int, C.c_int, i32p, i32p, f64p, vp]
     L.spk_get_assembly_seconds.argtypes = [vp, C.POINTER(dbl)]
+    L.spk_set_block_constraints.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.spk_assemble_constraints_csr.argtypes = [vp, C.c_int, C.c_int, C.c_int, i64, i64, i32p, f64p, i32p, i32p, f64p,
+                                               C.POINTER(i32), C.POINTER(i32), i32p, i64]
+    L.spk_host_constraints_csr.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i32p, f64p, i32p, i32p, f64p,
+                                           C.POINTER(i32), C.POINTER(i32), i32p, i64]
+    L.spk_get_constraints_seconds.argtypes = [vp, C.POINTER(dbl)]
     L.spk_pc_setup.argtypes = [vp, C.c_int, C.c_int]
     L.spk_pc_set_inner.argtypes = [vp, C.c_int, C.c_double]
     L.spk_default_amg_opts.argtypes = [C.POINTER(AmgOpts)]
@@ -292,6 +298,8 @@ def _load():
     L.SpkKSPSetOperators.argtypes = [vp, C.POINTER(MatCSR), C.POINTER(MatCSR)]
     L.SpkKSPSetOperatorsLaplace.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
     L.SpkKSPSetOperatorsLaplace3D.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(MatCSR), vp]
+    L.SpkKSPSetOperatorsLaplaceConstrained.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.SpkKSPSetOperatorsLaplaceConstrained3D.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.SpkKSPSetGrid.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.SpkKSPSetFromOptions.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
     L.SpkKSPSetUp.argtypes = [vp]

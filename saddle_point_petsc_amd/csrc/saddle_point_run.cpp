@@ -8,7 +8,7 @@
 //   saddle_point_run -da_grid_x 257 -da_grid_y 257 -ksp_type fgmres -ksp_rtol 1e-8 \
 //       -pc_type fieldsplit -pc_fieldsplit_type schur -pc_fieldsplit_schur_fact_type full \
 //       -ksp_converged_reason [-saddle 0] [-solution_view] [-no_vtk] [-spk_assembly host|device]
-//       [-spk_basis_precision double|single]
+//       [-spk_constraints host|device] [-spk_basis_precision double|single]
 // (every option of SpkKSPSetFromOptions, include/spk_ksp.h: e.g. -pc_type mg -spk_mg_galerkin stencil -spk_mg_operator
 // stencil -spk_mg_precision single)
 //
@@ -16,6 +16,8 @@
 // grid; that is the default here too.  -saddle 0 solves A u = f alone, as the
 // reference does at HEAD (KSPSetOperators(ksp, A, A), :66).  -spk_assembly device assembles A and f on
 // the GPU (SpkKSPSetOperatorsLaplace) instead of on host threads; the default, host, is the flow above.
+// -spk_constraints device (with -spk_assembly device) writes B and g there as well
+// (SpkKSPSetOperatorsLaplaceConstrained): the saddle system comes up without a host matrix.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -60,6 +62,11 @@ int main(int argc, char **argv)
     const char *route = opt_str(argc, argv, "-spk_assembly", "host");
     const bool on_device = !std::strcmp(route, "device");
     if (!on_device && std::strcmp(route, "host")) { std::fprintf(stderr, "-spk_assembly %s is not supported (host | device)\n", route); return 1; }
+    const char *broute = opt_str(argc, argv, "-spk_constraints", "host");
+    const bool b_on_device = !std::strcmp(broute, "device");
+    if (!b_on_device && std::strcmp(broute, "host")) { std::fprintf(stderr, "-spk_constraints %s is not supported (host | device)\n", broute); return 1; }
+    if (b_on_device && !on_device) { std::fprintf(stderr, "-spk_constraints device needs -spk_assembly device\n"); return 1; }
+    if (b_on_device && !saddle) { std::fprintf(stderr, "-spk_constraints device needs the saddle system (-saddle 1)\n"); return 1; }
     int64_t n = 0, nnz = 0;
     CHK(SpkAssemblySizes(mx, my, &n, &nnz));
 
@@ -82,6 +89,9 @@ int main(int argc, char **argv)
     if (saddle) {
         const int64_t bn = SpkConstraintsSlabNnz(mx, my, 0, n);
         if (bn < 0) { std::fprintf(stderr, "grid too small for the constraint block\n"); return 1; }
+    }
+    if (saddle && !b_on_device) {
+        const int64_t bn = SpkConstraintsSlabNnz(mx, my, 0, n);
         bci.resize((size_t)bn);
         bv.resize((size_t)bn);
         CHK(SpkAssembleOperator_Constraints(mx, my, 0, n, brp.data(), bci.data(), bv.data()));
@@ -91,7 +101,8 @@ int main(int argc, char **argv)
 
     // the call site SaddlePointProblem.c:65-72
     CHK(SpkKSPCreate(opt_int(argc, argv, "-spk_device", 0), &ksp));
-    if (on_device) CHK(SpkKSPSetOperatorsLaplace(ksp, mx, my, nullptr, saddle ? &B : nullptr, rhs.data()));
+    if (b_on_device) CHK(SpkKSPSetOperatorsLaplaceConstrained(ksp, mx, my, nullptr, rhs.data()));
+    else if (on_device) CHK(SpkKSPSetOperatorsLaplace(ksp, mx, my, nullptr, saddle ? &B : nullptr, rhs.data()));
     else CHK(SpkKSPSetOperators(ksp, &A, saddle ? &B : nullptr));
     CHK(SpkKSPSetGrid(ksp, mx, my, 1));   // the DMDA's grid: what -pc_type mg coarsens
     CHK(SpkKSPSetFromOptions(ksp, argc - 1, argv + 1));

@@ -324,6 +324,45 @@ int spk_get_assembly_seconds(const spk_ctx *c, double *seconds)
     return SPK_OK;
 }
 
+int spk_set_block_constraints(spk_ctx *c, int mx, int my, int mz, double *g_dev)
+{
+    SPK_TRY(c)
+    spk::set_block_constraints(c, mx, my, mz, g_dev);
+    SPK_CATCH(c)
+}
+
+int spk_assemble_constraints_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                                 int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                                 int64_t winptr_cap)
+{
+    SPK_TRY(c)
+    spk::assemble_constraints_csr(c, mx, my, mz, row_begin, row_end, b_colidx, b_val, bt_rowptr, bt_colidx, bt_val, win, nwin, winptr,
+                                  winptr_cap);
+    SPK_CATCH(c)
+}
+
+int spk_host_constraints_csr(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                             int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                             int64_t winptr_cap)
+{
+    try {
+        spk::host_constraints_csr(mx, my, mz, row_begin, row_end, b_colidx, b_val, bt_rowptr, bt_colidx, bt_val, win, nwin, winptr,
+                                  winptr_cap);
+    } catch (const spk::Error &e) {
+        return e.code;
+    } catch (const std::exception &) {
+        return SPK_ERR_NOMEM;
+    }
+    return SPK_OK;
+}
+
+int spk_get_constraints_seconds(const spk_ctx *c, double *seconds)
+{
+    if (!c || !seconds) return SPK_ERR_ARG;
+    *seconds = c->constraints_seconds;
+    return SPK_OK;
+}
+
 int spk_pc_setup(spk_ctx *c, int pc_type, int schur_fact)
 {
     SPK_TRY(c)

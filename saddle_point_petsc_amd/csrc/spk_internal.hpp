@@ -506,6 +506,11 @@ void assemble_laplace3d(int mx, int my, int mz, int k0, int k1, const double *ka
                         double *val, double *f, hipStream_t s);
 int64_t assemble_laplace3d_grid(int mx, int my, int k0, int k1);
 void kappa_check(const double *kappa, int64_t ne, int32_t *flag, hipStream_t s);   // flag[0] := 1 for an entry not finite and > 0
+// spk_k_constraints.hip: the constraint block of node lines (mz == 0) or planes [u0, u1) of the grid, bit for bit the host
+// chain's: B by rows with localised columns (bcol, bval), B^T by rows (trp: local rows + 1, tci, tv) and the window
+// pointers ((nwin + 1) x m, m = 4 or 6) for windows of `win` columns.
+void assemble_constraints(int mx, int my, int mz, int u0, int u1, int32_t *bcol, double *bval, int32_t *trp, int32_t *tci, double *tv,
+                          int32_t win, int32_t nwin, int32_t *winptr, hipStream_t s);
 // f.out[r] = B_r . x, r < m
 void wide_dot(const WideDev &B, const double *x, const Finish &f, const int32_t *done, hipStream_t s,
               const int32_t *rowmap = nullptr);
@@ -1108,6 +1113,7 @@ struct spk_ctx {
     std::vector<double> schur_S;           // S as factored (host, m x m)
     double schur_setup_seconds = 0.0;      // what W, S and the factor added to the last set-up
     double assembly_seconds = 0.0;         // the kernels of the last device assembly, up to a device synchronise
+    double constraints_seconds = 0.0;      // the same of the last set_block_constraints
     spk::k::SchurW schur_w() const { return spk::k::SchurW{amg_d ? sw.p : bd.p, ld, m, sfac.p}; }
     // FP32 inner solve (0 sweeps = plain diag(A)^-1)
     int inner_sweeps = 0;
@@ -1242,6 +1248,17 @@ void set_block_laplace(spk_ctx *c, int mx, int my, int mz, const double *kappa, 
 void assemble_laplace_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, const double *kappa, int kappa_mem,
                           int apply_bc, int32_t *rowptr, int32_t *colidx, double *val, double *f);
 int laplace_mz3(int mx, int my, int mz);
+// A10 of the reference's own discretisation (SpkAssembleOperator_Constraints[3D]) written on the device for the rows A00
+// gave this rank, then set_block(A10)'s chain; g into g_dev (m values, or null).  mz == 0: the 2-D block.
+// assemble_constraints_csr: the kernels' arrays of any slab back on the host (a test hook); host_constraints_csr: the same
+// arrays by the host chain, without a GPU.
+void set_block_constraints(spk_ctx *c, int mx, int my, int mz, double *g_dev);
+void assemble_constraints_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                              int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                              int64_t winptr_cap);
+void host_constraints_csr(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                          int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                          int64_t winptr_cap);
 
 // The host side of the frame MINRES and pipelined CG share (spk_minres.cpp, spk_pipecg.cpp).  The host only ENQUEUES
 // iterations, each gated by the state's `done` word; the scalar steps run on the device.  The state is copied into a

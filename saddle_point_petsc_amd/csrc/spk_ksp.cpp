@@ -37,6 +37,7 @@ struct SpkKSP_s {
     bool have_ops = false, is_setup = false, has_B = false;
     bool ops_device = false;   // the last KSPSetOperators assembled A00 on the device (-ksp_view)
     bool ops_device_3d = false;   // ... with the 3-D generator's kernel
+    bool ops_device_B = false;    // ... and wrote the constraint block there too (SpkKSPSetOperatorsLaplaceConstrained[3D])
     int32_t n_rows_B = 0;   // m (-ksp_view)
     // PETSc's own defaults (-ksp_type gmres with left preconditioning, -pc_type ilu / bjacobi+ilu) are
     // not implemented here: a run that leaves them unset must be refused, not silently changed
@@ -271,13 +272,17 @@ int SpkKSPSetCommRCCL(SpkKSP k, int rank, int nranks, const void *id128)
 }
 
 // what follows A00 in KSPSetOperators on either route: the constraint block, then the facade's state
-static int set_operators_tail(SpkKSP k, const SpkMatCSR *B, bool device)
+static int set_operators_tail(SpkKSP k, const SpkMatCSR *B, bool device, int device_B_rows = 0)
 {
     int rc = SPK_OK;
     k->ops_device = device;
+    k->ops_device_B = device_B_rows > 0;
     k->has_B = false;
     k->n_rows_B = 0;
-    if (B) {
+    if (device_B_rows > 0) {   // (spk_set_block_constraints has run)
+        k->has_B = true;
+        k->n_rows_B = device_B_rows;
+    } else if (B) {
         rc = spk_set_block(k->ctx, SPK_BLOCK_A10, 0, B->nrows_local, B->ncols_global, B->rowptr, B->colidx, B->val);
         if (rc != SPK_OK) return from_ctx(k, rc);
         k->has_B = B->nrows_local > 0;
@@ -300,7 +305,9 @@ int SpkKSPSetOperators(SpkKSP k, const SpkMatCSR *A, const SpkMatCSR *B)
 }
 
 // A00 assembled on the device, mz == 0: the 2-D grid (spk_set_block_laplace), else the 3-D generator's
-static int set_operators_device(SpkKSP k, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host)
+// device_B: the generator's constraint block written on the device as well (spk_set_block_constraints), g behind f in f_host
+static int set_operators_device(SpkKSP k, int mx, int my, int mz, const double *kappa, const SpkMatCSR *B, double *f_host,
+                                bool device_B = false)
 {
     if (!k) return SPK_ERR_ARG;
     int rc = ensure_ctx(k);
@@ -319,10 +326,18 @@ static int set_operators_device(SpkKSP k, int mx, int my, int mz, const double *
         spk_get_sizes(k->ctx, nullptr, &nl, nullptr, nullptr, nullptr);
         rc = spk_vec_get(k->ctx, fd, f_host, nl);
     }
+    int32_t nl = 0;
+    if (rc == SPK_OK && device_B) {
+        const int m = mz ? 6 : 4;
+        spk_get_sizes(k->ctx, nullptr, &nl, nullptr, nullptr, nullptr);
+        // (fd holds at least m values: a grid the block accepts has more rows than that; g overwrites f there once f is out)
+        rc = spk_set_block_constraints(k->ctx, mx, my, mz, fd);
+        if (rc == SPK_OK && fd) rc = spk_vec_get(k->ctx, fd, f_host + nl, m);
+    }
     if (rc != SPK_OK) from_ctx(k, rc);   // (the message, before the clean-up can replace it)
     if (fd) spk_vec_destroy(k->ctx, fd);
     if (rc != SPK_OK) return rc;
-    rc = set_operators_tail(k, B, true);
+    rc = set_operators_tail(k, B, true, device_B ? (mz ? 6 : 4) : 0);
     if (rc == SPK_OK) k->ops_device_3d = mz != 0;
     if (rc == SPK_OK) k->grid[0] = mx, k->grid[1] = my, k->grid[2] = mz ? mz : 1;
     return rc;
@@ -348,6 +363,17 @@ int SpkKSPSetOperatorsLaplace3D(SpkKSP k, int mx, int my, int mz, const double *
 {
     if (k && mz == 0) return set_err(k, SPK_ERR_ARG, "KSPSetOperatorsLaplace3D: mz = 0 (at least 2 x 2 x 2 nodes)");
     return set_operators_device(k, mx, my, mz, kappa, B, f_host);
+}
+
+int SpkKSPSetOperatorsLaplaceConstrained(SpkKSP k, int mx, int my, const double *kappa, double *rhs_host)
+{
+    return set_operators_device(k, mx, my, 0, kappa, nullptr, rhs_host, true);
+}
+
+int SpkKSPSetOperatorsLaplaceConstrained3D(SpkKSP k, int mx, int my, int mz, const double *kappa, double *rhs_host)
+{
+    if (k && mz == 0) return set_err(k, SPK_ERR_ARG, "KSPSetOperatorsLaplaceConstrained3D: mz = 0 (at least 3 x 3 x 3 nodes)");
+    return set_operators_device(k, mx, my, mz, kappa, nullptr, rhs_host, true);
 }
 
 int SpkKSPSetFromOptions(SpkKSP k, int argc, const char *const *argv)
@@ -669,6 +695,10 @@ int SpkKSPSolve(SpkKSP k, const double *b, double *x)
         if (k->ops_device && k->ops_device_3d) std::printf("  A00: assembled on the device (SpkKSPSetOperatorsLaplace3D), kernels %.6f s\n", secs);
         else if (k->ops_device) std::printf("  A00: assembled on the device (-spk_assembly device), kernels %.6f s\n", secs);
         else std::printf("  A00: the caller's host arrays (-spk_assembly host)\n");
+        if (k->ops_device_B) {
+            spk_get_constraints_seconds(k->ctx, &secs);
+            std::printf("  A10: written on the device (-spk_constraints device), kernels %.6f s\n", secs);
+        }
     }
     if (k->view && k->pc_type == SPK_PC_SCHUR) {
         double secs = 0.0;

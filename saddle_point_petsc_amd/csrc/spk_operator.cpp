@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "spk_internal.hpp"
+#include "spk_constraints_core.hpp"
 #include "../../include/spk_assembly.h"
 
 namespace spk {
@@ -571,6 +572,7 @@ static void set_block_A(spk_ctx *c, int64_t row_begin, int32_t nrows_local, int6
 // KSPSetOperators, A10: this rank's column slice of the constraint block
 // ---------------------------------------------------------------------------
 // Column windows over the wide rows (concatenated in `wide` order); for m <= 8 every row, in order: the arrays as they are.
+constexpr int32_t kWideRowNnz = 8192;   // a general block's rows beyond this many local entries take the window kernel
 static void b_windows(spk_ctx *c, int32_t m, const int32_t *rowptr, const int32_t *col, const double *v, const std::vector<int32_t> &wide)
 {
     WideDev &B = c->B;
@@ -597,46 +599,63 @@ static void b_windows(spk_ctx *c, int32_t m, const int32_t *rowptr, const int32_
     B.winptr.upload(winptr.data(), winptr.size(), 8);
 }
 
-static void set_block_B(spk_ctx *c, int32_t m, int64_t ncols_global, const int32_t *rowptr,
-                        const int32_t *colidx, const double *val)
+// the rows that take the window kernel (wide_rows, spk_host.cpp), into the context
+static void b_install_wide(spk_ctx *c, const std::vector<int32_t> &wide)
 {
-    if (!c->have_A) fail(SPK_ERR_STATE, "A10: set SPK_BLOCK_A00 first");
-    c->bt_cached = nullptr;
-    if (ncols_global != c->n_global) fail(SPK_ERR_ARG, "A10: %lld columns, A00 has %lld", (long long)ncols_global, (long long)c->n_global);
-    if (m < 0) fail(SPK_ERR_ARG, "A10: negative row count");
-    if ((int64_t)c->n_local + m > INT32_MAX - 1024) fail(SPK_ERR_UNSUPPORTED, "A10: n_local + m exceeds 32-bit vector indices");
-    for (int32_t r = 0; r < m; ++r)
-        if (rowptr[r + 1] < rowptr[r]) fail(SPK_ERR_ARG, "A10: rowptr not monotone at row %d", r);
+    c->m_wide = (int32_t)wide.size();
+    c->wide_rows_h = wide;
+    c->wide_rows.upload(wide.data(), wide.size(), 8);
+}
+
+static void b_release_general(spk_ctx *c)
+{
+    c->Bc.rowptr.release(); c->Bc.colidx.release(); c->Bc.val.release(); c->Bc.tile_row.release();
+    c->Bc.nrows = c->Bc.ncols = c->Bc.ntiles = 0;
+    c->Bc.nnz = 0;
+}
+
+// One source of the block: the caller's arrays, localised, windowed and transposed on the host and uploaded
+static void b_bring_upload(spk_ctx *c, int32_t m, const int32_t *rowptr, const int32_t *colidx, const double *val)
+{
     const int32_t nl = c->n_local;
     HostBuf<int32_t> col;
     HostBuf<double> v;
     col.alloc((size_t)rowptr[m]);
     v.alloc((size_t)rowptr[m]);
     localise_and_sort(m, rowptr, colidx, val, c->row_begin, c->row_begin + nl, col.data(), v.data());
-    constexpr int32_t kWideRowNnz = 8192;   // a general block's rows beyond this many local entries take the window kernel
     c->b_general = m > 8;
     const std::vector<int32_t> wide = wide_rows(m, rowptr, kWideRowNnz);
-    c->m_wide = (int32_t)wide.size();
-    c->wide_rows_h = wide;
-    c->wide_rows.upload(wide.data(), wide.size(), 8);
+    b_install_wide(c, wide);
     b_windows(c, m, rowptr, col.data(), v.data(), wide);
     // the general block by rows (its long rows left empty: the window kernel fills their results in)
-    c->Bc.rowptr.release(); c->Bc.colidx.release(); c->Bc.val.release(); c->Bc.tile_row.release();
-    c->Bc.nrows = c->Bc.ncols = c->Bc.ntiles = 0;
-    c->Bc.nnz = 0;
+    b_release_general(c);
     if (c->b_general) {
         std::vector<int32_t> crp, cci;
         std::vector<double> cv;
         gather_rows(m, rowptr, col.data(), v.data(), wide, true, crp, cci, cv);
         upload_csr(c, c->Bc, m, nl, crp, cci, cv, true);
     }
-    if ((size_t)m + 64 > c->y1tmp.n) c->y1tmp.alloc((size_t)m + 64);
-    if ((size_t)m + 64 > c->ttmp.n) c->ttmp.alloc((size_t)m + 64);
     // B^T by rows (n_local x m), entries of a row ordered by constraint index
     std::vector<int32_t> trp((size_t)nl + 1, 0), tci((size_t)rowptr[m]);
     std::vector<double> tv((size_t)rowptr[m]);
     transpose_rows(m, nl, rowptr, col.data(), v.data(), trp.data(), tci.data(), tv.data());
     upload_csr(c, c->Bt, nl, m, trp, tci, tv, c->b_general);   // (a general block: tiles for the stream kernel)
+}
+
+// One chain for both sources of the block.  prepare(): the source's own refusals, before anything of the previous block
+// is touched; bring(): c->B, c->Bt (a general block: c->Bc), b_general and the wide rows, in device memory.
+template <class Prepare, class Bring>
+static void set_block_B(spk_ctx *c, int32_t m, int64_t ncols_global, Prepare prepare, Bring bring)
+{
+    if (!c->have_A) fail(SPK_ERR_STATE, "A10: set SPK_BLOCK_A00 first");
+    c->bt_cached = nullptr;
+    if (ncols_global != c->n_global) fail(SPK_ERR_ARG, "A10: %lld columns, A00 has %lld", (long long)ncols_global, (long long)c->n_global);
+    if (m < 0) fail(SPK_ERR_ARG, "A10: negative row count");
+    if ((int64_t)c->n_local + m > INT32_MAX - 1024) fail(SPK_ERR_UNSUPPORTED, "A10: n_local + m exceeds 32-bit vector indices");
+    prepare();
+    bring();
+    if ((size_t)m + 64 > c->y1tmp.n) c->y1tmp.alloc((size_t)m + 64);
+    if ((size_t)m + 64 > c->ttmp.n) c->ttmp.alloc((size_t)m + 64);
     c->m = m;
     c->have_B = m > 0;
     c->pc_ready = false;
@@ -657,7 +676,12 @@ void set_block(spk_ctx *c, int which, int64_t row_begin, int32_t nrows_local, in
     else if (which == SPK_BLOCK_A10)
         // no collective inside, but every rank sets its column slice: agree on the outcome so that a rank
         // whose slice was refused does not leave the others to run into the next collective alone
-        agree_or_fail(c, locally([&] { set_block_B(c, nrows_local, ncols_global, rowptr, colidx, val); }), "A10");
+        agree_or_fail(c, locally([&] {
+            set_block_B(c, nrows_local, ncols_global, [&] {
+                for (int32_t r = 0; r < nrows_local; ++r)
+                    if (rowptr[r + 1] < rowptr[r]) fail(SPK_ERR_ARG, "A10: rowptr not monotone at row %d", r);
+            }, [&] { b_bring_upload(c, nrows_local, rowptr, colidx, val); });
+        }), "A10");
     else fail(SPK_ERR_ARG, "set_block: unknown block %d", which);
 }
 
@@ -751,6 +775,134 @@ void assemble_laplace_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin,
     SPK_HIP(hipMemcpy(colidx, in.colidx.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
     SPK_HIP(hipMemcpy(val, in.val.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
     if (f) SPK_HIP(hipMemcpy(f, fd.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------------------
+// KSPSetOperators, A10 of the reference's own discretisation: the column slice written on the device
+// ---------------------------------------------------------------------------
+namespace cs = spk::constraints;
+
+// the refusals that need no GPU; returns the slab (mz == 0: the 2-D grid)
+static cs::Slab constraints_slab(int mx, int my, int mz, int64_t row_begin, int64_t row_end)
+{
+    if (mx < 3 || my < 3 || (mz != 0 && mz < 3)) {
+        if (mz) fail(SPK_ERR_ARG, "device constraints: a grid of %d x %d x %d nodes (at least 3 x 3 x 3)", mx, my, mz);
+        fail(SPK_ERR_ARG, "device constraints: a grid of %d x %d nodes (at least 3 x 3)", mx, my);
+    }
+    const LaplaceGrid lg{mx, my, mz};
+    if (lg.rows() > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device constraints: %lld columns exceed 32-bit indices", (long long)lg.rows());
+    const int64_t nnz = mz ? SpkConstraintsSlabNnz3D(mx, my, mz, row_begin, row_end) : SpkConstraintsSlabNnz(mx, my, row_begin, row_end);
+    if (nnz < 0)
+        fail(SPK_ERR_ARG, "device constraints: rows [%lld,%lld) are not whole node %s of the grid", (long long)row_begin, (long long)row_end,
+             lg.unit_name());
+    if (nnz > INT32_MAX) fail(SPK_ERR_UNSUPPORTED, "device constraints: %lld stored non-zeros of the slice exceed 32-bit indices", (long long)nnz);
+    const cs::Slab g{mx, my, mz, (int)(row_begin / lg.unit_rows()), (int)(row_end / lg.unit_rows())};
+    if (cs::nnz(g) != nnz) fail(SPK_ERR_STATE, "device constraints: the closed-form entry count disagrees with the generator's");
+    return g;
+}
+
+// B, B^T and the window pointers of the slab into fresh device arrays, with the pads of the host route's uploads
+static void constraints_fill(spk_ctx *c, const cs::Slab &g, WideDev &B, CsrDev &Bt)
+{
+    hipStream_t s = c->stream;
+    const int32_t m = cs::rows(g), nl = (int32_t)cs::local_cols(g);
+    const int64_t nnz = cs::nnz(g);
+    B.m = m;
+    B.ncols = nl;
+    B.nnz = nnz;
+    B.win = window_width(nl, k::kMaxBlocks);
+    B.nwin = (nl + B.win - 1) / B.win;
+    B.colidx.alloc_raw((size_t)nnz, 16);
+    B.val.alloc_raw((size_t)nnz, 16);
+    B.winptr.alloc_raw((size_t)(B.nwin + 1) * (size_t)m, 8);
+    Bt.nrows = nl;
+    Bt.ncols = m;
+    Bt.nnz = nnz;
+    Bt.rowptr.alloc_raw((size_t)nl + 1, 8);
+    Bt.colidx.alloc_raw((size_t)nnz, 16);
+    Bt.val.alloc_raw((size_t)nnz, 16);
+    SPK_HIP(hipStreamSynchronize(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    k::assemble_constraints(g.mx, g.my, g.mz, g.u0, g.u1, B.colidx.p, B.val.p, Bt.rowptr.p, Bt.colidx.p, Bt.val.p, B.win, B.nwin,
+                            B.winptr.p, s);
+    SPK_HIP(hipStreamSynchronize(s));
+    c->constraints_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void set_block_constraints(spk_ctx *c, int mx, int my, int mz, double *g_dev)
+{
+    c->ensure_scratch();
+    // every rank fills the column slice of the rows A00 gave it; agreed on as set_block(A10) is
+    agree_or_fail(c, locally([&] {
+        cs::Slab g{};
+        const int32_t m = mz ? 6 : 4;
+        set_block_B(c, m, (int64_t)(mz ? 3 : 2) * mx * my * (mz ? mz : 1),
+                    [&] { g = constraints_slab(mx, my, mz, c->row_begin, c->row_begin + c->n_local); },
+                    [&] {
+                        c->b_general = false;
+                        std::vector<int32_t> wide((size_t)m);
+                        for (int32_t r = 0; r < m; ++r) wide[(size_t)r] = r;
+                        b_install_wide(c, wide);
+                        b_release_general(c);
+                        constraints_fill(c, g, c->B, c->Bt);
+                    });
+        if (g_dev) {
+            double gh[6];
+            if ((mz ? SpkAssembleRHS_Constraints3D(gh) : SpkAssembleRHS_Constraints(gh)) != SPK_OK) fail(SPK_ERR_STATE, "device constraints: g");
+            SPK_HIP(hipMemcpy(g_dev, gh, sizeof(double) * (size_t)m, hipMemcpyHostToDevice));
+        }
+    }), "A10 (device)");
+}
+
+void assemble_constraints_csr(spk_ctx *c, int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                              int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                              int64_t winptr_cap)
+{
+    if (!b_colidx || !b_val || !bt_rowptr || !bt_colidx || !bt_val || !win || !nwin || !winptr)
+        fail(SPK_ERR_ARG, "assemble_constraints_csr: null array");
+    const cs::Slab g = constraints_slab(mx, my, mz, row_begin, row_end);
+    WideDev B;
+    CsrDev Bt;
+    const double keep = c->constraints_seconds;
+    constraints_fill(c, g, B, Bt);
+    c->constraints_seconds = keep;   // (a test hook: the context's last figure is the operator's)
+    const size_t nw = (size_t)(B.nwin + 1) * (size_t)B.m;
+    if ((int64_t)nw > winptr_cap) fail(SPK_ERR_ARG, "assemble_constraints_csr: %zu window pointers, room for %lld", nw, (long long)winptr_cap);
+    *win = B.win;
+    *nwin = B.nwin;
+    SPK_HIP(hipMemcpy(b_colidx, B.colidx.p, sizeof(int32_t) * (size_t)B.nnz, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(b_val, B.val.p, sizeof(double) * (size_t)B.nnz, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(winptr, B.winptr.p, sizeof(int32_t) * nw, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(bt_rowptr, Bt.rowptr.p, sizeof(int32_t) * ((size_t)Bt.nrows + 1), hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(bt_colidx, Bt.colidx.p, sizeof(int32_t) * (size_t)Bt.nnz, hipMemcpyDeviceToHost));
+    SPK_HIP(hipMemcpy(bt_val, Bt.val.p, sizeof(double) * (size_t)Bt.nnz, hipMemcpyDeviceToHost));
+}
+
+// The same arrays by the host chain (the generator, localise_and_sort, window_pointers, transpose_rows): what
+// set_block(A10) uploads for the generated block.  Needs no GPU; the reference of the tests and of tools/assembly_bench.py.
+void host_constraints_csr(int mx, int my, int mz, int64_t row_begin, int64_t row_end, int32_t *b_colidx, double *b_val,
+                          int32_t *bt_rowptr, int32_t *bt_colidx, double *bt_val, int32_t *win, int32_t *nwin, int32_t *winptr,
+                          int64_t winptr_cap)
+{
+    if (!b_colidx || !b_val || !bt_rowptr || !bt_colidx || !bt_val || !win || !nwin || !winptr)
+        fail(SPK_ERR_ARG, "host_constraints_csr: null array");
+    const int64_t nnz = mz ? SpkConstraintsSlabNnz3D(mx, my, mz, row_begin, row_end) : SpkConstraintsSlabNnz(mx, my, row_begin, row_end);
+    if (nnz < 0 || nnz > INT32_MAX || row_end - row_begin > INT32_MAX) fail(SPK_ERR_ARG, "host_constraints_csr: not a slab of the grid");
+    const int32_t m = mz ? 6 : 4, nl = (int32_t)(row_end - row_begin);
+    std::vector<int32_t> rowptr((size_t)m + 1), colidx((size_t)nnz + 1);   // (+ 1: the generator refuses a null array)
+    std::vector<double> val((size_t)nnz + 1);
+    const int rc = mz ? SpkAssembleOperator_Constraints3D(mx, my, mz, row_begin, row_end, rowptr.data(), colidx.data(), val.data())
+                      : SpkAssembleOperator_Constraints(mx, my, row_begin, row_end, rowptr.data(), colidx.data(), val.data());
+    if (rc != SPK_OK) fail(rc, "host_constraints_csr: the generator refused");
+    localise_and_sort(m, rowptr.data(), colidx.data(), val.data(), row_begin, row_end, b_colidx, b_val);
+    const std::vector<int32_t> wide = wide_rows(m, rowptr.data(), kWideRowNnz);
+    if ((int32_t)wide.size() != m) fail(SPK_ERR_STATE, "host_constraints_csr: wide rows");
+    *win = window_width(nl, k::kMaxBlocks);
+    *nwin = (nl + *win - 1) / *win;
+    if ((int64_t)(*nwin + 1) * m > winptr_cap) fail(SPK_ERR_ARG, "host_constraints_csr: room for %lld window pointers", (long long)winptr_cap);
+    window_pointers(m, rowptr.data(), b_colidx, nl, *win, *nwin, winptr);
+    std::fill(bt_rowptr, bt_rowptr + nl + 1, 0);
+    transpose_rows(m, nl, rowptr.data(), b_colidx, b_val, bt_rowptr, bt_colidx, bt_val);
 }
 
 // ---------------------------------------------------------------------------

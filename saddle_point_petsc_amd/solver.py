@@ -615,6 +615,35 @@ class Context:
         return self._assemble_laplace_csr(lib.spk_assemble_laplace3d_csr, lib.SpkAssemblySlabNnz3D, (mx, my, mz), 3, "planes", row_begin,
                                           row_end, kappa, apply_bc)
 
+    def set_block_constraints(self, mx, my=None, mz=0, rhs=None):
+        """KSPSetOperators for A10 of the reference's own discretisation, written on the device (spk_set_block_constraints):
+        what AssembleOperator_Constraints[3D] + set_block(BLOCK_A10, B) do for this rank's column slice, without the host
+        arrays.  mz = 0: the 2-D block (4 rows), else the 3-D block (6 rows).  rhs: a device vector of vec_create (m values)
+        that receives g, or True to get g back as a numpy array."""
+        my = mx if my is None else my
+        if rhs is not True:
+            self._chk(lib.spk_set_block_constraints(self.h, mx, my, mz, rhs))
+            return None
+        gd = self.vec_create(n=8)
+        try:
+            self._chk(lib.spk_set_block_constraints(self.h, mx, my, mz, gd))
+            return self.vec_get(gd, 6 if mz else 4)
+        finally:
+            self.vec_destroy(gd)
+
+    def assemble_constraints_csr(self, mx, my=None, mz=0, row_begin=0, row_end=None):
+        """Test hook (spk_assemble_constraints_csr): the arrays the constraint kernels write for the columns
+        [row_begin,row_end) -- whole node lines, or planes with mz -- as a dict: b_colidx, b_val (B by rows, localised
+        columns), bt_rowptr, bt_colidx, bt_val (B^T by rows), win, nwin, winptr ((nwin + 1) x m).  Touches nothing of the
+        context's operator."""
+        return constraints_csr(mx, my, mz, row_begin, row_end, ctx=self)
+
+    def constraints_seconds(self):
+        """Wall seconds of the kernels of the last set_block_constraints, up to a device synchronise (0 before one)."""
+        v = C.c_double()
+        self._chk(lib.spk_get_constraints_seconds(self.h, C.byref(v)))
+        return v.value
+
     def assembly_seconds(self):
         """Wall seconds of the kernels of the last set_block_laplace, up to a device synchronise (0 before one)."""
         v = C.c_double()
@@ -967,6 +996,34 @@ def _time_kernel(self, which, nv=0, warmup=5, reps=50):
 Context.time_kernel = _time_kernel
 
 
+def constraints_csr(mx, my=None, mz=0, row_begin=0, row_end=None, ctx=None):
+    """The arrays KSPSetOperators keeps of the generator's constraint block over the columns [row_begin,row_end), as a
+    dict (Context.assemble_constraints_csr).  ctx None: by the host chain of set_block(BLOCK_A10)
+    (spk_host_constraints_csr; no GPU); a Context: by the device kernels."""
+    my = mx if my is None else my
+    dof = 3 if mz else 2
+    n = dof * mx * my * (mz if mz else 1)
+    row_end = n if row_end is None else row_end
+    nnz = lib.SpkConstraintsSlabNnz3D(mx, my, mz, row_begin, row_end) if mz else lib.SpkConstraintsSlabNnz(mx, my, row_begin, row_end)
+    if nnz < 0:
+        raise SpkError(-1, f"columns must be whole node {'planes' if mz else 'lines'} of a grid with sides of at least 3")
+    nl, m = row_end - row_begin, 2 * dof
+    cap = (nl // 1024 + 2) * m   # (windows are at least 1024 columns wide)
+    out = dict(b_colidx=np.zeros(nnz, np.int32), b_val=np.zeros(nnz), bt_rowptr=np.zeros(nl + 1, np.int32),
+               bt_colidx=np.zeros(nnz, np.int32), bt_val=np.zeros(nnz))
+    win, nwin, winptr = C.c_int32(), C.c_int32(), np.zeros(cap, np.int32)
+    args = (mx, my, mz, row_begin, row_end, out["b_colidx"], out["b_val"], out["bt_rowptr"], out["bt_colidx"], out["bt_val"],
+            C.byref(win), C.byref(nwin), winptr, cap)
+    if ctx is None:
+        rc = lib.spk_host_constraints_csr(*args)
+        if rc != 0:
+            raise SpkError(rc, "spk_host_constraints_csr")
+    else:
+        ctx._chk(lib.spk_assemble_constraints_csr(ctx.h, *args))
+    out.update(win=win.value, nwin=nwin.value, winptr=winptr[:(nwin.value + 1) * m].reshape(nwin.value + 1, m).copy())
+    return out
+
+
 def _mat(A):
     m = MatCSR()
     m.row_begin, m.nrows_local, m.ncols_global = A.row_begin, A.nrows, A.ncols
@@ -1002,10 +1059,13 @@ class KSP:
 
     def setOperatorsLaplace(self, mx, my=None, kappa=None, B=None, with_rhs=True):
         """setOperators with A of the reference's own discretisation assembled on the device (SpkKSPSetOperatorsLaplace);
-        kappa: None or one host value per element.  Returns f (numpy) when with_rhs."""
+        kappa: None or one host value per element.  Returns f (numpy) when with_rhs.  B="device": the generator's
+        constraint block written on the device as well (SpkKSPSetOperatorsLaplaceConstrained); returns f followed by g."""
         from .assembly import element_kappa
         my = mx if my is None else my
         k = element_kappa(mx, my, kappa)
+        if isinstance(B, str):
+            return self._set_operators_constrained(lib.SpkKSPSetOperatorsLaplaceConstrained, (mx, my), 2, k, B, with_rhs)
         b = _mat(B) if B is not None else None
         f = np.zeros(2 * mx * my if 2 <= mx and 2 <= my and 2 * mx * my < 2 ** 31 else 1) if with_rhs else None
         self._chk(lib.SpkKSPSetOperatorsLaplace(self.h, mx, my, k.ctypes.data if k is not None else None,
@@ -1018,11 +1078,13 @@ class KSP:
 
     def setOperatorsLaplace3D(self, mx, my=None, mz=None, kappa=None, B=None, with_rhs=True):
         """setOperatorsLaplace for the 3-D generator (SpkKSPSetOperatorsLaplace3D); kappa: None or one host value per
-        hexahedron.  Returns f (numpy) when with_rhs."""
+        hexahedron.  Returns f (numpy) when with_rhs.  B="device": as in setOperatorsLaplace, the six rows of the 3-D block."""
         from .assembly import element_kappa3d
         my = mx if my is None else my
         mz = mx if mz is None else mz
         k = element_kappa3d(mx, my, mz, kappa)
+        if isinstance(B, str):
+            return self._set_operators_constrained(lib.SpkKSPSetOperatorsLaplaceConstrained3D, (mx, my, mz), 3, k, B, with_rhs)
         b = _mat(B) if B is not None else None
         n = 3 * mx * my * mz
         f = np.zeros(n if min(mx, my, mz) >= 2 and n < 2 ** 31 else 1) if with_rhs else None
@@ -1033,6 +1095,19 @@ class KSP:
         lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
         self._n = nl.value + (B.nrows if B is not None else 0)
         return f[:nl.value] if with_rhs else None
+
+    def _set_operators_constrained(self, fn, grid, dof, k, B, with_rhs):
+        """setOperatorsLaplace / ...3D with B="device": fn is the facade's entry point for the grid"""
+        if B != "device":
+            raise ValueError(f'B = {B!r}: a CSR block, None or "device"')
+        n, m = dof * math.prod(grid), 2 * dof
+        rhs = np.zeros((n if min(grid) >= 2 and n < 2 ** 31 else 1) + m) if with_rhs else None
+        self._chk(fn(self.h, *grid, k.ctypes.data if k is not None else None, rhs.ctypes.data if with_rhs else None))
+        ctx, nl = C.c_void_p(), C.c_int32()
+        lib.SpkKSPGetContext(self.h, C.byref(ctx))
+        lib.spk_get_sizes(ctx, None, C.byref(nl), None, None, None)
+        self._n = nl.value + m
+        return rhs[:nl.value + m] if with_rhs else None
 
     def setGrid(self, mx, my, mz=1):
         """The node grid behind the operator of setOperators (SpkKSPSetGrid; the role of KSPSetDM): what -pc_type mg
