@@ -619,6 +619,15 @@ int spk_get_jacobi_diag(spk_ctx *ctx, double *dinv /* n_local */);
  * live on even / odd vector entries (x / y degrees of freedom of a dof-2 grid) and share a plane;
  * 0 when the fused path is not set up.  For byte models. */
 int spk_get_bd_planes(const spk_ctx *ctx, int32_t *planes);
+/* Which path the rows of the constraint block A10 take on this rank, as the last set_block left it (reads the context,
+ * launches nothing): *general = 1 for a block of more than 8 rows (short rows through the CSR stream kernel, its rows of
+ * more than 8192 local entries -- at most 8 -- through the column-window kernel), 0 for the few-rows path (every row
+ * through the window kernel); *m_wide = rows the window kernel takes and wide_rows[0 .. *m_wide) their row numbers,
+ * ascending; *win, *nwin = width and count of the column windows (nwin = 0 without a window row); *bc_tiles, *bt_tiles =
+ * workgroups of the stream kernel over the block by rows and over B^T (0 where that form is not tiled).  Any pointer may
+ * be NULL.  For tests. */
+int spk_get_constraint_layout(const spk_ctx *ctx, int32_t *general, int32_t *m_wide, int32_t wide_rows[8], int32_t *win,
+                              int32_t *nwin, int32_t *bc_tiles, int32_t *bt_tiles);
 
 /* ---- the three plug points ------------------------------------------------ */
 /* MATSHELL:  y = K x.   PCSHELL: y = M^-1 x.   Lengths n_local + m. */

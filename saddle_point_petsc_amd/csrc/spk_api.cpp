@@ -551,6 +551,21 @@ int spk_get_bd_planes(const spk_ctx *c, int32_t *planes)
     return SPK_OK;
 }
 
+int spk_get_constraint_layout(const spk_ctx *c, int32_t *general, int32_t *m_wide, int32_t wide_rows[8], int32_t *win,
+                              int32_t *nwin, int32_t *bc_tiles, int32_t *bt_tiles)
+{
+    if (!c) return SPK_ERR_ARG;
+    if (general) *general = c->b_general ? 1 : 0;
+    if (m_wide) *m_wide = c->m_wide;
+    if (wide_rows)
+        for (int r = 0; r < 8; ++r) wide_rows[r] = r < (int)c->wide_rows_h.size() ? c->wide_rows_h[(size_t)r] : -1;
+    if (win) *win = c->B.win;
+    if (nwin) *nwin = c->B.nwin;
+    if (bc_tiles) *bc_tiles = c->Bc.ntiles;
+    if (bt_tiles) *bt_tiles = c->Bt.ntiles;
+    return SPK_OK;
+}
+
 int spk_get_sizes(const spk_ctx *c, int64_t *n_global, int32_t *n_local, int32_t *m, int64_t *nnz_local,
                   int32_t *n_ghost)
 {

@@ -612,6 +612,8 @@ static void b_release_general(spk_ctx *c)
     c->Bc.rowptr.release(); c->Bc.colidx.release(); c->Bc.val.release(); c->Bc.tile_row.release();
     c->Bc.nrows = c->Bc.ncols = c->Bc.ntiles = 0;
     c->Bc.nnz = 0;
+    c->Bt.tile_row.release();   // (B^T is tiled for a general block only: upload_csr builds the table again then)
+    c->Bt.ntiles = 0;
 }
 
 // One source of the block: the caller's arrays, localised, windowed and transposed on the host and uploaded

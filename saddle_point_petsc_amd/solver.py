@@ -827,6 +827,17 @@ class Context:
         self._chk(lib.spk_get_bd_planes(self.h, C.byref(v)))
         return v.value
 
+    def constraint_layout(self):
+        """Which path the rows of A10 take on this rank (spk_get_constraint_layout; reads the context, launches nothing):
+        general (more than 8 rows: stream kernel + window kernel), m_wide and wide_rows (the rows the window kernel takes,
+        ascending), win / nwin (the column windows), bc_tiles / bt_tiles (stream-kernel workgroups over B by rows / B^T)."""
+        g, mw, win, nwin, bc, bt = (C.c_int32() for _ in range(6))
+        rows = (C.c_int32 * 8)()
+        self._chk(lib.spk_get_constraint_layout(self.h, C.byref(g), C.byref(mw), rows, C.byref(win), C.byref(nwin), C.byref(bc),
+                                                C.byref(bt)))
+        return dict(general=bool(g.value), m_wide=mw.value, wide_rows=[int(r) for r in rows[:mw.value]], win=win.value,
+                    nwin=nwin.value, bc_tiles=bc.value, bt_tiles=bt.value)
+
     def jacobi_diag(self):
         out = np.zeros(self.sizes()["n_local"])
         self._chk(lib.spk_get_jacobi_diag(self.h, out))

@@ -126,17 +126,19 @@ def cb_fgmres_ref(K, M, b, restart=30, max_it=10000, rtol=1e-5, abstol=1e-50, dt
                    cycle_its=cycle_its)
 
 
-def fgmres_textbook(K, M, b, restart=30, max_it=10000, rtol=1e-5):
+def fgmres_textbook(K, M, b, restart=30, max_it=10000, rtol=1e-5, reverse=False):
     """Right-preconditioned flexible GMRES with modified Gram-Schmidt on a normalised FP64 basis (Saad, Alg. 9.6), the
-    convergence test on the recurrence residual against rtol ||b|| (zero initial guess)."""
+    convergence test on the recurrence residual against rtol ||b|| (zero initial guess).  reverse=True sums every dot
+    product and norm over the reversed vectors, as in cb_fgmres_ref."""
+    nrm = lambda v: np.sqrt(_dot(v, v, reverse))
     b = np.asarray(b, np.float64)
     x = np.zeros_like(b)
     its = 0
-    ttol = rtol * np.linalg.norm(b)
-    hist = [np.linalg.norm(b)]
+    ttol = rtol * nrm(b)
+    hist = [nrm(b)]
     while True:
         r = b - K(x)
-        beta = np.linalg.norm(r)
+        beta = nrm(r)
         if beta <= ttol or its >= max_it:
             return x, dict(its=its, reason=RTOL if beta <= ttol else ITS, rnorm=beta, history=np.array(hist))
         V, Z = [r / beta], []
@@ -148,9 +150,9 @@ def fgmres_textbook(K, M, b, restart=30, max_it=10000, rtol=1e-5):
             Z.append(M(V[j]))
             w = K(Z[j])
             for i in range(j + 1):
-                H[i, j] = np.dot(V[i], w)
+                H[i, j] = _dot(V[i], w, reverse)
                 w -= H[i, j] * V[i]
-            H[j + 1, j] = np.linalg.norm(w)
+            H[j + 1, j] = nrm(w)
             its += 1
             k = j + 1
             y, *_ = np.linalg.lstsq(H[:k + 1, :k], e1[:k + 1], rcond=None)
@@ -163,4 +165,4 @@ def fgmres_textbook(K, M, b, restart=30, max_it=10000, rtol=1e-5):
             x += y[i] * Z[i]
         if its >= max_it:
             r = b - K(x)
-            return x, dict(its=its, reason=ITS, rnorm=np.linalg.norm(r), history=np.array(hist))
+            return x, dict(its=its, reason=ITS, rnorm=nrm(r), history=np.array(hist))

@@ -408,6 +408,20 @@ static void test_wide_rows()
     CHECK((wide_rows(12, rp.data(), 4) == ivec{0, 2, 3, 5, 6, 7, 10, 11}));
     CHECK((wide_rows(12, rp.data(), 9) == ivec{7, 10, 11}));
     CHECK(wide_rows(12, rp.data(), 12).empty());
+    // the set-up's own threshold (8192, strict): 8193 is wide, 8192 is not; twelve rows above it, ten of them 8200..8209
+    // entries with rows 7 and 12 equal at the eighth place -- the lower row goes wide, rows 12 and the shortest (5) stay,
+    // and so do the two 8193-entry rows 0 and 15, which are shorter than all ten
+    const int big[16] = {8193, 8192, 1, 8209, 8208, 8200, 8207, 8202, 2046, 8206, 8205, 8204, 8202, 8203, 2, 8193};
+    rp.assign(17, 0);
+    for (int r = 0; r < 16; ++r) rp[(size_t)r + 1] = rp[(size_t)r] + big[r];
+    CHECK((wide_rows(16, rp.data(), 8192) == ivec{3, 4, 6, 7, 9, 10, 11, 13}));
+    CHECK((wide_rows(16, rp.data(), 8193) == ivec{3, 4, 6, 7, 9, 10, 11, 13}));
+    CHECK((wide_rows(16, rp.data(), 8202) == ivec{3, 4, 6, 9, 10, 11, 13}));   // strict: the two of 8202 are not above it
+    // no more than eight above the threshold: all of them, the first and the last row included
+    const int few[11] = {8193, 8192, 5, 8192, 9000, 1, 8191, 2048, 3, 0, 8193};
+    rp.assign(12, 0);
+    for (int r = 0; r < 11; ++r) rp[(size_t)r + 1] = rp[(size_t)r] + few[r];
+    CHECK((wide_rows(11, rp.data(), 8192) == ivec{0, 4, 10}));
 }
 
 static void test_windows()
